@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: OSVOS-VGG one-shot online fine-tune throughput in 854x480 frames/s.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it builds the model, warms up (N = 1: behind the untimed pass of the
+`cold` object, as the headline always was), times the K steps, writes the outputs of the last timed step if
+--dump-outputs is given (see dump_outputs) and prints the JSON line.  Everything else this file measures - the extra
+objects listed below, and for N > 1 the dp_strict and replicas mappings - runs with --full only.
 
 N > 1 works both ways: under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (the ranks
 come from the environment) and as a plain ``python bench.py --gpus N``, which then starts N fresh child processes of
@@ -12,7 +17,8 @@ One "step" = one iteration of the reference's online loop body (src/train_online
 backward -> fused SGD step + zero_grad every 5th iteration.  It runs through the drop-in ``train_online._train`` with
 the drop-in ``OSVOS_VGG`` module, i.e. the shipped path (native layer loop, two-stream backward, deferred wgrad join).
 
-N > 1, one process per GPU over RCCL.  Three mappings of BASELINE.json configs[3] are timed in the same run:
+N > 1, one process per GPU over RCCL.  Three mappings of BASELINE.json configs[3] (a plain run: dp only; --full: all three,
+unless --mode picks one) are timed in the same run:
   dp        (``value``) every rank runs the same K steps on its own frames and the flat fp32 gradient buffer is
             SUM-all-reduced (bucketed, overlapped with the backward pass) before each optimizer step: weak scaling,
             5 local micro-batches per rank and step
@@ -25,7 +31,7 @@ N > 1, one process per GPU over RCCL.  Three mappings of BASELINE.json configs[3
 The line carries ``backend``, ``ranks`` and ``distinct_devices``; ``n_gpus`` is the number of DISTINCT devices, and
 the nccl backend is refused when two ranks share one (a gloo rehearsal of two ranks on one GPU reads n_gpus 1).
 
-Extra objects on the one JSON line rank 0 prints (N = 1):
+Extra objects on the one JSON line rank 0 prints with --full (N = 1):
   cold            the same K steps behind the W warm-up steps only (no preconditioning): what a short window measures on a
                   device that is still raising its clocks; timed FIRST, right after the model is built
   group1          one frame per pass (FOSVOS_MICROBATCH_GROUP=1: the reference's one-by-one order, and what a cycle of five
@@ -61,6 +67,7 @@ AVG_GRAD_EVERY_N = 5
 # untimed steps of the same loop in front of the W warm-up steps: ~60 ms of load, so that the timed window does not start on a
 # device that is still raising its clocks after the idle start-up of the process (FOSVOS_BENCH_PRECONDITION=0 turns it off)
 PRECONDITION_STEPS = int(os.environ.get("FOSVOS_BENCH_PRECONDITION", "70"))
+HEAD_SCALE = 0.02  # factor on the seeded fuse weights of the online workload (make_provider)
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md
 # the MFMA kernels the roofline object is about (forward: persistent k_conv3x3_pp or k_conv3x3_igemm; data gradient:
 # k_conv3x3_igemm; weight gradient: k_wgrad3x3_v2, k_wgrad_first)
@@ -72,9 +79,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--mode", choices=["both", "dp", "dp_strict", "replicas"], default="both",
-                    help="N > 1: which mapping(s) to time (both = dp, dp_strict and replicas); `value` is dp unless only "
-                         "another one is asked for")
+    ap.add_argument("--mode", choices=["both", "dp", "dp_strict", "replicas"], default=None,
+                    help="N > 1: which mapping(s) to time (both = dp, dp_strict and replicas; default dp, with --full both); "
+                         "`value` is dp unless only another one is asked for")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the variant objects, roofline, infer, cpu_baseline "
+                         "and (N > 1) the dp_strict and replicas mappings")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-variants", action="store_true", help="skip the cold / group1 / mixed_scales / offline objects")
     ap.add_argument("--no-alone", action="store_true",
                     help="skip roofline.alone (the conv kernels one at a time): its launches would sit in a rocprofv3 summary "
@@ -249,6 +261,38 @@ def offline_config(args, dev, make_frame, barrier):
                         f"(BASELINE.json configs[2]); one iteration is one step"}
 
 
+DUMP_SAMPLE = 1 << 18  # elements per dumped tensor; a larger tensor is written as a fixed, seeded sample of this many
+
+
+def dump_outputs(path, net, opt, losses):
+    """--dump-outputs: what the timed `_train` call leaves its caller after its last step, as .npy files under `path`: every
+    parameter of the network (param.<name>) and the optimizer's momentum buffer of it (momentum.<name>) in fp32, and the
+    loss log the call returned (loss, fp64).  A tensor of more than DUMP_SAMPLE elements is written as its elements at
+    DUMP_SAMPLE positions drawn without replacement by a generator seeded with its size, in ascending order - the same
+    positions in every run and build.  About 25 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+
+    def save(name, t):
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(n).choice(n, DUMP_SAMPLE, replace=False))
+                picks[n] = torch.from_numpy(idx).to(t.device)
+            t = t.reshape(-1)[picks[n]]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+    for name, p in net.named_parameters():
+        save("param." + name, p)
+        buf = opt.state.get(p, {}).get("momentum_buffer")
+        if buf is not None:
+            save("momentum." + name, buf)
+    np.save(os.path.join(path, "loss.npy"), np.asarray(losses or [], dtype=np.float64))
+
+
 def _with_steps(args, steps, warmup, fn):
     saved = args.steps, args.warmup
     args.steps, args.warmup = steps, warmup
@@ -354,9 +398,11 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus}, or run "
                          f"`python bench.py --gpus {args.gpus}` outside torchrun and let it start its own ranks")
 
+    # the variant objects (cold, steps100, power, group1, mixed_scales, davis_tree, offline): --full, one process
+    variants = args.full and world == 1 and not args.no_variants
     only_early = os.environ.get("FOSVOS_BENCH_ONLY")
     power_sampler = None
-    if world == 1 and not args.no_variants and (only_early is None or "power" in only_early.split(",")):
+    if variants and (only_early is None or "power" in only_early.split(",")):
         power_sampler = _start_power_sampler()
         import atexit
         atexit.register(_stop_power_sampler, power_sampler)
@@ -414,6 +460,11 @@ def main():
                     p.normal_(0, (2.0 / fan_in) ** 0.5 if name.startswith("stages") else (1.0 / fan_in) ** 0.5)
                 else:
                     p.normal_(0, 0.1)
+            # the fuse head scaled down as in the parent net of the fine-tune fixtures (oracle/osvos_ref.py TRAJ_FULL): the
+            # logits start O(1) and the reference's recipe (lr 1e-8 on the loss summed over 409,920 pixels) trains smoothly
+            # for thousands of steps; with the head at full scale the weights leave the fp32 range and the loss is NaN from
+            # the 16th step on
+            net.fuse.weight.mul_(HEAD_SCALE)
         prov = VGGOnlineProvider.__new__(VGGOnlineProvider)
         prov.network = net.to(dev)
         prov.name = "vgg16"
@@ -469,6 +520,7 @@ def main():
                 else:
                     os.environ[k] = v
         host_lead[mode] = ret.get("seconds_host_enqueue")
+        loss_log[mode] = ret.get("loss")
         comm_timing[mode] = ret.get("comm_timing")
         if world > 1:
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -480,18 +532,25 @@ def main():
     comm_timing = {}  # per data-parallel mode: parallel.GradSync.timing_summary() of the timed steps
     parallel.COMM_TIMING = world > 1
     host_lead = {}  # per mode: seconds the host loop needed to ENQUEUE the timed steps (the device finishes later)
-    modes = ["single"] if world == 1 else (["dp", "dp_strict", "replicas"] if args.mode == "both" else [args.mode])
+    loss_log = {}  # per mode: the loss log the timed call returned
+    mode = args.mode or ("both" if args.full else "dp")
+    modes = ["single"] if world == 1 else (["dp", "dp_strict", "replicas"] if mode == "both" else [mode])
     results = {}
     cold = None
     only = os.environ.get("FOSVOS_BENCH_ONLY")  # lab: comma-separated subset of cold,group1,mixed_scales,offline
     want = (lambda name: only is None or name in only.split(","))
     if world == 1 and not args.no_variants and want("cold"):
-        # FIRST, on the device as the start-up of the process left it: W warm-up steps, K timed steps, no preconditioning
+        # FIRST, on the device as the start-up of the process left it: W warm-up steps, K timed steps, no preconditioning.
+        # A plain run makes this pass too, as warm-up: the headline has always been timed behind it, and without it the
+        # headline step measured about 1 % longer on the same box; only --full reports it (`cold`)
         cold = timed("cold", precondition=0)[0]
     for m in modes:
         results[m] = timed(m)
     head = modes[0]
     elapsed, prov, opt, run = results[head]
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on this model (the roofline pass of --full trains it further)
+        dump_outputs(args.dump_outputs, prov.network, opt, loss_log[head])
 
     def parallelism(m):
         if m == "single":
@@ -551,10 +610,10 @@ def main():
                                 "unit": "frames/s",
                                 "note": "replicas = the reference's own multi-device mapping (independent sequences, results "
                                         "identical to one GPU); dp = weak scaling with 5 micro-batches per rank and step"}
-    if cold is not None:
+    if cold is not None and variants:
         out["cold"] = {"value": args.steps / cold, "unit": "frames/s", "ms_per_step": cold / args.steps * 1000.0,
                        "note": f"the same {args.steps} steps behind {args.warmup} warm-up steps only, timed first (no preconditioning)"}
-    if world == 1 and not args.no_variants and want("steps100") and args.steps != 100:
+    if variants and want("steps100") and args.steps != 100:
         # this file's default window (100 steps, 20 warm-up) beside the driver's --steps 20 --warmup 5: the same loop, the
         # per-call costs of a short window (0.25 ms of host set-up and tail) amortised
         saved_steps, saved_warm = args.steps, args.warmup
@@ -564,7 +623,7 @@ def main():
         finally:
             args.steps, args.warmup = saved_steps, saved_warm
         out["steps100"] = {"value": 100 / e, "unit": "frames/s", "ms_per_step": e / 100 * 1000.0, "steps": 100, "warmup": 20}
-    if world == 1 and not args.no_variants and want("power"):
+    if variants and want("power"):
         # What the card reports while the step runs for a few seconds (amd-smi, read-only, four times a second from a child
         # process; none of it inside the headline's timed region): socket power against its limit and the GFX clocks.
         # Context (profiles/r04_lab_power_clocks.txt): the forward / data-gradient kernels ALONE sit at the 1400 W limit
@@ -580,7 +639,7 @@ def main():
             power = _power_summary(power_sampler, t_end - e, t_end, n_power, e)
             if power is not None:
                 out["power"] = power
-    if world == 1 and not args.no_variants and want("group1"):
+    if variants and want("group1"):
         # one frame per pass: the reference's own order, and the worst case of the shape bucketing
         e = timed("group1", env={"FOSVOS_MICROBATCH_GROUP": "1"})[0]
         probe = {role: _engine.STREAM_PROBE.get((dev_index, role)) for role in ("aux", "pass")}
@@ -591,7 +650,7 @@ def main():
                          "pass_streams_overlap": (probe["pass"] or {}).get("overlaps_with"),
                          "aux_stream_overlap": (probe["aux"] or {}).get("overlaps_with"),
                          "stream_probe": probe}
-    if world == 1 and not args.no_variants and want("mixed_scales"):
+    if variants and want("mixed_scales"):
         # the reference's augmentation: a random scale per iteration, fixed seed; 20 frames per epoch
         import random
         rng = random.Random(1234)
@@ -624,7 +683,7 @@ def main():
                                "note": "frames drawn from {1.0, 0.8, 0.5} x 480x854 (seed 1234, 20 per epoch), bucketed by "
                                        "shape inside each accumulation cycle of 5 (src/dataloaders/custom_transforms.py:63-76)"}
         del mixed
-    if world == 1 and not args.no_variants and want("davis_tree"):
+    if variants and want("davis_tree"):
         # The training half of train_and_test on a DAVIS-shaped tree ON DISK (one sequence, 480x854 JPEG + PNG mask written
         # here): the loader the script itself builds - io_helper.get_data_loader_train(root, 1, seq) - feeds _train, so the
         # rate INCLUDES the loader: the one-shot sample's six flip / scale variants resident on the device, drawn per epoch
@@ -672,10 +731,10 @@ def main():
                                      "DAVIS tree on disk (src/util/io_helper.py:62-70, src/dataloaders/davis_2016.py:72-83)"}
         import shutil
         shutil.rmtree(root, ignore_errors=True)
-    if world == 1 and not args.no_variants and want("offline"):
+    if variants and want("offline"):
         out["offline"] = offline_config(args, dev, make_frame, barrier)
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # rank-0-only pass, so no collective: the single-process loop (what every replica runs; the dp loop differs only by
         # the all-reduce).  Same shipped execution as the timed region - native layer loop, two streams, deferred join -
         # with the library's event pair around every launch on its own stream.
@@ -771,7 +830,7 @@ def main():
         }
         if not args.no_alone:
             out["roofline"]["alone"] = alone_rates(dev, AVG_GRAD_EVERY_N, H, W)
-    if rank == 0 and not args.no_infer:
+    if rank == 0 and args.full and not args.no_infer:
         # f1: the reference's eval_speeds protocol on 480x854 frames, all five logit maps computed
         from util import experiment_helper, io_helper
         # frames materialised up front: generating a synthetic frame on the host takes ~10 ms, long enough for the idle GPU
@@ -791,7 +850,7 @@ def main():
                                     f"frame of each pass dropped ({len(ev['times'])} samples; host-to-device copy of the "
                                     f"frame outside the bracket), src/util/experiment_helper.py:29-53",
                         "reference_published_s_per_frame": 0.08083}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_iters)
     if world > 1:
         dist.barrier()

@@ -2,7 +2,8 @@
 ``train_offline._train`` - in data-parallel mode and compare the weights they leave with the same function run in one
 process on the whole work.  The HIP network and loss need a GPU, so both are replaced by CPU stand-ins with the same
 surface: a small torch module with OSVOS_VGG's attribute names (so the gradient buckets of ``parallel.VGG_BUCKETS`` apply
-as they do to the real net) and the oracle's class-balanced loss.  What is under test is the wiring: FlatGrads views and
+as they do to the real net) and the oracle's class-balanced loss; the minibatches stay on the CPU with it, whether or not
+the machine has a GPU.  What is under test is the wiring: FlatGrads views and
 buckets, the accumulation split (online) / batch split with global class counts (offline), the bucketed asynchronous
 all-reduce and where it is joined, the optimizer step on the reduced buffer."""
 import os
@@ -10,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import pytest
 import torch
 import torch.distributed as dist
 from torch import nn
@@ -17,6 +19,18 @@ from torch import nn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "fosvos_amd"))
+
+
+def _inputs_on_the_cpu(net, verbose=False):
+    """Stand-in for gpu_handler.cast_cuda_if_possible: the loops move every minibatch to the GPU when one is visible, but
+    the stand-in network is a CPU module, so its inputs stay on the CPU."""
+    return net
+
+
+@pytest.fixture(autouse=True)
+def _cpu_minibatches(monkeypatch):
+    from util import gpu_handler
+    monkeypatch.setattr(gpu_handler, "cast_cuda_if_possible", _inputs_on_the_cpu)
 
 
 def _free_port():
@@ -119,6 +133,8 @@ def _worker(rank, world, port, mode, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     import parallel
+    from util import gpu_handler
+    gpu_handler.cast_cuda_if_possible = _inputs_on_the_cpu  # (a process of its own: nothing to restore)
     assert parallel.init_distributed("gloo")
     if mode == "online":     # accumulation split: rank r runs micro-batches r, r + world, ... of every cycle
         net = _run_online(_frames(8)[rank::world], 4, True)

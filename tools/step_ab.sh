@@ -13,7 +13,7 @@ for r in $(seq 1 $ROUNDS); do
     cp $lib $L
     envs=$(echo "$rest" | tr ',' ' ')
     [ "$envs" == "-" ] && envs="FOO=1"
-    env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --no-infer --no-variants > $OUT/${name}_$r.json 2>/dev/null
+    env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-infer --no-variants > $OUT/${name}_$r.json 2>/dev/null
     python - <<PY
 import json
 d=json.load(open("$OUT/${name}_$r.json"))
