@@ -123,6 +123,40 @@ extern "C" size_t fosvos_vgg_arena_bytes(int N, int H, int W) {
     return make_arena(N, H, W).total;
 }
 
+extern "C" int fosvos_vgg_arena_layout(int N, int H, int W, fosvos_vgg_arena_layout_info *out) {
+    FOSVOS_REQUIRE(out, FOSVOS_E_ARG, "vgg_arena_layout: null output");
+    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0, FOSVOS_E_SHAPE, "vgg_arena_layout: bad shape N=%d H=%d W=%d", N, H, W);
+    const Arena a = make_arena(N, H, W);
+    *out = fosvos_vgg_arena_layout_info{};
+    out->total = a.total;
+    for (int s = 0; s < 5; ++s) { out->stage_h[s] = a.sh[s]; out->stage_w[s] = a.sw[s]; }
+    for (int c = 0; c < kNConv; ++c) {
+        const int s = kStageOf[c];
+        out->act[c] = a.act[c];
+        out->gact[c] = a.gact[c];
+        out->act_bytes[c] = (size_t)N * a.sh[s] * a.sw[s] * kCout[c] * 2;
+        out->wsa_conv[c] = a.wsa_conv[c];
+        out->wsa_conv_bytes[c] = a.wsa_conv_bytes[c];
+    }
+    for (int s = 1; s < 5; ++s) {
+        const size_t px = (size_t)N * a.sh[s] * a.sw[s];
+        out->pooled[s - 1] = a.pooled[s - 1];
+        out->gpooled[s - 1] = a.gpooled[s - 1];
+        out->pooled_bytes[s - 1] = px * kStageCh[s - 1] * 2;
+        out->side[s - 1] = a.side[s - 1];
+        out->side_bytes[s - 1] = px * 16 * 4;
+        out->dside[s - 1] = a.dside[s - 1];
+        out->dside_bytes[s - 1] = px * 32 * 2;
+        out->wsa_side[s - 1] = a.wsa_side[s - 1];
+        out->wsa_side_bytes[s - 1] = a.wsa_side_bytes[s - 1];
+    }
+    out->bits0 = a.bits0;
+    out->bits0_bytes = (size_t)N * H * W * (kCout[0] / 8);
+    out->ws = a.ws; out->ws_bytes = a.ws_bytes;
+    out->hws = a.hws; out->hws_bytes = a.hws_bytes;
+    return FOSVOS_OK;
+}
+
 // aux_stream (optional): the four side_prep convs (16 output channels: memory-bound, 120 us per five 480x854 frames) run on
 // it, beside the backbone's MFMA-bound convs of the NEXT stage, instead of between them; `stream` waits for them in front of
 // the head.  The caller sees single-stream semantics on `stream`.

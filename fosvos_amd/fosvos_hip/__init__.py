@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -49,6 +49,21 @@ class VggGrads(ctypes.Structure):
     _fields_ = [("conv_w", _P13), ("conv_b", _P13), ("side_w", _P4), ("side_b", _P4),
                 ("dsn_w", c_void_p), ("dsn_b", c_void_p), ("fuse_w", c_void_p), ("fuse_b", c_void_p),
                 ("accumulate", c_int), ("defer_join", c_int), ("bucket_events", c_int), ("last_pass_of_cycle", c_int)]
+
+_Z4 = c_size_t * 4
+_Z13 = c_size_t * 13
+
+
+class VggArenaLayout(ctypes.Structure):
+    """fosvos_vgg_arena_layout_info: byte offsets (from the aligned arena base) and sizes of every tensor of the native pass."""
+    _fields_ = [("total", c_size_t), ("stage_h", c_int * 5), ("stage_w", c_int * 5),
+                ("act", _Z13), ("gact", _Z13), ("act_bytes", _Z13),
+                ("pooled", _Z4), ("gpooled", _Z4), ("pooled_bytes", _Z4),
+                ("side", _Z4), ("side_bytes", _Z4), ("dside", _Z4), ("dside_bytes", _Z4),
+                ("bits0", c_size_t), ("bits0_bytes", c_size_t),
+                ("ws", c_size_t), ("ws_bytes", c_size_t), ("hws", c_size_t), ("hws_bytes", c_size_t),
+                ("wsa_conv", _Z13), ("wsa_conv_bytes", _Z13), ("wsa_side", _Z4), ("wsa_side_bytes", _Z4)]
+
 
 class Conv3x3PlanInfo(ctypes.Structure):
     """fosvos_conv3x3_plan_info."""
@@ -177,6 +192,7 @@ SIGNATURES = {
     "fosvos_resnet_forward": (c_int, [POINTER(ResnetNet), c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                       POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p]),
     "fosvos_vgg_arena_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fosvos_vgg_arena_layout": (c_int, [c_int, c_int, c_int, POINTER(VggArenaLayout)]),
     "fosvos_vgg_grad_bucket_wait": (c_int, [c_void_p, c_int, c_void_p]),
     "fosvos_profile_start": (c_int, [c_int, c_int]),
     "fosvos_profile_stop": (c_int, [c_int, POINTER(ProfileRecord), c_int, POINTER(c_int)]),

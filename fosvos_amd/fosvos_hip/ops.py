@@ -248,6 +248,20 @@ def conv3x3_fwd_plan(n: int, h: int, w: int, in_ch: int, out_ch: int, relu: bool
             "persistent": bool(info.persistent)}
 
 
+def vgg_arena_layout(n: int, h: int, w: int) -> dict:
+    """fosvos_vgg_arena_layout as a dict (host arithmetic only): field name -> int, or list of ints for the per-layer arrays
+    (byte offsets from the aligned arena base, byte sizes, stage resolutions)."""
+    import ctypes
+    from . import VggArenaLayout
+    info = VggArenaLayout()
+    check(lib().fosvos_vgg_arena_layout(n, h, w, ctypes.byref(info)), "vgg_arena_layout")
+    out = {}
+    for name, _ in VggArenaLayout._fields_:
+        v = getattr(info, name)
+        out[name] = list(v) if isinstance(v, ctypes.Array) else int(v)
+    return out
+
+
 def conv3x3_first_plan(n: int, h: int, w: int) -> Tuple[int, int]:
     """(tiles, persistent workgroups) of fosvos_conv3x3_first_fwd."""
     import ctypes

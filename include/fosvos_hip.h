@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 17
+#define FOSVOS_ABI_VERSION 18
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -96,6 +96,25 @@ int fosvos_nhwc_bf16_to_nchw_f32(const uint16_t *src, float *dst, int N, int C, 
 /* fp32 NHWC <-> fp32 NCHW */
 int fosvos_nhwc_f32_to_nchw_f32(const float *src, float *dst, int N, int C, int H, int W, int device, void *stream);
 int fosvos_nchw_f32_to_nhwc_f32(const float *src, float *dst, int N, int C, int H, int W, int device, void *stream);
+/* Where fosvos_vgg_forward / _backward keep each tensor in their arena (test/debug plumbing: the layer-parity tests read
+ * every layer back).  Byte offsets from the (256-byte aligned) arena base and unpadded byte sizes, from the same host
+ * arithmetic the two calls use (no device call).  Regions: act[c] / gact[c] bf16 NHWC [N,h,w,Co_c] (conv c's output and the gradient wrt it),
+ * pooled[s] / gpooled[s] bf16 NHWC [N,h,w,C] (the input of stage s+1 and its gradient), side[i] fp32 NHWC [N,h,w,16],
+ * dside[i] bf16 NHWC [N,h,w,32] (channels 16..31 zero), bits0 [N,H,W,8] bytes (conv1_1's ReLU mask); then the op
+ * workspaces: ws (main stream split-K), hws (head backward), wsa_conv[c] / wsa_side[i] (weight-gradient slabs).
+ * stage_h / stage_w: the five stage resolutions.  The layout may change with any ABI version. */
+typedef struct fosvos_vgg_arena_layout_info {
+    size_t total; /* fosvos_vgg_arena_bytes */
+    int stage_h[5], stage_w[5];
+    size_t act[13], gact[13], act_bytes[13];
+    size_t pooled[4], gpooled[4], pooled_bytes[4];
+    size_t side[4], side_bytes[4];
+    size_t dside[4], dside_bytes[4];
+    size_t bits0, bits0_bytes;
+    size_t ws, ws_bytes, hws, hws_bytes;
+    size_t wsa_conv[13], wsa_conv_bytes[13], wsa_side[4], wsa_side_bytes[4];
+} fosvos_vgg_arena_layout_info;
+int fosvos_vgg_arena_layout(int N, int H, int W, fosvos_vgg_arena_layout_info *out);
 
 /* ---- weight packing ---------------------------------------------------------------------------
  * fp32 OIHW master -> the two bf16 images the MFMA kernels read.

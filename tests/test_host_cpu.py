@@ -65,6 +65,48 @@ def test_conv_plan_of_the_480p_step():
     assert (tiles.value, wgs.value) == (60 * 27, 1024)             # the persistent conv1_1 loop iterates at 480x854
 
 
+@pytest.mark.parametrize("h,w", [(480, 854), (384, 683), (240, 427), (33, 47), (1, 1)])
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 16])
+def test_vgg_arena_layout(n, h, w):
+    """fosvos_vgg_arena_layout (what the layer-parity tests read the native pass back through): every tensor region and
+    workspace is 256-byte aligned, inside fosvos_vgg_arena_bytes, disjoint from every other, and as large as its layout;
+    the stage resolutions are the ceil-halvings of the frame."""
+    import fosvos_hip
+    from fosvos_hip import ops
+    L = ops.vgg_arena_layout(n, h, w)
+    assert L["total"] == fosvos_hip.lib().fosvos_vgg_arena_bytes(n, h, w) > 0
+    sh, sw = [h], [w]
+    for _ in range(4):
+        sh.append((sh[-1] + 1) // 2)
+        sw.append((sw[-1] + 1) // 2)
+    assert L["stage_h"] == sh and L["stage_w"] == sw
+    stage_of = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4)
+    cout = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+    px = [n * sh[s] * sw[s] for s in range(5)]
+    regions = []  # (name, offset, bytes)
+    for c in range(13):
+        want = px[stage_of[c]] * cout[c] * 2
+        assert L["act_bytes"][c] == want, c
+        regions += [(f"act{c}", L["act"][c], want), (f"gact{c}", L["gact"][c], want)]
+        regions.append((f"wsa_conv{c}", L["wsa_conv"][c], L["wsa_conv_bytes"][c]))
+    for i in range(4):
+        s = i + 1
+        assert L["pooled_bytes"][i] == px[s] * (64, 128, 256, 512)[i] * 2
+        assert L["side_bytes"][i] == px[s] * 16 * 4 and L["dside_bytes"][i] == px[s] * 32 * 2
+        regions += [(f"pooled{i}", L["pooled"][i], L["pooled_bytes"][i]), (f"gpooled{i}", L["gpooled"][i], L["pooled_bytes"][i]),
+                    (f"side{i}", L["side"][i], L["side_bytes"][i]), (f"dside{i}", L["dside"][i], L["dside_bytes"][i]),
+                    (f"wsa_side{i}", L["wsa_side"][i], L["wsa_side_bytes"][i])]
+    assert L["bits0_bytes"] == px[0] * 8
+    regions += [("bits0", L["bits0"], L["bits0_bytes"]), ("ws", L["ws"], L["ws_bytes"]), ("hws", L["hws"], L["hws_bytes"])]
+    assert L["ws_bytes"] > 0 and L["hws_bytes"] > 0
+    regions.sort(key=lambda r: r[1])
+    for name, off, nb in regions:
+        assert off % 256 == 0, name
+        assert off + nb <= L["total"], name
+    for (a, oa, na), (b, ob, _) in zip(regions, regions[1:]):
+        assert oa + na <= ob, f"{a} [{oa}, {oa + na}) overlaps {b} at {ob}"
+
+
 def test_module_surface_matches_reference_contract():
     from networks.osvos_vgg import OSVOS_VGG
     from fosvos_hip import engine
