@@ -44,12 +44,45 @@ def _cubic_weights(frac: np.ndarray) -> np.ndarray:
     return np.stack([w0, w1, w2, w3], axis=-1).astype(np.float32)
 
 
-def _resize_axis_cubic(arr: np.ndarray, out_len: int, scale: float, axis: int) -> np.ndarray:
-    n = arr.shape[axis]
+def cubic_taps(n: int, out_len: int, scale: float):
+    """The 4 source indices (clipped: replicated border) [out_len, 4] int64 and float32 weights [out_len, 4] of every
+    output position along an axis of ``n`` samples."""
     pos = (np.arange(out_len, dtype=np.float64) + 0.5) / scale - 0.5
     base = np.floor(pos).astype(np.int64)
     w = _cubic_weights((pos - base).astype(np.float32))          # [out_len, 4]
     idx = np.clip(base[:, None] + np.arange(-1, 3)[None, :], 0, n - 1)  # replicate border
+    return idx, w
+
+
+def nearest_taps(n: int, out_len: int, scale: float) -> np.ndarray:
+    """cv2's INTER_NEAREST source index of every output position along an axis of ``n`` samples."""
+    return np.minimum(np.floor(np.arange(out_len) / scale).astype(np.int64), n - 1)
+
+
+def output_size(h: int, w: int, fx: float, fy: float):
+    """(rows, cols) of cv2.resize(fx=fx, fy=fy) on an h x w array."""
+    ow, oh = _round_half_even(w * fx), _round_half_even(h * fy)
+    if ow <= 0 or oh <= 0:
+        raise ValueError('resize: empty output')
+    return oh, ow
+
+
+def resize_plan(h: int, w: int, fx: float, fy: float) -> dict:
+    """Everything ``resize`` computes from the sizes alone, for a resampler that reads tables (fosvos_augment_sample):
+    ``oh``, ``ow`` and, unless the size is kept (``copy``: resize returns the array itself), the bicubic taps of the
+    frame's columns and rows (``col_taps`` / ``col_w`` [ow, 4], ``row_taps`` / ``row_w`` [oh, 4]) and the mask's
+    nearest source column / row (``col_near`` [ow], ``row_near`` [oh])."""
+    oh, ow = output_size(h, w, fx, fy)
+    plan = {'oh': oh, 'ow': ow, 'copy': ow == w and oh == h}
+    if not plan['copy']:
+        plan['col_taps'], plan['col_w'] = cubic_taps(w, ow, fx)
+        plan['row_taps'], plan['row_w'] = cubic_taps(h, oh, fy)
+        plan['col_near'], plan['row_near'] = nearest_taps(w, ow, fx), nearest_taps(h, oh, fy)
+    return plan
+
+
+def _resize_axis_cubic(arr: np.ndarray, out_len: int, scale: float, axis: int) -> np.ndarray:
+    idx, w = cubic_taps(arr.shape[axis], out_len, scale)
     a = np.moveaxis(arr, axis, 0).astype(np.float32)
     out = np.zeros((out_len,) + a.shape[1:], dtype=np.float32)
     for k in range(4):
@@ -60,14 +93,11 @@ def _resize_axis_cubic(arr: np.ndarray, out_len: int, scale: float, axis: int) -
 def resize(arr: np.ndarray, fx: float, fy: float) -> np.ndarray:
     """cv2.resize(arr, None, fx=fx, fy=fy, interpolation=INTER_NEAREST if arr.ndim == 2 else INTER_CUBIC)."""
     h, w = arr.shape[:2]
-    ow, oh = _round_half_even(w * fx), _round_half_even(h * fy)
-    if ow <= 0 or oh <= 0:
-        raise ValueError('resize: empty output')
+    oh, ow = output_size(h, w, fx, fy)
     if ow == w and oh == h:
         return arr.copy()
     if arr.ndim == 2:
-        ys = np.minimum(np.floor(np.arange(oh) / fy).astype(np.int64), h - 1)
-        xs = np.minimum(np.floor(np.arange(ow) / fx).astype(np.int64), w - 1)
+        ys, xs = nearest_taps(h, oh, fy), nearest_taps(w, ow, fx)
         return np.ascontiguousarray(arr[ys][:, xs])
     out = _resize_axis_cubic(arr, ow, fx, axis=1)   # horizontal pass first, as cv2 does
     out = _resize_axis_cubic(out, oh, fy, axis=0)

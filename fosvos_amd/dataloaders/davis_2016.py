@@ -103,6 +103,11 @@ class DAVIS2016(Dataset):
         return sample
 
     def make_img_gt_pair(self, idx):
+        return self.convert_raw(*self.read_raw(idx))
+
+    def read_raw(self, idx):
+        """The sample as decoded (and resized to ``inputRes``): uint8 H x W x 3 BGR frame, uint8 H x W mask or None where
+        the annotation is hidden.  ``convert_raw`` turns the pair into what ``make_img_gt_pair`` returns."""
         img = read_bgr(os.path.join(self.db_root_dir, self.img_list[idx]))
         label = None
         if self.labels[idx] is not None:
@@ -111,6 +116,9 @@ class DAVIS2016(Dataset):
             img = _imresize(img, self.inputRes)
             if label is not None:
                 label = _imresize(label, self.inputRes, nearest=True)
+        return img, label
+
+    def convert_raw(self, img, label):
         img = np.asarray(img, dtype=np.float32) - np.asarray(self.meanval, dtype=np.float32)
         if label is not None:
             gt = np.asarray(label, dtype=np.float32)

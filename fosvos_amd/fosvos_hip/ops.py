@@ -918,3 +918,56 @@ def deconv_head_fwd(side: Sequence[torch.Tensor], strides: Sequence[int], filt: 
           "deconv_head_fwd")
     _pe(t0, "deconv_head_fwd", 2.0 * n * H * W * 256, 4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_side_out else 1)))
     return fused, outs
+
+
+# ------------------------------------------------------------------------------------------ training-sample augmentation
+_AUG_TABLES = (("col_taps", torch.int32, 1), ("col_w", _F32, 1), ("row_taps", torch.int32, 0), ("row_w", _F32, 0),
+               ("col_near", torch.int32, 1), ("row_near", torch.int32, 0))
+
+
+def augment_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, img_lut: torch.Tensor, gt_lut: torch.Tensor,
+                   image: torch.Tensor, gt: torch.Tensor, tables: Optional[Sequence[torch.Tensor]] = None) -> None:
+    """fosvos_augment_sample: uint8 frame [H,W,3] and mask [H,W] -> image [1,3,OH,OW] / gt [1,1,OH,OW] (fp32, written in
+    place), mirrored first if ``flip``.  ``tables`` = (col_taps [OW,4] int32, col_w [OW,4] fp32, row_taps [OH,4] int32,
+    row_w [OH,4] fp32, col_near [OW] int32, row_near [OH] int32) from custom_transforms.resize_plan, or None for the
+    size-keeping copy.  img_lut fp32 [256,3], gt_lut fp32 [256]."""
+    _need(frame, torch.uint8, "augment_sample frame")
+    _need(mask, torch.uint8, "augment_sample mask")
+    _need(img_lut, _F32, "augment_sample img_lut")
+    _need(gt_lut, _F32, "augment_sample gt_lut")
+    _need(image, _F32, "augment_sample image")
+    _need(gt, _F32, "augment_sample gt")
+    if frame.dim() != 3 or frame.shape[2] != 3:
+        raise ValueError(f"augment_sample: frame must be [H,W,3], got {tuple(frame.shape)}")
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    if tuple(mask.shape) != (h, w):
+        raise ValueError(f"augment_sample: mask {tuple(mask.shape)} does not match the frame's {(h, w)}")
+    if tuple(img_lut.shape) != (256, 3) or tuple(gt_lut.shape) != (256,):
+        raise ValueError("augment_sample: img_lut must be [256,3] and gt_lut [256]")
+    if image.dim() != 4 or tuple(image.shape[:2]) != (1, 3):
+        raise ValueError(f"augment_sample: image must be [1,3,OH,OW], got {tuple(image.shape)}")
+    oh, ow = int(image.shape[2]), int(image.shape[3])
+    if tuple(gt.shape) != (1, 1, oh, ow):
+        raise ValueError(f"augment_sample: gt must be [1,1,{oh},{ow}], got {tuple(gt.shape)}")
+    ptrs = [None] * 6
+    if tables is not None:
+        if len(tables) != 6:
+            raise ValueError("augment_sample: six tables (col_taps, col_w, row_taps, row_w, col_near, row_near)")
+        for k, (t, (name, dtype, is_col)) in enumerate(zip(tables, _AUG_TABLES)):
+            _need(t, dtype, "augment_sample " + name)
+            n = ow if is_col else oh
+            want = (n, 4) if name.endswith(("taps", "_w")) else (n,)
+            if tuple(t.shape) != want:
+                raise ValueError(f"augment_sample: {name} must be {want}, got {tuple(t.shape)}")
+            ptrs[k] = t.data_ptr()
+    elif (oh, ow) != (h, w):
+        raise ValueError(f"augment_sample: without tables the size is kept ({h}x{w}), got {oh}x{ow}")
+    for t in (mask, img_lut, gt_lut, image, gt) + tuple(tables or ()):
+        if t.device != frame.device:
+            raise RuntimeError(f"augment_sample: every tensor must be on {frame.device}, got one on {t.device}")
+    dev, st = _ctx(frame)
+    e0 = _pb()
+    check(lib().fosvos_augment_sample(frame.data_ptr(), mask.data_ptr(), h, w, 1 if flip else 0, *ptrs, oh, ow,
+                                      img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(), dev, st),
+          "augment_sample")
+    _pe(e0, "augment_sample", 0.0, float(frame.numel() + mask.numel() + 4 * (image.numel() + gt.numel())))

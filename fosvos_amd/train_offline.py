@@ -26,6 +26,7 @@ save_dir_results = Path('results')
 db_root_dir = None
 synthetic_size = None
 data_parallel = False
+resident_train_set = False
 
 
 def train_and_test(net_provider: NetworkProvider, settings: OfflineSettings) -> None:
@@ -34,7 +35,8 @@ def train_and_test(net_provider: NetworkProvider, settings: OfflineSettings) -> 
         net_provider.load_network_train()
         shard = (parallel.rank(), parallel.world_size()) if data_parallel else None
         data_loader_train = io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train,
-                                                            synthetic=synthetic_size, shard=shard)
+                                                            synthetic=synthetic_size, shard=shard,
+                                                            resident_set=resident_train_set)
         data_loader_test = io_helper.get_data_loader_test(db_root_dir, settings.batch_size_test,
                                                           synthetic=synthetic_size)
         optimizer = net_provider.get_optimizer()
@@ -161,7 +163,7 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
 
 
 def main(argv=None):
-    global db_root_dir, synthetic_size, data_parallel
+    global db_root_dir, synthetic_size, data_parallel, resident_train_set
     args = args_helper.parse_args(is_online=False, argv=argv)
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')
@@ -169,6 +171,7 @@ def main(argv=None):
     gpu_handler.select_gpu(args.gpu_id)
     db_root_dir = P.db_root_dir()
     synthetic_size = (args.height, args.width) if args.synthetic else None
+    resident_train_set = bool(args.resident_train_set)
     save_dir_models.mkdir(parents=True, exist_ok=True)
     save_dir_results.mkdir(parents=True, exist_ok=True)
 

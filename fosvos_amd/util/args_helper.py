@@ -3,7 +3,7 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel.
+--data-parallel, --resident-train-set (offline only).
 """
 import argparse
 from typing import List, Optional
@@ -39,6 +39,10 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('-sg', '--sequence-group', default=None, type=int)
         parser.add_argument('-sgs', '--sequence-group-size', default=None, type=int)
         parser.add_argument('--variant-online', default=None, type=int, help='version to try')
+    if not is_online:
+        parser.add_argument('--resident-train-set', action='store_true',
+                            help='decode the training set once, keep it on the GPU and flip / rescale each draw there '
+                                 '(same samples as the per-iteration DataLoader under the same seed)')
     args = parser.parse_args(argv)
     args.is_training = not args.no_training
     args.is_testing = not args.no_testing

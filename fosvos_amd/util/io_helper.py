@@ -46,13 +46,18 @@ def write_settings(save_dir: Path, name: str, settings, variant_offline: Optiona
 
 def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] = None,
                           synthetic: Optional[Tuple[int, int]] = None,
-                          shard: Optional[Tuple[int, int]] = None, resident: bool = True) -> DataLoader:
+                          shard: Optional[Tuple[int, int]] = None, resident: bool = True,
+                          resident_set: bool = False) -> DataLoader:
     """shard = (rank, world): this process draws its own 1/world of every epoch (data-parallel OFFLINE training, where
     the ranks split each iteration's batch); None: the reference's single-process loader.
     resident: a sequence run (``seq_name``: ONE training sample, src/dataloaders/davis_2016.py:72-83) gets the loader that
     keeps the sample's six flip / scale variants on the device and draws them with the reference pipeline's random numbers
     (dataloaders/resident.py: same tensors, same order as the DataLoader below under the same torch seed); False: that
-    DataLoader itself (one worker start + decode + resample per iteration)."""
+    DataLoader itself (one worker start + decode + resample per iteration).
+    resident_set (opt-in): the whole training set (no ``seq_name``, no ``synthetic``) gets the loader that decodes every
+    sample once, keeps the uint8 frames and masks on the device and flips / rescales each draw there in one HIP launch
+    (dataloaders/resident.py: ResidentTrainSetLoader, same tensors in the same order as the DataLoader below under the
+    same torch seed, ``shard`` included).  It yields batches of one sample only and raises for any other batch_size."""
     if synthetic is not None:
         ds = SyntheticSequence(seq_name or 'synthetic', synthetic[0], synthetic[1], n_frames=1,
                                seed=1234 + (shard[0] if shard else 0))
@@ -63,6 +68,10 @@ def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] 
     if resident and seq_name is not None and shard is None and batch_size == 1:
         from dataloaders.resident import ResidentOneShotLoader
         return ResidentOneShotLoader(DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=None, seq_name=seq_name))
+    if resident_set and seq_name is None:
+        from dataloaders.resident import ResidentTrainSetLoader
+        return ResidentTrainSetLoader(DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=None),
+                                      shard=shard, batch_size=batch_size)
     db_train = DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=composed, seq_name=seq_name)
     if shard is not None:
         from torch.utils.data.distributed import DistributedSampler

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 18
+#define FOSVOS_ABI_VERSION 19
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -355,6 +355,26 @@ typedef struct fosvos_sgd_entry {
 } fosvos_sgd_entry;
 int fosvos_sgd_momentum_step(const fosvos_sgd_entry *table, int n_tensors, int64_t max_numel, float momentum,
                              int first_step, int device, void *stream);
+
+/* ---- training-sample augmentation (offline training set resident on the device) -------------------------------
+ * One training sample of DAVIS2016 -> the minibatch the reference's training loader yields for it (flip, then rescale:
+ * src/util/io_helper.py:62-70, src/dataloaders/custom_transforms.py:63-111), in one launch on `stream`.
+ *   frame     uint8 [H,W,3] (BGR, as decoded); mask uint8 [H,W]
+ *   flip      nonzero: mirror left-right before the rescale
+ *   col_taps / col_w  int32 / fp32 [OW][4]: clipped source columns and bicubic weights of each output column (16-byte
+ *             aligned); row_taps / row_w [OH][4]: the same for the rows; col_near [OW], row_near [OH]: the mask's
+ *             nearest-neighbour source column / row.  Indices refer to the (flipped) frame, as the host's resize computes
+ *             them.  All six NULL: a plain copy (scale 1; OH == H and OW == W).
+ *   img_lut   fp32 [256][3]: the image value of byte v in channel c (v - mean[c]); gt_lut fp32 [256]: the gt value of v
+ *   image     fp32 [3,OH,OW] out; gt fp32 [OH,OW] out
+ * Each output value is ((((0 + a0*w0) + a1*w1) + a2*w2) + a3*w3) in fp32 with every product rounded (no multiply-add
+ * contraction), horizontally first and then vertically over the fp32 horizontal results: the numpy restatement of
+ * cv2.resize in the training pipeline, bit for bit.  W <= 4096.
+ * replaces: the per-iteration DataLoader worker's transforms of src/util/io_helper.py:62-70. */
+int fosvos_augment_sample(const uint8_t *frame, const uint8_t *mask, int H, int W, int flip, const int32_t *col_taps,
+                          const float *col_w, const int32_t *row_taps, const float *row_w, const int32_t *col_near,
+                          const int32_t *row_near, int OH, int OW, const float *img_lut, const float *gt_lut, float *image,
+                          float *gt, int device, void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
