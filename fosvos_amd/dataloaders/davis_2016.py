@@ -48,6 +48,23 @@ def _imresize(arr: np.ndarray, size, nearest: bool = False) -> np.ndarray:
     return np.asarray(im.resize((cols, rows), resample=Image.NEAREST if nearest else Image.BILINEAR))
 
 
+class DavisAnnotations:
+    """``annotations(seq_name, fname)`` for the scored test pass: reads Annotations/480p/<seq>/<fname>.png itself
+    (``DAVIS2016(mode='test', seq_name=...)`` hides every annotation but the first) and returns uint8 [H,W], 1 where the
+    normalised value is >= 0.5 (the loss's rule), or None where the tree has no such file."""
+
+    def __init__(self, db_root_dir):
+        self.db_root_dir = str(db_root_dir)
+
+    def __call__(self, seq_name, fname):
+        path = os.path.join(self.db_root_dir, 'Annotations', '480p', seq_name, fname + '.png')
+        if not os.path.exists(path):
+            return None
+        gt = np.asarray(read_gray(path), dtype=np.float32)
+        gt = gt / np.float32(max(float(gt.max()), 1e-8))
+        return (gt >= 0.5).astype(np.uint8)
+
+
 class DAVIS2016(Dataset):
     """mode 'train' reads ImageSets/480p/train.txt, 'test' reads val.txt; with ``seq_name`` both read trainval.txt,
     keep that sequence only, hide every annotation except the first frame's, and 'train' keeps the first frame only

@@ -8,14 +8,18 @@ from torch.utils.data import Dataset
 MEANVAL = (104.00699, 116.66877, 122.67892)  # src/dataloaders/davis_2016.py:28
 
 
+def make_gt(h: int, w: int, index: int = 0):
+    yy = torch.arange(h, dtype=torch.float32).view(h, 1)
+    xx = torch.arange(w, dtype=torch.float32).view(1, w)
+    cy, cx = h * (0.45 + 0.02 * (index % 5)), w * (0.5 - 0.02 * (index % 7))
+    return ((((yy - cy) / (h * 0.2)) ** 2 + ((xx - cx) / (w * 0.16)) ** 2) <= 1.0).float().unsqueeze(0)
+
+
 def make_frame(h: int, w: int, seed: int = 1234, index: int = 0):
     g = torch.Generator(device='cpu')
     g.manual_seed(seed + 7919 * index)
     noise = torch.rand((3, h, w), generator=g)
-    yy = torch.arange(h, dtype=torch.float32).view(h, 1)
-    xx = torch.arange(w, dtype=torch.float32).view(1, w)
-    cy, cx = h * (0.45 + 0.02 * (index % 5)), w * (0.5 - 0.02 * (index % 7))
-    gt = ((((yy - cy) / (h * 0.2)) ** 2 + ((xx - cx) / (w * 0.16)) ** 2) <= 1.0).float().unsqueeze(0)
+    gt = make_gt(h, w, index)
     # brighter, lower-contrast object on a darker noisy background, then the dataset mean comes off
     img = gt * (150.0 + 100.0 * noise) + (1.0 - gt) * (150.0 * noise) - torch.tensor(MEANVAL).view(3, 1, 1)
     return img, gt
@@ -35,3 +39,11 @@ class SyntheticSequence(Dataset):
     def __getitem__(self, idx):
         img, gt = make_frame(self.h, self.w, self.seed, idx)
         return {'image': img, 'gt': gt, 'seq_name': self.seq_name, 'fname': '%05d' % idx}
+
+    def annotation(self, seq_name, fname):
+        """The ground truth of frame ``fname`` as the scorer takes it: uint8 [H,W], 1 = object; None for a frame this
+        sequence does not hold."""
+        idx = int(fname)
+        if seq_name != self.seq_name or not 0 <= idx < self.n:
+            return None
+        return (make_gt(self.h, self.w, idx)[0] >= 0.5).to(torch.uint8).numpy()

@@ -971,3 +971,82 @@ def augment_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, img_lut:
                                       img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(), dev, st),
           "augment_sample")
     _pe(e0, "augment_sample", 0.0, float(frame.numel() + mask.numel() + 4 * (image.numel() + gt.numel())))
+
+
+# ------------------------------------------------------------------------------------------ scoring (eval.hip)
+def _need_eval(t: torch.Tensor, dtype, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: tensor must live on the GPU (the HIP path has no CPU fallback)")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: tensor must be contiguous")
+    return t
+
+
+def _logit_shape(logits: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    if logits.dim() != 4 or logits.shape[1] != 1 or logits.numel() == 0:
+        raise ValueError(f"{what}: logits must be a non-empty [N,1,H,W], got {tuple(logits.shape)}")
+    return int(logits.shape[0]), int(logits.shape[2]), int(logits.shape[3])
+
+
+def prob_bytes(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_prob_bytes: logits fp32 [N,1,H,W] -> uint8 [N,H,W], per frame ``bytescale(sigmoid(logits))`` of
+    util/experiment_helper.py evaluated in fp64 (the bytes of the probability PNG).  Launched on the current stream, no
+    synchronisation."""
+    _need_eval(logits, _F32, "prob_bytes logits")
+    n, h, w = _logit_shape(logits, "prob_bytes")
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=logits.device)
+    else:
+        _need_eval(out, torch.uint8, "prob_bytes out")
+        if tuple(out.shape) != (n, h, w):
+            raise ValueError(f"prob_bytes: out must be {(n, h, w)}, got {tuple(out.shape)}")
+        if out.device != logits.device:
+            raise RuntimeError(f"prob_bytes: every tensor must be on {logits.device}, got one on {out.device}")
+    ws, _ = _WS.get(8 * n, logits.device)
+    dev, st = _ctx(logits)
+    e0 = _pb()
+    check(lib().fosvos_prob_bytes(logits.data_ptr(), n, h, w, ws, out.data_ptr(), dev, st), "prob_bytes")
+    _pe(e0, "prob_bytes", 0.0, 9.0 * n * h * w)
+    return out
+
+
+def jf_default_radius(h: int, w: int) -> int:
+    """ceil(0.008 * diagonal), the DAVIS boundary tolerance (util/davis_measures.default_radius)."""
+    import math
+    return int(math.ceil(0.008 * math.sqrt(h * h + w * w)))
+
+
+def jf_counts(logits: torch.Tensor, gt: torch.Tensor, radius: Optional[int] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_jf_counts: logits fp32 [N,1,H,W] and gt uint8 [N,H,W] (non-zero = object) -> int32 [N,6] per frame: inter,
+    union, n_pred_b, n_gt_b, match_pred, match_gt of the mask ``logits >= 0`` against ``gt`` (util/davis_measures.py states
+    the definitions).  ``radius`` (1..63) defaults to ceil(0.008 * diagonal).  ``out`` may be any [N,6] int32 rows, e.g. a
+    slice of a sequence's counter tensor; the op zeroes them itself.  Launched on the current stream, no synchronisation."""
+    _need_eval(logits, _F32, "jf_counts logits")
+    _need_eval(gt, torch.uint8, "jf_counts gt")
+    n, h, w = _logit_shape(logits, "jf_counts")
+    if tuple(gt.shape) != (n, h, w):
+        raise ValueError(f"jf_counts: gt must be {(n, h, w)}, got {tuple(gt.shape)}")
+    if radius is None:
+        radius = jf_default_radius(h, w)
+    radius = int(radius)
+    if not 1 <= radius <= 63:
+        raise ValueError(f"jf_counts: radius {radius} outside [1, 63]")
+    if out is None:
+        out = torch.empty((n, 6), dtype=torch.int32, device=logits.device)
+    else:
+        _need_eval(out, torch.int32, "jf_counts out")
+        if tuple(out.shape) != (n, 6):
+            raise ValueError(f"jf_counts: out must be {(n, 6)}, got {tuple(out.shape)}")
+    for t in (gt, out):
+        if t.device != logits.device:
+            raise RuntimeError(f"jf_counts: every tensor must be on {logits.device}, got one on {t.device}")
+    L = lib()
+    ws, wsn = _WS.get(L.fosvos_jf_workspace_bytes(n, h, w), logits.device)
+    dev, st = _ctx(logits)
+    e0 = _pb()
+    check(L.fosvos_jf_counts(logits.data_ptr(), gt.data_ptr(), n, h, w, radius, out.data_ptr(), ws, wsn, dev, st), "jf_counts")
+    _pe(e0, "jf_counts", 0.0, 5.0 * n * h * w)
+    return out

@@ -37,6 +37,8 @@ path_stem = 'vgg16/online'
 db_root_dir = None
 synthetic_size = None       # (H, W) when --synthetic
 data_parallel = False
+score = False               # --score: the test pass computes J and F on the device (experiment_helper.test_scored)
+scored_sequences = []       # the score of every sequence of this run, in order
 
 sequences_val = ['blackswan', 'bmx-trees', 'breakdance', 'camel', 'car-roundabout', 'car-shadow', 'cows',
                  'dance-twirl', 'dog', 'drift-chicane', 'drift-straight', 'goat', 'horsejump-high', 'kite-surf',
@@ -66,6 +68,15 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
         else:
             save_dir = (save_dir_results / net_provider.name / str(settings.variant_offline) /
                         str(settings.variant_online))
+        if score:
+            result = experiment_helper.test_scored(net_provider, data_loader, save_dir,
+                                                   io_helper.get_annotations(db_root_dir, data_loader, synthetic_size),
+                                                   seq_name=seq_name)
+            log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
+            (Path(save_dir) / seq_name).mkdir(parents=True, exist_ok=True)
+            experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
+            scored_sequences.append(result)
+            return
         experiment_helper.test(net_provider, data_loader, save_dir, settings.is_visualizing_results,
                                settings.eval_speeds, seq_name=seq_name)
 
@@ -482,8 +493,12 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 
 def main(argv=None):
-    global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results
+    global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score
     args = args_helper.parse_args(is_online=True, argv=argv)
+    if args.score and args.eval_speeds:
+        raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
+    score = bool(args.score)
+    del scored_sequences[:]
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')
     data_parallel = bool(args.data_parallel) and parallel.init_distributed()
@@ -527,6 +542,12 @@ def main(argv=None):
         [train_and_test(net_provider, s, settings) for s in sequences]
     else:
         train_and_test(net_provider, args.sequence_name, settings)
+    if score and scored_sequences:
+        n = len(scored_sequences)
+        j_mean = sum(r['J_stats']['mean'] for r in scored_sequences) / n
+        f_mean = sum(r['F_stats']['mean'] for r in scored_sequences) / n
+        log.info('Score over {0} sequences: J mean {1:.4f}, F mean {2:.4f}, J&F {3:.4f}'.format(
+            n, j_mean, f_mean, (j_mean + f_mean) / 2))
 
 
 if __name__ == '__main__':

@@ -9,7 +9,7 @@ import yaml
 from torch.utils.data import DataLoader
 
 from dataloaders import custom_transforms
-from dataloaders.davis_2016 import DAVIS2016
+from dataloaders.davis_2016 import DAVIS2016, DavisAnnotations
 from dataloaders.synthetic import SyntheticSequence
 from util.logger import get_logger
 
@@ -88,3 +88,11 @@ def get_data_loader_test(db_root_dir, batch_size: int, seq_name: Optional[str] =
     db_test = DAVIS2016(mode='test', db_root_dir=str(db_root_dir), transform=custom_transforms.ToTensor(),
                         seq_name=seq_name)
     return DataLoader(db_test, batch_size=batch_size, shuffle=False, num_workers=2)
+
+
+def get_annotations(db_root_dir, data_loader: DataLoader, synthetic: Optional[Tuple[int, int]] = None):
+    """The ground truth source of the scored test pass for a loader of ``get_data_loader_test``:
+    ``annotations(seq_name, fname)`` -> uint8 [H,W] or None."""
+    if synthetic is not None:
+        return data_loader.dataset.annotation
+    return DavisAnnotations(db_root_dir)

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 19
+#define FOSVOS_ABI_VERSION 20
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -375,6 +375,29 @@ int fosvos_augment_sample(const uint8_t *frame, const uint8_t *mask, int H, int 
                           const float *col_w, const int32_t *row_taps, const float *row_w, const int32_t *col_near,
                           const int32_t *row_near, int OH, int OW, const float *img_lut, const float *gt_lut, float *image,
                           float *gt, int device, void *stream);
+
+/* ---- scoring a segmented sequence (DAVIS 2016 J and F) and its PNG bytes ------------------------------------------
+ * The reference writes probability PNGs and leaves the measures to an outside toolkit (src/eval/README.md); these two
+ * ops keep both on the device beside the logits.  The definitions are stated in numpy in util/davis_measures.py.
+ *
+ * fosvos_prob_bytes: logits fp32 [N,1,H,W] -> out uint8 [N,H,W], per frame bytescale(sigmoid(logits)) of
+ * src/util/experiment_helper.py:57-64 evaluated in fp64: p = 1 / (1 + exp(-(double)x)), cmin / cmax = p at the frame's
+ * smallest / largest logit, cscale = cmax - cmin (1 if that is 0), byte = (uint8)(clip((p - cmin) * (255 / cscale), 0,
+ * 255) + 0.5).  minmax: fp32 [N,2] scratch of the caller (it holds each frame's {min, max} logit afterwards).  NaN-free
+ * logits only.  Three launches on `stream`: 4 B read twice and 1 B written per pixel.
+ * replaces: the host's sigmoid + scipy.misc.imsave stretch of src/util/experiment_helper.py:57-64. */
+int fosvos_prob_bytes(const float *logits, int N, int H, int W, float *minmax, uint8_t *out, int device, void *stream);
+/* fosvos_jf_counts: logits fp32 [N,1,H,W] and gt uint8 [N,H,W] (non-zero = object) -> counts int32 [N,6] per frame:
+ * {inter, union, n_pred_b, n_gt_b, match_pred, match_gt} for the predicted mask A = (logit >= 0) and the ground truth
+ * B = (gt != 0): |A and B|, |A or B|, |bmap(A)|, |bmap(B)|, |bmap(A) and dil(bmap(B), radius)|, |bmap(B) and
+ * dil(bmap(A), radius)|.  bmap(S) at (y,x): S differs from its right, lower or lower-right neighbour (last row: right
+ * only; last column: lower only; the corner: 0).  dil(M, r): M dilated by the disk dy*dy + dx*dx <= r*r, pixels outside
+ * the image count as 0.  1 <= radius <= 63.  The op zeroes the counters itself; what `counts` and the workspace
+ * (fosvos_jf_workspace_bytes, 8-byte aligned: two bit planes of [N][H][ceil(W/64)] 64-bit words) held before does not
+ * matter.  Integer sums only: the result does not depend on the order the workgroups finish in.  Two launches. */
+size_t fosvos_jf_workspace_bytes(int N, int H, int W);
+int fosvos_jf_counts(const float *logits, const uint8_t *gt, int N, int H, int W, int radius, int32_t *counts,
+                     void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
