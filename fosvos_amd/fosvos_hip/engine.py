@@ -14,13 +14,15 @@ parameter version.
 """
 from __future__ import annotations
 
+import ctypes
+import time
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
-
-import os
 
 import torch
 
-from . import ops
+from . import Context, VggGrads, VggWeights, check, lib, ops, ptr_array4
+from .options import EngineOptions, native_loop_from_env
 
 STAGE_CHANNELS = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
 STAGE_IN = (3, 64, 128, 256, 512)
@@ -50,11 +52,40 @@ PARAM_NAMES = param_names()
 PARAM_INDEX = {n: i for i, n in enumerate(PARAM_NAMES)}
 
 
+@dataclass(slots=True)
+class PassFlags:
+    """What a loop tells the next passes of one model (``PackedWeights.flags``; OSVOS_VGG exposes every field as an attribute
+    of the same name).  All off by default, so plain ``loss.backward(); opt.step()`` is safe.  A misspelt name raises."""
+
+    # True: the weight-gradient kernels of a backward pass may still be running on the auxiliary stream when ``backward()``
+    # returns; call ``join_gradients()`` before reading ``p.grad`` (optimizer step, all-reduce).  Clearing it through the
+    # module joins first.
+    defer_wgrad_join: bool = False
+    # True: a batched forward pass keeps both of its chains of frames on the caller's stream (the online loop sets it while
+    # the passes of a cycle alternate between two streams of their own - the auxiliary stream is then busy with the previous
+    # pass's weight gradients, and the second chain would queue behind them).
+    forward_one_stream: bool = False
+    # True: backward passes publish their gradients in completion order (stage 5, stage 4, stage 3, the rest) through
+    # ``wait_grad_bucket`` - what the data-parallel loops overlap their bucketed all-reduce with.
+    publish_grad_buckets: bool = False
+    # True: the next backward passes WRITE the parameter gradients they compute (all but score_dsn's, which only a loss on the
+    # side outputs produces - such a pass refuses the flag) instead of adding them to ``p.grad``: what an accumulation
+    # cycle's first pass may do when nothing else adds to the buffers beside it, so that the buffers need no zeroing between
+    # cycles.  The online loop sets it around a cycle that is one batched pass.
+    overwrite_grads: bool = False
+    # Hint for the next backward pass: no forward pass follows it before the optimizer step, so its trailing weight-gradient
+    # kernels may take the whole chip (the training loops set it around a cycle's last pass).
+    last_pass_of_cycle: bool = False
+
+
 class PackedWeights:
     """bf16 MFMA images of the 3x3 conv weights and the diagonal deconv filters, rebuilt only when
-    the fp32 master changed (tracked by tensor version + storage pointer)."""
+    the fp32 master changed (tracked by tensor version + storage pointer).  Also the per-model state of the passes: their
+    options (fixed when the model is built) and the flags a loop sets between passes."""
 
-    def __init__(self) -> None:
+    def __init__(self, options: Optional[EngineOptions] = None) -> None:
+        self.options = options if options is not None else EngineOptions.from_env()
+        self.flags = PassFlags()
         self._cache: Dict[str, Tuple[Tuple[int, int], object]] = {}
         self._uniform: Dict[str, bool] = {}  # deconv filter name -> its channel filters are identical (deconv_diag)
         self.arenas = ArenaPool()
@@ -123,9 +154,9 @@ class PackedWeights:
     def head_uniform_mask(self, P: Dict[str, torch.Tensor]) -> int:
         """Bit s: upscale[s]'s 16 channel filters are identical - interp_surgery's bilinear filters, which the optimizers
         never move (lr 0) - so the head kernels may contract the channels before the upsampling (fosvos_head_fwd's
-        ``filt_uniform``).  Checked on the weights themselves whenever they change; FOSVOS_HEAD_UNIFORM=0 switches the
-        fast path off (A/B)."""
-        if os.environ.get("FOSVOS_HEAD_UNIFORM", "1") == "0":
+        ``filt_uniform``).  Checked on the weights themselves whenever they change; EngineOptions.head_uniform = False
+        switches the fast path off (A/B)."""
+        if not self.options.head_uniform:
             return 0
         mask = 0
         for i in range(4):
@@ -156,14 +187,28 @@ class Saved:
                  "filt_uniform")
 
 
-def forward(P: Dict[str, torch.Tensor], packs: PackedWeights, x: torch.Tensor, with_side_out: bool = True,
-            keep: bool = True):
-    """Returns ([side_out x4 (or None), fused], Saved or None)."""
+def _check_frame(x: torch.Tensor) -> None:
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f"OSVOS_VGG expects [N,3,H,W] frames, got {tuple(x.shape)}")
     if not x.is_cuda:
         raise RuntimeError("the HIP OSVOS_VGG runs on the GPU only: move the module and the frame to cuda "
                            "(there is no CPU fallback)")
+
+
+def _side_grads(d_outs: Sequence[Optional[torch.Tensor]]) -> Tuple[List[Optional[torch.Tensor]], bool]:
+    """(the four side-output gradients, whether there are any): all four or none - missing ones become zeros."""
+    d_so = list(d_outs[:4])
+    have = [g is not None for g in d_so]
+    if any(have) and not all(have):
+        ref = next(g for g in d_so if g is not None)
+        d_so = [g if g is not None else torch.zeros_like(ref) for g in d_so]
+    return d_so, any(have)
+
+
+def forward(P: Dict[str, torch.Tensor], packs: PackedWeights, x: torch.Tensor, with_side_out: bool = True,
+            keep: bool = True):
+    """Returns ([side_out x4 (or None), fused], Saved or None)."""
+    _check_frame(x)
     x = x.contiguous().float()
     N, _, H, W = x.shape
     sv = Saved() if keep else None
@@ -241,12 +286,7 @@ def backward(P: Dict[str, torch.Tensor], packs: PackedWeights, sv: "Saved", d_ou
             grads[wn], grads[bn] = ops.conv3x3_wgrad(x, dy, ci, co)
 
     d_fused = d_outs[4]
-    d_so = d_outs[:4]
-    have_so = [g is not None for g in d_so]
-    if any(have_so) and not all(have_so):
-        ref = next(g for g in d_so if g is not None)
-        d_so = [g if g is not None else torch.zeros_like(ref) for g in d_so]
-    with_so = any(have_so)
+    d_so, with_so = _side_grads(d_outs)
     if d_fused is None and not with_so:
         return grads
     dsn_w = torch.stack([P[f"score_dsn.{i}.weight"].detach().reshape(16) for i in range(4)]).contiguous()
@@ -255,7 +295,7 @@ def backward(P: Dict[str, torch.Tensor], packs: PackedWeights, sv: "Saved", d_ou
         sv.side, sv.filt, sv.filt1 if with_so else None, dsn_w if with_so else None, fuse_w,
         d_fused.contiguous().float() if d_fused is not None else None,
         [g.contiguous().float() for g in d_so] if with_so else None, sv.H, sv.W,
-        filt_uniform=getattr(sv, "filt_uniform", 0))
+        filt_uniform=sv.filt_uniform)
     grads["fuse.weight"] = d_fuse_w.reshape(1, 64, 1, 1)
     grads["fuse.bias"] = d_fuse_b
     if with_so:
@@ -299,12 +339,7 @@ def backward(P: Dict[str, torch.Tensor], packs: PackedWeights, sv: "Saved", d_ou
 # ------------------------------------------------------------------------------------------------------
 # Native layer loop (csrc/vgg_net.hip): one C-ABI call per forward, one per backward
 # ------------------------------------------------------------------------------------------------------
-import ctypes  # noqa: E402
-import os  # noqa: E402
-
-from . import Context, VggGrads, VggWeights, check, lib, ptr_array4  # noqa: E402
-
-USE_NATIVE_LOOP = os.environ.get("FOSVOS_PY_ENGINE", "0") != "1"  # debugging switch: Python-driven per-op loop
+USE_NATIVE_LOOP = native_loop_from_env()  # False: the Python-driven per-op loop (debugging switch; tests flip it)
 
 _CONV_NAMES = [(wn, bn) for (_, _, _, _, wn, bn) in CONVS]
 
@@ -325,7 +360,6 @@ def _streams_overlap(device_index: int, a: "torch.cuda.Stream", b: "torch.cuda.S
     """Do kernels on `a` and `b` run side by side?  Two spin kernels (torch.cuda._sleep), one per stream, timed on the host
     between device syncs against one spin kernel alone: two streams that share a hardware queue take twice as long as one.
     Returns (overlap, ms alone, ms of the pair).  Costs ~1 ms, once per pair and process."""
-    import time
     dev = torch.device("cuda", device_index)
 
     def run(streams):
@@ -343,16 +377,15 @@ def _streams_overlap(device_index: int, a: "torch.cuda.Stream", b: "torch.cuda.S
     return pair < 1.5 * alone, alone, pair
 
 
-def shared_stream(device_index: int, role: str) -> "torch.cuda.Stream":
+def shared_stream(device_index: int, role: str, probe: Optional[bool] = None) -> "torch.cuda.Stream":
+    """The process's stream of `role` on the device, created (and probed: EngineOptions.stream_probe, or `probe`) on first
+    use."""
     key = (device_index, role)
     st = _SHARED_STREAMS.get(key)
     if st is None:
         order = ("aux", "pass", "comm")  # creation order is part of the contract: the weight-gradient stream first
         for earlier in order[:order.index(role)] if role in order else ():
             shared_stream(device_index, earlier)
-        # lab switch FOSVOS_STREAM_SKIP_<ROLE>=k: k throw-away streams first (shifts the role onto another hardware queue)
-        skip = int(os.environ.get("FOSVOS_STREAM_SKIP_" + role.upper(), "0") or 0)
-        _SHARED_STREAMS[("skipped", role, device_index)] = [torch.cuda.Stream(device=device_index) for _ in range(skip)]
         # The mapping is MEASURED, not trusted: the new stream must overlap with the caller's stream and with every role
         # created before it (the weight-gradient stream beside the data-gradient chain; the pass stream beside both).  If the
         # probe finds the pair serialised, the stream is parked (it keeps its queue slot) and the next one is tried.
@@ -360,7 +393,9 @@ def shared_stream(device_index: int, role: str) -> "torch.cuda.Stream":
         for r in order:
             if (device_index, r) in _SHARED_STREAMS:
                 others[r] = _SHARED_STREAMS[(device_index, r)]
-        probe_on = os.environ.get("FOSVOS_STREAM_PROBE", "1") != "0" and role != "comm" and hasattr(torch.cuda, "_sleep")
+        if probe is None:
+            probe = EngineOptions.from_env().stream_probe
+        probe_on = probe and role != "comm" and hasattr(torch.cuda, "_sleep")
         parked, result = [], {"overlaps_with": {}, "tries": 0, "ms": {}}
         for attempt in range(6):
             st = torch.cuda.Stream(device=device_index)
@@ -401,10 +436,8 @@ class ArenaPool:
         self.reserve_frames = 0
 
     def aux_stream(self, device_index: int) -> int:
-        """Handle of the auxiliary HIP stream the backward pass issues its weight-gradient kernels on
-        (FOSVOS_TWO_STREAMS=0 disables it)."""
-        if os.environ.get("FOSVOS_TWO_STREAMS", "1") == "0":
-            return 0
+        """Handle of the auxiliary HIP stream the backward pass issues its weight-gradient kernels on (the passes ask for it
+        only under EngineOptions.two_streams)."""
         st = self._aux.get(device_index)
         if st is None:
             st = self._aux[device_index] = shared_stream(device_index, "aux")
@@ -494,11 +527,7 @@ def _weights_struct(P: Dict[str, torch.Tensor], packs: PackedWeights):
 
 
 def native_forward(P, packs, pool: ArenaPool, x: torch.Tensor, with_side_out: bool, keep: bool):
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"OSVOS_VGG expects [N,3,H,W] frames, got {tuple(x.shape)}")
-    if not x.is_cuda:
-        raise RuntimeError("the HIP OSVOS_VGG runs on the GPU only: move the module and the frame to cuda "
-                           "(there is no CPU fallback)")
+    _check_frame(x)
     for name in ("stages.0.0.weight", "fuse.weight"):
         if not P[name].is_cuda or P[name].dtype != torch.float32:
             raise RuntimeError("OSVOS_VGG parameters must be fp32 tensors on the GPU")
@@ -513,13 +542,11 @@ def native_forward(P, packs, pool: ArenaPool, x: torch.Tensor, with_side_out: bo
     so = ptr_array4([o.data_ptr() for o in outs]) if with_side_out else None
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     t0 = ops._pb()
-    # batched passes: the side_prep convs ride on the auxiliary stream beside the next stage's backbone convs (+0.4 % on the
-    # five-frame training pass; FOSVOS_FWD_AUX=0: one stream).  A single frame stays on one stream: its kernels are too
-    # short for the four event pairs to pay (inference protocol: 0.586 vs 0.564 ms per frame).
-    # (forward_one_stream: the online loop sets it while it runs the passes of a cycle on two alternating streams - the
-    # auxiliary stream is then busy with the previous pass's weight gradients, and the second chain would queue behind them)
-    aux = (pool.aux_stream(idx) if N >= 2 and os.environ.get("FOSVOS_FWD_AUX", "1") != "0"
-           and not getattr(packs, "forward_one_stream", False) else 0)
+    # batched passes: the side_prep convs ride on the auxiliary stream beside the next stage's backbone convs; a single frame
+    # stays on one stream (EngineOptions.fwd_aux, PassFlags.forward_one_stream)
+    opts = packs.options
+    aux = (pool.aux_stream(idx) if N >= 2 and opts.fwd_aux and opts.two_streams and not packs.flags.forward_one_stream
+           else 0)
     if aux:
         check(lib().fosvos_vgg_forward_streams(pool.ctx(idx), ctypes.byref(w), x.data_ptr(), N, H, W, ap, an, fused.data_ptr(),
                                                so, torch.cuda.current_stream(idx).cuda_stream, aux), "vgg_forward_streams")
@@ -533,16 +560,11 @@ def native_forward(P, packs, pool: ArenaPool, x: torch.Tensor, with_side_out: bo
     return (outs if outs is not None else [None] * 4) + [fused], (arena, x, w, keep_alive, (N, H, W))
 
 
-def native_backward(P, packs, saved, d_outs, inplace: bool, defer_join: bool = False) -> Dict[str, torch.Tensor]:
+def native_backward(P, packs, saved, d_outs, inplace: bool) -> Dict[str, torch.Tensor]:
     arena, x, w, keep_alive, (N, H, W) = saved
     dev = x.device
     d_fused = d_outs[4]
-    d_so = list(d_outs[:4])
-    have = [g is not None for g in d_so]
-    with_so = any(have)
-    if with_so and not all(have):
-        ref = next(g for g in d_so if g is not None)
-        d_so = [g if g is not None else torch.zeros_like(ref) for g in d_so]
+    d_so, with_so = _side_grads(d_outs)
     grads: Dict[str, torch.Tensor] = {}
     if d_fused is None and not with_so:
         return grads
@@ -570,18 +592,18 @@ def native_backward(P, packs, saved, d_outs, inplace: bool, defer_join: bool = F
         # the four score_dsn layers are separate [1,16,1,1] / [1] parameters: gather through one [4,16] / [4] scratch
         dsn_tmp = (torch.zeros((4, 16), dtype=torch.float32, device=dev), torch.zeros((4,), dtype=torch.float32, device=dev))
         g.dsn_w, g.dsn_b = dsn_tmp[0].data_ptr(), dsn_tmp[1].data_ptr()
-    # overwrite_grads (set by a loop for the FIRST backward pass of an accumulation cycle, osvos_vgg.OSVOS_VGG.overwrite_grads):
-    # the pass writes its gradients instead of adding them to what the buffers hold - the buffers then need no zeroing
-    # between cycles (one write and one read of every gradient less per cycle).  Only the gradients this call produces are
-    # written: the side-output layers' (score_dsn) go through a scratch and an add below, so the two do not combine.
-    overwrite = inplace and getattr(packs, "overwrite_grads", False)
+    # PassFlags.overwrite_grads: only the gradients this call produces are written - the side-output layers' (score_dsn) go
+    # through a scratch and an add below, so the two do not combine
+    flags = packs.flags
+    overwrite = inplace and flags.overwrite_grads
     if overwrite and with_so:
         raise RuntimeError("OSVOS_VGG backward: overwrite_grads with side-output gradients (score_dsn accumulates through a scratch)")
     g.accumulate = 1 if inplace and not overwrite else 0
-    aux = packs.arenas.aux_stream(dev.index if dev.index is not None else torch.cuda.current_device())
-    g.defer_join = 1 if (defer_join and inplace and aux) else 0
-    g.bucket_events = 1 if getattr(packs, "publish_grad_buckets", False) else 0
-    g.last_pass_of_cycle = 1 if getattr(packs, "last_pass_of_cycle", False) else 0
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    aux = packs.arenas.aux_stream(idx) if packs.options.two_streams else 0
+    g.defer_join = 1 if (flags.defer_wgrad_join and inplace and aux) else 0
+    g.bucket_events = 1 if flags.publish_grad_buckets else 0
+    g.last_pass_of_cycle = 1 if flags.last_pass_of_cycle else 0
     if d_fused is not None:
         d_fused = d_fused.contiguous().float()
         hold.append(d_fused)
@@ -591,7 +613,6 @@ def native_backward(P, packs, saved, d_outs, inplace: bool, defer_join: bool = F
         hold += d_so
         dso = ptr_array4([t.data_ptr() for t in d_so])
     ap, an = _aligned_ptr(arena)
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
     # the dsn scratch is overwritten, never accumulated, by a separate flag-free path: run with accumulate for the
     # parameter buffers and add the scratch afterwards
     t0 = ops._pb()
@@ -650,8 +671,7 @@ class _OSVOSFunction(torch.autograd.Function):
         if not ctx.with_side_out:
             d = [None] * 4 + [d[4]]
         if USE_NATIVE_LOOP:
-            grads = native_backward(ctx.P, ctx.packs, ctx.sv, d, inplace=ctx.inplace,
-                                    defer_join=getattr(ctx.packs, "defer_wgrad_join", False))
+            grads = native_backward(ctx.P, ctx.packs, ctx.sv, d, inplace=ctx.inplace)
         else:
             grads = backward(ctx.P, ctx.packs, ctx.sv, d, inplace=ctx.inplace)
         ctx.sv = None  # free the activations

@@ -1,0 +1,130 @@
+"""The switches of the Python face, declared: what the training loops decide (LoopOptions) and what a model's passes decide
+(EngineOptions).  ``from_env`` of each is the ONLY place of the package that parses a ``FOSVOS_*`` switch; everything else
+takes an options object.  The defaults are the measured best; every switch selects between two paths that both stay tested.
+The table of all of them is in DESIGN.md (section 2).
+
+No torch and no library load here: importable anywhere.
+"""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass
+from typing import Mapping
+
+
+def _on(environ: Mapping[str, str], name: str) -> bool:
+    """A switch that is on unless the variable is exactly '0'."""
+    return environ.get("FOSVOS_" + name, "1") != "0"
+
+
+def _opt_in(environ: Mapping[str, str], name: str) -> bool:
+    """A switch that is off unless the variable is exactly '1'."""
+    return environ.get("FOSVOS_" + name, "0") == "1"
+
+
+def _count(environ: Mapping[str, str], name: str, default: int) -> int:
+    """A positive count; malformed -> the default, below 1 -> 1."""
+    try:
+        return max(1, int(environ.get("FOSVOS_" + name, default)))
+    except ValueError:
+        return default
+
+
+@dataclass(frozen=True)
+class LoopOptions:
+    """What ``train_online._train`` / ``train_offline._train`` decide; resolved once at their entry (``options=`` or
+    ``from_env()`` at that moment)."""
+
+    # FOSVOS_MICROBATCH_GROUP.  Micro-batches of one accumulation cycle that may run as one batched pass (5 = the
+    # reference's whole cycle, avg_grad_every_n; 1 = the reference's one-by-one order).  A group never crosses an optimizer
+    # step, so the default runs a cycle of up to five same-size frames as ONE forward / backward pass: the fewest launches
+    # and the fullest kernels (measured on the 480x854 step: 1086 frames/s against 1010 with 3 + 2 and 932 with 2 + 2 + 1).
+    # Longer cycles are cut into groups of at most this many frames (activation memory grows with the group).
+    microbatch_group: int = 5
+    # FOSVOS_GROUP_WINDOW.  How many micro-batches of an accumulation cycle the loop looks at together before it forms its
+    # batched passes (never more than the cycle itself, never fewer than a group).  The reference's augmentation draws a
+    # random scale per iteration (src/dataloaders/custom_transforms.py:63-76), so consecutive frames rarely share a size;
+    # gradients inside a cycle are a sum, so the micro-batches of the window are bucketed BY SHAPE and every bucket runs as
+    # one batched pass.
+    group_window: int = 16
+    # FOSVOS_DEFER_JOIN=0 off.  Weights are constant inside an accumulation cycle: the next forward pass may overlap the
+    # weight-gradient tail of this backward pass (PassFlags.defer_wgrad_join for the length of the loop).
+    defer_join: bool = True
+    # FOSVOS_SPLIT_STEP=0 = one optimizer step.  On the GPU the step is split by gradient bucket: stages 5-3 (97 % of the
+    # parameters) are stepped, zeroed and repacked behind the data-gradient chain, while the weight-gradient stream still
+    # works through stages 3-1; only the small rest waits for that stream (train_online: close_cycle_if_due).
+    split_step: bool = True
+    # FOSVOS_STAGE_LOSS (on only when exactly '1').  The loss of a batched pass in three stages (class counts in front of the
+    # forward pass, values and host copy behind the backward pass; fosvos_cbce_loss_frames_parts): two launches and the copy
+    # leave the chain of small kernels between the passes.  +0.5 % when that chain was 150 us long, neutral after the head
+    # kernels got shorter, +0.3 % on the final build (5 of 5 interleaved rounds, profiles/r04_lab_step_ab_tunables.txt).
+    # The same arithmetic either way (tested bit for bit); off = the loss as one call between the passes.
+    stage_loss: bool = True
+    # FOSVOS_GRAD_OVERWRITE=0: zero in the optimizer step, always add.  Gradient buffers without zeroing: a cycle that is ONE
+    # batched pass (the usual case: nAveGrad frames of one shape) WRITES its gradients (PassFlags.overwrite_grads) instead of
+    # adding them to buffers the previous optimizer step had to zero - one write and one read of every gradient less per
+    # cycle, in the HBM-bound tail of the cycle (+0.6 %, profiles/r04_lab_step_ab_tunables.txt).  The optimizer step then
+    # leaves the gradients in place ("stale"), and a cycle of several passes - which do add - zeroes the buffer first.  The
+    # same values either way (a sum that starts from zero): tested bit for bit.
+    grad_overwrite: bool = True
+    # FOSVOS_PASS_STREAMS=0: one stream.  A cycle whose micro-batches cannot run as ONE batched pass (frames of different
+    # sizes, or microbatch_group < nAveGrad) runs its passes on two alternating streams: the weights do not change inside a
+    # cycle and every pass has its own arena, so the forward pass of one micro-batch may run beside the backward pass of the
+    # previous one (their weight-gradient kernels share one stream and stay in order, so the accumulation into the gradients
+    # does too).  Measured at 480x854, passes of 1 / 2 / 3+2 frames: +9.4 % / +2.0 % / -2.6 %, hence only for passes of at
+    # most two frames (train_online: run_window).
+    pass_streams: bool = True
+    # FOSVOS_COMM_TIMING=1.  parallel.GradSync records events around every bucket's all-reduce (GPU only; timing_summary()).
+    # ``parallel.COMM_TIMING``, which bench.py sets, turns the same on.
+    comm_timing: bool = False
+
+    @classmethod
+    def from_env(cls, environ: Mapping[str, str] = os.environ) -> "LoopOptions":
+        return cls(microbatch_group=_count(environ, "MICROBATCH_GROUP", 5), group_window=_count(environ, "GROUP_WINDOW", 16),
+                   defer_join=_on(environ, "DEFER_JOIN"), split_step=_on(environ, "SPLIT_STEP"),
+                   stage_loss=environ.get("FOSVOS_STAGE_LOSS", "1") == "1", grad_overwrite=_on(environ, "GRAD_OVERWRITE"),
+                   pass_streams=_on(environ, "PASS_STREAMS"), comm_timing=_opt_in(environ, "COMM_TIMING"))
+
+
+@dataclass(frozen=True)
+class EngineOptions:
+    """What the passes of one model decide; resolved when the model is constructed (``net.options``, replaceable with
+    ``dataclasses.replace``).  ``stream_probe`` alone is process-level: engine.shared_stream resolves it when it creates a
+    role's stream."""
+
+    # FOSVOS_TWO_STREAMS=0 off.  The backward pass issues its weight-gradient kernels on the auxiliary stream, beside the
+    # data-gradient chain (same kernels, same fixed-order reductions: tested bit for bit against one stream).
+    two_streams: bool = True
+    # FOSVOS_FWD_AUX=0: one stream.  Batched forward passes: the side_prep convs ride on the auxiliary stream beside the next
+    # stage's backbone convs (+0.4 % on the five-frame training pass).  A single frame stays on one stream whatever this says:
+    # its kernels are too short for the four event pairs to pay (inference protocol: 0.586 vs 0.564 ms per frame).
+    fwd_aux: bool = True
+    # FOSVOS_HEAD_UNIFORM=0 off (A/B).  Where the 16 channel filters of an upscale layer are identical - interp_surgery's
+    # bilinear filters, which the optimizers never move (lr 0) - the head kernels contract the channels before the
+    # upsampling (fosvos_head_fwd's ``filt_uniform``).  Checked on the weights themselves whenever they change.
+    head_uniform: bool = True
+    # FOSVOS_STREAM_PROBE=0 skips the ~1 ms probe.  The mapping of a shared stream onto a hardware queue is MEASURED when the
+    # stream is created, and a stream that is serialised with an earlier one is parked (engine.shared_stream).
+    stream_probe: bool = True
+    # FOSVOS_RESNET_MFMA=0 keeps every ResNet layer on the vector-ALU kernel at its real channel count, fp32 first layer (A/B
+    # runs); on, every map is widened to a channel count the MFMA implicit GEMM takes (resnet_engine.width).
+    resnet_mfma: bool = True
+    # FOSVOS_RESNET_FUSE_FIRST=0: the ResNet's first conv and max pool as two launches instead of one.
+    resnet_fuse_first: bool = True
+    # FOSVOS_RESNET_AUX=1 issues the ResNet's side_prep / downsample convs on a second stream beside the trunk.  Off by
+    # default: measured at 1080p it LOSES 0.09-0.12 ms per frame on every net (the ~20 cross-stream event waits cost more than
+    # the seven small kernels they take off the chain).
+    resnet_aux: bool = False
+
+    @classmethod
+    def from_env(cls, environ: Mapping[str, str] = os.environ) -> "EngineOptions":
+        return cls(two_streams=_on(environ, "TWO_STREAMS"), fwd_aux=_on(environ, "FWD_AUX"),
+                   head_uniform=_on(environ, "HEAD_UNIFORM"), stream_probe=_on(environ, "STREAM_PROBE"),
+                   resnet_mfma=_on(environ, "RESNET_MFMA"), resnet_fuse_first=_on(environ, "RESNET_FUSE_FIRST"),
+                   resnet_aux=_opt_in(environ, "RESNET_AUX"))
+
+
+def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:
+    """Initial value of ``engine.USE_NATIVE_LOOP``: FOSVOS_PY_ENGINE=1 selects the Python-driven per-op loop (debugging, and
+    the reference point the native loop is tested against)."""
+    return environ.get("FOSVOS_PY_ENGINE", "0") != "1"

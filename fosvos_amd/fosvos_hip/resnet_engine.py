@@ -14,22 +14,18 @@ import torch
 import torch.nn as nn
 
 import ctypes
-import os
 
 from . import Context, Conv2dDesc, ResnetBlock, ResnetNet, check, lib, ops, ptr_array4
+from .options import EngineOptions
 
 
-def use_mfma() -> bool:
-    """FOSVOS_RESNET_MFMA=0 keeps every layer on the vector-ALU kernel (A/B runs)."""
-    return os.environ.get("FOSVOS_RESNET_MFMA", "1") != "0"
-
-
-def width(c: int) -> int:
+def width(c: int, mfma: bool) -> int:
     """Channels a feature map is STORED with.  On the MFMA path every map is widened with zero channels to a count the
     implicit GEMM takes on both sides (32, or a multiple of 64): a 16-, 8- or 59-channel layer then runs on the matrix
     cores - padded weights, BatchNorm terms and biases are zero, so the extra channels hold exact zeros end to end and
-    the arithmetic on the real ones is unchanged.  Without MFMA: the next multiple of 8 (16-byte vectors)."""
-    if not use_mfma():
+    the arithmetic on the real ones is unchanged.  Without MFMA (EngineOptions.resnet_mfma = False): the next multiple of 8
+    (16-byte vectors)."""
+    if not mfma:
         return (c + 7) // 8 * 8
     return 32 if c <= 32 else (c + 63) // 64 * 64
 
@@ -49,7 +45,7 @@ class _Conv:
     __slots__ = ("packed", "bias", "ci", "co", "k", "stride", "kind", "ci_real", "co_real")
 
     def __init__(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d], what: str, ci_p: int, co_p: int,
-                 allow_mfma: bool = True) -> None:
+                 allow_mfma: bool) -> None:
         k = conv.kernel_size[0]
         if (conv.kernel_size not in ((1, 1), (3, 3)) or conv.stride not in ((1, 1), (2, 2)) or conv.dilation != (1, 1)
                 or conv.groups != 1 or conv.padding != (k // 2, k // 2)):
@@ -70,7 +66,7 @@ class _Conv:
         cb = None if conv.bias is None else _pad_to(conv.bias.detach(), co_p)
         # (16 output channels is the side_prep shape: the MFMA path has a 16-wide tile with an fp32 store for it;
         # stride 2 runs there too, with a subsampling store: fosvos_conv3x3_s2_fwd)
-        self.kind = int(allow_mfma and use_mfma() and k == 3 and ci_p % 32 == 0
+        self.kind = int(allow_mfma and k == 3 and ci_p % 32 == 0
                         and (co_p % 64 == 0 or co_p == 32 or (co_p == 16 and self.stride == 1)))
         if self.kind:
             folded, self.bias = ops.fold_conv_bn(w.contiguous(), cb, bnp)
@@ -99,7 +95,7 @@ class _Conv:
 class _Block:
     __slots__ = ("convs", "down", "c_out")
 
-    def __init__(self, blk: nn.Module, what: str, c_in: int) -> None:
+    def __init__(self, blk: nn.Module, what: str, c_in: int, mfma: bool) -> None:
         pairs = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
         if hasattr(blk, "conv3"):
             pairs.append((blk.conv3, blk.bn3))
@@ -110,7 +106,7 @@ class _Block:
                 raise RuntimeError(f"{what}.conv{i + 1} expects {conv.in_channels} input channels, its input has {c}")
             if bn.num_features != conv.out_channels:
                 raise RuntimeError(f"{what}.bn{i + 1} has {bn.num_features} features for {conv.out_channels} channels")
-            self.convs.append(_Conv(conv, bn, f"{what}.conv{i + 1}", width(c), width(conv.out_channels)))
+            self.convs.append(_Conv(conv, bn, f"{what}.conv{i + 1}", width(c, mfma), width(conv.out_channels, mfma), mfma))
             c = conv.out_channels
         self.c_out = c
         self.down = None
@@ -119,7 +115,7 @@ class _Block:
             if dconv.in_channels != c_in or dconv.out_channels != c:
                 raise RuntimeError(f"{what}.downsample maps {dconv.in_channels} -> {dconv.out_channels} channels, the block "
                                    f"{c_in} -> {c}")
-            self.down = _Conv(dconv, dbn, f"{what}.downsample", width(c_in), width(c), allow_mfma=False)
+            self.down = _Conv(dconv, dbn, f"{what}.downsample", width(c_in, mfma), width(c, mfma), allow_mfma=False)
         elif c != c_in:
             raise RuntimeError(f"{what}: identity residual with {c_in} channels in and {c} out")
 
@@ -132,15 +128,17 @@ class _Block:
 
 
 class ResnetPlan:
-    """Device-side images of one net's weights; rebuilt when any parameter or buffer was written or moved."""
+    """Device-side images of one net's weights; rebuilt when any parameter or buffer was written or moved, or the options
+    that shape the images (resnet_mfma, resnet_fuse_first) were replaced."""
 
-    def __init__(self) -> None:
+    def __init__(self, options: Optional[EngineOptions] = None) -> None:
+        self.options = options if options is not None else EngineOptions.from_env()
         self.signature = None
         self.aux = None  # the auxiliary HIP stream of the native loop (created on first use)
+        self.ctx = None  # ... and the execution context whose events order the two streams
 
-    @staticmethod
-    def _signature(net: nn.Module):
-        return (use_mfma(), os.environ.get("FOSVOS_RESNET_FUSE_FIRST", "1")) + tuple(
+    def _signature(self, net: nn.Module):
+        return (self.options.resnet_mfma, self.options.resnet_fuse_first) + tuple(
             (t.data_ptr(), t._version) for t in list(net.parameters()) + list(net.buffers()))
 
     # Walking the module tree for that signature costs 0.11-0.19 ms per call on the GPU box's host - as much as the device
@@ -167,7 +165,7 @@ class ResnetPlan:
         self._links, self._watched = links, params + bufs
 
     def _unchanged(self) -> bool:
-        if self.signature is None or self.signature[:2] != (use_mfma(), os.environ.get("FOSVOS_RESNET_FUSE_FIRST", "1")):
+        if self.signature is None or self.signature[:2] != (self.options.resnet_mfma, self.options.resnet_fuse_first):
             return False
         for d, name, child in self._links:
             if (len(d) != child) if name is None else (d.get(name) is not child):
@@ -181,6 +179,7 @@ class ResnetPlan:
         if self._unchanged():
             return
         sig = self._signature(net)
+        mfma = self.options.resnet_mfma
         conv1, bn1, _relu, pool = net.layer_base[0], net.layer_base[1], net.layer_base[2], net.layer_base[3]
         if ((conv1.kernel_size, conv1.stride, conv1.padding, conv1.in_channels) != ((7, 7), (2, 2), (3, 3), 3)
                 or conv1.bias is not None):
@@ -188,7 +187,7 @@ class ResnetPlan:
         if (pool.kernel_size, pool.stride, pool.padding, pool.ceil_mode) != (3, 2, 1, False):
             raise NotImplementedError(f"layer_base pool {pool}: the HIP path has MaxPool2d(3, 2, 1)")
         c = conv1.out_channels
-        self.c0 = width(c)  # (the first layer writes the padded width too: zero filters, zero shift)
+        self.c0 = width(c, mfma)  # (the first layer writes the padded width too: zero filters, zero shift)
         w1 = conv1.weight.detach()
         if self.c0 != c:
             w1p = torch.zeros((self.c0, 3, 7, 7), dtype=w1.dtype, device=w1.device)
@@ -204,13 +203,13 @@ class ResnetPlan:
         for i, stage in enumerate(net.layer_stages):
             blocks = []
             for j, b in enumerate(stage):
-                blocks.append(_Block(b, f"layer_stages.{i}.{j}", c))
+                blocks.append(_Block(b, f"layer_stages.{i}.{j}", c, mfma))
                 c = blocks[-1].c_out
             self.stages.append(blocks)
             sp = net.side_prep[i]
             if sp.in_channels != c:
                 raise RuntimeError(f"side_prep.{i} expects {sp.in_channels} input channels, the stage produces {c}")
-            self.side.append(_Conv(sp, None, f"side_prep.{i}", width(c), sp.out_channels))
+            self.side.append(_Conv(sp, None, f"side_prep.{i}", width(c, mfma), sp.out_channels, mfma))
         fuse_w = net.layer_fuse.weight.detach()
         if tuple(fuse_w.shape) != (1, 64, 1, 1) or any(s.co != 16 for s in self.side):
             raise NotImplementedError("the head kernel is built for 16-channel side maps and one output channel")
@@ -247,8 +246,8 @@ class ResnetPlan:
                 cb.down = b.down.desc()
         net = ResnetNet()
         net.first_w, net.first_b, net.first_co = self.first[0].data_ptr(), self.first[1].data_ptr(), self.c0
-        net.first_fp32_math = 0 if use_mfma() else 1
-        net.first_unfused = int(os.environ.get("FOSVOS_RESNET_FUSE_FIRST", "1") == "0")
+        net.first_fp32_math = 0 if self.options.resnet_mfma else 1
+        net.first_unfused = 0 if self.options.resnet_fuse_first else 1
         for s in range(4):
             net.blocks_per_stage[s] = len(self.stages[s])
             net.side[s] = self.side[s].desc()
@@ -277,10 +276,11 @@ def forward_ops(net: nn.Module, plan: ResnetPlan, x: torch.Tensor) -> List[torch
     with torch.no_grad():
         plan.refresh(net)
         n, _c, h, w = x.shape
-        if use_mfma() and plan.c0 <= 32 and os.environ.get("FOSVOS_RESNET_FUSE_FIRST", "1") != "0":
+        mfma = plan.options.resnet_mfma
+        if mfma and plan.c0 <= 32 and plan.options.resnet_fuse_first:
             y = ops.conv7x7s2_pool_first_fwd(x, plan.first[0], plan.first[1], plan.c0)   # conv + pool, one launch
         else:
-            y = ops.conv7x7s2_first_fwd(x, plan.first[0], plan.first[1], plan.c0, relu=True, fp32_math=not use_mfma())
+            y = ops.conv7x7s2_first_fwd(x, plan.first[0], plan.first[1], plan.c0, relu=True, fp32_math=not mfma)
             y = ops.maxpool3x3s2_fwd(y)
         sides = []
         for blocks, side in zip(plan.stages, plan.side):
@@ -311,14 +311,12 @@ def forward(net: nn.Module, plan: ResnetPlan, x: torch.Tensor) -> List[torch.Ten
     outs = [torch.empty((n, 1, h, w) if with_side or i == 4 else (0,), dtype=torch.float32, device=x.device) for i in range(5)]
     dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
     aux = ctx = None
-    # FOSVOS_RESNET_AUX=1 issues the side_prep / downsample convs on a second stream beside the trunk.  Off by default:
-    # measured at 1080p it LOSES 0.09-0.12 ms per frame on every net (the ~20 cross-stream event waits cost more than the
-    # seven small kernels they take off the chain).
-    if os.environ.get("FOSVOS_RESNET_AUX", "0") == "1":
+    # (EngineOptions.resnet_aux: the side_prep / downsample convs on a second stream beside the trunk; off by default)
+    if plan.options.resnet_aux:
         if plan.aux is None or plan.aux.device != x.device:
             plan.aux = torch.cuda.Stream(device=x.device)
         aux = plan.aux.cuda_stream
-        if getattr(plan, "ctx", None) is None or plan.ctx.device != dev:
+        if plan.ctx is None or plan.ctx.device != dev:
             plan.ctx = Context(dev)  # the events that order the two streams belong to this model's plan
         ctx = plan.ctx.handle
     check(L.fosvos_resnet_forward(ctypes.byref(plan.c_net), x.data_ptr(), n, h, w, plan.arena.data_ptr(),

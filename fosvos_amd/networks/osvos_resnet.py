@@ -94,6 +94,16 @@ class OSVOS_RESNET(nn.Module):
         (src/networks/osvos_resnet.py:42-68)."""
         return resnet_engine.forward(self, self._plan, x)
 
+    @property
+    def options(self):
+        """The model's fosvos_hip.options.EngineOptions (from the environment at construction); replace it, e.g. with
+        ``dataclasses.replace(net.options, resnet_aux=True)``, to change what the next passes do."""
+        return self._plan.options
+
+    @options.setter
+    def options(self, value):
+        self._plan.options = value
+
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop('_plan', None)

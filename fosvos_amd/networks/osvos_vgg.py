@@ -6,6 +6,7 @@ fuse), same 52-tensor state_dict (keys, shapes, order) and the same ``forward(x)
 parameters (so optimizers, checkpoints and code that walks ``net.stages`` keep working); the
 arithmetic of forward/backward runs in the hand-written HIP kernels through fosvos_hip.engine.
 """
+import dataclasses
 import os
 from copy import deepcopy
 
@@ -90,72 +91,35 @@ class OSVOS_VGG(nn.Module):
         self._packs.arenas.join()
 
     @property
-    def defer_wgrad_join(self):
-        return getattr(self._packs, "defer_wgrad_join", False)
+    def options(self):
+        """The model's fosvos_hip.options.EngineOptions (from the environment at construction); replace it, e.g. with
+        ``dataclasses.replace(net.options, fwd_aux=False)``, to change what the next passes do."""
+        return self._packs.options
 
-    @defer_wgrad_join.setter
-    def defer_wgrad_join(self, value):
-        if not value:
-            self._packs.arenas.join()
-        self._packs.defer_wgrad_join = bool(value)
-
-    @property
-    def forward_one_stream(self):
-        return getattr(self._packs, "forward_one_stream", False)
-
-    @forward_one_stream.setter
-    def forward_one_stream(self, value):
-        """True: a batched forward pass keeps both of its chains of frames on the caller's stream (the online loop sets it
-        while the passes of a cycle alternate between two streams of their own)."""
-        self._packs.forward_one_stream = bool(value)
+    @options.setter
+    def options(self, value):
+        self._packs.options = value
 
     @property
-    def publish_grad_buckets(self):
-        return getattr(self._packs, "publish_grad_buckets", False)
-
-    @publish_grad_buckets.setter
-    def publish_grad_buckets(self, value):
-        """True: backward passes publish their gradients in completion order (stage 5, stage 4, stage 3, the rest) through
-        ``wait_grad_bucket`` - what the data-parallel loops overlap their bucketed all-reduce with."""
-        self._packs.publish_grad_buckets = bool(value)
+    def pass_flags(self):
+        """The engine.PassFlags of this module: what the attributes of the same names read and write."""
+        return self._packs.flags
 
     @property
     def publishes_grad_buckets(self):
         """Whether backward passes of this module can publish gradient buckets at all: only the native layer loop records
-        the bucket events (the per-op Python engine behind FOSVOS_PY_ENGINE=1 does not)."""
+        the bucket events (the per-op Python engine, engine.USE_NATIVE_LOOP = False, does not)."""
         return bool(engine.USE_NATIVE_LOOP)
 
     @property
     def reserve_arena_frames(self):
+        """The largest batch of one frame size the caller's loop will pass: activation arenas allocated from now on are
+        sized for every batch up to it (engine.ArenaPool.reserve_frames), one allocation per frame size."""
         return self._packs.arenas.reserve_frames
 
     @reserve_arena_frames.setter
     def reserve_arena_frames(self, value):
-        """The largest batch of one frame size the caller's loop will pass: activation arenas allocated from now on are
-        sized for every batch up to it (engine.ArenaPool.reserve_frames), one allocation per frame size."""
         self._packs.arenas.reserve_frames = max(0, int(value))
-
-    @property
-    def overwrite_grads(self):
-        return getattr(self._packs, "overwrite_grads", False)
-
-    @overwrite_grads.setter
-    def overwrite_grads(self, value):
-        """True: the next backward passes WRITE the parameter gradients they compute (all but score_dsn's, which only a loss
-        on the side outputs produces - such a pass refuses the flag) instead of adding them to ``p.grad``: what an
-        accumulation cycle's first pass may do when nothing else adds to the buffers beside it, so that the buffers need no
-        zeroing between cycles.  The online loop sets it around a cycle that is one batched pass."""
-        self._packs.overwrite_grads = bool(value)
-
-    @property
-    def last_pass_of_cycle(self):
-        return getattr(self._packs, "last_pass_of_cycle", False)
-
-    @last_pass_of_cycle.setter
-    def last_pass_of_cycle(self, value):
-        """Hint for the next backward pass: no forward pass follows it before the optimizer step, so its trailing
-        weight-gradient kernels may take the whole chip (the training loops set it around a cycle's last pass)."""
-        self._packs.last_pass_of_cycle = bool(value)
 
     def wait_grad_bucket(self, bucket, stream=None):
         """Make `stream` (default: the current one) wait for gradient bucket `bucket` (``parallel.VGG_BUCKETS`` order) of
@@ -249,3 +213,20 @@ class OSVOS_VGG(nn.Module):
             assert conv.bias.data.shape == c_b.shape
             conv.weight.data = c_w
             conv.bias.data = c_b
+
+
+def _pass_flag(name):
+    """``net.<name>`` for a field of engine.PassFlags (documented there).  Clearing ``defer_wgrad_join`` joins first."""
+    def get(self):
+        return getattr(self._packs.flags, name)
+
+    def set_(self, value):
+        if name == 'defer_wgrad_join' and not value:
+            self._packs.arenas.join()
+        setattr(self._packs.flags, name, bool(value))
+
+    return property(get, set_, doc='engine.PassFlags.' + name)
+
+
+for _field in dataclasses.fields(engine.PassFlags):
+    setattr(OSVOS_VGG, _field.name, _pass_flag(_field.name))

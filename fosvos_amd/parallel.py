@@ -28,6 +28,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from fosvos_hip.options import LoopOptions
 
 SINGLE_RANK_ENV = "FOSVOS_DP_SINGLE_RANK"  # test hook, see collectives_on()
 
@@ -269,16 +270,16 @@ class GradSync:
     stage-5, -4 and -3 transfers (97 % of the bytes) run under the rest of the backward pass.  With CPU tensors (gloo
     tests) the same calls run the same bucketed arithmetic without streams."""
 
-    def __init__(self, net, flat: "FlatGrads"):
+    def __init__(self, net, flat: "FlatGrads", options: Optional[LoopOptions] = None):
         self.net, self.flat = net, flat
         self.active = collectives_on()
         self._comm = None
-        # Communication timing (COMM_TIMING / FOSVOS_COMM_TIMING=1; GPU only): per optimizer step, events on the
+        # Communication timing (COMM_TIMING / LoopOptions.comm_timing; GPU only): per optimizer step, events on the
         # communication stream in front of and behind every bucket's all-reduce, an event on the main stream where the data-
         # gradient chain of the cycle's last backward pass ended, and one on the auxiliary stream where its weight-gradient
         # kernels ended (the later of the two = when the optimizer step could start without communication): what
         # timing_summary() turns into per-bucket offsets and the exposed communication time per step.
-        self.timing = COMM_TIMING or os.environ.get("FOSVOS_COMM_TIMING", "0") == "1"
+        self.timing = COMM_TIMING or (options if options is not None else LoopOptions.from_env()).comm_timing
         self._steps: list = []   # per step: {"dgrad_end": ev, "aux_end": ev, "ready": ev, "buckets": [(start ev, end ev, bytes)]}
 
     def arm(self) -> None:
@@ -291,7 +292,7 @@ class GradSync:
         net = self.net
         if hasattr(net, "publish_grad_buckets"):
             net.publish_grad_buckets = False
-        # the bucket events exist only where the native backward pass recorded them (not under FOSVOS_PY_ENGINE=1)
+        # the bucket events exist only where the native backward pass recorded them (not with engine.USE_NATIVE_LOOP off)
         if self.flat.flat.is_cuda and hasattr(net, "wait_grad_bucket") and getattr(net, "publishes_grad_buckets", True):
             from fosvos_hip import engine
             d = self.flat.flat.device

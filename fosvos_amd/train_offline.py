@@ -4,14 +4,16 @@ Same entry points and loop semantics (src/train_offline.py:77-110): five deeply-
 ``loss = (1 - epoch / n_epochs) * sum(side losses) + fused loss``, ``loss /= avg_grad_every_n``,
 backward, step every ``avg_grad_every_n``-th iteration; snapshots every ``snapshot_every_n`` epochs.
 """
-import os
 import timeit
 from pathlib import Path
+from typing import Optional
 
 import torch
 from torch import optim
 
 from config.mypath import Path as P
+from fosvos_hip.engine import PassFlags
+from fosvos_hip.options import LoopOptions
 from layers.osvos_layers import class_balanced_cross_entropy_loss
 from util import gpu_handler, io_helper, experiment_helper, args_helper
 from util.logger import get_logger
@@ -73,12 +75,13 @@ def _losses(net, minibatch):
 
 def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, optimizer: optim.SGD, summary_writer,
            start_epoch: int, n_epochs: int, avg_grad_every_n: int, snapshot_every_n: int,
-           is_testing_while_training: bool, test_every_n: int) -> dict:
+           is_testing_while_training: bool, test_every_n: int, *, options: Optional[LoopOptions] = None) -> dict:
+    """options: the loop's switches (fosvos_hip.options.LoopOptions); None = from the environment as it is now."""
+    if options is None:
+        options = LoopOptions.from_env()
     log.info('Start of offline training')
     net = net_provider.network
-    net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
-    # weights are constant inside an accumulation cycle: let the next forward overlap the wgrad tail of this backward
-    net.defer_wgrad_join = os.environ.get('FOSVOS_DEFER_JOIN', '1') != '0'
+    flags = getattr(net, 'pass_flags', None) or PassFlags()  # (a module without the native engine: a throw-away set)
     world = parallel.world_size() if data_parallel else 1
     # Data parallel here splits the BATCH, not the accumulation (SURVEY.md section 8(e)(i)): every rank runs all
     # avg_grad_every_n iterations of a cycle on its own shard of each iteration's batch (global batch = world x
@@ -89,7 +92,7 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     # and under data parallelism it is the single all-reduce payload
     named = list(net.named_parameters())
     flat = parallel.FlatGrads.attach(net, [p for _, p in named], names=[n for n, _ in named])
-    sync = parallel.GradSync(net, flat)
+    sync = parallel.GradSync(net, flat, options)
     device = next(net.parameters()).device
 
     n_samples_train = len(data_loader_train)
@@ -97,65 +100,72 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     counter_gradient = 0
     n_iters = 0
     time_all_start = timeit.default_timer()
-    for epoch in range(start_epoch, n_epochs):
-        start_time = timeit.default_timer()
-        # a DistributedSampler (data-parallel loader) draws the same permutation every epoch unless it is told the epoch;
-        # the reference's shuffle=True loader draws a new order per epoch (src/util/io_helper.py:62-70)
-        sampler = getattr(data_loader_train, 'sampler', None)
-        if hasattr(sampler, 'set_epoch'):
-            sampler.set_epoch(epoch)
-        running = torch.zeros(5, device=device)
-        for index, minibatch in enumerate(data_loader_train):
-            losses = _losses(net, minibatch)
-            running += torch.stack([l.detach() for l in losses])
-            loss = (1 - epoch / n_epochs) * sum(losses[:-1]) + losses[-1]
+    net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
+    if not options.defer_join:
+        net.join_gradients()
+    # weights are constant inside an accumulation cycle: let the next forward overlap the wgrad tail of this backward
+    flags.defer_wgrad_join = options.defer_join
+    try:
+        for epoch in range(start_epoch, n_epochs):
+            start_time = timeit.default_timer()
+            # a DistributedSampler (data-parallel loader) draws the same permutation every epoch unless it is told the
+            # epoch; the reference's shuffle=True loader draws a new order per epoch (src/util/io_helper.py:62-70)
+            sampler = getattr(data_loader_train, 'sampler', None)
+            if hasattr(sampler, 'set_epoch'):
+                sampler.set_epoch(epoch)
+            running = torch.zeros(5, device=device)
+            for index, minibatch in enumerate(data_loader_train):
+                losses = _losses(net, minibatch)
+                running += torch.stack([l.detach() for l in losses])
+                loss = (1 - epoch / n_epochs) * sum(losses[:-1]) + losses[-1]
 
-            if index % n_samples_train == n_samples_train - 1:
-                if world > 1:  # every rank holds its shards' part of the batch losses: the logged value is their sum
-                    torch.distributed.all_reduce(running, op=torch.distributed.ReduceOp.SUM)
-                vals = (running / n_samples_train).tolist()  # one device->host sync per epoch
-                loss_train.append(vals[-1])
-                losses_train.append(vals)  # all five deeply supervised losses of the epoch
-                summary_writer.add_scalar('data/total_loss_epoch', vals[-1], epoch)
-                log.info('[Epoch: %d, numImages: %5d]' % (epoch, index + 1))
+                if index % n_samples_train == n_samples_train - 1:
+                    if world > 1:  # every rank holds its shards' part of the batch losses: the logged value is their sum
+                        torch.distributed.all_reduce(running, op=torch.distributed.ReduceOp.SUM)
+                    vals = (running / n_samples_train).tolist()  # one device->host sync per epoch
+                    loss_train.append(vals[-1])
+                    losses_train.append(vals)  # all five deeply supervised losses of the epoch
+                    summary_writer.add_scalar('data/total_loss_epoch', vals[-1], epoch)
+                    log.info('[Epoch: %d, numImages: %5d]' % (epoch, index + 1))
+                    for l in range(len(vals)):
+                        log.info('Loss %d: %f' % (l, vals[l]))
+                    log.info('Execution time: ' + str(timeit.default_timer() - start_time))
+
+                # `loss /= nAveGrad; loss.backward()` of the reference, as a backward pass seeded with 1/nAveGrad (same
+                # gradient, three fewer tiny kernels: see train_online._train)
+                last_of_cycle = world > 1 and (counter_gradient + 1) % local_accum == 0
+                if last_of_cycle:
+                    sync.arm()
+                loss.backward(torch.full_like(loss.detach(), 1.0 / avg_grad_every_n))
+                if last_of_cycle:
+                    sync.begin()
+                counter_gradient += 1
+                n_iters += 1
+
+                if counter_gradient % local_accum == 0:
+                    net.join_gradients()
+                    sync.finish()  # the bucketed all-reduce begun right behind the cycle's last backward pass
+                    optimizer.step()
+                    flat.zero()
+                    counter_gradient = 0
+
+            if (epoch % snapshot_every_n) == snapshot_every_n - 1 and epoch != 0 and parallel.rank() == 0:
+                net_provider.save_model(epoch)
+
+            if is_testing_while_training and epoch % test_every_n == (test_every_n - 1):
+                with torch.no_grad():
+                    running_t = torch.zeros(5, device=device)
+                    for index, minibatch in enumerate(data_loader_test):
+                        running_t += torch.stack(_losses(net, minibatch))
+                    vals = (running_t / max(len(data_loader_test), 1)).tolist()
+                loss_test.append(vals[-1])
+                summary_writer.add_scalar('data/test_loss_epoch', vals[-1], epoch)
                 for l in range(len(vals)):
-                    log.info('Loss %d: %f' % (l, vals[l]))
-                log.info('Execution time: ' + str(timeit.default_timer() - start_time))
-
-            # `loss /= nAveGrad; loss.backward()` of the reference, as a backward pass seeded with 1/nAveGrad (same gradient,
-            # three fewer tiny kernels: see train_online._train)
-            last_of_cycle = world > 1 and (counter_gradient + 1) % local_accum == 0
-            if last_of_cycle:
-                sync.arm()
-            loss.backward(torch.full_like(loss.detach(), 1.0 / avg_grad_every_n))
-            if last_of_cycle:
-                sync.begin()
-            counter_gradient += 1
-            n_iters += 1
-
-            if counter_gradient % local_accum == 0:
-                net.join_gradients()
-                sync.finish()  # the bucketed all-reduce begun right behind the cycle's last backward pass
-                optimizer.step()
-                flat.zero()
-                counter_gradient = 0
-
-        if (epoch % snapshot_every_n) == snapshot_every_n - 1 and epoch != 0 and parallel.rank() == 0:
-            net_provider.save_model(epoch)
-
-        if is_testing_while_training and epoch % test_every_n == (test_every_n - 1):
-            with torch.no_grad():
-                running_t = torch.zeros(5, device=device)
-                for index, minibatch in enumerate(data_loader_test):
-                    running_t += torch.stack(_losses(net, minibatch))
-                vals = (running_t / max(len(data_loader_test), 1)).tolist()
-            loss_test.append(vals[-1])
-            summary_writer.add_scalar('data/test_loss_epoch', vals[-1], epoch)
-            for l in range(len(vals)):
-                log.info('***Testing *** Loss %d: %f' % (l, vals[l]))
-
-    summary_writer.close()
-    net.defer_wgrad_join = False  # joins
+                    log.info('***Testing *** Loss %d: %f' % (l, vals[l]))
+        summary_writer.close()
+    finally:  # whatever happened in the loop, the caller's module does not keep the deferred join
+        net.join_gradients()
+        flags.defer_wgrad_join = False
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     return {'loss_train': loss_train, 'loss_test': loss_test, 'losses_train': losses_train, 'iterations': n_iters,

@@ -10,8 +10,6 @@ reference's logging points, so the loop does not synchronise every iteration.
 Run:  python train_online.py --synthetic --n-epochs 100        (one GPU)
       torchrun --nproc-per-node 8 train_online.py --synthetic --data-parallel --avg-grad-every-n 8
 """
-import sys
-import os
 import timeit
 from pathlib import Path
 from typing import Optional
@@ -20,6 +18,8 @@ import torch
 from torch import optim
 
 from config.mypath import Path as P
+from fosvos_hip.engine import PassFlags
+from fosvos_hip.options import LoopOptions
 from layers.osvos_layers import class_balanced_cross_entropy_loss, class_balanced_cross_entropy_loss_frames, stage_frames_loss
 from util import gpu_handler, io_helper, experiment_helper, args_helper
 from util.logger import get_logger
@@ -81,29 +81,6 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                                settings.eval_speeds, seq_name=seq_name)
 
 
-def _max_group() -> int:
-    """Micro-batches of one accumulation cycle that may run as one batched pass (FOSVOS_MICROBATCH_GROUP, default 5 = the
-    reference's whole cycle, avg_grad_every_n; 1 = the reference's one-by-one order).  A group never crosses an optimizer
-    step, so the default runs a cycle of up to five same-size frames as ONE forward / backward pass: the fewest launches
-    and the fullest kernels (measured on the 480x854 step: 1086 frames/s against 1010 with 3 + 2 and 932 with 2 + 2 + 1).
-    Longer cycles are cut into groups of at most this many frames (activation memory grows with the group)."""
-    try:
-        return max(1, int(os.environ.get('FOSVOS_MICROBATCH_GROUP', '5')))
-    except ValueError:
-        return 5
-
-
-def _group_window() -> int:
-    """How many micro-batches of an accumulation cycle the loop looks at together before it forms its batched passes
-    (FOSVOS_GROUP_WINDOW, default 16; never more than the cycle itself).  The reference's augmentation draws a random scale
-    per iteration (src/dataloaders/custom_transforms.py:63-76), so consecutive frames rarely share a size; gradients inside a
-    cycle are a sum, so the micro-batches of the window are bucketed BY SHAPE and every bucket runs as one batched pass."""
-    try:
-        return max(1, int(os.environ.get('FOSVOS_GROUP_WINDOW', '16')))
-    except ValueError:
-        return 16
-
-
 def _losses_per_frame(fused, gts, backward_seed=None, staged=None):
     """[k] per-frame losses of a batched pass; one fused op on the GPU, the reference's function per slice elsewhere.
     staged: the loss was started beside the forward pass (osvos_layers.stage_frames_loss): its values are written by
@@ -125,97 +102,27 @@ class _Landed:
         pass
 
 
-def _get_summary_writer(seq_name: str):
-    return io_helper.get_summary_writer(Path('tensorboard') / path_stem)
+class _LossLog:
+    """The loss log of one `_train` call.  The reference reads loss.item() every iteration and the running loss at 20 logging
+    points per run (device->host syncs that drain the launch queue).  Here every pass sends its per-frame losses to pinned
+    memory with ONE asynchronous copy and the host does the bookkeeping (running sum, logging points) once the copy has
+    landed: no device-side accumulator kernels, no sync.  `loss_tr` fills in iteration order, a few passes behind the device.
 
+    ring: pinned [slots, frames per pass] fp32 host tensor, or None for CPU tensors.  (Every slot is free at construction:
+    the previous call ended with a device sync.)"""
 
-def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summary_writer, seq_name: str,
-           start_epoch: int, n_epochs: int, avg_grad_every_n: int, snapshot_every_n: int) -> dict:
-    log.info('Start of Online Training, sequence: ' + seq_name)
-    net = net_provider.network
-    net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
-    net.compute_side_outputs = False      # ... on outputs[-1] only (src/train_online.py:80): skip the 4 side logit maps
-    # weights are constant inside an accumulation cycle: let the next forward overlap the wgrad tail of this backward
-    net.defer_wgrad_join = os.environ.get('FOSVOS_DEFER_JOIN', '1') != '0'
-    world = parallel.world_size() if data_parallel else 1
-    dp_on = data_parallel and parallel.collectives_on()  # (world > 1, or the single-rank test hook)
-    local_accum = parallel.split_accumulation(avg_grad_every_n, world)
-    # gradients live in one flat fp32 buffer: the wgrad kernels accumulate straight into it, zeroing is one memset,
-    # and under data parallelism it is the single all-reduce payload
-    flat = parallel.FlatGrads.attach_module(net)
-    sync = parallel.GradSync(net, flat)
+    def __init__(self, ring, n_samples: int, log_every: int, seq_name: str, summary_writer) -> None:
+        self.ring = ring
+        self.ring_free = list(range(ring.shape[0])) if ring is not None else []
+        self.n_samples, self.log_every, self.seq_name, self.summary_writer = n_samples, log_every, seq_name, summary_writer
+        self.loss_tr = []
+        self.running_host = 0.0
+        self.pending = []  # per window: ([(epoch, minibatch index, host tensor, position)] in iteration order, events, ring slots)
+        self.window = []   # (frames, host tensor, event, ring slot) of the passes of the window being run
 
-    # on the GPU the optimizer step is split by gradient bucket (see run_group); FOSVOS_SPLIT_STEP=0 = one step
-    # (slice indices of the flat buffer; flat.bucket_ids maps a slice to the native bucket its gradients are published as)
-    early_buckets = [b for b, bid in enumerate(flat.bucket_ids) if bid < parallel.VGG_EARLY_BUCKETS]
-    late_buckets = [b for b in range(len(flat.slices)) if b not in early_buckets]
-    split_step = (flat.flat.is_cuda and hasattr(net, 'wait_grad_bucket') and bool(early_buckets) and bool(late_buckets)
-                  and getattr(net, 'publishes_grad_buckets', True)  # the native backward pass records the bucket events
-                  and hasattr(optimizer, '_tables') and os.environ.get('FOSVOS_SPLIT_STEP', '1') != '0')
-    early_params = [p for b in early_buckets for p in flat.bucket_params[b]]
-    early_ids = {id(p) for p in early_params}
-    late_params = [p for group in optimizer.param_groups for p in group['params'] if id(p) not in early_ids]
-    early_prefixes = tuple(pre for b in early_buckets for pre in parallel.VGG_BUCKETS[flat.bucket_ids[b]])
-
-    # lab switch (A/B only): 0 = separate gradient memsets behind the optimizer step and an unannounced backward seed
-    fuse_small = os.environ.get('FOSVOS_LOOP_FUSE', '1') != '0'
-    # The loss of a batched pass in three stages (class counts in front of the forward pass, values and host copy behind the
-    # backward pass; fosvos_cbce_loss_frames_parts): two launches and the copy leave the chain of small kernels between the
-    # passes.  +0.5 % when that chain was 150 us long, neutral after the head kernels got shorter, +0.3 % on the final build
-    # (5 of 5 interleaved rounds, profiles/r04_lab_step_ab_tunables.txt).  The same arithmetic either way (tested bit for
-    # bit); FOSVOS_STAGE_LOSS=0 = the loss as one call between the passes.
-    stage_losses = os.environ.get('FOSVOS_STAGE_LOSS', '1') == '1'
-    # Gradient buffers without zeroing: a cycle that is ONE batched pass (the usual case: nAveGrad frames of one shape) WRITES
-    # its gradients (net.overwrite_grads) instead of adding them to buffers the previous optimizer step had to zero - one
-    # write and one read of every gradient less per cycle, in the HBM-bound tail of the cycle (+0.6 %,
-    # profiles/r04_lab_step_ab_tunables.txt).  The optimizer step then leaves the gradients in place ("stale"), and a cycle
-    # of several passes - which do add - zeroes the buffer first.  The same values either way (a sum that starts from zero):
-    # tested bit for bit.  FOSVOS_GRAD_OVERWRITE=0: zero in the optimizer step, always add.
-    lazy_zero = (fuse_small and flat.flat.is_cuda and hasattr(net, 'overwrite_grads')
-                 and os.environ.get('FOSVOS_GRAD_OVERWRITE', '1') != '0')
-    grads_stale = [False]
-    # A cycle whose micro-batches cannot run as ONE batched pass (frames of different sizes - the reference's augmentation
-    # draws a new scale per iteration - or FOSVOS_MICROBATCH_GROUP < nAveGrad) runs its passes on two alternating streams:
-    # the weights do not change inside a cycle and every pass has its own arena, so the forward pass of one micro-batch may
-    # run beside the backward pass of the previous one (their weight-gradient kernels share one stream and stay in order, so
-    # the accumulation into the gradients does too).  FOSVOS_PASS_STREAMS=0: one stream.
-    pass_streams = None
-    if flat.flat.is_cuda:
-        from fosvos_hip import engine as _engine
-        dev_index = flat.flat.device.index if flat.flat.device.index is not None else torch.cuda.current_device()
-        # the library's auxiliary streams exist from here on, in their fixed creation order (engine.shared_stream)
-        _engine.shared_stream(dev_index, "comm")
-        if (hasattr(net, 'join_gradients') and getattr(net, 'defer_wgrad_join', False)
-                and os.environ.get('FOSVOS_PASS_STREAMS', '1') != '0'):
-            pass_streams = [None, _engine.shared_stream(dev_index, "pass")]  # None = the caller's stream
-    n_samples = len(dataloader)
-    loss_tr = []
-    counter_gradient = 0
-    log_every = max(n_epochs // 20, 1)  # the reference divides by n_epochs // 20, which is 0 below 20 epochs
-    device = next(net.parameters()).device
-    max_group = _max_group()
-    consts = flat.cache.get(('online', avg_grad_every_n, max_group, str(device)))
-    if consts is None:  # (constants of the loop, kept with the gradient buffer: a short call should not re-create them)
-        consts = flat.cache[('online', avg_grad_every_n, max_group, str(device))] = {
-            'inv_avg': torch.ones((), device=device) / avg_grad_every_n,
-            'inv_avg_k': torch.full((max_group,), 1.0 / avg_grad_every_n, device=device),  # backward seed of a batched pass
-            'ring': torch.empty((64, max_group), dtype=torch.float32).pin_memory() if device.type == 'cuda' else None}
-    inv_avg, inv_avg_k = consts['inv_avg'], consts['inv_avg_k']
-
-    # The reference reads loss.item() every iteration and the running loss at 20 logging points per run (device->host
-    # syncs that drain the launch queue).  Here every pass sends its per-frame losses to pinned memory with ONE asynchronous
-    # copy and the host does the bookkeeping (running sum, logging points) once the copy has landed: no device-side
-    # accumulator kernels, no sync.  `loss_tr` fills in iteration order, a few passes behind the device.
-    pending_logs = []   # per window: ([(epoch, minibatch index, host tensor, position)] in iteration order, events, ring slots)
-    ring, ring_free = None, []
-    if device.type == 'cuda':
-        ring = consts['ring']  # (every slot is free again: the previous call ended with a device sync)
-        ring_free = list(range(ring.shape[0]))
-    running_host = [0.0]
-
-    def flush_logs(block: bool) -> None:
-        while pending_logs:
-            items, landed, slots = pending_logs[0]
+    def flush(self, block: bool) -> None:
+        while self.pending:
+            items, landed, slots = self.pending[0]
             # every pass's copy has its own event: the passes of a window alternate between two streams, so the last
             # event alone says nothing about the copies queued on the other stream
             if block:
@@ -223,58 +130,118 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
                     ev.synchronize()
             elif not all(ev.query() for ev in landed):
                 break
-            pending_logs.pop(0)
+            self.pending.pop(0)
             for ep, mb, host_vals, i in items:  # iteration order of the reference's loop, whatever order the passes ran in
-                running_host[0] += float(host_vals[i])
-                if is_log_epoch(ep):
-                    value = running_host[0] / n_samples
-                    running_host[0] = 0.0
-                    loss_tr.append(value)
-                    log.info('[Epoch {0}: {1}, numImages: {2}]'.format(seq_name, ep + 1, mb + 1))
-                    log.info('Loss {0}: {1}'.format(seq_name, value))
-                    summary_writer.add_scalar('data/total_loss_epoch', value, ep)
-            ring_free.extend(slots)
+                self.running_host += float(host_vals[i])
+                if ep % self.log_every == self.log_every - 1:
+                    value = self.running_host / self.n_samples
+                    self.running_host = 0.0
+                    self.loss_tr.append(value)
+                    log.info('[Epoch {0}: {1}, numImages: {2}]'.format(self.seq_name, ep + 1, mb + 1))
+                    log.info('Loss {0}: {1}'.format(self.seq_name, value))
+                    self.summary_writer.add_scalar('data/total_loss_epoch', value, ep)
+            self.ring_free.extend(slots)
 
-    window_logs = []  # (frames, host tensor, event, ring slot) of the passes of the window being run
-
-    def record_losses(group, losses) -> None:
+    def record(self, group, losses) -> None:
         """losses: [k] detached device tensor, frame by frame in the order of `group`."""
         frames = [(g[0], g[1]) for g in group]
-        if ring is not None:
-            if not ring_free:
-                flush_logs(True)
-            if not ring_free:  # every slot is held by the window in flight: a plain (pageable, synchronous) copy instead
-                window_logs.append((frames, losses.to('cpu'), _Landed(), None))
+        if self.ring is not None:
+            if not self.ring_free:
+                self.flush(True)
+            if not self.ring_free:  # every slot is held by the window in flight: a plain (pageable, synchronous) copy instead
+                self.window.append((frames, losses.to('cpu'), _Landed(), None))
                 return
-            slot = ring_free.pop()
-            host_vals = ring[slot, :len(frames)]
+            slot = self.ring_free.pop()
+            host_vals = self.ring[slot, :len(frames)]
             host_vals.copy_(losses, non_blocking=True)
             landed = torch.cuda.Event()
             landed.record()
         else:  # CPU tensors (the gloo tests of the data-parallel wiring): nothing to wait for
             slot, host_vals, landed = None, losses.clone(), _Landed()
-        window_logs.append((frames, host_vals, landed, slot))
+        self.window.append((frames, host_vals, landed, slot))
 
-    def close_window_logs() -> None:
+    def close_window(self) -> None:
         """The passes of a window ran bucket by bucket; the bookkeeping (running loss, logging points) follows the
         reference's iteration order: one pending entry per window, sorted, waiting on the copies of ALL its passes."""
-        if not window_logs:
+        if not self.window:
             return
-        items = sorted(((ep, mb, host_vals, i) for frames, host_vals, _, _ in window_logs
+        items = sorted(((ep, mb, host_vals, i) for frames, host_vals, _, _ in self.window
                         for i, (ep, mb) in enumerate(frames)), key=lambda t: (t[0], t[1]))
-        slots = [slot for _, _, _, slot in window_logs if slot is not None]
-        pending_logs.append((items, [landed for _, _, landed, _ in window_logs], slots))
-        window_logs.clear()
-        flush_logs(False)
+        slots = [slot for _, _, _, slot in self.window if slot is not None]
+        self.pending.append((items, [landed for _, _, landed, _ in self.window], slots))
+        self.window.clear()
+        self.flush(False)
 
-    def is_log_epoch(epoch: int) -> bool:
-        return epoch % log_every == log_every - 1
+
+def _get_summary_writer(seq_name: str):
+    return io_helper.get_summary_writer(Path('tensorboard') / path_stem)
+
+
+def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summary_writer, seq_name: str,
+           start_epoch: int, n_epochs: int, avg_grad_every_n: int, snapshot_every_n: int, *,
+           options: Optional[LoopOptions] = None) -> dict:
+    """options: the loop's switches (fosvos_hip.options.LoopOptions, where each is explained); None = from the environment
+    as it is now."""
+    if options is None:
+        options = LoopOptions.from_env()
+    log.info('Start of Online Training, sequence: ' + seq_name)
+    net = net_provider.network
+    # the flags the passes read (engine.PassFlags): the module's own, or - a module that does not run on the native engine,
+    # like the CPU stand-in of the data-parallel tests - a throw-away set nobody reads
+    flags = getattr(net, 'pass_flags', None)
+    native = flags is not None and all(callable(getattr(net, f, None)) for f in ('wait_grad_bucket', 'join_gradients'))
+    if flags is None:
+        flags = PassFlags()
+    world = parallel.world_size() if data_parallel else 1
+    dp_on = data_parallel and parallel.collectives_on()  # (world > 1, or the single-rank test hook)
+    local_accum = parallel.split_accumulation(avg_grad_every_n, world)
+    # gradients live in one flat fp32 buffer: the wgrad kernels accumulate straight into it, zeroing is one memset,
+    # and under data parallelism it is the single all-reduce payload
+    flat = parallel.FlatGrads.attach_module(net)
+    sync = parallel.GradSync(net, flat, options)
+    on_gpu = flat.flat.is_cuda and native
+
+    # on the GPU the optimizer step is split by gradient bucket (see close_cycle_if_due; LoopOptions.split_step)
+    # (slice indices of the flat buffer; flat.bucket_ids maps a slice to the native bucket its gradients are published as)
+    early_buckets = [b for b, bid in enumerate(flat.bucket_ids) if bid < parallel.VGG_EARLY_BUCKETS]
+    late_buckets = [b for b in range(len(flat.slices)) if b not in early_buckets]
+    split_step = (on_gpu and bool(early_buckets) and bool(late_buckets)
+                  and getattr(net, 'publishes_grad_buckets', True)  # the native backward pass records the bucket events
+                  and hasattr(optimizer, '_tables') and options.split_step)
+    early_params = [p for b in early_buckets for p in flat.bucket_params[b]]
+    early_ids = {id(p) for p in early_params}
+    late_params = [p for group in optimizer.param_groups for p in group['params'] if id(p) not in early_ids]
+    early_prefixes = tuple(pre for b in early_buckets for pre in parallel.VGG_BUCKETS[flat.bucket_ids[b]])
+
+    lazy_zero = on_gpu and options.grad_overwrite  # gradient buffers without zeroing (LoopOptions.grad_overwrite)
+    grads_stale = False
+    pass_streams = None  # a cycle of several passes on two alternating streams (LoopOptions.pass_streams)
+    if flat.flat.is_cuda:
+        from fosvos_hip import engine as _engine
+        dev_index = flat.flat.device.index if flat.flat.device.index is not None else torch.cuda.current_device()
+        # the library's auxiliary streams exist from here on, in their fixed creation order (engine.shared_stream)
+        _engine.shared_stream(dev_index, "comm")
+        if native and options.defer_join and options.pass_streams:
+            pass_streams = [None, _engine.shared_stream(dev_index, "pass")]  # None = the caller's stream
+    counter_gradient = 0
+    log_every = max(n_epochs // 20, 1)  # the reference divides by n_epochs // 20, which is 0 below 20 epochs
+    device = next(net.parameters()).device
+    max_group = options.microbatch_group
+    max_window = max(max_group, options.group_window)
+    consts = flat.cache.get(('online', avg_grad_every_n, max_group, str(device)))
+    if consts is None:  # (constants of the loop, kept with the gradient buffer: a short call should not re-create them)
+        consts = flat.cache[('online', avg_grad_every_n, max_group, str(device))] = {
+            'inv_avg': torch.ones((), device=device) / avg_grad_every_n,
+            'inv_avg_k': torch.full((max_group,), 1.0 / avg_grad_every_n, device=device),  # backward seed of a batched pass
+            'ring': torch.empty((64, max_group), dtype=torch.float32).pin_memory() if device.type == 'cuda' else None}
+    inv_avg, inv_avg_k = consts['inv_avg'], consts['inv_avg_k']
+    loss_log = _LossLog(consts['ring'], len(dataloader), log_every, seq_name, summary_writer)
 
     def is_snapshot_epoch(epoch: int) -> bool:
         return (epoch % snapshot_every_n) == snapshot_every_n - 1
 
-    side_stream_used = [False]  # a pass of the current cycle ran on pass_streams[1]: the optimizer step waits for it
-    last_pass_on_side = [False]  # ... and it was the most recent pass
+    side_stream_used = False   # a pass of the current cycle ran on pass_streams[1]: the optimizer step waits for it
+    last_pass_on_side = False  # ... and it was the most recent pass
 
     def run_group(group, stream=None) -> None:
         """One forward / loss / backward pass over the micro-batches of `group` (iterations of the reference's loop with
@@ -283,11 +250,11 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
         frame) and gradient contribution what the one-by-one loop computes; only the order of the fp32 sums over frames
         differs.  What it buys on the GPU: k frames per kernel launch (the small stage-5 layers fill the chip without
         split-K, fewer launch gaps) and one set of weight-gradient partial slabs per group instead of per frame."""
-        nonlocal counter_gradient, n_iters
+        nonlocal counter_gradient, n_iters, side_stream_used, last_pass_on_side
         k = len(group)
-        last_pass_on_side[0] = stream is not None
+        last_pass_on_side = stream is not None
         if stream is not None:
-            side_stream_used[0] = True
+            side_stream_used = True
             with torch.cuda.stream(stream):
                 run_pass(group, k)
         else:
@@ -305,19 +272,19 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
             gts = torch.cat([g[2]['gt'] for g in group])
         inputs, gts = gpu_handler.cast_cuda_if_possible([inputs, gts])
 
-        # A batched pass spreads its loss over three places: the class counts of the labels are taken here, in front of the
-        # forward pass (they need no logits), the loss kernel proper sits between the passes, and the loss VALUES - which
-        # only the log reads - are finished and copied to the host behind the backward pass.  Between the passes the
-        # whole chip waits on a chain of small kernels: this takes two of them and the copy out of that chain.
+        # A batched pass spreads its loss over three places (LoopOptions.stage_loss): the class counts of the labels are taken
+        # here, in front of the forward pass (they need no logits), the loss kernel proper sits between the passes, and the
+        # loss VALUES - which only the log reads - are finished and copied to the host behind the backward pass.  Between the
+        # passes the whole chip waits on a chain of small kernels: this takes two of them and the copy out of that chain.
         staged = None
-        if k > 1 and stage_losses and gts.is_cuda and class_balanced_cross_entropy_loss is _hip_cbce:
+        if k > 1 and options.stage_loss and gts.is_cuda and class_balanced_cross_entropy_loss is _hip_cbce:
             staged = stage_frames_loss(gts)
 
         outputs = net.forward(inputs)
 
         # (the seed of the backward pass below is announced to the loss: its kernel writes the gradient times 1 / nAveGrad
         # and the loss's own backward has nothing left to multiply)
-        seeded = fuse_small and outputs[-1].is_cuda and class_balanced_cross_entropy_loss is _hip_cbce
+        seeded = outputs[-1].is_cuda and class_balanced_cross_entropy_loss is _hip_cbce
         if k == 1:
             loss = (class_balanced_cross_entropy_loss(outputs[-1], gts, size_average=False,
                                                       backward_seed=(inv_avg, 1.0 / avg_grad_every_n))
@@ -328,19 +295,18 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
             loss = _losses_per_frame(outputs[-1], gts, (inv_avg_k, 1.0 / avg_grad_every_n) if seeded else None, staged)
             losses = loss.detach()
         if staged is None:
-            record_losses(group, losses)
+            loss_log.record(group, losses)
 
         # reference: `loss /= nAveGrad; loss.backward()` (src/train_online.py:92-93).  Seeding the backward pass with
         # 1/nAveGrad is the same gradient (the division's own backward produces exactly this factor) without the
         # three tiny kernels of the division, the ones-fill and its backward on the critical path
         closes_cycle = (counter_gradient + k) % local_accum == 0
         last_of_cycle = dp_on and closes_cycle
-        if hasattr(net, 'last_pass_of_cycle'):
-            net.last_pass_of_cycle = closes_cycle
+        flags.last_pass_of_cycle = closes_cycle
         if last_of_cycle:
             sync.arm()
         if split_step and closes_cycle:
-            net.publish_grad_buckets = True
+            flags.publish_grad_buckets = True
         loss.backward(inv_avg if k == 1 else inv_avg_k[:k])
         if last_of_cycle:
             sync.begin()
@@ -349,7 +315,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
             # communication stream instead, behind an event, they cost 0.6 % - a third stream with work in flight - where on
             # this stream they cost nothing measurable: profiles/r04_lab_step_ab_head_loss.txt.)
             staged.finish()
-            record_losses(group, losses)
+            loss_log.record(group, losses)
         # (the reference also sums loss.item() into a per-epoch tensorboard scalar, src/train_online.py:94-104: one
         # device sync per frame; the per-pass asynchronous copy above carries the same information without it)
 
@@ -361,13 +327,14 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
         pass's OWN data-gradient chain is not covered by its bucket events - a stage's event is recorded behind the weight
         gradient of the stage's first conv, which is issued in front of that conv's data gradient - so the closing pass runs
         on the caller's stream, where the step queues behind it; see run_window and close_cycle_if_due.)"""
-        if side_stream_used[0]:
+        nonlocal side_stream_used
+        if side_stream_used:
             torch.cuda.current_stream(device).wait_stream(pass_streams[1])
-            side_stream_used[0] = False
+            side_stream_used = False
 
     def close_cycle_if_due() -> None:
         """The optimizer step behind the cycle's last pass, on the caller's stream."""
-        nonlocal counter_gradient
+        nonlocal counter_gradient, grads_stale
         if counter_gradient % local_accum == 0:
             if split_step:
                 # Stages 5-3 hold 97 % of the parameters and their gradients are final well before the backward pass ends.
@@ -376,8 +343,8 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
                 # is still working through stages 3-1 - and only the small rest waits for that stream.
                 # Data parallel: "final" means all-reduced - the early buckets' collectives were begun while the backward pass
                 # was still running, and each is waited for on its own.
-                net.publish_grad_buckets = False
-                if last_pass_on_side[0]:
+                flags.publish_grad_buckets = False
+                if last_pass_on_side:
                     # (run_window schedules a window's last pass on the caller's stream, so this is a guard: the early step
                     # rewrites and repacks weights the closing pass's data-gradient chain on the other stream still reads)
                     wait_side_stream()
@@ -386,16 +353,12 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
                         sync.wait_bucket(b)
                     else:
                         net.wait_grad_bucket(flat.bucket_ids[b])
-                optimizer.step(only=early_params, tag='early', zero_grad=fuse_small and not lazy_zero)  # (the step kernel zeroes what it read)
-                if not fuse_small:
-                    flat.zero(early_buckets)
+                optimizer.step(only=early_params, tag='early', zero_grad=not lazy_zero)  # (the step kernel zeroes what it read)
                 net.prepack_weights(early_prefixes)
                 wait_side_stream()
                 net.join_gradients()
                 sync.finish()
-                optimizer.step(only=late_params, tag='late', zero_grad=fuse_small and not lazy_zero)
-                if not fuse_small:
-                    flat.zero(late_buckets)
+                optimizer.step(only=late_params, tag='late', zero_grad=not lazy_zero)
             else:
                 wait_side_stream()
                 net.join_gradients()
@@ -403,7 +366,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
                 optimizer.step()
                 if not lazy_zero:
                     flat.zero()
-            grads_stale[0] = lazy_zero
+            grads_stale = lazy_zero
             counter_gradient = 0
 
     def run_window(window) -> None:
@@ -412,6 +375,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
         frames.  The cycle's gradient is a sum over its micro-batches, so the order of the passes changes nothing but the
         order of fp32 additions - and a loader that yields the same frames already sorted by shape runs the IDENTICAL
         passes (tested bit for bit).  Minibatches that are batches themselves (N > 1) run alone."""
+        nonlocal grads_stale
         buckets = {}
         for item in window:
             shape = tuple(item[2]['image'].shape)
@@ -425,18 +389,17 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
             # a window that opens a cycle: one pass that is the whole cycle writes its gradients; anything else adds - to
             # zeros (queued here, on the caller's stream, in front of everything the window's passes do on either stream)
             whole_cycle = counter_gradient == 0 and len(groups) == 1 and len(groups[0]) == local_accum
-            net.overwrite_grads = whole_cycle
+            flags.overwrite_grads = whole_cycle
             if counter_gradient == 0:
-                if grads_stale[0] and not whole_cycle:
+                if grads_stale and not whole_cycle:
                     flat.zero()
-                grads_stale[0] = False
+                grads_stale = False
         if multi:
             # both pass streams must see the last optimizer step and the repacked weight images: pack once here, on the
             # caller's stream, instead of inside the first forward pass (which the second stream would have to wait for)
             net.prepack_weights()
             pass_streams[1].wait_stream(torch.cuda.current_stream(device))
-        if hasattr(net, 'forward_one_stream'):
-            net.forward_one_stream = multi
+        flags.forward_one_stream = multi
         for i, group in enumerate(groups):
             # the window's LAST pass (the one that may close the cycle) always runs on the caller's stream: the split
             # optimizer step is queued there, behind that pass's data-gradient chain
@@ -445,50 +408,55 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
             # the window's minibatches were allocated on the caller's stream and read on the other one: before they are
             # released (window = [] below; a window can end without a cycle close) the caller's stream waits for it
             wait_side_stream()
-        close_window_logs()
+        loss_log.close_window()
         epoch, _idx, _mb, end_of_epoch = window[-1]
         if end_of_epoch and is_snapshot_epoch(epoch) and parallel.rank() == 0:
             net_provider.save_model(epoch, sequence=seq_name)
 
     time_all_start = timeit.default_timer()
     n_iters = 0
-    max_group = _max_group()
-    max_window = max(max_group, _group_window())
-    if hasattr(net, 'reserve_arena_frames'):
+    if native:
         net.reserve_arena_frames = min(max_group, avg_grad_every_n)  # (a pass never holds more frames than a cycle)
-    window = []  # pending (epoch, minibatch index, minibatch, last of its epoch) tuples, all of one accumulation cycle
-    for epoch in range(start_epoch, n_epochs):
-        n_mb = len(dataloader)
-        for minibatch_index, minibatch in enumerate(dataloader):
-            end_of_epoch = minibatch_index == n_mb - 1
-            window.append((epoch, minibatch_index, minibatch, end_of_epoch))
-            # a window ends with its accumulation cycle, and before a snapshot is due (the snapshot must hold exactly the
-            # updates up to its epoch)
-            closes_cycle = (counter_gradient + len(window)) % local_accum == 0
-            if closes_cycle or len(window) >= max_window or (end_of_epoch and is_snapshot_epoch(epoch)):
-                run_window(window)
-                window = []
-    if window:
-        run_window(window)
-
-    net.defer_wgrad_join = False  # joins
-    if lazy_zero:
-        net.overwrite_grads = False
-        if grads_stale[0]:  # leave the buffers as optimizer.zero_grad() would (src/train_online.py:100-104)
-            flat.zero()
-    if hasattr(net, 'forward_one_stream'):
-        net.forward_one_stream = False
-    net.compute_side_outputs = True
+    net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
+    net.compute_side_outputs = False      # ... on outputs[-1] only (src/train_online.py:80): skip the 4 side logit maps
+    if not options.defer_join:
+        net.join_gradients()
+    flags.defer_wgrad_join = options.defer_join
+    try:
+        window = []  # pending (epoch, minibatch index, minibatch, last of its epoch) tuples, all of one accumulation cycle
+        for epoch in range(start_epoch, n_epochs):
+            n_mb = len(dataloader)
+            for minibatch_index, minibatch in enumerate(dataloader):
+                end_of_epoch = minibatch_index == n_mb - 1
+                window.append((epoch, minibatch_index, minibatch, end_of_epoch))
+                # a window ends with its accumulation cycle, and before a snapshot is due (the snapshot must hold exactly the
+                # updates up to its epoch)
+                closes_cycle = (counter_gradient + len(window)) % local_accum == 0
+                if closes_cycle or len(window) >= max_window or (end_of_epoch and is_snapshot_epoch(epoch)):
+                    run_window(window)
+                    window = []
+        if window:
+            run_window(window)
+    finally:  # whatever happened in the loop, the caller's module gets back the flags it came with
+        net.join_gradients()
+        flags.defer_wgrad_join = False
+        flags.publish_grad_buckets = False
+        if lazy_zero:
+            flags.overwrite_grads = False
+            if grads_stale:  # leave the buffers as optimizer.zero_grad() would (src/train_online.py:100-104)
+                flat.zero()
+        flags.forward_one_stream = False
+        net.compute_side_outputs = True
     time_enqueued = timeit.default_timer() - time_all_start  # how far ahead of the device the host loop ran
     if torch.cuda.is_available():
         torch.cuda.synchronize()
-    flush_logs(True)
+    loss_log.flush(True)
     time_for_all = timeit.default_timer() - time_all_start
     n_images = len(dataloader)
     log.info('Train {0}: total time {1} sec'.format(seq_name, str(time_for_all)))
     log.info('Train {0}: {1} images'.format(seq_name, str(n_images)))
     log.info('Train {0}: time per sample {1} sec'.format(seq_name, str(time_for_all / max(n_images, 1))))
-    return {'loss': loss_tr, 'seconds': time_for_all, 'iterations': n_iters, 'seconds_host_enqueue': time_enqueued,
+    return {'loss': loss_log.loss_tr, 'seconds': time_for_all, 'iterations': n_iters, 'seconds_host_enqueue': time_enqueued,
             'comm_timing': sync.timing_summary() if sync.active and sync.timing else None}
 
 

@@ -6,6 +6,7 @@ the SAME bf16-rounded operands, so what remains is summation order and the final
 output scale.  Network tests compare with the pure fp32 oracle: logits within 3 % of the oracle's logit range, the
 thresholded mask identical wherever the oracle's |logit| exceeds that tolerance.
 """
+import dataclasses
 import os
 import sys
 
@@ -266,7 +267,8 @@ def test_wide_net_on_the_vector_alu_path_only(monkeypatch):
     x = 50.0 * torch.randn(1, 3, 64, 96, generator=torch.Generator().manual_seed(9))
     outs, _ = _check_net(net, sd, x)
     assert all(b.convs[0].kind == 0 for st in net._plan.stages for b in st)
-    monkeypatch.setenv("FOSVOS_RESNET_MFMA", "1")
+    assert net.options.resnet_mfma is False                 # (read from the environment when the net was built)
+    net.options = dataclasses.replace(net.options, resnet_mfma=True)
     outs2 = net(x.to(DEV))                                  # same weights, plan rebuilt with the MFMA layers
     assert any(b.convs[0].kind == 1 for st in net._plan.stages for b in st)
     ref = R.forward(sd, x)[-1]
@@ -285,12 +287,13 @@ def test_native_loop_equals_the_op_by_op_loop():
         a = net(x)
         b = resnet_engine.forward_ops(net, net._plan, x)
         a2 = net(x)                                          # the arena is reused
-        os.environ["FOSVOS_RESNET_AUX"] = "1"                # side_prep / downsample convs on the auxiliary stream
+        default = net.options
+        net.options = dataclasses.replace(default, resnet_aux=True)  # side_prep / downsample convs on the auxiliary stream
         try:
             a3 = net(x)
             a4 = net(x)
         finally:
-            del os.environ["FOSVOS_RESNET_AUX"]
+            net.options = default
         torch.cuda.synchronize()
         for u, v, u2, u3, u4 in zip(a, b, a2, a3, a4):
             assert torch.equal(u, v) and torch.equal(u, u2) and torch.equal(u, u3) and torch.equal(u, u4)

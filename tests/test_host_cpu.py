@@ -209,3 +209,132 @@ def test_png_bytescale_known_answers():
     assert bytescale(np.array([[0.2, 0.7], [0.45, 0.2]])).tolist() == [[0, 255], [128, 0]]
     assert bytescale(np.full((2, 3), 0.37)).tolist() == [[0, 0, 0], [0, 0, 0]]
     assert bytescale(np.array([[0.0, 1.0, 0.5, 0.25]])).tolist() == [[0, 255, 128, 64]]
+
+
+# every switch: (options class, field, environment variable, a value that selects the non-default)
+_SWITCHES = [("LoopOptions", "microbatch_group", "FOSVOS_MICROBATCH_GROUP", "3"),
+             ("LoopOptions", "group_window", "FOSVOS_GROUP_WINDOW", "7"),
+             ("LoopOptions", "defer_join", "FOSVOS_DEFER_JOIN", "0"),
+             ("LoopOptions", "split_step", "FOSVOS_SPLIT_STEP", "0"),
+             ("LoopOptions", "stage_loss", "FOSVOS_STAGE_LOSS", "0"),
+             ("LoopOptions", "grad_overwrite", "FOSVOS_GRAD_OVERWRITE", "0"),
+             ("LoopOptions", "pass_streams", "FOSVOS_PASS_STREAMS", "0"),
+             ("LoopOptions", "comm_timing", "FOSVOS_COMM_TIMING", "1"),
+             ("EngineOptions", "two_streams", "FOSVOS_TWO_STREAMS", "0"),
+             ("EngineOptions", "fwd_aux", "FOSVOS_FWD_AUX", "0"),
+             ("EngineOptions", "head_uniform", "FOSVOS_HEAD_UNIFORM", "0"),
+             ("EngineOptions", "stream_probe", "FOSVOS_STREAM_PROBE", "0"),
+             ("EngineOptions", "resnet_mfma", "FOSVOS_RESNET_MFMA", "0"),
+             ("EngineOptions", "resnet_fuse_first", "FOSVOS_RESNET_FUSE_FIRST", "0"),
+             ("EngineOptions", "resnet_aux", "FOSVOS_RESNET_AUX", "1")]
+
+
+def test_options_from_an_empty_environment_are_the_defaults():
+    import dataclasses
+    from fosvos_hip import options
+    assert options.LoopOptions.from_env({}) == options.LoopOptions()
+    assert options.EngineOptions.from_env({}) == options.EngineOptions()
+    assert options.LoopOptions() == options.LoopOptions(
+        microbatch_group=5, group_window=16, defer_join=True, split_step=True, stage_loss=True, grad_overwrite=True,
+        pass_streams=True, comm_timing=False)
+    assert options.EngineOptions() == options.EngineOptions(
+        two_streams=True, fwd_aux=True, head_uniform=True, stream_probe=True, resnet_mfma=True, resnet_fuse_first=True,
+        resnet_aux=False)
+    assert options.native_loop_from_env({}) and not options.native_loop_from_env({"FOSVOS_PY_ENGINE": "1"})
+    # the table above covers every field of both classes
+    for cls in (options.LoopOptions, options.EngineOptions):
+        assert {f.name for f in dataclasses.fields(cls)} == {s[1] for s in _SWITCHES if s[0] == cls.__name__}
+
+
+@pytest.mark.parametrize("cls_name,field,var,value", _SWITCHES)
+def test_each_variable_changes_exactly_its_own_field(cls_name, field, var, value):
+    import dataclasses
+    from fosvos_hip import options
+    for name in ("LoopOptions", "EngineOptions"):
+        cls = getattr(options, name)
+        got, default = cls.from_env({var: value}), cls()
+        for f in dataclasses.fields(cls):
+            if name == cls_name and f.name == field:
+                assert getattr(got, f.name) != getattr(default, f.name), f.name
+                if f.type == "int":
+                    assert getattr(got, f.name) == int(value)
+            else:
+                assert getattr(got, f.name) == getattr(default, f.name), f.name
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        setattr(getattr(options, cls_name)(), field, None)
+
+
+@pytest.mark.parametrize("value,group,window", [("", 5, 16), ("five", 5, 16), ("2.5", 5, 16), ("0", 1, 1), ("-3", 1, 1),
+                                                ("4", 4, 4)])
+def test_malformed_and_non_positive_counts_fall_back(value, group, window):
+    from fosvos_hip.options import LoopOptions
+    got = LoopOptions.from_env({"FOSVOS_MICROBATCH_GROUP": value, "FOSVOS_GROUP_WINDOW": value})
+    assert (got.microbatch_group, got.group_window) == (group, window)
+
+
+def test_pass_flags_are_declared():
+    """A misspelt flag raises; the module's attributes of the same names are the flags."""
+    import dataclasses
+    from fosvos_hip.engine import PackedWeights, PassFlags
+    from networks.osvos_vgg import OSVOS_VGG
+    flags = PassFlags()
+    assert [f.name for f in dataclasses.fields(flags)] == ["defer_wgrad_join", "forward_one_stream", "publish_grad_buckets",
+                                                          "overwrite_grads", "last_pass_of_cycle"]
+    assert not any(getattr(flags, f.name) for f in dataclasses.fields(flags))
+    with pytest.raises(AttributeError):
+        flags.no_such_flag = True
+    with pytest.raises(AttributeError):
+        flags.no_such_flag
+    assert isinstance(PackedWeights().flags, PassFlags)
+    net = OSVOS_VGG(pretrained=0)
+    assert net.pass_flags is net._packs.flags and net.options is net._packs.options
+    for f in dataclasses.fields(PassFlags):
+        assert getattr(net, f.name) is False
+        setattr(net, f.name, 1)
+        assert getattr(net.pass_flags, f.name) is True and getattr(net, f.name) is True
+        setattr(net, f.name, False)
+        assert getattr(net.pass_flags, f.name) is False
+    net.options = dataclasses.replace(net.options, head_uniform=False)
+    assert net._packs.options.head_uniform is False
+
+
+class _ScalarLog:
+    def __init__(self):
+        self.calls = []
+
+    def add_scalar(self, tag, value, step):
+        self.calls.append((tag, value, step))
+
+
+def test_loss_log_keeps_iteration_order():
+    """`train_online._LossLog` on CPU tensors: the passes of a window arrive bucket by bucket (out of iteration order), the
+    log - `loss_tr` and the add_scalar calls - follows the reference's iteration order (src/train_online.py:84-90): the
+    running sum of the losses over the iterations since the last logging point, divided by n_samples, at every iteration of a
+    logging epoch."""
+    import train_online
+    n_samples, log_every, n_epochs = 3, 2, 4
+    g = torch.Generator().manual_seed(11)
+    loss = {(ep, mb): torch.rand((), generator=g) for ep in range(n_epochs) for mb in range(n_samples)}
+    writer = _ScalarLog()
+    log = train_online._LossLog(None, n_samples, log_every, "seq", writer)
+    its = sorted(loss)
+    for lo in range(0, len(its), 5):                 # windows of five iterations (they cross epoch ends)
+        window = its[lo:lo + 5]
+        passes = [window[0::2][::-1], window[1::2]]  # two passes per window: iterations 4 2 0, then 1 3
+        for group in passes:
+            log.record([(ep, mb, None, False) for ep, mb in group], torch.stack([loss[key] for key in group]))
+        assert log.window
+        log.close_window()
+        assert not log.window
+    log.flush(True)
+    assert not log.pending
+    # the plain loop
+    want, running = [], 0.0
+    for ep in range(n_epochs):
+        for mb in range(n_samples):
+            running += float(loss[(ep, mb)])
+            if ep % log_every == log_every - 1:
+                want.append((running / n_samples, ep))
+                running = 0.0
+    assert len(want) == 6 and log.loss_tr == [v for v, _ in want]
+    assert writer.calls == [("data/total_loss_epoch", v, ep) for v, ep in want]

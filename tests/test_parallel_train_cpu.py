@@ -189,6 +189,42 @@ def test_offline_train_dp_equals_single_process(tmp_path):
     _compare(_launch("offline", tmp_path), _run_offline(_frames(4, batch=2), 2, False))
 
 
+class _FailingLoader:
+    """A loader whose third minibatch of an epoch raises."""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __iter__(self):
+        for i, f in enumerate(self.frames):
+            if i == 2:
+                raise RuntimeError("loader failed")
+            yield f
+
+
+@pytest.mark.parametrize("loop", ["online", "offline"])
+def test_a_failing_loop_restores_the_module(loop):
+    """An exception half-way through `_train` propagates and leaves the caller's module as it came: side outputs on, no
+    deferred weight-gradient join."""
+    net = TinyOSVOS()
+    loader = _FailingLoader(_frames(4))
+    with pytest.raises(RuntimeError, match="loader failed"):
+        if loop == "online":
+            import train_online
+            train_online.class_balanced_cross_entropy_loss = _cbce
+            train_online.data_parallel = False
+            train_online._train(_Prov(net), loader, _sgd(net), _Writer(), "tiny", 0, 1, 2, 10 ** 9)
+        else:
+            import train_offline
+            train_offline.class_balanced_cross_entropy_loss = _cbce
+            train_offline.data_parallel = False
+            train_offline._train(_Prov(net), loader, None, _sgd(net), _Writer(), 0, 2, 2, 10 ** 9, False, 5)
+    assert net.compute_side_outputs is True and net.defer_wgrad_join is False
+
+
 def test_flat_grad_buckets_of_the_real_module():
     """Bucket slices of the real OSVOS_VGG parameter list: completion order, contiguous, frozen deconvs left out, every
     other trainable element covered exactly once (14,917,637 = 15,267,157 - 349,520 frozen)."""

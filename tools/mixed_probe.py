@@ -25,14 +25,14 @@ def run(epochs):
     r = train_online._train(prov, mixed, opt, W(), "t", 0, epochs, 5, 10 ** 9)
     torch.cuda.synchronize()
     return (time.perf_counter() - t) * 1e3, r["seconds_host_enqueue"] * 1e3, r["iterations"]
-import os
+import dataclasses
+from fosvos_hip.options import LoopOptions
 if len(sys.argv) > 1 and sys.argv[1] == "g1first":
     full = [m for m in mixed if m["image"].shape[2] == 480][:1]
-    os.environ["FOSVOS_MICROBATCH_GROUP"] = "1"
     torch.cuda.synchronize(); t = time.perf_counter()
-    train_online._train(prov, full, opt, W(), "t", 0, 40, 5, 10 ** 9)
+    train_online._train(prov, full, opt, W(), "t", 0, 40, 5, 10 ** 9,
+                        options=dataclasses.replace(LoopOptions.from_env(), microbatch_group=1))
     torch.cuda.synchronize(); print("single-frame passes, 40 steps: %.1f ms" % ((time.perf_counter() - t) * 1e3))
-    del os.environ["FOSVOS_MICROBATCH_GROUP"]
 run(2)
 for _ in range(3):
     ms, host, it = run(5)

@@ -4,7 +4,6 @@ import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "fosvos_amd"))
 from networks.osvos_resnet import OSVOS_RESNET
-from fosvos_hip.resnet_engine import ResnetPlan
 dev = "cuda:0"
 for version, e in ((18, 2), (18, 3), (34, 2)):
     torch.manual_seed(1)
@@ -18,6 +17,6 @@ for version, e in ((18, 2), (18, 3), (34, 2)):
     torch.cuda.synchronize()
     t_all = (time.perf_counter() - t0) / 300 * 1e3
     t0 = time.perf_counter()
-    for _ in range(300): ResnetPlan._signature(net)
+    for _ in range(300): net._plan._signature(net)
     t_sig = (time.perf_counter() - t0) / 300 * 1e3
     print("resnet%d e=%d: enqueue %.3f ms per call, with final sync %.3f ms per call, signature alone %.3f ms" % (version, e, t_enq, t_all, t_sig))
