@@ -748,9 +748,77 @@ void launch_conv2d(const ConvLaunch &L, dim3 grid, hipStream_t st, const uint4 *
 #undef FOSVOS_GO
 }
 
+// Shape arithmetic and plan of one fosvos_conv2d_fwd launch (shared with fosvos_conv2d_plan).
+struct Conv2dGeom {
+    int Ho, Wo, Cop, cic;
+    int64_t npix;
+    ConvLaunch L;
+    dim3 grid;
+};
+Conv2dGeom conv2d_geom(int N, int H, int W, int Ci, int Co, int k, int stride) {
+    Conv2dGeom g;
+    const int P = k / 2;
+    g.Ho = (H + 2 * P - k) / stride + 1;
+    g.Wo = (W + 2 * P - k) / stride + 1;
+    g.Cop = roundup(Co, 8);
+    g.cic = roundup(Ci, 8) / 8;
+    g.npix = (int64_t)N * g.Ho * g.Wo;
+    g.L = plan_conv2d(g.npix, g.Cop, g.cic);
+    g.grid = dim3((unsigned)cdiv(g.npix, g.L.threads), (unsigned)cdiv(g.Cop, g.L.cob));
+    return g;
+}
+
+// ... and of one fosvos_conv7x7s2_first_fwd launch: the MFMA form (nfb fragment blocks of 16 channels, one workgroup per
+// 8 x 32 tile) or the fp32 vector-ALU form (channel blocks of L.cob).
+struct FirstGeom {
+    int Ho, Wo, Cop, tiles_x, tiles_y, nfb;
+    bool mfma;
+    ConvLaunch L;
+    dim3 grid;
+};
+FirstGeom first_geom(int N, int H, int W, int Co, unsigned flags) {
+    FirstGeom g;
+    g.Ho = (H - 1) / 2 + 1;
+    g.Wo = (W - 1) / 2 + 1;
+    g.Cop = roundup(Co, 8);
+    g.tiles_x = (int)cdiv(g.Wo, F7_TW);
+    g.tiles_y = (int)cdiv(g.Ho, F7_TH);
+    g.mfma = !(flags & FOSVOS_CONV_FP32_MATH) && g.Cop <= 64;
+    g.nfb = std::min(f7_nc(g.Cop) / 16, 4);
+    g.L = plan_conv2d((int64_t)N * g.Ho * g.Wo, g.Cop, 1);
+    g.grid = g.mfma ? dim3((unsigned)(g.tiles_x * g.tiles_y), 1, (unsigned)N)
+                    : dim3((unsigned)(g.tiles_x * g.tiles_y), (unsigned)cdiv(g.Cop, g.L.cob), (unsigned)N);
+    return g;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C ABI
+extern "C" int fosvos_conv2d_plan(int N, int H, int W, int Ci, int Co, int k, int stride, fosvos_conv2d_plan_info *out) {
+    FOSVOS_REQUIRE(out, FOSVOS_E_ARG, "conv2d_plan: null output");
+    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, FOSVOS_E_ARG, "conv2d_plan: N=%d H=%d W=%d Ci=%d Co=%d", N, H,
+                   W, Ci, Co);
+    *out = fosvos_conv2d_plan_info{};
+    if (k == 7 && stride == 2 && Ci == 3) {  // the first layer: both of its forms
+        const FirstGeom v = first_geom(N, H, W, Co, FOSVOS_CONV_FP32_MATH), m = first_geom(N, H, W, Co, 0);
+        out->cob = v.L.cob;
+        out->threads = 256;
+        out->slices = 1;
+        out->workgroups = (int)(v.grid.x * v.grid.y * v.grid.z);
+        out->mfma_frag_blocks = m.mfma ? m.nfb : 0;
+        out->mfma_workgroups = m.mfma ? (int)(m.grid.x * m.grid.y * m.grid.z) : 0;
+        return FOSVOS_OK;
+    }
+    FOSVOS_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2), FOSVOS_E_SHAPE,
+                   "conv2d_plan: k=%d stride=%d (1 or 3, 1 or 2; or the 7x7 stride-2 first layer on 3 channels)", k, stride);
+    const Conv2dGeom g = conv2d_geom(N, H, W, Ci, Co, k, stride);
+    out->cob = g.L.slices > 1 ? 8 : g.L.cob;  // (sliced launches are only ever planned with 8-channel blocks)
+    out->threads = g.L.threads;
+    out->slices = g.L.slices;
+    out->workgroups = (int)(g.grid.x * g.grid.y);
+    return FOSVOS_OK;
+}
+
 extern "C" size_t fosvos_conv2d_packed_dwords(int out_ch, int in_ch, int k) {
     if (out_ch <= 0 || in_ch <= 0 || (k != 1 && k != 3)) return 0;
     return (size_t)(roundup(in_ch, 8) / 8) * k * k * 4 * roundup(out_ch, 8) + 64;  // + slack a partial block may read
@@ -802,14 +870,13 @@ extern "C" int fosvos_conv2d_fwd(const uint16_t *x, const uint32_t *w_packed, co
                    "conv2d_fwd: unknown flags 0x%x", flags);
     const bool f32 = flags & FOSVOS_CONV_OUT_F32;
     FOSVOS_REQUIRE(!(f32 && addend), FOSVOS_E_SHAPE, "conv2d_fwd: fp32 output with a residual operand");
-    const int P = k / 2, Ho = (H + 2 * P - k) / stride + 1, Wo = (W + 2 * P - k) / stride + 1;
-    const int Cop = roundup(Co, 8), cic = roundup(Ci, 8) / 8;
+    const Conv2dGeom geom = conv2d_geom(N, H, W, Ci, Co, k, stride);
+    const int Ho = geom.Ho, Wo = geom.Wo, Cop = geom.Cop, cic = geom.cic;
     FOSVOS_REQUIRE((int64_t)N * H * W * cic < (int64_t)1 << 31 && (int64_t)N * Ho * Wo * Cop < (int64_t)1 << 34, FOSVOS_E_ARG,
                    "conv2d_fwd: tensor too large for 32-bit tap offsets");
     FOSVOS_ENTER(device);
-    const int64_t npix = (int64_t)N * Ho * Wo;
-    const ConvLaunch L = plan_conv2d(npix, Cop, cic);
-    const dim3 grid((unsigned)cdiv(npix, L.threads), (unsigned)cdiv(Cop, L.cob));
+    const ConvLaunch L = geom.L;
+    const dim3 grid = geom.grid;
     const int relu = (flags & FOSVOS_CONV_RELU) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
     const uint4 *xv = reinterpret_cast<const uint4 *>(x), *av = reinterpret_cast<const uint4 *>(addend);
@@ -860,17 +927,17 @@ extern "C" int fosvos_conv7x7s2_first_fwd(const float *frame, const float *w_pac
     FOSVOS_REQUIRE((flags & ~(unsigned)(FOSVOS_CONV_RELU | FOSVOS_CONV_FP32_MATH)) == 0, FOSVOS_E_ARG,
                    "conv7x7s2_first_fwd: flags 0x%x", flags);
     FOSVOS_ENTER(device);
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, Cop = roundup(Co, 8);
     FOSVOS_REQUIRE(N < 65536, FOSVOS_E_ARG, "conv7x7s2_first_fwd: N=%d", N);
-    const int tiles_x = (int)cdiv(Wo, F7_TW), tiles_y = (int)cdiv(Ho, F7_TH);
+    const FirstGeom geom = first_geom(N, H, W, Co, flags);
+    const int Ho = geom.Ho, Wo = geom.Wo, Cop = geom.Cop, tiles_x = geom.tiles_x;
     const int relu = (flags & FOSVOS_CONV_RELU) ? 1 : 0;
-    if (!(flags & FOSVOS_CONV_FP32_MATH) && Cop <= 64) {  // bf16 MFMA form
+    if (geom.mfma) {  // bf16 MFMA form
         const uint4 *wimg = reinterpret_cast<const uint4 *>(w_packed + 147 * Cop + 64);
-        const dim3 g((unsigned)(tiles_x * tiles_y), 1, (unsigned)N);
+        const dim3 g = geom.grid;
 #define FOSVOS_GO(NFB)                                                                                                   \
     hipLaunchKernelGGL(k_conv7x7s2_first_mfma<NFB>, g, dim3(256), 0, (hipStream_t)stream, frame, wimg, bias, y, H, W, Ho, Wo, \
                        tiles_x, Cop, relu)
-        switch (f7_nc(Cop) / 16) {
+        switch (geom.nfb) {
             case 1: FOSVOS_GO(1); break;
             case 2: FOSVOS_GO(2); break;
             case 3: FOSVOS_GO(3); break;
@@ -880,8 +947,8 @@ extern "C" int fosvos_conv7x7s2_first_fwd(const float *frame, const float *w_pac
         FOSVOS_LAUNCH_CHECK();
         return 0;
     }
-    const ConvLaunch L = plan_conv2d((int64_t)N * Ho * Wo, Cop, 1);
-    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)cdiv(Cop, L.cob), (unsigned)N);
+    const ConvLaunch L = geom.L;
+    const dim3 grid = geom.grid;
     uint4 *yv = reinterpret_cast<uint4 *>(y);
 #define FOSVOS_GO(COB)                                                                                                \
     hipLaunchKernelGGL(k_conv7x7s2_first<COB>, grid, dim3(256), 0, (hipStream_t)stream, frame, w_packed, bias, yv, H, W, Ho, \

@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -69,6 +69,12 @@ class Conv3x3PlanInfo(ctypes.Structure):
     """fosvos_conv3x3_plan_info."""
     _fields_ = [("tile_h", c_int), ("tile_w", c_int), ("tile_co", c_int), ("k_splits", c_int), ("workgroups", c_int),
                 ("persistent", c_int)]
+
+
+class Conv2dPlanInfo(ctypes.Structure):
+    """fosvos_conv2d_plan_info."""
+    _fields_ = [("cob", c_int), ("threads", c_int), ("slices", c_int), ("workgroups", c_int), ("mfma_frag_blocks", c_int),
+                ("mfma_workgroups", c_int)]
 
 
 class ProfileRecord(ctypes.Structure):
@@ -175,6 +181,7 @@ SIGNATURES = {
     "fosvos_conv2d_bias_elems": (c_size_t, [c_int]),
     "fosvos_pack_conv2d_bn": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "fosvos_conv2d_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Conv2dPlanInfo)]),
     "fosvos_conv2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_uint, c_int, c_void_p]),
     "fosvos_conv7x7_packed_elems": (c_size_t, [c_int]),

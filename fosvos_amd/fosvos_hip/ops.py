@@ -774,6 +774,19 @@ def pack_conv2d_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn
     return packed, bias
 
 
+def conv2d_plan(n: int, h: int, w: int, ci: int, co: int, k: int, stride: int = 1, fp32_math: bool = False) -> dict:
+    """What fosvos_conv2d_fwd launches for this shape (host arithmetic only): {"cob", "threads", "slices", "workgroups"}.
+    k = 7, stride = 2, ci = 3: what fosvos_conv7x7s2_first_fwd launches - with fp32_math (or more than 64 channels) the same
+    keys for its vector-ALU form, else {"mfma_frag_blocks", "workgroups"} of the MFMA form."""
+    import ctypes
+    from . import Conv2dPlanInfo
+    info = Conv2dPlanInfo()
+    check(lib().fosvos_conv2d_plan(n, h, w, ci, co, k, stride, ctypes.byref(info)), "conv2d_plan")
+    if (k, stride, ci) == (7, 2, 3) and not fp32_math and info.mfma_frag_blocks:
+        return {"mfma_frag_blocks": info.mfma_frag_blocks, "workgroups": info.mfma_workgroups}
+    return {"cob": info.cob, "threads": info.threads, "slices": info.slices, "workgroups": info.workgroups}
+
+
 def conv2d_fwd(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, ci: int, co: int, k: int, stride: int = 1,
                relu: bool = False, addend: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
     """x: bf16 NHWC [N,H,W,ru8(ci)] -> bf16 (or fp32) NHWC [N,Ho,Wo,ru8(co)] = act(conv + bias + addend)."""

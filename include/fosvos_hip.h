@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 20
+#define FOSVOS_ABI_VERSION 21
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -424,6 +424,17 @@ int fosvos_pack_conv2d_bn(const float *w_oihw, int Co, int Ci, int k /* 1 or 3 *
  * stride 1 without addend only: the fp32 side maps the head reads). */
 int fosvos_conv2d_fwd(const uint16_t *x, const uint32_t *w_packed, const float *bias, const uint16_t *addend, void *y,
                       int N, int H, int W, int Ci, int Co, int k, int stride, unsigned flags, int device, void *stream);
+/* What fosvos_conv2d_fwd launches for a shape (host arithmetic only; test plumbing like fosvos_conv3x3_plan): output
+ * channels per thread (cob: 64, 32, 16 or 8), threads per K slice (64 or 256), K slices of a workgroup (1, 2, 4 or 8: the
+ * input-channel chunks of 8 are dealt round-robin to the slices) and workgroups.  The plan does not depend on the
+ * flags.  k = 7, stride = 2, Ci = 3 asks for fosvos_conv7x7s2_first_fwd instead: cob / threads / slices / workgroups are
+ * those of its FOSVOS_CONV_FP32_MATH form (which is also what more than 64 channels take), mfma_frag_blocks (16-channel
+ * fragment blocks, 1..4) and mfma_workgroups those of the default MFMA form (both 0 where it does not apply). */
+typedef struct fosvos_conv2d_plan_info {
+    int cob, threads, slices, workgroups;
+    int mfma_frag_blocks, mfma_workgroups;
+} fosvos_conv2d_plan_info;
+int fosvos_conv2d_plan(int N, int H, int W, int Ci, int Co, int k, int stride, fosvos_conv2d_plan_info *out);
 /* First layer: 7x7 stride 2 pad 3 on the fp32 NCHW frame (3 channels) + folded BatchNorm (+ ReLU) -> bf16 NHWC
  * [N,(H-1)/2+1,(W-1)/2+1,Cop].  Packed image (fosvos_conv7x7_packed_elems floats): fp32 [49*3][Cop], then the same
  * filter as bf16 MFMA fragments.  By default (Cop <= 64) the layer runs on the matrix cores with the frame rounded to

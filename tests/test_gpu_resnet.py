@@ -53,6 +53,9 @@ def _bn_params(c, g):
     (59, 16, 3, 1, False, False, False, True),    # side_prep: conv bias, no BatchNorm, fp32 NHWC out
 ])
 def test_conv2d_matches_torch(ci, co, k, stride, relu, with_bn, with_add, f32):
+    """BatchNorm fold + conv + residual + ReLU at one small map (2 x 19 x 27: every case lands on the 8-channel block with
+    64 threads and 1 to 8 slices).  The other launch classes of k_conv2d - 16, 32 and 64 channels per thread, 256 threads -
+    are covered class by class, against float64 and per element, in tests/test_gpu_resnet_classes.py."""
     from fosvos_hip import ops
     g = torch.Generator().manual_seed(ci * 131 + co * 7 + k + stride)
     n, h, w = 2, 19, 27
