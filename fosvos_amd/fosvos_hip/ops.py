@@ -1063,3 +1063,45 @@ def jf_counts(logits: torch.Tensor, gt: torch.Tensor, radius: Optional[int] = No
     check(L.fosvos_jf_counts(logits.data_ptr(), gt.data_ptr(), n, h, w, radius, out.data_ptr(), ws, wsn, dev, st), "jf_counts")
     _pe(e0, "jf_counts", 0.0, 5.0 * n * h * w)
     return out
+
+
+# ------------------------------------------------------------------------------------------ PNG files (png.hip)
+def png_capacity(h: int, w: int) -> int:
+    """Bytes ``png_encode`` reserves per frame: the layout's size bound (util/png_layout.max_file_bytes)."""
+    return int(lib().fosvos_png_capacity_bytes(1, int(h), int(w)))
+
+
+def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None,
+               lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fosvos_png_encode: uint8 [N,H,W] (``prob_bytes``' output) -> (buffer uint8 [N,capacity], lengths int32 [N]): frame n's
+    8-bit greyscale PNG file is ``buffer[n, :lengths[n]]``, in the layout util/png_layout.py states; the bytes behind it
+    are not written.  ``out`` (uint8 [N, >= png_capacity(H, W)]) and ``lengths`` (int32 [N]) may be views of a caller's
+    buffer.  Launched on the current stream, no synchronisation."""
+    _need_eval(bytes_u8, torch.uint8, "png_encode bytes")
+    if bytes_u8.dim() != 3 or bytes_u8.numel() == 0:
+        raise ValueError(f"png_encode: bytes must be a non-empty [N,H,W], got {tuple(bytes_u8.shape)}")
+    n, h, w = (int(v) for v in bytes_u8.shape)
+    L = lib()
+    cap = int(L.fosvos_png_capacity_bytes(n, h, w))
+    if out is None:
+        out = torch.empty((n, cap), dtype=torch.uint8, device=bytes_u8.device)
+    else:
+        _need_eval(out, torch.uint8, "png_encode out")
+        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cap:
+            raise ValueError(f"png_encode: out must be [{n}, >= {cap}], got {tuple(out.shape)}")
+    if lengths is None:
+        lengths = torch.empty((n,), dtype=torch.int32, device=bytes_u8.device)
+    else:
+        _need_eval(lengths, torch.int32, "png_encode lengths")
+        if tuple(lengths.shape) != (n,):
+            raise ValueError(f"png_encode: lengths must be {(n,)}, got {tuple(lengths.shape)}")
+    for t in (out, lengths):
+        if t.device != bytes_u8.device:
+            raise RuntimeError(f"png_encode: every tensor must be on {bytes_u8.device}, got one on {t.device}")
+    ws, wsn = _WS.get(L.fosvos_png_workspace_bytes(n, h, w), bytes_u8.device)
+    dev, st = _ctx(bytes_u8)
+    e0 = _pb()
+    check(L.fosvos_png_encode(bytes_u8.data_ptr(), n, h, w, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(), ws, wsn,
+                              dev, st), "png_encode")
+    _pe(e0, "png_encode", 0.0, 2.0 * n * h * w)
+    return out, lengths

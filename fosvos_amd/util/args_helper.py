@@ -3,7 +3,7 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --resident-train-set (offline only), --score (online only).
+--data-parallel, --resident-train-set (offline only), --score and --fast-test (online only).
 """
 import argparse
 from typing import List, Optional
@@ -42,6 +42,9 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--score', action='store_true',
                             help='score the test pass on the device (DAVIS 2016 J and F per sequence, scores.yml beside '
                                  'the PNGs)')
+        parser.add_argument('--fast-test', action='store_true',
+                            help='test pass in groups of frames with the PNG files encoded on the device (same pixels, '
+                                 'larger files of many IDAT chunks)')
     if not is_online:
         parser.add_argument('--resident-train-set', action='store_true',
                             help='decode the training set once, keep it on the GPU and flip / rescale each draw there '

@@ -5,7 +5,10 @@ no PNGs are written in that mode, as in the reference).
 
 ``test_scored`` (an extension: the reference leaves evaluation to an outside toolkit) is the same pass with the sigmoid,
 the byte stretch and the DAVIS 2016 J / F counts computed on the device beside the logits (fosvos_prob_bytes,
-fosvos_jf_counts); ``test`` itself keeps the reference's host path."""
+fosvos_jf_counts); ``test`` itself keeps the reference's host path.
+
+``test_fast`` (opt-in, ``--fast-test``) forwards the frames in groups, has the device encode the PNG files as well
+(fosvos_png_encode, layout: util/png_layout.py) and leaves the host nothing to do but write them."""
 import timeit
 from pathlib import Path
 from typing import Callable, Optional
@@ -24,6 +27,10 @@ log = get_logger(__file__)
 last_eval = {}
 # what the last call of test_scored() returned
 last_score = {}
+# what the last call of test_fast() did: {'n_frames', 'n_groups', 'group_sizes', 'seconds', host seconds per stage:
+# 'seconds_load' (waiting for the loader), 'seconds_issue' (upload, forward and encode calls), 'seconds_wait' (for the
+# device and the copy), 'seconds_write' (files), 'png_bytes'}
+last_fast = {}
 
 
 def bytescale(data: np.ndarray) -> np.ndarray:
@@ -171,6 +178,167 @@ def test_scored(net_provider, data_loader, save_dir: Path, annotations: Callable
              'seconds': time_for_all}
     log.info('Test {0}: {1} images, {2} scored, total test time {3} sec'.format(seq_name, len(fnames), int(keep.sum()),
                                                                                time_for_all))
+    last_score.clear()
+    last_score.update(score)
+    return score
+
+
+def _frame_groups(data_loader, group: int):
+    """The loader's minibatches, consecutive ones of one frame shape joined while they hold at most ``group`` frames."""
+    held, n_held = [], 0
+    for minibatch in data_loader:
+        n = int(minibatch['image'].shape[0])
+        if held and (n_held + n > group or minibatch['image'].shape[1:] != held[0]['image'].shape[1:]):
+            yield held
+            held, n_held = [], 0
+        held.append(minibatch)
+        n_held += n
+    if held:
+        yield held
+
+
+def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
+              seq_name: Optional[str] = None, forward_batch: int = 2) -> Optional[dict]:
+    """The test pass with the PNG files made on the device.  Up to ``group`` consecutive frames of one shape are uploaded
+    as one batch and forwarded ``forward_batch`` frames a call into one logit tensor.  Two frames a call is the largest
+    batch whose frames the engine computes exactly as it computes a frame alone (a batch runs as two chains of ceil(N/2)
+    and floor(N/2) frames, and a chain's tile plans and K splits depend on its frame count): the files hold the pixels of
+    the one-frame-a-call passes ``test`` and ``test_scored``, where a five-frame forward rounds its bf16 activations
+    differently and moves bytes by tens of steps on steep maps (``forward_batch=group`` selects that).
+    ``ops.prob_bytes`` and ``ops.png_encode`` turn the group's logits into complete PNG files (layout:
+    util/png_layout.py - the pixels ``test_scored`` writes, in a larger file of many IDAT chunks), ONE copy per group brings
+    the file buffer and the lengths to pinned host memory, and the host writes ``<save_dir>/<seq>/<fname>.png`` with plain
+    ``write`` calls - for the previous group, after the next group's forward pass has been issued.  The copy moves the
+    buffer at its capacity (the layout's size bound, about the stored size): the lengths are only known on the device, and
+    asking for them first would put a host synchronisation in front of every group's copy.
+    ``annotations`` (as for ``test_scored``): the J / F counts are taken on the device as well and the score dict of
+    ``test_scored`` is returned (and kept in ``last_score``); without it the pass returns None.
+    CPU logits take the host path: ``bytescale`` of the fp64 sigmoid, ``png_layout.encode``."""
+    from util import png_layout
+    if group < 1 or forward_batch < 1:
+        raise ValueError('test_fast: group and forward_batch must be at least 1, got {} and {}'.format(group, forward_batch))
+    log.info('Testing Network (fast)')
+    net = net_provider.network
+    n_frames = len(data_loader.dataset)
+    fnames, seqs, scored = [], [], []
+    counts_dev, counts_host, radius = None, np.zeros((n_frames, 6), dtype=np.int64), None
+    stores = {}      # (slot, n, h, w) -> (device bytes, host pinned bytes): two slots, a group's files are written one group later
+    pending = None   # (host bytes, n, capacity, copy-landed event, paths) of the group whose files are not written yet
+    stage = {'load': 0.0, 'issue': 0.0, 'wait': 0.0, 'write': 0.0}
+    group_sizes, png_bytes = [], 0
+
+    def write_files(paths, blobs):
+        for path, blob in zip(paths, blobs):
+            path.parent.mkdir(parents=True, exist_ok=True)
+            with open(str(path), 'wb') as fh:
+                fh.write(blob)
+
+    def retire(item):
+        nonlocal png_bytes
+        host, n, cap, landed, paths = item
+        t0 = timeit.default_timer()
+        landed.synchronize()
+        t1 = timeit.default_timer()
+        lengths = host[n * cap:n * cap + 4 * n].view(torch.int32).tolist()
+        data = host.numpy()
+        write_files(paths, [data[k * cap:k * cap + lengths[k]].data for k in range(n)])
+        png_bytes += sum(lengths)
+        stage['wait'] += t1 - t0
+        stage['write'] += timeit.default_timer() - t1
+
+    time_all_start = timeit.default_timer()
+    with torch.no_grad():
+        groups = iter(_frame_groups(data_loader, group))
+        while True:
+            t0 = timeit.default_timer()
+            minibatches = next(groups, None)
+            stage['load'] += timeit.default_timer() - t0
+            if minibatches is None:
+                break
+            t0 = timeit.default_timer()
+            images = minibatches[0]['image'] if len(minibatches) == 1 else torch.cat([m['image'] for m in minibatches])
+            inputs, = gpu_handler.cast_cuda_if_possible([images])
+            n = int(inputs.shape[0])
+            if n <= forward_batch:
+                logits = net.forward(inputs)[-1].detach().float().contiguous()
+            else:
+                logits = torch.cat([net.forward(inputs[k:k + forward_batch])[-1].detach().float()
+                                    for k in range(0, n, forward_batch)])
+            h, w = int(logits.shape[2]), int(logits.shape[3])
+            first = len(fnames)
+            if first + n > n_frames:
+                raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
+            group_sizes.append(n)
+            radius = davis_measures.default_radius(h, w)
+            gt = np.zeros((n, h, w), dtype=np.uint8) if annotations is not None else None
+            for minibatch in minibatches:
+                for seq, fname in zip(minibatch['seq_name'], minibatch['fname']):
+                    ann = _frame_annotation(annotations, seq, fname, h, w) if annotations is not None else None
+                    if ann is not None:
+                        gt[len(fnames) - first] = ann
+                    seqs.append(seq)
+                    fnames.append(fname)
+                    scored.append(ann is not None)
+            paths = [Path(save_dir) / seqs[k] / '{0}.png'.format(fnames[k]) for k in range(first, first + n)]
+            if logits.is_cuda:
+                from fosvos_hip import ops
+                if annotations is not None:
+                    if counts_dev is None:
+                        counts_dev = torch.zeros((n_frames, 6), dtype=torch.int32, device=logits.device)
+                    ops.jf_counts(logits, torch.from_numpy(gt).to(logits.device), radius, out=counts_dev[first:first + n])
+                cap = ops.png_capacity(h, w)
+                cap += -cap % 4  # the lengths sit behind the n file slots, in the same buffer: one copy brings both
+                key = (len(group_sizes) % 2, n, h, w)
+                if key not in stores:
+                    stores[key] = (torch.empty(n * cap + 4 * n, dtype=torch.uint8, device=logits.device),
+                                   torch.empty(n * cap + 4 * n, dtype=torch.uint8).pin_memory())
+                dev_store, host_store = stores[key]
+                ops.png_encode(ops.prob_bytes(logits), out=dev_store[:n * cap].view(n, cap),
+                               lengths=dev_store[n * cap:].view(torch.int32))
+                host_store.copy_(dev_store, non_blocking=True)
+                landed = torch.cuda.Event()
+                landed.record()
+                stage['issue'] += timeit.default_timer() - t0
+                if pending is not None:
+                    retire(pending)  # the previous group's files, while the device works on this group
+                pending = (host_store, n, cap, landed, paths)
+            else:
+                x = logits[:, 0].numpy().astype(np.float64)
+                blobs = []
+                for index in range(n):
+                    if annotations is not None:
+                        counts_host[first + index] = davis_measures.jf_counts_numpy(x[index] >= 0, gt[index], radius)
+                    blobs.append(png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x[index])))))
+                stage['issue'] += timeit.default_timer() - t0
+                t0 = timeit.default_timer()
+                write_files(paths, blobs)
+                png_bytes += sum(len(b) for b in blobs)
+                stage['write'] += timeit.default_timer() - t0
+        if pending is not None:
+            retire(pending)
+    if counts_dev is not None:
+        counts_host = counts_dev.cpu().numpy().astype(np.int64)
+    time_for_all = timeit.default_timer() - time_all_start
+    last_fast.clear()
+    last_fast.update(n_frames=len(fnames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
+                     seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],
+                     seconds_write=stage['write'], png_bytes=png_bytes)
+    log.info('Test {0}: {1} images in {2} groups, total test time {3} sec'.format(seq_name, len(fnames), len(group_sizes),
+                                                                                 time_for_all))
+    if annotations is None:
+        return None
+    counts_host = counts_host[:len(fnames)]
+    j, f = davis_measures.jf_from_counts(counts_host) if len(fnames) else (np.zeros(0), np.zeros(0))
+    keep = np.asarray(scored, dtype=bool)
+    j_stats = davis_measures.sequence_statistics(j[keep])
+    f_stats = davis_measures.sequence_statistics(f[keep])
+    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
+             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep],
+             'counts': [[int(v) for v in row] if k else None for row, k in zip(counts_host, keep)],
+             'J': [float(v) if k else None for v, k in zip(j, keep)],
+             'F': [float(v) if k else None for v, k in zip(f, keep)],
+             'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
+             'seconds': time_for_all}
     last_score.clear()
     last_score.update(score)
     return score

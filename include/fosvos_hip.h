@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 21
+#define FOSVOS_ABI_VERSION 22
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -398,6 +398,25 @@ int fosvos_prob_bytes(const float *logits, int N, int H, int W, float *minmax, u
 size_t fosvos_jf_workspace_bytes(int N, int H, int W);
 int fosvos_jf_counts(const float *logits, const uint8_t *gt, int N, int H, int W, int radius, int32_t *counts,
                      void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* ---- the probability PNGs, encoded on the device ------------------------------------------------------------------
+ * fosvos_png_encode: bytes uint8 [N,H,W] (what fosvos_prob_bytes writes) -> N standalone 8-bit greyscale PNG files: frame n's
+ * file is out[n * capacity .. n * capacity + lengths[n]), the bytes behind it are left as they were.  The layout is stated
+ * in numpy in util/png_layout.py (the tests compare byte for byte): the filtered stream (filter None) is cut into segments
+ * of 4096 bytes, each one fixed-Huffman deflate block (runs of a byte as distance-1 matches, everything else literals)
+ * closed by an empty stored block - or a stored block where that is shorter - in an IDAT chunk of its own; a last IDAT holds
+ * the final block and the Adler-32.  Any PNG reader decodes the files to the input bytes; they are larger than a
+ * level-6 zlib stream of the same image.
+ *   capacity   bytes reserved per frame in `out`, >= fosvos_png_capacity_bytes (the layout's size bound
+ *              65 + H (W+1) + 17 ceil(H (W+1) / 4096): no image encodes to more)
+ *   lengths    int32 [N]
+ *   workspace  fosvos_png_workspace_bytes, 4-byte aligned; what it and `out` held before does not matter
+ * H (W+1) <= 2^30.  Integer arithmetic only; two launches on `stream`.
+ * replaces: the PIL encoder behind scipy.misc.imsave of src/util/experiment_helper.py:64. */
+size_t fosvos_png_capacity_bytes(int N, int H, int W); /* per frame */
+size_t fosvos_png_workspace_bytes(int N, int H, int W);
+int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths,
+                      void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
