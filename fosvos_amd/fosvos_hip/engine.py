@@ -81,18 +81,29 @@ class PassFlags:
 class PackedWeights:
     """bf16 MFMA images of the 3x3 conv weights and the diagonal deconv filters, rebuilt only when
     the fp32 master changed (tracked by tensor version + storage pointer).  Also the per-model state of the passes: their
-    options (fixed when the model is built) and the flags a loop sets between passes."""
+    options (fixed when the model is built) and the flags a loop sets between passes.
+
+    Every entry is (key, image, the storage(s) the image was packed from).  The storage reference is what makes the address
+    half of the key safe: while an entry is cached its master's memory cannot be freed, so ``p.data = a; p.data = b`` cannot
+    bring the cached address back under other contents.  Writes that change neither version nor address (``p.data.mul_()``,
+    raw pointers) are invisible to any key: ``invalidate()`` (OSVOS_VGG.invalidate_weight_images) is for those."""
 
     def __init__(self, options: Optional[EngineOptions] = None) -> None:
         self.options = options if options is not None else EngineOptions.from_env()
         self.flags = PassFlags()
-        self._cache: Dict[str, Tuple[Tuple[int, int], object]] = {}
+        self._cache: Dict[str, Tuple[object, object, object]] = {}  # name -> (key, image, storage(s) packed from)
         self._uniform: Dict[str, bool] = {}  # deconv filter name -> its channel filters are identical (deconv_diag)
         self.arenas = ArenaPool()
 
     @staticmethod
     def _key(t: torch.Tensor) -> Tuple[int, int]:
         return (t.data_ptr(), t._version)
+
+    def invalidate(self) -> None:
+        """Forget every image and the head's uniform bits (the next pass rebuilds them); arenas, streams, the context, the
+        options and the flags stay."""
+        self._cache.clear()
+        self._uniform.clear()
 
     def small(self, name: str, parts: Sequence[torch.Tensor]) -> torch.Tensor:
         """Concatenation of a few tiny parameters (the four score_dsn layers) as one contiguous vector."""
@@ -101,7 +112,7 @@ class PackedWeights:
         if hit is not None and hit[0] == key:
             return hit[1]
         cat = torch.cat([t.detach().reshape(-1) for t in parts]).contiguous()
-        self._cache[name] = (key, cat)
+        self._cache[name] = (key, cat, tuple(t.untyped_storage() for t in parts))
         return cat
 
     def conv(self, name: str, w: torch.Tensor):
@@ -110,7 +121,7 @@ class PackedWeights:
         if hit is not None and hit[0] == key:
             return hit[1]
         packed = ops.pack_conv3x3_weights(w.detach(), True, True)
-        self._cache[name] = (key, packed)
+        self._cache[name] = (key, packed, w.untyped_storage())
         return packed
 
     def conv_many(self, named: Sequence[Tuple[str, torch.Tensor]]):
@@ -123,7 +134,7 @@ class PackedWeights:
         if stale:
             packed = ops.pack_conv3x3_weights_multi([w.detach() for _, w in stale])
             for (name, w), pk in zip(stale, packed):
-                self._cache[name] = (self._key(w), pk)
+                self._cache[name] = (self._key(w), pk, w.untyped_storage())
         return [self._cache[name][1] for name, _ in named]
 
     def deconv_diag(self, name: str, w: torch.Tensor) -> torch.Tensor:
@@ -140,13 +151,15 @@ class PackedWeights:
         idx = torch.arange(c, device=wd.device)
         diag = wd[idx, idx]  # [C,k,k]
         if c > 1:
-            off = wd.abs().sum() - diag.abs().sum()
-            if float(off) != 0.0:
+            # counted, not summed: a difference of two fp32 sums taken in different orders is not zero for a diagonal
+            # weight whose values are no dyadic fractions (per-channel scaled filters were refused for it)
+            off = torch.count_nonzero(wd) - torch.count_nonzero(diag)
+            if int(off) != 0:
                 raise NotImplementedError(
                     f"{name}: transposed-conv weight has off-diagonal (cross-channel) entries; the HIP head "
                     f"implements the per-channel (diagonal) form the reference initialises and freezes")
         diag = diag.permute(1, 2, 0).contiguous()  # [k,k,C]
-        self._cache[name] = (key, diag)
+        self._cache[name] = (key, diag, w.untyped_storage())
         # (the same sync as the off-diagonal check above, once per weight version): are the C channel filters identical?
         self._uniform[name] = bool((diag == diag[..., :1]).all().item())
         return diag

@@ -12,6 +12,7 @@ from typing import List, Optional
 
 import torch
 import torch.nn as nn
+from torch.nn.modules.batchnorm import _BatchNorm
 
 import ctypes
 
@@ -128,8 +129,10 @@ class _Block:
 
 
 class ResnetPlan:
-    """Device-side images of one net's weights; rebuilt when any parameter or buffer was written or moved, or the options
-    that shape the images (resnet_mfma, resnet_fuse_first) were replaced."""
+    """Device-side images of one net's weights; rebuilt when any parameter or buffer was written or moved, a BatchNorm eps
+    was changed, or the options that shape the images (resnet_mfma, resnet_fuse_first) were replaced.  A write that changes
+    neither a version counter nor an address (``p.data.mul_()``, raw pointers) is invisible here:
+    OSVOS_RESNET.invalidate_weight_images resets ``signature`` for those."""
 
     def __init__(self, options: Optional[EngineOptions] = None) -> None:
         self.options = options if options is not None else EngineOptions.from_env()
@@ -139,22 +142,28 @@ class ResnetPlan:
 
     def _signature(self, net: nn.Module):
         return (self.options.resnet_mfma, self.options.resnet_fuse_first) + tuple(
-            (t.data_ptr(), t._version) for t in list(net.parameters()) + list(net.buffers()))
+            (t.data_ptr(), t._version) for t in list(net.parameters()) + list(net.buffers())) + tuple(
+            m.eps for m in net.modules() if isinstance(m, _BatchNorm))
 
     # Walking the module tree for that signature costs 0.11-0.19 ms per call on the GPU box's host - as much as the device
     # needs for a whole 1080p frame of a thinned net.  So the walk is done once per packing; every later call re-checks the
     # recorded path instead: each module on it is still the child of its parent (a pruned block swapped in is seen), each
-    # tensor is still the attribute of its module, sits at the same address and has the same version counter.
+    # tensor is still the attribute of its module, sits at the same address and has the same version counter; each BatchNorm
+    # still has the eps that was folded into its image (an attribute, not a tensor: compared by value).
+    # Every watched tensor is recorded WITH its storage: the tensor object alone does not keep the memory `p.data = t` drops,
+    # and an address that is free can come back under other contents with the version counter unchanged.
     def _record(self, net: nn.Module) -> None:
-        links, params, bufs = [], [], []
+        links, params, bufs, eps = [], [], [], []
 
         def walk(m):
             for name, t in m._parameters.items():
                 if t is not None:
-                    params.append((m._parameters, name, t, t.data_ptr(), t._version))
+                    params.append((m._parameters, name, t, t.data_ptr(), t._version, t.untyped_storage()))
             for name, t in m._buffers.items():
                 if t is not None:
-                    bufs.append((m._buffers, name, t, t.data_ptr(), t._version))
+                    bufs.append((m._buffers, name, t, t.data_ptr(), t._version, t.untyped_storage()))
+            if isinstance(m, _BatchNorm):
+                eps.append((m, m.eps))
             for name, child in m._modules.items():
                 if child is not None:
                     links.append((m._modules, name, child))
@@ -162,7 +171,7 @@ class ResnetPlan:
             links.append((m._modules, None, len(m._modules)))
 
         walk(net)
-        self._links, self._watched = links, params + bufs
+        self._links, self._watched, self._eps = links, params + bufs, eps
 
     def _unchanged(self) -> bool:
         if self.signature is None or self.signature[:2] != (self.options.resnet_mfma, self.options.resnet_fuse_first):
@@ -170,8 +179,11 @@ class ResnetPlan:
         for d, name, child in self._links:
             if (len(d) != child) if name is None else (d.get(name) is not child):
                 return False
-        for d, name, t, ptr, ver in self._watched:
+        for d, name, t, ptr, ver, _storage in self._watched:
             if d.get(name) is not t or t._version != ver or t.data_ptr() != ptr:
+                return False
+        for m, eps in self._eps:
+            if m.eps != eps:
                 return False
         return True
 

@@ -94,6 +94,13 @@ class OSVOS_RESNET(nn.Module):
         (src/networks/osvos_resnet.py:42-68)."""
         return resnet_engine.forward(self, self._plan, x)
 
+    def invalidate_weight_images(self):
+        """Drop the packed (BatchNorm-folded) weight images: the next forward rebuilds the plan from the module tree.  The
+        plan notices a write by the tensor's version counter and address; call this after a write that changes neither -
+        ``p.data.mul_()``, a numpy alias, a kernel writing through ``data_ptr()`` (INTEGRATION.md has the table).  The
+        arena, the auxiliary stream and the execution context are untouched."""
+        self._plan.signature = None
+
     @property
     def options(self):
         """The model's fosvos_hip.options.EngineOptions (from the environment at construction); replace it, e.g. with
@@ -113,6 +120,7 @@ class OSVOS_RESNET(nn.Module):
     def __setstate__(self, state):
         self.__dict__.update(state)
         self._plan = resnet_engine.ResnetPlan()
+        self.invalidate_weight_images()
 
     # ------------------------------------------------------------------ structure / init (host side)
     @staticmethod

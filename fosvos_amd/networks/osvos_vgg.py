@@ -84,6 +84,14 @@ class OSVOS_VGG(nn.Module):
         if names:
             self._packs.conv_many([(n, P[n]) for n in names])
 
+    def invalidate_weight_images(self):
+        """Drop every cached weight image (bf16 MFMA images, score_dsn concatenations, deconv diagonals, the head's uniform
+        mask): the next pass rebuilds them from the fp32 masters.  The caches notice a write by the tensor's version counter
+        and address; call this after a write that changes neither - ``p.data.mul_()``, a numpy alias, a kernel writing through
+        ``data_ptr()`` - or bump ``torch.autograd.graph.increment_version(p)`` per tensor (INTEGRATION.md has the table).
+        Arenas, streams and the execution context are untouched."""
+        self._packs.invalidate()
+
     def join_gradients(self):
         """With ``defer_wgrad_join`` the weight-gradient kernels of a backward pass may still be running on the
         auxiliary stream when ``backward()`` returns; call this before reading ``p.grad`` (optimizer step,
@@ -157,6 +165,7 @@ class OSVOS_VGG(nn.Module):
     def __setstate__(self, state):
         self.__dict__.update(state)
         self._packs = engine.PackedWeights()
+        self.invalidate_weight_images()
 
     # ------------------------------------------------------------------ structure / init (host side)
     @staticmethod

@@ -908,3 +908,91 @@ def test_fused_sgd_matches_torch():
         o_hip.step()
         for pr, ph in zip(p_ref, p_hip):
             np.testing.assert_allclose(ph.detach().cpu().numpy(), pr.detach().numpy(), rtol=2e-6, atol=1e-7)
+
+
+def test_fused_sgd_table_follows_every_change():
+    """FusedSGD keeps a device-side table of pointers, lr and weight decay and re-sends it only when an entry differs; its
+    kernel writes through raw pointers, so it bumps the version counters by hand.  Six steps against CPU `torch.optim.SGD`
+    (same shapes and tolerance as test_fused_sgd_matches_torch), with between them everything that must reach the table:
+    an lr change, a weight_decay change, `zero_grad(set_to_none=True)` + gradients at new addresses, a resume
+    (`load_state_dict` of a deep copy: new momentum buffers), `add_param_group`, and a group whose lr goes 0 -> nonzero.
+    (7, 5) has numel % 4 != 0 and lives at a 4-byte-aligned, not 16-byte-aligned offset of a flat buffer, as does the gradient
+    of (64,): the scalar path of k_sgd.  Steps 0-1 write the gradients in place (same addresses: the table is NOT re-sent)."""
+    import copy
+    from fosvos_hip.sgd import FusedSGD
+    shapes = [(64, 3, 3, 3), (64,), (128, 64, 3, 3), (1, 64, 1, 1), (1,), (7, 5)]
+    g = torch.Generator().manual_seed(82)
+    p_ref = [torch.randn(s, generator=g).requires_grad_(True) for s in shapes]
+    p_hip = [p.detach().clone().to(DEV).requires_grad_(True) for p in p_ref[:5]]
+    flat_p = torch.zeros(64, device=DEV)
+    flat_p[1:36].copy_(p_ref[5].detach().reshape(-1).to(DEV))
+    p_hip.append(flat_p[1:36].view(7, 5).requires_grad_(True))
+    assert p_hip[5].is_leaf and p_hip[5].is_contiguous() and p_hip[5].data_ptr() % 16 == 4
+
+    def groups(ps):  # (ps[3] joins at step 4 through add_param_group)
+        return [{"params": ps[:2], "weight_decay": 2e-4}, {"params": ps[2:3], "lr": 2e-3},
+                {"params": ps[4:5], "lr": 0.0}, {"params": ps[5:], "lr": 1e-4, "weight_decay": 1e-2}]
+
+    o_ref = torch.optim.SGD(groups(p_ref), lr=1e-3, momentum=0.9)
+    o_hip = FusedSGD(groups(p_hip), lr=1e-3, momentum=0.9)
+    flats, retired = [], []
+
+    def new_grads():
+        for i, (pr, ph) in enumerate(zip(p_ref, p_hip)):
+            gr = torch.randn(pr.shape, generator=g)
+            pr.grad = gr.clone()
+            if i == 1:  # 4-byte-aligned view into a flat buffer
+                flats.append(torch.zeros(pr.numel() + 4, device=DEV))
+                ph.grad = flats[-1][1:1 + pr.numel()].view(pr.shape)
+                ph.grad.copy_(gr.to(DEV))
+                assert ph.grad.data_ptr() % 16 == 4
+            else:
+                ph.grad = gr.clone().to(DEV)
+
+    new_grads()
+    for step in range(6):
+        if step == 1:
+            for opt in (o_ref, o_hip):
+                opt.param_groups[0]["lr"] *= 0.1
+        if step == 2:
+            for opt in (o_ref, o_hip):
+                opt.param_groups[3]["weight_decay"] = 5e-3
+        if step == 3:
+            o_ref.load_state_dict(copy.deepcopy(o_ref.state_dict()))
+            o_hip.load_state_dict(copy.deepcopy(o_hip.state_dict()))
+        if step == 4:
+            o_ref.add_param_group({"params": [p_ref[3]], "lr": 5e-4})
+            o_hip.add_param_group({"params": [p_hip[3]], "lr": 5e-4})
+        if step == 5:
+            for opt in (o_ref, o_hip):
+                opt.param_groups[2]["lr"] = 1e-3
+        if step in (0, 1):  # same gradient tensors, new values
+            if step == 1:
+                for pr, ph in zip(p_ref, p_hip):
+                    gr = torch.randn(pr.shape, generator=g)
+                    pr.grad.copy_(gr)
+                    ph.grad.copy_(gr.to(DEV))
+        else:  # new gradient tensors at new addresses (the old ones stay allocated, so no address can come back)
+            retired += [ph.grad for ph in p_hip]
+            o_ref.zero_grad(set_to_none=True)
+            o_hip.zero_grad(set_to_none=True)
+            owned = {id(p) for grp in o_hip.param_groups for p in grp["params"]}  # (p_hip[3] joins at step 4)
+            assert all(ph.grad is None for ph in p_hip if id(ph) in owned)
+            new_grads()
+            assert {ph.grad.data_ptr() for ph in p_hip}.isdisjoint({t.data_ptr() for t in retired})
+        was = [(ph.detach().clone(), ph._version) for ph in p_hip]
+        o_ref.step()
+        o_hip.step()
+        torch.cuda.synchronize()
+        stepped = {id(p) for grp in o_hip.param_groups for p in grp["params"]}
+        for i, (pr, ph) in enumerate(zip(p_ref, p_hip)):
+            np.testing.assert_allclose(ph.detach().cpu().numpy(), pr.detach().numpy(), rtol=2e-6, atol=1e-7,
+                                       err_msg=f"step {step}, parameter {i}")
+            changed = not torch.equal(ph.detach(), was[i][0])
+            moves = id(ph) in stepped and not (i == 4 and step < 5)  # (the lr-0 group until its lr is set)
+            assert changed == moves, (step, i)
+            if changed:
+                assert ph._version > was[i][1], f"step {step}: parameter {i} changed without a version bump"
+        assert float(flat_p[0]) == 0.0 and not flat_p[36:].any()  # the misaligned slice's neighbours are untouched
+        for f in flats:
+            assert float(f[0]) == 0.0 and not f[65:].any()

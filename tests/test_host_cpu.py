@@ -338,3 +338,94 @@ def test_loss_log_keeps_iteration_order():
                 running = 0.0
     assert len(want) == 6 and log.loss_tr == [v for v, _ in want]
     assert writer.calls == [("data/total_loss_epoch", v, ep) for v, ep in want]
+
+
+def test_which_weight_writes_torch_counts():
+    """The torch behaviour the weight-image caches rest on ("Which weight writes the caches see"): they key
+    every image by `(data_ptr(), _version)` of its fp32 master.  Row 1 of the table there: these writes bump the version and
+    keep the address.  Row 2: in-place writes through `.data` or a numpy alias do neither - nothing can see them, the caller
+    says so (`increment_version` / `invalidate_weight_images()`).  Row 3: `p.data = t` moves the address without a bump.  A
+    torch upgrade that changes a row fails here, on the CPU, instead of as stale weights on the GPU."""
+    import torch.nn as nn
+    m = nn.Conv2d(4, 4, 3)
+    p = m.weight
+
+    def probe(write):
+        version, address = p._version, p.data_ptr()
+        write()
+        return p._version - version, p.data_ptr() == address
+
+    def no_grad_mul():
+        with torch.no_grad():
+            p.mul_(1.5)
+
+    def no_grad_copy():
+        with torch.no_grad():
+            p.copy_(torch.ones_like(p))
+
+    def sgd_step():
+        opt = torch.optim.SGD(m.parameters(), lr=0.1, momentum=0.9)
+        p.grad, m.bias.grad = torch.ones_like(p), torch.ones_like(m.bias)
+        opt.step()
+
+    def numpy_alias():
+        p.detach().numpy()[...] = 3.0
+
+    seen = {"no_grad mul_": no_grad_mul, "no_grad copy_": no_grad_copy, "detach().add_": lambda: p.detach().add_(1.0),
+            "nn.init.normal_": lambda: nn.init.normal_(p, 0.0, 0.1), "nn.init.constant_": lambda: nn.init.constant_(p, 0.5),
+            "load_state_dict": lambda: m.load_state_dict({k: v * 2 for k, v in m.state_dict().items()}),
+            "optim.SGD.step": sgd_step, "increment_version": lambda: torch.autograd.graph.increment_version(p)}
+    for name, write in seen.items():
+        bumps, same_address = probe(write)
+        assert bumps >= 1 and same_address, (name, bumps, same_address)
+    unseen = {".data.mul_": lambda: p.data.mul_(2.0), ".data.copy_": lambda: p.data.copy_(torch.ones_like(p)),
+              "numpy alias": numpy_alias}
+    for name, write in unseen.items():
+        before = p.detach().clone()
+        bumps, same_address = probe(write)
+        assert not torch.equal(p.detach(), before), name                # the write did land ...
+        assert bumps == 0 and same_address, (name, bumps, same_address)  # ... and left no trace
+    keep = p.data  # (the old storage stays allocated, so the new one cannot take its address)
+    bumps, same_address = probe(lambda: setattr(p, "data", torch.zeros_like(p)))
+    assert bumps == 0 and not same_address and keep.data_ptr() != p.data_ptr()
+
+
+def test_invalidate_weight_images_is_part_of_both_modules():
+    """The public way to say "my weights changed behind torch's back": drops the images, keeps arenas and options; a module
+    that comes out of a pickle starts without images."""
+    import pickle
+    from networks.osvos_resnet import OSVOS_RESNET
+    from networks.osvos_vgg import OSVOS_VGG
+    net = OSVOS_VGG(pretrained=0)
+    packs, arenas, options = net._packs, net._packs.arenas, net.options
+    w = net.stages[1][1].weight
+    packs._cache["probe"] = ((w.data_ptr(), w._version), None, w.untyped_storage())
+    packs._uniform["upscale.0.weight"] = True
+    net.invalidate_weight_images()
+    assert net._packs is packs and packs.arenas is arenas and net.options is options
+    assert not packs._cache and not packs._uniform
+    assert not pickle.loads(pickle.dumps(net))._packs._cache
+    res = OSVOS_RESNET(pretrained=False, scale_down_exponent=3)
+    plan, options = res._plan, res.options
+    plan.signature = ("stale",)
+    res.invalidate_weight_images()
+    assert res._plan is plan and plan.signature is None and res.options is options
+    assert pickle.loads(pickle.dumps(res))._plan.signature is None
+
+
+def test_deconv_diagonal_check_counts_instead_of_summing():
+    """`PackedWeights.deconv_diag` refuses a transposed-conv weight with cross-channel entries.  The check must be exact: as a
+    difference of two fp32 sums taken in different orders it came out nonzero for a purely diagonal weight whose values are
+    no dyadic fractions (per-channel scaled bilinear filters: -1.2e-4), and such a weight was refused."""
+    from fosvos_hip import engine
+    packs = engine.PackedWeights()
+    w = O.bilinear_deconv_weight(16, 16) * (1.0 + 0.1 * torch.arange(16.0)).view(16, 1, 1, 1)
+    diag = packs.deconv_diag("upscale.2.weight", w)
+    assert tuple(diag.shape) == (16, 16, 16) and packs._uniform["upscale.2.weight"] is False
+    assert torch.equal(diag[:, :, 5], w[5, 5])
+    packs.deconv_diag("upscale.1.weight", O.bilinear_deconv_weight(16, 8))
+    assert packs._uniform["upscale.1.weight"] is True
+    w2 = w.clone()
+    w2[0, 1, 0, 0] = 1e-30  # far below the rounding of any sum
+    with pytest.raises(NotImplementedError, match="off-diagonal"):
+        packs.deconv_diag("upscale.2.weight", w2)
