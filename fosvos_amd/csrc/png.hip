@@ -19,6 +19,17 @@
 //                  the Adler-32 combined over all segments, the final IDAT, IEND and the file length.
 // Run boundaries across the 256 threads come from a max-scan (start of the run entering a thread's bytes) and a reverse
 // min-scan (end of the run leaving them).  LDS: 4 KB segment + 4.1 KB chunk + 1 KB CRC table + scan scratch.
+//
+// fosvos_png_encode_mode(huffman = 1) runs the <true> instantiations of the same two kernels, which add a third form of a
+// segment: a dynamic-Huffman block (BTYPE = 10) with a literal/length code fitted to the segment's tokens (png_layout.py
+// states it: two-queue Huffman construction over the symbols sorted by (count, symbol), counts halved while the tree is
+// deeper than 15, canonical codes, HDIST = 0, a fixed code-length code, zero runs as symbols 17 / 18).
+//   measure  histogram of the token symbols (LDS atomics), rank sort by (count << 9 | symbol), the merge by one lane, depths
+//            by a walk to the root per leaf; the fitted block's bit count; the shortest of {fitted, fixed, stored} wins
+//            (fixed or stored on a tie) and, where it is the fitted one, the 286 lengths go to the workspace
+//   emit     canonical codes from the lengths (a ballot per code length gives a symbol's rank among its equals), the
+//            header, the code-length sequence (zero runs from a 320-bit mask of the non-zero lengths), the tokens
+//            recoded, the end-of-block code; chunk length, CRC and copy-out as for the other forms
 #include "common.hpp"
 
 using namespace fosvos;
@@ -27,7 +38,22 @@ namespace {
 constexpr int kSeg = 4096, kPngThreads = 256, kPer = kSeg / kPngThreads;  // 16 bytes a thread: one ds_read_b128
 constexpr int kChunkWords = (3 + 12 + 2 + 5 + kSeg + 3) / 4 + 1;
 constexpr uint32_t kCrcPoly = 0xedb88320u, kAdlerMod = 65521u, kStoredFlag = 0x80000000u;
-constexpr int kWsWords = 4;  // per segment: chunk data length | stored flag, adler a, adler b, unused
+constexpr int kWsWords = 4;  // per segment: chunk data length | stored flag, adler a, adler b, form (fitted mode)
+// the fitted form: 286 literal/length symbols (padded to 288: whole dwords), code lengths <= 15 bits; behind the N * S
+// records of a fitted-mode workspace come N * S times kLenWords words of code lengths, one byte a symbol
+constexpr int kLitLen = 286, kLitPad = 288, kLenWords = kLitPad / 4, kEob = 256, kMaxBits = 15, kZeroRun = 138;
+constexpr uint32_t kNoToken = kLitPad - 1;
+constexpr uint32_t kFormFixed = 0, kFormStored = 1, kFormFitted = 2;
+// code-length code: bits of symbol 0..18 (png_layout.CL_LENGTHS), written in the order of RFC 1951 3.2.7 with HCLEN = 19
+constexpr int kClBits[19] = {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 5, 5, 5, 5, 5, 5, 4, 4};
+constexpr int kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+constexpr unsigned long long cl_header_bits() {
+    unsigned long long v = 0;
+    for (int i = 0; i < 19; ++i) v |= (unsigned long long)kClBits[kClOrder[i]] << (3 * i);
+    return v;
+}
+constexpr unsigned long long kClHeader = cl_header_bits();  // the 57 bits behind HLIT, HDIST, HCLEN
+constexpr uint32_t kFitHeaderBits = 3 + 5 + 5 + 4 + 57;
 static_assert(kPer == 16, "a thread reads its bytes as one uint4");
 
 inline int64_t png_stream_bytes(int H, int W) { return (int64_t)H * ((int64_t)W + 1); }
@@ -66,6 +92,20 @@ struct PngShared {
     uint8_t small[72];
 };
 
+// what the fitted form needs beside PngShared
+struct PngFit {
+    uint32_t hist[kLitPad];                                // symbol counts
+    __attribute__((aligned(16))) uint32_t key[kLitPad];    // count << 9 | symbol; ~0 for an unused symbol
+    uint32_t lw[kLitPad], iw[kLitPad];                     // weights: leaves in sorted order, merged nodes in the order made
+    uint16_t lpar[kLitPad], ipar[kLitPad], order[kLitPad]; // parents (merged-node numbers); sorted place -> symbol
+    uint32_t tab[kLitPad];                                 // emit: code, bit-reversed | length << 16
+    __attribute__((aligned(16))) uint8_t len[kLitPad];     // code lengths
+    unsigned long long nz[5];                              // bit p: position p of the code-length sequence is not 0
+    uint32_t cnt[5][16];                                   // symbols of each length in each 64-symbol chunk
+    uint32_t next[16];                                     // first code of each length
+    uint32_t deepest;
+};
+
 __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wave) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -96,8 +136,13 @@ __device__ __forceinline__ int block_scan_max(int v, uint32_t *wave) {
     for (int i = 0; i < wv; ++i) v = max(v, (int)wave[i]);
     return v;
 }
+// kFresh (the fitted kernels' late scans): the lane number passes through an empty asm, so the six `lane >= o` masks are
+// taken anew where they are used; shared with the first scan of the kernel they stay alive, in twelve SGPRs, all the way.
+template <bool kFresh = false>
 __device__ __forceinline__ uint32_t block_scan_sum(uint32_t v, uint32_t *wave) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    if constexpr (kFresh) asm volatile("" : "+v"(lane));
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t u = __shfl_up(v, o, 64);
@@ -134,8 +179,11 @@ __device__ __forceinline__ void load_segment(const uint8_t *__restrict__ img, in
 
 // The tokens of this thread's 16 bytes: code[j] / nb[j] = the bits position 16 tid + j adds to the fixed-Huffman block (LSB
 // first; 0 bits where a match that started earlier covers the byte).  Returns the thread's bit total.
+// kFitted: tok[j] = the token's literal/length symbol | number of extra bits << 9 | extra bits << 12 | 1 << 17 for a match;
+// kNoToken (a padding symbol whose count and code length stay 0) where no token starts.
+template <bool kFitted>
 __device__ __forceinline__ uint32_t thread_tokens(PngShared &sh, int n, uint32_t (&code)[kPer], uint32_t (&nb)[kPer],
-                                                  uint32_t (&bytes)[kPer]) {
+                                                  uint32_t (&bytes)[kPer], uint32_t (&tok)[kPer]) {
     const int tid = threadIdx.x, p0 = tid * kPer;
     const uint4 v = *reinterpret_cast<const uint4 *>(sh.seg + p0);
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -190,12 +238,191 @@ __device__ __forceinline__ uint32_t thread_tokens(PngShared &sh, int n, uint32_t
         const uint32_t m_code = (__brev(sym_c) >> (32u - sym_bits)) | (extra << sym_bits);
         code[j] = literal ? __brev(lit_c) >> (32u - lit_bits) : (len ? m_code : 0u);
         nb[j] = literal ? lit_bits : (len ? sym_bits + eb + 5u : 0u);  // (+ the distance code of 1: five zero bits)
+        if constexpr (kFitted) {
+            tok[j] = literal ? b : (len ? sym | (eb << 9) | (extra << 12) | (1u << 17) : kNoToken);
+            // (taken here, in a VGPR: left to sink to its use behind the barriers, it keeps sixteen pairs of lane masks alive)
+            asm volatile("" : "+v"(tok[j]));
+        }
         total += nb[j];
     }
     return total;
 }
 
+// ------------------------------------------------------------------------------------------------- the fitted form
+// OR up to 32 bits into the chunk at bit `pos`
+__device__ __forceinline__ void or_bits(uint32_t *words, uint32_t pos, uint32_t v) {
+    const unsigned long long acc = (unsigned long long)v << (pos & 31u);
+    if ((uint32_t)acc) atomicOr(&words[pos >> 5], (uint32_t)acc);
+    if ((uint32_t)(acc >> 32)) atomicOr(&words[(pos >> 5) + 1], (uint32_t)(acc >> 32));
+}
+
+// f.hist (counts of the used symbols, at least two) -> f.len, by all 256 threads.  Ends in a barrier.
+__device__ __forceinline__ void fitted_lengths(PngFit &f) {
+    const int tid = threadIdx.x;
+    for (;;) {
+        for (int s = tid; s < kLitPad; s += kPngThreads) {
+            const uint32_t c = s < kLitLen ? f.hist[s] : 0u;
+            f.key[s] = c ? (c << 9 | (uint32_t)s) : 0xffffffffu;
+            f.len[s] = 0;
+        }
+        if (tid == 0) f.deepest = 0;
+        __syncthreads();
+        // rank sort: a symbol's place is the number of smaller keys (keys of used symbols are distinct)
+        const uint32_t my0 = f.key[tid], my1 = tid + kPngThreads < kLitPad ? f.key[tid + kPngThreads] : 0xffffffffu;
+        uint32_t r0 = 0, r1 = 0, m = 0;
+        for (int i = 0; i < kLitPad / 4; ++i) {
+            const uint4 k = reinterpret_cast<const uint4 *>(f.key)[i];
+            r0 += (k.x < my0) + (k.y < my0) + (k.z < my0) + (k.w < my0);
+            r1 += (k.x < my1) + (k.y < my1) + (k.z < my1) + (k.w < my1);
+            m += (k.x != 0xffffffffu) + (k.y != 0xffffffffu) + (k.z != 0xffffffffu) + (k.w != 0xffffffffu);
+        }
+        if (my0 != 0xffffffffu) f.lw[r0] = my0 >> 9, f.order[r0] = (uint16_t)tid;
+        if (my1 != 0xffffffffu) f.lw[r1] = my1 >> 9, f.order[r1] = (uint16_t)(tid + kPngThreads);
+        __syncthreads();
+        // the merge, a serial chain of m - 1 steps: one lane.  Heads of the two queues in registers; ~0 = queue empty.
+        if (tid == 0) {
+            uint32_t li = 0, ii = 0, wl = f.lw[0], wi = 0xffffffffu;
+            for (uint32_t k = 0; k + 1 < m; ++k) {
+                uint32_t w = 0;
+                for (int pick = 0; pick < 2; ++pick) {
+                    if (wl <= wi) {  // (a tie goes to the leaf)
+                        w += wl;
+                        f.lpar[li++] = (uint16_t)k;
+                        wl = li < m ? f.lw[li] : 0xffffffffu;
+                    } else {
+                        w += wi;
+                        f.ipar[ii++] = (uint16_t)k;
+                        wi = ii < k ? f.iw[ii] : 0xffffffffu;
+                    }
+                }
+                f.iw[k] = w;
+                if (ii == k) wi = w;  // the new node is the head of a queue that was empty
+            }
+        }
+        __syncthreads();
+        // a leaf's depth: steps to the root (node m - 2)
+        for (uint32_t i = tid; i < m; i += kPngThreads) {
+            uint32_t d = 1, p = f.lpar[i];
+            while (p != m - 2u) p = f.ipar[p], ++d;
+            f.len[f.order[i]] = (uint8_t)d;
+            atomicMax(&f.deepest, d);
+        }
+        __syncthreads();
+        if (f.deepest <= (uint32_t)kMaxBits) return;
+        __syncthreads();  // (everyone has read `deepest`)
+        for (int s = tid; s < kLitLen; s += kPngThreads) f.hist[s] = (f.hist[s] + 1u) >> 1;
+        __syncthreads();
+    }
+}
+
+// The code-length sequence of f.len: positions 0 .. n_lit - 1 are the literal/length lengths up to the last used symbol,
+// position n_lit the one distance length (1).  This thread's positions are tid and 256 + tid: hc / hn = their bits (LSB
+// first; 0 bits inside a zero run that an earlier position encodes), hoff = the bit offsets in the block.  Returns the
+// bits of header + sequence.  Zero runs: 18 while >= 11 zeros are left, 17 for 3..10, else plain zeros.
+__device__ __forceinline__ uint32_t fitted_header(PngFit &f, uint32_t *wave, uint32_t (&hc)[2], uint32_t (&hn)[2],
+                                                  uint32_t (&hoff)[2], uint32_t &n_lit) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t l[2] = {f.len[tid], tid < kLitLen - kPngThreads ? (uint32_t)f.len[kPngThreads + tid] : 0u};
+    const unsigned long long b0 = __ballot(l[0] != 0u), b1 = __ballot(l[1] != 0u);
+    if (lane == 0) {
+        f.nz[wv] = b0;
+        // (the end of block, symbol 256, is always used: b1 != 0)  bit n_lit - 256: the distance length
+        if (wv == 0) f.nz[4] = b1 | (2ull << (63 - __clzll((long long)b1)));
+    }
+    __syncthreads();
+    n_lit = (uint32_t)(kPngThreads + 63 - __clzll((long long)f.nz[4]));
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t p = (uint32_t)(h * kPngThreads + tid);
+        const uint32_t len = p == n_lit ? 1u : l[h];
+        uint32_t sym = len, xv = 0, xb = 0;
+        bool emits = p <= n_lit;
+        {
+            // the zero run around p: behind the last non-zero position below p, up to the first one above (bit n_lit is
+            // set: there is one).  Selects over the five mask words, no loops of data-dependent length.
+            const int pw = (int)(p >> 6);
+            const unsigned long long lo = (1ull << (p & 63u)) - 1ull, hi = ~((2ull << (p & 63u)) - 1ull);
+            int start = 0, end = 0;
+#pragma unroll 1
+            for (int w = 0; w < 5; ++w) {
+                const unsigned long long c = f.nz[w] & (w < pw ? ~0ull : (w == pw ? lo : 0ull));
+                start = c ? w * 64 + 64 - __clzll((long long)c) : start;
+            }
+#pragma unroll 1
+            for (int w = 4; w >= 0; --w) {
+                const unsigned long long c = f.nz[w] & (w > pw ? ~0ull : (w == pw ? hi : 0ull));
+                end = c ? w * 64 + __ffsll((long long)c) - 1 : end;
+            }
+            const int k = (int)p - start, blk = k / kZeroRun, off = k - blk * kZeroRun, rem = end - start - blk * kZeroRun;
+            const bool zero = emits && len == 0u, r18 = zero && rem >= 11, r17 = zero && !r18 && rem >= 3;
+            emits = emits && (!(r18 || r17) || off == 0);
+            sym = r18 ? 18u : (r17 ? 17u : sym);
+            xv = r18 ? (uint32_t)min(rem, kZeroRun) - 11u : (r17 ? (uint32_t)rem - 3u : 0u);
+            xb = r18 ? 7u : (r17 ? 3u : 0u);
+        }
+        // the canonical codes of kClBits: 4 bits 0..12 for symbols 0..10, 17, 18; 5 bits 26..31 for 11..16
+        const bool five = sym >= 11u && sym <= 16u;
+        const uint32_t c = five ? 15u + sym : (sym >= 17u ? sym - 6u : sym), bits = five ? 5u : 4u;
+        hc[h] = emits ? (__brev(c) >> (32u - bits)) | (xv << bits) : 0u;
+        hn[h] = emits ? bits + xb : 0u;
+    }
+    const uint32_t s0 = block_scan_sum<true>(hn[0], wave);
+    const uint32_t t0 = wave[0] + wave[1] + wave[2] + wave[3];
+    const uint32_t s1 = block_scan_sum<true>(hn[1], wave);
+    const uint32_t t1 = wave[0] + wave[1] + wave[2] + wave[3];
+    hoff[0] = kFitHeaderBits + s0 - hn[0];
+    hoff[1] = kFitHeaderBits + t0 + s1 - hn[1];
+    __syncthreads();  // (`wave` is free again)
+    return kFitHeaderBits + t0 + t1;
+}
+
+// f.len -> f.tab: canonical codes (RFC 1951 3.2.2), bit-reversed for LSB-first output.  A symbol's code is the first code
+// of its length + the number of smaller symbols of that length: a ballot per length, counts per 64-symbol chunk.
+__device__ __forceinline__ void fitted_codes(PngFit &f) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t l0 = f.len[tid], l1 = tid < kLitLen - kPngThreads ? (uint32_t)f.len[kPngThreads + tid] : 0u;
+    unsigned long long mine0 = 0, mine1 = 0;
+#pragma unroll 1
+    for (uint32_t b = 1; b <= (uint32_t)kMaxBits; ++b) {
+        const unsigned long long m0 = __ballot(l0 == b), m1 = __ballot(l1 == b);
+        mine0 = l0 == b ? m0 : mine0;
+        mine1 = l1 == b ? m1 : mine1;
+        if (lane == 0) {
+            f.cnt[wv][b] = (uint32_t)__popcll(m0);
+            if (wv == 0) f.cnt[4][b] = (uint32_t)__popcll(m1);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t code = 0, before = 0;
+        for (int b = 1; b <= kMaxBits; ++b) {
+            code = (code + before) << 1;
+            f.next[b] = code;
+            before = f.cnt[0][b] + f.cnt[1][b] + f.cnt[2][b] + f.cnt[3][b] + f.cnt[4][b];
+        }
+    }
+    __syncthreads();
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    uint32_t t = 0;
+    if (l0) {
+        uint32_t r = (uint32_t)__popcll(mine0 & lower);
+        for (int c = 0; c < wv; ++c) r += f.cnt[c][l0];
+        t = (__brev(f.next[l0] + r) >> (32u - l0)) | (l0 << 16);
+    }
+    f.tab[tid] = t;
+    if (tid < kLitPad - kPngThreads) {  // (wave 0)
+        t = 0;
+        if (l1) {
+            const uint32_t r = (uint32_t)__popcll(mine1 & lower) + f.cnt[0][l1] + f.cnt[1][l1] + f.cnt[2][l1] + f.cnt[3][l1];
+            t = (__brev(f.next[l1] + r) >> (32u - l1)) | (l1 << 16);
+        }
+        f.tab[kPngThreads + tid] = t;
+    }
+    __syncthreads();
+}
+
 // grid (segments, N)
+template <bool kFitted>
 __global__ __launch_bounds__(kPngThreads) void k_png_measure(const uint8_t *__restrict__ img, int H, int W,
                                                             uint32_t *__restrict__ ws) {
     __shared__ PngShared sh;
@@ -203,8 +430,8 @@ __global__ __launch_bounds__(kPngThreads) void k_png_measure(const uint8_t *__re
     const int n = (int)min((uint32_t)kSeg, n_total - seg * kSeg);
     img += (int64_t)blockIdx.y * H * W;
     load_segment(img, W, seg, n, sh);
-    uint32_t code[kPer], nb[kPer], bytes[kPer];
-    const uint32_t bits = block_sum(thread_tokens(sh, n, code, nb, bytes), sh.wave);
+    uint32_t code[kPer], nb[kPer], bytes[kPer], tok[kPer];
+    const uint32_t bits = block_sum(thread_tokens<kFitted>(sh, n, code, nb, bytes, tok), sh.wave);
     uint32_t a = 0, b = 0;
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
@@ -216,14 +443,37 @@ __global__ __launch_bounds__(kPngThreads) void k_png_measure(const uint8_t *__re
     }
     a = block_sum(a, sh.wave);
     b = block_sum(b, sh.wave);
+    const uint32_t fixed_len = (3u + bits + 7u + 3u + 7u) / 8u + 4u, stored_len = 5u + (uint32_t)n;
+    const bool stored = fixed_len > stored_len;
+    uint32_t len = stored ? stored_len : fixed_len, form = stored ? kFormStored : kFormFixed;
+    if constexpr (kFitted) {
+        __shared__ PngFit fit;
+        for (int s = threadIdx.x; s < kLitPad; s += kPngThreads) fit.hist[s] = s == kEob ? 1u : 0u;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+            if (tok[j] != kNoToken) atomicAdd(&fit.hist[tok[j] & 511u], 1u);
+        __syncthreads();
+        fitted_lengths(fit);
+        uint32_t tb = 0;  // a token: its code, its extra bits, and for a match the distance code of 1 bit
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) tb += fit.len[tok[j] & 511u] + ((tok[j] >> 9) & 7u) + (tok[j] >> 17);
+        tb = block_sum(tb, sh.wave);
+        uint32_t hc[2], hn[2], hoff[2], n_lit;
+        const uint32_t head = fitted_header(fit, sh.wave, hc, hn, hoff, n_lit);
+        const uint32_t fitted_len = (head + tb + fit.len[kEob] + 3u + 7u) / 8u + 4u;
+        if (fitted_len < len) {  // (a tie stays with the fixed / stored choice)
+            len = fitted_len, form = kFormFitted;
+            uint32_t *lens = ws + (size_t)gridDim.y * gridDim.x * kWsWords + ((size_t)blockIdx.y * gridDim.x + seg) * kLenWords;
+            if (threadIdx.x < kLenWords) lens[threadIdx.x] = reinterpret_cast<const uint32_t *>(fit.len)[threadIdx.x];
+        }
+    }
     if (threadIdx.x == 0) {
-        const uint32_t fixed_len = (3u + bits + 7u + 3u + 7u) / 8u + 4u, stored_len = 5u + (uint32_t)n;
-        const bool stored = fixed_len > stored_len;
         uint32_t *rec = ws + ((size_t)blockIdx.y * gridDim.x + seg) * kWsWords;
-        rec[0] = ((stored ? stored_len : fixed_len) + (seg == 0 ? 2u : 0u)) | (stored ? kStoredFlag : 0u);
+        rec[0] = (len + (seg == 0 ? 2u : 0u)) | (stored && form != kFormFitted ? kStoredFlag : 0u);
         rec[1] = a % kAdlerMod;
         rec[2] = b % kAdlerMod;
-        rec[3] = 0;
+        rec[3] = kFitted ? form : 0u;
     }
 }
 
@@ -285,6 +535,7 @@ __device__ __forceinline__ void png_frame_ends(PngShared &sh, int H, int W, cons
 }
 
 // grid (segments + 1, N)
+template <bool kFitted>
 __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restrict__ img, int H, int W,
                                                          const uint32_t *__restrict__ ws, uint8_t *__restrict__ out,
                                                          int64_t capacity, int32_t *__restrict__ lengths) {
@@ -294,6 +545,7 @@ __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restr
     const uint32_t seg = blockIdx.x, n_seg = gridDim.x - 1;
     const int n = (int)min((uint32_t)kSeg, n_total - seg * kSeg);
     img += (int64_t)blockIdx.y * H * W;
+    const uint32_t *lens = ws + (size_t)gridDim.y * n_seg * kWsWords + ((size_t)blockIdx.y * n_seg + seg) * kLenWords;
     ws += (int64_t)blockIdx.y * n_seg * kWsWords;
     out += (int64_t)blockIdx.y * capacity;
 
@@ -321,15 +573,36 @@ __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restr
     const uint32_t rec0 = ws[(size_t)seg * kWsWords];
     const bool stored = (rec0 & kStoredFlag) != 0;
     const uint32_t dlen = rec0 & ~kStoredFlag, zhdr = seg == 0 ? 2u : 0u;
+    const bool fitted = kFitted && ws[(size_t)seg * kWsWords + 3] == kFormFitted;
     uint8_t *dst = out + offset;
     const uint32_t mis = (uint32_t)((uintptr_t)dst & 3u);  // the chunk sits at byte `mis` of sh.chunk: dwords line up
     const uint32_t total = 12u + dlen, n_words = (mis + total + 3u) / 4u;
     for (uint32_t i = tid; i < n_words; i += kPngThreads) sh.chunk[i] = 0;
 
     load_segment(img, W, seg, n, sh);  // (ends in a barrier: tables and zeroes are visible)
-    uint32_t code[kPer], nb[kPer], bytes[kPer];
-    const uint32_t my_bits = thread_tokens(sh, n, code, nb, bytes);
-    const uint32_t bit_end = block_scan_sum(my_bits, sh.wave);
+    uint32_t code[kPer], nb[kPer], bytes[kPer], tok[kPer];
+    uint32_t my_bits = thread_tokens<kFitted>(sh, n, code, nb, bytes, tok);
+    uint32_t hc[2], hn[2], hoff[2], n_lit;     // (fitted form) this thread's part of the code-length sequence
+    uint32_t first_bit = 3u, eob = 0;  // where the tokens start in the block: behind its header; the end-of-block code
+    if constexpr (kFitted) {
+        __shared__ PngFit fit;
+        if (fitted) {  // (uniform over the workgroup)
+            if (tid < kLenWords) reinterpret_cast<uint32_t *>(fit.len)[tid] = lens[tid];
+            __syncthreads();
+            fitted_codes(fit);
+            first_bit = fitted_header(fit, sh.wave, hc, hn, hoff, n_lit);
+            my_bits = 0;
+#pragma unroll
+            for (int j = 0; j < kPer; ++j) {
+                const uint32_t t = fit.tab[tok[j] & 511u], l = t >> 16;  // (no token: an entry of 0 bits)
+                code[j] = (t & 0xffffu) | (((tok[j] >> 12) & 31u) << l);
+                nb[j] = l + ((tok[j] >> 9) & 7u) + (tok[j] >> 17);  // (+ a match's distance code: one 0 bit)
+                my_bits += nb[j];
+            }
+            eob = fit.tab[kEob];
+        }
+    }
+    const uint32_t bit_end = block_scan_sum<kFitted>(my_bits, sh.wave);
 
     uint8_t *cb = reinterpret_cast<uint8_t *>(sh.chunk) + mis;  // the chunk's bytes
     uint8_t *data = cb + 8 + zhdr;                              // the segment's deflate bytes
@@ -353,8 +626,21 @@ __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restr
     __syncthreads();
     if (!stored) {
         // the thread's bits, OR-ed into the words they fall in (its first and last word are shared with its neighbours)
-        uint32_t pos = 8u * (mis + 8u + zhdr) + 3u + (bit_end - my_bits);
-        if (tid == 0) atomicOr(&sh.chunk[(8u * (mis + 8u + zhdr)) >> 5], 2u << ((8u * (mis + 8u + zhdr)) & 31u));  // BFINAL 0, BTYPE 01
+        uint32_t pos = 8u * (mis + 8u + zhdr) + first_bit + (bit_end - my_bits);
+        if (!fitted && tid == 0) atomicOr(&sh.chunk[(8u * (mis + 8u + zhdr)) >> 5], 2u << ((8u * (mis + 8u + zhdr)) & 31u));  // BFINAL 0, BTYPE 01
+        if constexpr (kFitted) {
+            if (fitted) {
+                const uint32_t base = 8u * (mis + 8u + zhdr);
+                if (tid == 0) {  // BFINAL 0, BTYPE 10; HLIT, HDIST 0, HCLEN 19 - 4; the code-length code
+                    or_bits(sh.chunk, base, 4u | ((n_lit - 257u) << 3) | (15u << 13));
+                    or_bits(sh.chunk, base + 17u, (uint32_t)kClHeader);
+                    or_bits(sh.chunk, base + 49u, (uint32_t)(kClHeader >> 32));
+                }
+                if (hn[0]) or_bits(sh.chunk, base + hoff[0], hc[0]);
+                if (hn[1]) or_bits(sh.chunk, base + hoff[1], hc[1]);
+                if (tid == kPngThreads - 1) or_bits(sh.chunk, pos + my_bits, eob & 0xffffu);  // (the fixed one: 7 zeros)
+            }
+        }
         uint32_t word = pos >> 5, fill = pos & 31u;
         unsigned long long acc = 0;
 #pragma unroll
@@ -411,6 +697,11 @@ extern "C" size_t fosvos_png_workspace_bytes(int N, int H, int W) {
     return (size_t)N * (size_t)png_segments(H, W) * kWsWords * sizeof(uint32_t);
 }
 
+extern "C" size_t fosvos_png_workspace_bytes_mode(int N, int H, int W, int huffman) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)N * (size_t)png_segments(H, W) * (kWsWords + (huffman ? kLenWords : 0)) * sizeof(uint32_t);
+}
+
 extern "C" int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths,
                                  void *workspace, size_t workspace_bytes, int device, void *stream) {
     FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && png_stream_bytes(H, W) <= ((int64_t)1 << 30), FOSVOS_E_SHAPE,
@@ -427,11 +718,39 @@ extern "C" int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint
     const dim3 grid((unsigned)png_segments(H, W), (unsigned)N);
     uint32_t *ws = reinterpret_cast<uint32_t *>(workspace);
     FOSVOS_PROF("k_png_measure", stream, 0.0);
-    hipLaunchKernelGGL(k_png_measure, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
+    hipLaunchKernelGGL(k_png_measure<false>, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
     FOSVOS_LAUNCH_CHECK();
     FOSVOS_PROF("k_png_emit", stream, 0.0);
-    hipLaunchKernelGGL(k_png_emit, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out, (int64_t)capacity,
+    hipLaunchKernelGGL(k_png_emit<false>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out, (int64_t)capacity,
                        lengths);
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" int fosvos_png_encode_mode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
+                                      int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
+    FOSVOS_REQUIRE(huffman == 0 || huffman == 1, FOSVOS_E_ARG, "png_encode: huffman=%d (0 fixed, 1 fitted)", huffman);
+    if (huffman == 0)
+        return fosvos_png_encode(bytes, N, H, W, out, capacity, lengths, workspace, workspace_bytes, device, stream);
+    FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && png_stream_bytes(H, W) <= ((int64_t)1 << 30), FOSVOS_E_SHAPE,
+                   "png_encode: N=%d (<= 65535) H=%d W=%d (H * (W + 1) <= 2^30)", N, H, W);
+    FOSVOS_REQUIRE(bytes && out && lengths && workspace, FOSVOS_E_ARG, "png_encode: null pointer");
+    FOSVOS_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)lengths & 3) == 0, FOSVOS_E_ARG,
+                   "png_encode: the workspace and the lengths must be 4-byte aligned");
+    const size_t need_cap = fosvos_png_capacity_bytes(N, H, W), need_ws = fosvos_png_workspace_bytes_mode(N, H, W, huffman);
+    FOSVOS_REQUIRE(capacity >= need_cap, FOSVOS_E_WORKSPACE, "png_encode: capacity %zu B a frame < %zu B", capacity, need_cap);
+    FOSVOS_REQUIRE(workspace_bytes >= need_ws, FOSVOS_E_WORKSPACE, "png_encode: workspace %zu B < %zu B", workspace_bytes,
+                   need_ws);
+    FOSVOS_ENTER(device);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)png_segments(H, W), (unsigned)N);
+    uint32_t *ws = reinterpret_cast<uint32_t *>(workspace);
+    FOSVOS_PROF("k_png_measure_fitted", stream, 0.0);
+    hipLaunchKernelGGL(k_png_measure<true>, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
+    FOSVOS_LAUNCH_CHECK();
+    FOSVOS_PROF("k_png_emit_fitted", stream, 0.0);
+    hipLaunchKernelGGL(k_png_emit<true>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out,
+                       (int64_t)capacity, lengths);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }

@@ -1071,12 +1071,19 @@ def png_capacity(h: int, w: int) -> int:
     return int(lib().fosvos_png_capacity_bytes(1, int(h), int(w)))
 
 
-def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None,
-               lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+PNG_HUFFMAN = {'fixed': 0, 'fitted': 1}
+
+
+def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+               huffman: str = 'fixed') -> Tuple[torch.Tensor, torch.Tensor]:
     """fosvos_png_encode: uint8 [N,H,W] (``prob_bytes``' output) -> (buffer uint8 [N,capacity], lengths int32 [N]): frame n's
     8-bit greyscale PNG file is ``buffer[n, :lengths[n]]``, in the layout util/png_layout.py states; the bytes behind it
     are not written.  ``out`` (uint8 [N, >= png_capacity(H, W)]) and ``lengths`` (int32 [N]) may be views of a caller's
-    buffer.  Launched on the current stream, no synchronisation."""
+    buffer.  ``huffman='fitted'`` (fosvos_png_encode_mode): a segment may also be a dynamic-Huffman block with a code fitted
+    to it, where that is shorter - the same pixels in files that are never longer, ``png_layout.encode(img, 'fitted')``.
+    Launched on the current stream, no synchronisation."""
+    if huffman not in PNG_HUFFMAN:
+        raise ValueError(f"png_encode: huffman must be one of {tuple(PNG_HUFFMAN)}, got {huffman!r}")
     _need_eval(bytes_u8, torch.uint8, "png_encode bytes")
     if bytes_u8.dim() != 3 or bytes_u8.numel() == 0:
         raise ValueError(f"png_encode: bytes must be a non-empty [N,H,W], got {tuple(bytes_u8.shape)}")
@@ -1098,10 +1105,16 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None,
     for t in (out, lengths):
         if t.device != bytes_u8.device:
             raise RuntimeError(f"png_encode: every tensor must be on {bytes_u8.device}, got one on {t.device}")
-    ws, wsn = _WS.get(L.fosvos_png_workspace_bytes(n, h, w), bytes_u8.device)
+    mode = PNG_HUFFMAN[huffman]
+    ws, wsn = _WS.get(L.fosvos_png_workspace_bytes_mode(n, h, w, mode) if mode else L.fosvos_png_workspace_bytes(n, h, w),
+                      bytes_u8.device)
     dev, st = _ctx(bytes_u8)
     e0 = _pb()
-    check(L.fosvos_png_encode(bytes_u8.data_ptr(), n, h, w, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(), ws, wsn,
-                              dev, st), "png_encode")
+    if mode:
+        check(L.fosvos_png_encode_mode(bytes_u8.data_ptr(), n, h, w, mode, out.data_ptr(), int(out.shape[1]),
+                                       lengths.data_ptr(), ws, wsn, dev, st), "png_encode")
+    else:
+        check(L.fosvos_png_encode(bytes_u8.data_ptr(), n, h, w, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(), ws,
+                                  wsn, dev, st), "png_encode")
     _pe(e0, "png_encode", 0.0, 2.0 * n * h * w)
     return out, lengths

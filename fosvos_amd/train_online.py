@@ -39,6 +39,7 @@ synthetic_size = None       # (H, W) when --synthetic
 data_parallel = False
 score = False               # --score: the test pass computes J and F on the device (experiment_helper.test_scored)
 fast_test = False           # --fast-test: grouped forward passes, PNG files encoded on the device (experiment_helper.test_fast)
+png_fitted = False          # --png-fitted (with --fast-test): Huffman codes fitted to each segment of the PNG files
 scored_sequences = []       # the score of every sequence of this run, in order
 
 sequences_val = ['blackswan', 'bmx-trees', 'breakdance', 'camel', 'car-roundabout', 'car-shadow', 'cows',
@@ -71,7 +72,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                         str(settings.variant_online))
         if fast_test:
             annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
-            result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name)
+            result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name,
+                                                 png_huffman='fitted' if png_fitted else 'fixed')
             if result is not None:
                 log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
                 experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
@@ -470,7 +472,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 
 def main(argv=None):
-    global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test
+    global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -478,6 +480,7 @@ def main(argv=None):
         raise SystemExit('--fast-test is the PNG-writing test pass; --eval-speeds writes nothing')
     score = bool(args.score)
     fast_test = bool(args.fast_test)
+    png_fitted = bool(args.png_fitted)
     del scored_sequences[:]
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')

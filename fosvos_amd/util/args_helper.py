@@ -3,7 +3,7 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --resident-train-set (offline only), --score and --fast-test (online only).
+--data-parallel, --resident-train-set (offline only), --score, --fast-test and --png-fitted (online only).
 """
 import argparse
 from typing import List, Optional
@@ -45,11 +45,16 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--fast-test', action='store_true',
                             help='test pass in groups of frames with the PNG files encoded on the device (same pixels, '
                                  'larger files of many IDAT chunks)')
+        parser.add_argument('--png-fitted', action='store_true',
+                            help='with --fast-test: Huffman codes fitted to each segment of the PNG files (same pixels, '
+                                 'smaller files)')
     if not is_online:
         parser.add_argument('--resident-train-set', action='store_true',
                             help='decode the training set once, keep it on the GPU and flip / rescale each draw there '
                                  '(same samples as the per-iteration DataLoader under the same seed)')
     args = parser.parse_args(argv)
+    if is_online and args.png_fitted and not args.fast_test:
+        parser.error('--png-fitted chooses the codes of the device PNG encoder: it needs --fast-test')
     args.is_training = not args.no_training
     args.is_testing = not args.no_testing
     return args

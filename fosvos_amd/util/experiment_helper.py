@@ -29,7 +29,7 @@ last_eval = {}
 last_score = {}
 # what the last call of test_fast() did: {'n_frames', 'n_groups', 'group_sizes', 'seconds', host seconds per stage:
 # 'seconds_load' (waiting for the loader), 'seconds_issue' (upload, forward and encode calls), 'seconds_wait' (for the
-# device and the copy), 'seconds_write' (files), 'png_bytes'}
+# device and the copy), 'seconds_write' (files), 'png_bytes', 'png_huffman'}
 last_fast = {}
 
 
@@ -198,7 +198,7 @@ def _frame_groups(data_loader, group: int):
 
 
 def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
-              seq_name: Optional[str] = None, forward_batch: int = 2) -> Optional[dict]:
+              seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed') -> Optional[dict]:
     """The test pass with the PNG files made on the device.  Up to ``group`` consecutive frames of one shape are uploaded
     as one batch and forwarded ``forward_batch`` frames a call into one logit tensor.  Two frames a call is the largest
     batch whose frames the engine computes exactly as it computes a frame alone (a batch runs as two chains of ceil(N/2)
@@ -213,8 +213,12 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     asking for them first would put a host synchronisation in front of every group's copy.
     ``annotations`` (as for ``test_scored``): the J / F counts are taken on the device as well and the score dict of
     ``test_scored`` is returned (and kept in ``last_score``); without it the pass returns None.
-    CPU logits take the host path: ``bytescale`` of the fp64 sigmoid, ``png_layout.encode``."""
+    CPU logits take the host path: ``bytescale`` of the fp64 sigmoid, ``png_layout.encode``.
+    ``png_huffman='fitted'`` (``--png-fitted``): segments may be dynamic-Huffman blocks with a code fitted to them - the
+    same pixels in smaller files (never larger, segment by segment)."""
     from util import png_layout
+    if png_huffman not in png_layout.HUFFMAN_MODES:
+        raise ValueError('test_fast: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
     if group < 1 or forward_batch < 1:
         raise ValueError('test_fast: group and forward_batch must be at least 1, got {} and {}'.format(group, forward_batch))
     log.info('Testing Network (fast)')
@@ -294,7 +298,7 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                                    torch.empty(n * cap + 4 * n, dtype=torch.uint8).pin_memory())
                 dev_store, host_store = stores[key]
                 ops.png_encode(ops.prob_bytes(logits), out=dev_store[:n * cap].view(n, cap),
-                               lengths=dev_store[n * cap:].view(torch.int32))
+                               lengths=dev_store[n * cap:].view(torch.int32), huffman=png_huffman)
                 host_store.copy_(dev_store, non_blocking=True)
                 landed = torch.cuda.Event()
                 landed.record()
@@ -308,7 +312,7 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                 for index in range(n):
                     if annotations is not None:
                         counts_host[first + index] = davis_measures.jf_counts_numpy(x[index] >= 0, gt[index], radius)
-                    blobs.append(png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x[index])))))
+                    blobs.append(png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x[index]))), huffman=png_huffman))
                 stage['issue'] += timeit.default_timer() - t0
                 t0 = timeit.default_timer()
                 write_files(paths, blobs)
@@ -322,7 +326,7 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     last_fast.clear()
     last_fast.update(n_frames=len(fnames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
                      seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],
-                     seconds_write=stage['write'], png_bytes=png_bytes)
+                     seconds_write=stage['write'], png_bytes=png_bytes, png_huffman=png_huffman)
     log.info('Test {0}: {1} images in {2} groups, total test time {3} sec'.format(seq_name, len(fnames), len(group_sizes),
                                                                                  time_for_all))
     if annotations is None:

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 22
+#define FOSVOS_ABI_VERSION 23
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -417,6 +417,20 @@ size_t fosvos_png_capacity_bytes(int N, int H, int W); /* per frame */
 size_t fosvos_png_workspace_bytes(int N, int H, int W);
 int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths,
                       void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* fosvos_png_encode_mode: the same files with a choice of Huffman codes.  huffman = 0 is fosvos_png_encode, byte for byte.
+ * huffman = 1 (fitted) adds a third form of a segment: a dynamic-Huffman block (BTYPE = 10) whose literal/length code is
+ * fitted to the segment's tokens - deterministic two-queue Huffman construction over the symbols sorted by (count, symbol),
+ * lengths limited to 15 bits by halving the counts, canonical codes; HDIST = 0 (a match's distance costs 1 bit); a fixed,
+ * complete code-length code with HCLEN = 19; zero runs of the length sequence as symbols 17 / 18.  Each segment takes the
+ * shortest of {fitted, fixed, stored}, fixed or stored on a tie, so no file is longer than with huffman = 0 and the
+ * capacity is the same.  util/png_layout.py encode(img, huffman='fitted') states the bytes.
+ *   workspace  fosvos_png_workspace_bytes_mode(N, H, W, huffman): with huffman = 1 the records of huffman = 0 and 288
+ *              bytes of code lengths per segment
+ * Integer arithmetic only; two launches on `stream`. */
+size_t fosvos_png_workspace_bytes_mode(int N, int H, int W, int huffman);
+int fosvos_png_encode_mode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
+                           int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
