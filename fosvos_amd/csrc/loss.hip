@@ -7,6 +7,10 @@
 //              writes grad and per-block fp64 partial sums of the positive / negative losses
 //   k_finish   one wave sums the partials in index order and writes the fp32 loss
 // All sums are fixed-order: results are bitwise reproducible run to run.
+//
+// k_loss_multi is k_loss for M logit maps that share one label batch (the offline objective: four side maps and the fused
+// one): a thread reads its four labels once and walks the maps - 4 + M x 8 B/pixel instead of M x 16, one launch instead of
+// M x 3.  Same pixel partition, same float expressions (px_loss_grad), same fixed-order partials: bit for bit k_loss per map.
 #include "common.hpp"
 
 using namespace fosvos;
@@ -32,10 +36,21 @@ __device__ __forceinline__ void load4(const float *__restrict__ p, int64_t i, in
     }
 }
 
+// one pixel: its loss term and its gradient (the expressions k_loss and k_loss_multi share, so that they agree bit for bit)
+__device__ __forceinline__ float px_loss_grad(float xx, bool y, float w_pos, float w_neg, float &g) {
+    const float e = expf(-fabsf(xx));          // in (0,1]
+    const float l = fmaxf(xx, 0.f) - (y ? xx : 0.f) + log1pf(e);
+    const float inv = 1.f / (1.f + e);
+    const float sig = xx >= 0.f ? inv : e * inv;
+    g = y ? w_pos * (sig - 1.f) : w_neg * sig;
+    return l;
+}
+
 // blockIdx.y = frame: every frame of a batch is its own loss (own class counts, own workspace record, own output)
-__global__ __launch_bounds__(kBlock) void k_count(const float *__restrict__ label, int64_t n, Ws *ws) {
+// (ws_stride: records per frame - 1, or the number of maps of k_loss_multi, whose frame keeps its counts in its first record)
+__global__ __launch_bounds__(kBlock) void k_count(const float *__restrict__ label, int64_t n, Ws *ws, int ws_stride) {
     label += (int64_t)blockIdx.y * n;
-    ws += blockIdx.y;
+    ws += (int64_t)blockIdx.y * ws_stride;
     unsigned cnt = 0;
     const int64_t stride = (int64_t)gridDim.x * kBlock * kPerThread;
     for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPerThread; i < n; i += stride) {
@@ -92,12 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_loss(const float *__restrict__ x, co
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool y = yv[j] >= 0.5f;
-            const float xx = xv[j];
-            const float e = expf(-fabsf(xx));          // in (0,1]
-            const float l = fmaxf(xx, 0.f) - (y ? xx : 0.f) + log1pf(e);
-            const float inv = 1.f / (1.f + e);
-            const float sig = xx >= 0.f ? inv : e * inv;
-            g[j] = y ? w_pos * (sig - 1.f) : w_neg * sig;
+            const float l = px_loss_grad(xv[j], y, w_pos, w_neg, g[j]);
             if (i + j < n) {
                 if (y) pos += (double)l; else neg += (double)l;
             }
@@ -125,8 +135,101 @@ __global__ __launch_bounds__(kBlock) void k_loss(const float *__restrict__ x, co
     }
 }
 
+// The logit maps of k_loss_multi: separate tensors, so the table travels by value in the kernel arguments.
+struct Maps {
+    const float *x[FOSVOS_CBCE_MAX_MAPS];
+    float *grad[FOSVOS_CBCE_MAX_MAPS];  // an entry may be null
+    float scale[FOSVOS_CBCE_MAX_MAPS];  // grad_scale of k_loss, per map
+};
+
+// k_loss over M maps with one label: record blockIdx.y * M + m takes map m's partials, the counts are in the frame's first
+// record (k_count with ws_stride = M).  M is a template parameter so that the table is indexed by constants.
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_loss_multi(Maps maps, const float *__restrict__ label, int64_t n,
+                                                       int size_average, Ws *ws, int n_count_blocks) {
+    const int64_t frame_off = (int64_t)blockIdx.y * n;
+    label += frame_off;
+    ws += (int64_t)blockIdx.y * M;
+    __shared__ double s_pos[M][kBlock / 64], s_neg[M][kBlock / 64];
+    __shared__ unsigned long long s_np;
+    {
+        __shared__ unsigned long long s_c[kBlock / 64];
+        unsigned long long c = 0;
+        for (int b = threadIdx.x; b < n_count_blocks; b += kBlock) c += ws->count[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) s_np = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+        __syncthreads();
+    }
+    const double n_tot = (double)n;
+    const double n_pos = (double)s_np;
+    const double n_neg = n_tot - n_pos;
+    float w_pos[M], w_neg[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        double gscale = (double)maps.scale[m];
+        if (size_average) gscale /= n_tot;
+        w_pos[m] = (float)(n_neg / n_tot * gscale);
+        w_neg[m] = (float)(n_pos / n_tot * gscale);
+    }
+
+    double pos[M], neg[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) pos[m] = neg[m] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kBlock * kPerThread;
+    for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPerThread; i < n; i += stride) {
+        float yv[4], xv[M][4];
+        load4(label, i, n, yv, 0.f);
+#pragma unroll
+        for (int m = 0; m < M; ++m) load4(maps.x[m] + frame_off, i, n, xv[m], 0.f);  // all loads in flight before any store
+        bool y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = yv[j] >= 0.5f;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            float g[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float l = px_loss_grad(xv[m][j], y[j], w_pos[m], w_neg[m], g[j]);
+                if (i + j < n) {
+                    if (y[j]) pos[m] += (double)l; else neg[m] += (double)l;
+                }
+            }
+            if (maps.grad[m]) {
+                float *grad = maps.grad[m] + frame_off;
+                if (i + 3 < n) {
+                    *reinterpret_cast<float4 *>(grad + i) = make_float4(g[0], g[1], g[2], g[3]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (i + j < n) grad[i + j] = g[j];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const double p = wave_sum(pos[m]), q = wave_sum(neg[m]);
+        if ((threadIdx.x & 63) == 0) {
+            s_pos[m][threadIdx.x >> 6] = p;
+            s_neg[m][threadIdx.x >> 6] = q;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < M) {
+        const int m = threadIdx.x;
+        ws[m].pos[blockIdx.x] = (s_pos[m][0] + s_pos[m][1]) + (s_pos[m][2] + s_pos[m][3]);
+        ws[m].neg[blockIdx.x] = (s_neg[m][0] + s_neg[m][1]) + (s_neg[m][2] + s_neg[m][3]);
+    }
+}
+
+
+// blockIdx.x = record (frame x map, maps = 1 for k_loss); the class counts are in the first record of the frame
 __global__ __launch_bounds__(64) void k_finish(int64_t n, int size_average, const Ws *ws, int n_blocks,
-                                                float *__restrict__ loss_out, const double *__restrict__ ext_counts) {
+                                                float *__restrict__ loss_out, const double *__restrict__ ext_counts, int maps) {
+    const Ws *ws_count = ws + (blockIdx.x / maps) * maps;
     ws += blockIdx.x;
     loss_out += blockIdx.x;
     // lane t sums entries t, t+64, ... then a fixed butterfly: the order never changes run to run
@@ -138,7 +241,7 @@ __global__ __launch_bounds__(64) void k_finish(int64_t n, int size_average, cons
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int b = min(b0 + 64 * j, n_blocks - 1);
-            c[j] = ext_counts ? 0ull : ws->count[b];
+            c[j] = ext_counts ? 0ull : ws_count->count[b];
             p[j] = ws->pos[b];
             q[j] = ws->neg[b];
         }
@@ -192,7 +295,7 @@ int cbce_impl(const float *logits, const float *label, int64_t numel, int n_fram
     hipStream_t s = (hipStream_t)stream;
     if (!batch_counts && (parts & FOSVOS_CBCE_COUNT)) {
         FOSVOS_PROF("k_count", s, 0.0);
-        hipLaunchKernelGGL(k_count, dim3(blocks, n_frames), dim3(kBlock), 0, s, label, numel, ws);
+        hipLaunchKernelGGL(k_count, dim3(blocks, n_frames), dim3(kBlock), 0, s, label, numel, ws, 1);
         FOSVOS_LAUNCH_CHECK();
     }
     if (parts & FOSVOS_CBCE_LOSS) {
@@ -203,7 +306,7 @@ int cbce_impl(const float *logits, const float *label, int64_t numel, int n_fram
     }
     if (parts & FOSVOS_CBCE_FINISH) {
         FOSVOS_PROF("k_finish", s, 0.0);
-        hipLaunchKernelGGL(k_finish, dim3(n_frames), dim3(64), 0, s, numel, size_average, ws, blocks, loss_out, batch_counts);
+        hipLaunchKernelGGL(k_finish, dim3(n_frames), dim3(64), 0, s, numel, size_average, ws, blocks, loss_out, batch_counts, 1);
         FOSVOS_LAUNCH_CHECK();
     }
     return FOSVOS_OK;
@@ -238,4 +341,81 @@ extern "C" int fosvos_cbce_loss_batch_counts(const float *logits, const float *l
     FOSVOS_REQUIRE(batch_counts, FOSVOS_E_ARG, "cbce_loss_batch_counts: null batch_counts");
     return cbce_impl(logits, label, numel, 1, size_average, grad_scale, batch_counts, loss_out, grad, workspace,
                      workspace_bytes, device, stream);
+}
+
+extern "C" size_t fosvos_cbce_multi_workspace_bytes(int64_t, int n_frames, int n_maps) {
+    return n_frames > 0 && n_maps > 0 ? (size_t)n_frames * n_maps * sizeof(Ws) : 0;
+}
+
+namespace {
+template <int M>
+void launch_loss_multi(const Maps &maps, const float *label, int64_t numel, int n_frames, int size_average, Ws *ws,
+                       int blocks, hipStream_t s) {
+    hipLaunchKernelGGL(k_loss_multi<M>, dim3(blocks, n_frames), dim3(kBlock), 0, s, maps, label, numel, size_average, ws,
+                       blocks);
+}
+}  // namespace
+
+extern "C" int fosvos_cbce_loss_frames_multi(const float *const *logits, const float *label, int64_t frame_numel,
+                                             int n_frames, int n_maps, int size_average, const float *map_scale,
+                                             float *loss_out, float *const *grad, void *workspace, size_t workspace_bytes,
+                                             int parts, int device, void *stream) {
+    FOSVOS_REQUIRE(parts > 0 && parts <= 7, FOSVOS_E_ARG, "cbce_loss_frames_multi: parts=%d", parts);
+    FOSVOS_REQUIRE(n_maps >= 1 && n_maps <= FOSVOS_CBCE_MAX_MAPS, FOSVOS_E_ARG, "cbce_loss_frames_multi: n_maps=%d (1..%d)",
+                   n_maps, FOSVOS_CBCE_MAX_MAPS);
+    FOSVOS_REQUIRE(workspace && (label || !(parts & (FOSVOS_CBCE_COUNT | FOSVOS_CBCE_LOSS))) &&
+                       ((logits && map_scale) || !(parts & FOSVOS_CBCE_LOSS)) && (loss_out || !(parts & FOSVOS_CBCE_FINISH)),
+                   FOSVOS_E_ARG, "cbce_loss_frames_multi: null pointer");
+    FOSVOS_REQUIRE(frame_numel > 0, FOSVOS_E_SHAPE, "cbce_loss_frames_multi: frame_numel=%lld", (long long)frame_numel);
+    FOSVOS_REQUIRE(n_frames >= 1 && n_frames <= 65535, FOSVOS_E_SHAPE, "cbce_loss_frames_multi: n_frames=%d", n_frames);
+    FOSVOS_REQUIRE(n_frames == 1 || frame_numel % 4 == 0, FOSVOS_E_SHAPE,
+                   "cbce_loss_frames_multi: %lld elements per frame - frames after the first would start off a 16-byte boundary",
+                   (long long)frame_numel);
+    const size_t need = (size_t)n_frames * n_maps * sizeof(Ws);
+    FOSVOS_REQUIRE(workspace_bytes >= need, FOSVOS_E_WORKSPACE, "cbce_loss_frames_multi: workspace %zu < %zu", workspace_bytes,
+                   need);
+    FOSVOS_REQUIRE((uintptr_t)workspace % 8 == 0 && (!label || (uintptr_t)label % 16 == 0), FOSVOS_E_ARG,
+                   "cbce_loss_frames_multi: label must be 16-byte aligned, the workspace 8-byte");
+    Maps maps = {};
+    if (parts & FOSVOS_CBCE_LOSS) {
+        for (int m = 0; m < n_maps; ++m) {
+            FOSVOS_REQUIRE(logits[m], FOSVOS_E_ARG, "cbce_loss_frames_multi: logits[%d] is null", m);
+            FOSVOS_REQUIRE((uintptr_t)logits[m] % 16 == 0 && (!grad || (uintptr_t)grad[m] % 16 == 0), FOSVOS_E_ARG,
+                           "cbce_loss_frames_multi: map %d: pointers must be 16-byte aligned", m);
+            maps.x[m] = logits[m];
+            maps.grad[m] = grad ? grad[m] : nullptr;
+            maps.scale[m] = map_scale[m];
+        }
+    }
+    FOSVOS_ENTER(device);
+    int blocks = (int)cdiv(frame_numel, (int64_t)kBlock * kPerThread);
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    Ws *ws = reinterpret_cast<Ws *>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    if (parts & FOSVOS_CBCE_COUNT) {
+        FOSVOS_PROF("k_count", s, 0.0);
+        hipLaunchKernelGGL(k_count, dim3(blocks, n_frames), dim3(kBlock), 0, s, label, frame_numel, ws, n_maps);
+        FOSVOS_LAUNCH_CHECK();
+    }
+    if (parts & FOSVOS_CBCE_LOSS) {
+        FOSVOS_PROF("k_loss_multi", s, 0.0);
+        switch (n_maps) {
+        case 1: launch_loss_multi<1>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        case 2: launch_loss_multi<2>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        case 3: launch_loss_multi<3>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        case 4: launch_loss_multi<4>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        case 5: launch_loss_multi<5>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        case 6: launch_loss_multi<6>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        case 7: launch_loss_multi<7>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        default: launch_loss_multi<8>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
+        }
+        FOSVOS_LAUNCH_CHECK();
+    }
+    if (parts & FOSVOS_CBCE_FINISH) {
+        FOSVOS_PROF("k_finish", s, 0.0);
+        hipLaunchKernelGGL(k_finish, dim3(n_frames * n_maps), dim3(64), 0, s, frame_numel, size_average, ws, blocks, loss_out,
+                           (const double *)nullptr, n_maps);
+        FOSVOS_LAUNCH_CHECK();
+    }
+    return FOSVOS_OK;
 }

@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -168,6 +168,9 @@ SIGNATURES = {
                                         c_size_t, c_int, c_void_p]),
     "fosvos_cbce_loss_frames_parts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p,
                                               c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fosvos_cbce_multi_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "fosvos_cbce_loss_frames_multi": (c_int, [POINTER(c_void_p), c_void_p, c_int64, c_int, c_int, c_int, POINTER(c_float),
+                                              c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fosvos_cbce_loss_batch_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_sgd_momentum_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_int, c_int, c_void_p]),

@@ -665,6 +665,121 @@ class CbceFramesStaged(object):
         return self.losses
 
 
+CBCE_MAX_MAPS = 8
+
+
+def _map_tables(tensors):
+    """HOST array of device pointers (a NULL entry for None), as the multi-map loss takes its logits and gradients."""
+    import ctypes
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _multi_args(logits, label: torch.Tensor, map_scale, who: str):
+    """The checks the multi-map loss makes on the tensors themselves (the library checks counts, shapes and alignment)."""
+    _need(label, _F32, f"{who} label")
+    if label.dim() < 2:
+        raise ValueError(f"{who}: label {tuple(label.shape)}")
+    if len(map_scale) != len(logits):
+        raise ValueError(f"{who}: {len(logits)} logit maps, {len(map_scale)} scales")
+    for t in logits:
+        _need(t, _F32, f"{who} logits")
+        if t.device != label.device:
+            raise ValueError(f"{who}: logits on {t.device}, label on {label.device}")
+        if t.shape != label.shape:
+            raise ValueError(f"{who}: logits {tuple(t.shape)} vs label {tuple(label.shape)}")
+
+
+def cbce_multi_workspace_bytes(label: torch.Tensor, n_maps: int) -> int:
+    """Bytes of workspace the multi-map loss of ``label`` ([N,1,H,W]) and ``n_maps`` logit maps needs."""
+    n = label.shape[0]
+    return lib().fosvos_cbce_multi_workspace_bytes(label.numel() // max(n, 1), n, int(n_maps))
+
+
+def cbce_loss_frames_multi(logits: Sequence[torch.Tensor], label: torch.Tensor, map_scale: Sequence[float],
+                           size_average: bool = True, want_grad: bool = True, workspace: Optional[torch.Tensor] = None):
+    """The per-frame loss of M logit maps [N,1,H,W] that share the label batch ``label``: ([N,M] UNWEIGHTED losses, list of M
+    gradients or None); map m's gradient comes out multiplied by ``map_scale[m]``.  One count and one loss launch for all
+    maps (fosvos_cbce_loss_frames_multi); every value equals ``cbce_loss_frames(logits[m], label, grad_scale=map_scale[m])``
+    bit for bit.  workspace: a uint8 tensor of cbce_multi_workspace_bytes to use instead of the ops' scratch."""
+    import ctypes
+    logits = list(logits)
+    _multi_args(logits, label, map_scale, "cbce_loss_frames_multi")
+    m = len(logits)
+    n = label.shape[0]
+    per = label.numel() // n
+    L = lib()
+    losses = torch.empty((n, m), dtype=_F32, device=label.device)
+    grads = [torch.empty_like(t) for t in logits] if want_grad else None
+    if workspace is None:
+        ws, wsn = _WS.get(L.fosvos_cbce_multi_workspace_bytes(per, n, m), label.device)
+    else:
+        _need(workspace, torch.uint8, "cbce_loss_frames_multi workspace")
+        ws, wsn = workspace.data_ptr(), workspace.numel()
+    dev, st = _ctx(label)
+    t0 = _pb()
+    check(L.fosvos_cbce_loss_frames_multi(_map_tables(logits), label.data_ptr(), per, n, m, 1 if size_average else 0,
+                                          (ctypes.c_float * max(m, 1))(*[float(v) for v in map_scale]), losses.data_ptr(),
+                                          _map_tables(grads) if want_grad else None, ws, wsn,
+                                          CBCE_COUNT | CBCE_LOSS | CBCE_FINISH, dev, st), "cbce_loss_frames_multi")
+    _pe(t0, "cbce_loss", 0.0, label.numel() * (8 + m * (8 if want_grad else 4)))
+    return losses, grads
+
+
+class CbceFramesMultiStaged(object):
+    """``cbce_loss_frames_multi`` in its three launches, like CbceFramesStaged: the class counts of ``label`` are taken at
+    construction (in front of the forward pass), ``loss`` writes the gradients of all maps in one launch, ``finish`` - behind
+    the backward pass - the [N,M] loss values.  Same stream for all three calls."""
+
+    def __init__(self, label: torch.Tensor, n_maps: int):
+        _need(label, _F32, "CbceFramesMultiStaged label")
+        if label.dim() < 2:
+            raise ValueError(f"CbceFramesMultiStaged: label {tuple(label.shape)}")
+        self.n, self.m = label.shape[0], int(n_maps)
+        self.per = label.numel() // self.n
+        L = lib()
+        self.label = label
+        # the stages share this workspace across the passes in between: its own tensor, not the ops' scratch
+        self.wsn = L.fosvos_cbce_multi_workspace_bytes(self.per, self.n, self.m)
+        self.ws = torch.empty((max(self.wsn, 8),), dtype=torch.uint8, device=label.device)
+        self.losses = None
+        self.size_average = None
+        dev, st = _ctx(label)
+        t0 = _pb()
+        check(L.fosvos_cbce_loss_frames_multi(None, label.data_ptr(), self.per, self.n, self.m, 0, None, None, None,
+                                              self.ws.data_ptr(), self.wsn, CBCE_COUNT, dev, st),
+              "cbce_loss_frames_multi(count)")
+        _pe(t0, "cbce_loss", 0.0, label.numel() * 4)
+
+    def loss(self, logits: Sequence[torch.Tensor], map_scale: Sequence[float], size_average: bool = True,
+             want_grad: bool = True):
+        import ctypes
+        logits = list(logits)
+        _multi_args(logits, self.label, map_scale, "CbceFramesMultiStaged")
+        if len(logits) != self.m:
+            raise ValueError(f"CbceFramesMultiStaged: staged for {self.m} maps, got {len(logits)}")
+        self.losses = torch.empty((self.n, self.m), dtype=_F32, device=self.label.device)
+        self.size_average = bool(size_average)
+        grads = [torch.empty_like(t) for t in logits] if want_grad else None
+        dev, st = _ctx(self.label)
+        t0 = _pb()
+        check(lib().fosvos_cbce_loss_frames_multi(_map_tables(logits), self.label.data_ptr(), self.per, self.n, self.m,
+                                                  1 if size_average else 0,
+                                                  (ctypes.c_float * self.m)(*[float(v) for v in map_scale]), None,
+                                                  _map_tables(grads) if want_grad else None, self.ws.data_ptr(), self.wsn,
+                                                  CBCE_LOSS, dev, st), "cbce_loss_frames_multi(loss)")
+        _pe(t0, "cbce_loss", 0.0, self.label.numel() * (4 + self.m * (8 if want_grad else 4)))
+        return self.losses, grads
+
+    def finish(self) -> torch.Tensor:
+        if self.losses is None:
+            raise RuntimeError("CbceFramesMultiStaged.finish before loss")
+        dev, st = _ctx(self.losses)
+        check(lib().fosvos_cbce_loss_frames_multi(None, None, self.per, self.n, self.m, 1 if self.size_average else 0, None,
+                                                  self.losses.data_ptr(), None, self.ws.data_ptr(), self.wsn, CBCE_FINISH,
+                                                  dev, st), "cbce_loss_frames_multi(finish)")
+        return self.losses
+
+
 # ------------------------------------------------------------------------------------------ thin-channel ResNet path
 def fold_conv_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn: Optional[Sequence] = None):
     """(w * s, bn_bias - mean * s [+ conv_bias * s]) with s = bn_weight / sqrt(var + eps): fp32 OIHW in and out."""

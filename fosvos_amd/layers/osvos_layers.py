@@ -3,6 +3,7 @@ names, argument meaning and return values; the loss runs as one fused HIP kernel
 
   class_balanced_cross_entropy_loss  src/layers/osvos_layers.py:17-44  -> fosvos_cbce_loss
   class_balanced_cross_entropy_loss_frames  (extension) the same loss per frame of a batch
+  class_balanced_cross_entropy_loss_frames_multi  (extension) ... of several logit maps with one label batch
   center_crop                        src/layers/osvos_layers.py:47-54  (index arithmetic only)
   upsample_filt / interp_surgery     src/layers/osvos_layers.py:57-81  (one-off host init)
   logit / sigmoid_np                 src/layers/osvos_layers.py:9-14   (numpy helpers)
@@ -149,6 +150,73 @@ def class_balanced_cross_entropy_loss_frames(output, label, size_average=True, b
     if staged is not None and (staged.label.data_ptr() != label.data_ptr() or tuple(staged.label.shape) != tuple(label.shape)):
         raise ValueError("class_balanced_cross_entropy_loss_frames: `staged` was started on another label tensor")
     return _CBCELossFrames.apply(output, label, size_average, backward_seed, staged)
+
+
+class _CBCELossFramesMulti(torch.autograd.Function):
+    """The per-frame losses of M logit maps with one label batch (M x [N,1,H,W] -> [N,M]) as ONE autograd node: one loss
+    launch writes every map's gradient already multiplied by its map_scale (fosvos_cbce_loss_frames_multi).  The seed
+    convention is _CBCELossFrames': the announced tensor is passed through without a multiplication."""
+
+    @staticmethod
+    def forward(ctx, label, map_scale, size_average, backward_seed, staged, *outputs):
+        ctx.seed_ptr, ctx.seed_value = _seed_of(backward_seed)
+        want_grad = any(o.requires_grad for o in outputs)
+        outputs = [o.contiguous().float() for o in outputs]
+        if staged is not None:  # the class counts are already in the staged loss's workspace; the values come with finish()
+            losses, grads = staged.loss(outputs, map_scale, size_average=bool(size_average), want_grad=want_grad)
+        else:
+            losses, grads = ops.cbce_loss_frames_multi(outputs, label.contiguous().float(), map_scale,
+                                                       size_average=bool(size_average), want_grad=want_grad)
+        ctx.grads, ctx.n_outputs = grads, len(outputs)
+        return losses
+
+    @staticmethod
+    def backward(ctx, g):
+        global seed_hits
+        head = (None, None, None, None, None)
+        if ctx.grads is None:
+            return head + (None,) * ctx.n_outputs
+        if ctx.seed_ptr is not None:
+            if g.data_ptr() == ctx.seed_ptr:
+                seed_hits += 1
+                return head + tuple(ctx.grads)
+            g = g / ctx.seed_value
+        return head + tuple(d * g[:, m].reshape(-1, *([1] * (d.dim() - 1))) for m, d in enumerate(ctx.grads))
+
+
+def stage_frames_loss_multi(label, n_maps):
+    """stage_frames_loss for class_balanced_cross_entropy_loss_frames_multi (ops.CbceFramesMultiStaged): counts the classes
+    of ``label`` now, for ``n_maps`` logit maps.  None when the frames do not qualify."""
+    if not label.is_cuda or label.dtype != torch.float32 or not label.is_contiguous() or label.dim() < 2:
+        return None
+    if ((label.numel() // label.shape[0]) % 4 and label.shape[0] > 1) or label.data_ptr() % 16:
+        return None
+    return ops.CbceFramesMultiStaged(label, n_maps)
+
+
+def class_balanced_cross_entropy_loss_frames_multi(outputs, label, map_scale, size_average=False, backward_seed=None,
+                                                   staged=None):
+    """``class_balanced_cross_entropy_loss_frames`` of each of the M logit maps ``outputs`` against the same ``label``: a [N,M]
+    tensor of UNWEIGHTED losses (element [i,m] equals ``class_balanced_cross_entropy_loss(outputs[m][i:i+1], label[i:i+1],
+    size_average)``) whose gradient with respect to map m is multiplied by ``map_scale[m]`` (M floats): what the offline
+    objective ``(1 - epoch / n_epochs) * sum(side losses) + fused loss`` (src/train_offline.py:85-91) asks of a batched pass,
+    in one count and one loss launch.  Not in the reference.  ``backward_seed`` / ``staged`` as in
+    class_balanced_cross_entropy_loss_frames (stage_frames_loss_multi starts a staged loss)."""
+    outputs = list(outputs)
+    if not label.is_cuda or not all(o.is_cuda for o in outputs):
+        raise RuntimeError("class_balanced_cross_entropy_loss_frames_multi: the HIP implementation needs GPU tensors "
+                           "(no CPU fallback)")
+    for o in outputs:
+        if label.device != o.device:
+            raise ValueError("class_balanced_cross_entropy_loss_frames_multi: output on {} vs label on {}".format(
+                o.device, label.device))
+        if tuple(label.shape) != tuple(o.shape):
+            raise ValueError("class_balanced_cross_entropy_loss_frames_multi: output {} vs label {}".format(
+                tuple(o.shape), tuple(label.shape)))
+    map_scale = tuple(float(v) for v in map_scale)
+    if staged is not None and (staged.label.data_ptr() != label.data_ptr() or tuple(staged.label.shape) != tuple(label.shape)):
+        raise ValueError("class_balanced_cross_entropy_loss_frames_multi: `staged` was started on another label tensor")
+    return _CBCELossFramesMulti.apply(label, map_scale, size_average, backward_seed, staged, *outputs)
 
 
 def crop_offsets(size, target):

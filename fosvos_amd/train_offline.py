@@ -3,6 +3,9 @@
 Same entry points and loop semantics (src/train_offline.py:77-110): five deeply-supervised losses,
 ``loss = (1 - epoch / n_epochs) * sum(side losses) + fused loss``, ``loss /= avg_grad_every_n``,
 backward, step every ``avg_grad_every_n``-th iteration; snapshots every ``snapshot_every_n`` epochs.
+
+Opt-in (``--microbatch-group N``, ``_train(..., microbatch_group=N)``): the one-frame minibatches of an accumulation cycle
+run as shape-bucketed batched passes of up to N frames, as the online loop's do (window_closes / plan_passes below).
 """
 import timeit
 from pathlib import Path
@@ -14,7 +17,8 @@ from torch import optim
 from config.mypath import Path as P
 from fosvos_hip.engine import PassFlags
 from fosvos_hip.options import LoopOptions
-from layers.osvos_layers import class_balanced_cross_entropy_loss
+from layers.osvos_layers import (class_balanced_cross_entropy_loss, class_balanced_cross_entropy_loss_frames_multi,
+                                 stage_frames_loss_multi)
 from util import gpu_handler, io_helper, experiment_helper, args_helper
 from util.logger import get_logger
 from util.network_provider import NetworkProvider, provider_mapping
@@ -22,6 +26,7 @@ from util.settings import OfflineSettings
 import parallel
 
 log = get_logger(__file__)
+_hip_cbce = class_balanced_cross_entropy_loss  # tests may rebind the module-level name to a CPU stand-in
 
 save_dir_models = Path('models')
 save_dir_results = Path('results')
@@ -29,6 +34,7 @@ db_root_dir = None
 synthetic_size = None
 data_parallel = False
 resident_train_set = False
+microbatch_group = 1        # --microbatch-group: frames per batched pass of an accumulation cycle (1 = the reference's order)
 
 
 def train_and_test(net_provider: NetworkProvider, settings: OfflineSettings) -> None:
@@ -45,7 +51,7 @@ def train_and_test(net_provider: NetworkProvider, settings: OfflineSettings) -> 
         summary_writer = _get_summary_writer()
         _train(net_provider, data_loader_train, data_loader_test, optimizer, summary_writer, settings.start_epoch,
                settings.n_epochs, settings.avg_grad_every_n, settings.snapshot_every_n,
-               settings.is_testing_while_training, settings.test_every_n)
+               settings.is_testing_while_training, settings.test_every_n, microbatch_group=microbatch_group)
 
     if settings.is_testing:
         if not settings.is_training:
@@ -73,12 +79,65 @@ def _losses(net, minibatch):
     return [class_balanced_cross_entropy_loss(o, gts, size_average=False, batch_counts=counts) for o in outputs]
 
 
+def window_closes(n_window: int, counter_gradient: int, avg_grad_every_n: int, max_window: int, end_of_epoch: bool) -> bool:
+    """Whether the minibatches collected so far (``n_window`` of them, ``counter_gradient`` iterations of the accumulation
+    cycle already run in front of them) are run now: a window never crosses an optimizer step, never the end of an epoch
+    (the side-loss weight, the epoch log and the snapshot change there - a CYCLE may straddle it, as in the reference) and
+    holds at most ``max_window`` minibatches."""
+    return ((counter_gradient + n_window) % avg_grad_every_n == 0) or n_window >= max_window or end_of_epoch
+
+
+def plan_passes(shapes, group: int):
+    """The passes of one window.  shapes: the image shapes (N, C, H, W) of its minibatches in draw order.  Returns a list of
+    (indices, batched) in the order the passes run: one-frame minibatches are bucketed by shape, buckets in order of first
+    appearance and frames in draw order, each bucket cut into passes of at most ``group`` frames (batched = True: the frames
+    run concatenated, every frame with the class weights of its own label).  A minibatch that holds several frames is a
+    pass of its own at its place (the reference balances its classes over the whole batch tensor), and so is a frame whose
+    H x W is no multiple of 4 (the per-frame loss kernels read 16-byte vectors): batched = False, today's path."""
+    buckets = {}
+    for i, shape in enumerate(shapes):
+        shape = tuple(int(v) for v in shape)
+        alone = shape[0] != 1 or (shape[-2] * shape[-1]) % 4 != 0
+        buckets.setdefault(('alone', i) if alone else shape, []).append(i)
+    passes = []
+    for key, idx in buckets.items():
+        if key[0] == 'alone':
+            passes.append((idx, False))
+        else:
+            passes.extend((idx[j:j + group], True) for j in range(0, len(idx), group))
+    return passes
+
+
+def _losses_frames(outputs, gts, map_scale, ones, staged=None):
+    """[k,5] per-frame losses of a batched pass and the seed of its backward pass.  On the GPU one fused op whose kernel writes
+    every map's gradient times its map_scale (the seed is then `ones` [>= k, 5], announced and passed through untouched);
+    elsewhere (the CPU stand-ins of the tests) the module-level loss per frame and map, seeded with the scales."""
+    k = gts.shape[0]
+    if gts.is_cuda and class_balanced_cross_entropy_loss is _hip_cbce:
+        return class_balanced_cross_entropy_loss_frames_multi(outputs, gts, map_scale, size_average=False,
+                                                              backward_seed=(ones, 1.0), staged=staged), ones[:k]
+    losses = torch.stack([torch.stack([class_balanced_cross_entropy_loss(o[i:i + 1], gts[i:i + 1], size_average=False)
+                                       for o in outputs]) for i in range(k)])
+    return losses, torch.tensor(map_scale, dtype=losses.dtype, device=losses.device).expand(k, -1)
+
+
 def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, optimizer: optim.SGD, summary_writer,
            start_epoch: int, n_epochs: int, avg_grad_every_n: int, snapshot_every_n: int,
-           is_testing_while_training: bool, test_every_n: int, *, options: Optional[LoopOptions] = None) -> dict:
-    """options: the loop's switches (fosvos_hip.options.LoopOptions); None = from the environment as it is now."""
+           is_testing_while_training: bool, test_every_n: int, *, options: Optional[LoopOptions] = None,
+           microbatch_group: int = 1) -> dict:
+    """options: the loop's switches (fosvos_hip.options.LoopOptions); None = from the environment as it is now.
+    microbatch_group: 1 = the reference's loop, one minibatch per pass.  N > 1: the one-frame minibatches of an accumulation
+    cycle run as batched passes of up to N frames of one shape (``options.group_window`` minibatches are looked at together;
+    ``options.microbatch_group`` is the online loop's and is not read here).  The weights are constant inside a cycle and its
+    gradient is a sum, so only the order of fp32 additions changes; every frame keeps the class weights of its own label."""
     if options is None:
         options = LoopOptions.from_env()
+    microbatch_group = int(microbatch_group)
+    if microbatch_group < 1:
+        raise ValueError('microbatch_group must be at least 1, got {}'.format(microbatch_group))
+    if microbatch_group > 1 and data_parallel:
+        raise ValueError('microbatch_group > 1 with data_parallel: that mode splits every BATCH over the ranks with class '
+                         'counts of the whole batch; a grouped pass keeps the counts per frame')
     log.info('Start of offline training')
     net = net_provider.network
     flags = getattr(net, 'pass_flags', None) or PassFlags()  # (a module without the native engine: a throw-away set)
@@ -99,8 +158,73 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     loss_train, loss_test, losses_train = [], [], []
     counter_gradient = 0
     n_iters = 0
+    n_passes = 0
+    max_window = max(microbatch_group, options.group_window)
+    ones = torch.ones((microbatch_group, 5), device=device) if microbatch_group > 1 else None  # seed of a batched backward pass
+    reserved_frames = getattr(net, 'reserve_arena_frames', None)
+
+    def log_epoch(epoch, running, n_images, start_time):
+        if world > 1:  # every rank holds its shards' part of the batch losses: the logged value is their sum
+            torch.distributed.all_reduce(running, op=torch.distributed.ReduceOp.SUM)
+        vals = (running / n_samples_train).tolist()  # one device->host sync per epoch
+        loss_train.append(vals[-1])
+        losses_train.append(vals)  # all five deeply supervised losses of the epoch
+        summary_writer.add_scalar('data/total_loss_epoch', vals[-1], epoch)
+        log.info('[Epoch: %d, numImages: %5d]' % (epoch, n_images))
+        for l in range(len(vals)):
+            log.info('Loss %d: %f' % (l, vals[l]))
+        log.info('Execution time: ' + str(timeit.default_timer() - start_time))
+
+    def step_if_due():
+        nonlocal counter_gradient
+        if counter_gradient % local_accum == 0:
+            net.join_gradients()
+            sync.finish()  # the bucketed all-reduce begun right behind the cycle's last backward pass
+            optimizer.step()
+            flat.zero()
+            counter_gradient = 0
+
+    def run_window(window, epoch, running):
+        """The minibatches of `window` (inside one accumulation cycle and one epoch, draw order) as the passes of
+        plan_passes; `running` takes the five loss sums of every frame."""
+        nonlocal counter_gradient, n_iters, n_passes
+        w = 1 - epoch / n_epochs
+        map_scale = [w / avg_grad_every_n] * 4 + [1.0 / avg_grad_every_n]
+        for idx, batched in plan_passes([mb['image'].shape for mb in window], microbatch_group):
+            if not batched:  # today's pass: class counts over the whole minibatch tensor
+                losses = _losses(net, window[idx[0]])
+                running += torch.stack([l.detach() for l in losses])
+                loss = w * sum(losses[:-1]) + losses[-1]
+                loss.backward(torch.full_like(loss.detach(), 1.0 / avg_grad_every_n))
+            else:
+                if len(idx) == 1:
+                    inputs, gts = window[idx[0]]['image'], window[idx[0]]['gt']
+                else:
+                    inputs = torch.cat([window[i]['image'] for i in idx])
+                    gts = torch.cat([window[i]['gt'] for i in idx])
+                inputs, gts = gpu_handler.cast_cuda_if_possible([inputs, gts])
+                # the loss in three places, as in the online loop: the class counts in front of the forward pass (they need
+                # no logits), ONE launch for the five maps' gradients between the passes, the values behind the backward pass
+                staged = None
+                if options.stage_loss and gts.is_cuda and class_balanced_cross_entropy_loss is _hip_cbce:
+                    staged = stage_frames_loss_multi(gts.contiguous().float(), 5)
+                    if staged is not None:
+                        gts = staged.label
+                outputs = net.forward(inputs)
+                losses, seed = _losses_frames(outputs, gts, map_scale, ones, staged)
+                losses.backward(seed)
+                if staged is not None:
+                    staged.finish()
+                running += losses.detach().sum(0)  # (queued behind finish(): no host sync)
+            counter_gradient += len(idx)
+            n_iters += len(idx)
+            n_passes += 1
+        step_if_due()
+
     time_all_start = timeit.default_timer()
     net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
+    if microbatch_group > 1 and reserved_frames is not None:
+        net.reserve_arena_frames = min(microbatch_group, avg_grad_every_n)  # (a pass never holds more frames than a cycle)
     if not options.defer_join:
         net.join_gradients()
     # weights are constant inside an accumulation cycle: let the next forward overlap the wgrad tail of this backward
@@ -114,22 +238,23 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
             if hasattr(sampler, 'set_epoch'):
                 sampler.set_epoch(epoch)
             running = torch.zeros(5, device=device)
+            window = []
             for index, minibatch in enumerate(data_loader_train):
+                if microbatch_group > 1:
+                    end_of_epoch = index % n_samples_train == n_samples_train - 1
+                    window.append(minibatch)
+                    if window_closes(len(window), counter_gradient, local_accum, max_window, end_of_epoch):
+                        run_window(window, epoch, running)
+                        window = []
+                    if end_of_epoch:
+                        log_epoch(epoch, running, index + 1, start_time)
+                    continue
                 losses = _losses(net, minibatch)
                 running += torch.stack([l.detach() for l in losses])
                 loss = (1 - epoch / n_epochs) * sum(losses[:-1]) + losses[-1]
 
                 if index % n_samples_train == n_samples_train - 1:
-                    if world > 1:  # every rank holds its shards' part of the batch losses: the logged value is their sum
-                        torch.distributed.all_reduce(running, op=torch.distributed.ReduceOp.SUM)
-                    vals = (running / n_samples_train).tolist()  # one device->host sync per epoch
-                    loss_train.append(vals[-1])
-                    losses_train.append(vals)  # all five deeply supervised losses of the epoch
-                    summary_writer.add_scalar('data/total_loss_epoch', vals[-1], epoch)
-                    log.info('[Epoch: %d, numImages: %5d]' % (epoch, index + 1))
-                    for l in range(len(vals)):
-                        log.info('Loss %d: %f' % (l, vals[l]))
-                    log.info('Execution time: ' + str(timeit.default_timer() - start_time))
+                    log_epoch(epoch, running, index + 1, start_time)
 
                 # `loss /= nAveGrad; loss.backward()` of the reference, as a backward pass seeded with 1/nAveGrad (same
                 # gradient, three fewer tiny kernels: see train_online._train)
@@ -141,13 +266,10 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
                     sync.begin()
                 counter_gradient += 1
                 n_iters += 1
-
-                if counter_gradient % local_accum == 0:
-                    net.join_gradients()
-                    sync.finish()  # the bucketed all-reduce begun right behind the cycle's last backward pass
-                    optimizer.step()
-                    flat.zero()
-                    counter_gradient = 0
+                n_passes += 1
+                step_if_due()
+            if window:  # (a loader that ended before its own length)
+                run_window(window, epoch, running)
 
             if (epoch % snapshot_every_n) == snapshot_every_n - 1 and epoch != 0 and parallel.rank() == 0:
                 net_provider.save_model(epoch)
@@ -166,14 +288,16 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     finally:  # whatever happened in the loop, the caller's module does not keep the deferred join
         net.join_gradients()
         flags.defer_wgrad_join = False
+        if microbatch_group > 1 and reserved_frames is not None:
+            net.reserve_arena_frames = reserved_frames
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     return {'loss_train': loss_train, 'loss_test': loss_test, 'losses_train': losses_train, 'iterations': n_iters,
-            'seconds': timeit.default_timer() - time_all_start}
+            'passes': n_passes, 'seconds': timeit.default_timer() - time_all_start}
 
 
 def main(argv=None):
-    global db_root_dir, synthetic_size, data_parallel, resident_train_set
+    global db_root_dir, synthetic_size, data_parallel, resident_train_set, microbatch_group
     args = args_helper.parse_args(is_online=False, argv=argv)
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')
@@ -182,6 +306,7 @@ def main(argv=None):
     db_root_dir = P.db_root_dir()
     synthetic_size = (args.height, args.width) if args.synthetic else None
     resident_train_set = bool(args.resident_train_set)
+    microbatch_group = args.microbatch_group
     save_dir_models.mkdir(parents=True, exist_ok=True)
     save_dir_results.mkdir(parents=True, exist_ok=True)
 

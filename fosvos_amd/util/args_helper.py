@@ -3,7 +3,7 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --resident-train-set (offline only), --score, --fast-test and --png-fitted (online only).
+--data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test and --png-fitted (online only).
 """
 import argparse
 from typing import List, Optional
@@ -52,7 +52,16 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--resident-train-set', action='store_true',
                             help='decode the training set once, keep it on the GPU and flip / rescale each draw there '
                                  '(same samples as the per-iteration DataLoader under the same seed)')
+        parser.add_argument('--microbatch-group', default=1, type=int, metavar='N',
+                            help='run the one-frame minibatches of an accumulation cycle as batched passes of up to N '
+                                 'frames of one shape (every frame keeps the class weights of its own label; 1 = one '
+                                 'minibatch per pass, the reference\'s order)')
     args = parser.parse_args(argv)
+    if not is_online and args.microbatch_group < 1:
+        parser.error('--microbatch-group counts frames per pass: at least 1')
+    if not is_online and args.microbatch_group > 1 and args.data_parallel:
+        parser.error('--microbatch-group above 1 does not combine with --data-parallel (that mode splits every batch with '
+                     'class counts of the whole batch)')
     if is_online and args.png_fitted and not args.fast_test:
         parser.error('--png-fitted chooses the codes of the device PNG encoder: it needs --fast-test')
     args.is_training = not args.no_training

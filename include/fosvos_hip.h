@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 23
+#define FOSVOS_ABI_VERSION 24
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -327,6 +327,20 @@ int fosvos_cbce_loss_frames(const float *logits, const float *label, int64_t fra
 int fosvos_cbce_loss_frames_parts(const float *logits, const float *label, int64_t frame_numel, int n_frames,
                                   int size_average, float grad_scale, float *loss_out, float *grad, void *workspace,
                                   size_t workspace_bytes, int parts, int device, void *stream);
+/* The per-frame loss of n_maps LOGIT MAPS THAT SHARE ONE LABEL BATCH (the offline objective: four side maps and the fused
+ * map per frame, src/train_offline.py:85-91), with the stages of the call above.  logits / grad: HOST arrays of n_maps
+ * device pointers, each [n_frames][frame_numel] (separate tensors; grad, or any entry of it, may be NULL); map_scale: n_maps
+ * HOST floats, map m's gradient is multiplied by map_scale[m]; loss_out: [n_frames][n_maps] UNWEIGHTED loss values.  One
+ * count per frame serves all maps and one launch writes every gradient: a thread reads its labels once and walks the maps
+ * (4 + n_maps x 8 bytes per pixel against n_maps x 16).  For every frame and map the result equals fosvos_cbce_loss_frames
+ * on that map with grad_scale = map_scale[m], bit for bit.  1 <= n_maps <= FOSVOS_CBCE_MAX_MAPS; frame_numel a multiple of 4
+ * when n_frames > 1; workspace: fosvos_cbce_multi_workspace_bytes, shared by the stages of one loss.  Arguments a stage does
+ * not read may be NULL (COUNT: logits, map_scale, loss_out, grad; FINISH: logits, label, map_scale, grad). */
+#define FOSVOS_CBCE_MAX_MAPS 8
+size_t fosvos_cbce_multi_workspace_bytes(int64_t frame_numel, int n_frames, int n_maps);
+int fosvos_cbce_loss_frames_multi(const float *const *logits, const float *label, int64_t frame_numel, int n_frames,
+                                  int n_maps, int size_average, const float *map_scale, float *loss_out, float *const *grad,
+                                  void *workspace, size_t workspace_bytes, int parts, int device, void *stream);
 /* The same loss on ONE SHARD of a batch that is split over data-parallel ranks.  The reference counts positives /
  * negatives over the whole batch tensor (src/layers/osvos_layers.py:28-39), so the class weights of a shard must
  * come from the whole batch: batch_counts = DEVICE double[2] {positives, pixels} summed over all shards (the caller
