@@ -93,8 +93,6 @@ __global__ __launch_bounds__(kEvalThreads) void k_minmax(const float *__restrict
     }
 }
 
-__device__ __forceinline__ double sigmoid_f64(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
-
 __device__ __forceinline__ unsigned prob_byte(float x, double cmin, double k) {
     const double scaled = (sigmoid_f64(x) - cmin) * k;
     return (unsigned)(fmin(fmax(scaled, 0.0), 255.0) + 0.5);

@@ -1233,3 +1233,78 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengt
                                   wsn, dev, st), "png_encode")
     _pe(e0, "png_encode", 0.0, 2.0 * n * h * w)
     return out, lengths
+
+
+# ------------------------------------------------------------------------------------------ streaming inference (stream.hip)
+OVERLAY_CHANNEL = {'b': 0, 'g': 1, 'r': 2}
+_MEAN_BGR = None
+
+
+def _mean_bgr():
+    """The dataset mean the frames lose in front of the net: the one constant of dataloaders/davis_2016.py."""
+    global _MEAN_BGR
+    if _MEAN_BGR is None:
+        import ctypes
+        from dataloaders.davis_2016 import MEANVAL
+        _MEAN_BGR = (ctypes.c_float * 3)(*MEANVAL)
+    return _MEAN_BGR
+
+
+def _frame_shape(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    _need_eval(frames, torch.uint8, f"{what} frames")
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError(f"{what}: frames must be a non-empty [N,H,W,3], got {tuple(frames.shape)}")
+    return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+
+
+def _out_like(out: Optional[torch.Tensor], shape, dtype, like: torch.Tensor, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    _need_eval(out, dtype, f"{what} out")
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what}: out must be {tuple(shape)}, got {tuple(out.shape)}")
+    if out.device != like.device:
+        raise RuntimeError(f"{what}: every tensor must be on {like.device}, got one on {out.device}")
+    return out
+
+
+def frame_prep(frames_u8: torch.Tensor, mirror: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_frame_prep: raw frames uint8 [N,H,W,3] (BGR) -> the net's input fp32 [N,3,H,W]: ``float32(byte) - MEANVAL[c]``,
+    flipped left to right with ``mirror`` (util/frame_overlay.prepare_frame, bit for bit).  One launch on the current
+    stream, no synchronisation."""
+    n, h, w = _frame_shape(frames_u8, "frame_prep")
+    out = _out_like(out, (n, 3, h, w), _F32, frames_u8, "frame_prep")
+    dev, st = _ctx(frames_u8)
+    e0 = _pb()
+    check(lib().fosvos_frame_prep(frames_u8.data_ptr(), n, h, w, 1 if mirror else 0, _mean_bgr(), out.data_ptr(), dev, st),
+          "frame_prep")
+    _pe(e0, "frame_prep", 0.0, 15.0 * n * h * w)
+    return out
+
+
+def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False, boolean_mask: bool = True, color: str = 'r',
+            alpha: float = 1.0, overlay: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_overlay: raw frames uint8 [N,H,W,3] and the logits fp32 [N,1,H,W] the net made of them (of the mirrored
+    frames, with ``mirror``) -> uint8 [N,H,W,3], the (mirrored) frames with ``alpha * 255 * p`` added to the channel of
+    ``color`` and clamped at 255; p is the mask ``logit >= 0`` (``boolean_mask``) or the fp64 sigmoid.  ``overlay=False``:
+    uint8 [N,H,W], the mask as 0 / 255 or ``255 p`` rounded half up.  util/frame_overlay.py states the bytes.  One launch on
+    the current stream, no synchronisation."""
+    n, h, w = _frame_shape(frames_u8, "overlay")
+    _need_eval(logits, _F32, "overlay logits")
+    if tuple(logits.shape) != (n, 1, h, w):
+        raise ValueError(f"overlay: logits must be {(n, 1, h, w)}, got {tuple(logits.shape)}")
+    if logits.device != frames_u8.device:
+        raise RuntimeError(f"overlay: every tensor must be on {frames_u8.device}, got one on {logits.device}")
+    if color not in OVERLAY_CHANNEL:
+        raise ValueError(f"overlay: color must be one of {tuple(OVERLAY_CHANNEL)}, got {color!r}")
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and alpha != float("inf")):
+        raise ValueError(f"overlay: alpha must be a finite number >= 0, got {alpha!r}")
+    out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay")
+    mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
+    dev, st = _ctx(frames_u8)
+    e0 = _pb()
+    check(lib().fosvos_overlay(frames_u8.data_ptr(), logits.data_ptr(), n, h, w, 1 if mirror else 0, mode,
+                               OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st), "overlay")
+    _pe(e0, "overlay", 0.0, (10.0 if overlay else 5.0) * n * h * w)
+    return out

@@ -1,0 +1,205 @@
+"""Streaming inference: raw uint8 camera frames through a net, the frame that is shown back, ``depth`` frames in flight.
+
+What the reference does per frame on the host (src/run_webcam.py:81-133, ``apply_network``) happens on the device here:
+``ops.frame_prep`` in front of the net and ``ops.overlay`` behind it (csrc/stream.hip; util/frame_overlay.py states both).
+Only the raw bytes cross the bus, 3 B a pixel each way (1 B back without overlay).
+
+A segmenter owns ``depth`` SLOTS; a slot is everything one frame in flight needs, allocated once:
+
+    pinned host frame -> device frame (uint8) -> device image (fp32) -> [net] -> device output (uint8) -> pinned host output
+
+and two events.  Per frame:
+
+    upload stream    H2D frame, record slot.moved
+    net's stream     wait slot.moved; frame_prep, net.forward, overlay; record slot.computed
+    download stream  wait slot.computed; D2H output, record slot.moved
+
+``slot.moved`` marks the slot's last copy: first the upload (the net's stream waits for it as soon as it is recorded),
+then the download, which is the one event the host ever waits on - when it retires the slot.  Nothing synchronises a stream
+or the device per frame.  A slot is reused only after it was retired, so its upload cannot overtake the overlay that still
+reads the previous frame.  The net's stream is the current stream at ``submit``; the two copy streams are the segmenter's
+own (two, so that the upload of frame k+1 does not queue behind the download of frame k, which waits for the net).
+
+Not thread-safe: one host thread drives a segmenter.
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import Deque, Iterable, Iterator, List, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class _Slot:
+    def __init__(self, h: int, w: int, out_shape, device: torch.device) -> None:
+        self.host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
+        self.host_in_np = self.host_in.numpy()
+        self.frame = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
+        self.image = torch.empty((1, 3, h, w), dtype=torch.float32, device=device)
+        self.out = torch.empty(out_shape, dtype=torch.uint8, device=device)
+        self.host_out = torch.empty(out_shape, dtype=torch.uint8, pin_memory=True)
+        self.host_out_np = self.host_out.numpy()
+        self.moved = torch.cuda.Event()
+        self.computed = torch.cuda.Event()
+
+
+class FrameSegmenter:
+    """``FrameSegmenter(net, height, width)``: ``net`` is any module of this project (OSVOS_VGG, OSVOS_RESNET, a pruned
+    whole-module pickle) on a GPU; the segmenter calls ``net.forward(x)[-1]`` under ``no_grad`` with
+    ``net.compute_side_outputs = False`` for the call.
+
+    submit(frame)    queue one uint8 [H,W,3] BGR frame; blocks only when all ``depth`` slots are in flight (it then retires
+                     the oldest and keeps its output for ``result``)
+    result()         the oldest frame's output as an array of its own: uint8 [H,W,3], or [H,W] with ``overlay=False``
+    segment(frames)  generator: outputs in input order, ``depth`` frames in flight
+    apply(frame)     one frame, synchronously
+    close()          wait for what is in flight and release every buffer
+    """
+
+    def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
+                 boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0) -> None:
+        from util import frame_overlay
+        self.height, self.width, self.depth = int(height), int(width), int(depth)
+        if self.height <= 0 or self.width <= 0 or self.depth <= 0:
+            raise ValueError(f"FrameSegmenter: height, width and depth must be positive, got {height}, {width}, {depth}")
+        frame_overlay.check_color(color)
+        self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
+        self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
+        self.net = net
+        param = next(iter(net.parameters()), None)
+        if param is None or not param.is_cuda:
+            raise RuntimeError("FrameSegmenter: the net must live on the GPU (the HIP path has no CPU fallback)")
+        self.device = param.device
+        h, w = self.height, self.width
+        out_shape = (1, h, w, 3) if self.overlay else (1, h, w)
+        self._closed = False
+        with torch.cuda.device(self.device):
+            self._up = torch.cuda.Stream(device=self.device)
+            self._down = torch.cuda.Stream(device=self.device)
+            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device) for _ in range(self.depth)]
+        self._flight: Deque[_Slot] = deque()     # submitted, oldest first
+        self._ready: Deque[np.ndarray] = deque()  # retired by a submit that needed the slot, not yet asked for
+
+    # ---------------------------------------------------------------------------------------------- checks
+    def _check_open(self) -> None:
+        if self._closed:
+            raise RuntimeError("FrameSegmenter: closed")
+
+    def _check_frame(self, frame) -> np.ndarray:
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8:
+            raise ValueError(f"FrameSegmenter: a frame must be a uint8 numpy array, got {getattr(frame, 'dtype', type(frame))}")
+        if frame.shape != (self.height, self.width, 3):
+            raise ValueError(f"FrameSegmenter: a frame must be {(self.height, self.width, 3)}, got {frame.shape}")
+        return frame
+
+    @property
+    def pending(self) -> int:
+        """Frames submitted whose output has not been returned yet."""
+        return len(self._flight) + len(self._ready)
+
+    # ---------------------------------------------------------------------------------------------- the pipeline
+    def _retire(self) -> np.ndarray:
+        slot = self._flight[0]
+        slot.moved.synchronize()  # the download of this slot, nothing else
+        out = np.array(slot.host_out_np[0], copy=True)
+        self._flight.popleft()
+        self._free.append(slot)
+        return out
+
+    def _enqueue(self, slot: _Slot, main: torch.cuda.Stream) -> None:
+        with torch.cuda.stream(self._up):
+            slot.frame.copy_(slot.host_in, non_blocking=True)
+            slot.moved.record(self._up)
+        main.wait_event(slot.moved)
+        net = self.net
+        had, old = hasattr(net, 'compute_side_outputs'), getattr(net, 'compute_side_outputs', None)
+        net.compute_side_outputs = False
+        try:
+            with torch.no_grad():
+                ops.frame_prep(slot.frame, self.mirror, out=slot.image)
+                logits = net.forward(slot.image)[-1]
+                ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
+                            out=slot.out)
+        finally:
+            if had:
+                net.compute_side_outputs = old
+            else:
+                del net.compute_side_outputs
+        slot.computed.record(main)
+        with torch.cuda.stream(self._down):
+            self._down.wait_event(slot.computed)
+            slot.host_out.copy_(slot.out, non_blocking=True)
+            slot.moved.record(self._down)
+
+    def submit(self, frame: np.ndarray) -> None:
+        self._check_open()
+        frame = self._check_frame(frame)  # raises before anything is queued
+        if not self._free:
+            self._ready.append(self._retire())
+        slot = self._free.pop()
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            try:
+                np.copyto(slot.host_in_np[0], frame)
+                self._enqueue(slot, main)
+            except BaseException:
+                # never half-queued: whatever part of the frame was queued runs out, then the slot is free again
+                try:
+                    for st in (self._up, main, self._down):
+                        st.synchronize()
+                    self._free.append(slot)
+                except Exception:
+                    self.close()
+                raise
+        self._flight.append(slot)
+
+    def result(self) -> np.ndarray:
+        self._check_open()
+        if self._ready:
+            return self._ready.popleft()
+        if not self._flight:
+            raise RuntimeError("FrameSegmenter.result: no frame is in flight")
+        return self._retire()
+
+    def segment(self, frames: Iterable[np.ndarray]) -> Iterator[np.ndarray]:
+        self._check_open()
+        if self.pending:
+            raise RuntimeError("FrameSegmenter.segment: fetch the results of the frames already submitted first")
+        for frame in frames:
+            if len(self._flight) == self.depth:
+                yield self.result()
+            self.submit(frame)
+        while self.pending:
+            yield self.result()
+
+    def apply(self, frame: np.ndarray) -> np.ndarray:
+        self._check_open()
+        if self.pending:
+            raise RuntimeError("FrameSegmenter.apply: fetch the results of the frames already submitted first")
+        self.submit(frame)
+        return self.result()
+
+    def close(self) -> None:
+        if self._closed:
+            return
+        self._closed = True
+        for slot in self._flight:
+            try:
+                slot.moved.synchronize()
+            except Exception:  # a failed device: the buffers go either way
+                pass
+        self._flight.clear()
+        self._ready.clear()
+        self._free = []
+        self._up = self._down = None
+        self.net = None
+
+    def __enter__(self) -> "FrameSegmenter":
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self.close()
+        return False

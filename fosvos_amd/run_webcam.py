@@ -1,0 +1,202 @@
+"""The live demo's loop (reference: src/run_webcam.py) without its window: frames from a camera, a directory of images or
+the synthetic sequence go through ``fosvos_hip.stream.FrameSegmenter`` - prep, net and overlay on the device, ``depth``
+frames in flight - and the results are written as PNGs and / or timed.
+
+The options carry the reference's names and defaults.  Additions: ``--model`` (a checkpoint file instead of
+``models/<the reference's file name>``), ``--source DIR``, ``--synthetic N`` (with ``--height`` / ``--width``), ``--output DIR``
+and ``--depth``.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+"""
+import argparse
+import os
+import sys
+import time
+from pathlib import Path
+from typing import Iterator, List, Optional
+
+import numpy as np
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+from dataloaders import synthetic  # noqa: E402
+from dataloaders.davis_2016 import MEANVAL, read_bgr  # noqa: E402
+from networks.osvos_resnet import OSVOS_RESNET  # noqa: E402
+from networks.osvos_vgg import OSVOS_VGG  # noqa: E402
+from util.logger import get_logger  # noqa: E402
+
+log = get_logger(__file__)
+log.setLevel('INFO')
+
+IMAGE_SUFFIXES = ('.jpg', '.jpeg', '.png', '.bmp')
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, allow_abbrev=False)
+    p.add_argument('--variant', '-var', choices=['vgg', 'resnet', 'prune', 'mimic'], default='resnet')
+    p.add_argument('--version', '-ver', type=int, default=None)
+    p.add_argument('--webcam', '-wc', type=int, default=0, help='camera index, used when neither --source nor --synthetic is given')
+
+    def switch(on, off, dest, default=True):
+        p.add_argument(*on, dest=dest, action='store_true', default=default)
+        p.add_argument(*off, dest=dest, action='store_false')
+
+    switch(('--mirror', '-m'), ('--no-mirror', '-nm'), 'mirror')
+    switch(('--use-network', '-n'), ('--no-network', '-nn'), 'use_network')
+    switch(('--use-cuda', '-c'), ('--no-cuda', '-nc'), 'use_cuda')
+    switch(('--overlay', '-o'), ('--no-overlay', '-no'), 'overlay')
+    switch(('--boolean-mask', '-bm'), ('--no-boolean-mask', '-nbm'), 'boolean_mask')
+    p.add_argument('--overlay-color', '-oc', choices=['r', 'g', 'b'], default='r')
+    p.add_argument('--overlay-alpha', '-oa', type=float, default=1.0)
+    # not in the reference
+    p.add_argument('--model', type=str, default=None, help='checkpoint file (default: models/<the variant\'s file name>)')
+    p.add_argument('--source', type=str, default=None, help='directory of image files, read in sorted order')
+    p.add_argument('--synthetic', type=int, default=None, metavar='N', help='N frames of the synthetic sequence')
+    p.add_argument('--height', type=int, default=480)
+    p.add_argument('--width', type=int, default=854)
+    p.add_argument('--output', type=str, default=None, help='directory the results are written to as PNGs')
+    p.add_argument('--depth', type=int, default=2, help='frames in flight')
+    return p
+
+
+def model_file_name(variant: str, version: Optional[int]) -> str:
+    """The reference's file names (src/run_webcam.py:43-62)."""
+    if variant == 'vgg':
+        return 'vgg16.pth'
+    if variant == 'resnet':
+        return 'resnet{}.pth'.format(34 if version == 34 else 18)
+    if variant == 'prune':
+        return 'prune_64_1_{}.pth'.format(version)
+    if variant == 'mimic':
+        raise Exception('Not yet implemented')
+    raise Exception('argparse should have prevented this')
+
+
+def get_network(variant: str, version: Optional[int], path_models: str = 'models', model: Optional[str] = None) -> torch.nn.Module:
+    path_file = Path(model) if model is not None else Path(path_models) / model_file_name(variant, version)
+    if variant == 'mimic':
+        raise Exception('Not yet implemented')
+
+    def keep(storage, loc):
+        return storage
+
+    if variant == 'vgg':
+        net = OSVOS_VGG(pretrained=False)
+        net.load_state_dict(torch.load(str(path_file), map_location=keep))
+    elif variant == 'resnet':
+        net = OSVOS_RESNET(pretrained=False, version=34 if version == 34 else 18)
+        net.load_state_dict(torch.load(str(path_file), map_location=keep))
+    elif variant == 'prune':
+        net = torch.load(str(path_file), map_location=keep, weights_only=False)  # a whole-module pickle
+    else:
+        raise Exception('argparse should have prevented this')
+    return net
+
+
+# ---------------------------------------------------------------------------------------------- frame sources
+def synthetic_frame(h: int, w: int, index: int) -> np.ndarray:
+    """Frame ``index`` of dataloaders/synthetic.py as a camera would deliver it: uint8 [H,W,3] BGR (the mean back on)."""
+    img, _ = synthetic.make_frame(h, w, index=index)
+    img = img + torch.tensor(MEANVAL).view(3, 1, 1)
+    return np.ascontiguousarray(img.round().clamp(0, 255).to(torch.uint8).permute(1, 2, 0).numpy())
+
+
+def synthetic_frames(n: int, h: int, w: int) -> Iterator[np.ndarray]:
+    for k in range(n):
+        yield synthetic_frame(h, w, k)
+
+
+def source_files(directory: str) -> List[str]:
+    names = sorted(f for f in os.listdir(directory) if f.lower().endswith(IMAGE_SUFFIXES))
+    if not names:
+        raise FileNotFoundError('--source {}: no image files'.format(directory))
+    return [os.path.join(directory, f) for f in names]
+
+
+def open_webcam(index: int):
+    try:
+        import cv2
+    except ImportError:
+        raise RuntimeError('--webcam needs OpenCV (cv2) for the capture and it is not installed: '
+                           'read frames from image files with --source DIR instead') from None
+    return cv2.VideoCapture(index)
+
+
+def webcam_frames(cam) -> Iterator[np.ndarray]:
+    while True:
+        ok, img = cam.read()
+        if not ok:
+            return
+        yield np.ascontiguousarray(img)
+
+
+# ---------------------------------------------------------------------------------------------- the loop
+def write_png(directory: Path, index: int, out: np.ndarray) -> None:
+    from PIL import Image
+    if out.ndim == 3:
+        im = Image.fromarray(np.ascontiguousarray(out[:, :, ::-1]))  # BGR -> RGB
+    else:
+        im = Image.fromarray(out, mode='L')
+    im.save(str(directory / ('%05d.png' % index)))
+
+
+def loop_frames(results: Iterator[np.ndarray], output: Optional[Path]) -> List[float]:
+    """Takes the results as they come, logs the rate of each (the reference's line) and writes them."""
+    rates = []
+    start_time = time.time()
+    for index, out in enumerate(results):
+        if output is not None:
+            write_png(output, index, out)
+        now = time.time()
+        rates.append(1.0 / max(now - start_time, 1e-9))
+        log.info('FPS: {0:0.1f}'.format(rates[-1]))
+        start_time = now
+    if rates:
+        log.info('Mean FPS: {0:0.1f} over {1} frames'.format(len(rates) / sum(1.0 / r for r in rates), len(rates)))
+    return rates
+
+
+def main(argv=None) -> List[float]:
+    args = build_parser().parse_args(argv)
+    if not args.use_cuda:
+        raise RuntimeError('--no-cuda: the HIP path has no CPU fallback')
+    if args.variant == 'mimic' and args.use_network:
+        raise Exception('Not yet implemented')
+    if args.source is not None and args.synthetic is not None:
+        raise ValueError('choose one of --source and --synthetic')
+    cam = None
+    if args.synthetic is not None:
+        frames = synthetic_frames(args.synthetic, args.height, args.width)
+    elif args.source is not None:
+        frames = (read_bgr(f) for f in source_files(args.source))
+    else:
+        cam = open_webcam(args.webcam)
+        frames = webcam_frames(cam)
+    output = None
+    if args.output is not None:
+        output = Path(args.output)
+        output.mkdir(parents=True, exist_ok=True)
+    try:
+        if not args.use_network:
+            return loop_frames((np.ascontiguousarray(f[:, ::-1]) if args.mirror else f for f in frames), output)
+        net = get_network(args.variant, args.version, model=args.model).cuda().eval()  # (the nets here run eval-mode BatchNorm only)
+        first = next(frames, None)
+        if first is None:
+            return []
+        from fosvos_hip.stream import FrameSegmenter
+
+        def chained():
+            yield first
+            yield from frames
+
+        with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
+                            boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha) as seg:
+            return loop_frames(seg.segment(chained()), output)
+    finally:
+        if cam is not None:
+            cam.release()
+
+
+if __name__ == '__main__':
+    main()

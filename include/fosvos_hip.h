@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 24
+#define FOSVOS_ABI_VERSION 25
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -445,6 +445,31 @@ int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, s
 size_t fosvos_png_workspace_bytes_mode(int N, int H, int W, int huffman);
 int fosvos_png_encode_mode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
                            int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* ---- streaming inference: a raw camera frame in, the frame that is shown out -----------------------------------------
+ * The per-frame arithmetic of src/run_webcam.py:81-133 (apply_network) on the device beside the nets; the definitions are
+ * stated in numpy in util/frame_overlay.py.  One launch each on `stream`, no workspace, no library state.
+ *
+ * fosvos_frame_prep: frames uint8 [N,H,W,3] (BGR, as a camera or cv2.imread delivers them) -> image fp32 [N,3,H,W]:
+ * image[n][c][y][x] = (float)frames[n][y][xs][c] - mean[c], xs = x, or W-1-x with `mirror`.  `mean` is read on the host
+ * and travels in the kernel arguments.  Exactly numpy's float32(byte) - float32(mean).  3 B read, 12 B written per pixel.
+ * replaces: cv2.flip, `img - mean_value` and to_tensor of src/run_webcam.py:71-72, 84-85, 101-107 and the fp32 upload.
+ *
+ * fosvos_overlay: frames as above and logits fp32 [N,1,H,W] (of the mirrored frame, if `mirror`) -> out uint8.
+ *   mode 0  boolean overlay  out [N,H,W,3]: the (mirrored) frame with byte b of channel `channel` (0 b, 1 g, 2 r)
+ *                            replaced by (uint8)min(b + (alpha * 255) * p, 255) in fp64, p = 1 where logit >= 0 (+0.0
+ *                            and -0.0 alike) else 0
+ *   mode 1  soft overlay     the same with p = 1 / (1 + exp(-(double)logit)), operation for operation in fp64
+ *   mode 2  boolean mask     out [N,H,W]: 255 where logit >= 0 else 0 (`frames`, `mirror`, `channel`, `alpha` unused)
+ *   mode 3  soft mask        out [N,H,W]: (uint8)(255 p + 0.5)
+ * alpha finite and >= 0.  NaN-free logits only.  The boolean modes are exact; a soft byte can differ from the host's where
+ * the fp64 value lies within an ulp of exp() of a rounding boundary.  7 B read and 3 B written per pixel (4 and 1 in the
+ * mask modes).  Neither pointer needs more than its type's alignment: 16-byte accesses are used wherever they are aligned.
+ * replaces: to_numpy, the >= 0.5 threshold and perform_overlay of src/run_webcam.py:89-98, 110-133 and the fp32 download. */
+int fosvos_frame_prep(const uint8_t *frames, int N, int H, int W, int mirror, const float mean[3], float *image, int device,
+                      void *stream);
+int fosvos_overlay(const uint8_t *frames, const float *logits, int N, int H, int W, int mirror, int mode, int channel,
+                   double alpha, uint8_t *out, int device, void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
