@@ -20,12 +20,21 @@ or the device per frame.  A slot is reused only after it was retired, so its upl
 reads the previous frame.  The net's stream is the current stream at ``submit``; the two copy streams are the segmenter's
 own (two, so that the upload of frame k+1 does not queue behind the download of frame k, which waits for the net).
 
+``encode='jpeg'`` (opt-in) adds ``ops.jpeg_encode`` behind the overlay (csrc/jpeg.hip; util/jpeg_layout.py states the file)
+and the slot ends in a device file buffer with its length in front:
+
+    ... -> device output (uint8) -> device [length | file, capacity bytes] -> pinned host [length | first ``budget`` bytes]
+
+The download is ONE copy of the length and the first ``budget`` bytes of the file (a constructor-time constant, by default
+a quarter of the raw output), so the host still waits on ``slot.moved`` alone; only a frame whose file is longer fetches the
+rest with a second copy, on a stream of its own, when it is retired.  ``encode=None`` is the object described above.
+
 Not thread-safe: one host thread drives a segmenter.
 """
 from __future__ import annotations
 
 from collections import deque
-from typing import Deque, Iterable, Iterator, List, Optional
+from typing import Deque, Iterable, Iterator, List, Optional, Union
 
 import numpy as np
 import torch
@@ -33,14 +42,23 @@ import torch
 from . import ops
 
 
+_HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that the file starts 8-byte aligned
+
+
 class _Slot:
-    def __init__(self, h: int, w: int, out_shape, device: torch.device) -> None:
+    def __init__(self, h: int, w: int, out_shape, device: torch.device, capacity: int = 0, budget: int = 0) -> None:
         self.host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
         self.host_in_np = self.host_in.numpy()
         self.frame = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
         self.image = torch.empty((1, 3, h, w), dtype=torch.float32, device=device)
         self.out = torch.empty(out_shape, dtype=torch.uint8, device=device)
-        self.host_out = torch.empty(out_shape, dtype=torch.uint8, pin_memory=True)
+        if capacity:
+            self.store = torch.empty((_HEAD + capacity,), dtype=torch.uint8, device=device)
+            self.length = self.store[:4].view(torch.int32)
+            self.file = self.store[_HEAD:].view(1, capacity)
+            self.host_out = torch.empty((_HEAD + budget,), dtype=torch.uint8, pin_memory=True)
+        else:
+            self.host_out = torch.empty(out_shape, dtype=torch.uint8, pin_memory=True)
         self.host_out_np = self.host_out.numpy()
         self.moved = torch.cuda.Event()
         self.computed = torch.cuda.Event()
@@ -53,14 +71,16 @@ class FrameSegmenter:
 
     submit(frame)    queue one uint8 [H,W,3] BGR frame; blocks only when all ``depth`` slots are in flight (it then retires
                      the oldest and keeps its output for ``result``)
-    result()         the oldest frame's output as an array of its own: uint8 [H,W,3], or [H,W] with ``overlay=False``
+    result()         the oldest frame's output as an array of its own: uint8 [H,W,3], or [H,W] with ``overlay=False``;
+                     with ``encode='jpeg'`` the same picture as ``bytes``, a complete .jpg file of quality ``quality``
     segment(frames)  generator: outputs in input order, ``depth`` frames in flight
     apply(frame)     one frame, synchronously
     close()          wait for what is in flight and release every buffer
     """
 
     def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
-                 boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0) -> None:
+                 boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
+                 quality: int = 90, budget: Optional[int] = None) -> None:
         from util import frame_overlay
         self.height, self.width, self.depth = int(height), int(width), int(depth)
         if self.height <= 0 or self.width <= 0 or self.depth <= 0:
@@ -75,13 +95,33 @@ class FrameSegmenter:
         self.device = param.device
         h, w = self.height, self.width
         out_shape = (1, h, w, 3) if self.overlay else (1, h, w)
+        if encode not in (None, 'jpeg'):
+            raise ValueError(f"FrameSegmenter: encode must be None or 'jpeg', got {encode!r}")
+        self.encode, self.quality = encode, quality
+        self.capacity = self.budget = 0
+        self.second_copies = 0  # frames whose file was longer than the budget
+        self.bytes_down = 0     # bytes the downloads moved
+        if encode:
+            if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+                raise ValueError(f"FrameSegmenter: quality must be an integer in 1..100, got {quality!r}")
+            self.capacity = ops.jpeg_capacity(h, w, 3 if self.overlay else 1)
+            raw = h * w * (3 if self.overlay else 1)
+            if budget is None:
+                budget = max(raw // 4, 1024)
+            if isinstance(budget, bool) or not isinstance(budget, int) or budget <= 0:
+                raise ValueError(f"FrameSegmenter: budget must be a positive number of bytes, got {budget!r}")
+            self.budget = min(budget, self.capacity)
+        elif budget is not None:
+            raise ValueError("FrameSegmenter: budget is the download budget of encode='jpeg'")
         self._closed = False
         with torch.cuda.device(self.device):
             self._up = torch.cuda.Stream(device=self.device)
             self._down = torch.cuda.Stream(device=self.device)
-            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device) for _ in range(self.depth)]
+            self._rest = torch.cuda.Stream(device=self.device) if encode else None  # second copies of long files
+            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget)
+                                       for _ in range(self.depth)]
         self._flight: Deque[_Slot] = deque()     # submitted, oldest first
-        self._ready: Deque[np.ndarray] = deque()  # retired by a submit that needed the slot, not yet asked for
+        self._ready: Deque[Union[np.ndarray, bytes]] = deque()  # retired by a submit that needed the slot, not yet asked for
 
     # ---------------------------------------------------------------------------------------------- checks
     def _check_open(self) -> None:
@@ -101,10 +141,22 @@ class FrameSegmenter:
         return len(self._flight) + len(self._ready)
 
     # ---------------------------------------------------------------------------------------------- the pipeline
-    def _retire(self) -> np.ndarray:
+    def _retire(self) -> Union[np.ndarray, bytes]:
         slot = self._flight[0]
         slot.moved.synchronize()  # the download of this slot, nothing else
-        out = np.array(slot.host_out_np[0], copy=True)
+        if self.encode:
+            length = int(slot.host_out_np[:4].view(np.int32)[0])
+            if not 0 < length <= self.capacity:
+                raise RuntimeError(f"FrameSegmenter: the encoder reported a file of {length} bytes (capacity {self.capacity})")
+            out = slot.host_out_np[_HEAD:_HEAD + min(length, self.budget)].tobytes()
+            self.bytes_down += _HEAD + self.budget
+            if length > self.budget:  # the slot's work is done: nothing to wait for but the copy itself
+                with torch.cuda.stream(self._rest):
+                    out += slot.file[0, self.budget:length].cpu().numpy().tobytes()
+                self.second_copies += 1
+                self.bytes_down += length - self.budget
+        else:
+            out = np.array(slot.host_out_np[0], copy=True)
         self._flight.popleft()
         self._free.append(slot)
         return out
@@ -123,6 +175,8 @@ class FrameSegmenter:
                 logits = net.forward(slot.image)[-1]
                 ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
                             out=slot.out)
+                if self.encode:
+                    ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length)
         finally:
             if had:
                 net.compute_side_outputs = old
@@ -131,7 +185,10 @@ class FrameSegmenter:
         slot.computed.record(main)
         with torch.cuda.stream(self._down):
             self._down.wait_event(slot.computed)
-            slot.host_out.copy_(slot.out, non_blocking=True)
+            if self.encode:
+                slot.host_out.copy_(slot.store[:_HEAD + self.budget], non_blocking=True)
+            else:
+                slot.host_out.copy_(slot.out, non_blocking=True)
             slot.moved.record(self._down)
 
     def submit(self, frame: np.ndarray) -> None:
@@ -194,7 +251,7 @@ class FrameSegmenter:
         self._flight.clear()
         self._ready.clear()
         self._free = []
-        self._up = self._down = None
+        self._up = self._down = self._rest = None
         self.net = None
 
     def __enter__(self) -> "FrameSegmenter":

@@ -3,8 +3,9 @@ the synthetic sequence go through ``fosvos_hip.stream.FrameSegmenter`` - prep, n
 frames in flight - and the results are written as PNGs and / or timed.
 
 The options carry the reference's names and defaults.  Additions: ``--model`` (a checkpoint file instead of
-``models/<the reference's file name>``), ``--source DIR``, ``--synthetic N`` (with ``--height`` / ``--width``), ``--output DIR``
-and ``--depth``.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+``models/<the reference's file name>``), ``--source DIR``, ``--synthetic N`` (with ``--height`` / ``--width``), ``--output DIR``,
+``--depth``, and ``--output-format jpeg`` with ``--jpeg-quality``: the device encodes each result as a JPEG file
+(``FrameSegmenter(encode='jpeg')``) and the loop only writes ``%05d.jpg``.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -57,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--width', type=int, default=854)
     p.add_argument('--output', type=str, default=None, help='directory the results are written to as PNGs')
     p.add_argument('--depth', type=int, default=2, help='frames in flight')
+    p.add_argument('--output-format', choices=['png', 'jpeg'], default='png',
+                   help='files of --output: png (written by PIL on the host) or jpeg (encoded on the device)')
+    p.add_argument('--jpeg-quality', type=int, default=90, help='1..100, with --output-format jpeg')
     return p
 
 
@@ -141,13 +145,28 @@ def write_png(directory: Path, index: int, out: np.ndarray) -> None:
     im.save(str(directory / ('%05d.png' % index)))
 
 
-def loop_frames(results: Iterator[np.ndarray], output: Optional[Path]) -> List[float]:
-    """Takes the results as they come, logs the rate of each (the reference's line) and writes them."""
+def write_jpeg_host(directory: Path, index: int, out: np.ndarray, quality: int) -> None:
+    """The host path of --output-format jpeg (--no-network): PIL, with the parameters of util/jpeg_layout.py."""
+    from PIL import Image
+    from util import jpeg_layout
+    im = Image.fromarray(np.ascontiguousarray(out[:, :, ::-1])) if out.ndim == 3 else Image.fromarray(out, mode='L')
+    im.save(str(directory / ('%05d.jpg' % index)), 'JPEG', quality=quality, subsampling=0, optimize=False,
+            restart_marker_blocks=jpeg_layout.RI)
+
+
+def loop_frames(results: Iterator, output: Optional[Path], jpeg_quality: Optional[int] = None) -> List[float]:
+    """Takes the results as they come, logs the rate of each (the reference's line) and writes them: arrays as PNGs (as
+    JPEGs by PIL where ``jpeg_quality`` is given), ``bytes`` - files the device encoded - as they are."""
     rates = []
     start_time = time.time()
     for index, out in enumerate(results):
         if output is not None:
-            write_png(output, index, out)
+            if isinstance(out, bytes):
+                (output / ('%05d.jpg' % index)).write_bytes(out)
+            elif jpeg_quality is not None:
+                write_jpeg_host(output, index, out, jpeg_quality)
+            else:
+                write_png(output, index, out)
         now = time.time()
         rates.append(1.0 / max(now - start_time, 1e-9))
         log.info('FPS: {0:0.1f}'.format(rates[-1]))
@@ -165,6 +184,11 @@ def main(argv=None) -> List[float]:
         raise Exception('Not yet implemented')
     if args.source is not None and args.synthetic is not None:
         raise ValueError('choose one of --source and --synthetic')
+    jpeg = args.output_format == 'jpeg'
+    if jpeg and args.output is None:
+        raise ValueError('--output-format jpeg chooses the files of --output: give --output DIR')
+    if jpeg and not 1 <= args.jpeg_quality <= 100:
+        raise ValueError('--jpeg-quality must be 1..100, got {}'.format(args.jpeg_quality))
     cam = None
     if args.synthetic is not None:
         frames = synthetic_frames(args.synthetic, args.height, args.width)
@@ -179,7 +203,8 @@ def main(argv=None) -> List[float]:
         output.mkdir(parents=True, exist_ok=True)
     try:
         if not args.use_network:
-            return loop_frames((np.ascontiguousarray(f[:, ::-1]) if args.mirror else f for f in frames), output)
+            mirrored = (np.ascontiguousarray(f[:, ::-1]) if args.mirror else f for f in frames)
+            return loop_frames(mirrored, output, args.jpeg_quality) if jpeg else loop_frames(mirrored, output)
         net = get_network(args.variant, args.version, model=args.model).cuda().eval()  # (the nets here run eval-mode BatchNorm only)
         first = next(frames, None)
         if first is None:
@@ -190,8 +215,9 @@ def main(argv=None) -> List[float]:
             yield first
             yield from frames
 
+        encode = dict(encode='jpeg', quality=args.jpeg_quality) if jpeg else {}
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
-                            boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha) as seg:
+                            boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha, **encode) as seg:
             return loop_frames(seg.segment(chained()), output)
     finally:
         if cam is not None:

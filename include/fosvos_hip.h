@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 25
+#define FOSVOS_ABI_VERSION 26
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -445,6 +445,23 @@ int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, s
 size_t fosvos_png_workspace_bytes_mode(int N, int H, int W, int huffman);
 int fosvos_png_encode_mode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
                            int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* ---- the streamed output frames as JPEG files, encoded on the device --------------------------------------------------
+ * fosvos_jpeg_encode: frames uint8 [N,H,W,3] BGR (what fosvos_overlay writes; components = 3) or [N,H,W] grey (components =
+ * 1) -> N standalone baseline JFIF files: frame n's file is out[n * out_stride .. n * out_stride + lengths[n]), the bytes
+ * behind it are left as they were.  The layout is stated in integers in util/jpeg_layout.py (the tests compare byte for
+ * byte): 4:4:4, libjpeg's 16-bit fixed-point colour rows, the Loeffler-Ligtenberg-Moschytz DCT with 13-bit constants, the
+ * Annex K tables scaled by the IJG rule for `quality` (1..100), the standard Huffman tables, a restart interval of 32 MCUs.
+ * `frames` needs no alignment.
+ *   out_stride bytes reserved per frame in `out`, >= fosvos_jpeg_capacity_bytes (the layout's size bound: header + 416 B a
+ *              block + 2 B an interval; no image encodes to more; 0 for a shape the encoder does not take)
+ *   lengths    int32 [N]
+ *   workspace  fosvos_jpeg_workspace_bytes (4 B an interval), 4-byte aligned; what it and `out` held does not matter
+ * H, W <= 65535 and a size bound below 2^31.  Integer arithmetic only; two launches on `stream`. */
+size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components); /* per frame */
+size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components);
+int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int quality, uint8_t *out,
+                       size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* ---- streaming inference: a raw camera frame in, the frame that is shown out -----------------------------------------
  * The per-frame arithmetic of src/run_webcam.py:81-133 (apply_network) on the device beside the nets; the definitions are
