@@ -21,12 +21,27 @@
 //      bytes, the 00 behind every FF and its RST marker with byte stores).
 // One more workgroup per frame of the emit launch writes the header, EOI and the file length.  The DCT is the
 // Loeffler-Ligtenberg-Moschytz factorisation with 13-bit constants (jpeg_layout.fdct_1d).  Integers only.
+//
+// 4:2:0 (fosvos_jpeg_encode_sampled with sampling 420, colour only; k_jpeg<3, .., true>): an MCU is 16x16 pixels and six blocks, Y(0,0)
+// Y(0,1) Y(1,0) Y(1,1) Cb Cr, an interval is kRi420 = 16 MCUs - again 96 blocks, so phases 3 and 4 are the ones above with
+// another block -> (MCU, table) map - and phases 1 and 2 become (jpeg_blocks_420):
+//   1  thread (MCU m = tid & 15, row r = tid >> 4 of 16) loads the 16 pixels of its row (13 aligned words funnel-shifted to
+//      the row's byte offset where the segment is inside the frame, bytes with the edge replicated otherwise), converts
+//      them at full resolution and runs the row pass of its two luma blocks.  It sums its 8 horizontal chroma pairs; rows
+//      r and r ^ 1 are lanes tid and tid ^ 16 of one wave, so one __shfl_xor per pair completes the 2x2 sums in registers:
+//      the even row takes Cb, the odd row Cr, each adds the alternating bias, shifts and runs that block's row pass.
+//   2  thread (MCU m, column u = (tid >> 4) & 7, half = tid >> 7) runs the column pass of three blocks - Y(half,0)
+//      Y(half,1) and Cb or Cr.  A chroma row below the picture's last one reads that one's row-pass result (the layout
+//      replicates the halved plane).  A dummy luma block (beyond ceil(W/8) x ceil(H/8) blocks) is skipped here: its mask
+//      stays "DC only", and one thread per MCU then copies the DC of the block in front of it, in coding order.
+// LDS holds block (slot s of 6, MCU m) at index s * 16 + m, so that the 16 MCUs of a wave's lanes stay an odd word stride apart.
 #include "common.hpp"
 
 using namespace fosvos;
 
 namespace {
 constexpr int kRi = 32, kJpegThreads = 256, kStride = 66;  // halfwords per block in LDS: 33 words, odd
+constexpr int kRi420 = 16;                                 // MCUs of an interval with 4:2:0: 16 x 6 blocks
 constexpr int kAcMax = 1023, kBlockBytes = 208;           // 64 coefficients of at most 26 bits
 constexpr int kHeaderMax = 640;
 
@@ -113,15 +128,16 @@ constexpr HuffEnc make_enc(const HuffSpec &s) {
 }
 __device__ const HuffEnc kEnc[4] = {make_enc(kDc0), make_enc(kAc0), make_enc(kDc1), make_enc(kAc1)};
 
-inline int64_t jpeg_mcus(int H, int W) { return cdiv(H, 8) * cdiv(W, 8); }
-inline int64_t jpeg_intervals(int H, int W) { return cdiv(jpeg_mcus(H, W), kRi); }
+inline int64_t jpeg_mcus(int H, int W, bool s420 = false) { return s420 ? cdiv(H, 16) * cdiv(W, 16) : cdiv(H, 8) * cdiv(W, 8); }
+inline int64_t jpeg_intervals(int H, int W, bool s420 = false) { return cdiv(jpeg_mcus(H, W, s420), s420 ? kRi420 : kRi); }
 inline int jpeg_header_bytes(int C) {
     const int tables = C == 3 ? 2 : 1;
     return 2 + 18 + 69 * tables + 10 + 3 * C + 216 * tables + 6 + 8 + 2 * C;
 }
-// jpeg_layout.capacity: 26 bits a coefficient, doubled by the stuffing, two marker bytes an interval
-inline int64_t jpeg_file_bound(int H, int W, int C) {
-    return jpeg_header_bytes(C) + 2 * (int64_t)kBlockBytes * jpeg_mcus(H, W) * C + 2 * jpeg_intervals(H, W);
+// jpeg_layout.capacity: 26 bits a coefficient, doubled by the stuffing, two marker bytes an interval; 4:2:0: six blocks
+// for every MCU of the padded grid
+inline int64_t jpeg_file_bound(int H, int W, int C, bool s420 = false) {
+    return jpeg_header_bytes(C) + 2 * (int64_t)kBlockBytes * jpeg_mcus(H, W, s420) * (s420 ? 6 : C) + 2 * jpeg_intervals(H, W, s420);
 }
 
 template <int C>
@@ -233,7 +249,7 @@ __device__ __forceinline__ void put_bits(uint32_t *words, uint32_t pos, unsigned
 __device__ __forceinline__ void put_be16(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 8), p[1] = (uint8_t)v; }
 
 // SOI .. SOS into h; returns the length (jpeg_layout.header)
-template <int C>
+template <int C, bool k420>
 __device__ int build_header(uint8_t *h, int H, int W, const JpegQ &qt) {
     constexpr int kTables = C == 3 ? 2 : 1;
     int n = 0;
@@ -247,7 +263,7 @@ __device__ int build_header(uint8_t *h, int H, int W, const JpegQ &qt) {
     h[n++] = 0xFF, h[n++] = 0xC0, h[n++] = 0, h[n++] = (uint8_t)(8 + 3 * C), h[n++] = 8;
     put_be16(h + n, (uint32_t)H), put_be16(h + n + 2, (uint32_t)W), n += 4;
     h[n++] = (uint8_t)C;
-    for (int c = 0; c < C; ++c) h[n++] = (uint8_t)(c + 1), h[n++] = 0x11, h[n++] = c ? 1 : 0;
+    for (int c = 0; c < C; ++c) h[n++] = (uint8_t)(c + 1), h[n++] = (k420 && c == 0) ? 0x22 : 0x11, h[n++] = c ? 1 : 0;
     for (int t = 0; t < 2 * kTables; ++t) {
         const HuffSpec &s = kSpecs[t];
         h[n++] = 0xFF, h[n++] = 0xC4;
@@ -256,95 +272,84 @@ __device__ int build_header(uint8_t *h, int H, int W, const JpegQ &qt) {
         for (int i = 0; i < 16; ++i) h[n++] = s.counts[i];
         for (int i = 0; i < s.n; ++i) h[n++] = s.syms[i];
     }
-    h[n++] = 0xFF, h[n++] = 0xDD, h[n++] = 0, h[n++] = 4, h[n++] = 0, h[n++] = kRi;
+    h[n++] = 0xFF, h[n++] = 0xDD, h[n++] = 0, h[n++] = 4, h[n++] = 0, h[n++] = k420 ? kRi420 : kRi;
     h[n++] = 0xFF, h[n++] = 0xDA, h[n++] = 0, h[n++] = (uint8_t)(6 + 2 * C), h[n++] = (uint8_t)C;
     for (int c = 0; c < C; ++c) h[n++] = (uint8_t)(c + 1), h[n++] = c ? 0x11 : 0x00;
     h[n++] = 0, h[n++] = 63, h[n++] = 0;
     return n;
 }
 
-// grid (intervals, N) for the measure form, (intervals + 1, N) for the emit form
-template <int C, bool kEmit>
-__global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict__ frames, int H, int W, JpegQ qt,
-                                                       uint32_t *__restrict__ ws, uint8_t *__restrict__ out, int64_t capacity,
-                                                       int32_t *__restrict__ lengths) {
-    using Shared = JpegShared<C>;
-    constexpr int kBlocks = Shared::kBlocks;
-    constexpr int kPer = C == 3 ? 32 : 8, kParts = 64 / kPer;  // zigzag places a thread owns in phase 3
-    static_assert(kBlocks * kParts <= kJpegThreads, "a thread per part of a block");
-    __shared__ Shared sh;
-    const int tid = threadIdx.x;
-    const uint32_t n_int = kEmit ? gridDim.x - 1 : gridDim.x, interval = blockIdx.x;
-    const uint32_t mcus_w = ((uint32_t)W + 7u) / 8u, mcus = mcus_w * (((uint32_t)H + 7u) / 8u);  // (H, W <= 65535: < 2^26)
-    ws += (size_t)blockIdx.y * n_int;
-    constexpr uint32_t kHeaderBytes = 2 + 18 + 69 * (C == 3 ? 2 : 1) + 10 + 3 * C + 216 * (C == 3 ? 2 : 1) + 6 + 8 + 2 * C;
+// A luma block beyond the frame's block grid (jpeg_layout.dummy_blocks)
+__device__ __forceinline__ bool jpeg420_dummy(int slot, uint32_t mx, uint32_t my, uint32_t blocks_w, uint32_t blocks_h) {
+    return slot < 4 && (2u * mx + (uint32_t)(slot & 1) >= blocks_w || 2u * my + (uint32_t)(slot >> 1) >= blocks_h);
+}
 
-    if constexpr (kEmit) {
-        out += (int64_t)blockIdx.y * capacity;
-        if (interval == n_int) {  // the frame's ends: header, EOI, length
-            uint32_t before = 0;
-            for (uint32_t s = tid; s < n_int; s += kJpegThreads) before += ws[s] + 2u;
-            const uint32_t total = kHeaderBytes + jpeg_block_sum(before, sh.wave);
-            if (tid == 0) build_header<C>(sh.header, H, W, qt);
-            __syncthreads();
-            for (uint32_t i = tid; i < kHeaderBytes; i += kJpegThreads) out[i] = sh.header[i];
-            if (tid == 0) {
-                out[total - 2] = 0xFF, out[total - 1] = 0xD9;
-                lengths[blockIdx.y] = (int32_t)total;
-            }
-            return;
-        }
-    }
-    frames += (int64_t)blockIdx.y * H * W * C;
-    const uint32_t first = interval * kRi;
-    const int n_m = (int)min((uint32_t)kRi, mcus - first);  // MCUs of this interval
+// Phases 1 and 2 of the 4:2:0 form (see the top of the file); block (slot, MCU m) is at index slot * kRi420 + m.
+__device__ __forceinline__ void jpeg_blocks_420(JpegShared<3> &sh, const uint8_t *__restrict__ frames, int H, int W,
+                                                const JpegQ &qt, uint32_t first, int n_m, uint32_t mcus_w) {
+    const int tid = threadIdx.x, m = tid & 15, hi = tid >> 4;
+    const uint32_t blocks_w = ((uint32_t)W + 7u) / 8u, blocks_h = ((uint32_t)H + 7u) / 8u;
+    // (a thread beyond the interval's last MCU works on that one and stores nothing: the shuffles below stay whole-wave)
+    const uint32_t g = first + (uint32_t)min(m, n_m - 1), my = g / mcus_w, mx = g - my * mcus_w;
+    const bool live = m < n_m;
 
-    // tables into LDS, masks to zero
-    sh.enc_ac[0][tid] = kEnc[1].e[tid];
-    sh.enc_ac[1][tid] = kEnc[3].e[tid];
-    if (tid < 12) sh.enc_dc[0][tid] = kEnc[0].e[tid], sh.enc_dc[1][tid] = kEnc[2].e[tid];
-    for (int i = tid; i < kBlocks * 2; i += kJpegThreads) (&sh.nz[0][0])[i] = 0;
-
-    // ---- 1: pixels -> samples -> row pass
-    const int m = tid & 31, lane_hi = tid >> 5;
-    if (m < n_m) {
-        const uint32_t g = first + (uint32_t)m, my = g / mcus_w, mx = g - my * mcus_w;
-        const int y = min((int)(my * 8u) + lane_hi, H - 1), x0 = (int)(mx * 8u);
-        const uint8_t *p = frames + ((int64_t)y * W + x0) * C;
-        uint8_t px[8 * C];
-        const bool inside = x0 + 8 <= W;
-        if (inside && ((uintptr_t)p & 7u) == 0) {
+    // ---- 1: 16 pixels of row hi -> Y Cb Cr -> row pass of two luma blocks and one chroma block
+    {
+        const int r = hi, y = min((int)(my * 16u) + r, H - 1), x0 = (int)(mx * 16u);
+        const uint8_t *line = frames + (int64_t)y * W * 3;
+        uint8_t px[48];
+        if (x0 + 16 <= W) {
+            const uint8_t *p = line + x0 * 3;
+            const uint32_t shift = (uint32_t)((uintptr_t)p & 3u);
+            const uint32_t *a = reinterpret_cast<const uint32_t *>(p - shift);  // (an aligned word that holds a byte of the row)
+            uint32_t v[13];
 #pragma unroll
-            for (int i = 0; i < C; ++i) {
-                const uint2 v = reinterpret_cast<const uint2 *>(p)[i];
+            for (int i = 0; i < 12; ++i) v[i] = a[i];
+            v[12] = shift ? a[12] : 0u;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) px[8 * i + j] = (uint8_t)(v.x >> (8 * j)), px[8 * i + 4 + j] = (uint8_t)(v.y >> (8 * j));
+            for (int i = 0; i < 12; ++i) {
+                const uint32_t word = __builtin_amdgcn_alignbyte(v[i + 1], v[i], shift);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) px[4 * i + j] = (uint8_t)(word >> (8 * j));
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const uint8_t *q = frames + ((int64_t)y * W + min(x0 + i, W - 1)) * C;
+            for (int i = 0; i < 16; ++i) {
+                const uint8_t *q = line + min(x0 + i, W - 1) * 3;
 #pragma unroll
-                for (int c = 0; c < C; ++c) px[i * C + c] = q[c];
+                for (int c = 0; c < 3; ++c) px[i * 3 + c] = q[c];
             }
         }
+        int cb[16], cr[16];
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
+        for (int half = 0; half < 2; ++half) {
             int d[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                if constexpr (C == 3) {
-                    const int b = px[3 * i], gg = px[3 * i + 1], r = px[3 * i + 2];
-                    const int v = c == 0   ? 19595 * r + 38470 * gg + 7471 * b + 32768
-                                  : c == 1 ? -11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767
-                                           : 32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767;
-                    d[i] = (v >> 16) - 128;
-                } else {
-                    d[i] = (int)px[i] - 128;
-                }
+                const int k = half * 8 + i, b = px[3 * k], gg = px[3 * k + 1], rr = px[3 * k + 2];
+                d[i] = ((19595 * rr + 38470 * gg + 7471 * b + 32768) >> 16) - 128;
+                cb[k] = (-11059 * rr - 21709 * gg + 32768 * b + (128 << 16) + 32767) >> 16;
+                cr[k] = (32768 * rr - 27439 * gg - 5329 * b + (128 << 16) + 32767) >> 16;
             }
             fdct_1d<true>(d);
-            int16_t *row = sh.stage + (c * kRi + m) * kStride + lane_hi * 8;
+            if (live) {
+                int16_t *row = sh.stage + (((r >> 3) * 2 + half) * kRi420 + m) * kStride + (r & 7) * 8;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) row[u] = (int16_t)d[u];
+            }
+        }
+        // the 2x2 sums: rows r and r ^ 1 are lanes tid and tid ^ 16; the even row finishes Cb, the odd row Cr
+        const bool odd = r & 1;
+        int d[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int pair_cb = cb[2 * i] + cb[2 * i + 1], pair_cr = cr[2 * i] + cr[2 * i + 1];
+            const int other = __shfl_xor(odd ? pair_cb : pair_cr, 16, 64);
+            d[i] = (((odd ? pair_cr : pair_cb) + other + 1 + (i & 1)) >> 2) - 128;
+        }
+        fdct_1d<true>(d);
+        if (live) {
+            int16_t *row = sh.stage + ((4 + (r & 1)) * kRi420 + m) * kStride + (r >> 1) * 8;
 #pragma unroll
             for (int u = 0; u < 8; ++u) row[u] = (int16_t)d[u];
         }
@@ -352,20 +357,23 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
     __syncthreads();
 
     // ---- 2: column pass, quantisation, zigzag
-    if (m < n_m) {
-        const int u = lane_hi;
+    if (live) {
+        const int u = hi & 7, half = hi >> 3;
+        const int chroma_rows = min(8, (H + 1) / 2 - (int)(my * 8u));  // rows of this MCU's chroma blocks inside the halved plane
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int b = c * kRi + m;
+        for (int k = 0; k < 3; ++k) {
+            const int slot = k < 2 ? half * 2 + k : 4 + half;
+            if (jpeg420_dummy(slot, mx, my, blocks_w, blocks_h)) continue;
+            const int b = slot * kRi420 + m;
             int d[8];
 #pragma unroll
-            for (int yy = 0; yy < 8; ++yy) d[yy] = sh.stage[b * kStride + yy * 8 + u];
+            for (int yy = 0; yy < 8; ++yy) d[yy] = sh.stage[b * kStride + (k < 2 ? yy : min(yy, chroma_rows - 1)) * 8 + u];
             fdct_1d<false>(d);
             uint32_t nz0 = 0, nz1 = 0;
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
                 const int nat = v * 8 + u;
-                const uint32_t q8 = (uint32_t)qt.q[c ? 1 : 0][nat] << 3;
+                const uint32_t q8 = (uint32_t)qt.q[k < 2 ? 0 : 1][nat] << 3;
                 const uint32_t a = (uint32_t)(d[v] < 0 ? -d[v] : d[v]);
                 int mag = (int)((a + (q8 >> 1)) / q8);
                 if (nat != 0) mag = min(mag, kAcMax);
@@ -377,21 +385,157 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
             if (nz1) atomicOr(&sh.nz[b][1], nz1);
         }
     }
+    __syncthreads();
+    // dummy blocks: the DC of the block in front, in coding order (a copy may be copied on); their masks stay 0
+    if (tid < n_m) {
+        const uint32_t gm = first + (uint32_t)tid, ry = gm / mcus_w, rx = gm - ry * mcus_w;
+        for (int slot = 1; slot < 4; ++slot)
+            if (jpeg420_dummy(slot, rx, ry, blocks_w, blocks_h))
+                sh.coef[(slot * kRi420 + tid) * kStride] = sh.coef[((slot - 1) * kRi420 + tid) * kStride];
+    }
+}
+
+// grid (intervals, N) for the measure form, (intervals + 1, N) for the emit form
+template <int C, bool kEmit, bool k420 = false>
+__global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict__ frames, int H, int W, JpegQ qt,
+                                                       uint32_t *__restrict__ ws, uint8_t *__restrict__ out, int64_t capacity,
+                                                       int32_t *__restrict__ lengths) {
+    using Shared = JpegShared<C>;
+    constexpr int kBlocks = Shared::kBlocks;
+    constexpr int kPer = C == 3 ? 32 : 8, kParts = 64 / kPer;  // zigzag places a thread owns in phase 3
+    static_assert(kBlocks * kParts <= kJpegThreads, "a thread per part of a block");
+    static_assert(!k420 || (C == 3 && kRi420 * 6 == kBlocks), "4:2:0 is a colour form with the block count of 4:4:4");
+    constexpr int kMcus = k420 ? kRi420 : kRi, kSide = k420 ? 16 : 8, kPerMcu = k420 ? 6 : C;  // of an interval, an MCU, an MCU
+    __shared__ Shared sh;
+    const int tid = threadIdx.x;
+    const uint32_t n_int = kEmit ? gridDim.x - 1 : gridDim.x, interval = blockIdx.x;
+    const uint32_t mcus_w = ((uint32_t)W + kSide - 1u) / kSide, mcus = mcus_w * (((uint32_t)H + kSide - 1u) / kSide);  // (H, W <= 65535: < 2^26)
+    ws += (size_t)blockIdx.y * n_int;
+    constexpr uint32_t kHeaderBytes = 2 + 18 + 69 * (C == 3 ? 2 : 1) + 10 + 3 * C + 216 * (C == 3 ? 2 : 1) + 6 + 8 + 2 * C;
+
+    if constexpr (kEmit) {
+        out += (int64_t)blockIdx.y * capacity;
+        if (interval == n_int) {  // the frame's ends: header, EOI, length
+            uint32_t before = 0;
+            for (uint32_t s = tid; s < n_int; s += kJpegThreads) before += ws[s] + 2u;
+            const uint32_t total = kHeaderBytes + jpeg_block_sum(before, sh.wave);
+            if (tid == 0) build_header<C, k420>(sh.header, H, W, qt);
+            __syncthreads();
+            for (uint32_t i = tid; i < kHeaderBytes; i += kJpegThreads) out[i] = sh.header[i];
+            if (tid == 0) {
+                out[total - 2] = 0xFF, out[total - 1] = 0xD9;
+                lengths[blockIdx.y] = (int32_t)total;
+            }
+            return;
+        }
+    }
+    frames += (int64_t)blockIdx.y * H * W * C;
+    const uint32_t first = interval * kMcus;
+    const int n_m = (int)min((uint32_t)kMcus, mcus - first);  // MCUs of this interval
+
+    // tables into LDS, masks to zero
+    sh.enc_ac[0][tid] = kEnc[1].e[tid];
+    sh.enc_ac[1][tid] = kEnc[3].e[tid];
+    if (tid < 12) sh.enc_dc[0][tid] = kEnc[0].e[tid], sh.enc_dc[1][tid] = kEnc[2].e[tid];
+    for (int i = tid; i < kBlocks * 2; i += kJpegThreads) (&sh.nz[0][0])[i] = 0;
+
+    if constexpr (k420) {
+        jpeg_blocks_420(sh, frames, H, W, qt, first, n_m, mcus_w);
+    } else {
+        // ---- 1: pixels -> samples -> row pass
+        const int m = tid & 31, lane_hi = tid >> 5;
+        if (m < n_m) {
+            const uint32_t g = first + (uint32_t)m, my = g / mcus_w, mx = g - my * mcus_w;
+            const int y = min((int)(my * 8u) + lane_hi, H - 1), x0 = (int)(mx * 8u);
+            const uint8_t *p = frames + ((int64_t)y * W + x0) * C;
+            uint8_t px[8 * C];
+            const bool inside = x0 + 8 <= W;
+            if (inside && ((uintptr_t)p & 7u) == 0) {
+#pragma unroll
+                for (int i = 0; i < C; ++i) {
+                    const uint2 v = reinterpret_cast<const uint2 *>(p)[i];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) px[8 * i + j] = (uint8_t)(v.x >> (8 * j)), px[8 * i + 4 + j] = (uint8_t)(v.y >> (8 * j));
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const uint8_t *q = frames + ((int64_t)y * W + min(x0 + i, W - 1)) * C;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) px[i * C + c] = q[c];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int d[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    if constexpr (C == 3) {
+                        const int b = px[3 * i], gg = px[3 * i + 1], r = px[3 * i + 2];
+                        const int v = c == 0   ? 19595 * r + 38470 * gg + 7471 * b + 32768
+                                      : c == 1 ? -11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767
+                                               : 32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767;
+                        d[i] = (v >> 16) - 128;
+                    } else {
+                        d[i] = (int)px[i] - 128;
+                    }
+                }
+                fdct_1d<true>(d);
+                int16_t *row = sh.stage + (c * kRi + m) * kStride + lane_hi * 8;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) row[u] = (int16_t)d[u];
+            }
+        }
+        __syncthreads();
+
+        // ---- 2: column pass, quantisation, zigzag
+        if (m < n_m) {
+            const int u = lane_hi;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int b = c * kRi + m;
+                int d[8];
+#pragma unroll
+                for (int yy = 0; yy < 8; ++yy) d[yy] = sh.stage[b * kStride + yy * 8 + u];
+                fdct_1d<false>(d);
+                uint32_t nz0 = 0, nz1 = 0;
+#pragma unroll
+                for (int v = 0; v < 8; ++v) {
+                    const int nat = v * 8 + u;
+                    const uint32_t q8 = (uint32_t)qt.q[c ? 1 : 0][nat] << 3;
+                    const uint32_t a = (uint32_t)(d[v] < 0 ? -d[v] : d[v]);
+                    int mag = (int)((a + (q8 >> 1)) / q8);
+                    if (nat != 0) mag = min(mag, kAcMax);
+                    const int z = kZig.inv[nat];
+                    sh.coef[b * kStride + z] = (int16_t)(d[v] < 0 ? -mag : mag);
+                    if (mag) (z < 32 ? nz0 : nz1) |= 1u << (z & 31);
+                }
+                if (nz0) atomicOr(&sh.nz[b][0], nz0);
+                if (nz1) atomicOr(&sh.nz[b][1], nz1);
+            }
+        }
+    }
     __syncthreads();  // (stage is dead: the same bytes are `bits` from here on)
 
-    // ---- 3: codes.  Sequence block sb = MCU * C + component; this thread: places [part * kPer, part * kPer + kPer)
-    const int sb = tid / kParts, part = tid % kParts, sm = sb / C, sc = sb - sm * C;
-    const bool active = sb < n_m * C;
-    const int blk = sc * kRi + sm;
+    // ---- 3: codes.  Sequence block sb = MCU * kPerMcu + its place in the MCU; this thread: places [part * kPer, part * kPer + kPer)
+    const int sb = tid / kParts, part = tid % kParts, sm = sb / kPerMcu, sc = sb - sm * kPerMcu;
+    const bool active = sb < n_m * kPerMcu;
+    const int blk = sc * kMcus + sm;
+    const int table = k420 ? (sc >= 4 ? 1 : 0) : (sc ? 1 : 0);
     unsigned long long nzb = 1ull, mine = 0;
     int dc_diff = 0;
-    const uint32_t *enc_dc = sh.enc_dc[sc ? 1 : 0], *enc_ac = sh.enc_ac[sc ? 1 : 0];
+    const uint32_t *enc_dc = sh.enc_dc[table], *enc_ac = sh.enc_ac[table];
     const int16_t *cf = sh.coef + blk * kStride;
     if (active) {
         nzb |= (unsigned long long)sh.nz[blk][0] | ((unsigned long long)sh.nz[blk][1] << 32);
         const unsigned long long range = (kPer == 64 ? ~0ull : ((1ull << kPer) - 1ull)) << (part * kPer);
         mine = nzb & range;
-        if (part == 0) dc_diff = cf[0] - (sm > 0 ? sh.coef[(blk - 1) * kStride] : 0);
+        if constexpr (k420) {  // luma runs through the four blocks of an MCU and on to the next MCU's first
+            const int prev = (sc >= 1 && sc <= 3) ? blk - kRi420 : sc == 0 ? 3 * kRi420 + sm - 1 : blk - 1;
+            if (part == 0) dc_diff = cf[0] - ((sm > 0 || (sc >= 1 && sc <= 3)) ? sh.coef[prev * kStride] : 0);
+        } else {
+            if (part == 0) dc_diff = cf[0] - (sm > 0 ? sh.coef[(blk - 1) * kStride] : 0);
+        }
     }
     uint32_t my_bits = 0;
     for (unsigned long long rest = mine; rest; rest &= rest - 1ull) {
@@ -460,36 +604,29 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
     }
 }
 
-template <int C>
+template <int C, bool k420>
 int jpeg_launch(const uint8_t *frames, int N, int H, int W, const JpegQ &qt, uint8_t *out, size_t out_stride, int32_t *lengths,
                 uint32_t *ws, void *stream) {
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)jpeg_intervals(H, W), (unsigned)N);
-    FOSVOS_PROF(C == 3 ? "k_jpeg_measure" : "k_jpeg_measure_grey", stream, 0.0);
-    hipLaunchKernelGGL((k_jpeg<C, false>), grid, dim3(kJpegThreads), 0, st, frames, H, W, qt, ws, (uint8_t *)nullptr, (int64_t)0,
-                       (int32_t *)nullptr);
+    const dim3 grid((unsigned)jpeg_intervals(H, W, k420), (unsigned)N);
+    FOSVOS_PROF(k420 ? "k_jpeg_measure_420" : C == 3 ? "k_jpeg_measure" : "k_jpeg_measure_grey", stream, 0.0);
+    hipLaunchKernelGGL((k_jpeg<C, false, k420>), grid, dim3(kJpegThreads), 0, st, frames, H, W, qt, ws, (uint8_t *)nullptr,
+                       (int64_t)0, (int32_t *)nullptr);
     FOSVOS_LAUNCH_CHECK();
-    FOSVOS_PROF(C == 3 ? "k_jpeg_emit" : "k_jpeg_emit_grey", stream, 0.0);
-    hipLaunchKernelGGL((k_jpeg<C, true>), dim3(grid.x + 1, grid.y), dim3(kJpegThreads), 0, st, frames, H, W, qt, ws, out,
+    FOSVOS_PROF(k420 ? "k_jpeg_emit_420" : C == 3 ? "k_jpeg_emit" : "k_jpeg_emit_grey", stream, 0.0);
+    hipLaunchKernelGGL((k_jpeg<C, true, k420>), dim3(grid.x + 1, grid.y), dim3(kJpegThreads), 0, st, frames, H, W, qt, ws, out,
                        (int64_t)out_stride, lengths);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
-}  // namespace
 
-extern "C" size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components) {
-    if (N <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || (components != 1 && components != 3)) return 0;
-    return (size_t)jpeg_file_bound(H, W, components);
+bool jpeg_shape_ok(int N, int H, int W, int components) {
+    return N > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535 && (components == 1 || components == 3);
 }
 
-extern "C" size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components) {
-    if (N <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || (components != 1 && components != 3)) return 0;
-    return (size_t)N * (size_t)jpeg_intervals(H, W) * sizeof(uint32_t);
-}
-
-extern "C" int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int quality, uint8_t *out,
-                                  size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes, int device,
-                                  void *stream) {
+// the body of both encode entry points; s420: the 4:2:0 layout (colour only)
+int jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, bool s420, int quality, uint8_t *out, size_t out_stride,
+                int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
     FOSVOS_REQUIRE(components == 1 || components == 3, FOSVOS_E_SHAPE, "jpeg_encode: components=%d (1 grey, 3 BGR)", components);
     FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && H <= 65535 && W <= 65535, FOSVOS_E_SHAPE,
                    "jpeg_encode: N=%d H=%d W=%d (each 1..65535)", N, H, W);
@@ -497,8 +634,9 @@ extern "C" int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, in
     FOSVOS_REQUIRE(frames && out && lengths && workspace, FOSVOS_E_ARG, "jpeg_encode: null pointer");
     FOSVOS_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)lengths & 3) == 0, FOSVOS_E_ARG,
                    "jpeg_encode: the workspace and the lengths must be 4-byte aligned");
-    const size_t need_cap = fosvos_jpeg_capacity_bytes(N, H, W, components);
-    const size_t need_ws = fosvos_jpeg_workspace_bytes(N, H, W, components);
+    s420 = s420 && components == 3;
+    const size_t need_cap = (size_t)jpeg_file_bound(H, W, components, s420);
+    const size_t need_ws = (size_t)N * (size_t)jpeg_intervals(H, W, s420) * sizeof(uint32_t);
     FOSVOS_REQUIRE(need_cap <= (size_t)INT32_MAX, FOSVOS_E_SHAPE, "jpeg_encode: H=%d W=%d: the size bound %zu B exceeds 2^31 - 1", H,
                    W, need_cap);
     FOSVOS_REQUIRE(out_stride >= need_cap, FOSVOS_E_WORKSPACE, "jpeg_encode: out_stride %zu B a frame < %zu B", out_stride, need_cap);
@@ -513,6 +651,43 @@ extern "C" int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, in
         }
     FOSVOS_ENTER(device);
     uint32_t *ws = reinterpret_cast<uint32_t *>(workspace);
-    return components == 3 ? jpeg_launch<3>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream)
-                           : jpeg_launch<1>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream);
+    if (s420) return jpeg_launch<3, true>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream);
+    return components == 3 ? jpeg_launch<3, false>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream)
+                           : jpeg_launch<1, false>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream);
+}
+}  // namespace
+
+extern "C" size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components) {
+    if (!jpeg_shape_ok(N, H, W, components)) return 0;
+    return (size_t)jpeg_file_bound(H, W, components);
+}
+
+extern "C" size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components) {
+    if (!jpeg_shape_ok(N, H, W, components)) return 0;
+    return (size_t)N * (size_t)jpeg_intervals(H, W) * sizeof(uint32_t);
+}
+
+extern "C" int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int quality, uint8_t *out,
+                                  size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes, int device,
+                                  void *stream) {
+    return jpeg_encode(frames, N, H, W, components, false, quality, out, out_stride, lengths, workspace, workspace_bytes, device,
+                       stream);
+}
+
+extern "C" size_t fosvos_jpeg_capacity_bytes_sampled(int N, int H, int W, int components, int sampling) {
+    if (!jpeg_shape_ok(N, H, W, components) || (sampling != 444 && sampling != 420)) return 0;
+    return (size_t)jpeg_file_bound(H, W, components, sampling == 420 && components == 3);
+}
+
+extern "C" size_t fosvos_jpeg_workspace_bytes_sampled(int N, int H, int W, int components, int sampling) {
+    if (!jpeg_shape_ok(N, H, W, components) || (sampling != 444 && sampling != 420)) return 0;
+    return (size_t)N * (size_t)jpeg_intervals(H, W, sampling == 420 && components == 3) * sizeof(uint32_t);
+}
+
+extern "C" int fosvos_jpeg_encode_sampled(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality,
+                                          uint8_t *out, size_t out_stride, int32_t *lengths, void *workspace,
+                                          size_t workspace_bytes, int device, void *stream) {
+    FOSVOS_REQUIRE(sampling == 444 || sampling == 420, FOSVOS_E_ARG, "jpeg_encode: sampling=%d (444 or 420)", sampling);
+    return jpeg_encode(frames, N, H, W, components, sampling == 420, quality, out, out_stride, lengths, workspace, workspace_bytes,
+                       device, stream);
 }

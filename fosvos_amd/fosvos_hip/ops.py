@@ -1236,20 +1236,35 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengt
 
 
 # ------------------------------------------------------------------------------------------ JPEG files (jpeg.hip)
-def jpeg_capacity(h: int, w: int, components: int) -> int:
+JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
+
+
+def _jpeg_subsampling(subsampling, what: str) -> bool:
+    """True for '4:2:0', False for '4:4:4' (the entry points as they were), ValueError for anything else."""
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"{what}: subsampling must be one of {JPEG_SUBSAMPLINGS}, got {subsampling!r}")
+    return subsampling == '4:2:0'
+
+
+def jpeg_capacity(h: int, w: int, components: int, subsampling: str = '4:4:4') -> int:
     """Bytes ``jpeg_encode`` reserves per frame: the layout's size bound (util/jpeg_layout.capacity)."""
-    cap = int(lib().fosvos_jpeg_capacity_bytes(1, int(h), int(w), int(components)))
+    if _jpeg_subsampling(subsampling, "jpeg_capacity"):
+        cap = int(lib().fosvos_jpeg_capacity_bytes_sampled(1, int(h), int(w), int(components), 420))
+    else:
+        cap = int(lib().fosvos_jpeg_capacity_bytes(1, int(h), int(w), int(components)))
     if cap == 0:
         raise ValueError(f"jpeg_capacity: h, w in 1..65535 and components 1 or 3, got {h}, {w}, {components}")
     return cap
 
 
 def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.Tensor] = None,
-                lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                lengths: Optional[torch.Tensor] = None, subsampling: str = '4:4:4') -> Tuple[torch.Tensor, torch.Tensor]:
     """fosvos_jpeg_encode: uint8 [N,H,W,3] BGR (``overlay``'s output) or [N,H,W] grey -> (buffer uint8 [N,capacity], lengths
     int32 [N]): frame n's baseline JPEG file is ``buffer[n, :lengths[n]]``, in the layout util/jpeg_layout.py states; the
-    bytes behind it are not written.  ``out`` (uint8 [N, >= jpeg_capacity(H, W, components)]) and ``lengths`` (int32 [N]) may
-    be views of a caller's buffer.  Launched on the current stream, no synchronisation."""
+    bytes behind it are not written.  ``out`` (uint8 [N, >= jpeg_capacity(H, W, components, subsampling)]) and ``lengths``
+    (int32 [N]) may be views of a caller's buffer.  ``subsampling='4:2:0'`` (fosvos_jpeg_encode_sampled) halves the chroma
+    planes of a colour frame; a grey frame ignores it.  Launched on the current stream, no synchronisation."""
+    sampled = _jpeg_subsampling(subsampling, "jpeg_encode")
     _need_eval(frames_u8, torch.uint8, "jpeg_encode frames")
     if frames_u8.numel() == 0 or not (frames_u8.dim() == 3 or (frames_u8.dim() == 4 and frames_u8.shape[3] == 3)):
         raise ValueError(f"jpeg_encode: frames must be a non-empty [N,H,W,3] or [N,H,W], got {tuple(frames_u8.shape)}")
@@ -1258,7 +1273,7 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     n, h, w = (int(v) for v in frames_u8.shape[:3])
     comps = 3 if frames_u8.dim() == 4 else 1
     L = lib()
-    cap = int(L.fosvos_jpeg_capacity_bytes(n, h, w, comps))
+    cap = int(L.fosvos_jpeg_capacity_bytes_sampled(n, h, w, comps, 420) if sampled else L.fosvos_jpeg_capacity_bytes(n, h, w, comps))
     if cap == 0:
         raise ValueError(f"jpeg_encode: H and W must be at most 65535, got {h}, {w}")
     if out is None:
@@ -1276,11 +1291,16 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     for t in (out, lengths):
         if t.device != frames_u8.device:
             raise RuntimeError(f"jpeg_encode: every tensor must be on {frames_u8.device}, got one on {t.device}")
-    ws, wsn = _WS.get(L.fosvos_jpeg_workspace_bytes(n, h, w, comps), frames_u8.device)
+    need = L.fosvos_jpeg_workspace_bytes_sampled(n, h, w, comps, 420) if sampled else L.fosvos_jpeg_workspace_bytes(n, h, w, comps)
+    ws, wsn = _WS.get(need, frames_u8.device)
     dev, st = _ctx(frames_u8)
     e0 = _pb()
-    check(L.fosvos_jpeg_encode(frames_u8.data_ptr(), n, h, w, comps, int(quality), out.data_ptr(), int(out.shape[1]),
-                               lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
+    if sampled:
+        check(L.fosvos_jpeg_encode_sampled(frames_u8.data_ptr(), n, h, w, comps, 420, int(quality), out.data_ptr(),
+                                           int(out.shape[1]), lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
+    else:
+        check(L.fosvos_jpeg_encode(frames_u8.data_ptr(), n, h, w, comps, int(quality), out.data_ptr(), int(out.shape[1]),
+                                   lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
     _pe(e0, "jpeg_encode", 0.0, 2.0 * n * h * w * comps)
     return out, lengths
 

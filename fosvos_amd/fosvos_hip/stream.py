@@ -27,7 +27,8 @@ and the slot ends in a device file buffer with its length in front:
 
 The download is ONE copy of the length and the first ``budget`` bytes of the file (a constructor-time constant, by default
 a quarter of the raw output), so the host still waits on ``slot.moved`` alone; only a frame whose file is longer fetches the
-rest with a second copy, on a stream of its own, when it is retired.  ``encode=None`` is the object described above.
+rest with a second copy, on a stream of its own, when it is retired.  ``subsampling='4:2:0'`` chooses the encoder's 4:2:0
+form (smaller files; the default budget stays the quarter).  ``encode=None`` is the object described above.
 
 Not thread-safe: one host thread drives a segmenter.
 """
@@ -80,7 +81,7 @@ class FrameSegmenter:
 
     def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
-                 quality: int = 90, budget: Optional[int] = None) -> None:
+                 quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None) -> None:
         from util import frame_overlay
         self.height, self.width, self.depth = int(height), int(width), int(depth)
         if self.height <= 0 or self.width <= 0 or self.depth <= 0:
@@ -98,13 +99,18 @@ class FrameSegmenter:
         if encode not in (None, 'jpeg'):
             raise ValueError(f"FrameSegmenter: encode must be None or 'jpeg', got {encode!r}")
         self.encode, self.quality = encode, quality
+        if subsampling != '4:4:4' and not encode:
+            raise ValueError("FrameSegmenter: subsampling is the chroma sampling of encode='jpeg'")
+        self.subsampling = subsampling if encode else None
         self.capacity = self.budget = 0
         self.second_copies = 0  # frames whose file was longer than the budget
         self.bytes_down = 0     # bytes the downloads moved
         if encode:
             if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
                 raise ValueError(f"FrameSegmenter: quality must be an integer in 1..100, got {quality!r}")
-            self.capacity = ops.jpeg_capacity(h, w, 3 if self.overlay else 1)
+            if self.subsampling not in ops.JPEG_SUBSAMPLINGS:
+                raise ValueError(f"FrameSegmenter: subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {subsampling!r}")
+            self.capacity = ops.jpeg_capacity(h, w, 3 if self.overlay else 1, self.subsampling)
             raw = h * w * (3 if self.overlay else 1)
             if budget is None:
                 budget = max(raw // 4, 1024)
@@ -176,7 +182,7 @@ class FrameSegmenter:
                 ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
                             out=slot.out)
                 if self.encode:
-                    ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length)
+                    ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length, subsampling=self.subsampling)
         finally:
             if had:
                 net.compute_side_outputs = old

@@ -5,7 +5,9 @@ frames in flight - and the results are written as PNGs and / or timed.
 The options carry the reference's names and defaults.  Additions: ``--model`` (a checkpoint file instead of
 ``models/<the reference's file name>``), ``--source DIR``, ``--synthetic N`` (with ``--height`` / ``--width``), ``--output DIR``,
 ``--depth``, and ``--output-format jpeg`` with ``--jpeg-quality``: the device encodes each result as a JPEG file
-(``FrameSegmenter(encode='jpeg')``) and the loop only writes ``%05d.jpg``.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+(``FrameSegmenter(encode='jpeg')``) and the loop only writes ``%05d.jpg``; ``--jpeg-subsampling 420`` chooses the encoder's
+4:2:0 form, and ``--output NAME.avi`` (with ``--fps``) puts the same files into one Motion-JPEG AVI (util/mjpeg_avi.py)
+instead of a directory.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -56,11 +58,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--synthetic', type=int, default=None, metavar='N', help='N frames of the synthetic sequence')
     p.add_argument('--height', type=int, default=480)
     p.add_argument('--width', type=int, default=854)
-    p.add_argument('--output', type=str, default=None, help='directory the results are written to as PNGs')
+    p.add_argument('--output', type=str, default=None,
+                   help='directory the results are written to as PNGs; NAME.avi with --output-format jpeg: one Motion-JPEG file')
     p.add_argument('--depth', type=int, default=2, help='frames in flight')
     p.add_argument('--output-format', choices=['png', 'jpeg'], default='png',
                    help='files of --output: png (written by PIL on the host) or jpeg (encoded on the device)')
     p.add_argument('--jpeg-quality', type=int, default=90, help='1..100, with --output-format jpeg')
+    p.add_argument('--jpeg-subsampling', choices=['444', '420'], default='444', help='chroma sampling, with --output-format jpeg')
+    p.add_argument('--fps', type=float, default=25, help='frame rate written into --output NAME.avi')
     return p
 
 
@@ -145,26 +150,40 @@ def write_png(directory: Path, index: int, out: np.ndarray) -> None:
     im.save(str(directory / ('%05d.png' % index)))
 
 
-def write_jpeg_host(directory: Path, index: int, out: np.ndarray, quality: int) -> None:
-    """The host path of --output-format jpeg (--no-network): PIL, with the parameters of util/jpeg_layout.py."""
+SUBSAMPLING = {'444': '4:4:4', '420': '4:2:0'}
+
+
+def write_jpeg_host(directory: Path, index: int, out: np.ndarray, quality: int, subsampling: str = '4:4:4', target=None) -> None:
+    """The host path of --output-format jpeg (--no-network): PIL, with the parameters of util/jpeg_layout.py.  ``target``: a
+    file object that takes the bytes instead of ``%05d.jpg``."""
     from PIL import Image
     from util import jpeg_layout
     im = Image.fromarray(np.ascontiguousarray(out[:, :, ::-1])) if out.ndim == 3 else Image.fromarray(out, mode='L')
-    im.save(str(directory / ('%05d.jpg' % index)), 'JPEG', quality=quality, subsampling=0, optimize=False,
-            restart_marker_blocks=jpeg_layout.RI)
+    sampled = subsampling == '4:2:0' and out.ndim == 3
+    im.save(target if target is not None else str(directory / ('%05d.jpg' % index)), 'JPEG', quality=quality,
+            subsampling=2 if sampled else 0, optimize=False, restart_marker_blocks=jpeg_layout.RI_420 if sampled else jpeg_layout.RI)
 
 
-def loop_frames(results: Iterator, output: Optional[Path], jpeg_quality: Optional[int] = None) -> List[float]:
+def loop_frames(results: Iterator, output: Optional[Path], jpeg_quality: Optional[int] = None, subsampling: str = '4:4:4',
+                avi=None) -> List[float]:
     """Takes the results as they come, logs the rate of each (the reference's line) and writes them: arrays as PNGs (as
-    JPEGs by PIL where ``jpeg_quality`` is given), ``bytes`` - files the device encoded - as they are."""
+    JPEGs by PIL where ``jpeg_quality`` is given), ``bytes`` - files the device encoded - as they are.  ``avi`` (a
+    util.mjpeg_avi.AviWriter) takes the JPEG files instead of the directory ``output``."""
     rates = []
     start_time = time.time()
     for index, out in enumerate(results):
-        if output is not None:
+        if avi is not None:
+            if not isinstance(out, bytes):
+                import io
+                buf = io.BytesIO()
+                write_jpeg_host(None, index, out, jpeg_quality, subsampling, target=buf)
+                out = buf.getvalue()
+            avi.write(out)
+        elif output is not None:
             if isinstance(out, bytes):
                 (output / ('%05d.jpg' % index)).write_bytes(out)
             elif jpeg_quality is not None:
-                write_jpeg_host(output, index, out, jpeg_quality)
+                write_jpeg_host(output, index, out, jpeg_quality, subsampling)
             else:
                 write_png(output, index, out)
         now = time.time()
@@ -174,6 +193,19 @@ def loop_frames(results: Iterator, output: Optional[Path], jpeg_quality: Optiona
     if rates:
         log.info('Mean FPS: {0:0.1f} over {1} frames'.format(len(rates) / sum(1.0 / r for r in rates), len(rates)))
     return rates
+
+
+def chain_first(first: np.ndarray, rest: Iterator[np.ndarray]) -> Iterator[np.ndarray]:
+    yield first
+    yield from rest
+
+
+def open_avi(path: str, first: np.ndarray, fps: float):
+    """The Motion-JPEG file of --output NAME.avi, sized by the first frame."""
+    from util.mjpeg_avi import AviWriter
+    parent = os.path.dirname(os.path.abspath(path))
+    os.makedirs(parent, exist_ok=True)
+    return AviWriter(path, first.shape[1], first.shape[0], fps)
 
 
 def main(argv=None) -> List[float]:
@@ -189,6 +221,14 @@ def main(argv=None) -> List[float]:
         raise ValueError('--output-format jpeg chooses the files of --output: give --output DIR')
     if jpeg and not 1 <= args.jpeg_quality <= 100:
         raise ValueError('--jpeg-quality must be 1..100, got {}'.format(args.jpeg_quality))
+    if args.jpeg_subsampling != '444' and not jpeg:
+        raise ValueError('--jpeg-subsampling is the chroma sampling of --output-format jpeg')
+    subsampling = SUBSAMPLING[args.jpeg_subsampling]
+    to_avi = args.output is not None and args.output.lower().endswith('.avi')
+    if to_avi and not jpeg:
+        raise ValueError('--output NAME.avi is a Motion-JPEG file: give --output-format jpeg')
+    if to_avi and not args.fps > 0:
+        raise ValueError('--fps must be positive, got {}'.format(args.fps))
     cam = None
     if args.synthetic is not None:
         frames = synthetic_frames(args.synthetic, args.height, args.width)
@@ -198,28 +238,38 @@ def main(argv=None) -> List[float]:
         cam = open_webcam(args.webcam)
         frames = webcam_frames(cam)
     output = None
-    if args.output is not None:
+    if args.output is not None and not to_avi:
         output = Path(args.output)
         output.mkdir(parents=True, exist_ok=True)
+    avi = None
     try:
         if not args.use_network:
             mirrored = (np.ascontiguousarray(f[:, ::-1]) if args.mirror else f for f in frames)
+            if to_avi:
+                first = next(mirrored, None)
+                if first is None:
+                    return []
+                avi = open_avi(args.output, first, args.fps)
+                return loop_frames(chain_first(first, mirrored), None, args.jpeg_quality, subsampling, avi=avi)
+            if jpeg and subsampling != '4:4:4':
+                return loop_frames(mirrored, output, args.jpeg_quality, subsampling)
             return loop_frames(mirrored, output, args.jpeg_quality) if jpeg else loop_frames(mirrored, output)
         net = get_network(args.variant, args.version, model=args.model).cuda().eval()  # (the nets here run eval-mode BatchNorm only)
         first = next(frames, None)
         if first is None:
             return []
         from fosvos_hip.stream import FrameSegmenter
-
-        def chained():
-            yield first
-            yield from frames
-
         encode = dict(encode='jpeg', quality=args.jpeg_quality) if jpeg else {}
+        if jpeg and subsampling != '4:4:4':
+            encode['subsampling'] = subsampling
+        if to_avi:
+            avi = open_avi(args.output, first, args.fps)
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
                             boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha, **encode) as seg:
-            return loop_frames(seg.segment(chained()), output)
+            return loop_frames(seg.segment(chain_first(first, frames)), output, avi=avi)
     finally:
+        if avi is not None:
+            avi.close()
         if cam is not None:
             cam.release()
 

@@ -29,6 +29,30 @@ A uint8 [H,W,3] BGR frame (what ``ops.overlay`` writes) or a uint8 [H,W] grey on
   with 1-bits.
 * Restart interval: ``RI`` MCUs in raster order, so an interval needs nothing from another; RST(k mod 8) stands behind
   interval k except the last.
+
+``subsampling='4:2:0'`` (opt-in, colour only; a grey frame ignores it and gives the grey file above) halves both chroma
+planes.  What changes, everything else being as above:
+
+* An MCU is 16x16 pixels and six blocks in the order Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr (``MCU_COMPONENTS_420``); MCUs in
+  raster order, ``ceil(W/16) x ceil(H/16)`` of them; SOF0 sampling bytes 0x22 0x11 0x11; the restart interval is ``RI_420``
+  = 16 MCUs, again 96 blocks.
+* Colour conversion per full-resolution pixel, the rows above.  The luma plane is edge-replicated to ``ceil(W/8)*8 x
+  ceil(H/8)*8``.
+* Chroma: the full-resolution Cb / Cr planes are edge-replicated to ``16*ceil(W/16)`` columns and to an EVEN number of rows
+  (one more row for an odd H, no more); then ``out[y][x] = (p[2y][2x] + p[2y][2x+1] + p[2y+1][2x] + p[2y+1][2x+1] + bias)
+  >> 2``, ``bias`` 1 for even x and 2 for odd x (libjpeg's h2v2 downsampler); then the ``ceil(H/2)`` rows of the HALVED plane
+  are edge-replicated to ``8*ceil(H/16)`` rows.  So below the picture the last chroma row repeats, which for an even H is the
+  mean of rows H-2 and H-1, not row H-1 alone (libjpeg pads the downsampler's output to the MCU row, not its input).
+* Dummy luma blocks: a Y block of an MCU beyond ``ceil(W/8)`` block columns (W mod 16 in 1..8) or ``ceil(H/8)`` block rows (H
+  mod 16 in 1..8) is not computed from pixels: all its AC coefficients are 0 and its quantised DC is that of the block in
+  front of it in the MCU's coding order (libjpeg's coefficient controller; Y(0,0) is never a dummy, so in an MCU with a
+  dummy row and column all four DCs are Y(0,0)'s).  It takes part in the DC prediction: its difference is 0.
+* DC prediction per component over the blocks of an interval in coding order, so luma runs through the four blocks of an MCU.
+* PIL was asked with ``quality=q, subsampling=2, optimize=False, restart_marker_blocks=RI_420`` (the argument counts MCUs)
+  and these lines give its files byte for byte on the inputs of tests/jpeg420_cases.py
+  (tests/test_jpeg420_layout_cpu.py).  One line had to follow PIL against the first reading of libjpeg: the rows of the
+  chroma planes (above); replicating full-resolution rows to the 16-row MCU height differs for every even H that is no
+  multiple of 16.
 """
 import math
 import struct
@@ -38,6 +62,9 @@ from typing import List, Tuple
 import numpy as np
 
 RI = 32                 # MCUs per restart interval: 96 blocks in colour, one workgroup of the kernel
+RI_420 = 16             # the same with subsampling='4:2:0': 16 MCUs of six blocks
+SUBSAMPLINGS = ('4:4:4', '4:2:0')
+MCU_COMPONENTS_420 = (0, 0, 0, 0, 1, 2)   # the component of each block of a 4:2:0 MCU, in coding order
 FRAC_BITS = 3           # fractional bits of a DCT coefficient before quantisation
 AC_MAX = 1023
 
@@ -123,41 +150,81 @@ def _check(img) -> np.ndarray:
     return img
 
 
-def n_mcus(h: int, w: int) -> int:
-    return (-(-h // 8)) * (-(-w // 8))
+def _is_420(components: int, subsampling: str) -> bool:
+    """Whether the layout is the 4:2:0 one: a grey frame has one plane and ignores the argument."""
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError('jpeg_layout: subsampling must be one of {}, got {!r}'.format(SUBSAMPLINGS, subsampling))
+    return subsampling == '4:2:0' and components == 3
 
 
-def n_intervals(h: int, w: int) -> int:
-    return -(-n_mcus(h, w) // RI)
+def n_mcus(h: int, w: int, subsampling: str = '4:4:4') -> int:
+    """MCUs of a frame (``subsampling`` is the layout's: a grey frame is '4:4:4' whatever was asked for)."""
+    side = 16 if _is_420(3, subsampling) else 8
+    return (-(-h // side)) * (-(-w // side))
 
 
-def header_bytes(components: int) -> int:
+def n_intervals(h: int, w: int, subsampling: str = '4:4:4') -> int:
+    return -(-n_mcus(h, w, subsampling) // (RI_420 if _is_420(3, subsampling) else RI))
+
+
+def header_bytes(components: int, subsampling: str = '4:4:4') -> int:
     """SOI .. SOS: 2 + APP0 18 + DQT 69 a table + SOF0 10 + 3 a component + DHT 33 + 183 a table pair + DRI 6 + SOS 8 + 2 a
-    component."""
+    component.  The same for both samplings."""
+    _is_420(components, subsampling)
     tables = 2 if components == 3 else 1
     return 2 + 18 + 69 * tables + 10 + 3 * components + 216 * tables + 6 + 8 + 2 * components
 
 
-def capacity(h: int, w: int, components: int) -> int:
+def capacity(h: int, w: int, components: int, subsampling: str = '4:4:4') -> int:
     """Upper bound of ``len(encode(img))`` for any image of this shape.  A block's 64 coefficients cost at most 26 bits each:
     DC <= 11 code bits + 11 value bits; a non-zero AC <= 16 + 10 (the clamp); a ZRL is 11 bits for 16 zero coefficients, EOB
     <= 4 bits for a zero coefficient 63.  An interval of b blocks is therefore at most 208 b bytes after the padding (208 b is
-    whole), at most doubled by the stuffing: 416 bytes a block.  Plus the header, two bytes per interval (RST or EOI)."""
+    whole), at most doubled by the stuffing: 416 bytes a block.  Plus the header, two bytes per interval (RST or EOI).
+    4:2:0: the same per block, six blocks for every MCU of the padded 16x16 grid (dummy blocks counted as whole ones)."""
     if components not in (1, 3):
         raise ValueError('jpeg_layout: components must be 1 or 3, got {}'.format(components))
-    return header_bytes(components) + 416 * n_mcus(h, w) * components + 2 * n_intervals(h, w)
+    sampled = _is_420(components, subsampling)
+    layout = '4:2:0' if sampled else '4:4:4'
+    return header_bytes(components) + 416 * n_mcus(h, w, layout) * (6 if sampled else components) + 2 * n_intervals(h, w, layout)
 
 
-def blocks(img) -> np.ndarray:
-    """Level-shifted samples int32 [MCUs, components, 8, 8] in raster MCU order."""
-    img = _check(img)
-    h, w = img.shape[:2]
-    hp, wp = -(-h // 8) * 8, -(-w // 8) * 8
+def _planes(img: np.ndarray) -> np.ndarray:
+    """int32 [components, H, W]: Y Cb Cr of a BGR frame, or the grey plane."""
     if img.ndim == 3:
         b, g, r = (img[..., k].astype(np.int32) for k in range(3))
-        planes = np.stack([(cr * r + cg * g + cb * b + off) >> 16 for cr, cg, cb, off in YCC])
-    else:
-        planes = img.astype(np.int32)[None]
+        return np.stack([(cr * r + cg * g + cb * b + off) >> 16 for cr, cg, cb, off in YCC])
+    return img.astype(np.int32)[None]
+
+
+def dummy_blocks(h: int, w: int) -> np.ndarray:
+    """bool [MCUs, 6] of the 4:2:0 layout: the Y blocks beyond ceil(W/8) block columns or ceil(H/8) block rows."""
+    mh, mw = -(-h // 16), -(-w // 16)
+    bh, bw = -(-h // 8), -(-w // 8)
+    out = np.zeros((mh, mw, 6), dtype=bool)
+    for k in range(4):
+        rows = 2 * np.arange(mh) + (k >> 1) >= bh
+        cols = 2 * np.arange(mw) + (k & 1) >= bw
+        out[:, :, k] = rows[:, None] | cols[None, :]
+    return out.reshape(-1, 6)
+
+
+def blocks(img, subsampling: str = '4:4:4') -> np.ndarray:
+    """Level-shifted samples int32 [MCUs, blocks of an MCU, 8, 8] in raster MCU order: one block a component, or with 4:2:0
+    the six of ``MCU_COMPONENTS_420`` (a dummy block holds the replicated pixels here; ``coefficients`` replaces it)."""
+    img = _check(img)
+    h, w = img.shape[:2]
+    planes = _planes(img)
+    if _is_420(planes.shape[0], subsampling):
+        hp, wp = -(-h // 16) * 16, -(-w // 16) * 16
+        he = h + (h & 1)
+        luma = np.pad(planes[0], ((0, hp - h), (0, wp - w)), mode='edge') - 128
+        luma = luma.reshape(hp // 16, 2, 8, wp // 16, 2, 8).transpose(0, 3, 1, 4, 2, 5).reshape(-1, 4, 8, 8)
+        quad = np.pad(planes[1:], ((0, 0), (0, he - h), (0, wp - w)), mode='edge').reshape(2, he // 2, 2, wp // 2, 2).sum(axis=(2, 4))
+        bias = 1 + (np.arange(wp // 2, dtype=np.int32) & 1)
+        chroma = np.pad((quad + bias) >> 2, ((0, 0), (0, (hp - he) // 2), (0, 0)), mode='edge') - 128
+        chroma = chroma.reshape(2, hp // 16, 8, wp // 16, 8).transpose(1, 3, 0, 2, 4).reshape(-1, 2, 8, 8)
+        return np.concatenate([luma, chroma], axis=1).astype(np.int32)
+    hp, wp = -(-h // 8) * 8, -(-w // 8) * 8
     planes = np.pad(planes, ((0, 0), (0, hp - h), (0, wp - w)), mode='edge') - 128
     c = planes.shape[0]
     return planes.reshape(c, hp // 8, 8, wp // 8, 8).transpose(1, 3, 0, 2, 4).reshape(-1, c, 8, 8)
@@ -192,17 +259,24 @@ def fdct_1d(d: np.ndarray, first: bool) -> np.ndarray:
     return np.stack(o, -1).astype(np.int32)
 
 
-def coefficients(img, quality: int = 90) -> np.ndarray:
-    """Quantised coefficients int32 [MCUs, components, 64] in zigzag order."""
-    s = blocks(img)                                                           # [m, c, y, x]
+def coefficients(img, quality: int = 90, subsampling: str = '4:4:4') -> np.ndarray:
+    """Quantised coefficients int32 [MCUs, blocks of an MCU, 64] in zigzag order."""
+    s = blocks(img, subsampling)                                              # [m, c, y, x]
+    sampled = s.shape[1] == 6
+    comps = MCU_COMPONENTS_420 if sampled else tuple(range(s.shape[1]))
     rows = fdct_1d(s, True)                                                   # [m, c, y, u]
     f = fdct_1d(rows.swapaxes(-1, -2), False).swapaxes(-1, -2)                # [m, c, v, u]
     f = f.reshape(s.shape[0], s.shape[1], 64)
     tables = quant_tables(quality)
-    q = np.stack([tables[0 if c == 0 else 1] for c in range(s.shape[1])]).astype(np.int32)[None] << FRAC_BITS
+    q = np.stack([tables[0 if c == 0 else 1] for c in comps]).astype(np.int32)[None] << FRAC_BITS
     mag = (np.abs(f) + (q >> 1)) // q
     out = np.where(f < 0, -mag, mag).astype(np.int32)
     out[..., 1:] = np.clip(out[..., 1:], -AC_MAX, AC_MAX)
+    if sampled:
+        dummy = dummy_blocks(*np.asarray(img).shape[:2])
+        for k in range(1, 4):                                                 # in coding order: a copy may be copied on
+            out[dummy[:, k], k, 1:] = 0
+            out[dummy[:, k], k, 0] = out[dummy[:, k], k - 1, 0]
     return out[..., list(ZIGZAG)]
 
 
@@ -210,16 +284,17 @@ def _size(v: int) -> int:
     return int(abs(v)).bit_length()
 
 
-def _scan(img, quality: int):
+def _scan(img, quality: int, subsampling: str = '4:4:4'):
     """Per restart interval the list of (kind, rs, component, value bits, number of value bits)."""
-    coef = coefficients(img, quality)
+    coef = coefficients(img, quality, subsampling)
     n, c = coef.shape[:2]
+    comps, ri = (MCU_COMPONENTS_420, RI_420) if c == 6 else (tuple(range(c)), RI)
     out = []
-    for first in range(0, n, RI):
-        rec, pred = [], [0] * c
-        for m in range(first, min(first + RI, n)):
-            for k in range(c):
-                z = coef[m, k].tolist()
+    for first in range(0, n, ri):
+        rec, pred = [], [0] * 3
+        for m in range(first, min(first + ri, n)):
+            for j, k in enumerate(comps):
+                z = coef[m, j].tolist()
                 d = z[0] - pred[k]
                 pred[k] = z[0]
                 s = _size(d)
@@ -241,40 +316,42 @@ def _scan(img, quality: int):
     return out
 
 
-def symbols(img, quality: int = 90) -> List[Symbol]:
+def symbols(img, quality: int = 90, subsampling: str = '4:4:4') -> List[Symbol]:
     """The symbols the scan encodes, in order (for the tests: does an input reach ZRL, a block without EOB, ...)."""
-    return [Symbol(kind, rs, k, i) for i, rec in enumerate(_scan(img, quality)) for kind, rs, k, _, _ in rec]
+    return [Symbol(kind, rs, k, i) for i, rec in enumerate(_scan(img, quality, subsampling)) for kind, rs, k, _, _ in rec]
 
 
 def _segment(marker: int, payload: bytes) -> bytes:
     return struct.pack('>BBH', 0xFF, marker, len(payload) + 2) + payload
 
 
-def header(h: int, w: int, components: int, quality: int) -> bytes:
+def header(h: int, w: int, components: int, quality: int, subsampling: str = '4:4:4') -> bytes:
+    sampled = _is_420(components, subsampling)
     tables = quant_tables(quality)
     nt = 2 if components == 3 else 1
     out = b'\xff\xd8' + _segment(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
     for t in range(nt):
         out += _segment(0xDB, bytes([t]) + bytes(int(tables[t][z]) for z in ZIGZAG))
     out += _segment(0xC0, struct.pack('>BHHB', 8, h, w, components)
-                    + b''.join(bytes([k + 1, 0x11, 0 if k == 0 else 1]) for k in range(components)))
+                    + b''.join(bytes([k + 1, 0x22 if sampled and k == 0 else 0x11, 0 if k == 0 else 1])
+                               for k in range(components)))
     for tc_th, counts, syms in HUFFMAN[:2 * nt]:
         out += _segment(0xC4, bytes([tc_th]) + bytes(counts) + bytes(syms))
-    out += _segment(0xDD, struct.pack('>H', RI))
+    out += _segment(0xDD, struct.pack('>H', RI_420 if sampled else RI))
     out += _segment(0xDA, bytes([components]) + b''.join(bytes([k + 1, 0x00 if k == 0 else 0x11]) for k in range(components))
                     + b'\x00\x3f\x00')
     assert len(out) == header_bytes(components)
     return out
 
 
-def encode(img, quality: int = 90) -> bytes:
+def encode(img, quality: int = 90, subsampling: str = '4:4:4') -> bytes:
     """The JPEG file of a uint8 [H,W,3] BGR or [H,W] grey array in the layout above."""
     img = _check(img)
     h, w = img.shape[:2]
     components = 3 if img.ndim == 3 else 1
     codes = [huffman_codes(counts, syms) for _, counts, syms in HUFFMAN]
-    out = bytearray(header(h, w, components, quality))
-    scan = _scan(img, quality)
+    out = bytearray(header(h, w, components, quality, subsampling))
+    scan = _scan(img, quality, subsampling)
     for i, rec in enumerate(scan):
         acc, nbits = 0, 0
         for kind, rs, k, value, vbits in rec:

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 26
+#define FOSVOS_ABI_VERSION 27
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -462,6 +462,19 @@ size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components); /* per f
 size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components);
 int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int quality, uint8_t *out,
                        size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* The same with the chroma sampling chosen (ABI 27): sampling 444 is exactly the three entry points above, 420 halves both
+ * chroma planes.  With 420 an MCU is 16x16 pixels and six blocks (Y Y Y Y Cb Cr), SOF0 says 2x2 1x1 1x1, the restart
+ * interval is 16 MCUs; chroma is libjpeg's h2v2 mean with the alternating bias, luma blocks beyond ceil(W/8) x ceil(H/8)
+ * are dummies (DC of the block in front, no AC) - util/jpeg_layout.py states all of it, and the file is byte for byte
+ * libjpeg-turbo's for the same parameters.  The bound is header + 416 B x 6 blocks an MCU of the padded grid + 2 B an
+ * interval; the workspace 4 B an interval.  A grey frame (components = 1) has no chroma: 420 gives the 444 file and sizes.
+ * Any other sampling: the sizes are 0, the encode returns FOSVOS_E_ARG. */
+size_t fosvos_jpeg_capacity_bytes_sampled(int N, int H, int W, int components, int sampling); /* per frame */
+size_t fosvos_jpeg_workspace_bytes_sampled(int N, int H, int W, int components, int sampling);
+int fosvos_jpeg_encode_sampled(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality,
+                               uint8_t *out, size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes,
+                               int device, void *stream);
 
 /* ---- streaming inference: a raw camera frame in, the frame that is shown out -----------------------------------------
  * The per-frame arithmetic of src/run_webcam.py:81-133 (apply_network) on the device beside the nets; the definitions are
