@@ -1,16 +1,17 @@
 // Class-balanced BCE-with-logits: loss + gradient, fused (reference: src/layers/osvos_layers.py:17-44).
 //
-// HBM-bound.  Algorithmic bytes per pixel: pass 1 reads the label (4 B); pass 2 reads logit and
-// label (8 B) and writes the gradient (4 B) = 16 B/pixel.  Three launches:
-//   k_count    per-block positive counts            -> ws.count[block]
-//   k_loss     every block re-sums the counts in index order (so all agree bit-for-bit), then
-//              writes grad and per-block fp64 partial sums of the positive / negative losses
-//   k_finish   one wave sums the partials in index order and writes the fp32 loss
-// All sums are fixed-order: results are bitwise reproducible run to run.
+// One loss kernel serves every entry point: k_loss<M> walks M logit maps that share one label batch (M = 1: the plain and the
+// per-frame loss; M = 5: the offline objective's four side maps and the fused one).  Three launches:
+//   k_count    per-block positive counts            -> ws.count[block] of the frame's first record
+//   k_loss<M>  every block re-sums the counts in index order (so all agree bit-for-bit) - or takes them from ext_counts -,
+//              then writes each map's grad and per-block fp64 partial sums of its positive / negative losses
+//   k_finish   one wave per record sums the partials in index order and writes the fp32 loss
+// All sums are fixed-order: results are bitwise reproducible run to run, and a map's result does not depend on M - the
+// multi-map loss equals the per-map loss bit for bit because it IS the same code.
 //
-// k_loss_multi is k_loss for M logit maps that share one label batch (the offline objective: four side maps and the fused
-// one): a thread reads its four labels once and walks the maps - 4 + M x 8 B/pixel instead of M x 16, one launch instead of
-// M x 3.  Same pixel partition, same float expressions (px_loss_grad), same fixed-order partials: bit for bit k_loss per map.
+// HBM-bound.  Algorithmic bytes per pixel: pass 1 reads the label (4 B); pass 2 reads the label once (4 B) and per map reads
+// the logit and writes the gradient (8 B) = 16 B/pixel for one map.  M maps of one label cost 4 + (4 + M x 8) B/pixel where
+// M one-map losses cost M x 16, in one set of launches instead of M.
 #include "common.hpp"
 
 using namespace fosvos;
@@ -36,7 +37,7 @@ __device__ __forceinline__ void load4(const float *__restrict__ p, int64_t i, in
     }
 }
 
-// one pixel: its loss term and its gradient (the expressions k_loss and k_loss_multi share, so that they agree bit for bit)
+// one pixel: its loss term and its gradient
 __device__ __forceinline__ float px_loss_grad(float xx, bool y, float w_pos, float w_neg, float &g) {
     const float e = expf(-fabsf(xx));          // in (0,1]
     const float l = fmaxf(xx, 0.f) - (y ? xx : 0.f) + log1pf(e);
@@ -47,7 +48,7 @@ __device__ __forceinline__ float px_loss_grad(float xx, bool y, float w_pos, flo
 }
 
 // blockIdx.y = frame: every frame of a batch is its own loss (own class counts, own workspace record, own output)
-// (ws_stride: records per frame - 1, or the number of maps of k_loss_multi, whose frame keeps its counts in its first record)
+// (ws_stride: records per frame = the number of maps of k_loss; a frame keeps its counts in its first record)
 __global__ __launch_bounds__(kBlock) void k_count(const float *__restrict__ label, int64_t n, Ws *ws, int ws_stride) {
     label += (int64_t)blockIdx.y * n;
     ws += (int64_t)blockIdx.y * ws_stride;
@@ -68,15 +69,25 @@ __global__ __launch_bounds__(kBlock) void k_count(const float *__restrict__ labe
     if (threadIdx.x == 0) ws->count[blockIdx.x] = (unsigned long long)s[0] + s[1] + s[2] + s[3];
 }
 
-__global__ __launch_bounds__(kBlock) void k_loss(const float *__restrict__ x, const float *__restrict__ label,
-                                                  int64_t n, int size_average, float grad_scale,
-                                                  float *__restrict__ grad, Ws *ws, int n_count_blocks,
-                                                  const double *__restrict__ ext_counts) {
-    x += (int64_t)blockIdx.y * n;
-    label += (int64_t)blockIdx.y * n;
-    if (grad) grad += (int64_t)blockIdx.y * n;
-    ws += blockIdx.y;
-    __shared__ double s_pos[kBlock / 64], s_neg[kBlock / 64];
+// The logit maps of one launch: separate tensors, so the table travels by value in the kernel arguments (arrays of M: the
+// one-map instance carries two pointers and a float).
+template <int M>
+struct Maps {
+    const float *x[M];
+    float *grad[M];  // an entry may be null
+    float scale[M];  // the factor on map m's gradient
+};
+
+// M maps with one label: record blockIdx.y * M + m takes map m's partials, the counts are in the frame's first record
+// (k_count with ws_stride = M).  M is a template parameter so that the table is indexed by constants.
+// ext_counts (data-parallel batches): {positives, pixels} of the WHOLE batch, counted over all ranks, instead of the workspace's
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_loss(Maps<M> maps, const float *__restrict__ label, int64_t n, int size_average,
+                                                  Ws *ws, int n_count_blocks, const double *__restrict__ ext_counts) {
+    const int64_t frame_off = (int64_t)blockIdx.y * n;
+    label += frame_off;
+    ws += (int64_t)blockIdx.y * M;
+    __shared__ double s_pos[M][kBlock / 64], s_neg[M][kBlock / 64];
     __shared__ unsigned long long s_np;
     if (!ext_counts) {   // integer sum of the per-block counts: order-independent, so every block agrees exactly
         __shared__ unsigned long long s_c[kBlock / 64];
@@ -89,89 +100,15 @@ __global__ __launch_bounds__(kBlock) void k_loss(const float *__restrict__ x, co
         if (threadIdx.x == 0) s_np = s_c[0] + s_c[1] + s_c[2] + s_c[3];
         __syncthreads();
     }
-    // ext_counts (data-parallel batches): {positives, pixels} of the WHOLE batch, counted over all ranks
     const double n_tot = ext_counts ? ext_counts[1] : (double)n;
     const double n_pos = ext_counts ? ext_counts[0] : (double)s_np;
-    const double n_neg = n_tot - n_pos;
-    double gscale = (double)grad_scale;
-    if (size_average) gscale /= n_tot;
-    const float w_pos = (float)(n_neg / n_tot * gscale);  // weight of a positive pixel
-    const float w_neg = (float)(n_pos / n_tot * gscale);
-
-    double pos = 0.0, neg = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * kBlock * kPerThread;
-    for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPerThread; i < n; i += stride) {
-        float xv[4], yv[4], g[4];
-        load4(x, i, n, xv, 0.f);
-        load4(label, i, n, yv, 0.f);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool y = yv[j] >= 0.5f;
-            const float l = px_loss_grad(xv[j], y, w_pos, w_neg, g[j]);
-            if (i + j < n) {
-                if (y) pos += (double)l; else neg += (double)l;
-            }
-        }
-        if (grad) {
-            if (i + 3 < n) {
-                *reinterpret_cast<float4 *>(grad + i) = make_float4(g[0], g[1], g[2], g[3]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i + j < n) grad[i + j] = g[j];
-            }
-        }
-    }
-    pos = wave_sum(pos);
-    neg = wave_sum(neg);
-    if ((threadIdx.x & 63) == 0) {
-        s_pos[threadIdx.x >> 6] = pos;
-        s_neg[threadIdx.x >> 6] = neg;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ws->pos[blockIdx.x] = (s_pos[0] + s_pos[1]) + (s_pos[2] + s_pos[3]);
-        ws->neg[blockIdx.x] = (s_neg[0] + s_neg[1]) + (s_neg[2] + s_neg[3]);
-    }
-}
-
-// The logit maps of k_loss_multi: separate tensors, so the table travels by value in the kernel arguments.
-struct Maps {
-    const float *x[FOSVOS_CBCE_MAX_MAPS];
-    float *grad[FOSVOS_CBCE_MAX_MAPS];  // an entry may be null
-    float scale[FOSVOS_CBCE_MAX_MAPS];  // grad_scale of k_loss, per map
-};
-
-// k_loss over M maps with one label: record blockIdx.y * M + m takes map m's partials, the counts are in the frame's first
-// record (k_count with ws_stride = M).  M is a template parameter so that the table is indexed by constants.
-template <int M>
-__global__ __launch_bounds__(kBlock) void k_loss_multi(Maps maps, const float *__restrict__ label, int64_t n,
-                                                       int size_average, Ws *ws, int n_count_blocks) {
-    const int64_t frame_off = (int64_t)blockIdx.y * n;
-    label += frame_off;
-    ws += (int64_t)blockIdx.y * M;
-    __shared__ double s_pos[M][kBlock / 64], s_neg[M][kBlock / 64];
-    __shared__ unsigned long long s_np;
-    {
-        __shared__ unsigned long long s_c[kBlock / 64];
-        unsigned long long c = 0;
-        for (int b = threadIdx.x; b < n_count_blocks; b += kBlock) c += ws->count[b];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) s_np = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-        __syncthreads();
-    }
-    const double n_tot = (double)n;
-    const double n_pos = (double)s_np;
     const double n_neg = n_tot - n_pos;
     float w_pos[M], w_neg[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {
         double gscale = (double)maps.scale[m];
         if (size_average) gscale /= n_tot;
-        w_pos[m] = (float)(n_neg / n_tot * gscale);
+        w_pos[m] = (float)(n_neg / n_tot * gscale);  // weight of a positive pixel
         w_neg[m] = (float)(n_pos / n_tot * gscale);
     }
 
@@ -225,8 +162,7 @@ __global__ __launch_bounds__(kBlock) void k_loss_multi(Maps maps, const float *_
     }
 }
 
-
-// blockIdx.x = record (frame x map, maps = 1 for k_loss); the class counts are in the first record of the frame
+// blockIdx.x = record (frame x map); the class counts are in the first record of the frame
 __global__ __launch_bounds__(64) void k_finish(int64_t n, int size_average, const Ws *ws, int n_blocks,
                                                 float *__restrict__ loss_out, const double *__restrict__ ext_counts, int maps) {
     const Ws *ws_count = ws + (blockIdx.x / maps) * maps;
@@ -267,71 +203,115 @@ __global__ __launch_bounds__(64) void k_finish(int64_t n, int size_average, cons
 }
 }  // namespace
 
+
 extern "C" size_t fosvos_cbce_workspace_bytes(int64_t) { return sizeof(Ws); }
 
+extern "C" size_t fosvos_cbce_multi_workspace_bytes(int64_t, int n_frames, int n_maps) {
+    return n_frames > 0 && n_maps > 0 ? (size_t)n_frames * n_maps * sizeof(Ws) : 0;
+}
+
 namespace {
-// parts: which of the three launches run (FOSVOS_CBCE_COUNT | _LOSS | _FINISH; the one-call entry points pass all three)
-int cbce_impl(const float *logits, const float *label, int64_t numel, int n_frames, int size_average, float grad_scale,
-              const double *batch_counts, float *loss_out, float *grad, void *workspace, size_t workspace_bytes,
-              int device, void *stream, int parts = FOSVOS_CBCE_COUNT | FOSVOS_CBCE_LOSS | FOSVOS_CBCE_FINISH) {
-    FOSVOS_REQUIRE(parts > 0 && parts <= 7, FOSVOS_E_ARG, "cbce_loss: parts=%d", parts);
+typedef Maps<FOSVOS_CBCE_MAX_MAPS> MapTable;  // what an entry point fills; the launch takes its first M entries
+
+template <int M>
+void launch_loss(const MapTable &table, const float *label, int64_t numel, int n_frames, int size_average, Ws *ws, int blocks,
+                 const double *ext_counts, hipStream_t s) {
+    Maps<M> maps;
+    for (int m = 0; m < M; ++m) {
+        maps.x[m] = table.x[m];
+        maps.grad[m] = table.grad[m];
+        maps.scale[m] = table.scale[m];
+    }
+    hipLaunchKernelGGL(k_loss<M>, dim3(blocks, n_frames), dim3(kBlock), 0, s, maps, label, numel, size_average, ws, blocks,
+                       ext_counts);
+}
+
+// Every loss entry point: the argument checks (all of them in front of the first launch), then the launches `parts` names
+// (FOSVOS_CBCE_COUNT | _LOSS | _FINISH).  who: the entry point, for the messages; loss_label: what the launch profiler calls
+// the loss launch; ext_counts: the batch's class counts (null: k_count takes the frames' own).
+int cbce_run(const char *who, const char *loss_label, const MapTable &maps, int n_maps, const float *label, int64_t numel,
+             int n_frames, int size_average, const double *ext_counts, float *loss_out, void *workspace,
+             size_t workspace_bytes, int parts, int device, void *stream) {
+    FOSVOS_REQUIRE(parts > 0 && parts <= 7, FOSVOS_E_ARG, "%s: parts=%d", who, parts);
+    FOSVOS_REQUIRE(n_maps >= 1 && n_maps <= FOSVOS_CBCE_MAX_MAPS, FOSVOS_E_ARG, "%s: n_maps=%d (1..%d)", who, n_maps,
+                   FOSVOS_CBCE_MAX_MAPS);
     FOSVOS_REQUIRE(workspace && (label || !(parts & (FOSVOS_CBCE_COUNT | FOSVOS_CBCE_LOSS))) &&
-                       (logits || !(parts & FOSVOS_CBCE_LOSS)) && (loss_out || !(parts & FOSVOS_CBCE_FINISH)),
-                   FOSVOS_E_ARG, "cbce_loss: null pointer");
-    FOSVOS_REQUIRE(numel > 0, FOSVOS_E_SHAPE, "cbce_loss: numel=%lld", (long long)numel);
-    FOSVOS_REQUIRE(n_frames >= 1 && n_frames <= 65535, FOSVOS_E_SHAPE, "cbce_loss: n_frames=%d", n_frames);
+                       (loss_out || !(parts & FOSVOS_CBCE_FINISH)),
+                   FOSVOS_E_ARG, "%s: null pointer", who);
+    FOSVOS_REQUIRE(numel > 0, FOSVOS_E_SHAPE, "%s: numel=%lld", who, (long long)numel);
+    FOSVOS_REQUIRE(n_frames >= 1 && n_frames <= 65535, FOSVOS_E_SHAPE, "%s: n_frames=%d", who, n_frames);
     FOSVOS_REQUIRE(n_frames == 1 || numel % 4 == 0, FOSVOS_E_SHAPE,
-                   "cbce_loss_frames: %lld elements per frame - frames after the first would start off a 16-byte boundary",
+                   "%s: %lld elements per frame - frames after the first would start off a 16-byte boundary", who,
                    (long long)numel);
-    FOSVOS_REQUIRE(workspace_bytes >= n_frames * sizeof(Ws), FOSVOS_E_WORKSPACE, "cbce_loss: workspace %zu < %zu",
-                   workspace_bytes, n_frames * sizeof(Ws));
-    FOSVOS_REQUIRE((!logits || (uintptr_t)logits % 16 == 0) && (!label || (uintptr_t)label % 16 == 0) &&
-                       (!grad || (uintptr_t)grad % 16 == 0),
-                   FOSVOS_E_ARG, "cbce_loss: pointers must be 16-byte aligned");
+    const size_t need = (size_t)n_frames * n_maps * sizeof(Ws);
+    FOSVOS_REQUIRE(workspace_bytes >= need, FOSVOS_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    FOSVOS_REQUIRE((uintptr_t)workspace % 8 == 0 && (uintptr_t)label % 16 == 0, FOSVOS_E_ARG,
+                   "%s: label must be 16-byte aligned, the workspace 8-byte", who);
+    for (int m = 0; m < n_maps; ++m) {
+        FOSVOS_REQUIRE(maps.x[m] || !(parts & FOSVOS_CBCE_LOSS), FOSVOS_E_ARG, "%s: logits[%d] is null", who, m);
+        FOSVOS_REQUIRE((uintptr_t)maps.x[m] % 16 == 0 && (uintptr_t)maps.grad[m] % 16 == 0, FOSVOS_E_ARG,
+                       "%s: map %d: pointers must be 16-byte aligned", who, m);
+    }
     FOSVOS_ENTER(device);
     int blocks = (int)cdiv(numel, (int64_t)kBlock * kPerThread);
     if (blocks > kMaxBlocks) blocks = kMaxBlocks;
     Ws *ws = reinterpret_cast<Ws *>(workspace);
     hipStream_t s = (hipStream_t)stream;
-    if (!batch_counts && (parts & FOSVOS_CBCE_COUNT)) {
+    if (!ext_counts && (parts & FOSVOS_CBCE_COUNT)) {
         FOSVOS_PROF("k_count", s, 0.0);
-        hipLaunchKernelGGL(k_count, dim3(blocks, n_frames), dim3(kBlock), 0, s, label, numel, ws, 1);
+        hipLaunchKernelGGL(k_count, dim3(blocks, n_frames), dim3(kBlock), 0, s, label, numel, ws, n_maps);
         FOSVOS_LAUNCH_CHECK();
     }
     if (parts & FOSVOS_CBCE_LOSS) {
-        FOSVOS_PROF("k_loss", s, 0.0);
-        hipLaunchKernelGGL(k_loss, dim3(blocks, n_frames), dim3(kBlock), 0, s, logits, label, numel, size_average, grad_scale,
-                           grad, ws, blocks, batch_counts);
+        static constexpr decltype(&launch_loss<1>) launch[FOSVOS_CBCE_MAX_MAPS] = {
+            launch_loss<1>, launch_loss<2>, launch_loss<3>, launch_loss<4>,
+            launch_loss<5>, launch_loss<6>, launch_loss<7>, launch_loss<8>};
+        FOSVOS_PROF(loss_label, s, 0.0);
+        launch[n_maps - 1](maps, label, numel, n_frames, size_average, ws, blocks, ext_counts, s);
         FOSVOS_LAUNCH_CHECK();
     }
     if (parts & FOSVOS_CBCE_FINISH) {
         FOSVOS_PROF("k_finish", s, 0.0);
-        hipLaunchKernelGGL(k_finish, dim3(n_frames), dim3(64), 0, s, numel, size_average, ws, blocks, loss_out, batch_counts, 1);
+        hipLaunchKernelGGL(k_finish, dim3(n_frames * n_maps), dim3(64), 0, s, numel, size_average, ws, blocks, loss_out,
+                           ext_counts, n_maps);
         FOSVOS_LAUNCH_CHECK();
     }
     return FOSVOS_OK;
 }
+
+// the one-map entry points: one tensor of logits, one of gradients
+int cbce_run1(const char *who, const float *logits, const float *label, int64_t numel, int n_frames, int size_average,
+              float grad_scale, const double *ext_counts, float *loss_out, float *grad, void *workspace,
+              size_t workspace_bytes, int parts, int device, void *stream) {
+    MapTable maps = {};
+    maps.x[0] = logits;
+    maps.grad[0] = grad;
+    maps.scale[0] = grad_scale;
+    return cbce_run(who, "k_loss", maps, 1, label, numel, n_frames, size_average, ext_counts, loss_out, workspace,
+                    workspace_bytes, parts, device, stream);
+}
+constexpr int kAllParts = FOSVOS_CBCE_COUNT | FOSVOS_CBCE_LOSS | FOSVOS_CBCE_FINISH;
 }  // namespace
 
 extern "C" int fosvos_cbce_loss(const float *logits, const float *label, int64_t numel, int size_average,
                                 float grad_scale, float *loss_out, float *grad, void *workspace,
                                 size_t workspace_bytes, int device, void *stream) {
-    return cbce_impl(logits, label, numel, 1, size_average, grad_scale, nullptr, loss_out, grad, workspace, workspace_bytes,
-                     device, stream);
+    return cbce_run1("cbce_loss", logits, label, numel, 1, size_average, grad_scale, nullptr, loss_out, grad, workspace,
+                     workspace_bytes, kAllParts, device, stream);
 }
 
 extern "C" int fosvos_cbce_loss_frames(const float *logits, const float *label, int64_t frame_numel, int n_frames,
                                        int size_average, float grad_scale, float *loss_out, float *grad, void *workspace,
                                        size_t workspace_bytes, int device, void *stream) {
-    return cbce_impl(logits, label, frame_numel, n_frames, size_average, grad_scale, nullptr, loss_out, grad, workspace,
-                     workspace_bytes, device, stream);
+    return cbce_run1("cbce_loss_frames", logits, label, frame_numel, n_frames, size_average, grad_scale, nullptr, loss_out,
+                     grad, workspace, workspace_bytes, kAllParts, device, stream);
 }
 
 extern "C" int fosvos_cbce_loss_frames_parts(const float *logits, const float *label, int64_t frame_numel, int n_frames,
                                              int size_average, float grad_scale, float *loss_out, float *grad,
                                              void *workspace, size_t workspace_bytes, int parts, int device, void *stream) {
-    return cbce_impl(logits, label, frame_numel, n_frames, size_average, grad_scale, nullptr, loss_out, grad, workspace,
-                     workspace_bytes, device, stream, parts);
+    return cbce_run1("cbce_loss_frames_parts", logits, label, frame_numel, n_frames, size_average, grad_scale, nullptr,
+                     loss_out, grad, workspace, workspace_bytes, parts, device, stream);
 }
 
 extern "C" int fosvos_cbce_loss_batch_counts(const float *logits, const float *label, int64_t numel, int size_average,
@@ -339,83 +319,25 @@ extern "C" int fosvos_cbce_loss_batch_counts(const float *logits, const float *l
                                              float *grad, void *workspace, size_t workspace_bytes, int device,
                                              void *stream) {
     FOSVOS_REQUIRE(batch_counts, FOSVOS_E_ARG, "cbce_loss_batch_counts: null batch_counts");
-    return cbce_impl(logits, label, numel, 1, size_average, grad_scale, batch_counts, loss_out, grad, workspace,
-                     workspace_bytes, device, stream);
+    return cbce_run1("cbce_loss_batch_counts", logits, label, numel, 1, size_average, grad_scale, batch_counts, loss_out,
+                     grad, workspace, workspace_bytes, kAllParts, device, stream);
 }
-
-extern "C" size_t fosvos_cbce_multi_workspace_bytes(int64_t, int n_frames, int n_maps) {
-    return n_frames > 0 && n_maps > 0 ? (size_t)n_frames * n_maps * sizeof(Ws) : 0;
-}
-
-namespace {
-template <int M>
-void launch_loss_multi(const Maps &maps, const float *label, int64_t numel, int n_frames, int size_average, Ws *ws,
-                       int blocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_loss_multi<M>, dim3(blocks, n_frames), dim3(kBlock), 0, s, maps, label, numel, size_average, ws,
-                       blocks);
-}
-}  // namespace
 
 extern "C" int fosvos_cbce_loss_frames_multi(const float *const *logits, const float *label, int64_t frame_numel,
                                              int n_frames, int n_maps, int size_average, const float *map_scale,
                                              float *loss_out, float *const *grad, void *workspace, size_t workspace_bytes,
                                              int parts, int device, void *stream) {
-    FOSVOS_REQUIRE(parts > 0 && parts <= 7, FOSVOS_E_ARG, "cbce_loss_frames_multi: parts=%d", parts);
-    FOSVOS_REQUIRE(n_maps >= 1 && n_maps <= FOSVOS_CBCE_MAX_MAPS, FOSVOS_E_ARG, "cbce_loss_frames_multi: n_maps=%d (1..%d)",
-                   n_maps, FOSVOS_CBCE_MAX_MAPS);
-    FOSVOS_REQUIRE(workspace && (label || !(parts & (FOSVOS_CBCE_COUNT | FOSVOS_CBCE_LOSS))) &&
-                       ((logits && map_scale) || !(parts & FOSVOS_CBCE_LOSS)) && (loss_out || !(parts & FOSVOS_CBCE_FINISH)),
-                   FOSVOS_E_ARG, "cbce_loss_frames_multi: null pointer");
-    FOSVOS_REQUIRE(frame_numel > 0, FOSVOS_E_SHAPE, "cbce_loss_frames_multi: frame_numel=%lld", (long long)frame_numel);
-    FOSVOS_REQUIRE(n_frames >= 1 && n_frames <= 65535, FOSVOS_E_SHAPE, "cbce_loss_frames_multi: n_frames=%d", n_frames);
-    FOSVOS_REQUIRE(n_frames == 1 || frame_numel % 4 == 0, FOSVOS_E_SHAPE,
-                   "cbce_loss_frames_multi: %lld elements per frame - frames after the first would start off a 16-byte boundary",
-                   (long long)frame_numel);
-    const size_t need = (size_t)n_frames * n_maps * sizeof(Ws);
-    FOSVOS_REQUIRE(workspace_bytes >= need, FOSVOS_E_WORKSPACE, "cbce_loss_frames_multi: workspace %zu < %zu", workspace_bytes,
-                   need);
-    FOSVOS_REQUIRE((uintptr_t)workspace % 8 == 0 && (!label || (uintptr_t)label % 16 == 0), FOSVOS_E_ARG,
-                   "cbce_loss_frames_multi: label must be 16-byte aligned, the workspace 8-byte");
-    Maps maps = {};
+    // the only stage that reads the maps is the loss launch: the tables of another stage's call may be absent
+    FOSVOS_REQUIRE((logits && map_scale) || !(parts & FOSVOS_CBCE_LOSS), FOSVOS_E_ARG,
+                   "cbce_loss_frames_multi: null pointer");
+    MapTable maps = {};
     if (parts & FOSVOS_CBCE_LOSS) {
-        for (int m = 0; m < n_maps; ++m) {
-            FOSVOS_REQUIRE(logits[m], FOSVOS_E_ARG, "cbce_loss_frames_multi: logits[%d] is null", m);
-            FOSVOS_REQUIRE((uintptr_t)logits[m] % 16 == 0 && (!grad || (uintptr_t)grad[m] % 16 == 0), FOSVOS_E_ARG,
-                           "cbce_loss_frames_multi: map %d: pointers must be 16-byte aligned", m);
+        for (int m = 0; m < n_maps && m < FOSVOS_CBCE_MAX_MAPS; ++m) {
             maps.x[m] = logits[m];
             maps.grad[m] = grad ? grad[m] : nullptr;
             maps.scale[m] = map_scale[m];
         }
     }
-    FOSVOS_ENTER(device);
-    int blocks = (int)cdiv(frame_numel, (int64_t)kBlock * kPerThread);
-    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    Ws *ws = reinterpret_cast<Ws *>(workspace);
-    hipStream_t s = (hipStream_t)stream;
-    if (parts & FOSVOS_CBCE_COUNT) {
-        FOSVOS_PROF("k_count", s, 0.0);
-        hipLaunchKernelGGL(k_count, dim3(blocks, n_frames), dim3(kBlock), 0, s, label, frame_numel, ws, n_maps);
-        FOSVOS_LAUNCH_CHECK();
-    }
-    if (parts & FOSVOS_CBCE_LOSS) {
-        FOSVOS_PROF("k_loss_multi", s, 0.0);
-        switch (n_maps) {
-        case 1: launch_loss_multi<1>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        case 2: launch_loss_multi<2>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        case 3: launch_loss_multi<3>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        case 4: launch_loss_multi<4>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        case 5: launch_loss_multi<5>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        case 6: launch_loss_multi<6>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        case 7: launch_loss_multi<7>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        default: launch_loss_multi<8>(maps, label, frame_numel, n_frames, size_average, ws, blocks, s); break;
-        }
-        FOSVOS_LAUNCH_CHECK();
-    }
-    if (parts & FOSVOS_CBCE_FINISH) {
-        FOSVOS_PROF("k_finish", s, 0.0);
-        hipLaunchKernelGGL(k_finish, dim3(n_frames * n_maps), dim3(64), 0, s, frame_numel, size_average, ws, blocks, loss_out,
-                           (const double *)nullptr, n_maps);
-        FOSVOS_LAUNCH_CHECK();
-    }
-    return FOSVOS_OK;
+    return cbce_run("cbce_loss_frames_multi", "k_loss_multi", maps, n_maps, label, frame_numel, n_frames, size_average,
+                    nullptr, loss_out, workspace, workspace_bytes, parts, device, stream);
 }

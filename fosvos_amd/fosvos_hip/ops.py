@@ -602,69 +602,6 @@ def cbce_loss_frames(logits: torch.Tensor, label: torch.Tensor, size_average: bo
 
 
 CBCE_COUNT, CBCE_LOSS, CBCE_FINISH = 1, 2, 4
-
-
-class CbceFramesStaged(object):
-    """``cbce_loss_frames`` in its three launches (fosvos_cbce_loss_frames_parts), for a loop that has a forward pass to
-    put behind the first and a backward pass behind the second: the class counts need only the labels, the backward pass
-    only the gradient - counting beside the forward pass and writing the loss VALUES behind the backward pass takes two
-    small dependent launches (and the copy of the values to the host) off the path between the two passes.
-
-        staged = CbceFramesStaged(label)              # counts; before the forward pass
-        losses, grad = staged.loss(logits, ...)       # `losses` is allocated, NOT yet written
-        ...backward pass...
-        staged.finish()                               # now `losses` holds the values (stream order)
-
-    Same stream for all three calls.  Frames whose element count is not a multiple of 4 are not supported here (the caller
-    falls back to cbce_loss_frames)."""
-
-    def __init__(self, label: torch.Tensor):
-        _need(label, _F32, "CbceFramesStaged label")
-        if label.dim() < 2:
-            raise ValueError(f"CbceFramesStaged: label {tuple(label.shape)}")
-        self.n = label.shape[0]
-        self.per = label.numel() // self.n
-        if self.per % 4 or label.data_ptr() % 16:
-            raise ValueError("CbceFramesStaged: frames must be a multiple of 4 elements and 16-byte aligned")
-        L = lib()
-        self.label = label
-        # the stages share this workspace across the passes in between: its own tensor, not the ops' scratch
-        self.wsn = self.n * L.fosvos_cbce_workspace_bytes(self.per)
-        self.ws = torch.empty((self.wsn,), dtype=torch.uint8, device=label.device)
-        self.losses = None
-        self.size_average = None
-        dev, st = _ctx(label)
-        t0 = _pb()
-        check(L.fosvos_cbce_loss_frames_parts(None, label.data_ptr(), self.per, self.n, 0, 1.0, None, None, self.ws.data_ptr(),
-                                              self.wsn, CBCE_COUNT, dev, st), "cbce_loss_frames_parts(count)")
-        _pe(t0, "cbce_loss", 0.0, label.numel() * 4)
-
-    def loss(self, logits: torch.Tensor, size_average: bool = True, want_grad: bool = True, grad_scale: float = 1.0):
-        _need(logits, _F32, "CbceFramesStaged logits")
-        if logits.shape != self.label.shape or logits.data_ptr() % 16:
-            raise ValueError(f"CbceFramesStaged: logits {tuple(logits.shape)} vs label {tuple(self.label.shape)}")
-        self.losses = torch.empty((self.n,), dtype=_F32, device=logits.device)
-        self.size_average = bool(size_average)
-        grad = torch.empty_like(logits) if want_grad else None
-        dev, st = _ctx(logits)
-        t0 = _pb()
-        check(lib().fosvos_cbce_loss_frames_parts(logits.data_ptr(), self.label.data_ptr(), self.per, self.n,
-                                                  1 if size_average else 0, float(grad_scale), None, _p(grad),
-                                                  self.ws.data_ptr(), self.wsn, CBCE_LOSS, dev, st),
-              "cbce_loss_frames_parts(loss)")
-        _pe(t0, "cbce_loss", 0.0, logits.numel() * (12 if want_grad else 8))
-        return self.losses, grad
-
-    def finish(self) -> torch.Tensor:
-        if self.losses is None:
-            raise RuntimeError("CbceFramesStaged.finish before loss")
-        dev, st = _ctx(self.losses)
-        check(lib().fosvos_cbce_loss_frames_parts(None, None, self.per, self.n, 1 if self.size_average else 0, 1.0,
-                                                  self.losses.data_ptr(), None, self.ws.data_ptr(), self.wsn, CBCE_FINISH,
-                                                  dev, st), "cbce_loss_frames_parts(finish)")
-        return self.losses
-
-
 CBCE_MAX_MAPS = 8
 
 
@@ -726,58 +663,96 @@ def cbce_loss_frames_multi(logits: Sequence[torch.Tensor], label: torch.Tensor, 
 
 
 class CbceFramesMultiStaged(object):
-    """``cbce_loss_frames_multi`` in its three launches, like CbceFramesStaged: the class counts of ``label`` are taken at
-    construction (in front of the forward pass), ``loss`` writes the gradients of all maps in one launch, ``finish`` - behind
-    the backward pass - the [N,M] loss values.  Same stream for all three calls."""
+    """``cbce_loss_frames_multi`` in its three launches, for a loop that has a forward pass to put behind the first and a
+    backward pass behind the second: the class counts need only the labels, the backward pass only the gradients - counting
+    beside the forward pass and writing the loss VALUES behind the backward pass takes two small dependent launches (and the
+    copy of the values to the host) off the path between the two passes.
+
+        staged = CbceFramesMultiStaged(label, n_maps)        # counts; before the forward pass
+        losses, grads = staged.loss(logits, map_scale, ...)  # `losses` [N,M] is allocated, NOT yet written
+        ...backward pass...
+        staged.finish()                                      # now `losses` holds the values (stream order)
+
+    Same stream for all three calls."""
 
     def __init__(self, label: torch.Tensor, n_maps: int):
-        _need(label, _F32, "CbceFramesMultiStaged label")
+        self.who = type(self).__name__
+        _need(label, _F32, f"{self.who} label")
         if label.dim() < 2:
-            raise ValueError(f"CbceFramesMultiStaged: label {tuple(label.shape)}")
+            raise ValueError(f"{self.who}: label {tuple(label.shape)}")
         self.n, self.m = label.shape[0], int(n_maps)
         self.per = label.numel() // self.n
-        L = lib()
         self.label = label
         # the stages share this workspace across the passes in between: its own tensor, not the ops' scratch
-        self.wsn = L.fosvos_cbce_multi_workspace_bytes(self.per, self.n, self.m)
+        self.wsn = lib().fosvos_cbce_multi_workspace_bytes(self.per, self.n, self.m)
         self.ws = torch.empty((max(self.wsn, 8),), dtype=torch.uint8, device=label.device)
         self.losses = None
         self.size_average = None
-        dev, st = _ctx(label)
         t0 = _pb()
-        check(L.fosvos_cbce_loss_frames_multi(None, label.data_ptr(), self.per, self.n, self.m, 0, None, None, None,
-                                              self.ws.data_ptr(), self.wsn, CBCE_COUNT, dev, st),
-              "cbce_loss_frames_multi(count)")
+        self._launch(CBCE_COUNT, "count")
         _pe(t0, "cbce_loss", 0.0, label.numel() * 4)
+
+    def _launch(self, parts: int, stage: str, logits=None, map_scale=None, grads=None):
+        """One call of the C entry point for the stages ``parts``; the maps' arguments only with the loss stage."""
+        import ctypes
+        dev, st = _ctx(self.label)
+        check(lib().fosvos_cbce_loss_frames_multi(None if logits is None else _map_tables(logits), self.label.data_ptr(),
+                                                  self.per, self.n, self.m, 1 if self.size_average else 0,
+                                                  None if map_scale is None else (ctypes.c_float * self.m)(*map_scale),
+                                                  _p(self.losses), None if grads is None else _map_tables(grads),
+                                                  self.ws.data_ptr(), self.wsn, parts, dev, st),
+              f"cbce_loss_frames_multi({stage})")
 
     def loss(self, logits: Sequence[torch.Tensor], map_scale: Sequence[float], size_average: bool = True,
              want_grad: bool = True):
-        import ctypes
         logits = list(logits)
-        _multi_args(logits, self.label, map_scale, "CbceFramesMultiStaged")
+        _multi_args(logits, self.label, map_scale, self.who)
         if len(logits) != self.m:
-            raise ValueError(f"CbceFramesMultiStaged: staged for {self.m} maps, got {len(logits)}")
+            raise ValueError(f"{self.who}: staged for {self.m} maps, got {len(logits)}")
         self.losses = torch.empty((self.n, self.m), dtype=_F32, device=self.label.device)
         self.size_average = bool(size_average)
         grads = [torch.empty_like(t) for t in logits] if want_grad else None
-        dev, st = _ctx(self.label)
         t0 = _pb()
-        check(lib().fosvos_cbce_loss_frames_multi(_map_tables(logits), self.label.data_ptr(), self.per, self.n, self.m,
-                                                  1 if size_average else 0,
-                                                  (ctypes.c_float * self.m)(*[float(v) for v in map_scale]), None,
-                                                  _map_tables(grads) if want_grad else None, self.ws.data_ptr(), self.wsn,
-                                                  CBCE_LOSS, dev, st), "cbce_loss_frames_multi(loss)")
+        self._launch(CBCE_LOSS, "loss", logits, [float(v) for v in map_scale], grads)
         _pe(t0, "cbce_loss", 0.0, self.label.numel() * (4 + self.m * (8 if want_grad else 4)))
         return self.losses, grads
 
     def finish(self) -> torch.Tensor:
         if self.losses is None:
-            raise RuntimeError("CbceFramesMultiStaged.finish before loss")
-        dev, st = _ctx(self.losses)
-        check(lib().fosvos_cbce_loss_frames_multi(None, None, self.per, self.n, self.m, 1 if self.size_average else 0, None,
-                                                  self.losses.data_ptr(), None, self.ws.data_ptr(), self.wsn, CBCE_FINISH,
-                                                  dev, st), "cbce_loss_frames_multi(finish)")
+            raise RuntimeError(f"{self.who}.finish before loss")
+        self._launch(CBCE_FINISH, "finish")
         return self.losses
+
+
+class CbceFramesStaged(CbceFramesMultiStaged):
+    """``cbce_loss_frames`` in its three launches (fosvos_cbce_loss_frames_parts): CbceFramesMultiStaged for one logit
+    tensor, with the arguments and results of cbce_loss_frames ([N] losses, one gradient tensor).
+
+        staged = CbceFramesStaged(label)              # counts; before the forward pass
+        losses, grad = staged.loss(logits, ...)       # `losses` is allocated, NOT yet written
+        ...backward pass...
+        staged.finish()                               # now `losses` holds the values (stream order)
+
+    Frames whose element count is not a multiple of 4 are not supported here (the caller falls back to cbce_loss_frames)."""
+
+    def __init__(self, label: torch.Tensor):
+        if label.dim() >= 2 and ((label.numel() // label.shape[0]) % 4 or label.data_ptr() % 16):
+            raise ValueError("CbceFramesStaged: frames must be a multiple of 4 elements and 16-byte aligned")
+        super().__init__(label, 1)
+
+    def _launch(self, parts: int, stage: str, logits=(None,), map_scale=(1.0,), grads=None):
+        dev, st = _ctx(self.label)
+        check(lib().fosvos_cbce_loss_frames_parts(_p(logits[0]), self.label.data_ptr(), self.per, self.n,
+                                                  1 if self.size_average else 0, map_scale[0], _p(self.losses),
+                                                  None if grads is None else grads[0].data_ptr(), self.ws.data_ptr(),
+                                                  self.wsn, parts, dev, st), f"cbce_loss_frames_parts({stage})")
+
+    def loss(self, logits: torch.Tensor, size_average: bool = True, want_grad: bool = True, grad_scale: float = 1.0):
+        if logits.data_ptr() % 16:
+            raise ValueError("CbceFramesStaged: logits must be 16-byte aligned")
+        _, grads = super().loss([logits], [grad_scale], size_average=size_average, want_grad=want_grad)
+        self.losses = self.losses.view(self.n)  # (the same memory: finish() writes it)
+        return self.losses, grads[0] if want_grad else None
 
 
 # ------------------------------------------------------------------------------------------ thin-channel ResNet path

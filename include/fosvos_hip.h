@@ -302,6 +302,11 @@ size_t fosvos_head_bwd_workspace_bytes(int N, int H, int W);
  * weights (and the 1/numel factor when size_average).  Reductions run over the whole batch tensor
  * and are deterministic (fixed-order fp64 partials).  loss_out: one fp32 on the device.
  * grad may be NULL.  workspace: fosvos_cbce_workspace_bytes.
+ * Every entry point of this block runs the same three kernels (count, loss, finish) through one host path, which makes all
+ * its argument checks before the first launch: logits, label and grad 16-byte aligned, the workspace 8-byte aligned (device
+ * allocations are; a single-map call with a workspace off an 8-byte boundary was never valid and is now refused) and large
+ * enough.  The loss kernel is one template over the number of logit maps that share a label batch, so the forms below agree
+ * bit for bit by construction.
  * replaces: class_balanced_cross_entropy_loss + its autograd (src/layers/osvos_layers.py:17-44). */
 int fosvos_cbce_loss(const float *logits, const float *label, int64_t numel, int size_average, float grad_scale,
                      float *loss_out, float *grad, void *workspace, size_t workspace_bytes, int device,
@@ -333,7 +338,7 @@ int fosvos_cbce_loss_frames_parts(const float *logits, const float *label, int64
  * HOST floats, map m's gradient is multiplied by map_scale[m]; loss_out: [n_frames][n_maps] UNWEIGHTED loss values.  One
  * count per frame serves all maps and one launch writes every gradient: a thread reads its labels once and walks the maps
  * (4 + n_maps x 8 bytes per pixel against n_maps x 16).  For every frame and map the result equals fosvos_cbce_loss_frames
- * on that map with grad_scale = map_scale[m], bit for bit.  1 <= n_maps <= FOSVOS_CBCE_MAX_MAPS; frame_numel a multiple of 4
+ * on that map with grad_scale = map_scale[m], bit for bit (that call is this one with n_maps = 1).  1 <= n_maps <= FOSVOS_CBCE_MAX_MAPS; frame_numel a multiple of 4
  * when n_frames > 1; workspace: fosvos_cbce_multi_workspace_bytes, shared by the stages of one loss.  Arguments a stage does
  * not read may be NULL (COUNT: logits, map_scale, loss_out, grad; FINISH: logits, label, map_scale, grad). */
 #define FOSVOS_CBCE_MAX_MAPS 8

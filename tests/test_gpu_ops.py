@@ -853,6 +853,65 @@ def test_cbce_frames_staged_equals_one_call(ops):
     assert L.stage_frames_loss(y[:, :, :3, :5].contiguous()) is None  # 15 elements per frame: the one-call path
 
 
+@pytest.mark.parametrize("size_average", [False, True])
+@pytest.mark.parametrize("shape", [(1, 1, 3, 5),         # a ragged tail, less than one vector
+                                   (1, 1, 40, 52),       # three blocks, ragged last block
+                                   (2, 1, 40, 52),       # one loss over a two-frame tensor
+                                   (1, 1, 1028, 1024)])  # more than kMaxBlocks * 1024 pixels: the stride loop runs
+def test_cbce_batch_counts_of_the_tensor_itself_give_the_plain_bits(ops, shape, size_average):
+    """A shard that is the whole batch: handing the loss the tensor's own {positives, pixels} gives the bits of the call
+    that counts them itself - loss and gradient, and the loss without a gradient."""
+    x = gen(*shape, seed=78, scale=4.0).to(DEV)
+    y = (gen(*shape, seed=79) > 0.3).float().to(DEV)
+    positives = int((y >= 0.5).sum().item())
+    assert 0 < positives < y.numel()
+    counts = torch.tensor([positives, y.numel()], dtype=torch.float64, device=DEV)
+    want_l, want_g = ops.cbce_loss(x, y, size_average=size_average, grad_scale=0.2)
+    got_l, got_g = ops.cbce_loss(x, y, size_average=size_average, grad_scale=0.2, batch_counts=counts)
+    assert torch.equal(got_l, want_l) and torch.equal(got_g, want_g)
+    got_l, none = ops.cbce_loss(x, y, size_average=size_average, grad_scale=0.2, want_grad=False, batch_counts=counts)
+    assert none is None and torch.equal(got_l, want_l)
+
+
+def test_cbce_single_map_entries_reject_bad_arguments_before_any_launch(ops):
+    """The C entry points of the one-map loss, called directly: each bad argument is refused with its message and without
+    a single launch; the same call with the workspace the library asks for gives cbce_loss_frames' values."""
+    import fosvos_hip
+    L = fosvos_hip.lib()
+    x = gen(2, 1, 40, 52, seed=78, scale=4.0).to(DEV)
+    y = (gen(2, 1, 40, 52, seed=79) > 0.3).float().to(DEV)
+    per = 40 * 52
+    need = 2 * L.fosvos_cbce_workspace_bytes(per)
+    ws = torch.empty((need,), dtype=torch.uint8, device=DEV)
+    losses = torch.empty((2,), device=DEV)
+    grad = torch.empty_like(x)
+    off = torch.empty((per + 4,), device=DEV)[1:1 + per]  # starts one float past a 16-byte boundary
+    assert x.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 4
+    X, Y, LO, G, W = x.data_ptr(), y.data_ptr(), losses.data_ptr(), grad.data_ptr(), ws.data_ptr()
+    dev, st = 0, torch.cuda.current_stream(0).cuda_stream
+    cases = [
+        ("16-byte boundary", "cbce_loss_frames", lambda: L.fosvos_cbce_loss_frames(X, Y, 15, 2, 0, 1.0, LO, G, W, need, dev, st)),
+        ("workspace", "cbce_loss_frames", lambda: L.fosvos_cbce_loss_frames(X, Y, per, 2, 0, 1.0, LO, G, W, need - 8, dev, st)),
+        ("aligned", "cbce_loss", lambda: L.fosvos_cbce_loss(off.data_ptr(), Y, per, 0, 1.0, LO, G, W, need, dev, st)),
+        ("parts=0", "cbce_loss_frames_parts",
+         lambda: L.fosvos_cbce_loss_frames_parts(X, Y, per, 2, 0, 1.0, LO, G, W, need, 0, dev, st)),
+        ("parts=8", "cbce_loss_frames_parts",
+         lambda: L.fosvos_cbce_loss_frames_parts(X, Y, per, 2, 0, 1.0, LO, G, W, need, 8, dev, st)),
+        ("null", "cbce_loss_batch_counts",
+         lambda: L.fosvos_cbce_loss_batch_counts(X, Y, per, 0, 1.0, None, LO, G, W, need, dev, st)),
+    ]
+    torch.cuda.synchronize()
+    with fosvos_hip.LaunchProfile(0, max_launches=16) as prof:
+        for fragment, what, call in cases:
+            with pytest.raises(fosvos_hip.FosvosHipError, match=fragment):
+                fosvos_hip.check(call(), what)
+    assert prof.records == {}, prof.records
+    # the same arguments with the workspace the library asks for are accepted
+    fosvos_hip.check(L.fosvos_cbce_loss_frames(X, Y, per, 2, 0, 0.2, LO, G, W, need, dev, st), "cbce_loss_frames")
+    want_l, want_g = ops.cbce_loss_frames(x, y, size_average=False, grad_scale=0.2)
+    assert torch.equal(losses, want_l) and torch.equal(grad, want_g)
+
+
 # ------------------------------------------------------------------------------------------ SGD
 def test_fused_sgd_zero_grad_flag():
     """step(zero_grad=True) = step() then zero_grad(set_to_none=False), in one pass over the gradients - also for a subset."""
