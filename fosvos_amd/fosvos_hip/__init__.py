@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -229,6 +229,9 @@ SIGNATURES = {
     "fosvos_jpeg_workspace_bytes_sampled": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "fosvos_jpeg_encode_sampled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                            c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_jpeg_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fosvos_jpeg_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_png_workspace_bytes_mode": (c_size_t, [c_int, c_int, c_int, c_int]),
     "fosvos_png_encode_mode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
                                        c_int, c_void_p]),

@@ -1280,6 +1280,118 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     return out, lengths
 
 
+# ------------------------------------------------------------------------------------------ JPEG files in (jpeg_decode.hip)
+def _jpeg_decode_plans(files, plans):
+    from util import jpeg_read
+    if len(files) == 0:
+        raise ValueError("jpeg_decode: no files")
+    if plans is None:
+        plans = [jpeg_read.probe(f) for f in files]
+    if len(plans) != len(files):
+        raise ValueError(f"jpeg_decode: {len(files)} files but {len(plans)} plans")
+    for i, p in enumerate(plans):
+        if p is None:
+            raise ValueError(f"jpeg_decode: file {i} is not one the device decoder takes (util/jpeg_read.probe is None): "
+                             f"decode it on the host")
+    key = lambda p: (p.height, p.width, p.components, p.subsampling)  # noqa: E731
+    for i, p in enumerate(plans):
+        if key(p) != key(plans[0]):
+            raise ValueError(f"jpeg_decode: the files of one call share shape, components and sampling; file 0 is "
+                             f"{key(plans[0])}, file {i} is {key(p)}")
+    return plans
+
+
+def jpeg_decode_workspace(n: int, h: int, w: int, components: int, subsampling: str = '4:4:4') -> int:
+    """Bytes of scratch ``jpeg_decode`` needs for ``n`` files of this shape (fosvos_jpeg_decode_workspace_bytes)."""
+    need = int(lib().fosvos_jpeg_decode_workspace_bytes(int(n), int(h), int(w), int(components),
+                                                        420 if _jpeg_subsampling(subsampling, "jpeg_decode_workspace") else 444))
+    if need == 0:
+        raise ValueError(f"jpeg_decode_workspace: n, h, w in 1..65535, components 1 or 3, 4:2:0 from w = 5, got {n}, {h}, {w}, "
+                         f"{components}, {subsampling}")
+    return need
+
+
+def jpeg_decode_pack(files: Sequence[bytes], plans):
+    """What one call sends, in ONE pinned uint8 buffer: the segment rows (int32 [n_segments][5]: file, byte offset, byte
+    length, first MCU, MCU count) | the per-file tables (util/jpeg_read.pack_tables) | the scans of all files.  Returns
+    (buffer, n_segments, offset of the tables, offset of the scans, bytes of scans)."""
+    import numpy as np
+    from util import jpeg_read
+    n = len(files)
+    n_seg = sum(len(p.segments) for p in plans)
+    off_tables = _ru(20 * n_seg, 8)
+    off_bytes = off_tables + jpeg_read.TABLES_BYTES * n
+    n_bytes = sum(p.scan[1] - p.scan[0] for p in plans)
+    if n_bytes <= 0 or n_bytes >= 1 << 31:
+        raise ValueError(f"jpeg_decode: {n_bytes} bytes of entropy-coded data in one call (1 .. 2^31 - 1)")
+    host = torch.empty(off_bytes + n_bytes, dtype=torch.uint8, pin_memory=True)
+    hv = host.numpy()
+    hv[20 * n_seg:off_tables] = 0
+    rows = hv[:20 * n_seg].view(np.int32).reshape(n_seg, 5)
+    seg_at, byte_at = 0, 0
+    for i, (f, p) in enumerate(zip(files, plans)):
+        k, (b0, b1) = len(p.segments), p.scan
+        rows[seg_at:seg_at + k, 0] = i
+        rows[seg_at:seg_at + k, 1:] = p.segments
+        rows[seg_at:seg_at + k, 1] += byte_at - b0
+        hv[off_tables + i * jpeg_read.TABLES_BYTES:off_tables + (i + 1) * jpeg_read.TABLES_BYTES] = np.frombuffer(
+            jpeg_read.pack_tables(p, seg_at, k), dtype=np.uint8)
+        hv[off_bytes + byte_at:off_bytes + byte_at + b1 - b0] = np.frombuffer(f, dtype=np.uint8, count=b1 - b0, offset=b0)
+        seg_at += k
+        byte_at += b1 - b0
+    return host, n_seg, off_tables, off_bytes, n_bytes
+
+
+def jpeg_decode(files: Sequence[bytes], out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                device=None, plans=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fosvos_jpeg_decode: baseline JPEG files of one shape -> (frames uint8 [N,H,W,3] BGR or [N,H,W] grey, status int32 [N]),
+    byte for byte util/jpeg_read.decode.  Every file is probed (``plans``: the probes, where the caller has them already);
+    ValueError where a probe is None or the files disagree in shape, components or sampling - a caller that wants the host
+    fallback probes first.  The scans, the segment table and the per-file tables travel in ONE pinned buffer and one upload.
+    ``out`` and ``status`` may be views of a caller's buffers.  A frame whose status is not 0 is not meaningful (the codes:
+    util/jpeg_read.py); the status is the caller's to read.  Three launches on the current stream, no synchronisation."""
+    from util import jpeg_read
+    plans = _jpeg_decode_plans(files, plans)
+    p0 = plans[0]
+    n, h, w, comps = len(files), p0.height, p0.width, p0.components
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"jpeg_decode: the device must be a GPU (the HIP path has no CPU fallback), got {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    shape = (n, h, w, 3) if comps == 3 else (n, h, w)
+    for t, dtype, want, what in ((out, torch.uint8, shape, "out"), (status, torch.int32, (n,), "status")):
+        if t is None:
+            continue
+        _need_eval(t, dtype, f"jpeg_decode {what}")
+        if tuple(t.shape) != tuple(want):
+            raise ValueError(f"jpeg_decode: {what} must be {tuple(want)}, got {tuple(t.shape)}")
+        if t.device != device:
+            raise RuntimeError(f"jpeg_decode: every tensor must be on {device}, got {what} on {t.device}")
+    L = lib()
+    sampling = jpeg_read.SAMPLING_CODE[p0.subsampling]
+    need = int(L.fosvos_jpeg_decode_workspace_bytes(n, h, w, comps, sampling))
+    if need == 0:
+        raise ValueError(f"jpeg_decode: at most 65535 files, got {n}")
+    host, n_seg, off_tables, off_bytes, n_bytes = jpeg_decode_pack(files, plans)
+    with torch.cuda.device(device):
+        dev_buf = host.to(device, non_blocking=True)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=device)
+        if status is None:
+            status = torch.empty((n,), dtype=torch.int32, device=device)
+        ws, wsn = _WS.get(need, device)
+        dev, st = _ctx(out)
+        e0 = _pb()
+        base = dev_buf.data_ptr()
+        check(L.fosvos_jpeg_decode(base + off_bytes, n_bytes, base, n_seg, base + off_tables, n, h, w, comps, sampling,
+                                   out.data_ptr(), status.data_ptr(), ws, wsn, dev, st), "jpeg_decode")
+        _pe(e0, "jpeg_decode", 0.0, float(n_bytes) + float(out.numel()))
+    return out, status
+
+
 # ------------------------------------------------------------------------------------------ streaming inference (stream.hip)
 OVERLAY_CHANNEL = {'b': 0, 'g': 1, 'r': 2}
 _MEAN_BGR = None

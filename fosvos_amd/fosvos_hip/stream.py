@@ -70,7 +70,8 @@ class FrameSegmenter:
     whole-module pickle) on a GPU; the segmenter calls ``net.forward(x)[-1]`` under ``no_grad`` with
     ``net.compute_side_outputs = False`` for the call.
 
-    submit(frame)    queue one uint8 [H,W,3] BGR frame; blocks only when all ``depth`` slots are in flight (it then retires
+    submit(frame)    queue one uint8 [H,W,3] BGR frame - a numpy array, or a tensor already on the net's device, made on the
+                     current stream (``ops.jpeg_decode``'s output: no upload); blocks only when all ``depth`` slots are in flight (it then retires
                      the oldest and keeps its output for ``result``)
     result()         the oldest frame's output as an array of its own: uint8 [H,W,3], or [H,W] with ``overlay=False``;
                      with ``encode='jpeg'`` the same picture as ``bytes``, a complete .jpg file of quality ``quality``
@@ -134,7 +135,14 @@ class FrameSegmenter:
         if self._closed:
             raise RuntimeError("FrameSegmenter: closed")
 
-    def _check_frame(self, frame) -> np.ndarray:
+    def _check_frame(self, frame):
+        if isinstance(frame, torch.Tensor):  # a frame that is on the device already (ops.jpeg_decode made it)
+            if frame.dtype != torch.uint8 or frame.device != self.device or not frame.is_contiguous():
+                raise ValueError(f"FrameSegmenter: a device frame must be a contiguous uint8 tensor on {self.device}, got "
+                                 f"{frame.dtype} on {frame.device}")
+            if tuple(frame.shape) != (self.height, self.width, 3):
+                raise ValueError(f"FrameSegmenter: a frame must be {(self.height, self.width, 3)}, got {tuple(frame.shape)}")
+            return frame
         if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8:
             raise ValueError(f"FrameSegmenter: a frame must be a uint8 numpy array, got {getattr(frame, 'dtype', type(frame))}")
         if frame.shape != (self.height, self.width, 3):
@@ -167,11 +175,14 @@ class FrameSegmenter:
         self._free.append(slot)
         return out
 
-    def _enqueue(self, slot: _Slot, main: torch.cuda.Stream) -> None:
-        with torch.cuda.stream(self._up):
-            slot.frame.copy_(slot.host_in, non_blocking=True)
-            slot.moved.record(self._up)
-        main.wait_event(slot.moved)
+    def _enqueue(self, slot: _Slot, main: torch.cuda.Stream, device_frame: Optional[torch.Tensor] = None) -> None:
+        if device_frame is not None:  # made on the caller's stream, which is `main`: a copy in stream order, no upload
+            slot.frame[0].copy_(device_frame, non_blocking=True)
+        else:
+            with torch.cuda.stream(self._up):
+                slot.frame.copy_(slot.host_in, non_blocking=True)
+                slot.moved.record(self._up)
+            main.wait_event(slot.moved)
         net = self.net
         had, old = hasattr(net, 'compute_side_outputs'), getattr(net, 'compute_side_outputs', None)
         net.compute_side_outputs = False
@@ -206,8 +217,11 @@ class FrameSegmenter:
         with torch.cuda.device(self.device):
             main = torch.cuda.current_stream(self.device)
             try:
-                np.copyto(slot.host_in_np[0], frame)
-                self._enqueue(slot, main)
+                if isinstance(frame, torch.Tensor):
+                    self._enqueue(slot, main, device_frame=frame)
+                else:
+                    np.copyto(slot.host_in_np[0], frame)
+                    self._enqueue(slot, main)
             except BaseException:
                 # never half-queued: whatever part of the frame was queued runs out, then the slot is free again
                 try:

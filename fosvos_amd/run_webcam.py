@@ -7,7 +7,10 @@ The options carry the reference's names and defaults.  Additions: ``--model`` (a
 ``--depth``, and ``--output-format jpeg`` with ``--jpeg-quality``: the device encodes each result as a JPEG file
 (``FrameSegmenter(encode='jpeg')``) and the loop only writes ``%05d.jpg``; ``--jpeg-subsampling 420`` chooses the encoder's
 4:2:0 form, and ``--output NAME.avi`` (with ``--fps``) puts the same files into one Motion-JPEG AVI (util/mjpeg_avi.py)
-instead of a directory.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+instead of a directory.  ``--source NAME.avi`` reads such a file back (util/mjpeg_avi.AviReader), and ``--device-decode``
+decodes the JPEG frames of either source on the device (``ops.jpeg_decode``, in groups of ``DECODE_GROUP``): the frames reach
+the segmenter without ever being pixels on the host; other file types and files the device decoder does not take
+(util/jpeg_read.probe is None, grey files, a non-zero status) go through PIL as before.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -66,6 +69,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--jpeg-quality', type=int, default=90, help='1..100, with --output-format jpeg')
     p.add_argument('--jpeg-subsampling', choices=['444', '420'], default='444', help='chroma sampling, with --output-format jpeg')
     p.add_argument('--fps', type=float, default=25, help='frame rate written into --output NAME.avi')
+    p.add_argument('--device-decode', action='store_true',
+                   help='decode the JPEG frames of --source (a directory or NAME.avi) on the device')
     return p
 
 
@@ -121,6 +126,70 @@ def source_files(directory: str) -> List[str]:
     if not names:
         raise FileNotFoundError('--source {}: no image files'.format(directory))
     return [os.path.join(directory, f) for f in names]
+
+
+DECODE_GROUP = 8   # files a launch of --device-decode
+
+
+def bgr_of_bytes(data: bytes) -> np.ndarray:
+    """``read_bgr`` of a file that is in memory."""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        rgb = np.asarray(im.convert('RGB'))
+    return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+def avi_frames(path: str) -> Iterator[np.ndarray]:
+    from util.mjpeg_avi import AviReader
+    for payload in AviReader(path):
+        yield bgr_of_bytes(payload)
+
+
+def device_decoded_frames(items, group: int = DECODE_GROUP) -> Iterator:
+    """``items``: (name, bytes or None, host decode) per frame, in order.  Consecutive JPEG files the device decoder takes,
+    of one shape and sampling, are decoded ``group`` a launch on the current stream and yielded as uint8 [H,W,3] device
+    tensors; everything else, and a file whose status comes back non-zero, as the host decode's array."""
+    from fosvos_hip import ops
+    from util import jpeg_read
+    held = []
+
+    def flush():
+        if not held:
+            return
+        frames, status = ops.jpeg_decode([b for b, _, _ in held], plans=[p for _, p, _ in held])
+        codes = status.tolist()
+        for k, (_, _, host) in enumerate(held):
+            yield frames[k] if codes[k] == 0 else host()
+        del held[:]
+
+    for name, blob, host in items:
+        plan = jpeg_read.probe(blob) if blob is not None and name.lower().endswith(('.jpg', '.jpeg')) else None
+        if plan is not None and plan.components != 3:
+            plan = None
+        if plan is None or len(held) == group or (held and (held[0][1].height, held[0][1].width, held[0][1].subsampling)
+                                                  != (plan.height, plan.width, plan.subsampling)):
+            yield from flush()
+        if plan is None:
+            yield host()
+        else:
+            held.append((blob, plan, host))
+    yield from flush()
+
+
+def source_items(source: str):
+    """The (name, bytes, host decode) items of --source DIR or NAME.avi for ``device_decoded_frames``."""
+    if source.lower().endswith('.avi'):
+        from util.mjpeg_avi import AviReader
+        for k, payload in enumerate(AviReader(source)):
+            yield '%05d.jpg' % k, payload, (lambda payload=payload: bgr_of_bytes(payload))
+        return
+    for path in source_files(source):
+        blob = None
+        if path.lower().endswith(('.jpg', '.jpeg')):
+            with open(path, 'rb') as f:
+                blob = f.read()
+        yield path, blob, (lambda path=path: read_bgr(path))
 
 
 def open_webcam(index: int):
@@ -229,9 +298,15 @@ def main(argv=None) -> List[float]:
         raise ValueError('--output NAME.avi is a Motion-JPEG file: give --output-format jpeg')
     if to_avi and not args.fps > 0:
         raise ValueError('--fps must be positive, got {}'.format(args.fps))
+    if args.device_decode and args.source is None:
+        raise ValueError('--device-decode decodes the JPEG files of --source: give --source DIR or NAME.avi')
     cam = None
     if args.synthetic is not None:
         frames = synthetic_frames(args.synthetic, args.height, args.width)
+    elif args.source is not None and args.device_decode:
+        frames = device_decoded_frames(source_items(args.source))
+    elif args.source is not None and args.source.lower().endswith('.avi'):
+        frames = avi_frames(args.source)
     elif args.source is not None:
         frames = (read_bgr(f) for f in source_files(args.source))
     else:
@@ -244,6 +319,7 @@ def main(argv=None) -> List[float]:
     avi = None
     try:
         if not args.use_network:
+            frames = (f.cpu().numpy() if isinstance(f, torch.Tensor) else f for f in frames)
             mirrored = (np.ascontiguousarray(f[:, ::-1]) if args.mirror else f for f in frames)
             if to_avi:
                 first = next(mirrored, None)

@@ -40,6 +40,7 @@ data_parallel = False
 score = False               # --score: the test pass computes J and F on the device (experiment_helper.test_scored)
 fast_test = False           # --fast-test: grouped forward passes, PNG files encoded on the device (experiment_helper.test_fast)
 png_fitted = False          # --png-fitted (with --fast-test): Huffman codes fitted to each segment of the PNG files
+device_decode = False       # --device-decode: the test pass's JPEG frames are decoded on the device (dataloaders/device_decode.py)
 scored_sequences = []       # the score of every sequence of this run, in order
 
 sequences_val = ['blackswan', 'bmx-trees', 'breakdance', 'camel', 'car-roundabout', 'car-shadow', 'cows',
@@ -64,7 +65,7 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
         if not settings.is_training:
             net_provider.load_network_test(sequence=seq_name)
         data_loader = io_helper.get_data_loader_test(db_root_dir, settings.batch_size_test, seq_name,
-                                                     synthetic=synthetic_size)
+                                                     synthetic=synthetic_size, device_decode=device_decode)
         if settings.variant_offline is None:
             save_dir = save_dir_results / net_provider.name / 'online'
         else:
@@ -472,7 +473,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 
 def main(argv=None):
-    global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted
+    global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -481,6 +482,7 @@ def main(argv=None):
     score = bool(args.score)
     fast_test = bool(args.fast_test)
     png_fitted = bool(args.png_fitted)
+    device_decode = bool(args.device_decode)
     del scored_sequences[:]
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')

@@ -3,7 +3,7 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test and --png-fitted (online only).
+--data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test, --png-fitted and --device-decode (online only).
 """
 import argparse
 from typing import List, Optional
@@ -48,6 +48,9 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--png-fitted', action='store_true',
                             help='with --fast-test: Huffman codes fitted to each segment of the PNG files (same pixels, '
                                  'smaller files)')
+        parser.add_argument('--device-decode', action='store_true',
+                            help='decode the test pass\'s JPEG frames on the device (same tensors; files the device decoder '
+                                 'does not take go through PIL as before)')
     if not is_online:
         parser.add_argument('--resident-train-set', action='store_true',
                             help='decode the training set once, keep it on the GPU and flip / rescale each draw there '
@@ -64,6 +67,8 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                      'class counts of the whole batch)')
     if is_online and args.png_fitted and not args.fast_test:
         parser.error('--png-fitted chooses the codes of the device PNG encoder: it needs --fast-test')
+    if is_online and args.device_decode and args.synthetic:
+        parser.error('--device-decode decodes JPEG files: the synthetic sequence has none')
     args.is_training = not args.no_training
     args.is_testing = not args.no_testing
     return args

@@ -81,7 +81,15 @@ def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] 
 
 
 def get_data_loader_test(db_root_dir, batch_size: int, seq_name: Optional[str] = None,
-                         synthetic: Optional[Tuple[int, int]] = None, n_frames: int = 4) -> DataLoader:
+                         synthetic: Optional[Tuple[int, int]] = None, n_frames: int = 4, device_decode: bool = False):
+    """``device_decode`` (opt-in): the frames' JPEG files are decoded on the device - a
+    dataloaders.device_decode.DeviceDecodeLoader, which yields the same minibatches with ``image`` on the GPU."""
+    if device_decode:
+        if synthetic is not None:
+            raise ValueError('get_data_loader_test: device_decode decodes JPEG files; the synthetic sequence has none')
+        from dataloaders.device_decode import DeviceDecodeLoader
+        return DeviceDecodeLoader(DAVIS2016(mode='test', db_root_dir=str(db_root_dir), transform=None, seq_name=seq_name),
+                                  batch_size=batch_size)
     if synthetic is not None:
         ds = SyntheticSequence(seq_name or 'synthetic', synthetic[0], synthetic[1], n_frames=n_frames)
         return DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=0)

@@ -13,7 +13,8 @@ header, one file a player opens.  Host only, standard library only.
 
 All integers little-endian.  A chunk's size field is the payload's length without the padding byte.  The header is written
 with zeros for what is only known at the end (sizes, frame count, the largest chunk); ``close`` writes the index and patches
-them.  AVI 1.0 sizes are 32 bits and players read them as signed: a write that would take the finished file past ``MAX_BYTES``
+them.  ``AviReader`` reads such a file back: the JPEG payloads of the 'movi' list in order (the restart intervals of the
+device encoder's files make them the decoder's multi-segment input).  AVI 1.0 sizes are 32 bits and players read them as signed: a write that would take the finished file past ``MAX_BYTES``
 = 2^31 - 1 raises ``AviSizeError`` and leaves the file as it was (there is no OpenDML extension here).  No audio.
 """
 import struct
@@ -104,3 +105,51 @@ class AviWriter:
     def __exit__(self, *exc) -> bool:
         self.close()
         return False
+
+
+class AviReader:
+    """``AviReader(path)``: iterates the JPEG payloads (``bytes``) of the 'movi' list of a file ``AviWriter`` wrote, in order;
+    ``width``, ``height``, ``fps`` and ``len()`` come from the header.  ValueError on anything else: another header layout,
+    another codec, a chunk that is not '00dc' or runs past the list, a frame count that disagrees with the header."""
+
+    def __init__(self, path) -> None:
+        with open(str(path), 'rb') as f:
+            data = f.read()
+        head = _MOVI_AT + 12
+        if len(data) < head or data[:4] != b'RIFF' or data[8:12] != b'AVI ' or data[12:16] != b'LIST' \
+                or data[20:28] != b'hdrlavih' or struct.unpack('<I', data[16:20])[0] != _HDRL_BYTES:
+            raise ValueError('AviReader: {} is not an AVI file of the layout AviWriter writes'.format(path))
+        avih = struct.unpack('<14I', data[32:88])
+        strh_at = 88 + 12 + 8
+        if data[88:92] != b'LIST' or data[96:104] != b'strlstrh' or data[strh_at:strh_at + 8] != b'vidsMJPG':
+            raise ValueError('AviReader: {}: the stream is not Motion-JPEG video'.format(path))
+        scale, rate = struct.unpack('<II', data[strh_at + 20:strh_at + 28])
+        if data[_MOVI_AT:_MOVI_AT + 4] != b'LIST' or data[_MOVI_AT + 8:head] != b'movi' or scale == 0 or rate == 0:
+            raise ValueError('AviReader: {}: no movi list where AviWriter puts it'.format(path))
+        movi_size = struct.unpack('<I', data[_MOVI_AT + 4:_MOVI_AT + 8])[0]
+        end = _MOVI_AT + 8 + movi_size
+        if movi_size < 4 or end > len(data):
+            raise ValueError('AviReader: {}: the movi list runs past the end of the file (not closed?)'.format(path))
+        self.width, self.height = int(avih[8]), int(avih[9])
+        self.fps = Fraction(rate, scale)
+        self._frames: List[bytes] = []
+        at = head
+        while at < end:
+            if at + 8 > end or data[at:at + 4] != b'00dc':
+                raise ValueError('AviReader: {}: a chunk at {} that is not a video frame'.format(path, at))
+            n = struct.unpack('<I', data[at + 4:at + 8])[0]
+            if at + 8 + n > end:
+                raise ValueError('AviReader: {}: the chunk at {} runs past the movi list'.format(path, at))
+            self._frames.append(data[at + 8:at + 8 + n])
+            at += 8 + n + (n & 1)
+        if len(self._frames) != avih[4]:
+            raise ValueError('AviReader: {}: {} frames in the movi list, {} in the header'.format(path, len(self._frames), avih[4]))
+
+    def __len__(self) -> int:
+        return len(self._frames)
+
+    def __iter__(self):
+        return iter(self._frames)
+
+    def __getitem__(self, k: int) -> bytes:
+        return self._frames[k]

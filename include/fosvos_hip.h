@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 27
+#define FOSVOS_ABI_VERSION 28
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -480,6 +480,32 @@ size_t fosvos_jpeg_workspace_bytes_sampled(int N, int H, int W, int components, 
 int fosvos_jpeg_encode_sampled(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality,
                                uint8_t *out, size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes,
                                int device, void *stream);
+
+/* ---- JPEG files in, frames out: the decoder of the test pass's and the stream's input frames (ABI 28) ------------------
+ * fosvos_jpeg_decode: N baseline JPEG files of ONE shape, component count and sampling -> frames uint8 [N,H,W,3] BGR
+ * (components = 3) or [N,H,W] (components = 1) and status int32 [N].  util/jpeg_read.py states which files are taken
+ * (probe), the bytes of the result and the status codes; the host parses the markers and sends
+ *   bytes       the entropy-coded data of all files, n_bytes of it (< 2^31); stuffing and restart markers as in the files
+ *   segments    int32 [n_segments][5]: file, byte offset into `bytes`, byte length, first MCU, MCU count - one row per
+ *               restart interval (one per file without DRI), the rows of a file contiguous.  Rows are checked on the
+ *               device: one that points outside `bytes` or the MCU grid decodes nothing and gives its file status 1
+ *   tables      per file 2384 bytes: quant uint8 [3][64] (per component, natural order), dc_slot [3], ac_slot [3] (the
+ *               slot, class * 4 + id, of each component's Huffman tables), 2 bytes unused, int32 first row and row count of
+ *               the file in `segments`, then 8 slots of 272 bytes: the DHT payload (16 counts + symbols) as it stands in
+ *               the file, zero-filled.  8-byte aligned
+ *   sampling    444, or 420 (colour only: 2x2,1x1,1x1, W >= 5); a grey file ignores it
+ *   status      per file 0, or the smallest non-zero status of its segments (1 bytes ran out, 2 no code matches, 3 a
+ *               coefficient index beyond 63), or 5 (some coefficient x quant outside +-32767); the frame of a non-zero
+ *               status is not meaningful
+ *   workspace   fosvos_jpeg_decode_workspace_bytes (coefficients 128 B a block, the padded component planes, 4 B an MCU
+ *               and 4 B per 32 blocks of status words), 16-byte aligned; 0 for a shape the decoder does not take
+ * Argument checks come before any launch.  Integer arithmetic only; three launches on `stream`; every store is inside the
+ * workspace, `frames` or `status`.
+ * replaces: the PIL decode of src/dataloaders/davis_2016.py (make_img_gt_pair) and cv2.imread of src/run_webcam.py. */
+size_t fosvos_jpeg_decode_workspace_bytes(int N, int H, int W, int components, int sampling);
+int fosvos_jpeg_decode(const uint8_t *bytes, size_t n_bytes, const int32_t *segments, int n_segments, const void *tables, int N,
+                       int H, int W, int components, int sampling, uint8_t *frames, int32_t *status, void *workspace,
+                       size_t workspace_bytes, int device, void *stream);
 
 /* ---- streaming inference: a raw camera frame in, the frame that is shown out -----------------------------------------
  * The per-frame arithmetic of src/run_webcam.py:81-133 (apply_network) on the device beside the nets; the definitions are
