@@ -223,6 +223,7 @@ __device__ __forceinline__ uint4 max_nonneg_bf16x8(const uint4 &a, const uint4 &
 
 // the probability of a logit as the host states it in fp64 (eval.hip: the PNG bytes; stream.hip: the soft overlay)
 __device__ __forceinline__ double sigmoid_f64(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
+__device__ __forceinline__ double sigmoid_f64(double x) { return 1.0 / (1.0 + exp(-x)); }
 
 // wave64 all-lanes sum
 __device__ __forceinline__ float wave_sum(float v) {

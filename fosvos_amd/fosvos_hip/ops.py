@@ -1425,11 +1425,48 @@ def _out_like(out: Optional[torch.Tensor], shape, dtype, like: torch.Tensor, wha
     return out
 
 
-def frame_prep(frames_u8: torch.Tensor, mirror: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+MAX_FRAME_SIDE = 8192  # of a scaled call (util/frame_resample.MAX_SIDE)
+
+
+def _net_size(net_size, h: int, w: int, what: str) -> Optional[Tuple[int, int]]:
+    """``net_size`` of the scaled ops: None where it is unset or the frames' own size (the callers then take the unscaled
+    launch), else (Hn, Wn) checked against the frames."""
+    if net_size is None:
+        return None
+    try:
+        hn, wn = net_size
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: net_size must be a pair (Hn, Wn), got {net_size!r}") from None
+    for v in (hn, wn):
+        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+            raise ValueError(f"{what}: net_size must be a pair of positive ints, got {net_size!r}")
+    if hn > h or wn > w:
+        raise ValueError(f"{what}: the net's size {(hn, wn)} exceeds the frames' {(h, w)}")
+    if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
+        raise ValueError(f"{what}: scaled frames may have sides of up to {MAX_FRAME_SIDE}, got {(h, w)}")
+    return None if (hn, wn) == (h, w) else (hn, wn)
+
+
+def frame_prep(frames_u8: torch.Tensor, mirror: bool = False, out: Optional[torch.Tensor] = None,
+               net_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """fosvos_frame_prep: raw frames uint8 [N,H,W,3] (BGR) -> the net's input fp32 [N,3,H,W]: ``float32(byte) - MEANVAL[c]``,
     flipped left to right with ``mirror`` (util/frame_overlay.prepare_frame, bit for bit).  One launch on the current
-    stream, no synchronisation."""
+    stream, no synchronisation.
+
+    ``net_size=(Hn, Wn)`` (no larger than the frames): fosvos_frame_prep_scaled, the output is [N,3,Hn,Wn], the exact area
+    average of the frame less the mean (util/frame_resample.prepare_frame_scaled, bit for bit).  The frames' own size is
+    the launch above."""
     n, h, w = _frame_shape(frames_u8, "frame_prep")
+    scaled = _net_size(net_size, h, w, "frame_prep")
+    if scaled is not None:
+        hn, wn = scaled
+        out = _out_like(out, (n, 3, hn, wn), _F32, frames_u8, "frame_prep")
+        dev, st = _ctx(frames_u8)
+        e0 = _pb()
+        check(lib().fosvos_frame_prep_scaled(frames_u8.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, _mean_bgr(),
+                                             out.data_ptr(), dev, st), "frame_prep_scaled")
+        _pe(e0, "frame_prep_scaled", 0.0, 3.0 * n * h * w + 12.0 * n * hn * wn)
+        return out
     out = _out_like(out, (n, 3, h, w), _F32, frames_u8, "frame_prep")
     dev, st = _ctx(frames_u8)
     e0 = _pb()
@@ -1440,16 +1477,23 @@ def frame_prep(frames_u8: torch.Tensor, mirror: bool = False, out: Optional[torc
 
 
 def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False, boolean_mask: bool = True, color: str = 'r',
-            alpha: float = 1.0, overlay: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+            alpha: float = 1.0, overlay: bool = True, out: Optional[torch.Tensor] = None,
+            net_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """fosvos_overlay: raw frames uint8 [N,H,W,3] and the logits fp32 [N,1,H,W] the net made of them (of the mirrored
     frames, with ``mirror``) -> uint8 [N,H,W,3], the (mirrored) frames with ``alpha * 255 * p`` added to the channel of
     ``color`` and clamped at 255; p is the mask ``logit >= 0`` (``boolean_mask``) or the fp64 sigmoid.  ``overlay=False``:
     uint8 [N,H,W], the mask as 0 / 255 or ``255 p`` rounded half up.  util/frame_overlay.py states the bytes.  One launch on
-    the current stream, no synchronisation."""
+    the current stream, no synchronisation.
+
+    ``net_size=(Hn, Wn)`` (no larger than the frames): fosvos_overlay_scaled, the logits are [N,1,Hn,Wn] and are interpolated
+    up to the frames' size inside the launch; the output keeps the frames' size in every mode
+    (util/frame_resample.py states the bytes).  Scaling is never inferred from the shapes."""
     n, h, w = _frame_shape(frames_u8, "overlay")
+    scaled = _net_size(net_size, h, w, "overlay")
+    hn, wn = scaled if scaled is not None else (h, w)
     _need_eval(logits, _F32, "overlay logits")
-    if tuple(logits.shape) != (n, 1, h, w):
-        raise ValueError(f"overlay: logits must be {(n, 1, h, w)}, got {tuple(logits.shape)}")
+    if tuple(logits.shape) != (n, 1, hn, wn):
+        raise ValueError(f"overlay: logits must be {(n, 1, hn, wn)}, got {tuple(logits.shape)}")
     if logits.device != frames_u8.device:
         raise RuntimeError(f"overlay: every tensor must be on {frames_u8.device}, got one on {logits.device}")
     if color not in OVERLAY_CHANNEL:
@@ -1461,6 +1505,11 @@ def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False,
     mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
     dev, st = _ctx(frames_u8)
     e0 = _pb()
+    if scaled is not None:
+        check(lib().fosvos_overlay_scaled(frames_u8.data_ptr(), logits.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, mode,
+                                          OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st), "overlay_scaled")
+        _pe(e0, "overlay_scaled", 0.0, (6.0 if overlay else 1.0) * n * h * w + 4.0 * n * hn * wn)
+        return out
     check(lib().fosvos_overlay(frames_u8.data_ptr(), logits.data_ptr(), n, h, w, 1 if mirror else 0, mode,
                                OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st), "overlay")
     _pe(e0, "overlay", 0.0, (10.0 if overlay else 5.0) * n * h * w)

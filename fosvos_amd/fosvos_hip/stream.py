@@ -30,12 +30,17 @@ a quarter of the raw output), so the host still waits on ``slot.moved`` alone; o
 rest with a second copy, on a stream of its own, when it is retired.  ``subsampling='4:2:0'`` chooses the encoder's 4:2:0
 form (smaller files; the default budget stays the quarter).  ``encode=None`` is the object described above.
 
+``net_size=(Hn, Wn)`` (opt-in, no larger than the frame) runs the net at a size of its own: the slot's image is [1,3,Hn,Wn],
+``ops.frame_prep`` area-averages the frame down to it inside its launch and ``ops.overlay`` interpolates the logits back up
+inside its own (csrc/stream.hip; util/frame_resample.py states both).  Everything else - the uploads, the output, the JPEG
+capacity and budget, the downloads - stays at the frame's size.  ``None`` or the frame's own size is the object described above.
+
 Not thread-safe: one host thread drives a segmenter.
 """
 from __future__ import annotations
 
 from collections import deque
-from typing import Deque, Iterable, Iterator, List, Optional, Union
+from typing import Deque, Iterable, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -47,11 +52,12 @@ _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that t
 
 
 class _Slot:
-    def __init__(self, h: int, w: int, out_shape, device: torch.device, capacity: int = 0, budget: int = 0) -> None:
+    def __init__(self, h: int, w: int, out_shape, device: torch.device, capacity: int = 0, budget: int = 0,
+                 net_size=None) -> None:
         self.host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
         self.host_in_np = self.host_in.numpy()
         self.frame = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
-        self.image = torch.empty((1, 3, h, w), dtype=torch.float32, device=device)
+        self.image = torch.empty((1, 3) + tuple(net_size or (h, w)), dtype=torch.float32, device=device)
         self.out = torch.empty(out_shape, dtype=torch.uint8, device=device)
         if capacity:
             self.store = torch.empty((_HEAD + capacity,), dtype=torch.uint8, device=device)
@@ -66,7 +72,7 @@ class _Slot:
 
 
 class FrameSegmenter:
-    """``FrameSegmenter(net, height, width)``: ``net`` is any module of this project (OSVOS_VGG, OSVOS_RESNET, a pruned
+    """``FrameSegmenter(net, height, width, net_size=None)``: ``net`` is any module of this project (OSVOS_VGG, OSVOS_RESNET, a pruned
     whole-module pickle) on a GPU; the segmenter calls ``net.forward(x)[-1]`` under ``no_grad`` with
     ``net.compute_side_outputs = False`` for the call.
 
@@ -82,11 +88,14 @@ class FrameSegmenter:
 
     def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
-                 quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None) -> None:
+                 quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None,
+                 net_size: Optional[Tuple[int, int]] = None) -> None:
         from util import frame_overlay
         self.height, self.width, self.depth = int(height), int(width), int(depth)
         if self.height <= 0 or self.width <= 0 or self.depth <= 0:
             raise ValueError(f"FrameSegmenter: height, width and depth must be positive, got {height}, {width}, {depth}")
+        # None where the net runs at the frame's size: the unscaled launches, exactly
+        self.net_size = ops._net_size(net_size, self.height, self.width, "FrameSegmenter")
         frame_overlay.check_color(color)
         self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
         self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
@@ -125,7 +134,7 @@ class FrameSegmenter:
             self._up = torch.cuda.Stream(device=self.device)
             self._down = torch.cuda.Stream(device=self.device)
             self._rest = torch.cuda.Stream(device=self.device) if encode else None  # second copies of long files
-            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget)
+            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget, self.net_size)
                                        for _ in range(self.depth)]
         self._flight: Deque[_Slot] = deque()     # submitted, oldest first
         self._ready: Deque[Union[np.ndarray, bytes]] = deque()  # retired by a submit that needed the slot, not yet asked for
@@ -188,10 +197,10 @@ class FrameSegmenter:
         net.compute_side_outputs = False
         try:
             with torch.no_grad():
-                ops.frame_prep(slot.frame, self.mirror, out=slot.image)
+                ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
                 logits = net.forward(slot.image)[-1]
                 ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
-                            out=slot.out)
+                            out=slot.out, net_size=self.net_size)
                 if self.encode:
                     ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length, subsampling=self.subsampling)
         finally:

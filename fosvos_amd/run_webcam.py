@@ -10,14 +10,17 @@ The options carry the reference's names and defaults.  Additions: ``--model`` (a
 instead of a directory.  ``--source NAME.avi`` reads such a file back (util/mjpeg_avi.AviReader), and ``--device-decode``
 decodes the JPEG frames of either source on the device (``ops.jpeg_decode``, in groups of ``DECODE_GROUP``): the frames reach
 the segmenter without ever being pixels on the host; other file types and files the device decoder does not take
-(util/jpeg_read.probe is None, grey files, a non-zero status) go through PIL as before.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+(util/jpeg_read.probe is None, grey files, a non-zero status) go through PIL as before.  ``--net-height N --net-width N``
+(both, no larger than the frames) run the net at that size: the device area-averages each frame down to it in front of the net
+and interpolates the logits back up behind it (``FrameSegmenter(net_size=)``; util/frame_resample.py), and every output
+keeps the frame's size.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
 import sys
 import time
 from pathlib import Path
-from typing import Iterator, List, Optional
+from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -71,7 +74,21 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--fps', type=float, default=25, help='frame rate written into --output NAME.avi')
     p.add_argument('--device-decode', action='store_true',
                    help='decode the JPEG frames of --source (a directory or NAME.avi) on the device')
+    p.add_argument('--net-height', type=int, default=None, metavar='N',
+                   help='run the net at N rows (with --net-width; no more than the frames have)')
+    p.add_argument('--net-width', type=int, default=None, metavar='N', help='run the net at N columns (with --net-height)')
     return p
+
+
+def net_size_of(parser: argparse.ArgumentParser, args) -> Optional[Tuple[int, int]]:
+    """(--net-height, --net-width), or None: both are needed together."""
+    if (args.net_height is None) != (args.net_width is None):
+        parser.error('--net-height and --net-width are the net\'s size: give both or neither')
+    if args.net_height is None:
+        return None
+    if args.net_height <= 0 or args.net_width <= 0:
+        parser.error('--net-height and --net-width must be positive')
+    return args.net_height, args.net_width
 
 
 def model_file_name(variant: str, version: Optional[int]) -> str:
@@ -278,7 +295,9 @@ def open_avi(path: str, first: np.ndarray, fps: float):
 
 
 def main(argv=None) -> List[float]:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    net_size = net_size_of(parser, args)
     if not args.use_cuda:
         raise RuntimeError('--no-cuda: the HIP path has no CPU fallback')
     if args.variant == 'mimic' and args.use_network:
@@ -319,6 +338,8 @@ def main(argv=None) -> List[float]:
     avi = None
     try:
         if not args.use_network:
+            if net_size is not None:
+                log.info('--net-height / --net-width ignored: --no-network runs no net')
             frames = (f.cpu().numpy() if isinstance(f, torch.Tensor) else f for f in frames)
             mirrored = (np.ascontiguousarray(f[:, ::-1]) if args.mirror else f for f in frames)
             if to_avi:
@@ -338,6 +359,8 @@ def main(argv=None) -> List[float]:
         encode = dict(encode='jpeg', quality=args.jpeg_quality) if jpeg else {}
         if jpeg and subsampling != '4:4:4':
             encode['subsampling'] = subsampling
+        if net_size is not None:
+            encode['net_size'] = net_size
         if to_avi:
             avi = open_avi(args.output, first, args.fps)
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 28
+#define FOSVOS_ABI_VERSION 29
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -531,6 +531,26 @@ int fosvos_frame_prep(const uint8_t *frames, int N, int H, int W, int mirror, co
                       void *stream);
 int fosvos_overlay(const uint8_t *frames, const float *logits, int N, int H, int W, int mirror, int mode, int channel,
                    double alpha, uint8_t *out, int device, void *stream);
+
+/* The same two with the net at a size of its own (opt-in): frames uint8 [N,Hf,Wf,3], the net's image and logits at [Hn,Wn],
+ * 1 <= Hn <= Hf <= 8192 and 1 <= Wn <= Wf <= 8192 (FOSVOS_E_SHAPE otherwise).  util/frame_resample.py states both in numpy.
+ *
+ * fosvos_frame_prep_scaled: image fp32 [N,3,Hn,Wn] = the exact area average of the (mirrored) frame less the mean:
+ *   S[i][j][c] = sum_y sum_x wy[i][y] wx[j][x] frames[n][y][x][c] in integers, w[j][s] = max(0, min((s+1) n_dst, (j+1) n_src)
+ *   - max(s n_dst, j n_src)) along an axis of n_src source and n_dst output samples;
+ *   image[n][c][i][j] = (float)((double)S / (double)(Hf Wf)) - mean[c].  Bit for bit the host's.
+ *
+ * fosvos_overlay_scaled: logits fp32 [N,1,Hn,Wn] -> out uint8 [N,Hf,Wf,3] (modes 0, 1) or [N,Hf,Wf] (modes 2, 3): fosvos_overlay
+ * with the logit of an output pixel interpolated from the net's map, bilinear at half-pixel centres, clamped at the borders.
+ *   Along an axis: num = (2x+1) n_src - n_dst, i0 = floor(num / (2 n_dst)), r = num mod (2 n_dst); num < 0: i0 = 0, r = 0;
+ *   i0 >= n_src - 1: i0 = n_src - 1, r = 0; i1 = min(i0 + 1, n_src - 1); w0 = 2 n_dst - r, w1 = r.
+ *   In fp64, in this order: top = a[y0][x0] wx0 + a[y0][x1] wx1, bot = a[y1][x0] wx0 + a[y1][x1] wx1, v = top wy0 + bot wy1.
+ *   The boolean modes test v >= 0; the soft modes take the sigmoid of v / (double)(4 Hf Wf).
+ * Alignment, alpha, channel, modes and error codes as above.  One launch each, no workspace, no library state. */
+int fosvos_frame_prep_scaled(const uint8_t *frames, int N, int Hf, int Wf, int Hn, int Wn, int mirror, const float mean[3],
+                             float *image, int device, void *stream);
+int fosvos_overlay_scaled(const uint8_t *frames, const float *logits, int N, int Hf, int Wf, int Hn, int Wn, int mirror,
+                          int mode, int channel, double alpha, uint8_t *out, int device, void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
