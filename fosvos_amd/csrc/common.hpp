@@ -237,4 +237,54 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// ---- reductions over a workgroup of 256 threads (png.hip, jpeg.hip); wave: four words of LDS
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return wave[0] + wave[1] + wave[2] + wave[3];
+}
+__device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t *wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v ^= __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return wave[0] ^ wave[1] ^ wave[2] ^ wave[3];
+}
+// inclusive scans over the 256 threads (max of ints; sum of uints); afterwards wave[0..3] are the four waves' totals
+__device__ __forceinline__ int block_scan_max(int v, uint32_t *wave) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(v, o, 64);
+        if (lane >= o) v = max(v, u);
+    }
+    __syncthreads();
+    if (lane == 63) wave[wv] = (uint32_t)v;
+    __syncthreads();
+    for (int i = 0; i < wv; ++i) v = max(v, (int)wave[i]);
+    return v;
+}
+// kFresh (the fitted PNG kernels' late scans): the lane number passes through an empty asm, so the six `lane >= o` masks are
+// taken anew where they are used; shared with the first scan of the kernel they stay alive, in twelve SGPRs, all the way.
+template <bool kFresh = false>
+__device__ __forceinline__ uint32_t block_scan_sum(uint32_t v, uint32_t *wave) {
+    int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    if constexpr (kFresh) asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    __syncthreads();
+    if (lane == 63) wave[wv] = v;
+    __syncthreads();
+    for (int i = 0; i < wv; ++i) v += wave[i];
+    return v;
+}
+
 }  // namespace fosvos

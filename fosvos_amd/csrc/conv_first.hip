@@ -205,13 +205,8 @@ extern "C" int fosvos_conv3x3_first_plan(int N, int H, int W, int *tiles, int *w
     return FOSVOS_OK;
 }
 
-extern "C" int fosvos_conv3x3_first_fwd(const float *frame, const float *w, const float *bias, uint16_t *y, int N,
-                                        int H, int W, int Co, int device, void *stream) {
-    return fosvos_conv3x3_first_fwd_bits(frame, w, bias, y, nullptr, N, H, W, Co, device, stream);
-}
-
-extern "C" int fosvos_conv3x3_first_fwd_bits(const float *frame, const float *w, const float *bias, uint16_t *y,
-                                             uint8_t *relu_bits, int N, int H, int W, int Co, int device, void *stream) {
+extern "C" int fosvos_conv3x3_first_fwd(const float *frame, const float *w, const float *bias, uint16_t *y, uint8_t *relu_bits,
+                                        int N, int H, int W, int Co, int device, void *stream) {
     FOSVOS_REQUIRE(frame && w && bias && y, FOSVOS_E_ARG, "conv3x3_first_fwd: null pointer");
     FOSVOS_REQUIRE(Co == CO, FOSVOS_E_SHAPE, "conv3x3_first_fwd: Co=%d, only %d is built", Co, CO);
     FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && N <= 65535, FOSVOS_E_SHAPE, "conv3x3_first_fwd: bad shape N=%d H=%d W=%d",

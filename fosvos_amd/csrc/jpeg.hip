@@ -22,7 +22,7 @@
 // One more workgroup per frame of the emit launch writes the header, EOI and the file length.  The DCT is the
 // Loeffler-Ligtenberg-Moschytz factorisation with 13-bit constants (jpeg_layout.fdct_1d).  Integers only.
 //
-// 4:2:0 (fosvos_jpeg_encode_sampled with sampling 420, colour only; k_jpeg<3, .., true>): an MCU is 16x16 pixels and six blocks, Y(0,0)
+// 4:2:0 (sampling 420, colour only; k_jpeg<3, .., true>): an MCU is 16x16 pixels and six blocks, Y(0,0)
 // Y(0,1) Y(1,0) Y(1,1) Cb Cr, an interval is kRi420 = 16 MCUs - again 96 blocks, so phases 3 and 4 are the ones above with
 // another block -> (MCU, table) map - and phases 1 and 2 become (jpeg_blocks_420):
 //   1  thread (MCU m = tid & 15, row r = tid >> 4 of 16) loads the 16 pixels of its row (13 aligned words funnel-shifted to
@@ -44,6 +44,12 @@ constexpr int kRi = 32, kJpegThreads = 256, kStride = 66;  // halfwords per bloc
 constexpr int kRi420 = 16;                                 // MCUs of an interval with 4:2:0: 16 x 6 blocks
 constexpr int kAcMax = 1023, kBlockBytes = 208;           // 64 coefficients of at most 26 bits
 constexpr int kHeaderMax = 640;
+// SOI .. SOS (jpeg_layout.header_bytes)
+constexpr __host__ __device__ int jpeg_header_bytes(int C) {
+    const int tables = C == 3 ? 2 : 1;
+    return 2 + 18 + 69 * tables + 10 + 3 * C + 216 * tables + 6 + 8 + 2 * C;
+}
+static_assert(jpeg_header_bytes(1) <= kHeaderMax && jpeg_header_bytes(3) <= kHeaderMax, "the header is built in LDS");
 
 struct JpegQ {
     uint8_t q[2][64];  // natural order
@@ -128,15 +134,11 @@ constexpr HuffEnc make_enc(const HuffSpec &s) {
 }
 __device__ const HuffEnc kEnc[4] = {make_enc(kDc0), make_enc(kAc0), make_enc(kDc1), make_enc(kAc1)};
 
-inline int64_t jpeg_mcus(int H, int W, bool s420 = false) { return s420 ? cdiv(H, 16) * cdiv(W, 16) : cdiv(H, 8) * cdiv(W, 8); }
-inline int64_t jpeg_intervals(int H, int W, bool s420 = false) { return cdiv(jpeg_mcus(H, W, s420), s420 ? kRi420 : kRi); }
-inline int jpeg_header_bytes(int C) {
-    const int tables = C == 3 ? 2 : 1;
-    return 2 + 18 + 69 * tables + 10 + 3 * C + 216 * tables + 6 + 8 + 2 * C;
-}
+inline int64_t jpeg_mcus(int H, int W, bool s420) { return s420 ? cdiv(H, 16) * cdiv(W, 16) : cdiv(H, 8) * cdiv(W, 8); }
+inline int64_t jpeg_intervals(int H, int W, bool s420) { return cdiv(jpeg_mcus(H, W, s420), s420 ? kRi420 : kRi); }
 // jpeg_layout.capacity: 26 bits a coefficient, doubled by the stuffing, two marker bytes an interval; 4:2:0: six blocks
 // for every MCU of the padded grid
-inline int64_t jpeg_file_bound(int H, int W, int C, bool s420 = false) {
+inline int64_t jpeg_file_bound(int H, int W, int C, bool s420) {
     return jpeg_header_bytes(C) + 2 * (int64_t)kBlockBytes * jpeg_mcus(H, W, s420) * (s420 ? 6 : C) + 2 * jpeg_intervals(H, W, s420);
 }
 
@@ -155,29 +157,6 @@ struct JpegShared {
     uint32_t enc_dc[2][12];
     uint32_t wave[kJpegThreads / 64];
 };
-
-__device__ __forceinline__ uint32_t jpeg_block_sum(uint32_t v, uint32_t *wave) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wave[0] + wave[1] + wave[2] + wave[3];
-}
-// inclusive sum over the 256 threads; afterwards wave[0..3] are the four waves' totals
-__device__ __forceinline__ uint32_t jpeg_block_scan(uint32_t v, uint32_t *wave) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    __syncthreads();
-    if (lane == 63) wave[wv] = v;
-    __syncthreads();
-    for (int i = 0; i < wv; ++i) v += wave[i];
-    return v;
-}
 
 // One pass of the DCT over d[0..7], in place (jpeg_layout.fdct_1d)
 template <bool kFirst>
@@ -207,6 +186,39 @@ __device__ __forceinline__ void fdct_1d(int (&d)[8]) {
     d[5] = (t5 + z2 + z4 + r) >> n;
     d[3] = (t6 + z2 + z3 + r) >> n;
     d[1] = (t7 + z1 + z4 + r) >> n;
+}
+
+// Component c (Y, Cb, Cr) of a BGR pixel, 0..255: libjpeg's 16-bit fixed-point rows (jpeg_layout._planes)
+__device__ __forceinline__ int jpeg_ycc(int c, int b, int g, int r) {
+    const int v = c == 0   ? 19595 * r + 38470 * g + 7471 * b + 32768
+                  : c == 1 ? -11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767
+                           : 32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767;
+    return v >> 16;
+}
+
+// Phase 2 for column u of staged block b: column pass, quantisation with table `table` (round half away from zero, AC
+// clamped), the coefficients to their zigzag places, the block's non-zero mask.  `rows`: the real rows of the staged block;
+// a row beyond them reads row rows - 1.
+template <int C>
+__device__ __forceinline__ void quantise_column(JpegShared<C> &sh, const JpegQ &qt, int b, int u, int table, int rows) {
+    int d[8];
+#pragma unroll
+    for (int yy = 0; yy < 8; ++yy) d[yy] = sh.stage[b * kStride + min(yy, rows - 1) * 8 + u];
+    fdct_1d<false>(d);
+    uint32_t nz0 = 0, nz1 = 0;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const int nat = v * 8 + u;
+        const uint32_t q8 = (uint32_t)qt.q[table][nat] << 3;
+        const uint32_t a = (uint32_t)(d[v] < 0 ? -d[v] : d[v]);
+        int mag = (int)((a + (q8 >> 1)) / q8);
+        if (nat != 0) mag = min(mag, kAcMax);
+        const int z = kZig.inv[nat];
+        sh.coef[b * kStride + z] = (int16_t)(d[v] < 0 ? -mag : mag);
+        if (mag) (z < 32 ? nz0 : nz1) |= 1u << (z & 31);
+    }
+    if (nz0) atomicOr(&sh.nz[b][0], nz0);
+    if (nz1) atomicOr(&sh.nz[b][1], nz1);
 }
 
 // The bits the coefficient at zigzag place k of a block adds to the scan (see phase 3 above): code, right-aligned, and
@@ -327,9 +339,8 @@ __device__ __forceinline__ void jpeg_blocks_420(JpegShared<3> &sh, const uint8_t
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int k = half * 8 + i, b = px[3 * k], gg = px[3 * k + 1], rr = px[3 * k + 2];
-                d[i] = ((19595 * rr + 38470 * gg + 7471 * b + 32768) >> 16) - 128;
-                cb[k] = (-11059 * rr - 21709 * gg + 32768 * b + (128 << 16) + 32767) >> 16;
-                cr[k] = (32768 * rr - 27439 * gg - 5329 * b + (128 << 16) + 32767) >> 16;
+                d[i] = jpeg_ycc(0, b, gg, rr) - 128;
+                cb[k] = jpeg_ycc(1, b, gg, rr), cr[k] = jpeg_ycc(2, b, gg, rr);  // (the 2x2 sums come before the shift)
             }
             fdct_1d<true>(d);
             if (live) {
@@ -364,25 +375,7 @@ __device__ __forceinline__ void jpeg_blocks_420(JpegShared<3> &sh, const uint8_t
         for (int k = 0; k < 3; ++k) {
             const int slot = k < 2 ? half * 2 + k : 4 + half;
             if (jpeg420_dummy(slot, mx, my, blocks_w, blocks_h)) continue;
-            const int b = slot * kRi420 + m;
-            int d[8];
-#pragma unroll
-            for (int yy = 0; yy < 8; ++yy) d[yy] = sh.stage[b * kStride + (k < 2 ? yy : min(yy, chroma_rows - 1)) * 8 + u];
-            fdct_1d<false>(d);
-            uint32_t nz0 = 0, nz1 = 0;
-#pragma unroll
-            for (int v = 0; v < 8; ++v) {
-                const int nat = v * 8 + u;
-                const uint32_t q8 = (uint32_t)qt.q[k < 2 ? 0 : 1][nat] << 3;
-                const uint32_t a = (uint32_t)(d[v] < 0 ? -d[v] : d[v]);
-                int mag = (int)((a + (q8 >> 1)) / q8);
-                if (nat != 0) mag = min(mag, kAcMax);
-                const int z = kZig.inv[nat];
-                sh.coef[b * kStride + z] = (int16_t)(d[v] < 0 ? -mag : mag);
-                if (mag) (z < 32 ? nz0 : nz1) |= 1u << (z & 31);
-            }
-            if (nz0) atomicOr(&sh.nz[b][0], nz0);
-            if (nz1) atomicOr(&sh.nz[b][1], nz1);
+            quantise_column(sh, qt, slot * kRi420 + m, u, k < 2 ? 0 : 1, k < 2 ? 8 : chroma_rows);
         }
     }
     __syncthreads();
@@ -411,14 +404,14 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
     const uint32_t n_int = kEmit ? gridDim.x - 1 : gridDim.x, interval = blockIdx.x;
     const uint32_t mcus_w = ((uint32_t)W + kSide - 1u) / kSide, mcus = mcus_w * (((uint32_t)H + kSide - 1u) / kSide);  // (H, W <= 65535: < 2^26)
     ws += (size_t)blockIdx.y * n_int;
-    constexpr uint32_t kHeaderBytes = 2 + 18 + 69 * (C == 3 ? 2 : 1) + 10 + 3 * C + 216 * (C == 3 ? 2 : 1) + 6 + 8 + 2 * C;
+    constexpr uint32_t kHeaderBytes = jpeg_header_bytes(C);
 
     if constexpr (kEmit) {
         out += (int64_t)blockIdx.y * capacity;
         if (interval == n_int) {  // the frame's ends: header, EOI, length
             uint32_t before = 0;
             for (uint32_t s = tid; s < n_int; s += kJpegThreads) before += ws[s] + 2u;
-            const uint32_t total = kHeaderBytes + jpeg_block_sum(before, sh.wave);
+            const uint32_t total = kHeaderBytes + block_sum(before, sh.wave);
             if (tid == 0) build_header<C, k420>(sh.header, H, W, qt);
             __syncthreads();
             for (uint32_t i = tid; i < kHeaderBytes; i += kJpegThreads) out[i] = sh.header[i];
@@ -471,11 +464,7 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if constexpr (C == 3) {
-                        const int b = px[3 * i], gg = px[3 * i + 1], r = px[3 * i + 2];
-                        const int v = c == 0   ? 19595 * r + 38470 * gg + 7471 * b + 32768
-                                      : c == 1 ? -11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767
-                                               : 32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767;
-                        d[i] = (v >> 16) - 128;
+                        d[i] = jpeg_ycc(c, px[3 * i], px[3 * i + 1], px[3 * i + 2]) - 128;
                     } else {
                         d[i] = (int)px[i] - 128;
                     }
@@ -490,29 +479,8 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
 
         // ---- 2: column pass, quantisation, zigzag
         if (m < n_m) {
-            const int u = lane_hi;
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int b = c * kRi + m;
-                int d[8];
-#pragma unroll
-                for (int yy = 0; yy < 8; ++yy) d[yy] = sh.stage[b * kStride + yy * 8 + u];
-                fdct_1d<false>(d);
-                uint32_t nz0 = 0, nz1 = 0;
-#pragma unroll
-                for (int v = 0; v < 8; ++v) {
-                    const int nat = v * 8 + u;
-                    const uint32_t q8 = (uint32_t)qt.q[c ? 1 : 0][nat] << 3;
-                    const uint32_t a = (uint32_t)(d[v] < 0 ? -d[v] : d[v]);
-                    int mag = (int)((a + (q8 >> 1)) / q8);
-                    if (nat != 0) mag = min(mag, kAcMax);
-                    const int z = kZig.inv[nat];
-                    sh.coef[b * kStride + z] = (int16_t)(d[v] < 0 ? -mag : mag);
-                    if (mag) (z < 32 ? nz0 : nz1) |= 1u << (z & 31);
-                }
-                if (nz0) atomicOr(&sh.nz[b][0], nz0);
-                if (nz1) atomicOr(&sh.nz[b][1], nz1);
-            }
+            for (int c = 0; c < C; ++c) quantise_column(sh, qt, c * kRi + m, lane_hi, c ? 1 : 0, 8);
         }
     }
     __syncthreads();  // (stage is dead: the same bytes are `bits` from here on)
@@ -545,7 +513,7 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
         coef_code(k, nzb, k == 0 ? dc_diff : (int)cf[k], enc_dc, enc_ac, code, len);
         my_bits += len;
     }
-    const uint32_t bit_end = jpeg_block_scan(my_bits, sh.wave);
+    const uint32_t bit_end = block_scan_sum(my_bits, sh.wave);
     const uint32_t total_bits = sh.wave[0] + sh.wave[1] + sh.wave[2] + sh.wave[3];
     const uint32_t n_bytes = (total_bits + 7u) / 8u, n_words = (n_bytes + 3u) / 4u;
     for (uint32_t i = tid; i < n_words + 2u; i += kJpegThreads) sh.bits[i] = 0;
@@ -570,7 +538,7 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
     if constexpr (kEmit) {
         uint32_t before = 0;
         for (uint32_t s = tid; s < interval; s += kJpegThreads) before += ws[s] + 2u;
-        dst = out + kHeaderBytes + jpeg_block_sum(before, sh.wave);
+        dst = out + kHeaderBytes + block_sum(before, sh.wave);
     }
     uint32_t stuffed = 0;  // 0xFF bytes in front of the words of this round
     for (uint32_t base = 0; base < n_words; base += kJpegThreads) {
@@ -581,7 +549,7 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) ff += (j < valid && ((word >> (24u - 8u * j)) & 255u) == 255u) ? 1u : 0u;
         if constexpr (kEmit) {
-            const uint32_t incl = jpeg_block_scan(ff, sh.wave);
+            const uint32_t incl = block_scan_sum(ff, sh.wave);
             uint8_t *p = dst + 4u * i + stuffed + (incl - ff);
             for (uint32_t j = 0; j < valid; ++j) {
                 const uint8_t byte = (uint8_t)(word >> (24u - 8u * j));
@@ -599,7 +567,7 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg(const uint8_t *__restrict
             p[0] = 0xFF, p[1] = (uint8_t)(0xD0u + (interval & 7u));
         }
     } else {
-        const uint32_t all = jpeg_block_sum(stuffed, sh.wave);
+        const uint32_t all = block_sum(stuffed, sh.wave);
         if (tid == 0) ws[interval] = n_bytes + all;
     }
 }
@@ -620,13 +588,27 @@ int jpeg_launch(const uint8_t *frames, int N, int H, int W, const JpegQ &qt, uin
     return FOSVOS_OK;
 }
 
-bool jpeg_shape_ok(int N, int H, int W, int components) {
-    return N > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535 && (components == 1 || components == 3);
+// what the two size queries take (anything else: 0 bytes)
+bool jpeg_query_ok(int N, int H, int W, int components, int sampling) {
+    return N > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535 && (components == 1 || components == 3) &&
+           (sampling == 444 || sampling == 420);
+}
+}  // namespace
+
+extern "C" size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components, int sampling) {
+    if (!jpeg_query_ok(N, H, W, components, sampling)) return 0;
+    return (size_t)jpeg_file_bound(H, W, components, sampling == 420 && components == 3);
 }
 
-// the body of both encode entry points; s420: the 4:2:0 layout (colour only)
-int jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, bool s420, int quality, uint8_t *out, size_t out_stride,
-                int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
+extern "C" size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components, int sampling) {
+    if (!jpeg_query_ok(N, H, W, components, sampling)) return 0;
+    return (size_t)N * (size_t)jpeg_intervals(H, W, sampling == 420 && components == 3) * sizeof(uint32_t);
+}
+
+extern "C" int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality,
+                                  uint8_t *out, size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes,
+                                  int device, void *stream) {
+    FOSVOS_REQUIRE(sampling == 444 || sampling == 420, FOSVOS_E_ARG, "jpeg_encode: sampling=%d (444 or 420)", sampling);
     FOSVOS_REQUIRE(components == 1 || components == 3, FOSVOS_E_SHAPE, "jpeg_encode: components=%d (1 grey, 3 BGR)", components);
     FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && H <= 65535 && W <= 65535, FOSVOS_E_SHAPE,
                    "jpeg_encode: N=%d H=%d W=%d (each 1..65535)", N, H, W);
@@ -634,7 +616,7 @@ int jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, bool
     FOSVOS_REQUIRE(frames && out && lengths && workspace, FOSVOS_E_ARG, "jpeg_encode: null pointer");
     FOSVOS_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)lengths & 3) == 0, FOSVOS_E_ARG,
                    "jpeg_encode: the workspace and the lengths must be 4-byte aligned");
-    s420 = s420 && components == 3;
+    const bool s420 = sampling == 420 && components == 3;
     const size_t need_cap = (size_t)jpeg_file_bound(H, W, components, s420);
     const size_t need_ws = (size_t)N * (size_t)jpeg_intervals(H, W, s420) * sizeof(uint32_t);
     FOSVOS_REQUIRE(need_cap <= (size_t)INT32_MAX, FOSVOS_E_SHAPE, "jpeg_encode: H=%d W=%d: the size bound %zu B exceeds 2^31 - 1", H,
@@ -654,40 +636,4 @@ int jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, bool
     if (s420) return jpeg_launch<3, true>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream);
     return components == 3 ? jpeg_launch<3, false>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream)
                            : jpeg_launch<1, false>(frames, N, H, W, qt, out, out_stride, lengths, ws, stream);
-}
-}  // namespace
-
-extern "C" size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components) {
-    if (!jpeg_shape_ok(N, H, W, components)) return 0;
-    return (size_t)jpeg_file_bound(H, W, components);
-}
-
-extern "C" size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components) {
-    if (!jpeg_shape_ok(N, H, W, components)) return 0;
-    return (size_t)N * (size_t)jpeg_intervals(H, W) * sizeof(uint32_t);
-}
-
-extern "C" int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int quality, uint8_t *out,
-                                  size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes, int device,
-                                  void *stream) {
-    return jpeg_encode(frames, N, H, W, components, false, quality, out, out_stride, lengths, workspace, workspace_bytes, device,
-                       stream);
-}
-
-extern "C" size_t fosvos_jpeg_capacity_bytes_sampled(int N, int H, int W, int components, int sampling) {
-    if (!jpeg_shape_ok(N, H, W, components) || (sampling != 444 && sampling != 420)) return 0;
-    return (size_t)jpeg_file_bound(H, W, components, sampling == 420 && components == 3);
-}
-
-extern "C" size_t fosvos_jpeg_workspace_bytes_sampled(int N, int H, int W, int components, int sampling) {
-    if (!jpeg_shape_ok(N, H, W, components) || (sampling != 444 && sampling != 420)) return 0;
-    return (size_t)N * (size_t)jpeg_intervals(H, W, sampling == 420 && components == 3) * sizeof(uint32_t);
-}
-
-extern "C" int fosvos_jpeg_encode_sampled(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality,
-                                          uint8_t *out, size_t out_stride, int32_t *lengths, void *workspace,
-                                          size_t workspace_bytes, int device, void *stream) {
-    FOSVOS_REQUIRE(sampling == 444 || sampling == 420, FOSVOS_E_ARG, "jpeg_encode: sampling=%d (444 or 420)", sampling);
-    return jpeg_encode(frames, N, H, W, components, sampling == 420, quality, out, out_stride, lengths, workspace, workspace_bytes,
-                       device, stream);
 }

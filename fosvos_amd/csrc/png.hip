@@ -20,7 +20,7 @@
 // Run boundaries across the 256 threads come from a max-scan (start of the run entering a thread's bytes) and a reverse
 // min-scan (end of the run leaving them).  LDS: 4 KB segment + 4.1 KB chunk + 1 KB CRC table + scan scratch.
 //
-// fosvos_png_encode_mode(huffman = 1) runs the <true> instantiations of the same two kernels, which add a third form of a
+// huffman = 1 runs the <true> instantiations of the same two kernels, which add a third form of a
 // segment: a dynamic-Huffman block (BTYPE = 10) with a literal/length code fitted to the segment's tokens (png_layout.py
 // states it: two-queue Huffman construction over the symbols sorted by (count, symbol), counts halved while the tree is
 // deeper than 15, canonical codes, HDIST = 0, a fixed code-length code, zero runs as symbols 17 / 18).
@@ -105,55 +105,6 @@ struct PngFit {
     uint32_t next[16];                                     // first code of each length
     uint32_t deepest;
 };
-
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wave) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wave[0] + wave[1] + wave[2] + wave[3];
-}
-__device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t *wave) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v ^= __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wave[0] ^ wave[1] ^ wave[2] ^ wave[3];
-}
-// inclusive scans over the 256 threads (max of ints; sum of uints)
-__device__ __forceinline__ int block_scan_max(int v, uint32_t *wave) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o, 64);
-        if (lane >= o) v = max(v, u);
-    }
-    __syncthreads();
-    if (lane == 63) wave[wv] = (uint32_t)v;
-    __syncthreads();
-    for (int i = 0; i < wv; ++i) v = max(v, (int)wave[i]);
-    return v;
-}
-// kFresh (the fitted kernels' late scans): the lane number passes through an empty asm, so the six `lane >= o` masks are
-// taken anew where they are used; shared with the first scan of the kernel they stay alive, in twelve SGPRs, all the way.
-template <bool kFresh = false>
-__device__ __forceinline__ uint32_t block_scan_sum(uint32_t v, uint32_t *wave) {
-    int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    if constexpr (kFresh) asm volatile("" : "+v"(lane));
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    __syncthreads();
-    if (lane == 63) wave[wv] = v;
-    __syncthreads();
-    for (int i = 0; i < wv; ++i) v += wave[i];
-    return v;
-}
 
 // The n bytes of segment `seg` of the filtered stream of one frame -> sh.seg (coalesced byte loads; bytes past n are 0).
 __device__ __forceinline__ void load_segment(const uint8_t *__restrict__ img, int W, uint32_t seg, int n, PngShared &sh) {
@@ -685,6 +636,21 @@ __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restr
     }
 
 }
+
+template <bool kFitted>
+int png_launch(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths, uint32_t *ws,
+               void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)png_segments(H, W), (unsigned)N);
+    FOSVOS_PROF(kFitted ? "k_png_measure_fitted" : "k_png_measure", stream, 0.0);
+    hipLaunchKernelGGL(k_png_measure<kFitted>, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
+    FOSVOS_LAUNCH_CHECK();
+    FOSVOS_PROF(kFitted ? "k_png_emit_fitted" : "k_png_emit", stream, 0.0);
+    hipLaunchKernelGGL(k_png_emit<kFitted>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out,
+                       (int64_t)capacity, lengths);
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
 }  // namespace
 
 extern "C" size_t fosvos_png_capacity_bytes(int N, int H, int W) {
@@ -692,65 +658,26 @@ extern "C" size_t fosvos_png_capacity_bytes(int N, int H, int W) {
     return (size_t)png_file_bound(H, W);
 }
 
-extern "C" size_t fosvos_png_workspace_bytes(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)N * (size_t)png_segments(H, W) * kWsWords * sizeof(uint32_t);
-}
-
-extern "C" size_t fosvos_png_workspace_bytes_mode(int N, int H, int W, int huffman) {
+extern "C" size_t fosvos_png_workspace_bytes(int N, int H, int W, int huffman) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
     return (size_t)N * (size_t)png_segments(H, W) * (kWsWords + (huffman ? kLenWords : 0)) * sizeof(uint32_t);
 }
 
-extern "C" int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths,
-                                 void *workspace, size_t workspace_bytes, int device, void *stream) {
-    FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && png_stream_bytes(H, W) <= ((int64_t)1 << 30), FOSVOS_E_SHAPE,
-                   "png_encode: N=%d (<= 65535) H=%d W=%d (H * (W + 1) <= 2^30)", N, H, W);
-    FOSVOS_REQUIRE(bytes && out && lengths && workspace, FOSVOS_E_ARG, "png_encode: null pointer");
-    FOSVOS_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)lengths & 3) == 0, FOSVOS_E_ARG,
-                   "png_encode: the workspace and the lengths must be 4-byte aligned");
-    const size_t need_cap = fosvos_png_capacity_bytes(N, H, W), need_ws = fosvos_png_workspace_bytes(N, H, W);
-    FOSVOS_REQUIRE(capacity >= need_cap, FOSVOS_E_WORKSPACE, "png_encode: capacity %zu B a frame < %zu B", capacity, need_cap);
-    FOSVOS_REQUIRE(workspace_bytes >= need_ws, FOSVOS_E_WORKSPACE, "png_encode: workspace %zu B < %zu B", workspace_bytes,
-                   need_ws);
-    FOSVOS_ENTER(device);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)png_segments(H, W), (unsigned)N);
-    uint32_t *ws = reinterpret_cast<uint32_t *>(workspace);
-    FOSVOS_PROF("k_png_measure", stream, 0.0);
-    hipLaunchKernelGGL(k_png_measure<false>, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
-    FOSVOS_LAUNCH_CHECK();
-    FOSVOS_PROF("k_png_emit", stream, 0.0);
-    hipLaunchKernelGGL(k_png_emit<false>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out, (int64_t)capacity,
-                       lengths);
-    FOSVOS_LAUNCH_CHECK();
-    return FOSVOS_OK;
-}
-
-extern "C" int fosvos_png_encode_mode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
-                                      int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
+extern "C" int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
+                                 int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
     FOSVOS_REQUIRE(huffman == 0 || huffman == 1, FOSVOS_E_ARG, "png_encode: huffman=%d (0 fixed, 1 fitted)", huffman);
-    if (huffman == 0)
-        return fosvos_png_encode(bytes, N, H, W, out, capacity, lengths, workspace, workspace_bytes, device, stream);
     FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && png_stream_bytes(H, W) <= ((int64_t)1 << 30), FOSVOS_E_SHAPE,
                    "png_encode: N=%d (<= 65535) H=%d W=%d (H * (W + 1) <= 2^30)", N, H, W);
     FOSVOS_REQUIRE(bytes && out && lengths && workspace, FOSVOS_E_ARG, "png_encode: null pointer");
     FOSVOS_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)lengths & 3) == 0, FOSVOS_E_ARG,
                    "png_encode: the workspace and the lengths must be 4-byte aligned");
-    const size_t need_cap = fosvos_png_capacity_bytes(N, H, W), need_ws = fosvos_png_workspace_bytes_mode(N, H, W, huffman);
+    const size_t need_cap = fosvos_png_capacity_bytes(N, H, W), need_ws = fosvos_png_workspace_bytes(N, H, W, huffman);
     FOSVOS_REQUIRE(capacity >= need_cap, FOSVOS_E_WORKSPACE, "png_encode: capacity %zu B a frame < %zu B", capacity, need_cap);
     FOSVOS_REQUIRE(workspace_bytes >= need_ws, FOSVOS_E_WORKSPACE, "png_encode: workspace %zu B < %zu B", workspace_bytes,
                    need_ws);
     FOSVOS_ENTER(device);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)png_segments(H, W), (unsigned)N);
     uint32_t *ws = reinterpret_cast<uint32_t *>(workspace);
-    FOSVOS_PROF("k_png_measure_fitted", stream, 0.0);
-    hipLaunchKernelGGL(k_png_measure<true>, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
-    FOSVOS_LAUNCH_CHECK();
-    FOSVOS_PROF("k_png_emit_fitted", stream, 0.0);
-    hipLaunchKernelGGL(k_png_emit<true>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out,
-                       (int64_t)capacity, lengths);
-    FOSVOS_LAUNCH_CHECK();
-    return FOSVOS_OK;
+    // (<false> named first: the fixed kernels stay in front of the fitted ones in the code object)
+    return huffman == 0 ? png_launch<false>(bytes, N, H, W, out, capacity, lengths, ws, stream)
+                        : png_launch<true>(bytes, N, H, W, out, capacity, lengths, ws, stream);
 }

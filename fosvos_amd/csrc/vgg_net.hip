@@ -197,9 +197,9 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
                 void *wsc = half ? base + a.wsa_conv[c] : ws;
                 const size_t wsn = half ? a.wsa_conv_bytes[c] : a.ws_bytes;
                 if (c == 0) {
-                    FOSVOS_TRY(fosvos_conv3x3_first_fwd_bits(frame + (size_t)f0 * 3 * H * W, w->conv_w[0], w->conv_b[0], yc,
-                                                             reinterpret_cast<uint8_t *>(base + a.bits0) + (size_t)f0 * px * (kCout[0] / 8),
-                                                             nf, H, W, kCout[0], device, st));
+                    FOSVOS_TRY(fosvos_conv3x3_first_fwd(frame + (size_t)f0 * 3 * H * W, w->conv_w[0], w->conv_b[0], yc,
+                                                        reinterpret_cast<uint8_t *>(base + a.bits0) + (size_t)f0 * px * (kCout[0] / 8),
+                                                        nf, H, W, kCout[0], device, st));
                 } else {
                     if (c == kFirstOfStage[s]) {
                         const size_t ppx = (size_t)a.sh[s] * a.sw[s];
@@ -257,8 +257,8 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
     for (int c = 0; c < kNConv; ++c) {
         const int s = kStageOf[c];
         if (c == 0) {
-            FOSVOS_TRY(fosvos_conv3x3_first_fwd_bits(frame, w->conv_w[0], w->conv_b[0], act(0),
-                                                     reinterpret_cast<uint8_t *>(base + a.bits0), N, H, W, kCout[0], device, stream));
+            FOSVOS_TRY(fosvos_conv3x3_first_fwd(frame, w->conv_w[0], w->conv_b[0], act(0),
+                                                reinterpret_cast<uint8_t *>(base + a.bits0), N, H, W, kCout[0], device, stream));
         } else {
             if (c == kFirstOfStage[s])  // stage entry: the pooled map the previous stage's last conv wrote
                 x = reinterpret_cast<uint16_t *>(base + a.pooled[s - 1]);

@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -125,10 +125,8 @@ SIGNATURES = {
     "fosvos_pack_conv3x3_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fosvos_packed_weight_elems": (c_size_t, [c_int, c_int]),
     "fosvos_pack_conv3x3_weights_multi": (c_int, [POINTER(PackEntry), c_int, c_int, c_void_p]),
-    "fosvos_conv3x3_first_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+    "fosvos_conv3x3_first_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_void_p]),
-    "fosvos_conv3x3_first_fwd_bits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                              c_void_p]),
     "fosvos_conv3x3_dgrad_bits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_conv3x3_dgrad_unpool": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -218,23 +216,16 @@ SIGNATURES = {
     "fosvos_jf_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int,
                                  c_void_p]),
     "fosvos_png_capacity_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "fosvos_png_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "fosvos_png_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+    "fosvos_png_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fosvos_png_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
                                   c_void_p]),
-    "fosvos_jpeg_capacity_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "fosvos_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "fosvos_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
-                                   c_int, c_void_p]),
-    "fosvos_jpeg_capacity_bytes_sampled": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "fosvos_jpeg_workspace_bytes_sampled": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "fosvos_jpeg_encode_sampled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
-                                           c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_jpeg_capacity_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fosvos_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fosvos_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                   c_size_t, c_int, c_void_p]),
     "fosvos_jpeg_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "fosvos_jpeg_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "fosvos_png_workspace_bytes_mode": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "fosvos_png_encode_mode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
-                                       c_int, c_void_p]),
     "fosvos_frame_prep": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_int, c_void_p]),
     "fosvos_overlay": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int,
                                c_void_p]),

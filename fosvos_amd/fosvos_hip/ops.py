@@ -192,7 +192,7 @@ def pack_conv3x3_weights_multi(ws: Sequence[torch.Tensor]):
 # ------------------------------------------------------------------------------------------ conv
 def conv3x3_first_fwd(frame: torch.Tensor, w: torch.Tensor, b: torch.Tensor, want_bits: bool = False):
     """y bf16 NHWC; want_bits: (y, relu_bits) with relu_bits uint8 [N,H,W,Co/8], bit e of byte g = (y[..., 8 g + e] > 0)
-    (fosvos_conv3x3_first_fwd_bits: what conv3x3_dgrad takes as ``relu_bits``)."""
+    (what conv3x3_dgrad takes as ``relu_bits``)."""
     _need(frame, _F32, "conv3x3_first_fwd frame"); _need(w, _F32, "conv3x3_first_fwd weight"); _need(b, _F32, "conv3x3_first_fwd bias")
     n, c, h, wd = frame.shape
     if c != 3 or tuple(w.shape[1:]) != (3, 3, 3):
@@ -202,8 +202,8 @@ def conv3x3_first_fwd(frame: torch.Tensor, w: torch.Tensor, b: torch.Tensor, wan
     dev, st = _ctx(frame)
     t0 = _pb()
     bits = torch.empty((n, h, wd, co // 8), dtype=torch.uint8, device=frame.device) if want_bits else None
-    check(lib().fosvos_conv3x3_first_fwd_bits(frame.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), _p(bits), n, h, wd, co,
-                                              dev, st), "conv3x3_first_fwd")
+    check(lib().fosvos_conv3x3_first_fwd(frame.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), _p(bits), n, h, wd, co,
+                                         dev, st), "conv3x3_first_fwd")
     _pe(t0, "conv1_1_fwd", 2.0 * n * h * wd * 27 * co, n * h * wd * (12 + 2 * co))
     return (y, bits) if want_bits else y
 
@@ -1169,7 +1169,7 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengt
     """fosvos_png_encode: uint8 [N,H,W] (``prob_bytes``' output) -> (buffer uint8 [N,capacity], lengths int32 [N]): frame n's
     8-bit greyscale PNG file is ``buffer[n, :lengths[n]]``, in the layout util/png_layout.py states; the bytes behind it
     are not written.  ``out`` (uint8 [N, >= png_capacity(H, W)]) and ``lengths`` (int32 [N]) may be views of a caller's
-    buffer.  ``huffman='fitted'`` (fosvos_png_encode_mode): a segment may also be a dynamic-Huffman block with a code fitted
+    buffer.  ``huffman='fitted'``: a segment may also be a dynamic-Huffman block with a code fitted
     to it, where that is shorter - the same pixels in files that are never longer, ``png_layout.encode(img, 'fitted')``.
     Launched on the current stream, no synchronisation."""
     if huffman not in PNG_HUFFMAN:
@@ -1196,16 +1196,11 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengt
         if t.device != bytes_u8.device:
             raise RuntimeError(f"png_encode: every tensor must be on {bytes_u8.device}, got one on {t.device}")
     mode = PNG_HUFFMAN[huffman]
-    ws, wsn = _WS.get(L.fosvos_png_workspace_bytes_mode(n, h, w, mode) if mode else L.fosvos_png_workspace_bytes(n, h, w),
-                      bytes_u8.device)
+    ws, wsn = _WS.get(L.fosvos_png_workspace_bytes(n, h, w, mode), bytes_u8.device)
     dev, st = _ctx(bytes_u8)
     e0 = _pb()
-    if mode:
-        check(L.fosvos_png_encode_mode(bytes_u8.data_ptr(), n, h, w, mode, out.data_ptr(), int(out.shape[1]),
-                                       lengths.data_ptr(), ws, wsn, dev, st), "png_encode")
-    else:
-        check(L.fosvos_png_encode(bytes_u8.data_ptr(), n, h, w, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(), ws,
-                                  wsn, dev, st), "png_encode")
+    check(L.fosvos_png_encode(bytes_u8.data_ptr(), n, h, w, mode, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(), ws,
+                              wsn, dev, st), "png_encode")
     _pe(e0, "png_encode", 0.0, 2.0 * n * h * w)
     return out, lengths
 
@@ -1215,7 +1210,7 @@ JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
 
 
 def _jpeg_subsampling(subsampling, what: str) -> bool:
-    """True for '4:2:0', False for '4:4:4' (the entry points as they were), ValueError for anything else."""
+    """True for '4:2:0', False for '4:4:4', ValueError for anything else."""
     if subsampling not in JPEG_SUBSAMPLINGS:
         raise ValueError(f"{what}: subsampling must be one of {JPEG_SUBSAMPLINGS}, got {subsampling!r}")
     return subsampling == '4:2:0'
@@ -1223,10 +1218,8 @@ def _jpeg_subsampling(subsampling, what: str) -> bool:
 
 def jpeg_capacity(h: int, w: int, components: int, subsampling: str = '4:4:4') -> int:
     """Bytes ``jpeg_encode`` reserves per frame: the layout's size bound (util/jpeg_layout.capacity)."""
-    if _jpeg_subsampling(subsampling, "jpeg_capacity"):
-        cap = int(lib().fosvos_jpeg_capacity_bytes_sampled(1, int(h), int(w), int(components), 420))
-    else:
-        cap = int(lib().fosvos_jpeg_capacity_bytes(1, int(h), int(w), int(components)))
+    sampling = 420 if _jpeg_subsampling(subsampling, "jpeg_capacity") else 444
+    cap = int(lib().fosvos_jpeg_capacity_bytes(1, int(h), int(w), int(components), sampling))
     if cap == 0:
         raise ValueError(f"jpeg_capacity: h, w in 1..65535 and components 1 or 3, got {h}, {w}, {components}")
     return cap
@@ -1237,9 +1230,9 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     """fosvos_jpeg_encode: uint8 [N,H,W,3] BGR (``overlay``'s output) or [N,H,W] grey -> (buffer uint8 [N,capacity], lengths
     int32 [N]): frame n's baseline JPEG file is ``buffer[n, :lengths[n]]``, in the layout util/jpeg_layout.py states; the
     bytes behind it are not written.  ``out`` (uint8 [N, >= jpeg_capacity(H, W, components, subsampling)]) and ``lengths``
-    (int32 [N]) may be views of a caller's buffer.  ``subsampling='4:2:0'`` (fosvos_jpeg_encode_sampled) halves the chroma
+    (int32 [N]) may be views of a caller's buffer.  ``subsampling='4:2:0'`` halves the chroma
     planes of a colour frame; a grey frame ignores it.  Launched on the current stream, no synchronisation."""
-    sampled = _jpeg_subsampling(subsampling, "jpeg_encode")
+    sampling = 420 if _jpeg_subsampling(subsampling, "jpeg_encode") else 444
     _need_eval(frames_u8, torch.uint8, "jpeg_encode frames")
     if frames_u8.numel() == 0 or not (frames_u8.dim() == 3 or (frames_u8.dim() == 4 and frames_u8.shape[3] == 3)):
         raise ValueError(f"jpeg_encode: frames must be a non-empty [N,H,W,3] or [N,H,W], got {tuple(frames_u8.shape)}")
@@ -1248,7 +1241,7 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     n, h, w = (int(v) for v in frames_u8.shape[:3])
     comps = 3 if frames_u8.dim() == 4 else 1
     L = lib()
-    cap = int(L.fosvos_jpeg_capacity_bytes_sampled(n, h, w, comps, 420) if sampled else L.fosvos_jpeg_capacity_bytes(n, h, w, comps))
+    cap = int(L.fosvos_jpeg_capacity_bytes(n, h, w, comps, sampling))
     if cap == 0:
         raise ValueError(f"jpeg_encode: H and W must be at most 65535, got {h}, {w}")
     if out is None:
@@ -1266,16 +1259,11 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     for t in (out, lengths):
         if t.device != frames_u8.device:
             raise RuntimeError(f"jpeg_encode: every tensor must be on {frames_u8.device}, got one on {t.device}")
-    need = L.fosvos_jpeg_workspace_bytes_sampled(n, h, w, comps, 420) if sampled else L.fosvos_jpeg_workspace_bytes(n, h, w, comps)
-    ws, wsn = _WS.get(need, frames_u8.device)
+    ws, wsn = _WS.get(L.fosvos_jpeg_workspace_bytes(n, h, w, comps, sampling), frames_u8.device)
     dev, st = _ctx(frames_u8)
     e0 = _pb()
-    if sampled:
-        check(L.fosvos_jpeg_encode_sampled(frames_u8.data_ptr(), n, h, w, comps, 420, int(quality), out.data_ptr(),
-                                           int(out.shape[1]), lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
-    else:
-        check(L.fosvos_jpeg_encode(frames_u8.data_ptr(), n, h, w, comps, int(quality), out.data_ptr(), int(out.shape[1]),
-                                   lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
+    check(L.fosvos_jpeg_encode(frames_u8.data_ptr(), n, h, w, comps, sampling, int(quality), out.data_ptr(), int(out.shape[1]),
+                               lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
     _pe(e0, "jpeg_encode", 0.0, 2.0 * n * h * w * comps)
     return out, lengths
 

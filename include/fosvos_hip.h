@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 29
+#define FOSVOS_ABI_VERSION 30
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -140,13 +140,11 @@ int fosvos_pack_conv3x3_weights_multi(const fosvos_pack_entry *entries, int n, i
 
 /* ---- first layer: conv1_1 (Ci = 3) straight from the fp32 NCHW frame --------------------------
  * y[N,H,W,Co] bf16 = relu(conv3x3(frame, w, pad 1) + b), fp32 VALU arithmetic (K = 27).
+ * relu_bits [N,H,W,Co/8] bytes (NULL = none): the ReLU mask of y as one bit per element, bit e of byte g set where
+ * y[..., 8 g + e] > 0 - what fosvos_conv3x3_dgrad_bits reads instead of y.
  * replaces: stages[0][0..1] = Conv2d(3,64,3,pad=1)+ReLU (src/networks/osvos_vgg.py:92-93). */
-int fosvos_conv3x3_first_fwd(const float *frame, const float *w_oihw, const float *bias, uint16_t *y, int N, int H,
-                             int W, int Co, int device, void *stream);
-/* The same, also writing the ReLU mask of y as one bit per element: relu_bits [N,H,W,Co/8] bytes (NULL = none), bit e of
- * byte g set where y[..., 8 g + e] > 0 - what fosvos_conv3x3_dgrad_bits reads instead of y. */
-int fosvos_conv3x3_first_fwd_bits(const float *frame, const float *w_oihw, const float *bias, uint16_t *y,
-                                  uint8_t *relu_bits, int N, int H, int W, int Co, int device, void *stream);
+int fosvos_conv3x3_first_fwd(const float *frame, const float *w_oihw, const float *bias, uint16_t *y, uint8_t *relu_bits,
+                             int N, int H, int W, int Co, int device, void *stream);
 /* Launch geometry of the above: 8 x 32-pixel tiles and the (persistent) workgroups that walk them; tiles > workgroups
  * means every workgroup loops over several tiles with its double-buffered staging.  Host arithmetic only. */
 int fosvos_conv3x3_first_plan(int N, int H, int W, int *tiles, int *workgroups);
@@ -219,7 +217,7 @@ int fosvos_conv3x3_dgrad(const uint16_t *dy, const uint16_t *w_dgrad_packed, con
                          const uint16_t *addend, uint16_t *dx, int N, int H, int W, int Ci, int Co, void *workspace,
                          size_t workspace_bytes, int device, void *stream);
 /* The same with the ReLU mask given as ONE BIT per element: relu_bits [N,H,W,Ci/8] bytes, bit e of byte g set where channel
- * 8 g + e of the producing layer's output is > 0 (fosvos_conv3x3_first_fwd_bits writes it for conv1_1).  Bit for bit the
+ * 8 g + e of the producing layer's output is > 0 (fosvos_conv3x3_first_fwd writes it for conv1_1).  Bit for bit the
  * result of fosvos_conv3x3_dgrad on the bf16 image the bits were taken from; 1/16 of the mask bytes - conv1_2's data gradient
  * at 480x854 is bound by HBM traffic. */
 int fosvos_conv3x3_dgrad_bits(const uint16_t *dy, const uint16_t *w_dgrad_packed, const uint8_t *relu_bits,
@@ -422,64 +420,48 @@ int fosvos_jf_counts(const float *logits, const uint8_t *gt, int N, int H, int W
  * fosvos_png_encode: bytes uint8 [N,H,W] (what fosvos_prob_bytes writes) -> N standalone 8-bit greyscale PNG files: frame n's
  * file is out[n * capacity .. n * capacity + lengths[n]), the bytes behind it are left as they were.  The layout is stated
  * in numpy in util/png_layout.py (the tests compare byte for byte): the filtered stream (filter None) is cut into segments
- * of 4096 bytes, each one fixed-Huffman deflate block (runs of a byte as distance-1 matches, everything else literals)
- * closed by an empty stored block - or a stored block where that is shorter - in an IDAT chunk of its own; a last IDAT holds
- * the final block and the Adler-32.  Any PNG reader decodes the files to the input bytes; they are larger than a
- * level-6 zlib stream of the same image.
+ * of 4096 bytes, each in an IDAT chunk of its own; a last IDAT holds the final block and the Adler-32.  huffman = 0 (fixed):
+ * a segment is one fixed-Huffman deflate block (runs of a byte as distance-1 matches, everything else literals) closed by
+ * an empty stored block - or a stored block where that is shorter.  huffman = 1 (fitted) adds a third form: a
+ * dynamic-Huffman block (BTYPE = 10) whose literal/length code is fitted to the segment's tokens - deterministic two-queue
+ * Huffman construction over the symbols sorted by (count, symbol), lengths limited to 15 bits by halving the counts,
+ * canonical codes; HDIST = 0 (a match's distance costs 1 bit); a fixed, complete code-length code with HCLEN = 19; zero
+ * runs of the length sequence as symbols 17 / 18.  Each segment takes the shortest of {fitted, fixed, stored}, fixed or
+ * stored on a tie, so no file is longer than with huffman = 0.  Any other huffman: FOSVOS_E_ARG.  Any PNG reader decodes
+ * the files to the input bytes; they are larger than a level-6 zlib stream of the same image.
  *   capacity   bytes reserved per frame in `out`, >= fosvos_png_capacity_bytes (the layout's size bound
- *              65 + H (W+1) + 17 ceil(H (W+1) / 4096): no image encodes to more)
+ *              65 + H (W+1) + 17 ceil(H (W+1) / 4096): no image encodes to more, with either huffman)
  *   lengths    int32 [N]
- *   workspace  fosvos_png_workspace_bytes, 4-byte aligned; what it and `out` held before does not matter
+ *   workspace  fosvos_png_workspace_bytes (16 B a segment, and with huffman != 0 288 B of code lengths more), 4-byte
+ *              aligned; what it and `out` held before does not matter
  * H (W+1) <= 2^30.  Integer arithmetic only; two launches on `stream`.
  * replaces: the PIL encoder behind scipy.misc.imsave of src/util/experiment_helper.py:64. */
 size_t fosvos_png_capacity_bytes(int N, int H, int W); /* per frame */
-size_t fosvos_png_workspace_bytes(int N, int H, int W);
-int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths,
+size_t fosvos_png_workspace_bytes(int N, int H, int W, int huffman);
+int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity, int32_t *lengths,
                       void *workspace, size_t workspace_bytes, int device, void *stream);
-
-/* fosvos_png_encode_mode: the same files with a choice of Huffman codes.  huffman = 0 is fosvos_png_encode, byte for byte.
- * huffman = 1 (fitted) adds a third form of a segment: a dynamic-Huffman block (BTYPE = 10) whose literal/length code is
- * fitted to the segment's tokens - deterministic two-queue Huffman construction over the symbols sorted by (count, symbol),
- * lengths limited to 15 bits by halving the counts, canonical codes; HDIST = 0 (a match's distance costs 1 bit); a fixed,
- * complete code-length code with HCLEN = 19; zero runs of the length sequence as symbols 17 / 18.  Each segment takes the
- * shortest of {fitted, fixed, stored}, fixed or stored on a tie, so no file is longer than with huffman = 0 and the
- * capacity is the same.  util/png_layout.py encode(img, huffman='fitted') states the bytes.
- *   workspace  fosvos_png_workspace_bytes_mode(N, H, W, huffman): with huffman = 1 the records of huffman = 0 and 288
- *              bytes of code lengths per segment
- * Integer arithmetic only; two launches on `stream`. */
-size_t fosvos_png_workspace_bytes_mode(int N, int H, int W, int huffman);
-int fosvos_png_encode_mode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
-                           int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* ---- the streamed output frames as JPEG files, encoded on the device --------------------------------------------------
  * fosvos_jpeg_encode: frames uint8 [N,H,W,3] BGR (what fosvos_overlay writes; components = 3) or [N,H,W] grey (components =
  * 1) -> N standalone baseline JFIF files: frame n's file is out[n * out_stride .. n * out_stride + lengths[n]), the bytes
  * behind it are left as they were.  The layout is stated in integers in util/jpeg_layout.py (the tests compare byte for
- * byte): 4:4:4, libjpeg's 16-bit fixed-point colour rows, the Loeffler-Ligtenberg-Moschytz DCT with 13-bit constants, the
- * Annex K tables scaled by the IJG rule for `quality` (1..100), the standard Huffman tables, a restart interval of 32 MCUs.
- * `frames` needs no alignment.
+ * byte): libjpeg's 16-bit fixed-point colour rows, the Loeffler-Ligtenberg-Moschytz DCT with 13-bit constants, the Annex K
+ * tables scaled by the IJG rule for `quality` (1..100), the standard Huffman tables.  sampling 444: an MCU is one block a
+ * component, a restart interval 32 MCUs.  sampling 420 halves both chroma planes: an MCU is 16x16 pixels and six blocks
+ * (Y Y Y Y Cb Cr), SOF0 says 2x2 1x1 1x1, the restart interval is 16 MCUs; chroma is libjpeg's h2v2 mean with the
+ * alternating bias, luma blocks beyond ceil(W/8) x ceil(H/8) are dummies (DC of the block in front, no AC), and the file
+ * is byte for byte libjpeg-turbo's for the same parameters.  A grey frame has no chroma: 420 gives the 444 file and sizes.
+ * Any other sampling: the sizes are 0, the encode returns FOSVOS_E_ARG.  `frames` needs no alignment.
  *   out_stride bytes reserved per frame in `out`, >= fosvos_jpeg_capacity_bytes (the layout's size bound: header + 416 B a
- *              block + 2 B an interval; no image encodes to more; 0 for a shape the encoder does not take)
+ *              block - with 420 six blocks an MCU of the padded grid - + 2 B an interval; no image encodes to more; 0 for
+ *              a shape the encoder does not take)
  *   lengths    int32 [N]
  *   workspace  fosvos_jpeg_workspace_bytes (4 B an interval), 4-byte aligned; what it and `out` held does not matter
  * H, W <= 65535 and a size bound below 2^31.  Integer arithmetic only; two launches on `stream`. */
-size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components); /* per frame */
-size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components);
-int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int quality, uint8_t *out,
+size_t fosvos_jpeg_capacity_bytes(int N, int H, int W, int components, int sampling); /* per frame */
+size_t fosvos_jpeg_workspace_bytes(int N, int H, int W, int components, int sampling);
+int fosvos_jpeg_encode(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality, uint8_t *out,
                        size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream);
-
-/* The same with the chroma sampling chosen (ABI 27): sampling 444 is exactly the three entry points above, 420 halves both
- * chroma planes.  With 420 an MCU is 16x16 pixels and six blocks (Y Y Y Y Cb Cr), SOF0 says 2x2 1x1 1x1, the restart
- * interval is 16 MCUs; chroma is libjpeg's h2v2 mean with the alternating bias, luma blocks beyond ceil(W/8) x ceil(H/8)
- * are dummies (DC of the block in front, no AC) - util/jpeg_layout.py states all of it, and the file is byte for byte
- * libjpeg-turbo's for the same parameters.  The bound is header + 416 B x 6 blocks an MCU of the padded grid + 2 B an
- * interval; the workspace 4 B an interval.  A grey frame (components = 1) has no chroma: 420 gives the 444 file and sizes.
- * Any other sampling: the sizes are 0, the encode returns FOSVOS_E_ARG. */
-size_t fosvos_jpeg_capacity_bytes_sampled(int N, int H, int W, int components, int sampling); /* per frame */
-size_t fosvos_jpeg_workspace_bytes_sampled(int N, int H, int W, int components, int sampling);
-int fosvos_jpeg_encode_sampled(const uint8_t *frames, int N, int H, int W, int components, int sampling, int quality,
-                               uint8_t *out, size_t out_stride, int32_t *lengths, void *workspace, size_t workspace_bytes,
-                               int device, void *stream);
 
 /* ---- JPEG files in, frames out: the decoder of the test pass's and the stream's input frames (ABI 28) ------------------
  * fosvos_jpeg_decode: N baseline JPEG files of ONE shape, component count and sampling -> frames uint8 [N,H,W,3] BGR

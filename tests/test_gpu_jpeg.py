@@ -131,11 +131,11 @@ def test_bad_arguments_raise_and_launch_nothing():
     from fosvos_hip import LaunchProfile, lib, ops
     L = lib()
     n, h, w = 2, 24, 40
-    cap, need = L.fosvos_jpeg_capacity_bytes(n, h, w, 3), L.fosvos_jpeg_workspace_bytes(n, h, w, 3)
+    cap, need = L.fosvos_jpeg_capacity_bytes(n, h, w, 3, 444), L.fosvos_jpeg_workspace_bytes(n, h, w, 3, 444)
     assert cap == J.capacity(h, w, 3) and need == n * J.n_intervals(h, w) * 4
-    assert L.fosvos_jpeg_capacity_bytes(1, 1080, 1920, 3) == J.capacity(1080, 1920, 3)
-    assert L.fosvos_jpeg_capacity_bytes(1, 0, 5, 3) == 0 and L.fosvos_jpeg_capacity_bytes(1, 5, 5, 2) == 0
-    assert L.fosvos_jpeg_workspace_bytes(0, 5, 5, 1) == 0
+    assert L.fosvos_jpeg_capacity_bytes(1, 1080, 1920, 3, 444) == J.capacity(1080, 1920, 3)
+    assert L.fosvos_jpeg_capacity_bytes(1, 0, 5, 3, 444) == 0 and L.fosvos_jpeg_capacity_bytes(1, 5, 5, 2, 444) == 0
+    assert L.fosvos_jpeg_workspace_bytes(0, 5, 5, 1, 444) == 0
     x = torch.from_numpy(np.stack([C.picture(h, w)] * n)).to(DEV)
     out = torch.full((n, cap), FILL, dtype=torch.uint8, device=DEV)
     lengths = torch.full((n,), -1, dtype=torch.int32, device=DEV)
@@ -143,7 +143,7 @@ def test_bad_arguments_raise_and_launch_nothing():
     st = torch.cuda.current_stream().cuda_stream
 
     def call(b=x.data_ptr(), n_=n, h_=h, w_=w, c_=3, q=90, o=out.data_ptr(), c=cap, l=lengths.data_ptr(), w2=ws.data_ptr(), nb=need):
-        return L.fosvos_jpeg_encode(b, n_, h_, w_, c_, q, o, c, l, w2, nb, 0, st)
+        return L.fosvos_jpeg_encode(b, n_, h_, w_, c_, 444, q, o, c, l, w2, nb, 0, st)
 
     with LaunchProfile(0) as prof:
         assert call(nb=need - 1) == -3 and b"workspace" in L.fosvos_last_error()   # a short workspace

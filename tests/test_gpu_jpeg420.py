@@ -153,13 +153,13 @@ def test_bad_arguments_raise_and_launch_nothing():
     from fosvos_hip import LaunchProfile, lib, ops
     L = lib()
     n, h, w = 2, 24, 40
-    cap, need = L.fosvos_jpeg_capacity_bytes_sampled(n, h, w, 3, 420), L.fosvos_jpeg_workspace_bytes_sampled(n, h, w, 3, 420)
+    cap, need = L.fosvos_jpeg_capacity_bytes(n, h, w, 3, 420), L.fosvos_jpeg_workspace_bytes(n, h, w, 3, 420)
     assert cap == J.capacity(h, w, 3, S) and need == n * J.n_intervals(h, w, S) * 4
-    assert L.fosvos_jpeg_capacity_bytes_sampled(n, h, w, 3, 444) == L.fosvos_jpeg_capacity_bytes(n, h, w, 3)
-    assert L.fosvos_jpeg_workspace_bytes_sampled(n, h, w, 3, 444) == L.fosvos_jpeg_workspace_bytes(n, h, w, 3)
-    assert L.fosvos_jpeg_capacity_bytes_sampled(1, 1080, 1920, 3, 420) == J.capacity(1080, 1920, 3, S)
-    assert L.fosvos_jpeg_capacity_bytes_sampled(1, 8, 8, 3, 422) == 0 and L.fosvos_jpeg_workspace_bytes_sampled(1, 8, 8, 3, 0) == 0
-    assert L.fosvos_jpeg_capacity_bytes_sampled(1, 0, 8, 3, 420) == 0 and L.fosvos_jpeg_capacity_bytes_sampled(1, 8, 8, 2, 420) == 0
+    assert L.fosvos_jpeg_capacity_bytes(n, h, w, 3, 444) == J.capacity(h, w, 3, "4:4:4")
+    assert L.fosvos_jpeg_workspace_bytes(n, h, w, 3, 444) == J.n_intervals(h, w) * 4 * n
+    assert L.fosvos_jpeg_capacity_bytes(1, 1080, 1920, 3, 420) == J.capacity(1080, 1920, 3, S)
+    assert L.fosvos_jpeg_capacity_bytes(1, 8, 8, 3, 422) == 0 and L.fosvos_jpeg_workspace_bytes(1, 8, 8, 3, 0) == 0
+    assert L.fosvos_jpeg_capacity_bytes(1, 0, 8, 3, 420) == 0 and L.fosvos_jpeg_capacity_bytes(1, 8, 8, 2, 420) == 0
     x = torch.from_numpy(np.stack([C4.ramp(h, w)] * n)).to(DEV)
     out = torch.full((n, cap), FILL, dtype=torch.uint8, device=DEV)
     lengths = torch.full((n,), -1, dtype=torch.int32, device=DEV)
@@ -167,8 +167,7 @@ def test_bad_arguments_raise_and_launch_nothing():
     st = torch.cuda.current_stream().cuda_stream
 
     def call(s=420, q=90, c=cap, nb=need, c_=3):
-        return L.fosvos_jpeg_encode_sampled(x.data_ptr(), n, h, w, c_, s, q, out.data_ptr(), c, lengths.data_ptr(), ws.data_ptr(), nb,
-                                            0, st)
+        return L.fosvos_jpeg_encode(x.data_ptr(), n, h, w, c_, s, q, out.data_ptr(), c, lengths.data_ptr(), ws.data_ptr(), nb, 0, st)
 
     with LaunchProfile(0) as prof:
         assert call(s=422) == -2 and b"sampling" in L.fosvos_last_error()

@@ -600,7 +600,7 @@ def _head_ref(side, up, up1, dsn_w, dsn_b, fuse_w, fuse_b, H, W):
 
 @pytest.mark.parametrize("n,h,w,co", [(1, 48, 86, 64), (2, 61, 107, 128), (1, 30, 54, 512), (3, 480, 854, 64)])
 def test_relu_mask_as_bits(ops, n, h, w, co):
-    """conv1_1's forward can write the ReLU mask of its output as one bit per element (fosvos_conv3x3_first_fwd_bits), and the
+    """conv1_1's forward can write the ReLU mask of its output as one bit per element (fosvos_conv3x3_first_fwd), and the
     data gradient of the next conv can take its mask that way (fosvos_conv3x3_dgrad_bits: 8 instead of 128 bytes per pixel at
     64 channels - conv1_2's data gradient at 480x854 is bound by HBM traffic): the bits ARE (y > 0), and the data gradient is
     bit for bit the one computed from y itself - in the fused epilogue and in the split-K epilogue (the small shapes)."""

@@ -161,19 +161,23 @@ def test_png_encode_error_codes():
     from fosvos_hip import lib, ops
     L = lib()
     n, h, w = 2, 24, 40
-    cap, need = L.fosvos_png_capacity_bytes(n, h, w), L.fosvos_png_workspace_bytes(n, h, w)
+    cap, need = L.fosvos_png_capacity_bytes(n, h, w), L.fosvos_png_workspace_bytes(n, h, w, 0)
     assert cap == P.max_file_bytes(h, w) and need == n * P.n_segments(h, w) * 16
+    assert L.fosvos_png_workspace_bytes(n, h, w, 1) == n * P.n_segments(h, w) * (16 + 288)  # and a byte a symbol of 288
     assert L.fosvos_png_capacity_bytes(1, 480, 854) == P.max_file_bytes(480, 854)
-    assert L.fosvos_png_capacity_bytes(1, 0, 5) == 0 and L.fosvos_png_workspace_bytes(0, 5, 5) == 0
+    assert L.fosvos_png_capacity_bytes(1, 0, 5) == 0 and L.fosvos_png_workspace_bytes(0, 5, 5, 0) == 0
+    assert L.fosvos_png_workspace_bytes(0, 5, 5, 1) == 0
     x = torch.zeros((n, h, w), dtype=torch.uint8, device=DEV)
     out = torch.full((n, cap), FILL, dtype=torch.uint8, device=DEV)
     lengths = torch.full((n,), -1, dtype=torch.int32, device=DEV)
     ws = torch.full((need,), FILL, dtype=torch.uint8, device=DEV)
     st = torch.cuda.current_stream().cuda_stream
 
-    def call(b=x.data_ptr(), n_=n, h_=h, w_=w, o=out.data_ptr(), c=cap, l=lengths.data_ptr(), w2=ws.data_ptr(), nb=need):
-        return L.fosvos_png_encode(b, n_, h_, w_, o, c, l, w2, nb, 0, st)
+    def call(b=x.data_ptr(), n_=n, h_=h, w_=w, hf=0, o=out.data_ptr(), c=cap, l=lengths.data_ptr(), w2=ws.data_ptr(), nb=need):
+        return L.fosvos_png_encode(b, n_, h_, w_, hf, o, c, l, w2, nb, 0, st)
 
+    assert call(hf=2) == -2 and b"huffman" in L.fosvos_last_error() and call(hf=-1) == -2
+    assert call(hf=1) == -3 and b"workspace" in L.fosvos_last_error()   # the fitted form needs the larger workspace
     assert call(c=cap - 1) == -3 and b"capacity" in L.fosvos_last_error()
     assert call(nb=need - 1) == -3 and b"workspace" in L.fosvos_last_error()
     assert call(nb=0) == -3
