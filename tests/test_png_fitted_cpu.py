@@ -218,6 +218,7 @@ def test_fast_pass_host_path_writes_fitted_files(tmp_path):
 
     class Net:
         def forward(self, x):
+            x = x.cpu()  # test_fast moves the frame to the GPU where there is one; this net, and its logits, stay on the host
             g = torch.Generator().manual_seed(int(x.abs().sum() * 10) % 1000)
             base = (x[:, :1] - x[:, :1].flatten(1).median(dim=1).values.view(-1, 1, 1, 1)) * 4
             return [base + torch.randn(base.shape, generator=g)]
