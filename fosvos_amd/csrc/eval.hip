@@ -25,6 +25,17 @@
 //                  over the wave, the workgroup and - with integer atomics, so in any order - the frame.
 // After the pack pass everything works on data 32 times smaller than the logits (a 480x854 plane is 53 KB), which stays in L2;
 // LDS per workgroup: 2 * (16 + 2r) * 10 words + the span table = 5.6 KB at r = 8, 23.2 KB at r = 63.
+//
+// Several objects a sequence (util/object_merge.py states both in numpy):
+// fosvos_merge_objects, one launch:
+//   k_merge_objects   the K logit maps of the K per-object nets (pointers by value in the kernel's arguments) -> one label
+//                     byte a pixel: 0 where no logit is >= 0, else 1 + the lowest k holding the largest such logit.  A thread
+//                     takes 4 consecutive pixels (K float4 loads, one dword store) where size and alignment allow, else 1.
+//                     Memory-bound: 4K B read and 1 B written per pixel.
+// fosvos_jf_counts_labels, two launches:
+//   k_jf_pack_labels  a wave reads 64 predicted and 64 ground-truth label bytes; for k = 1..K __ballot(pred == k) and
+//                     __ballot(gt == k) are the words of object k's planes, laid out [N][K][H][Wp]: to k_jf_count, which runs
+//                     unchanged, these are N * K frames.  Its threads zero the 6 N K counters.
 #include "common.hpp"
 
 // the fp64 expressions are the host's, operation for operation
@@ -252,6 +263,88 @@ __global__ __launch_bounds__(kJfThreads) void k_jf_count(const u64 *__restrict__
     __syncthreads();
     if (threadIdx.x < 6 && s_cnt[threadIdx.x]) atomicAdd(&counts[blockIdx.z * 6 + threadIdx.x], s_cnt[threadIdx.x]);
 }
+
+// ------------------------------------------------------------------------------------------ several objects
+constexpr int kMaxObjects = FOSVOS_MAX_OBJECTS;
+struct ObjectLogits {
+    const float *p[kMaxObjects];
+};
+
+// the merge rule on one pixel, object k's logit v against the best so far (best = 0: none yet, bestv = -1): a NaN is never
+// valid, -0.0 is; a tie stays with the lower k
+__device__ __forceinline__ void merge_take(float v, uint32_t k, float &bestv, uint32_t &best) {
+    const bool take = v >= 0.f && v > bestv;
+    bestv = take ? v : bestv;
+    best = take ? k + 1u : best;
+}
+
+// grid (blocks, N).  vec: every map and the labels are 16-byte / 4-byte aligned and hw % 4 == 0
+__global__ __launch_bounds__(kEvalThreads) void k_merge_objects(const ObjectLogits maps, int K, int64_t hw, int vec,
+                                                                uint8_t *__restrict__ out) {
+    const int64_t frame = (int64_t)blockIdx.y * hw;
+    out += frame;
+    const int64_t t = (int64_t)blockIdx.x * kEvalThreads + threadIdx.x, nt = (int64_t)gridDim.x * kEvalThreads;
+    if (vec) {
+        uint32_t *__restrict__ o4 = reinterpret_cast<uint32_t *>(out);
+        for (int64_t i = t; i < (hw >> 2); i += nt) {
+            float bv[4] = {-1.f, -1.f, -1.f, -1.f};
+            uint32_t b[4] = {0u, 0u, 0u, 0u};
+            for (int k = 0; k < K; ++k) {
+                const float4 v = reinterpret_cast<const float4 *>(maps.p[k] + frame)[i];
+                merge_take(v.x, (uint32_t)k, bv[0], b[0]);
+                merge_take(v.y, (uint32_t)k, bv[1], b[1]);
+                merge_take(v.z, (uint32_t)k, bv[2], b[2]);
+                merge_take(v.w, (uint32_t)k, bv[3], b[3]);
+            }
+            o4[i] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        }
+    } else {
+        for (int64_t i = t; i < hw; i += nt) {
+            float bv = -1.f;
+            uint32_t b = 0u;
+            for (int k = 0; k < K; ++k) merge_take(maps.p[k][frame + i], (uint32_t)k, bv, b);
+            out[i] = (uint8_t)b;
+        }
+    }
+}
+
+// one wave packs kPackWordsPerWave consecutive words of the label maps into the planes of all K objects; lane k - 1 keeps
+// and writes object k's two words
+__global__ __launch_bounds__(kEvalThreads) void k_jf_pack_labels(const uint8_t *__restrict__ pred,
+                                                                 const uint8_t *__restrict__ gt, int H, int W, int Wp, int K,
+                                                                 int64_t n_words, u64 *__restrict__ plane_a,
+                                                                 u64 *__restrict__ plane_b, int32_t *__restrict__ counts,
+                                                                 int n_counts) {
+    const int64_t gtid = (int64_t)blockIdx.x * kEvalThreads + threadIdx.x;
+    for (int64_t i = gtid; i < n_counts; i += (int64_t)gridDim.x * kEvalThreads) counts[i] = 0;
+    const int lane = threadIdx.x & 63;
+    const int64_t w0 = (gtid >> 6) * kPackWordsPerWave;
+    uint8_t p[kPackWordsPerWave], g[kPackWordsPerWave];
+#pragma unroll
+    for (int j = 0; j < kPackWordsPerWave; ++j) {
+        const int64_t w = w0 + j, row = w / Wp;  // row counts through all frames
+        const int x = (int)(w - row * Wp) * 64 + lane;
+        const bool in = w < n_words && x < W;
+        p[j] = in ? pred[row * W + x] : (uint8_t)0;
+        g[j] = in ? gt[row * W + x] : (uint8_t)0;
+    }
+#pragma unroll
+    for (int j = 0; j < kPackWordsPerWave; ++j) {
+        u64 a = 0, b = 0;
+        for (int k = 1; k <= K; ++k) {
+            const u64 ak = __ballot(p[j] == k), bk = __ballot(g[j] == k);
+            a = lane == k - 1 ? ak : a;
+            b = lane == k - 1 ? bk : b;
+        }
+        const int64_t w = w0 + j, row = w / Wp, n = row / H;
+        if (lane < K && w < n_words) {
+            // word (y, c) of frame n -> plane n * K + lane
+            const int64_t at = ((n * K + lane) * H + (row - n * H)) * Wp + (w - row * Wp);
+            plane_a[at] = a;
+            plane_b[at] = b;
+        }
+    }
+}
 }  // namespace
 
 extern "C" int fosvos_prob_bytes(const float *logits, int N, int H, int W, float *minmax, uint8_t *out, int device,
@@ -307,6 +400,64 @@ extern "C" int fosvos_jf_counts(const float *logits, const uint8_t *gt, int N, i
     FOSVOS_LAUNCH_CHECK();
     FOSVOS_PROF("k_jf_count", stream, 0.0);
     hipLaunchKernelGGL(k_jf_count, dim3((unsigned)cdiv(Wp, kJfTileWords), (unsigned)cdiv(H, kJfTileRows), (unsigned)N),
+                       dim3(kJfThreads), jf_lds_bytes(radius), st, plane_a, plane_b, H, W, Wp, radius, counts);
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" int fosvos_merge_objects(const float *const *logits, int K, int N, int H, int W, uint8_t *labels, int device,
+                                    void *stream) {
+    FOSVOS_REQUIRE(K >= 1 && K <= kMaxObjects, FOSVOS_E_ARG, "merge_objects: K=%d outside [1, %d]", K, kMaxObjects);
+    FOSVOS_REQUIRE(logits && labels, FOSVOS_E_ARG, "merge_objects: null pointer");
+    FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, FOSVOS_E_SHAPE, "merge_objects: N=%d (<= 65535) H=%d W=%d", N, H, W);
+    ObjectLogits maps = {};
+    uintptr_t align = (uintptr_t)labels & 3;
+    for (int k = 0; k < K; ++k) {
+        FOSVOS_REQUIRE(logits[k] != nullptr, FOSVOS_E_ARG, "merge_objects: null logit map %d", k);
+        maps.p[k] = logits[k];
+        align |= (uintptr_t)logits[k] & 15;
+    }
+    FOSVOS_ENTER(device);
+    const int64_t hw = (int64_t)H * W;
+    const int vec = (hw % 4 == 0) && align == 0;
+    const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(vec ? hw / 4 : hw, kEvalThreads), 2048);
+    FOSVOS_PROF("k_merge_objects", stream, 0.0);
+    hipLaunchKernelGGL(k_merge_objects, dim3(blocks, (unsigned)N), dim3(kEvalThreads), 0, (hipStream_t)stream, maps, K, hw, vec,
+                       labels);
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" size_t fosvos_jf_labels_workspace_bytes(int N, int K, int H, int W) {
+    if (N <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)2 * N * K * H * jf_words(W) * sizeof(u64);
+}
+
+extern "C" int fosvos_jf_counts_labels(const uint8_t *pred, const uint8_t *gt, int N, int K, int H, int W, int radius,
+                                       int32_t *counts, void *workspace, size_t workspace_bytes, int device, void *stream) {
+    FOSVOS_REQUIRE(pred && gt && counts && workspace, FOSVOS_E_ARG, "jf_counts_labels: null pointer");
+    FOSVOS_REQUIRE(K >= 1 && K <= kMaxObjects, FOSVOS_E_ARG, "jf_counts_labels: K=%d outside [1, %d]", K, kMaxObjects);
+    FOSVOS_REQUIRE(N > 0 && (int64_t)N * K <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX &&
+                       cdiv(H, kJfTileRows) <= 65535 && (int64_t)N * K * H * W <= ((int64_t)1 << 40),
+                   FOSVOS_E_SHAPE, "jf_counts_labels: N=%d K=%d (N K <= 65535) H=%d W=%d", N, K, H, W);
+    FOSVOS_REQUIRE(radius >= 1 && radius <= kMaxRadius, FOSVOS_E_ARG, "jf_counts_labels: radius %d outside [1, %d]", radius,
+                   kMaxRadius);
+    FOSVOS_REQUIRE(((uintptr_t)workspace & 7) == 0, FOSVOS_E_ARG, "jf_counts_labels: the workspace must be 8-byte aligned");
+    const size_t need = fosvos_jf_labels_workspace_bytes(N, K, H, W);
+    FOSVOS_REQUIRE(workspace_bytes >= need, FOSVOS_E_WORKSPACE, "jf_counts_labels: workspace %zu B < %zu B", workspace_bytes,
+                   need);
+    FOSVOS_ENTER(device);
+    const int Wp = jf_words(W);
+    const int64_t n_words = (int64_t)N * H * Wp;  // of one label map
+    u64 *plane_a = reinterpret_cast<u64 *>(workspace), *plane_b = plane_a + n_words * K;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t pack_blocks = cdiv(n_words, (kEvalThreads / 64) * kPackWordsPerWave);
+    FOSVOS_PROF("k_jf_pack_labels", stream, 0.0);
+    hipLaunchKernelGGL(k_jf_pack_labels, dim3((unsigned)pack_blocks), dim3(kEvalThreads), 0, st, pred, gt, H, W, Wp, K, n_words,
+                       plane_a, plane_b, counts, 6 * N * K);
+    FOSVOS_LAUNCH_CHECK();
+    FOSVOS_PROF("k_jf_count", stream, 0.0);
+    hipLaunchKernelGGL(k_jf_count, dim3((unsigned)cdiv(Wp, kJfTileWords), (unsigned)cdiv(H, kJfTileRows), (unsigned)(N * K)),
                        dim3(kJfThreads), jf_lds_bytes(radius), st, plane_a, plane_b, H, W, Wp, radius, counts);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;

@@ -30,6 +30,11 @@
 //   emit     canonical codes from the lengths (a ballot per code length gives a symbol's rank among its equals), the
 //            header, the code-length sequence (zero runs from a 320-bit mask of the non-zero lengths), the tokens
 //            recoded, the end-of-block code; chunk length, CRC and copy-out as for the other forms
+//
+// fosvos_png_encode_indexed: the same two kernels write the label maps of a multi-object pass as palette files.  k_png_emit takes
+// the form of the file's head as a parameter (PngHead): IHDR colour type 3 instead of 0 and, between IHDR and the first IDAT,
+// one PLTE chunk of 256 entries whose CRC-32 the frame's last workgroup computes like a segment's; every chunk behind it
+// starts 780 bytes later.  fosvos_png_encode passes {0, 33, no palette}: its files are what they were.
 #include "common.hpp"
 
 using namespace fosvos;
@@ -81,6 +86,14 @@ __device__ __forceinline__ uint32_t gf_pow8(uint32_t n, const uint32_t *x8) {
 __device__ __forceinline__ uint32_t crc_step(uint32_t c, uint32_t byte, const uint32_t *tab) {
     return tab[(c ^ byte) & 255u] ^ (c >> 8);
 }
+
+// The form of a file's head: the IHDR colour type, the bytes in front of the first IDAT chunk (signature 8 + IHDR 25, and for
+// an indexed file the PLTE chunk of 12 + 768) and the 256 RGB entries of that chunk (null: no PLTE).
+struct PngHead {
+    uint32_t color_type, first_idat;
+    const uint8_t *palette;
+};
+constexpr uint32_t kHeadBytes = 33u, kPlteData = 768u, kPlteChunk = 12u + kPlteData;
 
 struct PngShared {
     __attribute__((aligned(16))) uint8_t seg[kSeg];
@@ -437,8 +450,9 @@ __device__ __forceinline__ void put_be32(uint8_t *p, uint32_t v) {
 
 // The parts of a file that belong to no segment, by one workgroup per frame (block n_seg of k_png_emit's grid): signature and
 // IHDR; behind the last segment's chunk the final IDAT with the Adler-32 combined over all segments, IEND; the length.
-__device__ __forceinline__ void png_frame_ends(PngShared &sh, int H, int W, const uint32_t *__restrict__ ws, uint32_t n_seg,
-                                               uint8_t *__restrict__ out, int32_t *__restrict__ length) {
+__device__ __forceinline__ void png_frame_ends(PngShared &sh, int H, int W, const PngHead head,
+                                               const uint32_t *__restrict__ ws, uint32_t n_seg, uint8_t *__restrict__ out,
+                                               int32_t *__restrict__ length) {
     const int tid = threadIdx.x;
     const uint32_t n_total = (uint32_t)H * ((uint32_t)W + 1u);
     // A = 1 + sum a_s;  B = n_total + sum (b_s + a_s * bytes behind segment s)      (mod 65521)
@@ -452,7 +466,27 @@ __device__ __forceinline__ void png_frame_ends(PngShared &sh, int H, int W, cons
     }
     sa = block_sum(sa, sh.wave);  // 256 terms below 65521 each
     sb = block_sum(sb, sh.wave);
-    const uint32_t end = 33u + block_sum(bytes, sh.wave);  // where the last segment's chunk ends
+    const uint32_t end = head.first_idat + block_sum(bytes, sh.wave);  // where the last segment's chunk ends
+    if (head.palette) {
+        // PLTE behind IHDR: length, tag, the 768 palette bytes, and the CRC-32 of tag + bytes from per-thread slices of 4
+        // bytes, each moved to its place by x^(8 * bytes behind it), as for the segments' chunks
+        const uint32_t L = 4u + kPlteData, lo = min(L, (uint32_t)tid * 4u), hi = min(L, lo + 4u);
+        uint32_t raw = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t byte = i < 4u ? (0x45544c50u >> (8u * i)) & 255u : head.palette[i - 4u];  // 'P' 'L' 'T' 'E'
+            raw = crc_step(raw, byte, sh.crc_tab);
+        }
+        uint32_t part = hi > lo ? gf_mul(gf_pow8(L - hi, sh.x8), raw) : 0u;
+        if (tid == 0) part ^= gf_mul(gf_pow8(L, sh.x8), 0xffffffffu);
+        const uint32_t crc = block_xor(part, sh.wave) ^ 0xffffffffu;
+        uint8_t *plte = out + kHeadBytes;
+        if (tid == 0) {
+            put_be32(plte, kPlteData);
+            plte[4] = 'P', plte[5] = 'L', plte[6] = 'T', plte[7] = 'E';
+            put_be32(plte + 8 + kPlteData, crc);
+        }
+        for (uint32_t i = tid; i < kPlteData; i += kPngThreads) plte[8 + i] = head.palette[i];
+    }
     if (tid == 0) {
         uint8_t *h = sh.small;
         const uint32_t sig0 = 0x474e5089u, sig1 = 0x0a1a0a0du;  // 89 'P' 'N' 'G' \r \n 1a \n
@@ -461,7 +495,7 @@ __device__ __forceinline__ void png_frame_ends(PngShared &sh, int H, int W, cons
         h[12] = 'I', h[13] = 'H', h[14] = 'D', h[15] = 'R';
         put_be32(h + 16, (uint32_t)W);
         put_be32(h + 20, (uint32_t)H);
-        h[24] = 8, h[25] = 0, h[26] = 0, h[27] = 0, h[28] = 0;
+        h[24] = 8, h[25] = (uint8_t)head.color_type, h[26] = 0, h[27] = 0, h[28] = 0;
         uint32_t c = 0xffffffffu;
         for (int i = 12; i < 29; ++i) c = crc_step(c, h[i], sh.crc_tab);
         put_be32(h + 29, c ^ 0xffffffffu);
@@ -487,7 +521,7 @@ __device__ __forceinline__ void png_frame_ends(PngShared &sh, int H, int W, cons
 
 // grid (segments + 1, N)
 template <bool kFitted>
-__global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restrict__ img, int H, int W,
+__global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restrict__ img, int H, int W, const PngHead head,
                                                          const uint32_t *__restrict__ ws, uint8_t *__restrict__ out,
                                                          int64_t capacity, int32_t *__restrict__ lengths) {
     __shared__ PngShared sh;
@@ -514,13 +548,13 @@ __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restr
     }
     if (seg == n_seg) {
         __syncthreads();
-        png_frame_ends(sh, H, W, ws, n_seg, out, lengths + blockIdx.y);
+        png_frame_ends(sh, H, W, head, ws, n_seg, out, lengths + blockIdx.y);
         return;
     }
-    // where this chunk starts: signature + IHDR, then the chunks of the segments in front
+    // where this chunk starts: the file's head, then the chunks of the segments in front
     uint32_t before = 0;
     for (uint32_t s = tid; s < seg; s += kPngThreads) before += 12u + (ws[(size_t)s * kWsWords] & ~kStoredFlag);
-    const uint32_t offset = 33u + block_sum(before, sh.wave);
+    const uint32_t offset = head.first_idat + block_sum(before, sh.wave);
     const uint32_t rec0 = ws[(size_t)seg * kWsWords];
     const bool stored = (rec0 & kStoredFlag) != 0;
     const uint32_t dlen = rec0 & ~kStoredFlag, zhdr = seg == 0 ? 2u : 0u;
@@ -638,16 +672,16 @@ __global__ __launch_bounds__(kPngThreads) void k_png_emit(const uint8_t *__restr
 }
 
 template <bool kFitted>
-int png_launch(const uint8_t *bytes, int N, int H, int W, uint8_t *out, size_t capacity, int32_t *lengths, uint32_t *ws,
-               void *stream) {
+int png_launch(const uint8_t *bytes, int N, int H, int W, const PngHead head, uint8_t *out, size_t capacity, int32_t *lengths,
+               uint32_t *ws, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)png_segments(H, W), (unsigned)N);
     FOSVOS_PROF(kFitted ? "k_png_measure_fitted" : "k_png_measure", stream, 0.0);
     hipLaunchKernelGGL(k_png_measure<kFitted>, grid, dim3(kPngThreads), 0, st, bytes, H, W, ws);
     FOSVOS_LAUNCH_CHECK();
     FOSVOS_PROF(kFitted ? "k_png_emit_fitted" : "k_png_emit", stream, 0.0);
-    hipLaunchKernelGGL(k_png_emit<kFitted>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, ws, out,
-                       (int64_t)capacity, lengths);
+    hipLaunchKernelGGL(k_png_emit<kFitted>, dim3(grid.x + 1, grid.y), dim3(kPngThreads), 0, st, bytes, H, W, head, ws,
+                       out, (int64_t)capacity, lengths);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
@@ -663,21 +697,43 @@ extern "C" size_t fosvos_png_workspace_bytes(int N, int H, int W, int huffman) {
     return (size_t)N * (size_t)png_segments(H, W) * (kWsWords + (huffman ? kLenWords : 0)) * sizeof(uint32_t);
 }
 
-extern "C" int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
-                                 int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
-    FOSVOS_REQUIRE(huffman == 0 || huffman == 1, FOSVOS_E_ARG, "png_encode: huffman=%d (0 fixed, 1 fitted)", huffman);
+// both file encoders: the greyscale one (no palette) and the indexed one
+static int png_encode_any(const char *who, const uint8_t *bytes, int N, int H, int W, int huffman, const uint8_t *palette,
+                          uint8_t *out, size_t capacity, int32_t *lengths, void *workspace, size_t workspace_bytes, int device,
+                          void *stream) {
+    FOSVOS_REQUIRE(huffman == 0 || huffman == 1, FOSVOS_E_ARG, "%s: huffman=%d (0 fixed, 1 fitted)", who, huffman);
     FOSVOS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && png_stream_bytes(H, W) <= ((int64_t)1 << 30), FOSVOS_E_SHAPE,
-                   "png_encode: N=%d (<= 65535) H=%d W=%d (H * (W + 1) <= 2^30)", N, H, W);
-    FOSVOS_REQUIRE(bytes && out && lengths && workspace, FOSVOS_E_ARG, "png_encode: null pointer");
+                   "%s: N=%d (<= 65535) H=%d W=%d (H * (W + 1) <= 2^30)", who, N, H, W);
+    FOSVOS_REQUIRE(bytes && out && lengths && workspace, FOSVOS_E_ARG, "%s: null pointer", who);
     FOSVOS_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)lengths & 3) == 0, FOSVOS_E_ARG,
-                   "png_encode: the workspace and the lengths must be 4-byte aligned");
-    const size_t need_cap = fosvos_png_capacity_bytes(N, H, W), need_ws = fosvos_png_workspace_bytes(N, H, W, huffman);
-    FOSVOS_REQUIRE(capacity >= need_cap, FOSVOS_E_WORKSPACE, "png_encode: capacity %zu B a frame < %zu B", capacity, need_cap);
-    FOSVOS_REQUIRE(workspace_bytes >= need_ws, FOSVOS_E_WORKSPACE, "png_encode: workspace %zu B < %zu B", workspace_bytes,
-                   need_ws);
+                   "%s: the workspace and the lengths must be 4-byte aligned", who);
+    const size_t need_cap = fosvos_png_capacity_bytes(N, H, W) + (palette ? kPlteChunk : 0u);
+    const size_t need_ws = fosvos_png_workspace_bytes(N, H, W, huffman);
+    FOSVOS_REQUIRE(capacity >= need_cap, FOSVOS_E_WORKSPACE, "%s: capacity %zu B a frame < %zu B", who, capacity, need_cap);
+    FOSVOS_REQUIRE(workspace_bytes >= need_ws, FOSVOS_E_WORKSPACE, "%s: workspace %zu B < %zu B", who, workspace_bytes, need_ws);
     FOSVOS_ENTER(device);
     uint32_t *ws = reinterpret_cast<uint32_t *>(workspace);
+    const PngHead head = {palette ? 3u : 0u, kHeadBytes + (palette ? kPlteChunk : 0u), palette};
     // (<false> named first: the fixed kernels stay in front of the fitted ones in the code object)
-    return huffman == 0 ? png_launch<false>(bytes, N, H, W, out, capacity, lengths, ws, stream)
-                        : png_launch<true>(bytes, N, H, W, out, capacity, lengths, ws, stream);
+    return huffman == 0 ? png_launch<false>(bytes, N, H, W, head, out, capacity, lengths, ws, stream)
+                        : png_launch<true>(bytes, N, H, W, head, out, capacity, lengths, ws, stream);
+}
+
+extern "C" int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity,
+                                 int32_t *lengths, void *workspace, size_t workspace_bytes, int device, void *stream) {
+    return png_encode_any("png_encode", bytes, N, H, W, huffman, nullptr, out, capacity, lengths, workspace, workspace_bytes,
+                          device, stream);
+}
+
+extern "C" size_t fosvos_png_indexed_capacity_bytes(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)png_file_bound(H, W) + kPlteChunk;
+}
+
+extern "C" int fosvos_png_encode_indexed(const uint8_t *labels, const uint8_t *palette, int N, int H, int W, int huffman,
+                                         uint8_t *out, size_t capacity, int32_t *lengths, void *workspace,
+                                         size_t workspace_bytes, int device, void *stream) {
+    FOSVOS_REQUIRE(palette != nullptr, FOSVOS_E_ARG, "png_encode_indexed: null palette");
+    return png_encode_any("png_encode_indexed", labels, N, H, W, huffman, palette, out, capacity, lengths, workspace,
+                          workspace_bytes, device, stream);
 }

@@ -1205,6 +1205,148 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengt
     return out, lengths
 
 
+# ------------------------------------------------------------------------------------------ several objects (eval.hip, png.hip)
+MAX_OBJECTS = 16
+_PALETTES = {}  # device -> the default palette (util/object_merge.davis_palette) on it
+
+
+def _same_device(what: str, first: torch.Tensor, *others: torch.Tensor) -> None:
+    for t in others:
+        if t.device != first.device:
+            raise RuntimeError(f"{what}: every tensor must be on {first.device}, got one on {t.device}")
+
+
+def merge_objects(logits: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_merge_objects: the logits fp32 [N,1,H,W] of K per-object nets (1 <= K <= 16) -> labels uint8 [N,H,W]: 0 where
+    no logit of the pixel is >= 0, else 1 + the lowest k holding the largest such logit (util/object_merge.merge_labels).
+    The K pointers travel by value: nothing is concatenated.  ``out`` may be a view of a caller's buffer.  Launched on the
+    current stream, no synchronisation."""
+    logits = list(logits)
+    k = len(logits)
+    if not 1 <= k <= MAX_OBJECTS:
+        raise ValueError(f"merge_objects: {k} logit maps, outside [1, {MAX_OBJECTS}]")
+    for t in logits:
+        _need_eval(t, _F32, "merge_objects logits")
+    n, h, w = _logit_shape(logits[0], "merge_objects")
+    for t in logits[1:]:
+        if tuple(t.shape) != (n, 1, h, w):
+            raise ValueError(f"merge_objects: every logit map must be {(n, 1, h, w)}, got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=logits[0].device)
+    else:
+        _need_eval(out, torch.uint8, "merge_objects out")
+        if tuple(out.shape) != (n, h, w):
+            raise ValueError(f"merge_objects: out must be {(n, h, w)}, got {tuple(out.shape)}")
+    _same_device("merge_objects", logits[0], out, *logits[1:])
+    import ctypes
+    table = (ctypes.c_void_p * k)(*[t.data_ptr() for t in logits])
+    dev, st = _ctx(logits[0])
+    e0 = _pb()
+    check(lib().fosvos_merge_objects(table, k, n, h, w, out.data_ptr(), dev, st), "merge_objects")
+    _pe(e0, "merge_objects", 0.0, (4.0 * k + 1.0) * n * h * w)
+    return out
+
+
+def jf_counts_labels(pred_labels: torch.Tensor, gt_labels: torch.Tensor, n_objects: int, radius: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_jf_counts_labels: two label maps uint8 [N,H,W] -> int32 [N,K,6]: row (n, k-1) holds the six counts of
+    ``jf_counts`` for the masks ``pred == k`` and ``gt == k`` (util/object_merge.jf_counts_labels_numpy); labels above
+    ``n_objects`` belong to no object.  ``radius`` (1..63) defaults to ceil(0.008 * diagonal).  ``out`` may be any [N,K,6]
+    int32 rows, e.g. a slice of a sequence's counter tensor; the op zeroes them itself.  Launched on the current stream, no
+    synchronisation."""
+    _need_eval(pred_labels, torch.uint8, "jf_counts_labels pred")
+    _need_eval(gt_labels, torch.uint8, "jf_counts_labels gt")
+    if pred_labels.dim() != 3 or pred_labels.numel() == 0:
+        raise ValueError(f"jf_counts_labels: labels must be a non-empty [N,H,W], got {tuple(pred_labels.shape)}")
+    n, h, w = (int(v) for v in pred_labels.shape)
+    if tuple(gt_labels.shape) != (n, h, w):
+        raise ValueError(f"jf_counts_labels: gt must be {(n, h, w)}, got {tuple(gt_labels.shape)}")
+    k = int(n_objects)
+    if not 1 <= k <= MAX_OBJECTS:
+        raise ValueError(f"jf_counts_labels: n_objects {k} outside [1, {MAX_OBJECTS}]")
+    if radius is None:
+        radius = jf_default_radius(h, w)
+    radius = int(radius)
+    if not 1 <= radius <= 63:
+        raise ValueError(f"jf_counts_labels: radius {radius} outside [1, 63]")
+    if out is None:
+        out = torch.empty((n, k, 6), dtype=torch.int32, device=pred_labels.device)
+    else:
+        _need_eval(out, torch.int32, "jf_counts_labels out")
+        if tuple(out.shape) != (n, k, 6):
+            raise ValueError(f"jf_counts_labels: out must be {(n, k, 6)}, got {tuple(out.shape)}")
+    _same_device("jf_counts_labels", pred_labels, gt_labels, out)
+    L = lib()
+    ws, wsn = _WS.get(L.fosvos_jf_labels_workspace_bytes(n, k, h, w), pred_labels.device)
+    dev, st = _ctx(pred_labels)
+    e0 = _pb()
+    check(L.fosvos_jf_counts_labels(pred_labels.data_ptr(), gt_labels.data_ptr(), n, k, h, w, radius, out.data_ptr(), ws, wsn,
+                                    dev, st), "jf_counts_labels")
+    _pe(e0, "jf_counts_labels", 0.0, 2.0 * n * h * w)
+    return out
+
+
+def png_indexed_capacity(h: int, w: int) -> int:
+    """Bytes ``png_encode_indexed`` reserves per frame (util/png_layout.max_file_bytes_indexed)."""
+    return int(lib().fosvos_png_indexed_capacity_bytes(1, int(h), int(w)))
+
+
+def default_palette(device) -> torch.Tensor:
+    """``object_merge.davis_palette()`` as a uint8 [256,3] tensor on ``device``, uploaded once per device."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f"default_palette: a GPU device, got {device} (the HIP path has no CPU fallback)")
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    pal = _PALETTES.get(key)
+    if pal is None:
+        from util.object_merge import davis_palette
+        pal = _PALETTES[key] = torch.from_numpy(davis_palette()).to(device)
+    return pal
+
+
+def png_encode_indexed(labels_u8: torch.Tensor, palette: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                       lengths: Optional[torch.Tensor] = None, huffman: str = 'fixed') -> Tuple[torch.Tensor, torch.Tensor]:
+    """fosvos_png_encode_indexed: labels uint8 [N,H,W] -> (buffer uint8 [N,capacity], lengths int32 [N]): frame n's 8-bit
+    palette PNG file is ``buffer[n, :lengths[n]]``, ``png_layout.encode_indexed(labels[n], palette, huffman)`` byte for byte.
+    ``palette``: uint8 [256,3] RGB on the device; None = the DAVIS palette (``default_palette``).  ``out`` (uint8
+    [N, >= png_indexed_capacity(H, W)]) and ``lengths`` (int32 [N]) may be views of a caller's buffer.  Launched on the
+    current stream, no synchronisation."""
+    if huffman not in PNG_HUFFMAN:
+        raise ValueError(f"png_encode_indexed: huffman must be one of {tuple(PNG_HUFFMAN)}, got {huffman!r}")
+    _need_eval(labels_u8, torch.uint8, "png_encode_indexed labels")
+    if labels_u8.dim() != 3 or labels_u8.numel() == 0:
+        raise ValueError(f"png_encode_indexed: labels must be a non-empty [N,H,W], got {tuple(labels_u8.shape)}")
+    n, h, w = (int(v) for v in labels_u8.shape)
+    if palette is None:
+        palette = default_palette(labels_u8.device)
+    _need_eval(palette, torch.uint8, "png_encode_indexed palette")
+    if tuple(palette.shape) != (256, 3):
+        raise ValueError(f"png_encode_indexed: palette must be (256, 3), got {tuple(palette.shape)}")
+    L = lib()
+    cap = int(L.fosvos_png_indexed_capacity_bytes(n, h, w))
+    if out is None:
+        out = torch.empty((n, cap), dtype=torch.uint8, device=labels_u8.device)
+    else:
+        _need_eval(out, torch.uint8, "png_encode_indexed out")
+        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cap:
+            raise ValueError(f"png_encode_indexed: out must be [{n}, >= {cap}], got {tuple(out.shape)}")
+    if lengths is None:
+        lengths = torch.empty((n,), dtype=torch.int32, device=labels_u8.device)
+    else:
+        _need_eval(lengths, torch.int32, "png_encode_indexed lengths")
+        if tuple(lengths.shape) != (n,):
+            raise ValueError(f"png_encode_indexed: lengths must be {(n,)}, got {tuple(lengths.shape)}")
+    _same_device("png_encode_indexed", labels_u8, palette, out, lengths)
+    mode = PNG_HUFFMAN[huffman]
+    ws, wsn = _WS.get(L.fosvos_png_workspace_bytes(n, h, w, mode), labels_u8.device)
+    dev, st = _ctx(labels_u8)
+    e0 = _pb()
+    check(L.fosvos_png_encode_indexed(labels_u8.data_ptr(), palette.data_ptr(), n, h, w, mode, out.data_ptr(),
+                                      int(out.shape[1]), lengths.data_ptr(), ws, wsn, dev, st), "png_encode_indexed")
+    _pe(e0, "png_encode_indexed", 0.0, 2.0 * n * h * w)
+    return out, lengths
+
+
 # ------------------------------------------------------------------------------------------ JPEG files (jpeg.hip)
 JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
 

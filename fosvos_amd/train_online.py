@@ -9,6 +9,7 @@ reference's logging points, so the loop does not synchronise every iteration.
 
 Run:  python train_online.py --synthetic --n-epochs 100        (one GPU)
       torchrun --nproc-per-node 8 train_online.py --synthetic --data-parallel --avg-grad-every-n 8
+      python train_online.py --synthetic --multi-object --objects 3 --score   (one net per object: train_and_test_objects)
 """
 import timeit
 from pathlib import Path
@@ -41,6 +42,8 @@ score = False               # --score: the test pass computes J and F on the dev
 fast_test = False           # --fast-test: grouped forward passes, PNG files encoded on the device (experiment_helper.test_fast)
 png_fitted = False          # --png-fitted (with --fast-test): Huffman codes fitted to each segment of the PNG files
 device_decode = False       # --device-decode: the test pass's JPEG frames are decoded on the device (dataloaders/device_decode.py)
+multi_object = False        # --multi-object: one net per object, merged and scored on the device (train_and_test_objects)
+synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
 
 sequences_val = ['blackswan', 'bmx-trees', 'breakdance', 'camel', 'car-roundabout', 'car-shadow', 'cows',
@@ -91,6 +94,71 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
             return
         experiment_helper.test(net_provider, data_loader, save_dir, settings.is_visualizing_results,
                                settings.eval_speeds, seq_name=seq_name)
+
+
+def _object_loaders(seq_name: str, object_id: int, settings: OnlineSettings, n_objects: int):
+    """(train loader, test loader or None, annotations) of one object of a multi-object sequence."""
+    if synthetic_size is not None:
+        from dataloaders.synthetic import SyntheticObjectsSequence
+        from torch.utils.data import DataLoader
+        h, w = synthetic_size
+        train = DataLoader(SyntheticObjectsSequence(seq_name, h, w, n_frames=1, n_objects=n_objects, object_id=object_id),
+                           batch_size=settings.batch_size_train, shuffle=True, num_workers=0)
+        test = DataLoader(SyntheticObjectsSequence(seq_name, h, w, n_frames=4, n_objects=n_objects),
+                          batch_size=settings.batch_size_test, shuffle=False, num_workers=0)
+        return train, test, test.dataset.annotation
+    from dataloaders import custom_transforms
+    from dataloaders.davis_2017 import DAVIS2017, Davis2017Annotations
+    from dataloaders.resident import ResidentOneShotLoader
+    from torch.utils.data import DataLoader
+    train = ResidentOneShotLoader(DAVIS2017(mode='train', db_root_dir=str(db_root_dir), seq_name=seq_name,
+                                            object_id=object_id, transform=None))
+    test = DataLoader(DAVIS2017(mode='test', db_root_dir=str(db_root_dir), seq_name=seq_name, object_id=object_id,
+                                transform=custom_transforms.ToTensor()),
+                      batch_size=settings.batch_size_test, shuffle=False, num_workers=2)
+    return train, test, Davis2017Annotations(db_root_dir)
+
+
+def train_and_test_objects(make_provider, seq_name: str, settings: OnlineSettings) -> Optional[dict]:
+    """A sequence of K objects: for k = 1..K a fresh provider (``make_provider()``) loads the parent weights and `_train`
+    fine-tunes it on object k against everything else, snapshots named ``<seq>_<k>`` through the provider's ``sequence``
+    argument; the K nets stay on the device and ``experiment_helper.test_objects`` runs them all on every frame.  The train
+    loop itself is `_train`, untouched."""
+    if synthetic_size is not None:
+        n_objects = synthetic_objects
+    else:
+        from dataloaders.davis_2017 import n_objects as count_objects
+        n_objects = count_objects(db_root_dir, seq_name)
+    if not 1 <= n_objects <= 16:
+        raise SystemExit('sequence {}: {} objects, outside [1, 16]'.format(seq_name, n_objects))
+    summary_writer = _get_summary_writer(path_stem)
+    providers, test_loader, annotations = [], None, None
+    for k in range(1, n_objects + 1):
+        provider = make_provider()
+        io_helper.write_settings(save_dir_models, provider.name, settings, variant_offline=settings.variant_offline,
+                                 variant_online=settings.variant_online)
+        train_loader, test_loader, annotations = _object_loaders(seq_name, k, settings, n_objects)
+        name_k = '{0}_{1}'.format(seq_name, k)
+        if settings.is_training:
+            provider.load_network_train()
+            _train(provider, train_loader, provider.get_optimizer(), summary_writer, name_k, settings.start_epoch,
+                   settings.n_epochs, settings.avg_grad_every_n, settings.snapshot_every_n)
+        elif settings.is_testing:
+            provider.load_network_test(sequence=name_k)
+        providers.append(provider)
+    if not settings.is_testing:
+        return None
+    if settings.variant_offline is None:
+        save_dir = save_dir_results / providers[0].name / 'online'
+    else:
+        save_dir = save_dir_results / providers[0].name / str(settings.variant_offline) / str(settings.variant_online)
+    result = experiment_helper.test_objects(providers, test_loader, save_dir, annotations if score else None,
+                                            seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
+    if result is not None:
+        log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
+        experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
+        scored_sequences.append(result)
+    return result
 
 
 def _losses_per_frame(fused, gts, backward_seed=None, staged=None):
@@ -474,6 +542,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
+    global multi_object, synthetic_objects
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -483,6 +552,8 @@ def main(argv=None):
     fast_test = bool(args.fast_test)
     png_fitted = bool(args.png_fitted)
     device_decode = bool(args.device_decode)
+    multi_object = bool(args.multi_object)
+    synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')
@@ -505,9 +576,12 @@ def main(argv=None):
                               variant_online=args.variant_online, eval_speeds=args.eval_speeds)
 
     provider_class = provider_mapping[('online', args.network)]
-    net_provider = provider_class(name=args.network, save_dir=(path_input_model, path_output_model_base),
-                                  settings=settings, variant_offline=args.variant_offline,
-                                  variant_online=args.variant_online)
+
+    def make_provider():
+        return provider_class(name=args.network, save_dir=(path_input_model, path_output_model_base), settings=settings,
+                              variant_offline=args.variant_offline, variant_online=args.variant_online)
+
+    net_provider = make_provider()
     if args.synthetic and not path_input_model.exists():
         # no parent checkpoint offline: write a seeded random-init one so the load path is exercised
         from networks.osvos_vgg import OSVOS_VGG
@@ -518,6 +592,25 @@ def main(argv=None):
         if data_parallel:
             torch.distributed.barrier()
 
+    if multi_object:
+        if args.sequence_name is not None:
+            sequences = [args.sequence_name]
+        elif args.synthetic:
+            sequences = ['synthetic']
+        else:
+            from dataloaders.davis_2017 import sequence_names
+            sequences = parallel.shard_sequences(sequence_names(db_root_dir, 'val'), args.sequence_group,
+                                                 args.sequence_group_size)
+        for s in sequences:
+            train_and_test_objects(make_provider, s, settings)
+        if score and scored_sequences:
+            # the run's mean is over OBJECTS: every object of every sequence counts once
+            objects = [o for r in scored_sequences for o in r['objects']]
+            j_mean = sum(o['J_stats']['mean'] for o in objects) / len(objects)
+            f_mean = sum(o['F_stats']['mean'] for o in objects) / len(objects)
+            log.info('Score over {0} objects of {1} sequences: J mean {2:.4f}, F mean {3:.4f}, J&F {4:.4f}'.format(
+                len(objects), len(scored_sequences), j_mean, f_mean, (j_mean + f_mean) / 2))
+        return
     if args.sequence_name is None:
         # replicas: the reference's -sg/-sgs sharding; under torchrun without --data-parallel the ranks shard
         group, group_size = args.sequence_group, args.sequence_group_size

@@ -3,7 +3,8 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test, --png-fitted and --device-decode (online only).
+--data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
+--multi-object and --objects (online only).
 """
 import argparse
 from typing import List, Optional
@@ -51,6 +52,12 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--device-decode', action='store_true',
                             help='decode the test pass\'s JPEG frames on the device (same tensors; files the device decoder '
                                  'does not take go through PIL as before)')
+        parser.add_argument('--multi-object', action='store_true',
+                            help='several objects a sequence (a DAVIS 2017 tree): one net per object, fine-tuned on that '
+                                 'object against everything else; the test pass merges the nets\' answers into palette PNGs '
+                                 'on the device and scores J and F per object')
+        parser.add_argument('--objects', default=2, type=int, metavar='K',
+                            help='with --multi-object --synthetic: the number of objects of the synthetic sequence (1..16)')
     if not is_online:
         parser.add_argument('--resident-train-set', action='store_true',
                             help='decode the training set once, keep it on the GPU and flip / rescale each draw there '
@@ -65,7 +72,17 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
     if not is_online and args.microbatch_group > 1 and args.data_parallel:
         parser.error('--microbatch-group above 1 does not combine with --data-parallel (that mode splits every batch with '
                      'class counts of the whole batch)')
-    if is_online and args.png_fitted and not args.fast_test:
+    if is_online and args.multi_object:
+        if args.eval_speeds:
+            parser.error('--multi-object is a PNG-writing test pass of K nets; --eval-speeds times one net and writes nothing')
+        if args.data_parallel:
+            parser.error('--multi-object fine-tunes K nets one after the other on one device; --data-parallel spreads ONE '
+                         'net\'s accumulation cycle over the ranks')
+        if args.device_decode:
+            parser.error('--multi-object reads its frames through the host loader; --device-decode is not wired to it')
+        if not 1 <= args.objects <= 16:
+            parser.error('--objects counts the objects of the synthetic sequence: 1..16')
+    if is_online and args.png_fitted and not args.fast_test and not args.multi_object:
         parser.error('--png-fitted chooses the codes of the device PNG encoder: it needs --fast-test')
     if is_online and args.device_decode and args.synthetic:
         parser.error('--device-decode decodes JPEG files: the synthetic sequence has none')

@@ -8,7 +8,11 @@ the byte stretch and the DAVIS 2016 J / F counts computed on the device beside t
 fosvos_jf_counts); ``test`` itself keeps the reference's host path.
 
 ``test_fast`` (opt-in, ``--fast-test``) forwards the frames in groups, has the device encode the PNG files as well
-(fosvos_png_encode, layout: util/png_layout.py) and leaves the host nothing to do but write them."""
+(fosvos_png_encode, layout: util/png_layout.py) and leaves the host nothing to do but write them.
+
+``test_objects`` (``--multi-object``) is ``test_fast`` for a sequence of several objects: K nets, one per object, forward every
+group; the device merges their answers into label maps, encodes palette PNG files and counts J / F per object
+(util/object_merge.py states the definitions)."""
 import timeit
 from pathlib import Path
 from typing import Callable, Optional
@@ -25,7 +29,7 @@ log = get_logger(__file__)
 # what the last call of test() did: {'n_runs', 'n_forward', 'times' (seconds, the kept samples), 'accurate_images',
 # 'time_per_sample'}.  The reference only logs these numbers (:70-80); tests and bench.py read them here.
 last_eval = {}
-# what the last call of test_scored() returned
+# what the last call of test_scored() (or of test_fast() / test_objects() with annotations) returned
 last_score = {}
 # what the last call of test_fast() did: {'n_frames', 'n_groups', 'group_sizes', 'seconds', host seconds per stage:
 # 'seconds_load' (waiting for the loader), 'seconds_issue' (upload, forward and encode calls), 'seconds_wait' (for the
@@ -348,10 +352,159 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     return score
 
 
+def _frame_ids(annotations: Callable, seq: str, fname: str, h: int, w: int) -> Optional[np.ndarray]:
+    ann = annotations(seq, fname)
+    if ann is None:
+        return None
+    ann = np.asarray(ann)
+    if ann.shape != (h, w):
+        raise ValueError('annotation of {}/{} is {}, the logits are {}'.format(seq, fname, ann.shape, (h, w)))
+    return ann.astype(np.uint8)
+
+
+def test_objects(net_providers, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
+                 seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed',
+                 palette=None) -> Optional[dict]:
+    """The test pass of a sequence with several objects: ``net_providers[k - 1]`` holds the net fine-tuned on object k
+    against everything else.  ``test_fast``'s structure - groups of up to ``group`` frames uploaded once, ``forward_batch``
+    frames a forward call, two buffer slots, ONE copy per group of files plus lengths, the host writing the previous group's
+    files while the device works on this one - with every one of the K nets forwarding the same uploaded batch.  On the
+    device ``ops.merge_objects`` gives each pixel to the object whose net answers highest, or to the background where no
+    logit is >= 0 (util/object_merge.merge_labels), ``ops.png_encode_indexed`` turns the label maps into palette PNG files
+    (util/png_layout.encode_indexed; ``palette``: uint8 [256,3], None = the DAVIS palette) written as
+    ``<save_dir>/<seq>/<fname>.png``, and ``ops.jf_counts_labels`` takes J / F counts per object into one [n_frames,K,6]
+    counter tensor read back once.  ``annotations(seq_name, fname)`` -> uint8 [H,W] object ids or None; without
+    ``annotations`` the pass returns None.  CPU logits take the numpy path (``merge_labels``, ``encode_indexed``,
+    ``jf_counts_labels_numpy``).
+    The score dict (kept in ``last_score``): 'seq_name', 'radius', 'fnames', 'scored', 'n_objects', 'objects' - per object
+    {'object_id', 'counts', 'J', 'F', 'J_stats', 'F_stats'} as ``test_scored`` forms them -, 'J_stats' / 'F_stats' - each
+    statistic averaged over the objects -, 'J&F' and 'seconds'.  Toolkit parity unpinned, as for the single-object J / F."""
+    from util import object_merge, png_layout
+    if png_huffman not in png_layout.HUFFMAN_MODES:
+        raise ValueError('test_objects: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
+    if group < 1 or forward_batch < 1:
+        raise ValueError('test_objects: group and forward_batch must be at least 1, got {} and {}'.format(group, forward_batch))
+    nets = [p.network for p in net_providers]
+    n_obj = len(nets)
+    if not 1 <= n_obj <= object_merge.MAX_OBJECTS:
+        raise ValueError('test_objects: {} nets, outside [1, {}]'.format(n_obj, object_merge.MAX_OBJECTS))
+    log.info('Testing Network ({} objects)'.format(n_obj))
+    n_frames = len(data_loader.dataset)
+    fnames, seqs, scored = [], [], []
+    counts_dev, counts_host, radius = None, np.zeros((n_frames, n_obj, 6), dtype=np.int64), None
+    palette_dev, palette_host = None, (None if palette is None else np.asarray(palette, dtype=np.uint8))
+    stores = {}      # (slot, n, h, w) -> (device bytes, host pinned bytes)
+    pending = None   # (host bytes, n, capacity, copy-landed event, paths) of the group whose files are not written yet
+    group_sizes, png_bytes = [], 0
+
+    def write_files(paths, blobs):
+        for path, blob in zip(paths, blobs):
+            path.parent.mkdir(parents=True, exist_ok=True)
+            with open(str(path), 'wb') as fh:
+                fh.write(blob)
+
+    def retire(item):
+        nonlocal png_bytes
+        host, n, cap, landed, paths = item
+        landed.synchronize()
+        lengths = host[n * cap:n * cap + 4 * n].view(torch.int32).tolist()
+        data = host.numpy()
+        write_files(paths, [data[k * cap:k * cap + lengths[k]].data for k in range(n)])
+        png_bytes += sum(lengths)
+
+    time_all_start = timeit.default_timer()
+    with torch.no_grad():
+        for minibatches in _frame_groups(data_loader, group):
+            images = minibatches[0]['image'] if len(minibatches) == 1 else torch.cat([m['image'] for m in minibatches])
+            inputs, = gpu_handler.cast_cuda_if_possible([images])
+            n = int(inputs.shape[0])
+            logits = []
+            for net in nets:  # every net forwards the same uploaded batch
+                if n <= forward_batch:
+                    logits.append(net.forward(inputs)[-1].detach().float().contiguous())
+                else:
+                    logits.append(torch.cat([net.forward(inputs[k:k + forward_batch])[-1].detach().float()
+                                             for k in range(0, n, forward_batch)]))
+            h, w = int(logits[0].shape[2]), int(logits[0].shape[3])
+            first = len(fnames)
+            if first + n > n_frames:
+                raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
+            group_sizes.append(n)
+            radius = davis_measures.default_radius(h, w)
+            gt = np.zeros((n, h, w), dtype=np.uint8) if annotations is not None else None
+            for minibatch in minibatches:
+                for seq, fname in zip(minibatch['seq_name'], minibatch['fname']):
+                    ann = _frame_ids(annotations, seq, fname, h, w) if annotations is not None else None
+                    if ann is not None:
+                        gt[len(fnames) - first] = ann
+                    seqs.append(seq)
+                    fnames.append(fname)
+                    scored.append(ann is not None)
+            paths = [Path(save_dir) / seqs[k] / '{0}.png'.format(fnames[k]) for k in range(first, first + n)]
+            if logits[0].is_cuda:
+                from fosvos_hip import ops
+                device = logits[0].device
+                if palette_host is not None and palette_dev is None:
+                    palette_dev = torch.from_numpy(palette_host).to(device)
+                labels = ops.merge_objects(logits)
+                if annotations is not None:
+                    if counts_dev is None:
+                        counts_dev = torch.zeros((n_frames, n_obj, 6), dtype=torch.int32, device=device)
+                    ops.jf_counts_labels(labels, torch.from_numpy(gt).to(device), n_obj, radius,
+                                         out=counts_dev[first:first + n])
+                cap = ops.png_indexed_capacity(h, w)
+                cap += -cap % 4  # the lengths sit behind the n file slots, in the same buffer: one copy brings both
+                key = (len(group_sizes) % 2, n, h, w)
+                if key not in stores:
+                    stores[key] = (torch.empty(n * cap + 4 * n, dtype=torch.uint8, device=device),
+                                   torch.empty(n * cap + 4 * n, dtype=torch.uint8).pin_memory())
+                dev_store, host_store = stores[key]
+                ops.png_encode_indexed(labels, palette_dev, out=dev_store[:n * cap].view(n, cap),
+                                       lengths=dev_store[n * cap:].view(torch.int32), huffman=png_huffman)
+                host_store.copy_(dev_store, non_blocking=True)
+                landed = torch.cuda.Event()
+                landed.record()
+                if pending is not None:
+                    retire(pending)  # the previous group's files, while the device works on this group
+                pending = (host_store, n, cap, landed, paths)
+            else:
+                labels = object_merge.merge_labels([x[:, 0].numpy() for x in logits])
+                blobs = []
+                for index in range(n):
+                    if annotations is not None:
+                        counts_host[first + index] = object_merge.jf_counts_labels_numpy(labels[index], gt[index], n_obj,
+                                                                                         radius)
+                    blobs.append(png_layout.encode_indexed(labels[index], palette_host, huffman=png_huffman))
+                write_files(paths, blobs)
+                png_bytes += sum(len(b) for b in blobs)
+        if pending is not None:
+            retire(pending)
+    if counts_dev is not None:
+        counts_host = counts_dev.cpu().numpy().astype(np.int64)
+    time_for_all = timeit.default_timer() - time_all_start
+    log.info('Test {0}: {1} images of {2} objects in {3} groups, {4} PNG bytes, total test time {5} sec'.format(
+        seq_name, len(fnames), n_obj, len(group_sizes), png_bytes, time_for_all))
+    if annotations is None:
+        return None
+    counts_host = counts_host[:len(fnames)]
+    keep = np.asarray(scored, dtype=bool)
+    objects = [object_merge.object_score(counts_host[:, k], keep, k + 1) for k in range(n_obj)]
+    j_stats = object_merge.mean_statistics([o['J_stats'] for o in objects])
+    f_stats = object_merge.mean_statistics([o['F_stats'] for o in objects])
+    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
+             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep], 'n_objects': n_obj,
+             'objects': objects, 'J_stats': j_stats, 'F_stats': f_stats,
+             'J&F': (j_stats['mean'] + f_stats['mean']) / 2, 'seconds': time_for_all}
+    last_score.clear()
+    last_score.update(score)
+    return score
+
+
 def format_score(score: dict) -> str:
     js, fs = score['J_stats'], score['F_stats']
-    return ('J mean {:.4f} recall {:.4f} decay {:.4f}, F mean {:.4f} recall {:.4f} decay {:.4f}, J&F {:.4f}'
-            .format(js['mean'], js['recall'], js['decay'], fs['mean'], fs['recall'], fs['decay'], score['J&F']))
+    objects = ' (mean over {} objects)'.format(score['n_objects']) if 'n_objects' in score else ''
+    return ('J mean {:.4f} recall {:.4f} decay {:.4f}, F mean {:.4f} recall {:.4f} decay {:.4f}, J&F {:.4f}{}'
+            .format(js['mean'], js['recall'], js['decay'], fs['mean'], fs['recall'], fs['decay'], score['J&F'], objects))
 
 
 def write_scores(path: Path, score: dict) -> None:

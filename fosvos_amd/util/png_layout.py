@@ -350,6 +350,31 @@ def encode(img: np.ndarray, huffman: str = 'fixed') -> bytes:
     return b''.join(parts)
 
 
+PLTE_BYTES = 12 + 768                     # the palette chunk of an indexed file: always 256 entries
+
+
+def max_file_bytes_indexed(h: int, w: int) -> int:
+    return max_file_bytes(h, w) + PLTE_BYTES
+
+
+def encode_indexed(labels: np.ndarray, palette=None, huffman: str = 'fixed') -> bytes:
+    """The palette PNG file of a uint8 [H,W] label map (fosvos_png_encode_indexed): the file of ``encode(labels, huffman)`` -
+    same filtered stream, segments, segment forms, IDAT chunks, final IDAT and IEND - under an IHDR of colour type 3 (bit
+    depth 8) and with ONE ``PLTE`` chunk of 768 bytes between IHDR and the first IDAT.  ``palette``: uint8 [256,3] RGB;
+    None = ``object_merge.davis_palette()``."""
+    if palette is None:
+        from util import object_merge
+        palette = object_merge.davis_palette()
+    palette = np.asarray(palette)
+    if palette.dtype != np.uint8 or palette.shape != (256, 3):
+        raise ValueError('png_layout.encode_indexed: a uint8 [256,3] palette, got {} {}'.format(palette.dtype, palette.shape))
+    grey = encode(labels, huffman)
+    h, w = np.asarray(labels).shape
+    first_idat = len(SIGNATURE) + 25
+    return (SIGNATURE + _chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 3, 0, 0, 0)) + _chunk(b'PLTE', palette.tobytes())
+            + grey[first_idat:])
+
+
 def chunks(file: bytes) -> List[Tuple[bytes, bytes]]:
     """[(tag, data)] of a PNG file, CRCs checked."""
     if file[:8] != SIGNATURE:

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 30
+#define FOSVOS_ABI_VERSION 31
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -440,6 +440,36 @@ size_t fosvos_png_capacity_bytes(int N, int H, int W); /* per frame */
 size_t fosvos_png_workspace_bytes(int N, int H, int W, int huffman);
 int fosvos_png_encode(const uint8_t *bytes, int N, int H, int W, int huffman, uint8_t *out, size_t capacity, int32_t *lengths,
                       void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* ---- several objects a sequence: label merge, per-object counts, palette files (ABI 31) ---------------------------------
+ * One net per object is fine-tuned on "this object against everything else"; all K nets run on every frame.  The
+ * definitions are stated in numpy in util/object_merge.py and util/png_layout.py (encode_indexed); the tests compare byte
+ * for byte.
+ *
+ * fosvos_merge_objects: logits[k] fp32 [N,1,H,W] of net k (k = 0..K-1, 1 <= K <= FOSVOS_MAX_OBJECTS; `logits` is a host
+ * array of K device pointers, which travel to the kernel by value) -> labels uint8 [N,H,W]: 0 where no logit of the pixel is
+ * >= 0 (a NaN never is, -0.0 is), else 1 + k* with k* the lowest k among those holding the largest such logit.  For K = 1
+ * that is the mask of fosvos_jf_counts.  One launch; 4 K B read and 1 B written per pixel.
+ *
+ * fosvos_jf_counts_labels: pred and gt uint8 [N,H,W] label maps -> counts int32 [N,K,6]: row (n, k-1) is what
+ * fosvos_jf_counts gives for the masks (pred == k) and (gt == k) of frame n; labels above K belong to no object.  A pack
+ * kernel writes the bit planes of every object ([N][K][H][ceil(W/64)] words twice: fosvos_jf_labels_workspace_bytes, 8-byte
+ * aligned) and zeroes the counters, then the count kernel of fosvos_jf_counts runs on N K frames.  N K <= 65535,
+ * 1 <= radius <= 63.  Two launches.
+ *
+ * fosvos_png_encode_indexed: labels uint8 [N,H,W] -> N standalone 8-bit palette PNG files (IHDR colour type 3): the file
+ * of fosvos_png_encode with one PLTE chunk of the 256 RGB entries `palette` (uint8 [256,3], device memory) between IHDR and
+ * the first IDAT, so it is 780 bytes longer: capacity >= fosvos_png_indexed_capacity_bytes.  huffman, lengths and workspace
+ * (fosvos_png_workspace_bytes) as for fosvos_png_encode. */
+#define FOSVOS_MAX_OBJECTS 16
+int fosvos_merge_objects(const float *const *logits, int K, int N, int H, int W, uint8_t *labels, int device, void *stream);
+size_t fosvos_jf_labels_workspace_bytes(int N, int K, int H, int W);
+int fosvos_jf_counts_labels(const uint8_t *pred, const uint8_t *gt, int N, int K, int H, int W, int radius, int32_t *counts,
+                            void *workspace, size_t workspace_bytes, int device, void *stream);
+size_t fosvos_png_indexed_capacity_bytes(int N, int H, int W); /* per frame */
+int fosvos_png_encode_indexed(const uint8_t *labels, const uint8_t *palette, int N, int H, int W, int huffman, uint8_t *out,
+                              size_t capacity, int32_t *lengths, void *workspace, size_t workspace_bytes, int device,
+                              void *stream);
 
 /* ---- the streamed output frames as JPEG files, encoded on the device --------------------------------------------------
  * fosvos_jpeg_encode: frames uint8 [N,H,W,3] BGR (what fosvos_overlay writes; components = 3) or [N,H,W] grey (components =
