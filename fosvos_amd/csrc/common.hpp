@@ -225,6 +225,21 @@ __device__ __forceinline__ uint4 max_nonneg_bf16x8(const uint4 &a, const uint4 &
 __device__ __forceinline__ double sigmoid_f64(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
 __device__ __forceinline__ double sigmoid_f64(double x) { return 1.0 / (1.0 + exp(-x)); }
 
+// several objects a sequence (eval.hip: the label merge; stream.hip: the palette overlay): the K logit maps of the K
+// per-object nets, pointers by value in the kernel's arguments
+constexpr int kMaxObjects = FOSVOS_MAX_OBJECTS;
+struct ObjectLogits {
+    const float *p[kMaxObjects];
+};
+// the merge rule on one pixel, object k's logit v against the best so far (best = 0: none yet, bestv = -1): a NaN is never
+// valid, -0.0 is; a tie stays with the lower k.  T = float, or double for logits interpolated in fp64
+template <typename T>
+__device__ __forceinline__ void merge_take(T v, uint32_t k, T &bestv, uint32_t &best) {
+    const bool take = v >= T(0) && v > bestv;
+    bestv = take ? v : bestv;
+    best = take ? k + 1u : best;
+}
+
 // wave64 all-lanes sum
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

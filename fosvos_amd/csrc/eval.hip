@@ -265,19 +265,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jf_count(const u64 *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------ several objects
-constexpr int kMaxObjects = FOSVOS_MAX_OBJECTS;
-struct ObjectLogits {
-    const float *p[kMaxObjects];
-};
-
-// the merge rule on one pixel, object k's logit v against the best so far (best = 0: none yet, bestv = -1): a NaN is never
-// valid, -0.0 is; a tie stays with the lower k
-__device__ __forceinline__ void merge_take(float v, uint32_t k, float &bestv, uint32_t &best) {
-    const bool take = v >= 0.f && v > bestv;
-    bestv = take ? v : bestv;
-    best = take ? k + 1u : best;
-}
-
+// (ObjectLogits and the merge rule of one pixel, merge_take: common.hpp)
 // grid (blocks, N).  vec: every map and the labels are 16-byte / 4-byte aligned and hw % 4 == 0
 __global__ __launch_bounds__(kEvalThreads) void k_merge_objects(const ObjectLogits maps, int K, int64_t hw, int vec,
                                                                 uint8_t *__restrict__ out) {

@@ -30,6 +30,16 @@
 // fosvos_overlay_scaled, one launch:
 //   k_overlay_scaled     k_overlay with the logit of an output pixel gathered from the [Hn,Wn] map: bilinear at half-pixel
 //                        centres with integer weights, in fp64, as 4 Hf Wf times the logit (its sign is the boolean mask).
+//
+// Several objects a stream (opt-in; util/object_overlay.py states both): the K logit maps of K per-object nets, pointers by value.
+// fosvos_overlay_objects, one launch:
+//   k_overlay_objects         k_overlay's partition anchored on map 0; a thread takes its 16 logits from each of the K maps in
+//                             turn and keeps (best value, label) per pixel - the rule of fosvos_merge_objects - then blends
+//                             every labelled pixel towards its palette colour: b + alpha (col - b) in fp64, rounded half up.
+//                             4 K + 3 B read, 3 B written per pixel; no label map in between.
+// fosvos_overlay_objects_scaled, one launch:
+//   k_overlay_objects_scaled  k_overlay_scaled's thread map; the taps of a pixel are taken once and applied to all K maps,
+//                             the rule then runs on the fp64 values.  Mode 0 the overlay, mode 1 the label map.
 #include <math.h>
 
 #include "common.hpp"
@@ -430,6 +440,175 @@ __global__ __launch_bounds__(kStreamThreads) void k_overlay_scaled(const uint8_t
     }
 }
 
+// ------------------------------------------------------------------------------------------ overlay_objects
+// Several objects (util/object_overlay.py): the label of a pixel is the merge rule (common.hpp: merge_take) over the K maps,
+// its colour entry `label` of the palette, blended into all three channels.
+// The palette's entries 1..K as B | G << 8 | R << 16 (entry 0 is never painted), read once per workgroup.  Every thread of
+// the workgroup passes here before any of them leaves.
+__device__ __forceinline__ void stage_colours(const uint8_t *__restrict__ palette, int K, uint32_t (&cols)[kMaxObjects + 1]) {
+    const int k = threadIdx.x;
+    if (k <= K)
+        cols[k] = k == 0 ? 0u : (uint32_t)palette[3 * k + 2] | ((uint32_t)palette[3 * k + 1] << 8) | ((uint32_t)palette[3 * k] << 16);
+    __syncthreads();
+}
+// the three output bytes (in bits 0..23) of a pixel with the frame's bytes b[3] and the colour `col`, label 0 keeps b
+__device__ __forceinline__ uint32_t paint(const uint32_t (&b)[3], uint32_t label, uint32_t col, double alpha) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double fb = (double)b[c];
+        const double v = fb + alpha * ((double)((col >> (8 * c)) & 0xffu) - fb);
+        o |= (label ? (uint32_t)(v + 0.5) : b[c]) << (8 * c);
+    }
+    return o;
+}
+
+// k_overlay's partition; the groups are anchored on map 0, so maps 1..K-1 lie wherever their base pointers put them: all of
+// them are loaded as floats4 (alignment 4), which is what they are known to have.
+template <bool MIRROR>
+__global__ __launch_bounds__(kStreamThreads) void k_overlay_objects(const uint8_t *__restrict__ frames, const ObjectLogits maps,
+                                                                    int K, const uint8_t *__restrict__ palette,
+                                                                    uint8_t *__restrict__ out, int64_t L, int64_t slots,
+                                                                    int64_t total, double alpha) {
+    __shared__ uint32_t cols[kMaxObjects + 1];
+    stage_colours(palette, K, cols);
+    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
+    if (gid >= total) return;
+    const int64_t seg = segment_of(gid, slots);
+    const Span s = span_of(gid, seg, slots, L, maps.p[0] + seg * L);
+    const uint8_t *__restrict__ src = frames + seg * 3 * L;
+    uint8_t *__restrict__ dst = out + seg * 3 * L;
+    if (s.qb - s.qa == kGroup) {
+        float bv[kGroup];
+        uint32_t lab[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) bv[i] = -1.f, lab[i] = 0u;
+        for (int k = 0; k < K; ++k) {
+            const floats4 *__restrict__ lv = reinterpret_cast<const floats4 *>(maps.p[k] + seg * L + s.qa);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const floats4 t = lv[j];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) merge_take(t.v[i], (uint32_t)k, bv[4 * j + i], lab[4 * j + i]);
+            }
+        }
+        uint32_t w[12], o[12];
+        load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o[k] = 0;
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const int px = MIRROR ? kGroup - 1 - i : i;
+            const uint32_t b[3] = {byte_at(w, 3 * px), byte_at(w, 3 * px + 1), byte_at(w, 3 * px + 2)};
+            const uint32_t v = paint(b, lab[i], cols[lab[i]], alpha);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int at = 3 * i + c;
+                o[at >> 2] |= ((v >> (8 * c)) & 0xffu) << (8 * (at & 3));
+            }
+        }
+        bytes16 *__restrict__ ov = reinterpret_cast<bytes16 *>(dst + 3 * s.qa);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            bytes16 t;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t.w[i] = o[4 * k + i];
+            ov[k] = t;
+        }
+    } else {
+        for (int64_t q = s.qa; q < s.qb; ++q) {
+            float bv = -1.f;
+            uint32_t lab = 0u;
+            for (int k = 0; k < K; ++k) merge_take(maps.p[k][seg * L + q], (uint32_t)k, bv, lab);
+            const int64_t sp = MIRROR ? L - 1 - q : q;
+            const uint32_t b[3] = {src[3 * sp], src[3 * sp + 1], src[3 * sp + 2]};
+            const uint32_t v = paint(b, lab, cols[lab], alpha);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dst[3 * q + c] = (uint8_t)(v >> (8 * c));
+        }
+    }
+}
+
+// the label of the output pixel whose taps are tx, ty: the taps are taken once and applied to all K maps (rows at `top` and
+// `bot` floats into every map)
+__device__ __forceinline__ uint32_t label_up(const ObjectLogits &maps, int K, int64_t top, int64_t bot, const Tap &tx,
+                                             const Tap &ty) {
+    double bv = -1.0;
+    uint32_t lab = 0u;
+    for (int k = 0; k < K; ++k) merge_take(logit_up(maps.p[k] + top, maps.p[k] + bot, tx, ty), (uint32_t)k, bv, lab);
+    return lab;
+}
+
+// k_overlay_scaled's thread map.  MODE 0: the overlay; MODE 1: the label map, one byte a pixel
+template <int MODE, bool MIRROR>
+__global__ __launch_bounds__(kStreamThreads) void k_overlay_objects_scaled(const uint8_t *__restrict__ frames,
+                                                                           const ObjectLogits maps, int K,
+                                                                           const uint8_t *__restrict__ palette,
+                                                                           uint8_t *__restrict__ out, int Hf, int Wf, int Hn,
+                                                                           int Wn, int64_t slots, int64_t total, double alpha) {
+    constexpr bool kBlend = MODE == 0;
+    __shared__ uint32_t cols[kMaxObjects + 1];
+    if (kBlend) stage_colours(palette, K, cols);
+    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
+    if (gid >= total) return;
+    const int64_t seg = segment_of(gid, slots), L = Wf;
+    const int64_t n = seg / Hf;
+    const int y = (int)(seg - n * Hf);
+    const uint8_t *__restrict__ src = kBlend ? frames + seg * 3 * L : nullptr;
+    uint8_t *__restrict__ dst = out + seg * (kBlend ? 3 : 1) * L;
+    const unsigned lead = (16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u;
+    const Span s = span_at(gid, seg, slots, L, (int)(kBlend ? (11u * lead) & 15u : lead));
+    const Tap ty = tap_of(walk_from(y, Hn, Hf), Hn, Hf);
+    const int64_t top = (n * Hn + ty.i0) * Wn, bot = (n * Hn + ty.i1) * Wn;
+    Walk wx = walk_from((int)s.qa, Wn, Wf);
+    if (s.qb - s.qa == kGroup) {
+        if (kBlend) {
+            uint32_t w[12], o[12];
+            load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) o[k] = 0;
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                const uint32_t lab = label_up(maps, K, top, bot, tap_of(wx, Wn, Wf), ty);
+                walk_on(wx, Wn, Wf);
+                const int px = MIRROR ? kGroup - 1 - i : i;
+                const uint32_t b[3] = {byte_at(w, 3 * px), byte_at(w, 3 * px + 1), byte_at(w, 3 * px + 2)};
+                const uint32_t v = paint(b, lab, cols[lab], alpha);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int at = 3 * i + c;
+                    o[at >> 2] |= ((v >> (8 * c)) & 0xffu) << (8 * (at & 3));
+                }
+            }
+            uint4 *__restrict__ ov = reinterpret_cast<uint4 *>(dst + 3 * s.qa);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ov[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+        } else {
+            uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                o[i >> 2] |= label_up(maps, K, top, bot, tap_of(wx, Wn, Wf), ty) << (8 * (i & 3));
+                walk_on(wx, Wn, Wf);
+            }
+            *reinterpret_cast<uint4 *>(dst + s.qa) = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+    } else {
+        for (int64_t q = s.qa; q < s.qb; ++q) {
+            const uint32_t lab = label_up(maps, K, top, bot, tap_of(wx, Wn, Wf), ty);
+            walk_on(wx, Wn, Wf);
+            if (kBlend) {
+                const int64_t sp = MIRROR ? L - 1 - q : q;
+                const uint32_t b[3] = {src[3 * sp], src[3 * sp + 1], src[3 * sp + 2]};
+                const uint32_t v = paint(b, lab, cols[lab], alpha);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dst[3 * q + c] = (uint8_t)(v >> (8 * c));
+            } else {
+                dst[q] = (uint8_t)lab;
+            }
+        }
+    }
+}
+
 // segments and threads of a launch
 struct Partition {
     int64_t L, slots, total;
@@ -574,6 +753,71 @@ extern "C" int fosvos_overlay_scaled(const uint8_t *frames, const float *logits,
         case 2: launch_overlay_scaled<2>(false, grid, st, frames, logits, out, Hf, Wf, Hn, Wn, p, channel, a255); break;
         default: launch_overlay_scaled<3>(false, grid, st, frames, logits, out, Hf, Wf, Hn, Wn, p, channel, a255); break;
     }
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+namespace {
+// the K pointers of a several-objects call, by value
+int object_maps(const char *who, const float *const *logits, int K, ObjectLogits &maps) {
+    FOSVOS_REQUIRE(K >= 1 && K <= kMaxObjects, FOSVOS_E_ARG, "%s: K=%d outside [1, %d]", who, K, kMaxObjects);
+    FOSVOS_REQUIRE(logits, FOSVOS_E_ARG, "%s: null pointer", who);
+    for (int k = 0; k < K; ++k) {
+        FOSVOS_REQUIRE(logits[k] != nullptr, FOSVOS_E_ARG, "%s: null logit map %d", who, k);
+        FOSVOS_REQUIRE(((uintptr_t)logits[k] & 3) == 0, FOSVOS_E_ARG, "%s: logit map %d must be 4-byte aligned", who, k);
+        maps.p[k] = logits[k];
+    }
+    return FOSVOS_OK;
+}
+}  // namespace
+
+extern "C" int fosvos_overlay_objects(const uint8_t *frames, const float *const *logits, int K, int N, int H, int W, int mirror,
+                                      const uint8_t *palette, double alpha, uint8_t *out, int device, void *stream) {
+    ObjectLogits maps = {};
+    if (int rc = object_maps("overlay_objects", logits, K, maps)) return rc;
+    FOSVOS_REQUIRE(frames && palette && out, FOSVOS_E_ARG, "overlay_objects: null pointer");
+    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)N * H * W <= kMaxPixels, FOSVOS_E_SHAPE, "overlay_objects: N=%d H=%d W=%d",
+                   N, H, W);
+    FOSVOS_REQUIRE(alpha >= 0.0 && alpha <= 1.0, FOSVOS_E_ARG, "overlay_objects: alpha %g is not a number in [0, 1]", alpha);
+    FOSVOS_ENTER(device);
+    const Partition p = partition_of(N, H, W, mirror);
+    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads));
+    hipStream_t st = (hipStream_t)stream;
+    FOSVOS_PROF("k_overlay_objects", stream, 0.0);
+    if (mirror)
+        hipLaunchKernelGGL(k_overlay_objects<true>, grid, dim3(kStreamThreads), 0, st, frames, maps, K, palette, out, p.L, p.slots,
+                           p.total, alpha);
+    else
+        hipLaunchKernelGGL(k_overlay_objects<false>, grid, dim3(kStreamThreads), 0, st, frames, maps, K, palette, out, p.L, p.slots,
+                           p.total, alpha);
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" int fosvos_overlay_objects_scaled(const uint8_t *frames, const float *const *logits, int K, int N, int Hf, int Wf,
+                                             int Hn, int Wn, int mirror, int mode, const uint8_t *palette, double alpha,
+                                             uint8_t *out, int device, void *stream) {
+    FOSVOS_REQUIRE(mode == 0 || mode == 1, FOSVOS_E_ARG, "overlay_objects_scaled: mode %d outside [0, 1]", mode);
+    ObjectLogits maps = {};
+    if (int rc = object_maps("overlay_objects_scaled", logits, K, maps)) return rc;
+    FOSVOS_REQUIRE(out && ((frames && palette) || mode == 1), FOSVOS_E_ARG, "overlay_objects_scaled: null pointer");
+    if (int rc = check_sizes("overlay_objects_scaled", N, Hf, Wf, Hn, Wn)) return rc;
+    FOSVOS_REQUIRE(mode == 1 || (alpha >= 0.0 && alpha <= 1.0), FOSVOS_E_ARG,
+                   "overlay_objects_scaled: alpha %g is not a number in [0, 1]", alpha);
+    FOSVOS_ENTER(device);
+    const Partition p = partition_of(N, Hf, Wf, 1);  // rows, in both modes
+    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads)), block(kStreamThreads);
+    hipStream_t st = (hipStream_t)stream;
+    FOSVOS_PROF("k_overlay_objects_scaled", stream, 0.0);
+    if (mode == 1)  // a label map has nothing to mirror: the logits already are in output order
+        hipLaunchKernelGGL((k_overlay_objects_scaled<1, false>), grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn, Wn,
+                           p.slots, p.total, alpha);
+    else if (mirror)
+        hipLaunchKernelGGL((k_overlay_objects_scaled<0, true>), grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn, Wn,
+                           p.slots, p.total, alpha);
+    else
+        hipLaunchKernelGGL((k_overlay_objects_scaled<0, false>), grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn, Wn,
+                           p.slots, p.total, alpha);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }

@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -240,6 +240,10 @@ SIGNATURES = {
                                          c_void_p]),
     "fosvos_overlay_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       ctypes.c_double, c_void_p, c_int, c_void_p]),
+    "fosvos_overlay_objects": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                       ctypes.c_double, c_void_p, c_int, c_void_p]),
+    "fosvos_overlay_objects_scaled": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_void_p, ctypes.c_double, c_void_p, c_int, c_void_p]),
     "fosvos_vgg_backward": (c_int, [c_void_p, POINTER(VggWeights), POINTER(VggGrads), c_void_p, c_int, c_int, c_int, c_void_p,
                                     c_size_t, c_void_p, POINTER(c_void_p), c_void_p, c_void_p]),
 }

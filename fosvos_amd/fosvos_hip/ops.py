@@ -1644,3 +1644,56 @@ def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False,
                                OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st), "overlay")
     _pe(e0, "overlay", 0.0, (10.0 if overlay else 5.0) * n * h * w)
     return out
+
+
+def overlay_objects(frames_u8: torch.Tensor, logits: Sequence[torch.Tensor], mirror: bool = False, overlay: bool = True,
+                    palette: Optional[torch.Tensor] = None, alpha: float = 0.5, out: Optional[torch.Tensor] = None,
+                    net_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """fosvos_overlay_objects: raw frames uint8 [N,H,W,3] and the logits fp32 [N,1,H,W] that K per-object nets (1 <= K <= 16)
+    made of them (of the mirrored frames, with ``mirror``) -> uint8 [N,H,W,3]: the (mirrored) frames with every pixel that
+    ``merge_objects`` would label k > 0 blended towards ``palette[k]``, ``b + alpha * (colour - b)`` rounded half up, in all
+    three channels; label 0 keeps its bytes.  ``palette``: uint8 [256,3] RGB on the device, None = ``default_palette``;
+    ``alpha`` a finite number in [0, 1] (this overlay blends; ``overlay`` adds to one channel and takes more).
+    ``overlay=False``: the label map uint8 [N,H,W] (``merge_objects`` itself).  util/object_overlay.py states the bytes.
+    The K pointers travel by value, no label map is written in between; ``out`` may be a view of a caller's buffer at any
+    byte offset.  One launch on the current stream, no synchronisation.
+
+    ``net_size=(Hn, Wn)`` (no larger than the frames): fosvos_overlay_objects_scaled, the logits are [N,1,Hn,Wn] and every
+    map is interpolated up to the frames' size inside the launch, in both forms.  The frames' own size is the launch above."""
+    n, h, w = _frame_shape(frames_u8, "overlay_objects")
+    scaled = _net_size(net_size, h, w, "overlay_objects")
+    hn, wn = scaled if scaled is not None else (h, w)
+    logits = list(logits)
+    k = len(logits)
+    if not 1 <= k <= MAX_OBJECTS:
+        raise ValueError(f"overlay_objects: {k} logit maps, outside [1, {MAX_OBJECTS}]")
+    for t in logits:
+        _need_eval(t, _F32, "overlay_objects logits")
+        if tuple(t.shape) != (n, 1, hn, wn):
+            raise ValueError(f"overlay_objects: every logit map must be {(n, 1, hn, wn)}, got {tuple(t.shape)}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"overlay_objects: alpha must be a finite number in [0, 1], got {alpha!r}")
+    if palette is None:
+        palette = default_palette(frames_u8.device)
+    _need_eval(palette, torch.uint8, "overlay_objects palette")
+    if tuple(palette.shape) != (256, 3):
+        raise ValueError(f"overlay_objects: palette must be (256, 3), got {tuple(palette.shape)}")
+    out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay_objects")
+    _same_device("overlay_objects", frames_u8, palette, *logits)
+    if not overlay and scaled is None:
+        return merge_objects(logits, out=out)
+    import ctypes
+    table = (ctypes.c_void_p * k)(*[t.data_ptr() for t in logits])
+    dev, st = _ctx(frames_u8)
+    e0 = _pb()
+    if scaled is not None:
+        check(lib().fosvos_overlay_objects_scaled(frames_u8.data_ptr(), table, k, n, h, w, hn, wn, 1 if mirror else 0,
+                                                  0 if overlay else 1, palette.data_ptr(), alpha, out.data_ptr(), dev, st),
+              "overlay_objects_scaled")
+        _pe(e0, "overlay_objects_scaled", 0.0, (6.0 if overlay else 1.0) * n * h * w + 4.0 * k * n * hn * wn)
+        return out
+    check(lib().fosvos_overlay_objects(frames_u8.data_ptr(), table, k, n, h, w, 1 if mirror else 0, palette.data_ptr(), alpha,
+                                       out.data_ptr(), dev, st), "overlay_objects")
+    _pe(e0, "overlay_objects", 0.0, (4.0 * k + 6.0) * n * h * w)
+    return out

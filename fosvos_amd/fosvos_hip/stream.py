@@ -35,11 +35,18 @@ form (smaller files; the default budget stays the quarter).  ``encode=None`` is 
 inside its own (csrc/stream.hip; util/frame_resample.py states both).  Everything else - the uploads, the output, the JPEG
 capacity and budget, the downloads - stays at the frame's size.  ``None`` or the frame's own size is the object described above.
 
+``ObjectSegmenter`` (opt-in) is the same object for several objects a frame: K per-object nets run on the slot's one image and
+ONE ``ops.overlay_objects`` merges their logits and paints the palette overlay (csrc/stream.hip; util/object_overlay.py
+states the bytes).  Its label-map form can end in a palette PNG (``encode='png'``, ``ops.png_encode_indexed``), which leaves the
+slot exactly like the JPEG: ``[length | file]`` on the device, ``[length | first budget bytes]`` on the host.  Only the
+compute step differs from ``FrameSegmenter``, whose launches, order and bytes are what they were.
+
 Not thread-safe: one host thread drives a segmenter.
 """
 from __future__ import annotations
 
 from collections import deque
+from contextlib import contextmanager
 from typing import Deque, Iterable, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
@@ -91,49 +98,73 @@ class FrameSegmenter:
                  quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None,
                  net_size: Optional[Tuple[int, int]] = None) -> None:
         from util import frame_overlay
-        self.height, self.width, self.depth = int(height), int(width), int(depth)
-        if self.height <= 0 or self.width <= 0 or self.depth <= 0:
-            raise ValueError(f"FrameSegmenter: height, width and depth must be positive, got {height}, {width}, {depth}")
-        # None where the net runs at the frame's size: the unscaled launches, exactly
-        self.net_size = ops._net_size(net_size, self.height, self.width, "FrameSegmenter")
+        self._set_geometry(height, width, depth, net_size)
         frame_overlay.check_color(color)
         self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
         self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
         self.net = net
+        self.device = self._device_of(net)
+        if encode not in (None, 'jpeg'):
+            raise ValueError(f"{self._who}: encode must be None or 'jpeg', got {encode!r}")
+        self._set_jpeg(encode, quality, subsampling, budget)
+        self._open()
+
+    # ---------------------------------------------------------------------------------------------- construction, in steps
+    @property
+    def _who(self) -> str:
+        return type(self).__name__
+
+    def _set_geometry(self, height, width, depth, net_size) -> None:
+        self.height, self.width, self.depth = int(height), int(width), int(depth)
+        if self.height <= 0 or self.width <= 0 or self.depth <= 0:
+            raise ValueError(f"{self._who}: height, width and depth must be positive, got {height}, {width}, {depth}")
+        # None where the net runs at the frame's size: the unscaled launches, exactly
+        self.net_size = ops._net_size(net_size, self.height, self.width, self._who)
+
+    def _device_of(self, net) -> torch.device:
         param = next(iter(net.parameters()), None)
         if param is None or not param.is_cuda:
-            raise RuntimeError("FrameSegmenter: the net must live on the GPU (the HIP path has no CPU fallback)")
-        self.device = param.device
+            raise RuntimeError(f"{self._who}: the net must live on the GPU (the HIP path has no CPU fallback)")
+        return param.device
+
+    def _set_budget(self, budget, default: int) -> None:
+        """The download budget of an encoder whose capacity is set: ``default`` bytes where none is given."""
+        if budget is None:
+            budget = default
+        if isinstance(budget, bool) or not isinstance(budget, int) or budget <= 0:
+            raise ValueError(f"{self._who}: budget must be a positive number of bytes, got {budget!r}")
+        self.budget = min(budget, self.capacity)
+
+    def _set_jpeg(self, encode, quality, subsampling, budget) -> None:
+        """``encode`` is None or 'jpeg' (``self.overlay`` says how many components the output has)."""
         h, w = self.height, self.width
-        out_shape = (1, h, w, 3) if self.overlay else (1, h, w)
-        if encode not in (None, 'jpeg'):
-            raise ValueError(f"FrameSegmenter: encode must be None or 'jpeg', got {encode!r}")
         self.encode, self.quality = encode, quality
-        if subsampling != '4:4:4' and not encode:
-            raise ValueError("FrameSegmenter: subsampling is the chroma sampling of encode='jpeg'")
+        if subsampling != '4:4:4' and encode != 'jpeg':
+            raise ValueError(f"{self._who}: subsampling is the chroma sampling of encode='jpeg'")
         self.subsampling = subsampling if encode else None
         self.capacity = self.budget = 0
         self.second_copies = 0  # frames whose file was longer than the budget
         self.bytes_down = 0     # bytes the downloads moved
         if encode:
             if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-                raise ValueError(f"FrameSegmenter: quality must be an integer in 1..100, got {quality!r}")
+                raise ValueError(f"{self._who}: quality must be an integer in 1..100, got {quality!r}")
             if self.subsampling not in ops.JPEG_SUBSAMPLINGS:
-                raise ValueError(f"FrameSegmenter: subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {subsampling!r}")
+                raise ValueError(f"{self._who}: subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {subsampling!r}")
             self.capacity = ops.jpeg_capacity(h, w, 3 if self.overlay else 1, self.subsampling)
             raw = h * w * (3 if self.overlay else 1)
-            if budget is None:
-                budget = max(raw // 4, 1024)
-            if isinstance(budget, bool) or not isinstance(budget, int) or budget <= 0:
-                raise ValueError(f"FrameSegmenter: budget must be a positive number of bytes, got {budget!r}")
-            self.budget = min(budget, self.capacity)
+            self._set_budget(budget, max(raw // 4, 1024))
         elif budget is not None:
-            raise ValueError("FrameSegmenter: budget is the download budget of encode='jpeg'")
+            raise ValueError(f"{self._who}: budget is the download budget of encode='jpeg'")
+
+    def _open(self) -> None:
+        """The streams, the slots and the queues, once everything above is decided."""
+        h, w = self.height, self.width
+        out_shape = (1, h, w, 3) if self.overlay else (1, h, w)
         self._closed = False
         with torch.cuda.device(self.device):
             self._up = torch.cuda.Stream(device=self.device)
             self._down = torch.cuda.Stream(device=self.device)
-            self._rest = torch.cuda.Stream(device=self.device) if encode else None  # second copies of long files
+            self._rest = torch.cuda.Stream(device=self.device) if self.encode else None  # second copies of long files
             self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget, self.net_size)
                                        for _ in range(self.depth)]
         self._flight: Deque[_Slot] = deque()     # submitted, oldest first
@@ -142,20 +173,20 @@ class FrameSegmenter:
     # ---------------------------------------------------------------------------------------------- checks
     def _check_open(self) -> None:
         if self._closed:
-            raise RuntimeError("FrameSegmenter: closed")
+            raise RuntimeError(f"{self._who}: closed")
 
     def _check_frame(self, frame):
         if isinstance(frame, torch.Tensor):  # a frame that is on the device already (ops.jpeg_decode made it)
             if frame.dtype != torch.uint8 or frame.device != self.device or not frame.is_contiguous():
-                raise ValueError(f"FrameSegmenter: a device frame must be a contiguous uint8 tensor on {self.device}, got "
+                raise ValueError(f"{self._who}: a device frame must be a contiguous uint8 tensor on {self.device}, got "
                                  f"{frame.dtype} on {frame.device}")
             if tuple(frame.shape) != (self.height, self.width, 3):
-                raise ValueError(f"FrameSegmenter: a frame must be {(self.height, self.width, 3)}, got {tuple(frame.shape)}")
+                raise ValueError(f"{self._who}: a frame must be {(self.height, self.width, 3)}, got {tuple(frame.shape)}")
             return frame
         if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8:
-            raise ValueError(f"FrameSegmenter: a frame must be a uint8 numpy array, got {getattr(frame, 'dtype', type(frame))}")
+            raise ValueError(f"{self._who}: a frame must be a uint8 numpy array, got {getattr(frame, 'dtype', type(frame))}")
         if frame.shape != (self.height, self.width, 3):
-            raise ValueError(f"FrameSegmenter: a frame must be {(self.height, self.width, 3)}, got {frame.shape}")
+            raise ValueError(f"{self._who}: a frame must be {(self.height, self.width, 3)}, got {frame.shape}")
         return frame
 
     @property
@@ -170,7 +201,7 @@ class FrameSegmenter:
         if self.encode:
             length = int(slot.host_out_np[:4].view(np.int32)[0])
             if not 0 < length <= self.capacity:
-                raise RuntimeError(f"FrameSegmenter: the encoder reported a file of {length} bytes (capacity {self.capacity})")
+                raise RuntimeError(f"{self._who}: the encoder reported a file of {length} bytes (capacity {self.capacity})")
             out = slot.host_out_np[_HEAD:_HEAD + min(length, self.budget)].tobytes()
             self.bytes_down += _HEAD + self.budget
             if length > self.budget:  # the slot's work is done: nothing to wait for but the copy itself
@@ -184,6 +215,30 @@ class FrameSegmenter:
         self._free.append(slot)
         return out
 
+    @staticmethod
+    @contextmanager
+    def _last_output_only(net):
+        """``net.compute_side_outputs = False`` for the calls inside, and whatever it was (or was not) afterwards."""
+        had, old = hasattr(net, 'compute_side_outputs'), getattr(net, 'compute_side_outputs', None)
+        net.compute_side_outputs = False
+        try:
+            yield
+        finally:
+            if had:
+                net.compute_side_outputs = old
+            else:
+                del net.compute_side_outputs
+
+    def _compute(self, slot: _Slot) -> None:
+        """What a frame needs on the net's stream, from ``slot.frame`` to ``slot.out`` (and the slot's file)."""
+        with self._last_output_only(self.net), torch.no_grad():
+            ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
+            logits = self.net.forward(slot.image)[-1]
+            ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
+                        out=slot.out, net_size=self.net_size)
+            if self.encode:
+                ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length, subsampling=self.subsampling)
+
     def _enqueue(self, slot: _Slot, main: torch.cuda.Stream, device_frame: Optional[torch.Tensor] = None) -> None:
         if device_frame is not None:  # made on the caller's stream, which is `main`: a copy in stream order, no upload
             slot.frame[0].copy_(device_frame, non_blocking=True)
@@ -192,22 +247,7 @@ class FrameSegmenter:
                 slot.frame.copy_(slot.host_in, non_blocking=True)
                 slot.moved.record(self._up)
             main.wait_event(slot.moved)
-        net = self.net
-        had, old = hasattr(net, 'compute_side_outputs'), getattr(net, 'compute_side_outputs', None)
-        net.compute_side_outputs = False
-        try:
-            with torch.no_grad():
-                ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
-                logits = net.forward(slot.image)[-1]
-                ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
-                            out=slot.out, net_size=self.net_size)
-                if self.encode:
-                    ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length, subsampling=self.subsampling)
-        finally:
-            if had:
-                net.compute_side_outputs = old
-            else:
-                del net.compute_side_outputs
+        self._compute(slot)
         slot.computed.record(main)
         with torch.cuda.stream(self._down):
             self._down.wait_event(slot.computed)
@@ -247,13 +287,13 @@ class FrameSegmenter:
         if self._ready:
             return self._ready.popleft()
         if not self._flight:
-            raise RuntimeError("FrameSegmenter.result: no frame is in flight")
+            raise RuntimeError(f"{self._who}.result: no frame is in flight")
         return self._retire()
 
     def segment(self, frames: Iterable[np.ndarray]) -> Iterator[np.ndarray]:
         self._check_open()
         if self.pending:
-            raise RuntimeError("FrameSegmenter.segment: fetch the results of the frames already submitted first")
+            raise RuntimeError(f"{self._who}.segment: fetch the results of the frames already submitted first")
         for frame in frames:
             if len(self._flight) == self.depth:
                 yield self.result()
@@ -264,7 +304,7 @@ class FrameSegmenter:
     def apply(self, frame: np.ndarray) -> np.ndarray:
         self._check_open()
         if self.pending:
-            raise RuntimeError("FrameSegmenter.apply: fetch the results of the frames already submitted first")
+            raise RuntimeError(f"{self._who}.apply: fetch the results of the frames already submitted first")
         self.submit(frame)
         return self.result()
 
@@ -289,3 +329,91 @@ class FrameSegmenter:
     def __exit__(self, *exc) -> bool:
         self.close()
         return False
+
+
+class ObjectSegmenter(FrameSegmenter):
+    """``ObjectSegmenter(nets, height, width, ...)``: a FrameSegmenter for several objects.  ``nets`` are the 1..16 per-object
+    nets of a sequence (``train_online.py --multi-object``: net k - 1 is object k), distinct module objects on one GPU.  The
+    slots, events, copy streams, ``submit`` / ``result`` / ``segment`` / ``apply`` / ``close`` / ``pending``, device-frame input
+    and failure handling are FrameSegmenter's; per frame the net's stream runs ``ops.frame_prep`` once,
+    ``net.forward(image)[-1]`` of every net on that one image, and ONE ``ops.overlay_objects`` (csrc/stream.hip;
+    util/object_overlay.py states the bytes): the K logit maps never leave the device and no label map is written in between.
+
+    overlay=True    uint8 [H,W,3]: every labelled pixel blended towards ``palette[label]`` (uint8 [256,3] RGB, a numpy array
+                    or a device tensor; None = the DAVIS palette) with ``alpha`` in [0, 1]; ``encode='jpeg'``: the .jpg bytes
+    overlay=False   uint8 [H,W], the label map; ``encode='png'``: a palette PNG file of it (``ops.png_encode_indexed`` with
+                    the palette and ``huffman``), downloaded as [length | first ``budget`` bytes] like the JPEG: the default
+                    budget is a quarter of ``ops.png_indexed_capacity``, at least 1024
+
+    A lossy label map means nothing and the frame's PNG is the host's job, so 'jpeg' goes with the overlay only and 'png'
+    with the label map only.
+    """
+
+    def __init__(self, nets, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
+                 palette=None, alpha: float = 0.5, encode: Optional[str] = None, quality: int = 90,
+                 subsampling: str = '4:4:4', budget: Optional[int] = None, huffman: str = 'fixed',
+                 net_size: Optional[Tuple[int, int]] = None) -> None:
+        from util import object_overlay
+        self._set_geometry(height, width, depth, net_size)
+        self.mirror, self.overlay = bool(mirror), bool(overlay)
+        self.alpha = object_overlay.check_alpha(alpha)
+        self.nets = list(nets)
+        if not 1 <= len(self.nets) <= ops.MAX_OBJECTS:
+            raise ValueError(f"ObjectSegmenter: {len(self.nets)} nets, outside [1, {ops.MAX_OBJECTS}]")
+        if len({id(net) for net in self.nets}) != len(self.nets):
+            raise ValueError("ObjectSegmenter: the same net twice (a net's output buffer belongs to its next call): "
+                             "one module object per object")
+        self.device = self._device_of(self.nets[0])
+        for net in self.nets[1:]:
+            if self._device_of(net) != self.device:
+                raise RuntimeError(f"ObjectSegmenter: every net must be on {self.device}, got one on {self._device_of(net)}")
+        if encode not in (None, 'jpeg', 'png'):
+            raise ValueError(f"ObjectSegmenter: encode must be None, 'jpeg' or 'png', got {encode!r}")
+        if encode == 'jpeg' and not self.overlay:
+            raise ValueError("ObjectSegmenter: encode='jpeg' is lossy and a lossy label map means nothing: "
+                             "overlay=False goes with encode='png'")
+        if encode == 'png' and self.overlay:
+            raise ValueError("ObjectSegmenter: encode='png' is the palette file of the label map (overlay=False); "
+                             "the frame's PNG is the host's job")
+        if huffman not in ops.PNG_HUFFMAN:
+            raise ValueError(f"ObjectSegmenter: huffman must be one of {tuple(ops.PNG_HUFFMAN)}, got {huffman!r}")
+        if huffman != 'fixed' and encode != 'png':
+            raise ValueError("ObjectSegmenter: huffman is the table choice of encode='png'")
+        self.huffman = huffman
+        if encode == 'png':
+            self._set_jpeg(None, quality, subsampling, None)   # no JPEG: its fields at rest
+            self.encode = encode
+            self.capacity = ops.png_indexed_capacity(self.height, self.width)
+            self._set_budget(budget, max(self.capacity // 4, 1024))
+        else:
+            if encode is None and budget is not None:
+                raise ValueError("ObjectSegmenter: budget is the download budget of an encoder (encode='jpeg' or 'png')")
+            self._set_jpeg(encode, quality, subsampling, budget)
+        if palette is None:
+            self.palette = ops.default_palette(self.device)
+        else:
+            if isinstance(palette, np.ndarray):
+                palette = torch.from_numpy(object_overlay.check_palette(palette)).to(self.device)
+            if not isinstance(palette, torch.Tensor) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) \
+                    or palette.device != self.device or not palette.is_contiguous():
+                raise ValueError(f"ObjectSegmenter: a palette must be a contiguous uint8 [256,3] array or tensor on {self.device}")
+            self.palette = palette
+        self._open()
+
+    def _compute(self, slot: _Slot) -> None:
+        with torch.no_grad():
+            ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
+            logits = []
+            for net in self.nets:
+                with self._last_output_only(net):
+                    logits.append(net.forward(slot.image)[-1])
+            ops.overlay_objects(slot.frame, logits, self.mirror, self.overlay, self.palette, self.alpha, out=slot.out,
+                                net_size=self.net_size)
+            if self.encode == 'jpeg':
+                ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length, subsampling=self.subsampling)
+            elif self.encode == 'png':
+                ops.png_encode_indexed(slot.out, self.palette, out=slot.file, lengths=slot.length, huffman=self.huffman)
+
+    def close(self) -> None:
+        super().close()
+        self.nets = []

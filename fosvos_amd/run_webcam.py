@@ -13,7 +13,11 @@ the segmenter without ever being pixels on the host; other file types and files 
 (util/jpeg_read.probe is None, grey files, a non-zero status) go through PIL as before.  ``--net-height N --net-width N``
 (both, no larger than the frames) run the net at that size: the device area-averages each frame down to it in front of the net
 and interpolates the logits back up behind it (``FrameSegmenter(net_size=)``; util/frame_resample.py), and every output
-keeps the frame's size.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+keeps the frame's size.  ``--models A.pth B.pth ...`` (instead of ``--model``; file k is object k, ``--variant`` / ``--version``
+say what all of them are) streams several objects: the nets a ``train_online.py --multi-object`` run left go through
+``fosvos_hip.stream.ObjectSegmenter``, every frame through all of them, and the result is the frame with each object blended
+towards its DAVIS palette colour (``--palette-alpha``, 0..1), or with ``--no-overlay`` the label map - written to ``--output DIR``
+as palette PNG files that the device encoded.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -77,6 +81,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--net-height', type=int, default=None, metavar='N',
                    help='run the net at N rows (with --net-width; no more than the frames have)')
     p.add_argument('--net-width', type=int, default=None, metavar='N', help='run the net at N columns (with --net-height)')
+    p.add_argument('--models', type=str, nargs='+', default=None, metavar='FILE',
+                   help='several objects: one checkpoint file per object, file k is object k (instead of --model)')
+    p.add_argument('--palette-alpha', type=float, default=0.5,
+                   help='0..1: how far an object\'s pixels go towards its palette colour, with --models')
     return p
 
 
@@ -89,6 +97,30 @@ def net_size_of(parser: argparse.ArgumentParser, args) -> Optional[Tuple[int, in
     if args.net_height <= 0 or args.net_width <= 0:
         parser.error('--net-height and --net-width must be positive')
     return args.net_height, args.net_width
+
+
+SINGLE_OBJECT_ONLY = (('--overlay-color', '-oc'), ('--overlay-alpha', '-oa'), ('--no-boolean-mask', '-nbm'))
+
+
+def check_models(parser: argparse.ArgumentParser, args, argv) -> None:
+    """What --models does not go with, each refused with its reason."""
+    argv = sys.argv[1:] if argv is None else list(argv)
+
+    def given(names) -> bool:
+        return any(a == n or a.startswith(n + '=') for a in argv for n in names)
+
+    if args.model is not None:
+        parser.error('--models and --model exclude each other: one object with --model, several with --models')
+    if not args.use_network:
+        parser.error('--models with --no-network: there would be no net to run')
+    for names in SINGLE_OBJECT_ONLY:
+        if given(names):
+            parser.error('{} belongs to the single-object overlay (one colour channel, soft or boolean); several objects '
+                         'are decided by the arg-max and painted with the palette: use --palette-alpha'.format(names[0]))
+    if len(args.models) > 16:
+        parser.error('--models takes at most 16 files, got {}'.format(len(args.models)))
+    if not 0.0 <= args.palette_alpha <= 1.0:
+        parser.error('--palette-alpha must be a number in [0, 1], got {}'.format(args.palette_alpha))
 
 
 def model_file_name(variant: str, version: Optional[int]) -> str:
@@ -251,9 +283,9 @@ def write_jpeg_host(directory: Path, index: int, out: np.ndarray, quality: int, 
 
 
 def loop_frames(results: Iterator, output: Optional[Path], jpeg_quality: Optional[int] = None, subsampling: str = '4:4:4',
-                avi=None) -> List[float]:
+                avi=None, suffix: str = '.jpg') -> List[float]:
     """Takes the results as they come, logs the rate of each (the reference's line) and writes them: arrays as PNGs (as
-    JPEGs by PIL where ``jpeg_quality`` is given), ``bytes`` - files the device encoded - as they are.  ``avi`` (a
+    JPEGs by PIL where ``jpeg_quality`` is given), ``bytes`` - files the device encoded, named by ``suffix`` - as they are.  ``avi`` (a
     util.mjpeg_avi.AviWriter) takes the JPEG files instead of the directory ``output``."""
     rates = []
     start_time = time.time()
@@ -267,7 +299,7 @@ def loop_frames(results: Iterator, output: Optional[Path], jpeg_quality: Optiona
             avi.write(out)
         elif output is not None:
             if isinstance(out, bytes):
-                (output / ('%05d.jpg' % index)).write_bytes(out)
+                (output / ('%05d%s' % (index, suffix))).write_bytes(out)
             elif jpeg_quality is not None:
                 write_jpeg_host(output, index, out, jpeg_quality, subsampling)
             else:
@@ -298,6 +330,8 @@ def main(argv=None) -> List[float]:
     parser = build_parser()
     args = parser.parse_args(argv)
     net_size = net_size_of(parser, args)
+    if args.models is not None:
+        check_models(parser, args, argv)
     if not args.use_cuda:
         raise RuntimeError('--no-cuda: the HIP path has no CPU fallback')
     if args.variant == 'mimic' and args.use_network:
@@ -351,18 +385,28 @@ def main(argv=None) -> List[float]:
             if jpeg and subsampling != '4:4:4':
                 return loop_frames(mirrored, output, args.jpeg_quality, subsampling)
             return loop_frames(mirrored, output, args.jpeg_quality) if jpeg else loop_frames(mirrored, output)
-        net = get_network(args.variant, args.version, model=args.model).cuda().eval()  # (the nets here run eval-mode BatchNorm only)
+        if args.models is not None:
+            nets = [get_network(args.variant, args.version, model=m).cuda().eval() for m in args.models]
+        else:
+            net = get_network(args.variant, args.version, model=args.model).cuda().eval()  # (the nets here run eval-mode BatchNorm only)
         first = next(frames, None)
         if first is None:
             return []
-        from fosvos_hip.stream import FrameSegmenter
+        from fosvos_hip.stream import FrameSegmenter, ObjectSegmenter
         encode = dict(encode='jpeg', quality=args.jpeg_quality) if jpeg else {}
         if jpeg and subsampling != '4:4:4':
             encode['subsampling'] = subsampling
         if net_size is not None:
             encode['net_size'] = net_size
+        if args.models is not None and not args.overlay and output is not None and not jpeg:
+            encode['encode'] = 'png'  # the label maps as palette files, encoded on the device
         if to_avi:
             avi = open_avi(args.output, first, args.fps)
+        if args.models is not None:
+            with ObjectSegmenter(nets, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror,
+                                 overlay=args.overlay, alpha=args.palette_alpha, **encode) as seg:
+                return loop_frames(seg.segment(chain_first(first, frames)), output, avi=avi,
+                                   suffix='.png' if seg.encode == 'png' else '.jpg')
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
                             boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha, **encode) as seg:
             return loop_frames(seg.segment(chain_first(first, frames)), output, avi=avi)

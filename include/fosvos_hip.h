@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 31
+#define FOSVOS_ABI_VERSION 32
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -563,6 +563,31 @@ int fosvos_frame_prep_scaled(const uint8_t *frames, int N, int Hf, int Wf, int H
                              float *image, int device, void *stream);
 int fosvos_overlay_scaled(const uint8_t *frames, const float *logits, int N, int Hf, int Wf, int Hn, int Wn, int mirror,
                           int mode, int channel, double alpha, uint8_t *out, int device, void *stream);
+
+/* Several objects a stream (ABI 32, opt-in): the K logit maps of K per-object nets on the same frames (`logits` as for
+ * fosvos_merge_objects: a host array of K device pointers that travel by value, 1 <= K <= FOSVOS_MAX_OBJECTS) are merged
+ * and painted in one pass; no label map is written in between.  util/object_overlay.py states both in numpy; every byte is
+ * exact.
+ *   label    0 where no object's value is >= 0 (a NaN never is, -0.0 is), else 1 + the lowest k among those that hold the
+ *            largest such value: the rule of fosvos_merge_objects
+ *   pixel    label 0: the (mirrored) frame's three bytes.  Label k: per BGR channel c, with col = palette[k][2 - c] and the
+ *            frame's byte b, in fp64 and one operation at a time: v = b + alpha * (col - b), out = (uint8)(v + 0.5)
+ *   palette  uint8 [256][3] RGB in device memory; entries 1..K are read, once per workgroup
+ *   alpha    finite, in [0, 1] (0: the frame; 1: the pure colour)
+ *
+ * fosvos_overlay_objects: logits[k] fp32 [N,1,H,W] -> out uint8 [N,H,W,3].  4 K + 3 B read and 3 B written per pixel.
+ *
+ * fosvos_overlay_objects_scaled: logits[k] fp32 [N,1,Hn,Wn]; the value of object k at an output pixel is the v of
+ * fosvos_overlay_scaled (4 Hf Wf times the bilinear logit, fp64, that order), the taps taken once for all K maps.
+ *   mode 0  out uint8 [N,Hf,Wf,3], the overlay
+ *   mode 1  out uint8 [N,Hf,Wf], the label map (`frames`, `mirror`, `palette`, `alpha` unused)
+ * Sizes as for fosvos_overlay_scaled.  The unscaled label map is fosvos_merge_objects.
+ * Every map 4-byte aligned, nothing else needs more than its type's alignment.  One launch each, no workspace, no state. */
+int fosvos_overlay_objects(const uint8_t *frames, const float *const *logits, int K, int N, int H, int W, int mirror,
+                           const uint8_t *palette, double alpha, uint8_t *out, int device, void *stream);
+int fosvos_overlay_objects_scaled(const uint8_t *frames, const float *const *logits, int K, int N, int Hf, int Wf, int Hn,
+                                  int Wn, int mirror, int mode, const uint8_t *palette, double alpha, uint8_t *out, int device,
+                                  void *stream);
 
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
