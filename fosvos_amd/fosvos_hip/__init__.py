@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 
@@ -223,6 +223,10 @@ SIGNATURES = {
     "fosvos_jf_labels_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "fosvos_jf_counts_labels": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                         c_int, c_void_p]),
+    "fosvos_components_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fosvos_component_roots": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_clean_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_png_indexed_capacity_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fosvos_png_encode_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                           c_void_p, c_size_t, c_int, c_void_p]),

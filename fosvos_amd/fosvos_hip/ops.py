@@ -1155,6 +1155,73 @@ def jf_counts(logits: torch.Tensor, gt: torch.Tensor, radius: Optional[int] = No
     return out
 
 
+# ------------------------------------------------------------------------------------------ mask cleaning (components.hip)
+def component_roots(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_component_roots: logits fp32 [N,1,H,W] -> int32 [N,H,W]: -1 where ``logits >= 0`` does not hold, else the
+    smallest raster index ``y * W + x`` of the pixel's 8-connected component (util/mask_components.component_roots).
+    Launched on the current stream, no synchronisation."""
+    _need_eval(logits, _F32, "component_roots logits")
+    n, h, w = _logit_shape(logits, "component_roots")
+    if h * w >= 1 << 31 or n > 65535:
+        raise ValueError(f"component_roots: N={n} (<= 65535) H={h} W={w} (H W < 2^31)")
+    out = _out_like(out, (n, h, w), torch.int32, logits, "component_roots")
+    dev, st = _ctx(logits)
+    e0 = _pb()
+    check(lib().fosvos_component_roots(logits.data_ptr(), n, h, w, out.data_ptr(), None, 0, dev, st), "component_roots")
+    _pe(e0, "component_roots", 0.0, 8.0 * n * h * w)
+    return out
+
+
+def clean_components(logits: torch.Tensor, seed: Optional[torch.Tensor] = None, radius: int = 0, min_area: int = 0,
+                     largest: bool = False, chain: bool = False, fill: float = -100.0, out: Optional[torch.Tensor] = None,
+                     kept: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_clean_components: logits fp32 [N,1,H,W] -> fp32 [N,1,H,W] with every foreground pixel (``logits >= 0``) of a
+    component that is not kept set to ``fill`` (finite, < 0) and every other value passed bit for bit
+    (util/mask_components.clean_sequence states the rules).  A component stays when its area is >= ``min_area`` and, with a
+    non-empty seed, it has a pixel within ``radius`` (0..63) of it; ``largest`` keeps only the largest of those.  ``seed``:
+    uint8 [N,H,W], a non-zero byte is a set pixel; with ``chain`` uint8 [1,H,W] or None for frame 0, and frame n is gated by
+    what frame n - 1 kept.  ``out`` may be ``logits`` itself; ``kept`` (uint8 [N,H,W]) receives 1 on kept pixels.  Launched
+    on the current stream, no synchronisation."""
+    _need_eval(logits, _F32, "clean_components logits")
+    n, h, w = _logit_shape(logits, "clean_components")
+    if h * w >= 1 << 31 or n > 65535:
+        raise ValueError(f"clean_components: N={n} (<= 65535) H={h} W={w} (H W < 2^31)")
+    for name, v in (("radius", radius), ("min_area", min_area)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"clean_components: {name} must be an integer, got {v!r}")
+    if not 0 <= radius <= 63:
+        raise ValueError(f"clean_components: radius {radius} outside [0, 63]")
+    if not 0 <= min_area < 1 << 31:
+        raise ValueError(f"clean_components: min_area {min_area} must be >= 0")
+    fill = float(fill)
+    if not -3.4028234663852886e38 <= fill < 0:  # finite as a float32 too
+        raise ValueError(f"clean_components: fill must be finite and negative, got {fill!r}")
+    if seed is not None:
+        _need_eval(seed, torch.uint8, "clean_components seed")
+        want = (1, h, w) if chain else (n, h, w)
+        if tuple(seed.shape) != want:
+            raise ValueError(f"clean_components: seed must be {want}{' with chain' if chain else ''}, got {tuple(seed.shape)}")
+    if out is None:
+        out = torch.empty_like(logits)
+    else:
+        _need_eval(out, _F32, "clean_components out")
+        if tuple(out.shape) != (n, 1, h, w):
+            raise ValueError(f"clean_components: out must be {(n, 1, h, w)}, got {tuple(out.shape)}")
+    if kept is not None:
+        _need_eval(kept, torch.uint8, "clean_components kept")
+        if tuple(kept.shape) != (n, h, w):
+            raise ValueError(f"clean_components: kept must be {(n, h, w)}, got {tuple(kept.shape)}")
+    _same_device("clean_components", logits, out, *[t for t in (seed, kept) if t is not None])
+    L = lib()
+    ws, wsn = _WS.get(L.fosvos_components_workspace_bytes(n, h, w), logits.device)
+    dev, st = _ctx(logits)
+    e0 = _pb()
+    check(L.fosvos_clean_components(logits.data_ptr(), _p(seed), n, h, w, radius, min_area, int(bool(largest)),
+                                    int(bool(chain)), fill, out.data_ptr(), _p(kept), ws, wsn, dev, st), "clean_components")
+    _pe(e0, "clean_components", 0.0, 25.0 * n * h * w)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ PNG files (png.hip)
 def png_capacity(h: int, w: int) -> int:
     """Bytes ``png_encode`` reserves per frame: the layout's size bound (util/png_layout.max_file_bytes)."""

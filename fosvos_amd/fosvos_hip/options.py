@@ -1,7 +1,8 @@
 """The switches of the Python face, declared: what the training loops decide (LoopOptions) and what a model's passes decide
 (EngineOptions).  ``from_env`` of each is the ONLY place of the package that parses a ``FOSVOS_*`` switch; everything else
 takes an options object.  The defaults are the measured best; every switch selects between two paths that both stay tested.
-The table of all of them is in DESIGN.md (section 2).
+The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleaning) is opt-in by being
+passed and has no environment switch.
 
 No torch and no library load here: importable anywhere.
 """
@@ -9,7 +10,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Mapping
+from typing import Mapping, Optional
 
 
 def _on(environ: Mapping[str, str], name: str) -> bool:
@@ -122,6 +123,43 @@ class EngineOptions:
                    head_uniform=_on(environ, "HEAD_UNIFORM"), stream_probe=_on(environ, "STREAM_PROBE"),
                    resnet_mfma=_on(environ, "RESNET_MFMA"), resnet_fuse_first=_on(environ, "RESNET_FUSE_FIRST"),
                    resnet_aux=_opt_in(environ, "RESNET_AUX"))
+
+
+@dataclass(frozen=True)
+class CleanOptions:
+    """Cleaning a mask by its shape (``ops.clean_components``; util/mask_components.py states the rules), for
+    ``FrameSegmenter(clean=)`` and ``test_fast(clean=)``.  Opt-in: None where it is accepted means no cleaning, and this
+    class reads no environment variable."""
+
+    # components of fewer pixels are dropped (an area equal to min_area stays)
+    min_area: int = 0
+    # keep only the largest of the components that are left
+    largest: bool = False
+    # None: no temporal gate.  0..63: keep only components with a pixel within this many pixels of what the frame before
+    # kept (of the initial seed for the first frame); a frame that kept nothing gates nothing in the next
+    temporal_radius: Optional[int] = None
+    # what a dropped pixel's logit becomes: finite (the overlay interpolates logits) and negative
+    fill: float = -100.0
+
+    def __post_init__(self) -> None:
+        if isinstance(self.min_area, bool) or not isinstance(self.min_area, int) or not 0 <= self.min_area < 1 << 31:
+            raise ValueError(f"CleanOptions: min_area must be an integer >= 0, got {self.min_area!r}")
+        if not isinstance(self.largest, bool):
+            raise ValueError(f"CleanOptions: largest must be a bool, got {self.largest!r}")
+        r = self.temporal_radius
+        if r is not None and (isinstance(r, bool) or not isinstance(r, int) or not 0 <= r <= 63):
+            raise ValueError(f"CleanOptions: temporal_radius must be None or an integer in 0..63, got {r!r}")
+        if isinstance(self.fill, bool) or not isinstance(self.fill, (int, float)) \
+                or not -3.4028234663852886e38 <= self.fill < 0:
+            raise ValueError(f"CleanOptions: fill must be finite and negative, got {self.fill!r}")
+
+    @property
+    def chain(self) -> bool:
+        return self.temporal_radius is not None
+
+    def as_dict(self) -> dict:
+        return {'min_area': self.min_area, 'largest': self.largest, 'temporal_radius': self.temporal_radius,
+                'fill': float(self.fill)}
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

@@ -35,6 +35,13 @@ form (smaller files; the default budget stays the quarter).  ``encode=None`` is 
 inside its own (csrc/stream.hip; util/frame_resample.py states both).  Everything else - the uploads, the output, the JPEG
 capacity and budget, the downloads - stays at the frame's size.  ``None`` or the frame's own size is the object described above.
 
+``clean=CleanOptions(...)`` (opt-in, ``fosvos_hip.options``) puts ONE ``ops.clean_components`` between the net and the overlay,
+in place on the net's logits (csrc/components.hip; util/mask_components.py states the rules): connected components of the mask
+that are too small, not the largest, or - ``temporal_radius`` - too far from what the frame before kept become background.
+With ``net_size`` it runs at the net's size, the radius in net pixels.  The temporal gate needs one more device buffer, the
+segmenter's seed: the kept mask of the last frame computed, written by that frame's call and read by the next one's;
+``seed(mask)`` sets it by hand.  ``None`` is the object described above.
+
 ``ObjectSegmenter`` (opt-in) is the same object for several objects a frame: K per-object nets run on the slot's one image and
 ONE ``ops.overlay_objects`` merges their logits and paints the palette overlay (csrc/stream.hip; util/object_overlay.py
 states the bytes).  Its label-map form can end in a palette PNG (``encode='png'``, ``ops.png_encode_indexed``), which leaves the
@@ -53,6 +60,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .options import CleanOptions
 
 
 _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that the file starts 8-byte aligned
@@ -90,15 +98,24 @@ class FrameSegmenter:
                      with ``encode='jpeg'`` the same picture as ``bytes``, a complete .jpg file of quality ``quality``
     segment(frames)  generator: outputs in input order, ``depth`` frames in flight
     apply(frame)     one frame, synchronously
+    seed(mask)       with ``clean.temporal_radius``: the mask (uint8 or bool, the frame's size or the net's; non-zero = object)
+                     the next submitted frame is gated by, e.g. the annotation the net was fine-tuned on; never called, the
+                     first frame is not gated
     close()          wait for what is in flight and release every buffer
     """
+
+    clean: Optional[CleanOptions] = None  # (ObjectSegmenter has none)
+    _seed = None
 
     def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
                  quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None,
-                 net_size: Optional[Tuple[int, int]] = None) -> None:
+                 net_size: Optional[Tuple[int, int]] = None, clean: Optional[CleanOptions] = None) -> None:
         from util import frame_overlay
         self._set_geometry(height, width, depth, net_size)
+        if clean is not None and not isinstance(clean, CleanOptions):
+            raise ValueError(f"{self._who}: clean must be a fosvos_hip.options.CleanOptions or None, got {type(clean).__name__}")
+        self.clean = clean
         frame_overlay.check_color(color)
         self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
         self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
@@ -167,6 +184,11 @@ class FrameSegmenter:
             self._rest = torch.cuda.Stream(device=self.device) if self.encode else None  # second copies of long files
             self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget, self.net_size)
                                        for _ in range(self.depth)]
+            # the temporal gate's seed: what the last frame computed kept, at the net's size.  Empty = no gate (the rule
+            # of an empty seed), so a segmenter nobody seeded starts ungated
+            chained = self.clean is not None and self.clean.chain
+            self._seed = torch.zeros((1,) + tuple(self.net_size or (h, w)), dtype=torch.uint8, device=self.device) \
+                if chained else None
         self._flight: Deque[_Slot] = deque()     # submitted, oldest first
         self._ready: Deque[Union[np.ndarray, bytes]] = deque()  # retired by a submit that needed the slot, not yet asked for
 
@@ -234,6 +256,15 @@ class FrameSegmenter:
         with self._last_output_only(self.net), torch.no_grad():
             ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
             logits = self.net.forward(slot.image)[-1]
+            if self.clean is not None:
+                # in place on the net's output.  The seed is read AND written by this one call (chain over one frame: gated
+                # by self._seed, the kept mask goes back into it).  Every slot's compute is issued on the one net's
+                # stream in submit order, so frame t finds frame t - 1's kept mask there without an event of its own
+                c = self.clean
+                logits = logits.contiguous()
+                ops.clean_components(logits, self._seed, 0 if c.temporal_radius is None else c.temporal_radius, c.min_area,
+                                     c.largest, chain=c.chain, fill=c.fill, out=logits,
+                                     kept=None if self._seed is None else self._seed)
             ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
                         out=slot.out, net_size=self.net_size)
             if self.encode:
@@ -308,10 +339,37 @@ class FrameSegmenter:
         self.submit(frame)
         return self.result()
 
+    def seed(self, mask) -> None:
+        """Set the temporal gate's seed (see the class)."""
+        self._check_open()
+        if self._seed is None:
+            raise RuntimeError(f"{self._who}.seed: there is no temporal gate (clean=CleanOptions(temporal_radius=...))")
+        if isinstance(mask, torch.Tensor):
+            mask = mask.detach().cpu().numpy()
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.uint8, np.bool_) or mask.ndim != 2:
+            raise ValueError(f"{self._who}.seed: a uint8 or bool [H,W] mask, got {mask.dtype} {mask.shape}")
+        hn, wn = self._seed.shape[1:]
+        if mask.shape == (self.height, self.width) and (hn, wn) != (self.height, self.width):
+            # to the net's size: a net pixel is set when a frame pixel it averages is (util/frame_resample.box_weights)
+            from util import frame_resample
+            rows = frame_resample.box_weights(self.height, hn) > 0
+            cols = frame_resample.box_weights(self.width, wn) > 0
+            mask = (rows.astype(np.int64) @ (mask != 0).astype(np.int64) @ cols.T.astype(np.int64)) > 0
+        if mask.shape != (hn, wn):
+            raise ValueError(f"{self._who}.seed: the mask must be {(self.height, self.width)} or the net's {(hn, wn)}, "
+                             f"got {mask.shape}")
+        if self.mirror:  # the mask is in the frame's coordinates, the net sees the mirrored frame
+            mask = mask[:, ::-1]
+        host = torch.from_numpy(np.ascontiguousarray((mask != 0).astype(np.uint8)))[None]
+        with torch.cuda.device(self.device):
+            self._seed.copy_(host)  # on the current stream, the net's: ordered with the frames before and behind
+
     def close(self) -> None:
         if self._closed:
             return
         self._closed = True
+        self._seed = None
         for slot in self._flight:
             try:
                 slot.moved.synchronize()
@@ -352,8 +410,11 @@ class ObjectSegmenter(FrameSegmenter):
     def __init__(self, nets, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  palette=None, alpha: float = 0.5, encode: Optional[str] = None, quality: int = 90,
                  subsampling: str = '4:4:4', budget: Optional[int] = None, huffman: str = 'fixed',
-                 net_size: Optional[Tuple[int, int]] = None) -> None:
+                 net_size: Optional[Tuple[int, int]] = None, clean=None) -> None:
         from util import object_overlay
+        if clean is not None:
+            raise ValueError("ObjectSegmenter: clean= cleans the mask of ONE object (FrameSegmenter); per-object cleaning of "
+                             "K logit maps before the merge is not built")
         self._set_geometry(height, width, depth, net_size)
         self.mirror, self.overlay = bool(mirror), bool(overlay)
         self.alpha = object_overlay.check_alpha(alpha)

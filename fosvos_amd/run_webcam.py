@@ -17,7 +17,10 @@ keeps the frame's size.  ``--models A.pth B.pth ...`` (instead of ``--model``; f
 say what all of them are) streams several objects: the nets a ``train_online.py --multi-object`` run left go through
 ``fosvos_hip.stream.ObjectSegmenter``, every frame through all of them, and the result is the frame with each object blended
 towards its DAVIS palette colour (``--palette-alpha``, 0..1), or with ``--no-overlay`` the label map - written to ``--output DIR``
-as palette PNG files that the device encoded.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+as palette PNG files that the device encoded.  ``--clean-min-area N``, ``--clean-largest`` and ``--clean-temporal R`` (any of them;
+single object only) clean the net's mask on the device before the overlay (``FrameSegmenter(clean=)``;
+util/mask_components.py): connected components that are too small, not the largest, or further than R net pixels from what the
+frame before kept are dropped; ``--clean-seed FILE.png`` is the mask the first frame is gated by.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -85,7 +88,48 @@ def build_parser() -> argparse.ArgumentParser:
                    help='several objects: one checkpoint file per object, file k is object k (instead of --model)')
     p.add_argument('--palette-alpha', type=float, default=0.5,
                    help='0..1: how far an object\'s pixels go towards its palette colour, with --models')
+    p.add_argument('--clean-min-area', type=int, default=None, metavar='N',
+                   help='clean the mask on the device: drop connected components of fewer than N pixels')
+    p.add_argument('--clean-largest', action='store_true', help='clean the mask on the device: keep the largest component only')
+    p.add_argument('--clean-temporal', type=int, default=None, metavar='R',
+                   help='clean the mask on the device: keep only components within R (0..63) net pixels of what the '
+                        'frame before kept')
+    p.add_argument('--clean-seed', type=str, default=None, metavar='FILE.png',
+                   help='the mask --clean-temporal starts from (non-zero = object; the frames\' or the net\'s size), '
+                        'e.g. the annotation the net was fine-tuned on')
     return p
+
+
+def clean_of(parser: argparse.ArgumentParser, args):
+    """The CleanOptions of --clean-min-area / --clean-largest / --clean-temporal, or None when none of them is given; what
+    they do not go with is refused with its reason."""
+    wanted = args.clean_min_area is not None or args.clean_largest or args.clean_temporal is not None
+    if args.clean_seed is not None and args.clean_temporal is None:
+        parser.error('--clean-seed is the mask --clean-temporal starts from: give --clean-temporal R')
+    if not wanted:
+        return None
+    if not args.use_network:
+        parser.error('--clean-min-area / --clean-largest / --clean-temporal clean the net\'s mask: --no-network runs no net')
+    if args.models is not None:
+        parser.error('--clean-min-area / --clean-largest / --clean-temporal clean the mask of one object (--model): '
+                     'per-object cleaning with --models is not built')
+    from fosvos_hip.options import CleanOptions
+    try:
+        return CleanOptions(min_area=0 if args.clean_min_area is None else args.clean_min_area, largest=args.clean_largest,
+                            temporal_radius=args.clean_temporal)
+    except ValueError as e:
+        parser.error(str(e).replace('CleanOptions: min_area', '--clean-min-area').replace(
+            'CleanOptions: temporal_radius', '--clean-temporal'))
+
+
+def read_seed(path: str) -> np.ndarray:
+    """--clean-seed: uint8 [H,W], non-zero = object."""
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.asarray(im)
+    if a.ndim == 3:
+        a = a.max(axis=2)
+    return np.ascontiguousarray((a != 0).astype(np.uint8))
 
 
 def net_size_of(parser: argparse.ArgumentParser, args) -> Optional[Tuple[int, int]]:
@@ -330,6 +374,7 @@ def main(argv=None) -> List[float]:
     parser = build_parser()
     args = parser.parse_args(argv)
     net_size = net_size_of(parser, args)
+    clean = clean_of(parser, args)
     if args.models is not None:
         check_models(parser, args, argv)
     if not args.use_cuda:
@@ -407,8 +452,12 @@ def main(argv=None) -> List[float]:
                                  overlay=args.overlay, alpha=args.palette_alpha, **encode) as seg:
                 return loop_frames(seg.segment(chain_first(first, frames)), output, avi=avi,
                                    suffix='.png' if seg.encode == 'png' else '.jpg')
+        if clean is not None:  # (absent: the segmenter is constructed exactly as it was)
+            encode['clean'] = clean
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
                             boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha, **encode) as seg:
+            if args.clean_seed is not None:
+                seg.seed(read_seed(args.clean_seed))
             return loop_frames(seg.segment(chain_first(first, frames)), output, avi=avi)
     finally:
         if avi is not None:

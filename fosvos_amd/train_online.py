@@ -15,6 +15,7 @@ import timeit
 from pathlib import Path
 from typing import Optional
 
+import numpy as np
 import torch
 from torch import optim
 
@@ -43,6 +44,7 @@ fast_test = False           # --fast-test: grouped forward passes, PNG files enc
 png_fitted = False          # --png-fitted (with --fast-test): Huffman codes fitted to each segment of the PNG files
 device_decode = False       # --device-decode: the test pass's JPEG frames are decoded on the device (dataloaders/device_decode.py)
 multi_object = False        # --multi-object: one net per object, merged and scored on the device (train_and_test_objects)
+clean = None                # --clean-min-area / --clean-largest / --clean-temporal (with --fast-test): a CleanOptions
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
 
@@ -51,7 +53,32 @@ sequences_val = ['blackswan', 'bmx-trees', 'breakdance', 'camel', 'car-roundabou
                  'libby', 'motocross-jump', 'paragliding-launch', 'parkour', 'scooter-black', 'soapbox']
 
 
+def _train_annotation(data_loader) -> Optional[np.ndarray]:
+    """``gt >= 0.5`` of the one-shot training sample at the frame's own size (uint8 [H,W]), or None where the loader does
+    not hold exactly one untransformed sample."""
+    dataset = getattr(data_loader, 'dataset', None)
+    if dataset is None or len(dataset) != 1 or getattr(dataset, 'transform', None) is not None:
+        return None
+    gt = np.squeeze(np.asarray(dataset[0]['gt'], dtype=np.float32))
+    return (gt >= 0.5).astype(np.uint8) if gt.ndim == 2 else None
+
+
+def _clean_seed(train_seed, annotations, data_loader, seq_name: str) -> Optional[np.ndarray]:
+    """The first seed of --clean-temporal: the training sample's annotation when this call trained, else the first test
+    frame's annotation when --score gives one, else None."""
+    if train_seed is not None:
+        return train_seed
+    if annotations is not None and len(data_loader.dataset):
+        first = data_loader.dataset[0]
+        ann = annotations(first.get('seq_name', seq_name), first['fname'])
+        if ann is not None:
+            return (np.asarray(ann) != 0).astype(np.uint8)
+    log.info('Clean {0}: no annotation to start the temporal gate from, the first frame is not gated'.format(seq_name))
+    return None
+
+
 def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: OnlineSettings) -> None:
+    train_seed = None
     io_helper.write_settings(save_dir_models, net_provider.name, settings, variant_offline=settings.variant_offline,
                              variant_online=settings.variant_online)
     summary_writer = _get_summary_writer(path_stem)
@@ -63,6 +90,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
         optimizer = net_provider.get_optimizer()
         _train(net_provider, data_loader, optimizer, summary_writer, seq_name, settings.start_epoch, settings.n_epochs,
                settings.avg_grad_every_n, settings.snapshot_every_n)
+        if clean is not None and clean.chain:
+            train_seed = _train_annotation(data_loader)
 
     if settings.is_testing:
         if not settings.is_training:
@@ -76,8 +105,13 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                         str(settings.variant_online))
         if fast_test:
             annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
+            cleaning = {}
+            if clean is not None:  # (absent: the call is what it was)
+                cleaning['clean'] = clean
+                if clean.chain:
+                    cleaning['clean_seed'] = _clean_seed(train_seed, annotations, data_loader, seq_name)
             result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name,
-                                                 png_huffman='fitted' if png_fitted else 'fixed')
+                                                 png_huffman='fitted' if png_fitted else 'fixed', **cleaning)
             if result is not None:
                 log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
                 experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
@@ -542,7 +576,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects
+    global multi_object, synthetic_objects, clean
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -553,6 +587,11 @@ def main(argv=None):
     png_fitted = bool(args.png_fitted)
     device_decode = bool(args.device_decode)
     multi_object = bool(args.multi_object)
+    clean = None
+    if args.clean_min_area is not None or args.clean_largest or args.clean_temporal is not None:
+        from fosvos_hip.options import CleanOptions
+        clean = CleanOptions(min_area=args.clean_min_area or 0, largest=bool(args.clean_largest),
+                             temporal_radius=args.clean_temporal)
     synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':

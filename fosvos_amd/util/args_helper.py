@@ -4,7 +4,7 @@ Same flag names and meanings.  The reference declares ``type=Optional[str]`` for
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
 --data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
---multi-object and --objects (online only).
+--multi-object, --objects, --clean-min-area, --clean-largest and --clean-temporal (online only).
 """
 import argparse
 from typing import List, Optional
@@ -56,6 +56,14 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                             help='several objects a sequence (a DAVIS 2017 tree): one net per object, fine-tuned on that '
                                  'object against everything else; the test pass merges the nets\' answers into palette PNGs '
                                  'on the device and scores J and F per object')
+        parser.add_argument('--clean-min-area', type=int, default=None, metavar='N',
+                            help='with --fast-test: clean each mask on the device, dropping connected components of fewer '
+                                 'than N pixels')
+        parser.add_argument('--clean-largest', action='store_true',
+                            help='with --fast-test: clean each mask on the device, keeping its largest component only')
+        parser.add_argument('--clean-temporal', type=int, default=None, metavar='R',
+                            help='with --fast-test: keep only components within R (0..63) pixels of what the frame before '
+                                 'kept; the first frame is gated by the training annotation')
         parser.add_argument('--objects', default=2, type=int, metavar='K',
                             help='with --multi-object --synthetic: the number of objects of the synthetic sequence (1..16)')
     if not is_online:
@@ -84,6 +92,17 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
             parser.error('--objects counts the objects of the synthetic sequence: 1..16')
     if is_online and args.png_fitted and not args.fast_test and not args.multi_object:
         parser.error('--png-fitted chooses the codes of the device PNG encoder: it needs --fast-test')
+    if is_online and (args.clean_min_area is not None or args.clean_largest or args.clean_temporal is not None):
+        if args.multi_object:
+            parser.error('--clean-min-area / --clean-largest / --clean-temporal clean the mask of one object; per-object '
+                         'cleaning under --multi-object is not built')
+        if not args.fast_test:
+            parser.error('--clean-min-area / --clean-largest / --clean-temporal clean the logits of the device test pass: '
+                         'they need --fast-test')
+        if args.clean_min_area is not None and args.clean_min_area < 0:
+            parser.error('--clean-min-area must be >= 0, got {}'.format(args.clean_min_area))
+        if args.clean_temporal is not None and not 0 <= args.clean_temporal <= 63:
+            parser.error('--clean-temporal must be 0..63, got {}'.format(args.clean_temporal))
     if is_online and args.device_decode and args.synthetic:
         parser.error('--device-decode decodes JPEG files: the synthetic sequence has none')
     args.is_training = not args.no_training

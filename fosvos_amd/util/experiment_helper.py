@@ -202,7 +202,8 @@ def _frame_groups(data_loader, group: int):
 
 
 def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
-              seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed') -> Optional[dict]:
+              seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed', clean=None,
+              clean_seed: Optional[np.ndarray] = None) -> Optional[dict]:
     """The test pass with the PNG files made on the device.  Up to ``group`` consecutive frames of one shape are uploaded
     as one batch and forwarded ``forward_batch`` frames a call into one logit tensor.  Two frames a call is the largest
     batch whose frames the engine computes exactly as it computes a frame alone (a batch runs as two chains of ceil(N/2)
@@ -219,12 +220,35 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     ``test_scored`` is returned (and kept in ``last_score``); without it the pass returns None.
     CPU logits take the host path: ``bytescale`` of the fp64 sigmoid, ``png_layout.encode``.
     ``png_huffman='fitted'`` (``--png-fitted``): segments may be dynamic-Huffman blocks with a code fitted to them - the
-    same pixels in smaller files (never larger, segment by segment)."""
+    same pixels in smaller files (never larger, segment by segment).
+    ``clean`` (a ``fosvos_hip.options.CleanOptions``; None: nothing changes): each group's logits go through ONE
+    ``ops.clean_components``, in place, before the counts and the bytes are taken (util/mask_components.py states the rules;
+    CPU logits: ``mask_components.clean_sequence``).  With ``clean.temporal_radius`` the group is a chain: its first frame is
+    gated by what the last frame of the group before kept - carried on the device - and the very first frame by
+    ``clean_seed`` (uint8 or bool [H,W], non-zero = object; None: not gated).  The score dict then holds the options under
+    'clean'."""
     from util import png_layout
     if png_huffman not in png_layout.HUFFMAN_MODES:
         raise ValueError('test_fast: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
     if group < 1 or forward_batch < 1:
         raise ValueError('test_fast: group and forward_batch must be at least 1, got {} and {}'.format(group, forward_batch))
+    if clean is None and clean_seed is not None:
+        raise ValueError('test_fast: clean_seed is the first seed of clean=CleanOptions(temporal_radius=...)')
+    if clean is not None:
+        from fosvos_hip.options import CleanOptions
+        if not isinstance(clean, CleanOptions):
+            raise ValueError('test_fast: clean must be a fosvos_hip.options.CleanOptions or None, got {!r}'.format(clean))
+        if clean_seed is not None and not clean.chain:
+            raise ValueError('test_fast: clean_seed is the first seed of the temporal gate: set clean.temporal_radius')
+        if clean_seed is not None:
+            clean_seed = np.asarray(clean_seed)
+            if clean_seed.ndim != 2 or clean_seed.dtype not in (np.uint8, np.bool_):
+                raise ValueError('test_fast: clean_seed must be a uint8 or bool [H,W] mask, got {} {}'.format(
+                    clean_seed.dtype, clean_seed.shape))
+            clean_seed = np.ascontiguousarray((clean_seed != 0).astype(np.uint8))
+    seed_host = clean_seed   # the chain's seed for the next group: host form (CPU logits) ...
+    seed_dev = None          # ... and device form, uint8 [1,H,W]
+    kept_dev = {}            # (n, h, w) -> the group's kept masks
     log.info('Testing Network (fast)')
     net = net_provider.network
     n_frames = len(data_loader.dataset)
@@ -288,8 +312,29 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                     fnames.append(fname)
                     scored.append(ann is not None)
             paths = [Path(save_dir) / seqs[k] / '{0}.png'.format(fnames[k]) for k in range(first, first + n)]
+            if clean is not None and seed_host is not None and seed_host.shape != (h, w):
+                if first == 0:
+                    raise ValueError('test_fast: clean_seed is {}, the logits are {}'.format(seed_host.shape, (h, w)))
+                seed_host = seed_dev = None  # the frames changed their size: the chain starts again, ungated
             if logits.is_cuda:
                 from fosvos_hip import ops
+                if clean is not None:
+                    if clean.chain:
+                        if seed_dev is not None and tuple(seed_dev.shape) != (1, h, w):
+                            seed_dev = None
+                        if seed_dev is None and first == 0 and seed_host is not None:
+                            seed_dev = torch.from_numpy(seed_host[None]).to(logits.device)
+                        if (n, h, w) not in kept_dev:
+                            kept_dev[(n, h, w)] = torch.empty((n, h, w), dtype=torch.uint8, device=logits.device)
+                        kept = kept_dev[(n, h, w)]
+                        ops.clean_components(logits, seed_dev, clean.temporal_radius, clean.min_area, clean.largest,
+                                             chain=True, fill=clean.fill, out=logits, kept=kept)
+                        # what the group's last frame kept gates the next group's first: a copy in stream order, no host
+                        if seed_dev is None:
+                            seed_dev = torch.empty((1, h, w), dtype=torch.uint8, device=logits.device)
+                        seed_dev.copy_(kept[n - 1:n])
+                    else:
+                        ops.clean_components(logits, None, 0, clean.min_area, clean.largest, fill=clean.fill, out=logits)
                 if annotations is not None:
                     if counts_dev is None:
                         counts_dev = torch.zeros((n_frames, 6), dtype=torch.int32, device=logits.device)
@@ -311,7 +356,15 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                     retire(pending)  # the previous group's files, while the device works on this group
                 pending = (host_store, n, cap, landed, paths)
             else:
-                x = logits[:, 0].numpy().astype(np.float64)
+                x = logits[:, 0].numpy()
+                if clean is not None:
+                    from util import mask_components
+                    x, kept = mask_components.clean_sequence(
+                        np.ascontiguousarray(x, dtype=np.float32), seed_host if clean.chain else None,
+                        clean.temporal_radius if clean.chain else 0, clean.min_area, clean.largest, chain=clean.chain,
+                        fill=clean.fill)
+                    seed_host = kept[n - 1].astype(np.uint8) if clean.chain else None
+                x = x.astype(np.float64)
                 blobs = []
                 for index in range(n):
                     if annotations is not None:
@@ -331,6 +384,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     last_fast.update(n_frames=len(fnames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
                      seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],
                      seconds_write=stage['write'], png_bytes=png_bytes, png_huffman=png_huffman)
+    if clean is not None:
+        last_fast['clean'] = clean.as_dict()
     log.info('Test {0}: {1} images in {2} groups, total test time {3} sec'.format(seq_name, len(fnames), len(group_sizes),
                                                                                  time_for_all))
     if annotations is None:
@@ -347,6 +402,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
              'F': [float(v) if k else None for v, k in zip(f, keep)],
              'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
              'seconds': time_for_all}
+    if clean is not None:
+        score['clean'] = clean.as_dict()
     last_score.clear()
     last_score.update(score)
     return score

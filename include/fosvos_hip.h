@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FOSVOS_ABI_VERSION 32
+#define FOSVOS_ABI_VERSION 33
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -470,6 +470,32 @@ size_t fosvos_png_indexed_capacity_bytes(int N, int H, int W); /* per frame */
 int fosvos_png_encode_indexed(const uint8_t *labels, const uint8_t *palette, int N, int H, int W, int huffman, uint8_t *out,
                               size_t capacity, int32_t *lengths, void *workspace, size_t workspace_bytes, int device,
                               void *stream);
+
+/* ---- cleaning a mask by its shape: connected components and a temporal gate (ABI 33) -----------------------------------
+ * The definitions are stated in numpy in util/mask_components.py; the tests compare with exact equality.  The mask of a
+ * frame is logits >= 0 (a NaN is background, -0.0 foreground), its components are 8-connected, and a component's root is
+ * the smallest raster index y * W + x of its pixels.
+ *
+ * fosvos_component_roots: logits fp32 [N,1,H,W] -> roots int32 [N,H,W]: -1 on the background, else the pixel's root.  The
+ * labels are built in `roots` itself; workspace is not used (it may be null).  Three launches.
+ *
+ * fosvos_clean_components: a component is eligible when its area is >= min_area and - with the gate on - one of its pixels
+ * lies inside the seed dilated by the disk of `radius` (0..63; 0 = touches the seed itself).  largest != 0 keeps of the
+ * eligible components only the one of the largest area, on equal areas the one with the smaller root; otherwise all eligible
+ * ones are kept.  out_logits fp32 [N,1,H,W]: a foreground pixel that is not kept becomes `fill` (finite and < 0), every
+ * other value passes bit for bit; out_logits == logits is allowed.  kept uint8 [N,H,W] (may be null): 1 on kept pixels.
+ *   chain == 0: seed uint8 [N,H,W] (non-zero = set) gates frame n with seed[n]; null: no gate.
+ *   chain != 0: seed uint8 [1,H,W] or null gates frame 0; frame n > 0 is gated by the kept mask of frame n - 1.
+ * The gate of a frame is off when its seed has no set pixel (decided on the device; the host never synchronises).
+ * Launches: (1 with a seed) + per pass (1 with a gate) + 3 + (1 with largest) + 1; a chain makes one pass per frame,
+ * otherwise all frames share one.  workspace: fosvos_components_workspace_bytes (0 for sizes outside the limits), 8-byte
+ * aligned.  Limits: N <= 65535, H W < 2^31 (FOSVOS_E_SHAPE); radius, min_area >= 0, fill, null pointers (FOSVOS_E_ARG). */
+size_t fosvos_components_workspace_bytes(int N, int H, int W);
+int fosvos_component_roots(const float *logits, int N, int H, int W, int32_t *roots, void *workspace, size_t workspace_bytes,
+                           int device, void *stream);
+int fosvos_clean_components(const float *logits, const uint8_t *seed, int N, int H, int W, int radius, int min_area,
+                            int largest, int chain, float fill, float *out_logits, uint8_t *kept, void *workspace,
+                            size_t workspace_bytes, int device, void *stream);
 
 /* ---- the streamed output frames as JPEG files, encoded on the device --------------------------------------------------
  * fosvos_jpeg_encode: frames uint8 [N,H,W,3] BGR (what fosvos_overlay writes; components = 3) or [N,H,W] grey (components =
