@@ -33,14 +33,26 @@
 //
 // Several objects a stream (opt-in; util/object_overlay.py states both): the K logit maps of K per-object nets, pointers by value.
 // fosvos_overlay_objects, one launch:
-//   k_overlay_objects         k_overlay's partition anchored on map 0; a thread takes its 16 logits from each of the K maps in
-//                             turn and keeps (best value, label) per pixel - the rule of fosvos_merge_objects - then blends
-//                             every labelled pixel towards its palette colour: b + alpha (col - b) in fp64, rounded half up.
-//                             4 K + 3 B read, 3 B written per pixel; no label map in between.
+//   k_overlay_objects         a thread takes its 16 logits from each of the K maps in turn and keeps (best value, label) per
+//                             pixel - the rule of fosvos_merge_objects - then blends every labelled pixel towards its palette
+//                             colour: b + alpha (col - b) in fp64, rounded half up.  4 K + 3 B read, 3 B written per pixel; no
+//                             label map in between.
 // fosvos_overlay_objects_scaled, one launch:
-//   k_overlay_objects_scaled  k_overlay_scaled's thread map; the taps of a pixel are taken once and applied to all K maps,
-//                             the rule then runs on the fp64 values.  Mode 0 the overlay, mode 1 the label map.
+//   k_overlay_objects_scaled  the same from [Hn,Wn] maps; the taps of a pixel are taken once and applied to all K maps, the
+//                             rule then runs on the fp64 values.  Mode 0 the overlay, mode 1 the label map.
+//
+// The four overlay kernels are one body, paint_pixels<MIRROR, Source, Paint>, behind thin __global__ wrappers.  The body owns
+// the partition above, the 48-byte load and its mirror unpack, the packing and the 16-byte stores, and the scalar loop of a
+// head or tail.  A SOURCE says where a pixel's value comes from, and with that where the groups are anchored and which store
+// goes with the anchor: MapInPlace (one fp32 map, a float) and MapsInPlace (K maps merged in fp32, a label) anchor on their
+// first map and store bytes16; MapUp (one map interpolated, a double) and MapsUp (K maps through shared taps, merged in fp64,
+// a label) anchor on the output row and store aligned uint4.  A PAINT turns the value and the frame's bytes into the output's:
+// OneChannel (level<MODE> in one channel), PaletteBlend (towards the label's colour, all three) or OneByte (a mask or a label,
+// no frame read).  k_overlay = MapInPlace + OneChannel | OneByte, k_overlay_scaled = MapUp + the same, k_overlay_objects =
+// MapsInPlace + PaletteBlend, k_overlay_objects_scaled = MapsUp + PaletteBlend | OneByte.
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -241,7 +253,10 @@ __global__ __launch_bounds__(kScaleThreads) void k_frame_prep_scaled(const uint8
     }
 }
 
-// ------------------------------------------------------------------------------------------ overlay
+// ------------------------------------------------------------------------------------------ the overlays: paints
+// A paint turns the value of a pixel and the frame's bytes b[3] into the output bytes o[0..kBytes): 3 repaint the frame, 1
+// writes a map of its own and reads no frame.
+//
 // the new byte of one pixel: `byte` is the frame's value in the overlay's channel (unused in the mask modes); x is the fp32
 // logit, or (scaled) the fp64 one - in the boolean modes any positive multiple of it
 template <int MODE, typename T>
@@ -251,78 +266,124 @@ __device__ __forceinline__ uint32_t level(T x, uint32_t byte, double a255) {
     const double p = MODE == 0 ? (x >= T(0) ? 1.0 : 0.0) : sigmoid_f64(x);
     return (uint32_t)fmin((double)byte + a255 * p, 255.0);
 }
+// MODE 0, 1: the level in one channel, the other two as they are
+template <int MODE>
+struct OneChannel {
+    static constexpr int kBytes = 3;
+    int channel;
+    double a255;
+    template <typename T>
+    __device__ __forceinline__ void operator()(T x, const uint32_t (&b)[3], uint32_t (&o)[3]) const {
+        const uint32_t b0 = b[0], b1 = b[1], b2 = b[2];  // read before the choice: selects, where a reference would branch
+        const uint32_t v = level<MODE>(x, channel == 0 ? b0 : (channel == 1 ? b1 : b2), a255);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = channel == c ? v : b[c];
+    }
+};
+// one byte a pixel: the mask of a logit (MODE 2, 3), or the label of a several-objects source as it is
+template <int MODE>
+struct OneByte {
+    static constexpr int kBytes = 1;
+    template <typename T>
+    __device__ __forceinline__ void operator()(T x, const uint32_t (&)[3], uint32_t (&o)[3]) const {
+        o[0] = level<MODE>(x, 0u, 0.0);
+    }
+    __device__ __forceinline__ void operator()(uint32_t label, const uint32_t (&)[3], uint32_t (&o)[3]) const { o[0] = label; }
+};
+using LabelByte = OneByte<2>;  // no level is taken of a label, so the mode stands for nothing
+// Several objects (util/object_overlay.py): a labelled pixel is blended towards entry `label` of the palette in all three
+// channels, b + alpha (col - b) in fp64, rounded half up; label 0 keeps b.
+// The palette's entries 1..K as B | G << 8 | R << 16 (entry 0 is never painted), read once per workgroup.  Every thread of
+// the workgroup passes here before any of them leaves.
+__device__ __forceinline__ void stage_colours(const uint8_t *__restrict__ palette, int K, uint32_t (&cols)[kMaxObjects + 1]) {
+    const int k = threadIdx.x;
+    if (k <= K)
+        cols[k] = k == 0 ? 0u : (uint32_t)palette[3 * k + 2] | ((uint32_t)palette[3 * k + 1] << 8) | ((uint32_t)palette[3 * k] << 16);
+    __syncthreads();
+}
+struct PaletteBlend {
+    static constexpr int kBytes = 3;
+    const uint32_t *cols;  // what stage_colours staged
+    double alpha;
+    __device__ __forceinline__ void operator()(uint32_t label, const uint32_t (&b)[3], uint32_t (&o)[3]) const {
+        const uint32_t col = cols[label];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double fb = (double)b[c];
+            const double v = fb + alpha * ((double)((col >> (8 * c)) & 0xffu) - fb);
+            o[c] = label ? (uint32_t)(v + 0.5) : b[c];
+        }
+    }
+};
 
-template <int MODE, bool MIRROR>
-__global__ __launch_bounds__(kStreamThreads) void k_overlay(const uint8_t *__restrict__ frames,
-                                                            const float *__restrict__ logits, uint8_t *__restrict__ out,
-                                                            int64_t L, int64_t slots, int64_t total, int channel,
-                                                            double a255) {
-    constexpr bool kBlend = MODE < 2;
-    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
-    if (gid >= total) return;
-    const int64_t seg = segment_of(gid, slots);
-    const float *__restrict__ lg = logits + seg * L;
-    const Span s = span_of(gid, seg, slots, L, lg);
-    const uint8_t *__restrict__ src = kBlend ? frames + seg * 3 * L : nullptr;
-    uint8_t *__restrict__ dst = out + seg * (kBlend ? 3 : 1) * L;
-    if (s.qb - s.qa == kGroup) {
-        float x[kGroup];
-        const floats4 *__restrict__ lv = reinterpret_cast<const floats4 *>(lg + s.qa);
+// ------------------------------------------------------------------------------------------ the overlays: sources
+// A source says where a pixel's value comes from.  open() places the thread: it takes the segment, decides where the
+// segment's groups start (the anchor) and returns the thread's span; Store is the 16-byte store that goes with that anchor.
+// load_group() and take(i), i = 0..15 in turn, serve a full group, at(q), q rising, the pixels of a head or tail.
+//
+// Maps read in place, at the frames' size: the groups start where the (first) map crosses a 16-byte boundary, so its loads
+// are aligned and the output bytes lie wherever they fall (bytes16: alignment 1).  A group's logits are loaded up front.
+struct MapInPlace {
+    using Store = bytes16;
+    const float *__restrict__ logits;
+    int64_t L;
+    const float *__restrict__ lg;  // the thread's segment
+    float x[kGroup];
+    __device__ __forceinline__ int64_t length() const { return L; }
+    __device__ __forceinline__ Span open(int64_t gid, int64_t seg, int64_t slots, const uint8_t *, int) {
+        lg = logits + seg * L;
+        return span_of(gid, seg, slots, L, lg);
+    }
+    __device__ __forceinline__ void load_group(int64_t qa) {
+        const floats4 *__restrict__ lv = reinterpret_cast<const floats4 *>(lg + qa);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const floats4 t = lv[k];
 #pragma unroll
             for (int i = 0; i < 4; ++i) x[4 * k + i] = t.v[i];
         }
-        if (kBlend) {
-            uint32_t w[12], o[12];
-            load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
+    }
+    __device__ __forceinline__ float take(int i) const { return x[i]; }
+    __device__ __forceinline__ float at(int64_t q) const { return lg[q]; }
+};
+// K maps in place, merged by the rule of fosvos_merge_objects (common.hpp: merge_take) in fp32 into a label.  The anchor is
+// map 0, so maps 1..K-1 lie wherever their base pointers put them: all of them are loaded as floats4 (alignment 4), which
+// is what they are known to have.
+struct MapsInPlace {
+    using Store = bytes16;
+    const ObjectLogits &maps;
+    int K;
+    int64_t L;
+    int64_t first;  // of the thread's segment, in floats into every map
+    uint32_t lab[kGroup];
+    __device__ __forceinline__ int64_t length() const { return L; }
+    __device__ __forceinline__ Span open(int64_t gid, int64_t seg, int64_t slots, const uint8_t *, int) {
+        first = seg * L;
+        return span_of(gid, seg, slots, L, maps.p[0] + first);
+    }
+    __device__ __forceinline__ void load_group(int64_t qa) {
+        float bv[kGroup];
 #pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = 0;
+        for (int i = 0; i < kGroup; ++i) bv[i] = -1.f, lab[i] = 0u;
+        for (int k = 0; k < K; ++k) {
+            const floats4 *__restrict__ lv = reinterpret_cast<const floats4 *>(maps.p[k] + first + qa);
 #pragma unroll
-            for (int i = 0; i < kGroup; ++i) {
-                const int px = MIRROR ? kGroup - 1 - i : i;
-                uint32_t b[3] = {byte_at(w, 3 * px), byte_at(w, 3 * px + 1), byte_at(w, 3 * px + 2)};
-                const uint32_t v = level<MODE>(x[i], channel == 0 ? b[0] : (channel == 1 ? b[1] : b[2]), a255);
+            for (int j = 0; j < 4; ++j) {
+                const floats4 t = lv[j];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int at = 3 * i + c;
-                    o[at >> 2] |= (channel == c ? v : b[c]) << (8 * (at & 3));
-                }
-            }
-            bytes16 *__restrict__ ov = reinterpret_cast<bytes16 *>(dst + 3 * s.qa);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                bytes16 t;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) t.w[i] = o[4 * k + i];
-                ov[k] = t;
-            }
-        } else {
-            bytes16 t;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                t.w[k] = level<MODE>(x[4 * k], 0, a255) | (level<MODE>(x[4 * k + 1], 0, a255) << 8) |
-                         (level<MODE>(x[4 * k + 2], 0, a255) << 16) | (level<MODE>(x[4 * k + 3], 0, a255) << 24);
-            *reinterpret_cast<bytes16 *>(dst + s.qa) = t;
-        }
-    } else {
-        for (int64_t q = s.qa; q < s.qb; ++q) {
-            if (kBlend) {
-                const int64_t sp = MIRROR ? L - 1 - q : q;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const uint32_t b = src[3 * sp + c];
-                    dst[3 * q + c] = (uint8_t)(channel == c ? level<MODE>(lg[q], b, a255) : b);
-                }
-            } else {
-                dst[q] = (uint8_t)level<MODE>(lg[q], 0, a255);
+                for (int i = 0; i < 4; ++i) merge_take(t.v[i], (uint32_t)k, bv[4 * j + i], lab[4 * j + i]);
             }
         }
     }
-}
+    __device__ __forceinline__ uint32_t take(int i) const { return lab[i]; }
+    __device__ __forceinline__ uint32_t at(int64_t q) const {
+        float bv = -1.f;
+        uint32_t label = 0u;
+        for (int k = 0; k < K; ++k) merge_take(maps.p[k][first + q], (uint32_t)k, bv, label);
+        return label;
+    }
+};
 
-// ------------------------------------------------------------------------------------------ overlay_scaled
 // Output sample x of an axis with n_src samples in and n_dst out (util/frame_resample.taps): u = (2x+1) n_src + n_dst is the
 // numerator moved up by one step, so that it is positive; `at` is its floor less that step (-1: left of the first centre).
 struct Walk {
@@ -364,107 +425,144 @@ __device__ __forceinline__ double logit_up(const float *__restrict__ a0, const f
     return top * ty.w0 + bot * ty.w1;
 }
 
-// k_overlay's thread map with rows as the segments; the groups of a row start where the OUTPUT row crosses a 16-byte boundary
-// (the logits are gathered, four floats a pixel out of a map that stays in L2, so they have no aligned side to offer).
+// What the interpolated sources share: maps of [Hn,Wn] gathered for frames of [Hf,Wf], bilinear at half-pixel centres with
+// integer weights, in fp64.  The segments are the rows; their groups start where the OUTPUT row crosses a 16-byte boundary
+// (the logits are gathered, four floats a pixel out of a map that stays in L2, so they have no aligned side to offer), which
+// makes every group store an aligned uint4.  The row's taps are taken once, the column taps walk along with the pixels.
+struct RowsUp {
+    using Store = uint4;
+    int Hf, Wf, Hn, Wn;
+    Tap ty;
+    Walk wx;
+    int64_t top, bot;  // the rows of ty, in floats into a map
+    __device__ __forceinline__ int64_t length() const { return Wf; }
+    __device__ __forceinline__ Span open(int64_t gid, int64_t seg, int64_t slots, const uint8_t *dst, int bytes) {
+        const int64_t n = seg / Hf;
+        ty = tap_of(walk_from((int)(seg - n * Hf), Hn, Hf), Hn, Hf);
+        top = (n * Hn + ty.i0) * Wn, bot = (n * Hn + ty.i1) * Wn;
+        // pixels up to the boundary: k0 (or 3 k0, 3 * 11 = 1 mod 16) + the address = 0 mod 16
+        const unsigned lead = (16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u;
+        const Span s = span_at(gid, seg, slots, Wf, (int)(bytes == 3 ? (11u * lead) & 15u : lead));
+        wx = walk_from((int)s.qa, Wn, Wf);
+        return s;
+    }
+    __device__ __forceinline__ void load_group(int64_t) {}
+    __device__ __forceinline__ Tap next_tap() {
+        const Tap tx = tap_of(wx, Wn, Wf);
+        walk_on(wx, Wn, Wf);
+        return tx;
+    }
+};
+// one map: the soft modes want the logit itself, the boolean modes only its sign
+template <bool SOFT>
+struct MapUp : RowsUp {
+    const float *__restrict__ logits;
+    __device__ __forceinline__ double take(int) {
+        const double v = logit_up(logits + top, logits + bot, next_tap(), ty);
+        return SOFT ? v / (double)(4 * Hf * Wf) : v;
+    }
+    __device__ __forceinline__ double at(int64_t) { return take(0); }
+};
+// K maps: the taps of a pixel are taken once and applied to all K maps, the merge rule then runs on the fp64 values
+struct MapsUp : RowsUp {
+    const ObjectLogits &maps;
+    int K;
+    __device__ __forceinline__ uint32_t take(int) {
+        const Tap tx = next_tap();
+        double bv = -1.0;
+        uint32_t label = 0u;
+        for (int k = 0; k < K; ++k) merge_take(logit_up(maps.p[k] + top, maps.p[k] + bot, tx, ty), (uint32_t)k, bv, label);
+        return label;
+    }
+    __device__ __forceinline__ uint32_t at(int64_t) { return take(0); }
+};
+
+// ------------------------------------------------------------------------------------------ the overlays: the skeleton
+__device__ __forceinline__ void store16(bytes16 *__restrict__ p, const uint32_t *o) {
+    bytes16 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t.w[i] = o[i];
+    *p = t;
+}
+__device__ __forceinline__ void store16(uint4 *__restrict__ p, const uint32_t *o) { *p = make_uint4(o[0], o[1], o[2], o[3]); }
+
+// Every overlay kernel is this body: the thread's span of its segment; for a full group the 48 frame bytes, unpacked
+// through the mirror permutation, a value and a paint per pixel, the bytes packed into 12 or 4 registers and stored as
+// three or one 16-byte runs; for a head or tail the same per pixel, byte by byte.
+template <bool MIRROR, typename Source, typename Paint>
+__device__ __forceinline__ void paint_pixels(Source from, const Paint paint, const uint8_t *__restrict__ frames,
+                                             uint8_t *__restrict__ out, int64_t slots, int64_t total) {
+    constexpr int NB = Paint::kBytes;
+    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
+    if (gid >= total) return;
+    const int64_t seg = segment_of(gid, slots), L = from.length();
+    const uint8_t *__restrict__ src = NB == 3 ? frames + seg * 3 * L : nullptr;
+    uint8_t *__restrict__ dst = out + seg * NB * L;
+    const Span s = from.open(gid, seg, slots, dst, NB);
+    if (__builtin_expect(s.qb - s.qa == kGroup, 1)) {  // nearly every thread: keeps the group's code in the straight line
+        from.load_group(s.qa);
+        uint32_t w[12], o[4 * NB];
+        if constexpr (NB == 3) load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
+#pragma unroll
+        for (int k = 0; k < 4 * NB; ++k) o[k] = 0;
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const auto v = from.take(i);
+            uint32_t b[3] = {0, 0, 0}, ob[3];
+            if constexpr (NB == 3) {
+                const int px = MIRROR ? kGroup - 1 - i : i;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) b[c] = byte_at(w, 3 * px + c);
+            }
+            paint(v, b, ob);
+#pragma unroll
+            for (int c = 0; c < NB; ++c) {
+                const int at = NB * i + c;
+                o[at >> 2] |= ob[c] << (8 * (at & 3));
+            }
+        }
+        typename Source::Store *__restrict__ ov = reinterpret_cast<typename Source::Store *>(dst + NB * s.qa);
+#pragma unroll
+        for (int k = 0; k < NB; ++k) store16(ov + k, o + 4 * k);
+    } else {
+        for (int64_t q = s.qa; q < s.qb; ++q) {
+            const auto v = from.at(q);
+            uint32_t b[3] = {0, 0, 0}, ob[3];
+            if constexpr (NB == 3) {
+                const int64_t sp = MIRROR ? L - 1 - q : q;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) b[c] = src[3 * sp + c];
+            }
+            paint(v, b, ob);
+#pragma unroll
+            for (int c = 0; c < NB; ++c) dst[NB * q + c] = (uint8_t)ob[c];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ the overlays: the kernels
+// MODE 0, 1 the overlay, MODE 2, 3 the mask (never mirrored: the logits already are in output order)
+template <int MODE, bool MIRROR>
+__global__ __launch_bounds__(kStreamThreads) void k_overlay(const uint8_t *__restrict__ frames,
+                                                            const float *__restrict__ logits, uint8_t *__restrict__ out,
+                                                            int64_t L, int64_t slots, int64_t total, int channel,
+                                                            double a255) {
+    if constexpr (MODE < 2)
+        paint_pixels<MIRROR>(MapInPlace{logits, L}, OneChannel<MODE>{channel, a255}, frames, out, slots, total);
+    else
+        paint_pixels<MIRROR>(MapInPlace{logits, L}, OneByte<MODE>{}, frames, out, slots, total);
+}
 template <int MODE, bool MIRROR>
 __global__ __launch_bounds__(kStreamThreads) void k_overlay_scaled(const uint8_t *__restrict__ frames,
                                                                    const float *__restrict__ logits, uint8_t *__restrict__ out,
                                                                    int Hf, int Wf, int Hn, int Wn, int64_t slots, int64_t total,
                                                                    int channel, double a255) {
-    constexpr bool kBlend = MODE < 2;
-    constexpr bool kSoft = (MODE & 1) != 0;
-    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
-    if (gid >= total) return;
-    const int64_t seg = segment_of(gid, slots), L = Wf;
-    const int64_t n = seg / Hf;
-    const int y = (int)(seg - n * Hf);
-    const uint8_t *__restrict__ src = kBlend ? frames + seg * 3 * L : nullptr;
-    uint8_t *__restrict__ dst = out + seg * (kBlend ? 3 : 1) * L;
-    // pixels up to the boundary: k0 (or 3 k0, 3 * 11 = 1 mod 16) + the address = 0 mod 16
-    const unsigned lead = (16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u;
-    const Span s = span_at(gid, seg, slots, L, (int)(kBlend ? (11u * lead) & 15u : lead));
-    const Tap ty = tap_of(walk_from(y, Hn, Hf), Hn, Hf);
-    const float *__restrict__ a0 = logits + (n * Hn + ty.i0) * Wn;
-    const float *__restrict__ a1 = logits + (n * Hn + ty.i1) * Wn;
-    const double scale = (double)(4 * Hf * Wf);
-    Walk wx = walk_from((int)s.qa, Wn, Wf);
-    if (s.qb - s.qa == kGroup) {
-        if (kBlend) {
-            uint32_t w[12], o[12];
-            load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = 0;
-#pragma unroll
-            for (int i = 0; i < kGroup; ++i) {
-                const double v = logit_up(a0, a1, tap_of(wx, Wn, Wf), ty);
-                walk_on(wx, Wn, Wf);
-                const int px = MIRROR ? kGroup - 1 - i : i;
-                uint32_t b[3] = {byte_at(w, 3 * px), byte_at(w, 3 * px + 1), byte_at(w, 3 * px + 2)};
-                const uint32_t lv =
-                    level<MODE>(kSoft ? v / scale : v, channel == 0 ? b[0] : (channel == 1 ? b[1] : b[2]), a255);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int at = 3 * i + c;
-                    o[at >> 2] |= (channel == c ? lv : b[c]) << (8 * (at & 3));
-                }
-            }
-            uint4 *__restrict__ ov = reinterpret_cast<uint4 *>(dst + 3 * s.qa);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ov[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-        } else {
-            uint32_t o[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < kGroup; ++i) {
-                const double v = logit_up(a0, a1, tap_of(wx, Wn, Wf), ty);
-                walk_on(wx, Wn, Wf);
-                o[i >> 2] |= level<MODE>(kSoft ? v / scale : v, 0, a255) << (8 * (i & 3));
-            }
-            *reinterpret_cast<uint4 *>(dst + s.qa) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-    } else {
-        for (int64_t q = s.qa; q < s.qb; ++q) {
-            const double v = logit_up(a0, a1, tap_of(wx, Wn, Wf), ty);
-            walk_on(wx, Wn, Wf);
-            const double x = kSoft ? v / scale : v;
-            if (kBlend) {
-                const int64_t sp = MIRROR ? L - 1 - q : q;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const uint32_t b = src[3 * sp + c];
-                    dst[3 * q + c] = (uint8_t)(channel == c ? level<MODE>(x, b, a255) : b);
-                }
-            } else {
-                dst[q] = (uint8_t)level<MODE>(x, 0, a255);
-            }
-        }
-    }
+    const MapUp<(MODE & 1) != 0> from = {{Hf, Wf, Hn, Wn}, logits};
+    if constexpr (MODE < 2)
+        paint_pixels<MIRROR>(from, OneChannel<MODE>{channel, a255}, frames, out, slots, total);
+    else
+        paint_pixels<MIRROR>(from, OneByte<MODE>{}, frames, out, slots, total);
 }
-
-// ------------------------------------------------------------------------------------------ overlay_objects
-// Several objects (util/object_overlay.py): the label of a pixel is the merge rule (common.hpp: merge_take) over the K maps,
-// its colour entry `label` of the palette, blended into all three channels.
-// The palette's entries 1..K as B | G << 8 | R << 16 (entry 0 is never painted), read once per workgroup.  Every thread of
-// the workgroup passes here before any of them leaves.
-__device__ __forceinline__ void stage_colours(const uint8_t *__restrict__ palette, int K, uint32_t (&cols)[kMaxObjects + 1]) {
-    const int k = threadIdx.x;
-    if (k <= K)
-        cols[k] = k == 0 ? 0u : (uint32_t)palette[3 * k + 2] | ((uint32_t)palette[3 * k + 1] << 8) | ((uint32_t)palette[3 * k] << 16);
-    __syncthreads();
-}
-// the three output bytes (in bits 0..23) of a pixel with the frame's bytes b[3] and the colour `col`, label 0 keeps b
-__device__ __forceinline__ uint32_t paint(const uint32_t (&b)[3], uint32_t label, uint32_t col, double alpha) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double fb = (double)b[c];
-        const double v = fb + alpha * ((double)((col >> (8 * c)) & 0xffu) - fb);
-        o |= (label ? (uint32_t)(v + 0.5) : b[c]) << (8 * c);
-    }
-    return o;
-}
-
-// k_overlay's partition; the groups are anchored on map 0, so maps 1..K-1 lie wherever their base pointers put them: all of
-// them are loaded as floats4 (alignment 4), which is what they are known to have.
 template <bool MIRROR>
 __global__ __launch_bounds__(kStreamThreads) void k_overlay_objects(const uint8_t *__restrict__ frames, const ObjectLogits maps,
                                                                     int K, const uint8_t *__restrict__ palette,
@@ -472,147 +570,31 @@ __global__ __launch_bounds__(kStreamThreads) void k_overlay_objects(const uint8_
                                                                     int64_t total, double alpha) {
     __shared__ uint32_t cols[kMaxObjects + 1];
     stage_colours(palette, K, cols);
-    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
-    if (gid >= total) return;
-    const int64_t seg = segment_of(gid, slots);
-    const Span s = span_of(gid, seg, slots, L, maps.p[0] + seg * L);
-    const uint8_t *__restrict__ src = frames + seg * 3 * L;
-    uint8_t *__restrict__ dst = out + seg * 3 * L;
-    if (s.qb - s.qa == kGroup) {
-        float bv[kGroup];
-        uint32_t lab[kGroup];
-#pragma unroll
-        for (int i = 0; i < kGroup; ++i) bv[i] = -1.f, lab[i] = 0u;
-        for (int k = 0; k < K; ++k) {
-            const floats4 *__restrict__ lv = reinterpret_cast<const floats4 *>(maps.p[k] + seg * L + s.qa);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const floats4 t = lv[j];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) merge_take(t.v[i], (uint32_t)k, bv[4 * j + i], lab[4 * j + i]);
-            }
-        }
-        uint32_t w[12], o[12];
-        load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
-#pragma unroll
-        for (int k = 0; k < 12; ++k) o[k] = 0;
-#pragma unroll
-        for (int i = 0; i < kGroup; ++i) {
-            const int px = MIRROR ? kGroup - 1 - i : i;
-            const uint32_t b[3] = {byte_at(w, 3 * px), byte_at(w, 3 * px + 1), byte_at(w, 3 * px + 2)};
-            const uint32_t v = paint(b, lab[i], cols[lab[i]], alpha);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int at = 3 * i + c;
-                o[at >> 2] |= ((v >> (8 * c)) & 0xffu) << (8 * (at & 3));
-            }
-        }
-        bytes16 *__restrict__ ov = reinterpret_cast<bytes16 *>(dst + 3 * s.qa);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            bytes16 t;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) t.w[i] = o[4 * k + i];
-            ov[k] = t;
-        }
-    } else {
-        for (int64_t q = s.qa; q < s.qb; ++q) {
-            float bv = -1.f;
-            uint32_t lab = 0u;
-            for (int k = 0; k < K; ++k) merge_take(maps.p[k][seg * L + q], (uint32_t)k, bv, lab);
-            const int64_t sp = MIRROR ? L - 1 - q : q;
-            const uint32_t b[3] = {src[3 * sp], src[3 * sp + 1], src[3 * sp + 2]};
-            const uint32_t v = paint(b, lab, cols[lab], alpha);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dst[3 * q + c] = (uint8_t)(v >> (8 * c));
-        }
-    }
+    paint_pixels<MIRROR>(MapsInPlace{maps, K, L}, PaletteBlend{cols, alpha}, frames, out, slots, total);
 }
-
-// the label of the output pixel whose taps are tx, ty: the taps are taken once and applied to all K maps (rows at `top` and
-// `bot` floats into every map)
-__device__ __forceinline__ uint32_t label_up(const ObjectLogits &maps, int K, int64_t top, int64_t bot, const Tap &tx,
-                                             const Tap &ty) {
-    double bv = -1.0;
-    uint32_t lab = 0u;
-    for (int k = 0; k < K; ++k) merge_take(logit_up(maps.p[k] + top, maps.p[k] + bot, tx, ty), (uint32_t)k, bv, lab);
-    return lab;
-}
-
-// k_overlay_scaled's thread map.  MODE 0: the overlay; MODE 1: the label map, one byte a pixel
+// MODE 0: the overlay; MODE 1: the label map, one byte a pixel, which needs no colours
 template <int MODE, bool MIRROR>
 __global__ __launch_bounds__(kStreamThreads) void k_overlay_objects_scaled(const uint8_t *__restrict__ frames,
                                                                            const ObjectLogits maps, int K,
                                                                            const uint8_t *__restrict__ palette,
                                                                            uint8_t *__restrict__ out, int Hf, int Wf, int Hn,
                                                                            int Wn, int64_t slots, int64_t total, double alpha) {
-    constexpr bool kBlend = MODE == 0;
-    __shared__ uint32_t cols[kMaxObjects + 1];
-    if (kBlend) stage_colours(palette, K, cols);
-    const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
-    if (gid >= total) return;
-    const int64_t seg = segment_of(gid, slots), L = Wf;
-    const int64_t n = seg / Hf;
-    const int y = (int)(seg - n * Hf);
-    const uint8_t *__restrict__ src = kBlend ? frames + seg * 3 * L : nullptr;
-    uint8_t *__restrict__ dst = out + seg * (kBlend ? 3 : 1) * L;
-    const unsigned lead = (16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u;
-    const Span s = span_at(gid, seg, slots, L, (int)(kBlend ? (11u * lead) & 15u : lead));
-    const Tap ty = tap_of(walk_from(y, Hn, Hf), Hn, Hf);
-    const int64_t top = (n * Hn + ty.i0) * Wn, bot = (n * Hn + ty.i1) * Wn;
-    Walk wx = walk_from((int)s.qa, Wn, Wf);
-    if (s.qb - s.qa == kGroup) {
-        if (kBlend) {
-            uint32_t w[12], o[12];
-            load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = 0;
-#pragma unroll
-            for (int i = 0; i < kGroup; ++i) {
-                const uint32_t lab = label_up(maps, K, top, bot, tap_of(wx, Wn, Wf), ty);
-                walk_on(wx, Wn, Wf);
-                const int px = MIRROR ? kGroup - 1 - i : i;
-                const uint32_t b[3] = {byte_at(w, 3 * px), byte_at(w, 3 * px + 1), byte_at(w, 3 * px + 2)};
-                const uint32_t v = paint(b, lab, cols[lab], alpha);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int at = 3 * i + c;
-                    o[at >> 2] |= ((v >> (8 * c)) & 0xffu) << (8 * (at & 3));
-                }
-            }
-            uint4 *__restrict__ ov = reinterpret_cast<uint4 *>(dst + 3 * s.qa);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ov[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-        } else {
-            uint32_t o[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < kGroup; ++i) {
-                o[i >> 2] |= label_up(maps, K, top, bot, tap_of(wx, Wn, Wf), ty) << (8 * (i & 3));
-                walk_on(wx, Wn, Wf);
-            }
-            *reinterpret_cast<uint4 *>(dst + s.qa) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
+    const MapsUp from = {{Hf, Wf, Hn, Wn}, maps, K};
+    if constexpr (MODE == 0) {
+        __shared__ uint32_t cols[kMaxObjects + 1];
+        stage_colours(palette, K, cols);
+        paint_pixels<MIRROR>(from, PaletteBlend{cols, alpha}, frames, out, slots, total);
     } else {
-        for (int64_t q = s.qa; q < s.qb; ++q) {
-            const uint32_t lab = label_up(maps, K, top, bot, tap_of(wx, Wn, Wf), ty);
-            walk_on(wx, Wn, Wf);
-            if (kBlend) {
-                const int64_t sp = MIRROR ? L - 1 - q : q;
-                const uint32_t b[3] = {src[3 * sp], src[3 * sp + 1], src[3 * sp + 2]};
-                const uint32_t v = paint(b, lab, cols[lab], alpha);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dst[3 * q + c] = (uint8_t)(v >> (8 * c));
-            } else {
-                dst[q] = (uint8_t)lab;
-            }
-        }
+        paint_pixels<MIRROR>(from, LabelByte{}, frames, out, slots, total);
     }
 }
 
+// ------------------------------------------------------------------------------------------ host
 // segments and threads of a launch
 struct Partition {
     int64_t L, slots, total;
     int R;
+    dim3 grid;
 };
 inline Partition partition_of(int N, int H, int W, int mirror) {
     Partition p;
@@ -620,29 +602,34 @@ inline Partition partition_of(int N, int H, int W, int mirror) {
     p.L = mirror ? (int64_t)W : (int64_t)H * W;
     p.slots = p.L / kGroup + 2;
     p.total = (int64_t)N * p.R * p.slots;
+    p.grid = dim3((unsigned)cdiv(p.total, kStreamThreads));
     return p;
 }
 constexpr int64_t kMaxPixels = (int64_t)1 << 36;  // N H W: keeps every count far inside int64 and the grid inside 2^31
 
-template <int MODE>
-void launch_overlay(bool mirror, dim3 grid, hipStream_t st, const uint8_t *frames, const float *logits, uint8_t *out,
-                    const Partition &p, int channel, double a255) {
+// `mirror` as a template argument: f(std::true_type) or f(std::false_type)
+template <typename F>
+void with_mirror(int mirror, F &&f) {
     if (mirror)
-        hipLaunchKernelGGL((k_overlay<MODE, true>), grid, dim3(kStreamThreads), 0, st, frames, logits, out, p.L, p.slots, p.total,
-                           channel, a255);
+        f(std::true_type{});
     else
-        hipLaunchKernelGGL((k_overlay<MODE, false>), grid, dim3(kStreamThreads), 0, st, frames, logits, out, p.L, p.slots, p.total,
-                           channel, a255);
+        f(std::false_type{});
 }
-template <int MODE>
-void launch_overlay_scaled(bool mirror, dim3 grid, hipStream_t st, const uint8_t *frames, const float *logits, uint8_t *out,
-                           int Hf, int Wf, int Hn, int Wn, const Partition &p, int channel, double a255) {
-    if (mirror)
-        hipLaunchKernelGGL((k_overlay_scaled<MODE, true>), grid, dim3(kStreamThreads), 0, st, frames, logits, out, Hf, Wf, Hn,
-                           Wn, p.slots, p.total, channel, a255);
-    else
-        hipLaunchKernelGGL((k_overlay_scaled<MODE, false>), grid, dim3(kStreamThreads), 0, st, frames, logits, out, Hf, Wf, Hn,
-                           Wn, p.slots, p.total, channel, a255);
+// the mode of a one-map overlay as well: f(mode, mirror).  A mask (modes 2, 3) has nothing to mirror
+template <typename F>
+void with_mode(int mode, int mirror, F &&f) {
+    switch (mode) {
+        case 0: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 0>{}, m); }); break;
+        case 1: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 1>{}, m); }); break;
+        case 2: f(std::integral_constant<int, 2>{}, std::false_type{}); break;
+        default: f(std::integral_constant<int, 3>{}, std::false_type{}); break;
+    }
+}
+
+// the sizes of a call at the frames' size
+int check_frames(const char *who, int N, int H, int W) {
+    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)N * H * W <= kMaxPixels, FOSVOS_E_SHAPE, "%s: N=%d H=%d W=%d", who, N, H, W);
+    return FOSVOS_OK;
 }
 // the sizes of a scaled call: the frame's and the net's
 int check_sizes(const char *who, int N, int Hf, int Wf, int Hn, int Wn) {
@@ -653,52 +640,70 @@ int check_sizes(const char *who, int N, int Hf, int Wf, int Hn, int Wn) {
                    Wf);
     return FOSVOS_OK;
 }
+// a one-map overlay, in front of its sizes: the mode and the pointers (a mask reads no frames) ...
+int check_map(const char *who, int mode, const uint8_t *frames, const float *logits, const uint8_t *out) {
+    FOSVOS_REQUIRE(mode >= 0 && mode <= 3, FOSVOS_E_ARG, "%s: mode %d outside [0, 3]", who, mode);
+    FOSVOS_REQUIRE(logits && out && (frames || mode >= 2), FOSVOS_E_ARG, "%s: null pointer", who);
+    return FOSVOS_OK;
+}
+// ... and behind them: what it paints with
+int check_level(const char *who, int channel, double alpha, const float *logits) {
+    FOSVOS_REQUIRE(channel >= 0 && channel <= 2, FOSVOS_E_ARG, "%s: channel %d outside [0, 2]", who, channel);
+    FOSVOS_REQUIRE(alpha >= 0.0 && isfinite(alpha), FOSVOS_E_ARG, "%s: alpha %g is not a finite number >= 0", who, alpha);
+    FOSVOS_REQUIRE(((uintptr_t)logits & 3) == 0, FOSVOS_E_ARG, "%s: the logits must be 4-byte aligned", who);
+    return FOSVOS_OK;
+}
+// a several-objects overlay, in front of its sizes: the K pointers, by value from here on, and the others (a label map,
+// `blend` false, reads neither frames nor palette) ...
+int check_maps(const char *who, const float *const *logits, int K, ObjectLogits &maps, bool blend, const uint8_t *frames,
+               const uint8_t *palette, const uint8_t *out) {
+    FOSVOS_REQUIRE(K >= 1 && K <= kMaxObjects, FOSVOS_E_ARG, "%s: K=%d outside [1, %d]", who, K, kMaxObjects);
+    FOSVOS_REQUIRE(logits, FOSVOS_E_ARG, "%s: null pointer", who);
+    for (int k = 0; k < K; ++k) {
+        FOSVOS_REQUIRE(logits[k] != nullptr, FOSVOS_E_ARG, "%s: null logit map %d", who, k);
+        FOSVOS_REQUIRE(((uintptr_t)logits[k] & 3) == 0, FOSVOS_E_ARG, "%s: logit map %d must be 4-byte aligned", who, k);
+        maps.p[k] = logits[k];
+    }
+    FOSVOS_REQUIRE(out && ((frames && palette) || !blend), FOSVOS_E_ARG, "%s: null pointer", who);
+    return FOSVOS_OK;
+}
+// ... and behind them: how far it blends
+int check_blend(const char *who, bool blend, double alpha) {
+    FOSVOS_REQUIRE(!blend || (alpha >= 0.0 && alpha <= 1.0), FOSVOS_E_ARG, "%s: alpha %g is not a number in [0, 1]", who, alpha);
+    return FOSVOS_OK;
+}
 }  // namespace
 
 extern "C" int fosvos_frame_prep(const uint8_t *frames, int N, int H, int W, int mirror, const float mean[3], float *image,
                                  int device, void *stream) {
     FOSVOS_REQUIRE(frames && mean && image, FOSVOS_E_ARG, "frame_prep: null pointer");
-    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)N * H * W <= kMaxPixels, FOSVOS_E_SHAPE, "frame_prep: N=%d H=%d W=%d", N,
-                   H, W);
+    if (int rc = check_frames("frame_prep", N, H, W)) return rc;
     FOSVOS_REQUIRE(((uintptr_t)image & 3) == 0, FOSVOS_E_ARG, "frame_prep: the image must be 4-byte aligned");
     FOSVOS_ENTER(device);
     const Partition p = partition_of(N, H, W, mirror);
-    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads));
     const int64_t plane = (int64_t)H * W;
     const MeanBGR m = {{mean[0], mean[1], mean[2]}};
-    hipStream_t st = (hipStream_t)stream;
     FOSVOS_PROF("k_frame_prep", stream, 0.0);
-    if (mirror)
-        hipLaunchKernelGGL(k_frame_prep<true>, grid, dim3(kStreamThreads), 0, st, frames, image, p.L, p.R, plane, p.slots, p.total,
-                           m);
-    else
-        hipLaunchKernelGGL(k_frame_prep<false>, grid, dim3(kStreamThreads), 0, st, frames, image, p.L, p.R, plane, p.slots,
-                           p.total, m);
+    with_mirror(mirror, [&](auto mi) {
+        hipLaunchKernelGGL(k_frame_prep<decltype(mi)::value>, p.grid, dim3(kStreamThreads), 0, (hipStream_t)stream, frames, image,
+                           p.L, p.R, plane, p.slots, p.total, m);
+    });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
 
 extern "C" int fosvos_overlay(const uint8_t *frames, const float *logits, int N, int H, int W, int mirror, int mode, int channel,
                               double alpha, uint8_t *out, int device, void *stream) {
-    FOSVOS_REQUIRE(mode >= 0 && mode <= 3, FOSVOS_E_ARG, "overlay: mode %d outside [0, 3]", mode);
-    FOSVOS_REQUIRE(logits && out && (frames || mode >= 2), FOSVOS_E_ARG, "overlay: null pointer");
-    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)N * H * W <= kMaxPixels, FOSVOS_E_SHAPE, "overlay: N=%d H=%d W=%d", N, H, W);
-    FOSVOS_REQUIRE(channel >= 0 && channel <= 2, FOSVOS_E_ARG, "overlay: channel %d outside [0, 2]", channel);
-    FOSVOS_REQUIRE(alpha >= 0.0 && isfinite(alpha), FOSVOS_E_ARG, "overlay: alpha %g is not a finite number >= 0", alpha);
-    FOSVOS_REQUIRE(((uintptr_t)logits & 3) == 0, FOSVOS_E_ARG, "overlay: the logits must be 4-byte aligned");
+    if (int rc = check_map("overlay", mode, frames, logits, out)) return rc;
+    if (int rc = check_frames("overlay", N, H, W)) return rc;
+    if (int rc = check_level("overlay", channel, alpha, logits)) return rc;
     FOSVOS_ENTER(device);
-    // a mask (modes 2, 3) has nothing to mirror: the logits already are in output order
     const Partition p = partition_of(N, H, W, mode < 2 ? mirror : 0);
-    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads));
-    const double a255 = alpha * 255.0;
-    hipStream_t st = (hipStream_t)stream;
     FOSVOS_PROF("k_overlay", stream, 0.0);
-    switch (mode) {
-        case 0: launch_overlay<0>(mirror != 0, grid, st, frames, logits, out, p, channel, a255); break;
-        case 1: launch_overlay<1>(mirror != 0, grid, st, frames, logits, out, p, channel, a255); break;
-        case 2: launch_overlay<2>(false, grid, st, frames, logits, out, p, channel, a255); break;
-        default: launch_overlay<3>(false, grid, st, frames, logits, out, p, channel, a255); break;
-    }
+    with_mode(mode, mirror, [&](auto mo, auto mi) {
+        hipLaunchKernelGGL((k_overlay<decltype(mo)::value, decltype(mi)::value>), p.grid, dim3(kStreamThreads), 0,
+                           (hipStream_t)stream, frames, logits, out, p.L, p.slots, p.total, channel, alpha * 255.0);
+    });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
@@ -721,75 +726,44 @@ extern "C" int fosvos_frame_prep_scaled(const uint8_t *frames, int N, int Hf, in
     const MeanBGR m = {{mean[0], mean[1], mean[2]}};
     const int64_t frame_bytes = (int64_t)N * Hf * Wf * 3;
     const size_t lds = (size_t)g.pitch * g.rows;
-    hipStream_t st = (hipStream_t)stream;
     FOSVOS_PROF("k_frame_prep_scaled", stream, 0.0);
-    if (mirror)
-        hipLaunchKernelGGL(k_frame_prep_scaled<true>, dim3((unsigned)blocks), dim3(kScaleThreads), lds, st, frames, image, g,
-                           frame_bytes, m);
-    else
-        hipLaunchKernelGGL(k_frame_prep_scaled<false>, dim3((unsigned)blocks), dim3(kScaleThreads), lds, st, frames, image, g,
-                           frame_bytes, m);
+    with_mirror(mirror, [&](auto mi) {
+        hipLaunchKernelGGL(k_frame_prep_scaled<decltype(mi)::value>, dim3((unsigned)blocks), dim3(kScaleThreads), lds,
+                           (hipStream_t)stream, frames, image, g, frame_bytes, m);
+    });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
 
 extern "C" int fosvos_overlay_scaled(const uint8_t *frames, const float *logits, int N, int Hf, int Wf, int Hn, int Wn,
                                      int mirror, int mode, int channel, double alpha, uint8_t *out, int device, void *stream) {
-    FOSVOS_REQUIRE(mode >= 0 && mode <= 3, FOSVOS_E_ARG, "overlay_scaled: mode %d outside [0, 3]", mode);
-    FOSVOS_REQUIRE(logits && out && (frames || mode >= 2), FOSVOS_E_ARG, "overlay_scaled: null pointer");
+    if (int rc = check_map("overlay_scaled", mode, frames, logits, out)) return rc;
     if (int rc = check_sizes("overlay_scaled", N, Hf, Wf, Hn, Wn)) return rc;
-    FOSVOS_REQUIRE(channel >= 0 && channel <= 2, FOSVOS_E_ARG, "overlay_scaled: channel %d outside [0, 2]", channel);
-    FOSVOS_REQUIRE(alpha >= 0.0 && isfinite(alpha), FOSVOS_E_ARG, "overlay_scaled: alpha %g is not a finite number >= 0", alpha);
-    FOSVOS_REQUIRE(((uintptr_t)logits & 3) == 0, FOSVOS_E_ARG, "overlay_scaled: the logits must be 4-byte aligned");
+    if (int rc = check_level("overlay_scaled", channel, alpha, logits)) return rc;
     FOSVOS_ENTER(device);
     const Partition p = partition_of(N, Hf, Wf, 1);  // rows, in every mode
-    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads));
-    const double a255 = alpha * 255.0;
-    hipStream_t st = (hipStream_t)stream;
     FOSVOS_PROF("k_overlay_scaled", stream, 0.0);
-    switch (mode) {
-        case 0: launch_overlay_scaled<0>(mirror != 0, grid, st, frames, logits, out, Hf, Wf, Hn, Wn, p, channel, a255); break;
-        case 1: launch_overlay_scaled<1>(mirror != 0, grid, st, frames, logits, out, Hf, Wf, Hn, Wn, p, channel, a255); break;
-        case 2: launch_overlay_scaled<2>(false, grid, st, frames, logits, out, Hf, Wf, Hn, Wn, p, channel, a255); break;
-        default: launch_overlay_scaled<3>(false, grid, st, frames, logits, out, Hf, Wf, Hn, Wn, p, channel, a255); break;
-    }
+    with_mode(mode, mirror, [&](auto mo, auto mi) {
+        hipLaunchKernelGGL((k_overlay_scaled<decltype(mo)::value, decltype(mi)::value>), p.grid, dim3(kStreamThreads), 0,
+                           (hipStream_t)stream, frames, logits, out, Hf, Wf, Hn, Wn, p.slots, p.total, channel, alpha * 255.0);
+    });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
 
-namespace {
-// the K pointers of a several-objects call, by value
-int object_maps(const char *who, const float *const *logits, int K, ObjectLogits &maps) {
-    FOSVOS_REQUIRE(K >= 1 && K <= kMaxObjects, FOSVOS_E_ARG, "%s: K=%d outside [1, %d]", who, K, kMaxObjects);
-    FOSVOS_REQUIRE(logits, FOSVOS_E_ARG, "%s: null pointer", who);
-    for (int k = 0; k < K; ++k) {
-        FOSVOS_REQUIRE(logits[k] != nullptr, FOSVOS_E_ARG, "%s: null logit map %d", who, k);
-        FOSVOS_REQUIRE(((uintptr_t)logits[k] & 3) == 0, FOSVOS_E_ARG, "%s: logit map %d must be 4-byte aligned", who, k);
-        maps.p[k] = logits[k];
-    }
-    return FOSVOS_OK;
-}
-}  // namespace
-
 extern "C" int fosvos_overlay_objects(const uint8_t *frames, const float *const *logits, int K, int N, int H, int W, int mirror,
                                       const uint8_t *palette, double alpha, uint8_t *out, int device, void *stream) {
     ObjectLogits maps = {};
-    if (int rc = object_maps("overlay_objects", logits, K, maps)) return rc;
-    FOSVOS_REQUIRE(frames && palette && out, FOSVOS_E_ARG, "overlay_objects: null pointer");
-    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)N * H * W <= kMaxPixels, FOSVOS_E_SHAPE, "overlay_objects: N=%d H=%d W=%d",
-                   N, H, W);
-    FOSVOS_REQUIRE(alpha >= 0.0 && alpha <= 1.0, FOSVOS_E_ARG, "overlay_objects: alpha %g is not a number in [0, 1]", alpha);
+    if (int rc = check_maps("overlay_objects", logits, K, maps, true, frames, palette, out)) return rc;
+    if (int rc = check_frames("overlay_objects", N, H, W)) return rc;
+    if (int rc = check_blend("overlay_objects", true, alpha)) return rc;
     FOSVOS_ENTER(device);
     const Partition p = partition_of(N, H, W, mirror);
-    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads));
-    hipStream_t st = (hipStream_t)stream;
     FOSVOS_PROF("k_overlay_objects", stream, 0.0);
-    if (mirror)
-        hipLaunchKernelGGL(k_overlay_objects<true>, grid, dim3(kStreamThreads), 0, st, frames, maps, K, palette, out, p.L, p.slots,
-                           p.total, alpha);
-    else
-        hipLaunchKernelGGL(k_overlay_objects<false>, grid, dim3(kStreamThreads), 0, st, frames, maps, K, palette, out, p.L, p.slots,
-                           p.total, alpha);
+    with_mirror(mirror, [&](auto mi) {
+        hipLaunchKernelGGL(k_overlay_objects<decltype(mi)::value>, p.grid, dim3(kStreamThreads), 0, (hipStream_t)stream, frames,
+                           maps, K, palette, out, p.L, p.slots, p.total, alpha);
+    });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
@@ -799,25 +773,23 @@ extern "C" int fosvos_overlay_objects_scaled(const uint8_t *frames, const float 
                                              uint8_t *out, int device, void *stream) {
     FOSVOS_REQUIRE(mode == 0 || mode == 1, FOSVOS_E_ARG, "overlay_objects_scaled: mode %d outside [0, 1]", mode);
     ObjectLogits maps = {};
-    if (int rc = object_maps("overlay_objects_scaled", logits, K, maps)) return rc;
-    FOSVOS_REQUIRE(out && ((frames && palette) || mode == 1), FOSVOS_E_ARG, "overlay_objects_scaled: null pointer");
+    if (int rc = check_maps("overlay_objects_scaled", logits, K, maps, mode == 0, frames, palette, out)) return rc;
     if (int rc = check_sizes("overlay_objects_scaled", N, Hf, Wf, Hn, Wn)) return rc;
-    FOSVOS_REQUIRE(mode == 1 || (alpha >= 0.0 && alpha <= 1.0), FOSVOS_E_ARG,
-                   "overlay_objects_scaled: alpha %g is not a number in [0, 1]", alpha);
+    if (int rc = check_blend("overlay_objects_scaled", mode == 0, alpha)) return rc;
     FOSVOS_ENTER(device);
     const Partition p = partition_of(N, Hf, Wf, 1);  // rows, in both modes
-    const dim3 grid((unsigned)cdiv(p.total, kStreamThreads)), block(kStreamThreads);
+    const dim3 block(kStreamThreads);
     hipStream_t st = (hipStream_t)stream;
     FOSVOS_PROF("k_overlay_objects_scaled", stream, 0.0);
     if (mode == 1)  // a label map has nothing to mirror: the logits already are in output order
-        hipLaunchKernelGGL((k_overlay_objects_scaled<1, false>), grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn, Wn,
-                           p.slots, p.total, alpha);
-    else if (mirror)
-        hipLaunchKernelGGL((k_overlay_objects_scaled<0, true>), grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn, Wn,
-                           p.slots, p.total, alpha);
+        hipLaunchKernelGGL((k_overlay_objects_scaled<1, false>), p.grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn,
+                           Wn, p.slots, p.total, alpha);
     else
-        hipLaunchKernelGGL((k_overlay_objects_scaled<0, false>), grid, block, 0, st, frames, maps, K, palette, out, Hf, Wf, Hn, Wn,
-                           p.slots, p.total, alpha);
+        with_mirror(mirror, [&](auto mi) {
+            hipLaunchKernelGGL((k_overlay_objects_scaled<0, decltype(mi)::value>), p.grid, block, 0, st, frames, maps, K, palette,
+                               out, Hf, Wf, Hn, Wn, p.slots, p.total, alpha);
+        });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }
+
