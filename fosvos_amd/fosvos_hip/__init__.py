@@ -227,6 +227,15 @@ SIGNATURES = {
     "fosvos_component_roots": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_clean_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                         c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_cbce_void_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "fosvos_cbce_loss_frames_void": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p,
+                                             c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_distance_gate_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fosvos_distance_gate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int,
+                                     c_void_p]),
+    "fosvos_adapt_labels_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fosvos_adapt_labels": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_png_indexed_capacity_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fosvos_png_encode_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                           c_void_p, c_size_t, c_int, c_void_p]),

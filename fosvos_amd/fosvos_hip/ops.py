@@ -576,13 +576,54 @@ def cbce_loss(logits: torch.Tensor, label: torch.Tensor, size_average: bool = Tr
     return loss, grad
 
 
+def _cbce_loss_frames_void(logits: torch.Tensor, label: torch.Tensor, void: torch.Tensor, size_average: bool, want_grad: bool,
+                           grad_scale: float):
+    """cbce_loss_frames with ignored pixels (fosvos_cbce_loss_frames_void)."""
+    if void.dtype != torch.uint8:
+        raise TypeError(f"cbce_loss_frames void: expected torch.uint8, got {void.dtype}")
+    if not void.is_cuda or void.device != logits.device:
+        raise RuntimeError(f"cbce_loss_frames void: must be on {logits.device}, got {void.device}")
+    if not void.is_contiguous():
+        raise ValueError("cbce_loss_frames void: tensor must be contiguous")
+    if void.shape != logits.shape:
+        raise ValueError(f"cbce_loss_frames: logits {tuple(logits.shape)} vs void {tuple(void.shape)}")
+    n = logits.shape[0]
+    per = logits.numel() // n
+    if n > 1 and (per % 4 or logits.data_ptr() % 16 or label.data_ptr() % 16 or void.data_ptr() % 4):
+        parts = [_cbce_loss_frames_void(logits[i:i + 1], label[i:i + 1], void[i:i + 1], size_average, want_grad, grad_scale)
+                 for i in range(n)]
+        return torch.cat([p[0] for p in parts]), (torch.cat([p[1] for p in parts]) if want_grad else None)
+    # one frame (or a slice of a batch) may start off the boundaries the kernels read at
+    if logits.data_ptr() % 16:
+        logits = logits.clone()
+    if label.data_ptr() % 16:
+        label = label.clone()
+    if void.data_ptr() % 4:
+        void = void.clone()
+    L = lib()
+    losses = torch.empty((n,), dtype=_F32, device=logits.device)
+    grad = torch.empty_like(logits) if want_grad else None
+    ws, wsn = _WS.get(L.fosvos_cbce_void_workspace_bytes(per, n), logits.device)
+    dev, st = _ctx(logits)
+    t0 = _pb()
+    check(L.fosvos_cbce_loss_frames_void(logits.data_ptr(), label.data_ptr(), void.data_ptr(), per, n,
+                                         1 if size_average else 0, float(grad_scale), losses.data_ptr(), _p(grad), ws, wsn,
+                                         dev, st), "cbce_loss_frames_void")
+    _pe(t0, "cbce_loss_void", 0.0, logits.numel() * (18 if want_grad else 14))
+    return losses, grad
+
+
 def cbce_loss_frames(logits: torch.Tensor, label: torch.Tensor, size_average: bool = True, want_grad: bool = True,
-                     grad_scale: float = 1.0):
+                     grad_scale: float = 1.0, void: Optional[torch.Tensor] = None):
     """The loss of every frame of [N,1,H,W] logits on its own: ([N] losses, grad like logits or None), one set of launches.
-    Frames whose element count is not a multiple of 4 go through one call per frame (16-byte alignment of the kernels)."""
+    Frames whose element count is not a multiple of 4 go through one call per frame (16-byte alignment of the kernels).
+    ``void`` (uint8 like logits, non-zero = ignored; None: the call is what it was): the classes are balanced over the valid
+    pixels only, a void pixel's logit reaches nothing and its gradient is +0.0 (util/online_adapt.cbce_void)."""
     _need(logits, _F32, "cbce_loss_frames logits"); _need(label, _F32, "cbce_loss_frames label")
     if logits.shape != label.shape or logits.dim() < 2:
         raise ValueError(f"cbce_loss_frames: logits {tuple(logits.shape)} vs label {tuple(label.shape)}")
+    if void is not None:
+        return _cbce_loss_frames_void(logits, label, void, bool(size_average), bool(want_grad), float(grad_scale))
     n = logits.shape[0]
     per = logits.numel() // n
     if per % 4 or logits.data_ptr() % 16 or label.data_ptr() % 16:
@@ -1220,6 +1261,81 @@ def clean_components(logits: torch.Tensor, seed: Optional[torch.Tensor] = None, 
                                     int(bool(chain)), fill, out.data_ptr(), _p(kept), ws, wsn, dev, st), "clean_components")
     _pe(e0, "clean_components", 0.0, 25.0 * n * h * w)
     return out
+
+
+# ------------------------------------------------------------------------------------------ online adaptation (adapt.hip)
+GATE_MAX_DISTANCE = 4095  # util/online_adapt.MAX_DISTANCE
+GATE_MAX_SIDE = 8192
+
+
+def _gate_int(who: str, name: str, v) -> int:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError(f"{who}: {name} must be an integer, got {v!r}")
+    if not 0 <= v <= GATE_MAX_DISTANCE:
+        raise ValueError(f"{who}: {name} {v} outside [0, {GATE_MAX_DISTANCE}]")
+    return v
+
+
+def _gate_shape(who: str, n: int, h: int, w: int) -> None:
+    if n > 65535 or h > GATE_MAX_SIDE or w > GATE_MAX_SIDE:
+        raise ValueError(f"{who}: N={n} (<= 65535) H={h} W={w} (<= {GATE_MAX_SIDE})")
+
+
+def distance_gate(mask: torch.Tensor, distance: int, invert: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_distance_gate: mask uint8 [N,H,W] -> uint8 [N,H,W], 1 where every set pixel of the frame is further than
+    ``distance`` (0..4095, Euclidean, exact in integers); a pixel is set when ``(mask != 0) != invert``, and a frame without
+    a set pixel gives all 1 (util/online_adapt.far_from).  With ``invert`` it is the erosion of the mask by the disk.
+    Launched on the current stream, no synchronisation."""
+    _need_eval(mask, torch.uint8, "distance_gate mask")
+    if mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError(f"distance_gate: mask must be a non-empty [N,H,W], got {tuple(mask.shape)}")
+    n, h, w = (int(v) for v in mask.shape)
+    _gate_shape("distance_gate", n, h, w)
+    distance = _gate_int("distance_gate", "distance", distance)
+    out = _out_like(out, (n, h, w), torch.uint8, mask, "distance_gate")
+    if out.data_ptr() == mask.data_ptr():
+        raise ValueError("distance_gate: out must not be the mask itself")
+    L = lib()
+    ws, wsn = _WS.get(L.fosvos_distance_gate_workspace_bytes(n, h, w), mask.device)
+    dev, st = _ctx(mask)
+    e0 = _pb()
+    check(L.fosvos_distance_gate(mask.data_ptr(), n, h, w, distance, int(bool(invert)), out.data_ptr(), ws, wsn, dev, st),
+          "distance_gate")
+    _pe(e0, "distance_gate", 0.0, 6.0 * n * h * w)
+    return out
+
+
+def adapt_labels(logits: torch.Tensor, last_mask: torch.Tensor, pos_logit: float, neg_distance: int, erode: int = 0,
+                 label: Optional[torch.Tensor] = None, void: Optional[torch.Tensor] = None,
+                 counts: Optional[torch.Tensor] = None):
+    """fosvos_adapt_labels: logits fp32 [N,1,H,W] and last_mask uint8 [N,H,W] (non-zero = object) -> (label fp32 [N,1,H,W],
+    void uint8 [N,1,H,W], counts int32 [N,3] = positives, negatives, void): the pseudo-labels of online adaptation
+    (util/online_adapt.adapt_labels).  Further than ``neg_distance`` from the mask eroded by ``erode`` (both 0..4095) is a
+    negative - unless that core is empty -, elsewhere ``logits >= float32(pos_logit)`` is a positive, the rest is void.
+    ``counts`` may be any [N,3] int32 rows, e.g. a slice of a sequence's counter tensor; the op zeroes them itself.
+    Launched on the current stream, no synchronisation."""
+    _need_eval(logits, _F32, "adapt_labels logits")
+    _need_eval(last_mask, torch.uint8, "adapt_labels last_mask")
+    n, h, w = _logit_shape(logits, "adapt_labels")
+    _gate_shape("adapt_labels", n, h, w)
+    if tuple(last_mask.shape) != (n, h, w):
+        raise ValueError(f"adapt_labels: last_mask must be {(n, h, w)}, got {tuple(last_mask.shape)}")
+    neg_distance = _gate_int("adapt_labels", "neg_distance", neg_distance)
+    erode = _gate_int("adapt_labels", "erode", erode)
+    if isinstance(pos_logit, bool) or not isinstance(pos_logit, (int, float)) or pos_logit != pos_logit:
+        raise ValueError(f"adapt_labels: pos_logit must be a number, got {pos_logit!r}")
+    label = _out_like(label, (n, 1, h, w), _F32, logits, "adapt_labels label")
+    void = _out_like(void, (n, 1, h, w), torch.uint8, logits, "adapt_labels void")
+    counts = _out_like(counts, (n, 3), torch.int32, logits, "adapt_labels counts")
+    _same_device("adapt_labels", logits, last_mask)
+    L = lib()
+    ws, wsn = _WS.get(L.fosvos_adapt_labels_workspace_bytes(n, h, w), logits.device)
+    dev, st = _ctx(logits)
+    e0 = _pb()
+    check(L.fosvos_adapt_labels(logits.data_ptr(), last_mask.data_ptr(), n, h, w, float(pos_logit), neg_distance, erode,
+                                label.data_ptr(), void.data_ptr(), counts.data_ptr(), ws, wsn, dev, st), "adapt_labels")
+    _pe(e0, "adapt_labels", 0.0, (15.0 if erode == 0 else 21.0) * n * h * w)
+    return label, void, counts
 
 
 # ------------------------------------------------------------------------------------------ PNG files (png.hip)

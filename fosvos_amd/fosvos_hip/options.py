@@ -2,7 +2,7 @@
 (EngineOptions).  ``from_env`` of each is the ONLY place of the package that parses a ``FOSVOS_*`` switch; everything else
 takes an options object.  The defaults are the measured best; every switch selects between two paths that both stay tested.
 The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleaning) is opt-in by being
-passed and has no environment switch.
+passed and has no environment switch; so is AdaptOptions (online adaptation of the test pass).
 
 No torch and no library load here: importable anywhere.
 """
@@ -160,6 +160,60 @@ class CleanOptions:
     def as_dict(self) -> dict:
         return {'min_area': self.min_area, 'largest': self.largest, 'temporal_radius': self.temporal_radius,
                 'fill': float(self.fill)}
+
+
+def _real(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+@dataclass(frozen=True)
+class AdaptOptions:
+    """Online adaptation of the test pass (``experiment_helper.test_adaptive``; util/online_adapt.py states the rules;
+    DESIGN.md section 17).  Opt-in by being passed; this class reads no environment variable.  The defaults are OnAVOS's
+    published ones at 480p and are unmeasured here."""
+
+    # fine-tune steps on every frame; 0 = the pass labels the frames and trains nothing
+    steps: int = 1
+    # a pixel whose probability is at least this is a positive (outside the negatives): 0.5 < p < 1
+    pos_prob: float = 0.97
+    # a pixel further than this many pixels from the eroded last mask is a negative: 0..4095
+    neg_distance: int = 220
+    # the last mask is eroded by the disk of this radius first: 0..4095
+    erode: int = 15
+    # weight of the current frame's pseudo-label loss in a step: > 0
+    frame_weight: float = 1.0
+    # weight of the annotated first frame's loss in a step: >= 0 (0: the first frame is not passed through the net at all)
+    first_weight: float = 1.0
+    # learning rate of the adaptation's optimizer (net_provider.get_optimizer(learning_rate=)): > 0
+    learning_rate: float = 1e-8
+
+    def __post_init__(self) -> None:
+        if isinstance(self.steps, bool) or not isinstance(self.steps, int) or self.steps < 0:
+            raise ValueError(f"AdaptOptions: steps must be an integer >= 0, got {self.steps!r}")
+        if not _real(self.pos_prob) or not 0.5 < self.pos_prob < 1:
+            raise ValueError(f"AdaptOptions: pos_prob must be a probability in (0.5, 1), got {self.pos_prob!r}")
+        for name in ("neg_distance", "erode"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 4095:
+                raise ValueError(f"AdaptOptions: {name} must be an integer in 0..4095, got {v!r}")
+        if not _real(self.frame_weight) or not self.frame_weight > 0:
+            raise ValueError(f"AdaptOptions: frame_weight must be a finite number > 0, got {self.frame_weight!r}")
+        if not _real(self.first_weight) or not self.first_weight >= 0:
+            raise ValueError(f"AdaptOptions: first_weight must be a finite number >= 0, got {self.first_weight!r}")
+        if not _real(self.learning_rate) or not self.learning_rate > 0:
+            raise ValueError(f"AdaptOptions: learning_rate must be a finite number > 0, got {self.learning_rate!r}")
+
+    @property
+    def pos_logit(self) -> float:
+        """log(p / (1 - p)) in float64, rounded to float32 once (the value the kernel and the numpy definition compare with)."""
+        import math
+        import struct
+        return struct.unpack("f", struct.pack("f", math.log(self.pos_prob / (1.0 - self.pos_prob))))[0]
+
+    def as_dict(self) -> dict:
+        return {'steps': self.steps, 'pos_prob': float(self.pos_prob), 'pos_logit': self.pos_logit,
+                'neg_distance': self.neg_distance, 'erode': self.erode, 'frame_weight': float(self.frame_weight),
+                'first_weight': float(self.first_weight), 'learning_rate': float(self.learning_rate)}
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

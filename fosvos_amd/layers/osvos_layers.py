@@ -55,11 +55,18 @@ class _CBCELoss(torch.autograd.Function):
     """Loss value and d(loss)/d(logits) come out of the same kernel pass; backward only scales."""
 
     @staticmethod
-    def forward(ctx, output, label, size_average, batch_counts=None, backward_seed=None):
+    def forward(ctx, output, label, size_average, batch_counts=None, backward_seed=None, void_pixels=None):
         ctx.seed_ptr, ctx.seed_value = _seed_of(backward_seed)
-        loss, grad = ops.cbce_loss(output.contiguous().float(), label.contiguous().float(),
-                                   size_average=bool(size_average), grad_scale=ctx.seed_value,
-                                   want_grad=output.requires_grad, batch_counts=batch_counts)
+        if void_pixels is not None:  # the whole tensor as one frame of the per-frame void loss: one node, one kernel group
+            x = output.contiguous().float()
+            losses, grad = ops.cbce_loss_frames(x.reshape(1, -1), label.contiguous().float().reshape(1, -1),
+                                                size_average=bool(size_average), want_grad=output.requires_grad,
+                                                grad_scale=ctx.seed_value, void=void_pixels.contiguous().reshape(1, -1))
+            loss, grad = losses.reshape(()), (None if grad is None else grad.reshape(x.shape))
+        else:
+            loss, grad = ops.cbce_loss(output.contiguous().float(), label.contiguous().float(),
+                                       size_average=bool(size_average), grad_scale=ctx.seed_value,
+                                       want_grad=output.requires_grad, batch_counts=batch_counts)
         ctx.grad = grad
         ctx.shape = output.shape
         return loss
@@ -67,11 +74,26 @@ class _CBCELoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if ctx.grad is None:
-            return None, None, None, None, None
-        return _scaled(ctx, g).reshape(ctx.shape), None, None, None, None
+            return None, None, None, None, None, None
+        return _scaled(ctx, g).reshape(ctx.shape), None, None, None, None, None
 
 
-def class_balanced_cross_entropy_loss(output, label, size_average=True, batch_counts=None, backward_seed=None):
+def _check_void(who, output, void_pixels, *exclusive):
+    """void_pixels: uint8 of the label's shape on the output's device; the (name, value) pairs it does not combine with."""
+    for name, value in exclusive:
+        if value is not None:
+            raise ValueError("{}: void_pixels does not combine with {} (the void form counts the classes of its own valid "
+                             "pixels in its own launches)".format(who, name))
+    if not torch.is_tensor(void_pixels) or void_pixels.dtype != torch.uint8:
+        raise ValueError("{}: void_pixels must be a uint8 tensor (non-zero = ignored), got {}".format(
+            who, getattr(void_pixels, 'dtype', type(void_pixels))))
+    if tuple(void_pixels.shape) != tuple(output.shape):
+        raise ValueError("{}: output {} vs void_pixels {}".format(who, tuple(output.shape), tuple(void_pixels.shape)))
+    return void_pixels if void_pixels.device == output.device else void_pixels.to(output.device)
+
+
+def class_balanced_cross_entropy_loss(output, label, size_average=True, batch_counts=None, backward_seed=None,
+                                      void_pixels=None):
     """Class-balanced cross entropy loss (same contract as the reference).
 
     Args:
@@ -85,6 +107,10 @@ def class_balanced_cross_entropy_loss(output, label, size_average=True, batch_co
         that every element of ``tensor`` equals ``value`` (the online loop's 1 / nAveGrad): the loss kernel then writes the
         gradient already multiplied, and the backward pass of that very tensor launches nothing.  Any other incoming
         gradient is still handled correctly (divided by ``value`` first).
+    void_pixels: (extension) uint8 tensor of the label's shape, non-zero = ignored: the classes are balanced over the other
+        pixels only, an ignored pixel's logit reaches nothing and its gradient is +0.0 (util/online_adapt.cbce_void; NOT
+        upstream OSVOS-PyTorch's ``void_pixels``, which still counts the ignored pixels among the negatives).  Not together
+        with ``batch_counts``.
     Returns:
     0-dim tensor with the loss; reductions run over the whole batch tensor."""
     if not output.is_cuda:
@@ -95,7 +121,10 @@ def class_balanced_cross_entropy_loss(output, label, size_average=True, batch_co
     if tuple(label.shape) != tuple(output.shape):
         raise ValueError("class_balanced_cross_entropy_loss: output {} vs label {}".format(
             tuple(output.shape), tuple(label.shape)))
-    return _CBCELoss.apply(output, label, size_average, batch_counts, backward_seed)
+    if void_pixels is not None:
+        void_pixels = _check_void("class_balanced_cross_entropy_loss", output, void_pixels, ("batch_counts", batch_counts))
+        return _CBCELoss.apply(output, label, size_average, None, backward_seed, void_pixels)
+    return _CBCELoss.apply(output, label, size_average, batch_counts, backward_seed, None)
 
 
 class _CBCELossFrames(torch.autograd.Function):
@@ -103,9 +132,13 @@ class _CBCELossFrames(torch.autograd.Function):
     gradients in one buffer so that backward is a single scale."""
 
     @staticmethod
-    def forward(ctx, output, label, size_average, backward_seed=None, staged=None):
+    def forward(ctx, output, label, size_average, backward_seed=None, staged=None, void_pixels=None):
         ctx.seed_ptr, ctx.seed_value = _seed_of(backward_seed)
-        if staged is not None:  # the class counts are already in the staged loss's workspace; the values come with finish()
+        if void_pixels is not None:
+            losses, grad = ops.cbce_loss_frames(output.contiguous().float(), label.contiguous().float(),
+                                                size_average=bool(size_average), want_grad=output.requires_grad,
+                                                grad_scale=ctx.seed_value, void=void_pixels.contiguous())
+        elif staged is not None:  # the class counts are already in the staged loss's workspace; the values come with finish()
             losses, grad = staged.loss(output.contiguous().float(), size_average=bool(size_average),
                                        want_grad=output.requires_grad, grad_scale=ctx.seed_value)
         else:
@@ -118,8 +151,8 @@ class _CBCELossFrames(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if ctx.grad is None:
-            return None, None, None, None, None
-        return _scaled(ctx, g), None, None, None, None
+            return None, None, None, None, None, None
+        return _scaled(ctx, g), None, None, None, None, None
 
 
 def stage_frames_loss(label):
@@ -134,11 +167,13 @@ def stage_frames_loss(label):
     return ops.CbceFramesStaged(label)
 
 
-def class_balanced_cross_entropy_loss_frames(output, label, size_average=True, backward_seed=None, staged=None):
+def class_balanced_cross_entropy_loss_frames(output, label, size_average=True, backward_seed=None, staged=None,
+                                             void_pixels=None):
     """``class_balanced_cross_entropy_loss`` of each frame of a batch separately: a [N] tensor whose element i equals
     ``class_balanced_cross_entropy_loss(output[i:i+1], label[i:i+1], size_average)``.  Not in the reference; the
     online loop uses it when it runs several micro-batches of an accumulation cycle as one batched pass, where every
-    frame must keep the class weights of its own [1,1,H,W] tensor (src/train_online.py:80 calls the loss per frame)."""
+    frame must keep the class weights of its own [1,1,H,W] tensor (src/train_online.py:80 calls the loss per frame).
+    ``void_pixels`` as in class_balanced_cross_entropy_loss, per frame; not together with ``staged``."""
     if not output.is_cuda:
         raise RuntimeError("class_balanced_cross_entropy_loss_frames: the HIP implementation needs GPU tensors "
                            "(no CPU fallback)")
@@ -149,7 +184,10 @@ def class_balanced_cross_entropy_loss_frames(output, label, size_average=True, b
             tuple(output.shape), tuple(label.shape)))
     if staged is not None and (staged.label.data_ptr() != label.data_ptr() or tuple(staged.label.shape) != tuple(label.shape)):
         raise ValueError("class_balanced_cross_entropy_loss_frames: `staged` was started on another label tensor")
-    return _CBCELossFrames.apply(output, label, size_average, backward_seed, staged)
+    if void_pixels is not None:
+        void_pixels = _check_void("class_balanced_cross_entropy_loss_frames", output, void_pixels, ("staged", staged))
+        return _CBCELossFrames.apply(output, label, size_average, backward_seed, None, void_pixels)
+    return _CBCELossFrames.apply(output, label, size_average, backward_seed, staged, None)
 
 
 class _CBCELossFramesMulti(torch.autograd.Function):

@@ -10,6 +10,7 @@ reference's logging points, so the loop does not synchronise every iteration.
 Run:  python train_online.py --synthetic --n-epochs 100        (one GPU)
       torchrun --nproc-per-node 8 train_online.py --synthetic --data-parallel --avg-grad-every-n 8
       python train_online.py --synthetic --multi-object --objects 3 --score   (one net per object: train_and_test_objects)
+      python train_online.py --synthetic --adapt-steps 1 --score    (online adaptation in the test pass: test_adaptive)
 """
 import timeit
 from pathlib import Path
@@ -45,6 +46,7 @@ png_fitted = False          # --png-fitted (with --fast-test): Huffman codes fit
 device_decode = False       # --device-decode: the test pass's JPEG frames are decoded on the device (dataloaders/device_decode.py)
 multi_object = False        # --multi-object: one net per object, merged and scored on the device (train_and_test_objects)
 clean = None                # --clean-min-area / --clean-largest / --clean-temporal (with --fast-test): a CleanOptions
+adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
 
@@ -77,8 +79,28 @@ def _clean_seed(train_seed, annotations, data_loader, seq_name: str) -> Optional
     return None
 
 
+def _first_sample(data_loader) -> dict:
+    """The one-shot training frame as it is, neither flipped nor rescaled: ``image`` [1,3,H,W] and ``gt`` [1,1,H,W], what
+    online adaptation keeps training on beside each new frame."""
+    variants = getattr(data_loader, 'variants', None)
+    if variants is not None and 1 in list(data_loader.scales):  # the resident loader: its unflipped variant at scale 1
+        sample = variants[(False, list(data_loader.scales).index(1))]
+        return {'image': sample['image'], 'gt': sample['gt']}
+    dataset = data_loader.dataset
+    if len(dataset) < 1:
+        raise ValueError('online adaptation needs the training frame: the training loader is empty')
+    if getattr(dataset, 'transform', None) is None:
+        sample = dataset[0]
+        if not torch.is_tensor(sample['image']):
+            from dataloaders import custom_transforms
+            sample = custom_transforms.ToTensor()(sample)
+        return {'image': sample['image'][None], 'gt': sample['gt'][None]}
+    raise ValueError('online adaptation needs the training frame as it is; this training loader only yields augmented ones')
+
+
 def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: OnlineSettings) -> None:
     train_seed = None
+    first_sample = None
     io_helper.write_settings(save_dir_models, net_provider.name, settings, variant_offline=settings.variant_offline,
                              variant_online=settings.variant_online)
     summary_writer = _get_summary_writer(path_stem)
@@ -92,6 +114,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                settings.avg_grad_every_n, settings.snapshot_every_n)
         if clean is not None and clean.chain:
             train_seed = _train_annotation(data_loader)
+        if adapt is not None:
+            first_sample = _first_sample(data_loader)
 
     if settings.is_testing:
         if not settings.is_training:
@@ -103,6 +127,18 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
         else:
             save_dir = (save_dir_results / net_provider.name / str(settings.variant_offline) /
                         str(settings.variant_online))
+        if adapt is not None:
+            if first_sample is None:  # this call did not train: the training loader still holds the annotated frame
+                first_sample = _first_sample(io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train, seq_name,
+                                                                             synthetic=synthetic_size))
+            annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
+            result = experiment_helper.test_adaptive(net_provider, data_loader, save_dir, first_sample, adapt, annotations,
+                                                     seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
+            if result is not None:
+                log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
+                experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
+                scored_sequences.append(result)
+            return
         if fast_test:
             annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
             cleaning = {}
@@ -576,7 +612,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean
+    global multi_object, synthetic_objects, clean, adapt
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -592,6 +628,7 @@ def main(argv=None):
         from fosvos_hip.options import CleanOptions
         clean = CleanOptions(min_area=args.clean_min_area or 0, largest=bool(args.clean_largest),
                              temporal_radius=args.clean_temporal)
+    adapt = args.adapt
     synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':

@@ -4,7 +4,8 @@ Same flag names and meanings.  The reference declares ``type=Optional[str]`` for
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
 --data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
---multi-object, --objects, --clean-min-area, --clean-largest and --clean-temporal (online only).
+--multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal and --adapt-steps with its --adapt-* options
+(online only).
 """
 import argparse
 from typing import List, Optional
@@ -64,6 +65,24 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--clean-temporal', type=int, default=None, metavar='R',
                             help='with --fast-test: keep only components within R (0..63) pixels of what the frame before '
                                  'kept; the first frame is gated by the training annotation')
+        parser.add_argument('--adapt-steps', type=int, default=None, metavar='N',
+                            help='online adaptation in the test pass: N (>= 1) fine-tune steps on every frame against '
+                                 'pseudo-labels made from the net\'s own output (confident pixels positive, pixels far from '
+                                 'the last mask negative, the rest ignored); the net leaves the pass adapted')
+        parser.add_argument('--adapt-pos-prob', type=float, default=None, metavar='P',
+                            help='with --adapt-steps: probability from which a pixel is a positive (0.5 < P < 1; default 0.97)')
+        parser.add_argument('--adapt-distance', type=int, default=None, metavar='D',
+                            help='with --adapt-steps: pixels further than D (0..4095) from the eroded last mask are negatives '
+                                 '(default 220)')
+        parser.add_argument('--adapt-erode', type=int, default=None, metavar='E',
+                            help='with --adapt-steps: the last mask is eroded by the disk of radius E (0..4095) first '
+                                 '(default 15)')
+        parser.add_argument('--adapt-frame-weight', type=float, default=None, metavar='W',
+                            help='with --adapt-steps: weight of the current frame\'s loss in a step (> 0; default 1)')
+        parser.add_argument('--adapt-first-weight', type=float, default=None, metavar='W',
+                            help='with --adapt-steps: weight of the annotated first frame\'s loss in a step (>= 0; default 1)')
+        parser.add_argument('--adapt-lr', type=float, default=None, metavar='LR',
+                            help='with --adapt-steps: learning rate of the adaptation steps (default: the online loop\'s, 1e-8)')
         parser.add_argument('--objects', default=2, type=int, metavar='K',
                             help='with --multi-object --synthetic: the number of objects of the synthetic sequence (1..16)')
     if not is_online:
@@ -90,7 +109,7 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
             parser.error('--multi-object reads its frames through the host loader; --device-decode is not wired to it')
         if not 1 <= args.objects <= 16:
             parser.error('--objects counts the objects of the synthetic sequence: 1..16')
-    if is_online and args.png_fitted and not args.fast_test and not args.multi_object:
+    if is_online and args.png_fitted and not args.fast_test and not args.multi_object and args.adapt_steps is None:
         parser.error('--png-fitted chooses the codes of the device PNG encoder: it needs --fast-test')
     if is_online and (args.clean_min_area is not None or args.clean_largest or args.clean_temporal is not None):
         if args.multi_object:
@@ -103,6 +122,45 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
             parser.error('--clean-min-area must be >= 0, got {}'.format(args.clean_min_area))
         if args.clean_temporal is not None and not 0 <= args.clean_temporal <= 63:
             parser.error('--clean-temporal must be 0..63, got {}'.format(args.clean_temporal))
+    if is_online:
+        given = [flag for flag, v in (('--adapt-pos-prob', args.adapt_pos_prob), ('--adapt-distance', args.adapt_distance),
+                                      ('--adapt-erode', args.adapt_erode), ('--adapt-frame-weight', args.adapt_frame_weight),
+                                      ('--adapt-first-weight', args.adapt_first_weight), ('--adapt-lr', args.adapt_lr))
+                 if v is not None]
+        if args.adapt_steps is None and given:
+            parser.error('{} set(s) an option of online adaptation: it needs --adapt-steps'.format(' / '.join(given)))
+        if args.adapt_steps is not None:
+            if args.adapt_steps < 1:
+                parser.error('--adapt-steps counts fine-tune steps per frame: at least 1, got {}'.format(args.adapt_steps))
+            if args.multi_object:
+                parser.error('--adapt-steps adapts ONE net to its own output; adaptation of the K nets of --multi-object '
+                             'is not built')
+            if args.data_parallel:
+                parser.error('--adapt-steps trains inside the test pass, frame by frame on one device; --data-parallel '
+                             'spreads a training cycle over the ranks')
+            if args.eval_speeds:
+                parser.error('--adapt-steps is a PNG-writing test pass that trains; --eval-speeds times a frozen net and '
+                             'writes nothing')
+            if args.device_decode:
+                parser.error('--adapt-steps reads its frames through the host loader; --device-decode is not wired to it')
+            if args.clean_min_area is not None or args.clean_largest or args.clean_temporal is not None:
+                parser.error('--adapt-steps trains the net on the stray blobs that --clean-min-area / --clean-largest / '
+                             '--clean-temporal would filter from the output; the two are not combined')
+            try:
+                from fosvos_hip.options import AdaptOptions
+                defaults = AdaptOptions()
+                args.adapt = AdaptOptions(
+                    steps=args.adapt_steps,
+                    pos_prob=defaults.pos_prob if args.adapt_pos_prob is None else args.adapt_pos_prob,
+                    neg_distance=defaults.neg_distance if args.adapt_distance is None else args.adapt_distance,
+                    erode=defaults.erode if args.adapt_erode is None else args.adapt_erode,
+                    frame_weight=defaults.frame_weight if args.adapt_frame_weight is None else args.adapt_frame_weight,
+                    first_weight=defaults.first_weight if args.adapt_first_weight is None else args.adapt_first_weight,
+                    learning_rate=defaults.learning_rate if args.adapt_lr is None else args.adapt_lr)
+            except ValueError as err:
+                parser.error(str(err).replace('AdaptOptions: ', '--adapt-*: '))
+        else:
+            args.adapt = None
     if is_online and args.device_decode and args.synthetic:
         parser.error('--device-decode decodes JPEG files: the synthetic sequence has none')
     args.is_training = not args.no_training

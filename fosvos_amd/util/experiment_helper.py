@@ -12,7 +12,10 @@ fosvos_jf_counts); ``test`` itself keeps the reference's host path.
 
 ``test_objects`` (``--multi-object``) is ``test_fast`` for a sequence of several objects: K nets, one per object, forward every
 group; the device merges their answers into label maps, encodes palette PNG files and counts J / F per object
-(util/object_merge.py states the definitions)."""
+(util/object_merge.py states the definitions).
+
+``test_adaptive`` (``--adapt-steps N``) is the test pass with online adaptation: between a frame's two forward passes the net
+takes fine-tune steps against pseudo-labels made from its own output on the device (util/online_adapt.py states them)."""
 import timeit
 from pathlib import Path
 from typing import Callable, Optional
@@ -404,6 +407,257 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
              'seconds': time_for_all}
     if clean is not None:
         score['clean'] = clean.as_dict()
+    last_score.clear()
+    last_score.update(score)
+    return score
+
+
+def _first_sample_tensors(first_sample):
+    """(image [1,3,H,W], gt [1,1,H,W]) float32 of the annotated training frame, as the loaders' minibatches hold them."""
+    image, gt = torch.as_tensor(first_sample['image']).float(), torch.as_tensor(first_sample['gt']).float()
+    if image.dim() == 3:
+        image = image[None]
+    while gt.dim() < 4:
+        gt = gt[None]
+    if image.dim() != 4 or image.shape[0] != 1 or gt.dim() != 4 or tuple(gt.shape[:2]) != (1, 1) \
+            or tuple(gt.shape[2:]) != tuple(image.shape[2:]):
+        raise ValueError('test_adaptive: first_sample holds one frame, image [1,3,H,W] and gt [1,1,H,W]; got {} and {}'.format(
+            tuple(image.shape), tuple(gt.shape)))
+    return image.contiguous(), gt.contiguous()
+
+
+def adapt_accumulate(net, first_image, first_gt, x, label, void, weights, with_first: bool = True, no_void=None) -> None:
+    """One accumulation of online adaptation on the device: adds ``weights[0] * grad L(first_image, first_gt) + weights[1] *
+    grad L(x, label, void)`` (``size_average=False``; ``weights``: float32 [2] on the device) to the ``.grad`` of the net's
+    parameters.  Where both frames have one size and H W is a multiple of 4 it is ONE 2-frame pass through the per-frame
+    loss - ``void`` zero for the first frame (``no_void``: that map, made here when None), the backward seed ``weights`` -,
+    else two passes.  ``with_first`` False: the first frame is not forwarded at all.  No host synchronisation."""
+    from layers.osvos_layers import (class_balanced_cross_entropy_loss as cbce,
+                                     class_balanced_cross_entropy_loss_frames as cbce_frames)
+    h, w = int(x.shape[2]), int(x.shape[3])
+    with torch.enable_grad():
+        if with_first and (h * w) % 4 == 0 and tuple(first_image.shape) == tuple(x.shape):
+            if no_void is None:
+                no_void = torch.zeros_like(void)
+            out = net.forward(torch.cat([first_image, x]))[-1]
+            losses = cbce_frames(out, torch.cat([first_gt, label]), size_average=False, void_pixels=torch.cat([no_void, void]))
+            losses.backward(weights)
+            return
+        if with_first:
+            cbce(net.forward(first_image)[-1], first_gt, size_average=False).backward(weights[0])
+        cbce(net.forward(x)[-1], label, size_average=False, void_pixels=void).backward(weights[1])
+
+
+def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt, annotations: Optional[Callable] = None,
+                  seq_name: Optional[str] = None, png_huffman: str = 'fixed', trace: Optional[list] = None) -> Optional[dict]:
+    """The test pass with online adaptation (as in OnAVOS): while the sequence is segmented the net keeps taking fine-tune
+    steps on each new frame against pseudo-labels made from its own output (util/online_adapt.py states them).
+    ``adapt``: a ``fosvos_hip.options.AdaptOptions``.  ``first_sample``: the training frame's ``image`` and ``gt``.  Frames
+    come one at a time, in order (a loader batch of more than one frame is refused).  The chain's first ``last_mask`` is
+    ``first_sample['gt'] >= 0.5``; the optimizer is a fresh ``net_provider.get_optimizer(learning_rate=adapt.learning_rate)``.
+    Per frame x:
+      1. ``logits0 = net.forward(x)[-1]`` under ``no_grad``
+      2. ``ops.adapt_labels(logits0, last_mask, adapt.pos_logit, adapt.neg_distance, adapt.erode)`` -> label, void, counts
+      3. ``adapt.steps`` times: zero the gradients, accumulate ``first_weight * grad L(first frame, gt) + frame_weight *
+         grad L(x, label, void)`` with ``size_average=False``, ``optimizer.step()``.  Where the first frame has x's size and
+         H W is a multiple of 4 this is ONE 2-frame pass through the per-frame loss (``void`` zero for the first frame,
+         backward seed ``[first_weight, frame_weight]``), else two passes; with ``first_weight == 0`` the first frame is
+         not forwarded at all
+      4. ``logits1 = net.forward(x)[-1]`` under ``no_grad``
+      5. ``logits1`` through ``test_fast``'s device path: ``prob_bytes``, ``png_encode``, ``jf_counts`` into one counter
+         tensor read back once, the files written one frame behind
+      6. ``last_mask = logits1 >= 0``
+    Nothing in the per-frame work synchronises with the host.  The class counts of ``adapt_labels`` land in a [n_frames,3]
+    tensor copied once at the end; they go into ``last_fast`` and the score dict under 'adapt', beside the options.
+    ``steps == 0`` performs no training call and constructs no optimizer: the files are ``test_fast``'s.
+    THE NET LEAVES THE PASS ADAPTED: its weights are the ones after the last frame's last step (restoring them is not built;
+    the caller reloads the snapshot where it needs the one-shot net again).
+    ``trace`` (a list, or None) receives per frame a dict of the tensors the loop used, cloned: 'logits0', 'last_mask',
+    'label', 'void' and 'logits1'.
+    CPU logits (the stand-in nets of the CPU tests) take the numpy definitions and ``online_adapt.cbce_void_torch``, the way
+    ``test_fast`` has a host branch.  Returns the score dict of ``test_fast`` with ``annotations``, else None."""
+    from fosvos_hip.options import AdaptOptions
+    from util import online_adapt, png_layout
+    if not isinstance(adapt, AdaptOptions):
+        raise ValueError('test_adaptive: adapt must be a fosvos_hip.options.AdaptOptions, got {!r}'.format(adapt))
+    if png_huffman not in png_layout.HUFFMAN_MODES:
+        raise ValueError('test_adaptive: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
+    if trace is not None and not isinstance(trace, list):
+        raise ValueError('test_adaptive: trace must be a list or None')
+    first_image, first_gt = _first_sample_tensors(first_sample)
+    log.info('Testing Network (adaptive, {} steps a frame)'.format(adapt.steps))
+    net = net_provider.network
+    optimizer = net_provider.get_optimizer(learning_rate=adapt.learning_rate) if adapt.steps > 0 else None
+    pos_logit = adapt.pos_logit
+    n_frames = len(data_loader.dataset)
+    fnames, seqs, scored = [], [], []
+    counts_dev, counts_host, radius = None, np.zeros((n_frames, 6), dtype=np.int64), None
+    adapt_dev, adapt_host = None, np.zeros((n_frames, 3), dtype=np.int64)
+    stores = {}      # (slot, h, w) -> (device bytes, host pinned bytes): two slots, a frame's file is written one frame later
+    pending = None   # (host bytes, capacity, copy-landed event, path) of the frame whose file is not written yet
+    buffers = {}     # (h, w) -> (label, void) of the device labelling
+    on_device = {}   # the first frame, its labels and the pass's constants on the logits' device, made at the first frame
+    last_mask = None
+    png_bytes = 0
+
+    def write_file(path, blob):
+        path.parent.mkdir(parents=True, exist_ok=True)
+        with open(str(path), 'wb') as fh:
+            fh.write(blob)
+
+    def retire(item):
+        nonlocal png_bytes
+        host, cap, landed, path = item
+        landed.synchronize()
+        length = int(host[cap:cap + 4].view(torch.int32)[0])
+        write_file(path, host.numpy()[:length].data)
+        png_bytes += length
+
+    def train_steps(x, label, void):
+        """Step 3 on the device."""
+        for _ in range(adapt.steps):
+            optimizer.zero_grad(set_to_none=False)
+            adapt_accumulate(net, on_device['image'], on_device['gt'], x, label, void, on_device['weights'],
+                             with_first=adapt.first_weight > 0, no_void=on_device['no_void'])
+            optimizer.step()
+
+    def train_steps_host(x, label, void):
+        """Step 3 for CPU logits: the same sum of two losses as one torch-autograd expression per frame."""
+        label_t, void_t = torch.from_numpy(label)[None, None], torch.from_numpy(void)[None, None]
+        with torch.enable_grad():
+            for _ in range(adapt.steps):
+                optimizer.zero_grad(set_to_none=False)
+                if adapt.first_weight > 0:
+                    out = net.forward(first_image)[-1]
+                    (adapt.first_weight * online_adapt.cbce_void_torch(out, first_gt.to(out.device), None, False)).backward()
+                out = net.forward(x)[-1]
+                (adapt.frame_weight * online_adapt.cbce_void_torch(out, label_t.to(out.device), void_t.to(out.device),
+                                                                   False)).backward()
+                optimizer.step()
+
+    time_all_start = timeit.default_timer()
+    for minibatch in data_loader:
+        inputs, = gpu_handler.cast_cuda_if_possible([minibatch['image']])
+        if int(inputs.shape[0]) != 1:
+            raise ValueError('test_adaptive: frames come one at a time (the chain of masks and steps is sequential); the '
+                             'loader yields batches of {}'.format(int(inputs.shape[0])))
+        first = len(fnames)
+        if first + 1 > n_frames:
+            raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
+        with torch.no_grad():
+            logits0 = net.forward(inputs)[-1].detach().float().contiguous()
+        h, w = int(logits0.shape[2]), int(logits0.shape[3])
+        radius = davis_measures.default_radius(h, w)
+        seq, fname = minibatch['seq_name'][0], minibatch['fname'][0]
+        ann = _frame_annotation(annotations, seq, fname, h, w) if annotations is not None else None
+        seqs.append(seq)
+        fnames.append(fname)
+        scored.append(ann is not None)
+        path = Path(save_dir) / seq / '{0}.png'.format(fname)
+        if first == 0 and tuple(first_gt.shape[2:]) != (h, w):
+            raise ValueError('test_adaptive: first_sample is {}, the logits are {}'.format(tuple(first_gt.shape[2:]), (h, w)))
+        if logits0.is_cuda:
+            from fosvos_hip import ops
+            device = logits0.device
+            if not on_device:
+                on_device['image'], on_device['gt'] = first_image.to(device), first_gt.to(device)
+                on_device['weights'] = torch.tensor([adapt.first_weight, adapt.frame_weight], dtype=torch.float32,
+                                                    device=device)
+                on_device['no_void'] = torch.zeros((1, 1, h, w), dtype=torch.uint8, device=device)
+                adapt_dev = torch.zeros((n_frames, 3), dtype=torch.int32, device=device)
+                last_mask = (on_device['gt'][:, 0] >= 0.5).to(torch.uint8)
+            if tuple(last_mask.shape) != (1, h, w):
+                raise ValueError('test_adaptive: the frames changed their size from {} to {}'.format(
+                    tuple(last_mask.shape[1:]), (h, w)))
+            if (h, w) not in buffers:
+                buffers[(h, w)] = (torch.empty((1, 1, h, w), dtype=torch.float32, device=device),
+                                   torch.empty((1, 1, h, w), dtype=torch.uint8, device=device))
+            label, void = buffers[(h, w)]
+            ops.adapt_labels(logits0, last_mask, pos_logit, adapt.neg_distance, adapt.erode, label=label, void=void,
+                             counts=adapt_dev[first:first + 1])
+            if adapt.steps > 0:
+                train_steps(inputs, label, void)
+                with torch.no_grad():
+                    logits1 = net.forward(inputs)[-1].detach().float().contiguous()
+            else:
+                logits1 = logits0
+            if trace is not None:
+                trace.append({'logits0': logits0.clone(), 'last_mask': last_mask.clone(), 'label': label.clone(),
+                              'void': void.clone(), 'logits1': logits1.clone()})
+            with torch.no_grad():
+                if annotations is not None:
+                    if counts_dev is None:
+                        counts_dev = torch.zeros((n_frames, 6), dtype=torch.int32, device=device)
+                    gt = ann[None] if ann is not None else np.zeros((1, h, w), dtype=np.uint8)
+                    ops.jf_counts(logits1, torch.from_numpy(gt).to(device), radius, out=counts_dev[first:first + 1])
+                cap = ops.png_capacity(h, w)
+                cap += -cap % 4  # the length sits behind the file slot, in the same buffer: one copy brings both
+                key = (first % 2, h, w)
+                if key not in stores:
+                    stores[key] = (torch.empty(cap + 4, dtype=torch.uint8, device=device),
+                                   torch.empty(cap + 4, dtype=torch.uint8).pin_memory())
+                dev_store, host_store = stores[key]
+                ops.png_encode(ops.prob_bytes(logits1), out=dev_store[:cap].view(1, cap),
+                               lengths=dev_store[cap:].view(torch.int32), huffman=png_huffman)
+                host_store.copy_(dev_store, non_blocking=True)
+                landed = torch.cuda.Event()
+                landed.record()
+                last_mask = (logits1[:, 0] >= 0).to(torch.uint8)
+            if pending is not None:
+                retire(pending)  # the previous frame's file, while the device works on this frame
+            pending = (host_store, cap, landed, path)
+        else:
+            if last_mask is None:
+                last_mask = (first_gt[0, 0].numpy() >= 0.5).astype(np.uint8)
+            if last_mask.shape != (h, w):
+                raise ValueError('test_adaptive: the frames changed their size from {} to {}'.format(last_mask.shape, (h, w)))
+            x0 = np.ascontiguousarray(logits0[0, 0].numpy(), dtype=np.float32)
+            label, void, adapt_host[first] = online_adapt.adapt_labels(x0, last_mask, pos_logit, adapt.neg_distance,
+                                                                       adapt.erode)
+            if adapt.steps > 0:
+                train_steps_host(inputs, label, void)
+                with torch.no_grad():
+                    logits1 = net.forward(inputs)[-1].detach().float().contiguous()
+            else:
+                logits1 = logits0
+            if trace is not None:
+                trace.append({'logits0': logits0.clone(), 'last_mask': torch.from_numpy(last_mask.copy())[None],
+                              'label': torch.from_numpy(label.copy())[None, None],
+                              'void': torch.from_numpy(void.copy())[None, None], 'logits1': logits1.clone()})
+            x1 = logits1[0, 0].numpy().astype(np.float64)
+            if ann is not None:
+                counts_host[first] = davis_measures.jf_counts_numpy(x1 >= 0, ann, radius)
+            blob = png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x1))), huffman=png_huffman)
+            write_file(path, blob)
+            png_bytes += len(blob)
+            last_mask = (logits1[0, 0].numpy() >= 0).astype(np.uint8)
+    if pending is not None:
+        retire(pending)
+    if counts_dev is not None:
+        counts_host = counts_dev.cpu().numpy().astype(np.int64)
+    if adapt_dev is not None:
+        adapt_host = adapt_dev.cpu().numpy().astype(np.int64)
+    time_for_all = timeit.default_timer() - time_all_start
+    adapt_report = dict(adapt.as_dict(), counts=[[int(v) for v in row] for row in adapt_host[:len(fnames)]])
+    last_fast.clear()
+    last_fast.update(n_frames=len(fnames), n_groups=len(fnames), group_sizes=[1] * len(fnames), seconds=time_for_all,
+                     png_bytes=png_bytes, png_huffman=png_huffman, adapt=adapt_report)
+    log.info('Test {0}: {1} images adapted with {2} steps each, total test time {3} sec'.format(seq_name, len(fnames),
+                                                                                              adapt.steps, time_for_all))
+    if annotations is None:
+        return None
+    counts_host = counts_host[:len(fnames)]
+    j, f = davis_measures.jf_from_counts(counts_host) if len(fnames) else (np.zeros(0), np.zeros(0))
+    keep = np.asarray(scored, dtype=bool)
+    j_stats = davis_measures.sequence_statistics(j[keep])
+    f_stats = davis_measures.sequence_statistics(f[keep])
+    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
+             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep],
+             'counts': [[int(v) for v in row] if k else None for row, k in zip(counts_host, keep)],
+             'J': [float(v) if k else None for v, k in zip(j, keep)],
+             'F': [float(v) if k else None for v, k in zip(f, keep)],
+             'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
+             'seconds': time_for_all, 'adapt': adapt_report}
     last_score.clear()
     last_score.update(score)
     return score

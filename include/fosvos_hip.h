@@ -352,6 +352,19 @@ int fosvos_cbce_loss_frames_multi(const float *const *logits, const float *label
 int fosvos_cbce_loss_batch_counts(const float *logits, const float *label, int64_t numel, int size_average,
                                   float grad_scale, const double *batch_counts, float *loss_out, float *grad,
                                   void *workspace, size_t workspace_bytes, int device, void *stream);
+/* The per-frame loss WITH IGNORED PIXELS (online adaptation trains on pseudo-labels that leave most of a frame undecided):
+ * void_px uint8 [n_frames][frame_numel], non-zero = ignored.  Np and Nn are counted over the valid pixels only and
+ * Ntot = Np + Nn takes numel's place: loss = (Nn/Ntot) * sum_{valid, y=1} l_i + (Np/Ntot) * sum_{valid, y=0} l_i [divided by
+ * Ntot when size_average]; grad_i = scale * w_i * (sigmoid(x_i) - y_i) on a valid pixel and exactly +0.0 on a void one, whose
+ * logit - a NaN too - reaches neither a sum nor a gradient.  Ntot == 0: loss 0, gradient 0.  util/online_adapt.cbce_void
+ * states it in float64.  (Not upstream OSVOS-PyTorch's void_pixels variant, which still counts void pixels as negatives.)
+ * The same kernels as fosvos_cbce_loss_frames in a compile-time void form, the same fixed-order sums: with void_px all zero
+ * the results are that call's bit for bit, a frame of a batch equals the frame alone, two calls agree.  void_px 4-byte
+ * aligned, everything else as for fosvos_cbce_loss_frames; workspace: fosvos_cbce_void_workspace_bytes. */
+size_t fosvos_cbce_void_workspace_bytes(int64_t frame_numel, int n_frames);
+int fosvos_cbce_loss_frames_void(const float *logits, const float *label, const uint8_t *void_px, int64_t frame_numel,
+                                 int n_frames, int size_average, float grad_scale, float *loss_out, float *grad,
+                                 void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* ---- SGD with momentum, torch.optim.SGD semantics, many tensors per launch --------------------
  * For tensor t with n[t] elements: g = grad + wd[t]*p; buf = first_step ? g : momentum*buf + g;
@@ -496,6 +509,33 @@ int fosvos_component_roots(const float *logits, int N, int H, int W, int32_t *ro
 int fosvos_clean_components(const float *logits, const uint8_t *seed, int N, int H, int W, int radius, int min_area,
                             int largest, int chain, float fill, float *out_logits, uint8_t *kept, void *workspace,
                             size_t workspace_bytes, int device, void *stream);
+
+/* ---- pseudo-labels for online adaptation: an exact Euclidean distance gate, and the labelling behind it -----------------
+ * The definitions are stated in numpy in util/online_adapt.py (far_from, adapt_labels); the tests compare with exact
+ * equality.  All distance arithmetic is int32.
+ *
+ * fosvos_distance_gate: mask uint8 [N,H,W] -> out uint8 [N,H,W].  A pixel q is "set" when (mask[q] != 0) != (invert != 0);
+ * out[p] = 1 iff every set q of the frame has (py - qy)^2 + (px - qx)^2 > distance^2 (no set pixel: all 1).  With invert it
+ * is the erosion of the mask by the Euclidean disk, the frame border not eating into it.  Two launches: a column pass
+ * (vertical distances, uint16 saturated at distance + 1) and a row pass over a row staged in LDS.  The first N int32 words
+ * of the workspace receive the frames' flags "the frame has a set pixel".
+ *
+ * fosvos_adapt_labels: logits fp32 [N,1,H,W], last_mask uint8 [N,H,W] -> label fp32 [N,1,H,W], void_px uint8 [N,1,H,W],
+ * counts int32 [N,3] {positives, negatives, void} (zeroed by the call).  core = the mask eroded by the disk of `erode`
+ * (erode == 0: last_mask != 0); a pixel further than neg_distance from every core pixel is a negative (label 0, void 0) -
+ * unless the core is empty, which names no negatives; elsewhere logits >= pos_logit is a positive (label 1, void 0; a NaN
+ * is not, +inf is); the rest is void (label 0, void 1).  Two launches, four with erode > 0; the last row pass labels and
+ * counts (one atomic per workgroup and class).
+ *
+ * Limits: distance, neg_distance, erode 0..4095 (FOSVOS_E_ARG); 1 <= H, W <= 8192, 1 <= N <= 65535 (FOSVOS_E_SHAPE; the
+ * workspace sizes are 0 outside them).  workspace: 16-byte aligned.  Nothing is launched when a check fails. */
+size_t fosvos_distance_gate_workspace_bytes(int N, int H, int W);
+int fosvos_distance_gate(const uint8_t *mask, int N, int H, int W, int distance, int invert, uint8_t *out, void *workspace,
+                         size_t workspace_bytes, int device, void *stream);
+size_t fosvos_adapt_labels_workspace_bytes(int N, int H, int W);
+int fosvos_adapt_labels(const float *logits, const uint8_t *last_mask, int N, int H, int W, float pos_logit, int neg_distance,
+                        int erode, float *label, uint8_t *void_px, int32_t *counts, void *workspace, size_t workspace_bytes,
+                        int device, void *stream);
 
 /* ---- the streamed output frames as JPEG files, encoded on the device --------------------------------------------------
  * fosvos_jpeg_encode: frames uint8 [N,H,W,3] BGR (what fosvos_overlay writes; components = 3) or [N,H,W] grey (components =
