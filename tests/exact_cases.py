@@ -234,13 +234,15 @@ def pool_windows(x):
     return xp.reshape(n, c, (h + 1) // 2, 2, (w + 1) // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, (h + 1) // 2, (w + 1) // 2, 4)
 
 
-def pool_backward(x, d_pooled):
-    """Exactly routed pool gradient: each window's gradient goes to its FIRST maximum in scan order, and only where that
-    maximum is > 0 (the ReLU mask of the producer)."""
+def pool_backward(x, d_pooled, relu_mask=True):
+    """Exactly routed pool gradient: each window's gradient goes to its FIRST maximum in scan order, and (relu_mask) only
+    where that maximum is > 0 (the ReLU mask of the producer)."""
     n, c, h, w = x.shape
     win = pool_windows(x)
     is_max = win == win.max(-1, keepdim=True).values
-    first = is_max & (is_max.int().cumsum(-1) == 1) & (win > 0)
+    first = is_max & (is_max.int().cumsum(-1) == 1)
+    if relu_mask:
+        first = first & (win > 0)
     r = torch.where(first, d_pooled.unsqueeze(-1).expand_as(win), torch.zeros_like(win))  # (+0 elsewhere, not -0)
     oh, ow = (h + 1) // 2, (w + 1) // 2
     r = r.reshape(n, c, oh, ow, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, 2 * oh, 2 * ow)
