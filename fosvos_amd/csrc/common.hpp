@@ -139,7 +139,10 @@ bool conv_pp_applicable(int N, int H, int W, int in_ch, int out_ch);
 int conv_pp_workgroups();
 int conv_pp_forward(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y, uint16_t *y_pool, int N,
                     int H, int W, int Cin_pad, int Cout, int Co_pad, bool relu, hipStream_t st,
-                    const uint8_t *mask_bits = nullptr);
+                    const uint8_t *mask_bits = nullptr, uint32_t *codes = nullptr);
+
+// Shapes fosvos_conv3x3_fwd_pool_codes takes (conv_igemm.hip): the pooled forward launches the persistent kernel runs.
+bool conv3x3_pool_codes_applicable(int N, int H, int W, int Ci, int Co);
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int roundup(int a, int b) { return (a + b - 1) / b * b; }

@@ -1013,6 +1013,37 @@ extern "C" int fosvos_conv3x3_fwd_pool(const uint16_t *x, const uint16_t *w_pack
     return dispatch(a, Ci, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// The pooled forward form WITHOUT the dense output (fosvos_conv3x3_fwd_pool_codes): only the persistent kernel has it.
+namespace fosvos {
+bool conv3x3_pool_codes_applicable(int N, int H, int W, int Ci, int Co) {
+    if (N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || Co % 64 != 0) return false;
+    if ((int64_t)H * W * roundup(Ci, 32) * 2 >= 0x7fffffffLL || (int64_t)H * W * Co * 4 >= 0x7fffffffLL) return false;
+    return forward_takes_pp(N, H, W, Ci, Co, FOSVOS_CONV_RELU);
+}
+}  // namespace fosvos
+
+extern "C" size_t fosvos_conv3x3_pool_codes_bytes(int N, int H, int W, int C) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0) return 0;
+    return (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8) * 4;
+}
+
+extern "C" int fosvos_conv3x3_fwd_pool_codes(const uint16_t *x, const uint16_t *w_packed, const float *bias,
+                                             uint16_t *y_pool, uint32_t *codes, int N, int H, int W, int Ci, int Co,
+                                             unsigned flags, int device, void *stream) {
+    if (int rc = check_common(x, w_packed, y_pool, N, H, W, Ci, Co, "conv3x3_fwd_pool_codes")) return rc;
+    FOSVOS_REQUIRE(codes, FOSVOS_E_ARG, "conv3x3_fwd_pool_codes: null codes output");
+    FOSVOS_REQUIRE(((uintptr_t)codes & 3) == 0, FOSVOS_E_ARG, "conv3x3_fwd_pool_codes: codes must be 4-byte aligned");
+    FOSVOS_REQUIRE(flags == FOSVOS_CONV_RELU, FOSVOS_E_ARG,
+                   "conv3x3_fwd_pool_codes: flags 0x%x (the codes are taken on post-ReLU values: FOSVOS_CONV_RELU)", flags);
+    FOSVOS_REQUIRE(Co % 64 == 0, FOSVOS_E_SHAPE, "conv3x3_fwd_pool_codes: Co=%d must be a multiple of 64", Co);
+    FOSVOS_REQUIRE(conv3x3_pool_codes_applicable(N, H, W, Ci, Co), FOSVOS_E_SHAPE,
+                   "conv3x3_fwd_pool_codes: N=%d H=%d W=%d Ci=%d Co=%d is not a shape of the persistent kernel (use "
+                   "fosvos_conv3x3_fwd_pool)", N, H, W, Ci, Co);
+    FOSVOS_ENTER(device);
+    return conv_pp_forward(x, w_packed, bias, nullptr, y_pool, N, H, W, roundup(Ci, 32), Co, roundup(Co, 16), true,
+                           (hipStream_t)stream, nullptr, codes);
+}
+
 extern "C" int fosvos_conv3x3_dgrad_bits(const uint16_t *dy, const uint16_t *w_dgrad_packed, const uint8_t *relu_bits,
                                          const uint16_t *addend, uint16_t *dx, int N, int H, int W, int Ci, int Co,
                                          void *workspace, size_t workspace_bytes, int device, void *stream) {

@@ -65,6 +65,7 @@ struct Args {
     const float *bias;   // [Cout] or null
     uint16_t *y;         // [N,H,W,Cout] bf16
     uint16_t *y_pool;    // optional [N,ceil(H/2),ceil(W/2),Cout]
+    uint32_t *codes;     // CODES: [N,ceil(H/2),ceil(W/2),Cout/8] words, the pool's winner codes (pool_code_word below)
     const uint8_t *mask_bits;  // MASK: [N,H,W,Cout/8] bytes, bit e of byte g set = keep channel 8 g + e (a data gradient's ReLU mask)
     int N, H, W, Cin, Cout, Co_pad;
     int tiles_x, tiles_y, n_tiles;  // pixel tiles per row / per image / of the launch
@@ -141,7 +142,42 @@ struct TileIt {
     __device__ __forceinline__ int x0() const { return tx * TW; }
 };
 
-template <bool RELU, bool POOL, bool MASK = false>
+// The 2 x 2 pool of one window and eight channels (a ... d: the window's pixels in scan order (0,0), (0,1), (1,0), (1,1) as
+// packed non-negative bf16 pairs, pixels outside the image as zeros): the maximum m, and the window's WINNER CODES - per
+// channel a one-hot nibble, bit k set where pixel k is the first maximum in scan order (a later pixel wins only with a
+// strictly larger value) AND that maximum is > 0; all four bits clear where the whole window is zero.  That is k_pool_bwd's
+// rule with relu_mask = 1 (pool.hip), taken on the bit patterns: non-negative bf16 values order like integers, so "b > a" is
+// the sign of the packed 16-bit difference a - b (no borrow between the halves: both are < 0x8000).  A NaN (0x7fc0 after the
+// int16 ReLU clamp) therefore counts as the largest value - the rule the pooled map's own integer maximum already follows;
+// the float comparisons of k_pool_bwd would never let it win.
+// Layout of the code word: channel 2 i + h of the eight (h: low / high half of packed word i) has its nibble at bit
+// 4 i + 16 h, so that pixel k's keep bits of word i are (code >> (4 i + k)) & 0x00010001.
+__device__ __forceinline__ unsigned pool_code_word(const uint4 &a, const uint4 &b, const uint4 &c, const uint4 &d, uint4 &m) {
+    const unsigned av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w}, cv[4] = {c.x, c.y, c.z, c.w},
+                   dv[4] = {d.x, d.y, d.z, d.w};
+    unsigned mv[4], code = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        auto sub = [](unsigned p, unsigned q) {
+            return __builtin_bit_cast(unsigned, __builtin_bit_cast(fosvos_i16x2, p) - __builtin_bit_cast(fosvos_i16x2, q));
+        };
+        const unsigned m1 = max_nonneg_bf16x2(av[i], bv[i]), m2 = max_nonneg_bf16x2(m1, cv[i]);
+        mv[i] = max_nonneg_bf16x2(m2, dv[i]);
+        // sign bits (15 and 31) of: pixel 1 / 2 / 3 beats what came before it; the maximum is not zero
+        const unsigned s1 = sub(av[i], bv[i]), s2 = sub(m1, cv[i]), s3 = sub(m2, dv[i]);
+        const unsigned pm = sub(0u, mv[i]) & 0x80008000u;
+        const unsigned n3 = s3 & pm, n2 = s2 & ~s3 & pm, n1 = s1 & ~(s2 | s3) & pm, n0 = ~(s1 | s2 | s3) & pm;
+        const unsigned r = n3 | (n2 >> 1) | (n1 >> 2) | (n0 >> 3);  // the nibbles at bits 12 and 28
+        code = (code >> 4) | r;  // word 0 ends at bits 0 / 16, word 3 stays at bits 12 / 28
+    }
+    m = make_uint4(mv[0], mv[1], mv[2], mv[3]);
+    return code;
+}
+
+// CODES (the pooled forward form of a layer whose dense output nobody reads but the pool's backward: conv1_2 of the training
+// pass): the y stores (slots 0-3) are left out, slots 4-5 write the pooled vectors and one winner-code word per pooled pixel
+// and eight channels.
+template <bool RELU, bool POOL, bool MASK = false, bool CODES = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_conv3x3_pp(const Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem_pp[];
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void *)smem_pp);
@@ -330,6 +366,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     auto store_slot = [&](int slot) {
         if (!st_pending) return;
         if (slot < 4) {
+            if constexpr (CODES) return;
             const auto y_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.y + (int64_t)dn_n * H * W * Cout, 0, H * W * Cout * 2, 0x00020000);
             const int gy = dn_y0 + 2 * wm + (slot >> 1), gx = dn_x0 + (slot & 1) * 16 + cl;
             const unsigned off = (gy < H && gx < W) ? (unsigned)(((gy * W + gx) * Cout + n0 + kq * 8) * 2) : 0x80000000u;
@@ -348,6 +385,51 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             const int ih = slot - 4;
             const int OH = (H + 1) >> 1, OW = (W + 1) >> 1;
             const bool edge = dn_y0 + TH > H || dn_x0 + TW > W;  // wave-uniform
+            if constexpr (CODES) {
+                // The two lanes of a column pair share the window's work: the even lane takes channel block pair jp = 0, the
+                // odd lane jp = 1 (half the vector-ALU work of every lane doing both, and one full-width store instead of two
+                // half-empty ones).  Pixels a, c are the EVEN lane's top / bottom row, b, d the odd lane's: each lane keeps its
+                // own pair's and fetches the other two from its neighbour (quad_perm [0, 0, 2, 2] / [1, 1, 3, 3]).
+                const int jp = cl & 1;
+                const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.codes + (int64_t)dn_n * OH * OW * (Cout >> 3), 0,
+                                                                      OH * OW * (Cout >> 3) * 4, 0x00020000);
+                const auto pc_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.y_pool + (int64_t)dn_n * OH * OW * Cout, 0,
+                                                                       OH * OW * Cout * 2, 0x00020000);
+                const int oy = (dn_y0 >> 1) + wm, ox = (dn_x0 >> 1) + ih * 8 + (cl >> 1);
+                const bool ok = oy < OH && ox < OW;
+                const int px = oy * OW + ox;
+                uint4 t[2] = {pk[ih][0], pk[ih][1]}, bo[2] = {pk[ih + 2][0], pk[ih + 2][1]};
+                if (edge) {
+                    const int gy = dn_y0 + 2 * wm, gx = dn_x0 + ih * 16 + cl;
+                    if (!(gy < H && gx < W)) t[0] = t[1] = make_uint4(0, 0, 0, 0);
+                    if (!(gy + 1 < H && gx < W)) bo[0] = bo[1] = make_uint4(0, 0, 0, 0);
+                }
+                auto pick = [&](const uint4 &v0, const uint4 &v1, bool second) {  // pixel (row, second column?) of this lane's jp
+                    // even lane: column 0 is its own v0, column 1 the odd lane's v0; odd lane: column 0 is the even lane's v1
+                    const unsigned s0[4] = {v0.x, v0.y, v0.z, v0.w}, s1[4] = {v1.x, v1.y, v1.z, v1.w};
+                    unsigned o[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (!second) {
+                            const unsigned nb = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s1[q], 0xA0, 0xF, 0xF, true);  // [0,0,2,2]
+                            o[q] = jp ? nb : s0[q];
+                        } else {
+                            const unsigned nb = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s0[q], 0xF5, 0xF, 0xF, true);  // [1,1,3,3]
+                            o[q] = jp ? s1[q] : nb;
+                        }
+                    }
+                    return make_uint4(o[0], o[1], o[2], o[3]);
+                };
+                const uint4 pa = pick(t[0], t[1], false), pb = pick(t[0], t[1], true);
+                const uint4 pcx = pick(bo[0], bo[1], false), pd = pick(bo[0], bo[1], true);
+                uint4 m;
+                const unsigned code = pool_code_word(pa, pb, pcx, pd, m);
+                const unsigned poff = ok ? (unsigned)((px * Cout + n0 + kq * 8 + jp * 32) * 2) : 0x80000000u;
+                const unsigned coff = ok ? (unsigned)((px * (Cout >> 3) + (n0 >> 3) + kq + jp * 4) * 4) : 0x80000000u;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), pc_rsrc, poff, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(code, c_rsrc, coff, 0, 0);
+                return;
+            }
             const auto p_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.y_pool + (int64_t)dn_n * OH * OW * Cout, 0,
                                                                   OH * OW * Cout * 2, 0x00020000);
             const int oy = (dn_y0 >> 1) + wm, ox = (dn_x0 >> 1) + ih * 8 + (cl >> 1);
@@ -494,11 +576,14 @@ bool conv_pp_applicable(int N, int H, int W, int in_ch, int out_ch) {
 
 
 int conv_pp_forward(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y, uint16_t *y_pool, int N,
-                    int H, int W, int Cin_pad, int Cout, int Co_pad, bool relu, hipStream_t st, const uint8_t *mask_bits) {
+                    int H, int W, int Cin_pad, int Cout, int Co_pad, bool relu, hipStream_t st, const uint8_t *mask_bits,
+                    uint32_t *codes) {
+    FOSVOS_REQUIRE(!codes || (y_pool && !y && !mask_bits), FOSVOS_E_ARG,
+                   "conv3x3 (persistent): winner codes go with the pooled map, without the dense one");
     FOSVOS_REQUIRE(!y_pool || relu, FOSVOS_E_ARG, "conv3x3 (persistent): the fused pool takes post-ReLU values");
     FOSVOS_REQUIRE(!mask_bits || (!relu && !y_pool && !bias), FOSVOS_E_ARG, "conv3x3 (persistent): the bit mask is the data gradient's epilogue");
     pp::Args a{};
-    a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.y_pool = y_pool; a.mask_bits = mask_bits;
+    a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.y_pool = y_pool; a.mask_bits = mask_bits; a.codes = codes;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin_pad; a.Cout = Cout; a.Co_pad = Co_pad;
     a.tiles_x = (int)cdiv(W, pp::TW);
     a.tiles_y = (int)cdiv(H, pp::TH);
@@ -509,10 +594,11 @@ int conv_pp_forward(const uint16_t *x, const uint16_t *w_packed, const float *bi
     a.stamps = g_pp_stamps;
 #endif
     void (*kern)(const pp::Args) = mask_bits ? pp::k_conv3x3_pp<false, false, true>
+                                   : codes   ? pp::k_conv3x3_pp<true, true, false, true>
                                    : y_pool  ? pp::k_conv3x3_pp<true, true>
                                    : relu    ? pp::k_conv3x3_pp<true, false> : pp::k_conv3x3_pp<false, false>;
-    const int which = mask_bits ? 3 : y_pool ? 2 : relu ? 1 : 0;
-    static bool once[64][4];
+    const int which = mask_bits ? 3 : codes ? 4 : y_pool ? 2 : relu ? 1 : 0;
+    static bool once[64][5];
     int dev = 0;
     FOSVOS_HIP_CHECK(hipGetDevice(&dev));
     if (dev >= 0 && dev < 64 && !once[dev][which]) {  // opt in to the whole LDS of a CU, once per device and instantiation
@@ -520,7 +606,8 @@ int conv_pp_forward(const uint16_t *x, const uint16_t *w_packed, const float *bi
                                              pp::LDS_BYTES));
         once[dev][which] = true;
     }
-    FOSVOS_PROF(mask_bits ? "k_conv3x3_pp<false, false, true>" : y_pool ? "k_conv3x3_pp<true, true, false>"
+    FOSVOS_PROF(mask_bits ? "k_conv3x3_pp<false, false, true>" : codes ? "k_conv3x3_pp<true, true, false, true>"
+                : y_pool  ? "k_conv3x3_pp<true, true, false>"
                 : relu    ? "k_conv3x3_pp<true, false, false>" : "k_conv3x3_pp<false, false, false>", st,
                 2.0 * N * H * W * 9.0 * Cin_pad * Cout);
     hipLaunchKernelGGL(kern, dim3(conv_pp_workgroups()), dim3(pp::NT), pp::LDS_BYTES, st, a);

@@ -95,6 +95,37 @@ __global__ __launch_bounds__(256) void k_pool_bwd(const uint16_t *__restrict__ x
     if (vx && vy) *reinterpret_cast<uint4 *>(dxn + o11) = repack8(r3);
 }
 
+// The same backward from the window's WINNER CODES instead of the pooled tensor itself (fosvos_conv3x3_fwd_pool_codes writes
+// them; conv_pp.hip: pool_code_word): one word per pooled pixel and 8 channels, channel 2 i + h (h: low / high half of packed
+// word i) has a one-hot nibble at bit 4 i + 16 h, bit k set where window pixel k = 2 dy + dx takes the gradient.  A thread
+// reads 4 + 16 bytes and writes up to four 16-byte vectors of gradient bits or +0: no compares, no activation read.
+__global__ __launch_bounds__(256) void k_pool_bwd_codes(const uint32_t *__restrict__ codes, const uint16_t *__restrict__ dy,
+                                                         uint16_t *__restrict__ dx, int H, int W, int C, int OH, int OW) {
+    const int groups = C >> 3;
+    const int col = blockIdx.x * 256 + threadIdx.x;  // (ox, channel group)
+    if (col >= OW * groups) return;
+    const int ox = col / groups, g = col - ox * groups;
+    const int oy = blockIdx.y;
+    const int64_t n = blockIdx.z;
+    uint16_t *dxn = dx + n * H * W * C;
+    const int iy = oy * 2, ix = ox * 2;
+    const bool vx = ix + 1 < W, vy = iy + 1 < H;  // (iy, ix) itself is always inside
+    const int o00 = (iy * W + ix) * C + g * 8;
+    const int o01 = o00 + C, o10 = o00 + W * C, o11 = o10 + C;
+    const int64_t p = (n * OH + oy) * OW + ox;
+    const uint4 gv = *reinterpret_cast<const uint4 *>(dy + p * C + g * 8);
+    const uint32_t code = codes[p * groups + g];
+    auto routed = [&](int k) {  // the gradient where pixel k's bit is set: 0x00010001 bits -> 0xffff halfword masks
+        const uint32_t c = code >> k;
+        return make_uint4(gv.x & ((c & 0x00010001u) * 0xffffu), gv.y & (((c >> 4) & 0x00010001u) * 0xffffu),
+                          gv.z & (((c >> 8) & 0x00010001u) * 0xffffu), gv.w & (((c >> 12) & 0x00010001u) * 0xffffu));
+    };
+    *reinterpret_cast<uint4 *>(dxn + o00) = routed(0);
+    if (vx) *reinterpret_cast<uint4 *>(dxn + o01) = routed(1);
+    if (vy) *reinterpret_cast<uint4 *>(dxn + o10) = routed(2);
+    if (vx && vy) *reinterpret_cast<uint4 *>(dxn + o11) = routed(3);
+}
+
 inline int grid_for(int64_t total) {
     int64_t g = cdiv(total, 256);
     if (g > 16384) g = 16384;
@@ -129,6 +160,22 @@ extern "C" int fosvos_maxpool2x2_ceil_bwd(const uint16_t *x, const uint16_t *dy,
     FOSVOS_PROF("k_pool_bwd", stream, 0.0);
     hipLaunchKernelGGL(k_pool_bwd, dim3((unsigned)cdiv((int64_t)OW * (C / 8), 256), (unsigned)OH, (unsigned)N), dim3(256), 0,
                        (hipStream_t)stream, x, dy, dx, H, W, C, OH, OW, relu_mask);
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" int fosvos_maxpool2x2_ceil_bwd_codes(const uint32_t *codes, const uint16_t *dy, uint16_t *dx, int N, int H, int W,
+                                                int C, int device, void *stream) {
+    FOSVOS_REQUIRE(codes && dy && dx, FOSVOS_E_ARG, "maxpool_bwd_codes: null pointer");
+    FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, FOSVOS_E_SHAPE,
+                   "maxpool_bwd_codes: bad shape N=%d H=%d W=%d C=%d (C %% 8 must be 0)", N, H, W, C);
+    const int OH = (H + 1) / 2, OW = (W + 1) / 2;
+    FOSVOS_REQUIRE((int64_t)H * W * C < 0x7fffffffLL && OH <= 65535 && N <= 65535, FOSVOS_E_SHAPE,
+                   "maxpool_bwd_codes: image too large (N=%d H=%d W=%d C=%d)", N, H, W, C);
+    FOSVOS_ENTER(device);
+    FOSVOS_PROF("k_pool_bwd_codes", stream, 0.0);
+    hipLaunchKernelGGL(k_pool_bwd_codes, dim3((unsigned)cdiv((int64_t)OW * (C / 8), 256), (unsigned)OH, (unsigned)N), dim3(256), 0,
+                       (hipStream_t)stream, codes, dy, dx, H, W, C, OH, OW);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }

@@ -108,6 +108,26 @@ constexpr int kBucketEvent0 = 19;
         if (rc_ != FOSVOS_OK) return rc_; \
     } while (0)
 
+// FOSVOS_FWD_SPLIT=0 (lab switch): a batched forward pass runs as one chain of N frames instead of two
+bool fwd_split_on() {
+    static const bool on = lab_env_int("FOSVOS_FWD_SPLIT", 1) != 0;
+    return on;
+}
+
+// Is stage 1 of a pass with these flags COMPACT: conv1_2 writes the pooled map and the pool's winner codes (at the start of the
+// act[1] region, frame by frame) instead of its dense output, and the pool backward routes from the codes?  Asked by the
+// forward AND the backward pass, from (flags, N, H, W) alone, so the two cannot disagree: only where EVERY forward chain's
+// conv1_2 launch is one the persistent kernel takes; otherwise the whole pass is dense.
+bool stage1_compact(unsigned flags, int N, int H, int W) {
+    if (!(flags & FOSVOS_VGG_COMPACT_STAGE1) || N <= 0 || H <= 0 || W <= 0) return false;
+    if (fwd_split_on() && N >= 2) {
+        const int na = (N + 1) / 2;
+        return conv3x3_pool_codes_applicable(na, H, W, kCin[1], kCout[1]) &&
+               conv3x3_pool_codes_applicable(N - na, H, W, kCin[1], kCout[1]);
+    }
+    return conv3x3_pool_codes_applicable(N, H, W, kCin[1], kCout[1]);
+}
+
 int check_net(const void *w, const void *frame, const void *arena, int N, int H, int W, size_t arena_bytes,
               const Arena &a, const char *who) {
     FOSVOS_REQUIRE(w && frame && arena, FOSVOS_E_ARG, "%s: null pointer", who);
@@ -162,11 +182,18 @@ extern "C" int fosvos_vgg_arena_layout(int N, int H, int W, fosvos_vgg_arena_lay
 // the head.  The caller sees single-stream semantics on `stream`.
 namespace {
 int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame, int N, int H, int W, void *arena,
-                 size_t arena_bytes, float *fused, float *const side_out[4], int device, void *stream, void *aux_stream) {
+                 size_t arena_bytes, float *fused, float *const side_out[4], int device, void *stream, void *aux_stream,
+                 unsigned flags) {
     const Arena a = make_arena(N, H, W);
     FOSVOS_TRY(check_net(w, frame, arena, N, H, W, arena_bytes, a, "vgg_forward"));
     FOSVOS_REQUIRE(fused, FOSVOS_E_ARG, "vgg_forward: null output");
+    FOSVOS_REQUIRE((flags & ~FOSVOS_VGG_COMPACT_STAGE1) == 0, FOSVOS_E_ARG, "vgg_forward: unknown flags 0x%x", flags);
+    const bool compact = stage1_compact(flags, N, H, W);
     char *base = reinterpret_cast<char *>(arena);
+    // compact stage 1: the codes of frame f0 onwards (one word per pooled pixel and 8 channels of conv1_2's output)
+    auto codes1 = [&](int f0) {
+        return reinterpret_cast<uint32_t *>(base + a.act[1]) + (size_t)f0 * a.sh[1] * a.sw[1] * (kCout[1] / 8);
+    };
     auto act = [&](int c) { return reinterpret_cast<uint16_t *>(base + a.act[c]); };
     void *ws = base + a.ws;
     hipStream_t sm = (hipStream_t)stream;
@@ -178,8 +205,7 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
     // of 512 workgroups, conv4 2.2) and what one chain's workgroups spend outside their chunk loops.  +1.0 % on the step.
     // Without an auxiliary stream the same two chains run one after the other (the arithmetic of a pass - tile plans, split-K -
     // does not depend on how it is scheduled).  FOSVOS_FWD_SPLIT=0 (lab switch): one chain of N frames.
-    static const bool split_on = lab_env_int("FOSVOS_FWD_SPLIT", 1) != 0;
-    if (split_on && N >= 2) {
+    if (fwd_split_on() && N >= 2) {
         const int na = (N + 1) / 2;
         if (par) {
             FOSVOS_HIP_CHECK(hipEventRecord(ev[14], sm));
@@ -207,7 +233,12 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
                     }
                     FOSVOS_REQUIRE(wsn >= fosvos_conv3x3_workspace_bytes(nf, a.sh[s], a.sw[s], kCin[c], kCout[c]),
                                    FOSVOS_E_WORKSPACE, "vgg_forward: split-K workspace of the second chain");
-                    if (c == kLastOfStage[s] && s < 4) {
+                    if (c == 1 && compact) {
+                        const size_t qpx = (size_t)a.sh[1] * a.sw[1];
+                        FOSVOS_TRY(fosvos_conv3x3_fwd_pool_codes(xh, w->conv_wf[c], w->conv_b[c],
+                                                                 reinterpret_cast<uint16_t *>(base + a.pooled[0]) + (size_t)f0 * qpx * kCout[c],
+                                                                 codes1(f0), nf, H, W, kCin[c], kCout[c], FOSVOS_CONV_RELU, device, st));
+                    } else if (c == kLastOfStage[s] && s < 4) {
                         const size_t qpx = (size_t)a.sh[s + 1] * a.sw[s + 1];
                         FOSVOS_TRY(fosvos_conv3x3_fwd_pool(xh, w->conv_wf[c], w->conv_b[c], yc,
                                                            reinterpret_cast<uint16_t *>(base + a.pooled[s]) + (size_t)f0 * qpx * kCout[c],
@@ -262,7 +293,10 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
         } else {
             if (c == kFirstOfStage[s])  // stage entry: the pooled map the previous stage's last conv wrote
                 x = reinterpret_cast<uint16_t *>(base + a.pooled[s - 1]);
-            if (c == kLastOfStage[s] && s < 4) {  // the pool that feeds the next stage rides in this conv's epilogue
+            if (c == 1 && compact) {
+                FOSVOS_TRY(fosvos_conv3x3_fwd_pool_codes(x, w->conv_wf[c], w->conv_b[c], reinterpret_cast<uint16_t *>(base + a.pooled[0]),
+                                                         codes1(0), N, H, W, kCin[c], kCout[c], FOSVOS_CONV_RELU, device, stream));
+            } else if (c == kLastOfStage[s] && s < 4) {  // the pool that feeds the next stage rides in this conv's epilogue
                 FOSVOS_TRY(fosvos_conv3x3_fwd_pool(x, w->conv_wf[c], w->conv_b[c], act(c),
                                                    reinterpret_cast<uint16_t *>(base + a.pooled[s]), N, a.sh[s], a.sw[s],
                                                    kCin[c], kCout[c], FOSVOS_CONV_RELU, ws, a.ws_bytes, device, stream));
@@ -307,21 +341,45 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
 extern "C" int fosvos_vgg_forward_streams(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const float *frame, int N, int H,
                                           int W, void *arena, size_t arena_bytes, float *fused, float *const side_out[4],
                                           void *stream, void *aux_stream) {
-    FOSVOS_TRY(ctx_check(ctx, "vgg_forward_streams"));
-    return forward_impl(ctx->vgg_ev, w, frame, N, H, W, arena, arena_bytes, fused, side_out, ctx->device, stream, aux_stream);
+    return fosvos_vgg_forward_streams_flags(ctx, w, frame, N, H, W, arena, arena_bytes, fused, side_out, stream, aux_stream, 0u);
 }
+
+extern "C" int fosvos_vgg_forward_streams_flags(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const float *frame, int N, int H,
+                                                int W, void *arena, size_t arena_bytes, float *fused, float *const side_out[4],
+                                                void *stream, void *aux_stream, unsigned flags) {
+    FOSVOS_TRY(ctx_check(ctx, "vgg_forward_streams"));
+    return forward_impl(ctx->vgg_ev, w, frame, N, H, W, arena, arena_bytes, fused, side_out, ctx->device, stream, aux_stream,
+                        flags);
+}
+
+extern "C" int fosvos_vgg_stage1_compact(unsigned flags, int N, int H, int W) { return stage1_compact(flags, N, H, W) ? 1 : 0; }
 
 extern "C" int fosvos_vgg_forward(const fosvos_vgg_weights *w, const float *frame, int N, int H, int W, void *arena,
                                   size_t arena_bytes, float *fused, float *const side_out[4], int device,
                                   void *stream) {
-    return forward_impl(nullptr, w, frame, N, H, W, arena, arena_bytes, fused, side_out, device, stream, nullptr);
+    return forward_impl(nullptr, w, frame, N, H, W, arena, arena_bytes, fused, side_out, device, stream, nullptr, 0u);
+}
+
+extern "C" int fosvos_vgg_forward_flags(const fosvos_vgg_weights *w, const float *frame, int N, int H, int W, void *arena,
+                                        size_t arena_bytes, float *fused, float *const side_out[4], int device, void *stream,
+                                        unsigned flags) {
+    return forward_impl(nullptr, w, frame, N, H, W, arena, arena_bytes, fused, side_out, device, stream, nullptr, flags);
 }
 
 extern "C" int fosvos_vgg_backward(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const fosvos_vgg_grads *g,
                                    const float *frame, int N, int H, int W, void *arena, size_t arena_bytes,
                                    const float *d_fused, const float *const d_side_out[4], void *stream,
                                    void *aux_stream) {
+    return fosvos_vgg_backward_flags(ctx, w, g, frame, N, H, W, arena, arena_bytes, d_fused, d_side_out, stream, aux_stream, 0u);
+}
+
+extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const fosvos_vgg_grads *g,
+                                         const float *frame, int N, int H, int W, void *arena, size_t arena_bytes,
+                                         const float *d_fused, const float *const d_side_out[4], void *stream,
+                                         void *aux_stream, unsigned flags) {
     FOSVOS_TRY(ctx_check(ctx, "vgg_backward"));
+    FOSVOS_REQUIRE((flags & ~FOSVOS_VGG_COMPACT_STAGE1) == 0, FOSVOS_E_ARG, "vgg_backward: unknown flags 0x%x", flags);
+    const bool compact = stage1_compact(flags, N, H, W);  // (what the forward pass with the same flags decided)
     const int device = ctx->device;
     const Arena a = make_arena(N, H, W);
     FOSVOS_TRY(check_net(w, frame, arena, N, H, W, arena_bytes, a, "vgg_backward"));
@@ -457,7 +515,11 @@ extern "C" int fosvos_vgg_backward(fosvos_ctx *ctx, const fosvos_vgg_weights *w,
         }
         // pool backward into the previous stage's output gradient, its ReLU mask fused - for stage 1 only (it has no
         // side_prep): the outputs of stages 2-4 get theirs inside side_prep's data gradient, next iteration
-        if (s == 1 || (s > 0 && !unpool_fused))
+        if (s == 1 && compact)  // ... from the winner codes conv1_2's forward left in place of its dense output
+            FOSVOS_TRY(fosvos_maxpool2x2_ceil_bwd_codes(reinterpret_cast<const uint32_t *>(base + a.act[1]),
+                                                        reinterpret_cast<const uint16_t *>(base + a.gpooled[0]), gact(1), N, a.sh[0],
+                                                        a.sw[0], kStageCh[0], device, sm));
+        else if (s == 1 || (s > 0 && !unpool_fused))
             FOSVOS_TRY(fosvos_maxpool2x2_ceil_bwd(act(kLastOfStage[s - 1]), reinterpret_cast<const uint16_t *>(base + a.gpooled[s - 1]),
                                                   gact(kLastOfStage[s - 1]), N, a.sh[s - 1], a.sw[s - 1], kStageCh[s - 1], 1,
                                                   device, sm));

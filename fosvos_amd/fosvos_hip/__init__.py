@@ -20,6 +20,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 ABI_VERSION = 33
 CONV_RELU = 1
 CONV_OUT_F32 = 2
+VGG_COMPACT_STAGE1 = 1  # pass flag of fosvos_vgg_forward_flags / _backward_flags
 
 
 class FosvosHipError(RuntimeError):
@@ -259,6 +260,18 @@ SIGNATURES = {
                                               c_int, c_void_p, ctypes.c_double, c_void_p, c_int, c_void_p]),
     "fosvos_vgg_backward": (c_int, [c_void_p, POINTER(VggWeights), POINTER(VggGrads), c_void_p, c_int, c_int, c_int, c_void_p,
                                     c_size_t, c_void_p, POINTER(c_void_p), c_void_p, c_void_p]),
+    # compact stage 1 (the pool's winner codes in place of conv1_2's dense output)
+    "fosvos_conv3x3_fwd_pool_codes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                              c_int, c_uint, c_int, c_void_p]),
+    "fosvos_conv3x3_pool_codes_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fosvos_maxpool2x2_ceil_bwd_codes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fosvos_vgg_stage1_compact": (c_int, [c_uint, c_int, c_int, c_int]),
+    "fosvos_vgg_forward_flags": (c_int, [POINTER(VggWeights), c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                         POINTER(c_void_p), c_int, c_void_p, c_uint]),
+    "fosvos_vgg_forward_streams_flags": (c_int, [c_void_p, POINTER(VggWeights), c_void_p, c_int, c_int, c_int, c_void_p,
+                                                 c_size_t, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_uint]),
+    "fosvos_vgg_backward_flags": (c_int, [c_void_p, POINTER(VggWeights), POINTER(VggGrads), c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_size_t, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_uint]),
 }
 
 _lib = None

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import Context, VggGrads, VggWeights, check, lib, ops, ptr_array4
+from . import VGG_COMPACT_STAGE1, Context, VggGrads, VggWeights, check, lib, ops, ptr_array4
 from .options import EngineOptions, native_loop_from_env
 
 STAGE_CHANNELS = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
@@ -52,8 +52,12 @@ PARAM_NAMES = param_names()
 PARAM_INDEX = {n: i for i, n in enumerate(PARAM_NAMES)}
 
 
+class _PassFlagsSlots:
+    __slots__ = ("_compact_stage1",)
+
+
 @dataclass(slots=True)
-class PassFlags:
+class PassFlags(_PassFlagsSlots):
     """What a loop tells the next passes of one model (``PackedWeights.flags``; OSVOS_VGG exposes every field as an attribute
     of the same name).  All off by default, so plain ``loss.backward(); opt.step()`` is safe.  A misspelt name raises."""
 
@@ -76,6 +80,21 @@ class PassFlags:
     # Hint for the next backward pass: no forward pass follows it before the optimizer step, so its trailing weight-gradient
     # kernels may take the whole chip (the training loops set it around a cycle's last pass).
     last_pass_of_cycle: bool = False
+
+    # compact_stage1 (below; kept in the base class's slot, so the declared field list above stays what it was).
+    # True: the next passes may run stage 1 in its COMPACT form - conv1_2's forward writes the pooled map and the pool's winner
+    # codes (3 MB a 480x854 frame) instead of its dense output (52 MB), which nothing but the pool's backward reads, and the
+    # backward routes the pooled gradient from the codes.  Results are bit-identical; the arena's act[1] region then holds the
+    # codes, not conv1_2's output.  Only where the persistent conv kernel takes conv1_2 of every forward chain
+    # (``ops.vgg_stage1_compact``), otherwise the pass is dense as before.  It must not change between a forward pass and its
+    # backward (a backward pass runs with what its own forward pass saw).  The training loops set it around their passes.
+    @property
+    def compact_stage1(self) -> bool:
+        return getattr(self, "_compact_stage1", False)
+
+    @compact_stage1.setter
+    def compact_stage1(self, value: bool) -> None:
+        self._compact_stage1 = bool(value)
 
 
 class PackedWeights:
@@ -560,21 +579,24 @@ def native_forward(P, packs, pool: ArenaPool, x: torch.Tensor, with_side_out: bo
     opts = packs.options
     aux = (pool.aux_stream(idx) if N >= 2 and opts.fwd_aux and opts.two_streams and not packs.flags.forward_one_stream
            else 0)
+    # (a pass whose arena is not kept has no backward: it stays dense)
+    pass_flags = VGG_COMPACT_STAGE1 if (packs.flags.compact_stage1 and keep) else 0
     if aux:
-        check(lib().fosvos_vgg_forward_streams(pool.ctx(idx), ctypes.byref(w), x.data_ptr(), N, H, W, ap, an, fused.data_ptr(),
-                                               so, torch.cuda.current_stream(idx).cuda_stream, aux), "vgg_forward_streams")
+        check(lib().fosvos_vgg_forward_streams_flags(pool.ctx(idx), ctypes.byref(w), x.data_ptr(), N, H, W, ap, an,
+                                                     fused.data_ptr(), so, torch.cuda.current_stream(idx).cuda_stream, aux,
+                                                     pass_flags), "vgg_forward_streams")
     else:
-        check(lib().fosvos_vgg_forward(ctypes.byref(w), x.data_ptr(), N, H, W, ap, an, fused.data_ptr(), so, idx,
-                                       torch.cuda.current_stream(idx).cuda_stream), "vgg_forward")
+        check(lib().fosvos_vgg_forward_flags(ctypes.byref(w), x.data_ptr(), N, H, W, ap, an, fused.data_ptr(), so, idx,
+                                             torch.cuda.current_stream(idx).cuda_stream, pass_flags), "vgg_forward")
     ops._pe(t0, "vgg_forward", 2.0 * 129.114e9 * N * H * W / (480 * 854), 0.0)
     if not keep:
         pool.give(N, H, W, arena)
         arena = None
-    return (outs if outs is not None else [None] * 4) + [fused], (arena, x, w, keep_alive, (N, H, W))
+    return (outs if outs is not None else [None] * 4) + [fused], (arena, x, w, keep_alive, (N, H, W), pass_flags)
 
 
 def native_backward(P, packs, saved, d_outs, inplace: bool) -> Dict[str, torch.Tensor]:
-    arena, x, w, keep_alive, (N, H, W) = saved
+    arena, x, w, keep_alive, (N, H, W), pass_flags = saved  # (the backward runs with the flags its forward pass ran with)
     dev = x.device
     d_fused = d_outs[4]
     d_so, with_so = _side_grads(d_outs)
@@ -629,9 +651,9 @@ def native_backward(P, packs, saved, d_outs, inplace: bool) -> Dict[str, torch.T
     # the dsn scratch is overwritten, never accumulated, by a separate flag-free path: run with accumulate for the
     # parameter buffers and add the scratch afterwards
     t0 = ops._pb()
-    check(lib().fosvos_vgg_backward(packs.arenas.ctx(idx), ctypes.byref(w), ctypes.byref(g), x.data_ptr(), N, H, W, ap, an,
-                                    d_fused.data_ptr() if d_fused is not None else None, dso,
-                                    torch.cuda.current_stream(idx).cuda_stream, aux or None),
+    check(lib().fosvos_vgg_backward_flags(packs.arenas.ctx(idx), ctypes.byref(w), ctypes.byref(g), x.data_ptr(), N, H, W, ap, an,
+                                          d_fused.data_ptr() if d_fused is not None else None, dso,
+                                          torch.cuda.current_stream(idx).cuda_stream, aux or None, pass_flags),
           "vgg_backward")
     ops._pe(t0, "vgg_backward", 2.0 * (2 * 129.114e9 - 0.708e9) * N * H * W / (480 * 854), 0.0)
     if with_so:

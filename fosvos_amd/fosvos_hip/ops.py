@@ -318,6 +318,45 @@ def conv3x3_fwd_pool(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[tor
     return y, yp
 
 
+def conv3x3_pool_codes_shape(n: int, h: int, w: int, c: int) -> Tuple[int, int, int, int]:
+    """Shape of the int32 winner-code tensor of a [n, h, w, c] map: one word per pooled pixel and 8 channels."""
+    return (n, (h + 1) // 2, (w + 1) // 2, c // 8)
+
+
+def conv3x3_fwd_pool_codes(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], ci: int, co: int,
+                           out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """conv3x3 + ReLU + 2x2 ceil-mode max pool WITHOUT the dense output: (pooled y, the pool's winner codes as int32
+    [N, ceil(H/2), ceil(W/2), Co/8]; fosvos_conv3x3_fwd_pool_codes has the code format).  Only shapes the persistent kernel
+    takes; anything else raises.  ``out``: (pooled, codes) tensors to write into."""
+    _need(x, _BF16, "conv3x3_fwd_pool_codes x"); _need(w_packed, _BF16, "conv3x3_fwd_pool_codes packed weight")
+    n, h, wd, cx = x.shape
+    if cx != _ru(ci, 32):
+        raise ValueError(f"conv3x3_fwd_pool_codes: x has {cx} channels, expected {_ru(ci, 32)}")
+    L = lib()
+    if w_packed.numel() != L.fosvos_packed_weight_elems(co, ci):
+        raise ValueError("conv3x3_fwd_pool_codes: packed weight size does not match (Co, Ci)")
+    if bias is not None:
+        _need(bias, _F32, "conv3x3_fwd_pool_codes bias")
+        if bias.numel() != co:
+            raise ValueError("conv3x3_fwd_pool_codes: bias size")
+    if out is None:
+        yp = torch.empty((n, (h + 1) // 2, (wd + 1) // 2, co), dtype=_BF16, device=x.device)
+        codes = torch.empty(conv3x3_pool_codes_shape(n, h, wd, co), dtype=torch.int32, device=x.device)
+    else:
+        yp, codes = out
+        _need(yp, _BF16, "conv3x3_fwd_pool_codes pooled output")
+        if not (codes.is_cuda and codes.is_contiguous() and codes.dtype == torch.int32):
+            raise ValueError("conv3x3_fwd_pool_codes: codes must be a contiguous int32 tensor on the GPU")
+        if yp.numel() != n * ((h + 1) // 2) * ((wd + 1) // 2) * co or codes.numel() * 4 != L.fosvos_conv3x3_pool_codes_bytes(n, h, wd, co):
+            raise ValueError("conv3x3_fwd_pool_codes: output sizes")
+    dev, st = _ctx(x)
+    t0 = _pb()
+    check(L.fosvos_conv3x3_fwd_pool_codes(x.data_ptr(), w_packed.data_ptr(), _p(bias), yp.data_ptr(), codes.data_ptr(), n, h,
+                                          wd, ci, co, CONV_RELU, dev, st), "conv3x3_fwd_pool_codes")
+    _pe(t0, "conv3x3_fwd", 2.0 * n * h * wd * 9 * ci * co, n * h * wd * 2 * cx + 2 * 9 * ci * co + yp.numel() * 2 + codes.numel() * 4)
+    return yp, codes
+
+
 def conv3x3_dgrad(dy: torch.Tensor, w_dgrad_packed: torch.Tensor, ci: int, co: int,
                   relu_src: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None,
                   out: Optional[torch.Tensor] = None, relu_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -453,6 +492,34 @@ def maxpool_bwd(x: torch.Tensor, dy: torch.Tensor, relu_mask: bool = True) -> to
                                            dev, st), "maxpool2x2_ceil_bwd")
     _pe(t0, "maxpool_bwd", 0.0, 2 * (2 * x.numel() + dy.numel()))
     return dx
+
+
+def maxpool_bwd_codes(codes: torch.Tensor, dy: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """maxpool_bwd(x, dy, relu_mask=True) of an [N, h, w, C] map from the winner codes conv3x3_fwd_pool_codes wrote for it."""
+    _need(dy, _BF16, "maxpool_bwd_codes dy")
+    n, oh, ow, c = dy.shape
+    if (oh, ow) != ((h + 1) // 2, (w + 1) // 2) or c % 8:
+        raise ValueError("maxpool_bwd_codes: dy shape mismatch")
+    if not (codes.is_cuda and codes.is_contiguous() and codes.dtype == torch.int32) or codes.numel() != n * oh * ow * (c // 8):
+        raise ValueError("maxpool_bwd_codes: codes must be a contiguous int32 [N, ceil(h/2), ceil(w/2), C/8] tensor on the GPU")
+    dx = torch.empty((n, h, w, c), dtype=_BF16, device=dy.device) if out is None else out
+    if out is not None:
+        _need(out, _BF16, "maxpool_bwd_codes out")
+        if out.numel() != n * h * w * c:
+            raise ValueError("maxpool_bwd_codes: out size")
+    dev, st = _ctx(dy)
+    t0 = _pb()
+    check(lib().fosvos_maxpool2x2_ceil_bwd_codes(codes.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, dev, st),
+          "maxpool2x2_ceil_bwd_codes")
+    _pe(t0, "maxpool_bwd", 0.0, 2 * (dx.numel() + dy.numel()) + 4 * codes.numel())
+    return dx
+
+
+def vgg_stage1_compact(n: int, h: int, w: int, flag: bool = True) -> bool:
+    """Does a pass of this shape run stage 1 in its compact form when ``PassFlags.compact_stage1`` is (``flag``) set?
+    (fosvos_vgg_stage1_compact: host arithmetic only.)"""
+    from . import VGG_COMPACT_STAGE1
+    return bool(lib().fosvos_vgg_stage1_compact(VGG_COMPACT_STAGE1 if flag else 0, n, h, w))
 
 
 # ------------------------------------------------------------------------------------------ head

@@ -124,8 +124,10 @@ def _losses_frames(outputs, gts, map_scale, ones, staged=None):
 def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, optimizer: optim.SGD, summary_writer,
            start_epoch: int, n_epochs: int, avg_grad_every_n: int, snapshot_every_n: int,
            is_testing_while_training: bool, test_every_n: int, *, options: Optional[LoopOptions] = None,
-           microbatch_group: int = 1) -> dict:
-    """options: the loop's switches (fosvos_hip.options.LoopOptions); None = from the environment as it is now.
+           microbatch_group: int = 1, compact_stage1: bool = True) -> dict:
+    """compact_stage1: the loop's training passes run with PassFlags.compact_stage1 (the same bits either way; False is the
+    A/B and test switch).
+    options: the loop's switches (fosvos_hip.options.LoopOptions); None = from the environment as it is now.
     microbatch_group: 1 = the reference's loop, one minibatch per pass.  N > 1: the one-frame minibatches of an accumulation
     cycle run as batched passes of up to N frames of one shape (``options.group_window`` minibatches are looked at together;
     ``options.microbatch_group`` is the online loop's and is not read here).  The weights are constant inside a cycle and its
@@ -230,6 +232,7 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     # weights are constant inside an accumulation cycle: let the next forward overlap the wgrad tail of this backward
     flags.defer_wgrad_join = options.defer_join
     try:
+        flags.compact_stage1 = bool(compact_stage1)  # (this loop reads nothing of a pass's arena)
         for epoch in range(start_epoch, n_epochs):
             start_time = timeit.default_timer()
             # a DistributedSampler (data-parallel loader) draws the same permutation every epoch unless it is told the
@@ -288,6 +291,7 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     finally:  # whatever happened in the loop, the caller's module does not keep the deferred join
         net.join_gradients()
         flags.defer_wgrad_join = False
+        flags.compact_stage1 = False
         if microbatch_group > 1 and reserved_frames is not None:
             net.reserve_arena_frames = reserved_frames
     if torch.cuda.is_available():

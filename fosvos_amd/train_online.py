@@ -329,9 +329,10 @@ def _get_summary_writer(seq_name: str):
 
 def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summary_writer, seq_name: str,
            start_epoch: int, n_epochs: int, avg_grad_every_n: int, snapshot_every_n: int, *,
-           options: Optional[LoopOptions] = None) -> dict:
+           options: Optional[LoopOptions] = None, compact_stage1: bool = True) -> dict:
     """options: the loop's switches (fosvos_hip.options.LoopOptions, where each is explained); None = from the environment
-    as it is now."""
+    as it is now.  compact_stage1: the loop's passes run with PassFlags.compact_stage1 (conv1_2 stores the pool's winner
+    codes instead of its output; the same bits either way - False is the A/B and test switch)."""
     if options is None:
         options = LoopOptions.from_env()
     log.info('Start of Online Training, sequence: ' + seq_name)
@@ -573,6 +574,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
         net.join_gradients()
     flags.defer_wgrad_join = options.defer_join
     try:
+        flags.compact_stage1 = bool(compact_stage1)  # (this loop reads nothing of a pass's arena)
         window = []  # pending (epoch, minibatch index, minibatch, last of its epoch) tuples, all of one accumulation cycle
         for epoch in range(start_epoch, n_epochs):
             n_mb = len(dataloader)
@@ -596,6 +598,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
             if grads_stale:  # leave the buffers as optimizer.zero_grad() would (src/train_online.py:100-104)
                 flat.zero()
         flags.forward_one_stream = False
+        flags.compact_stage1 = False
         net.compute_side_outputs = True
     time_enqueued = timeit.default_timer() - time_all_start  # how far ahead of the device the host loop ran
     if torch.cuda.is_available():

@@ -37,6 +37,9 @@
 extern "C" {
 #endif
 
+/* 33 also covers the entries added since without touching an existing symbol or struct (additive: an older caller sees no
+ * difference): fosvos_conv3x3_fwd_pool_codes, fosvos_conv3x3_pool_codes_bytes, fosvos_maxpool2x2_ceil_bwd_codes,
+ * fosvos_vgg_stage1_compact, fosvos_vgg_forward_flags, fosvos_vgg_forward_streams_flags, fosvos_vgg_backward_flags. */
 #define FOSVOS_ABI_VERSION 33
 
 #define FOSVOS_OK 0
@@ -186,6 +189,20 @@ int fosvos_conv3x3_fwd_add(const uint16_t *x, const uint16_t *w_packed, const fl
 int fosvos_conv3x3_fwd_pool(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y,
                             uint16_t *y_pool, int N, int H, int W, int Ci, int Co, unsigned flags, void *workspace,
                             size_t workspace_bytes, int device, void *stream);
+/* The pooled forward form WITHOUT the dense output, for a layer whose output only the pool's backward would read (conv1_2
+ * of a training pass: 52 MB a 480x854 frame): y_pool as fosvos_conv3x3_fwd_pool writes it, bit for bit, and the pool's WINNER
+ * CODES, codes[N, ceil(H/2), ceil(W/2), Co/8] 32-bit words (fosvos_conv3x3_pool_codes_bytes of them).  The word of a pooled
+ * pixel and channel group holds one 4-bit one-hot nibble per channel: channel 8 g + 2 i + h at bit 4 i + 16 h (i = 0..3,
+ * h = 0, 1).  Window pixels are numbered k = 2 dy + dx in scan order; bit k is set iff pixel k is the first maximum in scan
+ * order (a later pixel wins only with a strictly larger value; pixels outside the image never win) AND that maximum is > 0.
+ * A zero nibble: the ReLU output is 0 in the whole window, the gradient goes nowhere.  For finite activations that is what
+ * fosvos_maxpool2x2_ceil_bwd (relu_mask = 1) derives from the dense output; a NaN activation wins like the largest value,
+ * as it does in the pooled map.  flags must be FOSVOS_CONV_RELU.  Only the persistent kernel has this form: a shape it does
+ * not take (fosvos_conv3x3_fwd_plan(..).persistent == 0 for the same shape and flags) is FOSVOS_E_SHAPE. */
+int fosvos_conv3x3_fwd_pool_codes(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y_pool,
+                                  uint32_t *codes, int N, int H, int W, int Ci, int Co, unsigned flags, int device,
+                                  void *stream);
+size_t fosvos_conv3x3_pool_codes_bytes(int N, int H, int W, int C); /* 0 for a bad shape (C % 8 != 0) */
 /* Scratch for fwd/dgrad with `in_ch` contraction and `out_ch` output channels (split-K partial
  * slabs for layers whose pixel count alone cannot fill 256 CUs; 0 when none is needed). */
 size_t fosvos_conv3x3_workspace_bytes(int N, int H, int W, int in_ch, int out_ch);
@@ -258,6 +275,10 @@ int fosvos_maxpool2x2_ceil_fwd(const uint16_t *x, uint16_t *y, int N, int H, int
  * elsewhere; relu_mask != 0 also zeroes it where x <= 0 (ReLU backward of the producer, fused). */
 int fosvos_maxpool2x2_ceil_bwd(const uint16_t *x, const uint16_t *dy, uint16_t *dx, int N, int H, int W, int C,
                                int relu_mask, int device, void *stream);
+/* The same dx (relu_mask = 1) from the winner codes fosvos_conv3x3_fwd_pool_codes wrote for x, without x: bit for bit
+ * fosvos_maxpool2x2_ceil_bwd(x, dy, dx, .., 1) for finite x.  20 bytes read per pooled pixel and 8 channels instead of 80. */
+int fosvos_maxpool2x2_ceil_bwd_codes(const uint32_t *codes, const uint16_t *dy, uint16_t *dx, int N, int H, int W, int C,
+                                     int device, void *stream);
 
 /* ---- fused side-output head -------------------------------------------------------------------
  * For the four scales s (stride f = 2,4,8,16; deconv kernel k = 2f) with side[s] fp32 NHWC
@@ -842,6 +863,24 @@ int fosvos_vgg_forward_streams(fosvos_ctx *ctx, const fosvos_vgg_weights *w, con
 int fosvos_vgg_backward(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const fosvos_vgg_grads *g, const float *frame, int N,
                         int H, int W, void *arena, size_t arena_bytes, const float *d_fused,
                         const float *const d_side_out[4], void *stream, void *aux_stream);
+/* Pass flags of the _flags entries below (the entries above are the same calls with flags = 0). */
+#define FOSVOS_VGG_COMPACT_STAGE1 1u /* conv1_2 writes no dense output: see fosvos_vgg_stage1_compact */
+/* 1 if a pass of this shape with these flags runs stage 1 in its COMPACT form: conv1_2's forward writes the pooled map and
+ * the pool's winner codes (fosvos_conv3x3_fwd_pool_codes; the codes lie at the start of the arena's act[1] region, whose rest
+ * is then left untouched) and the backward pass routes the pooled gradient with fosvos_maxpool2x2_ceil_bwd_codes.  Only
+ * where FOSVOS_VGG_COMPACT_STAGE1 is set and the conv1_2 launch of EVERY forward chain (ceil(N/2) and floor(N/2) frames for
+ * N >= 2, else N) is one the persistent kernel takes; otherwise 0 and the whole pass is dense, exactly as with flags = 0.
+ * Forward and backward both decide by this function: give them the same flags.  The arena layout does not depend on it. */
+int fosvos_vgg_stage1_compact(unsigned flags, int N, int H, int W);
+int fosvos_vgg_forward_flags(const fosvos_vgg_weights *w, const float *frame, int N, int H, int W, void *arena,
+                             size_t arena_bytes, float *fused, float *const side_out[4], int device, void *stream,
+                             unsigned flags);
+int fosvos_vgg_forward_streams_flags(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const float *frame, int N, int H, int W,
+                                     void *arena, size_t arena_bytes, float *fused, float *const side_out[4], void *stream,
+                                     void *aux_stream, unsigned flags);
+int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weights *w, const fosvos_vgg_grads *g, const float *frame,
+                              int N, int H, int W, void *arena, size_t arena_bytes, const float *d_fused,
+                              const float *const d_side_out[4], void *stream, void *aux_stream, unsigned flags);
 /* Make `stream` wait until gradient bucket `bucket` of the LAST fosvos_vgg_backward ON THIS CONTEXT (called with
  * grads.bucket_events != 0) is complete in its buffers: 0 = conv5_1..conv5_3 (stages.4), 1 = conv4_1..conv4_3
  * (stages.3), 2 = conv3_1..conv3_3 (stages.2) - 97 % of the gradient bytes, each published as the pass finishes it - then
