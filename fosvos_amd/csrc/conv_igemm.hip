@@ -707,6 +707,22 @@ struct ConvPlan {
     size_t workspace_bytes;
 };
 
+// TileId -> tile type: f(T{}) for the tile T that `id` names, and what it returns
+template <class F>
+int with_tile(TileId id, F &&f) {
+    switch (id) {
+        case kBig: return f(TileBig{});
+        case kSquare: return f(TileSquare{});
+        case kMid: return f(TileMid{});
+        case kSmall: return f(TileSmall{});
+        case kSide: return f(TileSide{});
+        case kSideS: return f(TileSideS{});
+        case kHalf: return f(TileHalf{});
+        case kHalfS: return f(TileHalfS{});
+    }
+    return fail(FOSVOS_E_ARG, "conv3x3: bad plan");
+}
+
 // Pick the tile and the K split: prefer the largest pixel tile that still yields >= kMinBlocks workgroups
 // (256 CUs x 2 resident workgroups); when even the smallest tile cannot, split the K chunks over blockIdx.z
 // so that weights are streamed once per pixel tile and the chip is filled.
@@ -716,20 +732,21 @@ ConvPlan make_plan(int N, int H, int W, int in_ch, int out_ch) {
     ConvPlan p{};
     const int n_chunks = roundup(in_ch, 32) / 32;
     const int64_t pixels = (int64_t)N * H * W;
-    auto blocks = [&](int th, int tw, int bn) { return cdiv(W, tw) * cdiv(H, th) * N * (int64_t)(out_ch / bn); };
+    auto blocks = [&](auto t) { return cdiv(W, t.TW) * cdiv(H, t.TH) * N * (int64_t)(out_ch / t.BN); };  // workgroups in tiles t
+    auto area = [&](auto t) { return cdiv(H, t.TH) * cdiv(W, t.TW) * t.BM; };  // pixels of a map that tiles t compute
     int64_t nb;
     if (out_ch % 64 == 0) {
         // 256-pixel tiles as soon as there is one per CU (measured: 420 workgroups of 8x32 beat 840 of 8x16 by 8 % at
         // 120x214x256 alone; at 60x107x512, 256 of them beat 448 of 8x16 by 1 % of the whole step beside the wgrad
         // stream, which fills the second slot of each CU); below that the 128-pixel tile, 3 per CU
-        bool big = blocks(8, 32, 64) >= kMinBlocks / 2;
+        bool big = blocks(TileBig{}) >= kMinBlocks / 2;
         if (big) {
             // ... as 8 x 32 or as 16 x 16 pixels, whichever overhangs the map less (a tile computes all of its 256 pixels:
             // 60 x 107 is 64 x 128 = 8192 pixels of work in 8 x 32 tiles, 64 x 112 = 7168 in 16 x 16 ones)
-            const int64_t area_wide = cdiv(H, 8) * 8 * cdiv(W, 32) * 32, area_sq = cdiv(H, 16) * 16 * cdiv(W, 16) * 16;
+            const int64_t area_wide = area(TileBig{}), area_sq = area(TileSquare{});
             static const bool allow_sq = lab_env_int("FOSVOS_NO_SQUARE_TILE", 0) == 0;
-            if (allow_sq && area_sq < area_wide) { p.tile = kSquare; nb = blocks(16, 16, 64); }
-            else { p.tile = kBig; nb = blocks(8, 32, 64); }
+            if (allow_sq && area_sq < area_wide) { p.tile = kSquare; nb = blocks(TileSquare{}); }
+            else { p.tile = kBig; nb = blocks(TileBig{}); }
             // ... unless the 128-pixel tiles fit in ONE round (3 per CU = 768) and the 256-pixel tiles chosen are not even one
             // per CU (one frame's 60x107x512 layers: 224 tiles of 16 x 16, which would go on to split K).  Until round 4 the
             // condition was "fewer than 384 of the 8 x 32 tiles" (lab switch FOSVOS_MID_ONE_ROUND=1), which also took the
@@ -737,23 +754,22 @@ ConvPlan make_plan(int N, int H, int W, int in_ch, int out_ch) {
             // ones: alone the small ones win, 53 against 60 us per launch; beside the weight-gradient stream, where these
             // launches run, they lose: the step +0.5 % with the big tile (profiles/r04_lab_step_ab_tunables.txt).
             static const bool one_round = lab_env_int("FOSVOS_MID_ONE_ROUND", 0) != 0;
-            if (blocks(8, 16, 64) <= 768 && (one_round ? blocks(8, 32, 64) < kMinBlocks * 3 / 4 : nb < kMinBlocks / 2)) big = false;
+            if (blocks(TileMid{}) <= 768 && (one_round ? blocks(TileBig{}) < kMinBlocks * 3 / 4 : nb < kMinBlocks / 2)) big = false;
         }
-        if (!big) { p.tile = kMid; nb = blocks(8, 16, 64); }
+        if (!big) { p.tile = kMid; nb = blocks(TileMid{}); }
     } else if (out_ch == 32) {
-        if (pixels >= 256 * 256) { p.tile = kHalf; nb = blocks(8, 32, 32); }
-        else { p.tile = kHalfS; nb = blocks(4, 16, 32); }
+        if (pixels >= 256 * 256) { p.tile = kHalf; nb = blocks(TileHalf{}); }
+        else { p.tile = kHalfS; nb = blocks(TileHalfS{}); }
     } else {
-        if (pixels >= 256 * 256) { p.tile = kSide; nb = blocks(8, 32, 16); }
-        else { p.tile = kSideS; nb = blocks(4, 16, 16); }
+        if (pixels >= 256 * 256) { p.tile = kSide; nb = blocks(TileSide{}); }
+        else { p.tile = kSideS; nb = blocks(TileSideS{}); }
     }
     if (out_ch % 64 == 0) {
         // lab switch: 0 = 8x32, 1 = 8x16, 2 = 4x16 pixel tiles of 64 channels; 5 = 8x32 pixels x 32 channels
         static const char *force = lab_env("FOSVOS_FORCE_TILE");
         if (force && ((atoi(force) >= 0 && atoi(force) <= 2) || atoi(force) == (int)kHalf)) {
             p.tile = (TileId)atoi(force);
-            nb = p.tile == kBig ? blocks(8, 32, 64) : p.tile == kMid ? blocks(8, 16, 64)
-                 : p.tile == kHalf ? blocks(8, 32, 32) : blocks(4, 16, 64);
+            with_tile(p.tile, [&](auto t) { nb = blocks(t); return 0; });
         }
     }
     int ks = 1;
@@ -858,34 +874,42 @@ int dispatch(ConvArgs a, int in_ch, void *workspace, size_t workspace_bytes, hip
                        "conv3x3: split-K needs %zu workspace bytes, got %zu", plan.workspace_bytes, workspace_bytes);
         a.partial = reinterpret_cast<float *>(workspace);
     }
-    if (a.unpool_g) {  // (fosvos_conv3x3_dgrad_unpool has checked that the plan is one of these, unsplit)
-        switch (plan.tile) {
-            case kBig: return launch<TileBig, false, true>(a, plan, st, in_ch);
-            case kSquare: return launch<TileSquare, false, true>(a, plan, st, in_ch);
-            case kMid: return launch<TileMid, false, true>(a, plan, st, in_ch);
-            default: return fail(FOSVOS_E_ARG, "conv3x3: no fused pool backward for this tile");
-        }
-    }
-    switch (plan.tile) {
-        case kBig: return launch<TileBig, false>(a, plan, st, in_ch);
-        case kSquare: return launch<TileSquare, false>(a, plan, st, in_ch);
-        case kMid: return launch<TileMid, false>(a, plan, st, in_ch);
-        case kSmall: return launch<TileSmall, false>(a, plan, st, in_ch);
-        case kSide: return f32 ? launch<TileSide, true>(a, plan, st, in_ch) : launch<TileSide, false>(a, plan, st, in_ch);
-        case kSideS: return f32 ? launch<TileSideS, true>(a, plan, st, in_ch) : launch<TileSideS, false>(a, plan, st, in_ch);
-        case kHalf: return launch<TileHalf, false>(a, plan, st, in_ch);
-        case kHalfS: return launch<TileHalfS, false>(a, plan, st, in_ch);
-    }
-    return fail(FOSVOS_E_ARG, "conv3x3: bad plan");
+    // built: the fused pool backward for the 64-channel tiles of 128 pixels and more (fosvos_conv3x3_dgrad_unpool has checked
+    // that the plan is one of these, unsplit), fp32 output for the 16-channel tiles (the checks above), bf16 output for all
+    if (a.unpool_g)
+        return with_tile(plan.tile, [&](auto t) {
+            if constexpr (t.BN == 64 && t.BM >= 128) return launch<decltype(t), false, true>(a, plan, st, in_ch);
+            return fail(FOSVOS_E_ARG, "conv3x3: no fused pool backward for this tile");
+        });
+    return with_tile(plan.tile, [&](auto t) {
+        if constexpr (t.BN == 16)
+            if (f32) return launch<decltype(t), true>(a, plan, st, in_ch);
+        return launch<decltype(t), false>(a, plan, st, in_ch);
+    });
 }
 
-// Forward launches with bf16 output and no addend take the persistent eight-wave kernel (conv_pp.hip) where its tiles fill
-// the chip.  Lab builds: FOSVOS_PP=0 never, 1 whenever the shape fits.
-bool forward_takes_pp(int N, int H, int W, int in_ch, int out_ch, unsigned flags) {
-    if (flags & ~FOSVOS_CONV_RELU) return false;
-    static const int mode = lab_env_int("FOSVOS_PP", -1);
-    if (mode == 0) return false;
-    return conv_pp_applicable(N, H, W, roundup(in_ch, 32), out_ch);
+// The operands every form has, over `in_ch` contraction channels and `out_ch` result channels; what makes an entry point what
+// it is (bias, mask, bits, addend, pool, unpool, flags) starts null / 0 and is set there.
+ConvArgs conv_args(const uint16_t *x, const uint16_t *w_packed, void *y, int N, int H, int W, int in_ch, int out_ch) {
+    ConvArgs a{};
+    a.x = x; a.w = w_packed; a.y = y;
+    a.N = N; a.H = H; a.W = W; a.Cin = roundup(in_ch, 32); a.Cout = out_ch; a.Co_pad = roundup(out_ch, 16);
+    return a;
+}
+
+// Does this launch take the persistent eight-wave kernel (conv_pp.hip)?  Forward launches with bf16 output and no addend do,
+// and (`dgrad`) the bit-mask data gradient without an addend - the same conv on the rotated filter image, its epilogue the
+// mask - where the kernel's tiles fill the chip.  Lab builds: FOSVOS_PP=0 never, 1 whenever the shape fits;
+// FOSVOS_PP_DGRAD=0 the data gradient by the igemm (those two read per call).
+bool takes_pp(int N, int H, int W, int in_ch, int out_ch, unsigned flags, bool dgrad = false, const void *addend = nullptr) {
+    if ((flags & ~FOSVOS_CONV_RELU) || addend) return false;
+    if (dgrad) {
+        if (lab_env_int("FOSVOS_PP_DGRAD", 1) == 0 || lab_env_int("FOSVOS_PP", -1) == 0) return false;
+    } else {
+        static const int mode = lab_env_int("FOSVOS_PP", -1);
+        if (mode == 0) return false;
+    }
+    return conv_pp_applicable(N, H, W, roundup(in_ch, 32), out_ch);  // (64-channel output blocks only)
 }
 
 int check_common(const void *x, const void *w, const void *y, int N, int H, int W, int in_ch, int out_ch,
@@ -911,28 +935,19 @@ extern "C" int fosvos_conv3x3_plan(int N, int H, int W, int in_ch, int out_ch, f
     FOSVOS_REQUIRE(N > 0 && H > 0 && W > 0 && in_ch > 0 && out_ch > 0 && (out_ch % 64 == 0 || out_ch == 32 || out_ch == 16),
                    FOSVOS_E_SHAPE, "conv3x3_plan: bad shape N=%d H=%d W=%d in=%d out=%d", N, H, W, in_ch, out_ch);
     const ConvPlan p = make_plan(N, H, W, in_ch, out_ch);
-    int th = 0, tw = 0, bn = 0;
-    switch (p.tile) {
-        case kBig: th = TileBig::TH; tw = TileBig::TW; bn = TileBig::BN; break;
-        case kSquare: th = TileSquare::TH; tw = TileSquare::TW; bn = TileSquare::BN; break;
-        case kMid: th = TileMid::TH; tw = TileMid::TW; bn = TileMid::BN; break;
-        case kSmall: th = TileSmall::TH; tw = TileSmall::TW; bn = TileSmall::BN; break;
-        case kSide: th = TileSide::TH; tw = TileSide::TW; bn = TileSide::BN; break;
-        case kSideS: th = TileSideS::TH; tw = TileSideS::TW; bn = TileSideS::BN; break;
-        case kHalf: th = TileHalf::TH; tw = TileHalf::TW; bn = TileHalf::BN; break;
-        case kHalfS: th = TileHalfS::TH; tw = TileHalfS::TW; bn = TileHalfS::BN; break;
-    }
-    out->tile_h = th; out->tile_w = tw; out->tile_co = bn;
     out->k_splits = p.k_splits;
-    out->workgroups = (int)(cdiv(W, tw) * cdiv(H, th) * N * (out_ch / bn));
     out->persistent = 0;
-    return FOSVOS_OK;
+    return with_tile(p.tile, [&](auto t) {
+        out->tile_h = t.TH; out->tile_w = t.TW; out->tile_co = t.BN;
+        out->workgroups = (int)(cdiv(W, t.TW) * cdiv(H, t.TH) * N * (out_ch / t.BN));
+        return FOSVOS_OK;
+    });
 }
 
 extern "C" int fosvos_conv3x3_fwd_plan(int N, int H, int W, int in_ch, int out_ch, unsigned flags,
                                        fosvos_conv3x3_plan_info *out) {
     if (int rc = fosvos_conv3x3_plan(N, H, W, in_ch, out_ch, out)) return rc;
-    if (out_ch % 64 == 0 && forward_takes_pp(N, H, W, in_ch, out_ch, flags)) {
+    if (takes_pp(N, H, W, in_ch, out_ch, flags)) {
         out->tile_h = 8; out->tile_w = 32; out->tile_co = 64;
         out->k_splits = 1;
         out->workgroups = conv_pp_workgroups();
@@ -947,12 +962,11 @@ extern "C" int fosvos_conv3x3_fwd(const uint16_t *x, const uint16_t *w_packed, c
     if (int rc = check_common(x, w_packed, y, N, H, W, Ci, Co, "conv3x3_fwd")) return rc;
     FOSVOS_REQUIRE((flags & ~(FOSVOS_CONV_RELU | FOSVOS_CONV_OUT_F32)) == 0, FOSVOS_E_ARG, "conv3x3_fwd: unknown flags 0x%x", flags);
     FOSVOS_ENTER(device);
-    if (Co % 64 == 0 && forward_takes_pp(N, H, W, Ci, Co, flags))
+    if (takes_pp(N, H, W, Ci, Co, flags))
         return conv_pp_forward(x, w_packed, bias, (uint16_t *)y, nullptr, N, H, W, roundup(Ci, 32), Co, roundup(Co, 16),
                                (flags & FOSVOS_CONV_RELU) != 0, (hipStream_t)stream);
-    ConvArgs a{};
-    a.x = x; a.w = w_packed; a.bias = bias; a.relu_src = nullptr; a.addend = nullptr; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Ci, 32); a.Cout = Co; a.Co_pad = roundup(Co, 16); a.flags = flags;
+    ConvArgs a = conv_args(x, w_packed, y, N, H, W, Ci, Co);
+    a.bias = bias; a.flags = flags;
     return dispatch(a, Ci, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -968,9 +982,8 @@ extern "C" int fosvos_conv3x3_fwd_add(const uint16_t *x, const uint16_t *w_packe
     FOSVOS_REQUIRE(!(flags & FOSVOS_CONV_OUT_F32) || (Co == 16 && !addend), FOSVOS_E_ARG,
                    "conv3x3_fwd_add: fp32 output is the 16-channel side_prep form");
     FOSVOS_ENTER(device);
-    ConvArgs a{};
-    a.x = x; a.w = w_packed; a.bias = bias; a.relu_src = nullptr; a.addend = addend; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Ci, 32); a.Cout = Co; a.Co_pad = roundup(Co, 16);
+    ConvArgs a = conv_args(x, w_packed, y, N, H, W, Ci, Co);
+    a.bias = bias; a.addend = addend;
     a.flags = kNoSplitK | (addend ? ((flags & FOSVOS_CONV_RELU) ? kReluAfterAdd : 0u) : flags);
     return dispatch(a, Ci, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -982,10 +995,8 @@ extern "C" int fosvos_conv3x3_s2_fwd(const uint16_t *x, const uint16_t *w_packed
     FOSVOS_REQUIRE((flags & ~FOSVOS_CONV_RELU) == 0, FOSVOS_E_ARG, "conv3x3_s2_fwd: unknown flags 0x%x", flags);
     FOSVOS_REQUIRE(Co % 64 == 0 || Co == 32, FOSVOS_E_SHAPE, "conv3x3_s2_fwd: Co=%d must be 32 or a multiple of 64", Co);
     FOSVOS_ENTER(device);
-    ConvArgs a{};
-    a.x = x; a.w = w_packed; a.bias = bias; a.relu_src = nullptr; a.addend = nullptr; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Ci, 32); a.Cout = Co; a.Co_pad = roundup(Co, 16);
-    a.flags = flags | kSubsample2 | kNoSplitK;
+    ConvArgs a = conv_args(x, w_packed, y, N, H, W, Ci, Co);
+    a.bias = bias; a.flags = flags | kSubsample2 | kNoSplitK;
     return dispatch(a, Ci, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -996,7 +1007,7 @@ extern "C" int fosvos_conv3x3_fwd_pool(const uint16_t *x, const uint16_t *w_pack
     FOSVOS_REQUIRE(y_pool, FOSVOS_E_ARG, "conv3x3_fwd_pool: null pooled output");
     FOSVOS_REQUIRE((flags & ~FOSVOS_CONV_RELU) == 0, FOSVOS_E_ARG, "conv3x3_fwd_pool: unknown flags 0x%x", flags);
     FOSVOS_REQUIRE(Co % 64 == 0, FOSVOS_E_SHAPE, "conv3x3_fwd_pool: Co=%d must be a multiple of 64", Co);
-    if ((flags & FOSVOS_CONV_RELU) && forward_takes_pp(N, H, W, Ci, Co, flags)) {  // (the fused pool takes post-ReLU values)
+    if ((flags & FOSVOS_CONV_RELU) && takes_pp(N, H, W, Ci, Co, flags)) {  // (the fused pool takes post-ReLU values)
         FOSVOS_ENTER(device);
         return conv_pp_forward(x, w_packed, bias, y, y_pool, N, H, W, roundup(Ci, 32), Co, roundup(Co, 16), true,
                                (hipStream_t)stream);
@@ -1007,9 +1018,8 @@ extern "C" int fosvos_conv3x3_fwd_pool(const uint16_t *x, const uint16_t *w_pack
         return fosvos_maxpool2x2_ceil_fwd(y, y_pool, N, H, W, Co, device, stream);
     }
     FOSVOS_ENTER(device);
-    ConvArgs a{};
-    a.x = x; a.w = w_packed; a.bias = bias; a.relu_src = nullptr; a.addend = nullptr; a.y = y; a.y_pool = y_pool;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Ci, 32); a.Cout = Co; a.Co_pad = roundup(Co, 16); a.flags = flags;
+    ConvArgs a = conv_args(x, w_packed, y, N, H, W, Ci, Co);
+    a.bias = bias; a.y_pool = y_pool; a.flags = flags;
     return dispatch(a, Ci, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1018,7 +1028,7 @@ namespace fosvos {
 bool conv3x3_pool_codes_applicable(int N, int H, int W, int Ci, int Co) {
     if (N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || Co % 64 != 0) return false;
     if ((int64_t)H * W * roundup(Ci, 32) * 2 >= 0x7fffffffLL || (int64_t)H * W * Co * 4 >= 0x7fffffffLL) return false;
-    return forward_takes_pp(N, H, W, Ci, Co, FOSVOS_CONV_RELU);
+    return takes_pp(N, H, W, Ci, Co, FOSVOS_CONV_RELU);
 }
 }  // namespace fosvos
 
@@ -1050,15 +1060,11 @@ extern "C" int fosvos_conv3x3_dgrad_bits(const uint16_t *dy, const uint16_t *w_d
     if (int rc = check_common(dy, w_dgrad_packed, dx, N, H, W, Co, Ci, "conv3x3_dgrad_bits")) return rc;
     FOSVOS_REQUIRE(relu_bits && Ci % 8 == 0, FOSVOS_E_ARG, "conv3x3_dgrad_bits: null mask or Ci=%d not a multiple of 8", Ci);
     FOSVOS_ENTER(device);
-    // the persistent kernel (conv_pp.hip) where the forward pass takes it too - as a data gradient it is the same conv on the
-    // rotated filter image, its epilogue the bit mask (lab switch FOSVOS_PP_DGRAD=0: the igemm)
-    if (!addend && lab_env_int("FOSVOS_PP_DGRAD", 1) != 0 && lab_env_int("FOSVOS_PP", -1) != 0 &&
-        conv_pp_applicable(N, H, W, roundup(Co, 32), Ci))
+    if (takes_pp(N, H, W, Co, Ci, 0u, true, addend))  // (where the forward pass takes the persistent kernel too)
         return conv_pp_forward(dy, w_dgrad_packed, nullptr, dx, nullptr, N, H, W, roundup(Co, 32), Ci, roundup(Ci, 16), false,
                                (hipStream_t)stream, relu_bits);
-    ConvArgs a{};
-    a.x = dy; a.w = w_dgrad_packed; a.bias = nullptr; a.relu_src = nullptr; a.relu_bits = relu_bits; a.addend = addend; a.y = dx;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Co, 32); a.Cout = Ci; a.Co_pad = roundup(Ci, 16); a.flags = 0;
+    ConvArgs a = conv_args(dy, w_dgrad_packed, dx, N, H, W, Co, Ci);
+    a.relu_bits = relu_bits; a.addend = addend;
     return dispatch(a, Co, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1075,9 +1081,8 @@ extern "C" int fosvos_conv3x3_dgrad_unpool(const uint16_t *dy, const uint16_t *w
         if (int rc = fosvos_maxpool2x2_ceil_bwd(x, d_pooled, dx, N, H, W, Ci, 1, device, stream)) return rc;
         return fosvos_conv3x3_dgrad(dy, w_dgrad_packed, x, dx, dx, N, H, W, Ci, Co, workspace, workspace_bytes, device, stream);
     }
-    ConvArgs a{};
-    a.x = dy; a.w = w_dgrad_packed; a.relu_src = x; a.unpool_g = d_pooled; a.y = dx;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Co, 32); a.Cout = Ci; a.Co_pad = roundup(Ci, 16); a.flags = 0;
+    ConvArgs a = conv_args(dy, w_dgrad_packed, dx, N, H, W, Co, Ci);
+    a.relu_src = x; a.unpool_g = d_pooled;
     return dispatch(a, Co, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1087,8 +1092,7 @@ extern "C" int fosvos_conv3x3_dgrad(const uint16_t *dy, const uint16_t *w_dgrad_
     // contraction over the forward op's output channels (Co), result has its input channels (Ci)
     if (int rc = check_common(dy, w_dgrad_packed, dx, N, H, W, Co, Ci, "conv3x3_dgrad")) return rc;
     FOSVOS_ENTER(device);
-    ConvArgs a{};
-    a.x = dy; a.w = w_dgrad_packed; a.bias = nullptr; a.relu_src = relu_src; a.addend = addend; a.y = dx;
-    a.N = N; a.H = H; a.W = W; a.Cin = roundup(Co, 32); a.Cout = Ci; a.Co_pad = roundup(Ci, 16); a.flags = 0;
+    ConvArgs a = conv_args(dy, w_dgrad_packed, dx, N, H, W, Co, Ci);
+    a.relu_src = relu_src; a.addend = addend;
     return dispatch(a, Co, workspace, workspace_bytes, (hipStream_t)stream);
 }

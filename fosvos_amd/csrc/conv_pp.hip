@@ -593,24 +593,25 @@ int conv_pp_forward(const uint16_t *x, const uint16_t *w_packed, const float *bi
 #ifdef FOSVOS_LAB_BUILD
     a.stamps = g_pp_stamps;
 #endif
-    void (*kern)(const pp::Args) = mask_bits ? pp::k_conv3x3_pp<false, false, true>
-                                   : codes   ? pp::k_conv3x3_pp<true, true, false, true>
-                                   : y_pool  ? pp::k_conv3x3_pp<true, true>
-                                   : relu    ? pp::k_conv3x3_pp<true, false> : pp::k_conv3x3_pp<false, false>;
-    const int which = mask_bits ? 3 : codes ? 4 : y_pool ? 2 : relu ? 1 : 0;
+    // the five instantiations and the names rocprofv3 prints for them
+    static const struct { void (*kern)(const pp::Args); const char *name; } kForms[5] = {
+        {pp::k_conv3x3_pp<true, false>, "k_conv3x3_pp<true, false, false>"},                    // 0: ReLU
+        {pp::k_conv3x3_pp<false, false>, "k_conv3x3_pp<false, false, false>"},                  // 1: plain
+        {pp::k_conv3x3_pp<true, true>, "k_conv3x3_pp<true, true, false>"},                      // 2: dense + pooled map
+        {pp::k_conv3x3_pp<true, true, false, true>, "k_conv3x3_pp<true, true, false, true>"},   // 3: pooled map + winner codes
+        {pp::k_conv3x3_pp<false, false, true>, "k_conv3x3_pp<false, false, true>"}};            // 4: data gradient, bit mask
+    const int which = mask_bits ? 4 : codes ? 3 : y_pool ? 2 : relu ? 0 : 1;
+    const auto &form = kForms[which];
     static bool once[64][5];
     int dev = 0;
     FOSVOS_HIP_CHECK(hipGetDevice(&dev));
     if (dev >= 0 && dev < 64 && !once[dev][which]) {  // opt in to the whole LDS of a CU, once per device and instantiation
-        FOSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             pp::LDS_BYTES));
+        FOSVOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(form.kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, pp::LDS_BYTES));
         once[dev][which] = true;
     }
-    FOSVOS_PROF(mask_bits ? "k_conv3x3_pp<false, false, true>" : codes ? "k_conv3x3_pp<true, true, false, true>"
-                : y_pool  ? "k_conv3x3_pp<true, true, false>"
-                : relu    ? "k_conv3x3_pp<true, false, false>" : "k_conv3x3_pp<false, false, false>", st,
-                2.0 * N * H * W * 9.0 * Cin_pad * Cout);
-    hipLaunchKernelGGL(kern, dim3(conv_pp_workgroups()), dim3(pp::NT), pp::LDS_BYTES, st, a);
+    FOSVOS_PROF(form.name, st, 2.0 * N * H * W * 9.0 * Cin_pad * Cout);
+    hipLaunchKernelGGL(form.kern, dim3(conv_pp_workgroups()), dim3(pp::NT), pp::LDS_BYTES, st, a);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }

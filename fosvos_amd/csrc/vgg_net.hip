@@ -22,15 +22,18 @@ constexpr int kStageCh[5] = {64, 128, 256, 512, 512};
 
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
+// (offsets; X_bytes: the size of region X before its rounding up to 256)
 struct Arena {
     int sh[5], sw[5];        // stage resolutions
     size_t act[kNConv];      // conv outputs, bf16 NHWC
-    size_t gact[kNConv];     // gradients wrt conv outputs (ReLU-masked), bf16 NHWC
+    size_t gact[kNConv];     // gradients wrt conv outputs (ReLU-masked), bf16 NHWC: act_bytes too
+    size_t act_bytes[kNConv];
     size_t pooled[4];        // pool outputs = inputs of stages 1..4
-    size_t gpooled[4];       // gradients wrt them
+    size_t gpooled[4];       // gradients wrt them: pooled_bytes too
     size_t side[4];          // fp32 NHWC [N,h,w,16]
     size_t dside[4];         // bf16 NHWC [N,h,w,32]
-    size_t bits0;            // the ReLU mask of conv1_1's output as bits, [N,H,W,8] bytes (conv1_2's data gradient reads it)
+    size_t pooled_bytes[4], side_bytes[4], dside_bytes[4];
+    size_t bits0, bits0_bytes;  // the ReLU mask of conv1_1's output as bits, [N,H,W,8] bytes (conv1_2's data gradient reads it)
     size_t ws, ws_bytes;     // op workspace of the main stream (split-K slabs)
     size_t hws, hws_bytes;   // head backward slabs (written from both streams, so never shared with `ws`)
     // per-layer slab workspaces of the wgrad (auxiliary) stream: every layer's slabs stay live until the batched
@@ -47,18 +50,18 @@ Arena make_arena(int N, int H, int W) {
     auto take = [&](size_t bytes) { const size_t o = off; off += up256(bytes); return o; };
     for (int c = 0; c < kNConv; ++c) {
         const int s = kStageOf[c];
-        const size_t bytes = (size_t)N * a.sh[s] * a.sw[s] * kCout[c] * 2;
-        a.act[c] = take(bytes);
-        a.gact[c] = take(bytes);
+        a.act_bytes[c] = (size_t)N * a.sh[s] * a.sw[s] * kCout[c] * 2;
+        a.act[c] = take(a.act_bytes[c]);
+        a.gact[c] = take(a.act_bytes[c]);
     }
     for (int s = 1; s < 5; ++s) {
-        const size_t bytes = (size_t)N * a.sh[s] * a.sw[s] * kStageCh[s - 1] * 2;
-        a.pooled[s - 1] = take(bytes);
-        a.gpooled[s - 1] = take(bytes);
-        a.side[s - 1] = take((size_t)N * a.sh[s] * a.sw[s] * 16 * 4);
-        a.dside[s - 1] = take((size_t)N * a.sh[s] * a.sw[s] * 32 * 2);
+        const size_t px = (size_t)N * a.sh[s] * a.sw[s];
+        a.pooled[s - 1] = take(a.pooled_bytes[s - 1] = px * kStageCh[s - 1] * 2);
+        a.gpooled[s - 1] = take(a.pooled_bytes[s - 1]);
+        a.side[s - 1] = take(a.side_bytes[s - 1] = px * 16 * 4);
+        a.dside[s - 1] = take(a.dside_bytes[s - 1] = px * 32 * 2);
     }
-    a.bits0 = take((size_t)N * H * W * (kCout[0] / 8));
+    a.bits0 = take(a.bits0_bytes = (size_t)N * H * W * (kCout[0] / 8));
     a.hws_bytes = up256(fosvos_head_bwd_workspace_bytes(N, H, W));
     a.hws = take(a.hws_bytes);
     size_t ws = 256;
@@ -151,36 +154,131 @@ extern "C" int fosvos_vgg_arena_layout(int N, int H, int W, fosvos_vgg_arena_lay
     out->total = a.total;
     for (int s = 0; s < 5; ++s) { out->stage_h[s] = a.sh[s]; out->stage_w[s] = a.sw[s]; }
     for (int c = 0; c < kNConv; ++c) {
-        const int s = kStageOf[c];
         out->act[c] = a.act[c];
         out->gact[c] = a.gact[c];
-        out->act_bytes[c] = (size_t)N * a.sh[s] * a.sw[s] * kCout[c] * 2;
+        out->act_bytes[c] = a.act_bytes[c];
         out->wsa_conv[c] = a.wsa_conv[c];
         out->wsa_conv_bytes[c] = a.wsa_conv_bytes[c];
     }
-    for (int s = 1; s < 5; ++s) {
-        const size_t px = (size_t)N * a.sh[s] * a.sw[s];
-        out->pooled[s - 1] = a.pooled[s - 1];
-        out->gpooled[s - 1] = a.gpooled[s - 1];
-        out->pooled_bytes[s - 1] = px * kStageCh[s - 1] * 2;
-        out->side[s - 1] = a.side[s - 1];
-        out->side_bytes[s - 1] = px * 16 * 4;
-        out->dside[s - 1] = a.dside[s - 1];
-        out->dside_bytes[s - 1] = px * 32 * 2;
-        out->wsa_side[s - 1] = a.wsa_side[s - 1];
-        out->wsa_side_bytes[s - 1] = a.wsa_side_bytes[s - 1];
+    for (int i = 0; i < 4; ++i) {
+        out->pooled[i] = a.pooled[i];
+        out->gpooled[i] = a.gpooled[i];
+        out->pooled_bytes[i] = a.pooled_bytes[i];
+        out->side[i] = a.side[i];
+        out->side_bytes[i] = a.side_bytes[i];
+        out->dside[i] = a.dside[i];
+        out->dside_bytes[i] = a.dside_bytes[i];
+        out->wsa_side[i] = a.wsa_side[i];
+        out->wsa_side_bytes[i] = a.wsa_side_bytes[i];
     }
     out->bits0 = a.bits0;
-    out->bits0_bytes = (size_t)N * H * W * (kCout[0] / 8);
+    out->bits0_bytes = a.bits0_bytes;
     out->ws = a.ws; out->ws_bytes = a.ws_bytes;
     out->hws = a.hws; out->hws_bytes = a.hws_bytes;
     return FOSVOS_OK;
 }
 
-// aux_stream (optional): the four side_prep convs (16 output channels: memory-bound, 120 us per five 480x854 frames) run on
-// it, beside the backbone's MFMA-bound convs of the NEXT stage, instead of between them; `stream` waits for them in front of
-// the head.  The caller sees single-stream semantics on `stream`.
 namespace {
+// The four side maps of frames f0 onwards, their gradients and their resolutions: what the head kernels take.
+struct SideTable {
+    const float *side[4];
+    uint16_t *dside[4];
+    int hs[4], ws[4];
+};
+SideTable side_table(const Arena &a, char *base, int f0 = 0) {
+    SideTable t;
+    for (int i = 0; i < 4; ++i) {
+        t.hs[i] = a.sh[i + 1];
+        t.ws[i] = a.sw[i + 1];
+        const size_t first = (size_t)f0 * t.hs[i] * t.ws[i];
+        t.side[i] = reinterpret_cast<const float *>(base + a.side[i]) + first * 16;
+        t.dside[i] = reinterpret_cast<uint16_t *>(base + a.dside[i]) + first * 32;
+    }
+    return t;
+}
+
+// One forward pass over its arena: the chain and the head of a range of frames, which forward_impl arranges on its streams.
+struct Forward {
+    const Arena &a;
+    char *base;
+    const fosvos_vgg_weights *w;
+    const float *frame;
+    int H, W, device;
+    bool compact;  // stage1_compact() of the pass
+    hipEvent_t *ev;
+
+    // frame f0 onwards of the region at `off`, `per_frame` elements a frame
+    template <class T>
+    T *at(size_t off, int f0, size_t per_frame) const { return reinterpret_cast<T *>(base + off) + (size_t)f0 * per_frame; }
+
+    // conv1_1 ... conv5_3 and the four side convs of frames [f0, f0 + nf), on `st`.  The side convs of stages 2-4 run on `ss`:
+    // `st` itself, or the other stream behind an event (16 output channels: memory-bound, 120 us per five 480x854 frames -
+    // beside the backbone's MFMA-bound convs of the NEXT stage instead of between them).  The last stage's side conv has
+    // nothing left to run beside and stays on `st` (the round trip through the other stream cost 25 us in front of the head).
+    // own_ws: the split-K workspace of a layer is its own weight-gradient workspace (idle in the forward pass) instead of the
+    // shared `ws` - for a chain that runs beside another one; a side conv off its chain's stream takes its own in any case
+    // (`ws` is in use by the backbone convs running beside it).
+    int chain(int f0, int nf, hipStream_t st, hipStream_t ss, bool own_ws) const {
+        const uint16_t *x = nullptr;
+        for (int c = 0; c < kNConv; ++c) {
+            const int s = kStageOf[c], h = a.sh[s], wd = a.sw[s];
+            const size_t px = (size_t)h * wd;
+            uint16_t *y = at<uint16_t>(a.act[c], f0, px * kCout[c]);
+            void *ws = base + (own_ws ? a.wsa_conv[c] : a.ws);
+            const size_t wsn = own_ws ? a.wsa_conv_bytes[c] : a.ws_bytes;
+            if (c == 0) {
+                FOSVOS_TRY(fosvos_conv3x3_first_fwd(frame + (size_t)f0 * 3 * H * W, w->conv_w[0], w->conv_b[0], y,
+                                                    at<uint8_t>(a.bits0, f0, px * (kCout[0] / 8)), nf, H, W, kCout[0], device, st));
+            } else {
+                if (c == kFirstOfStage[s])  // stage entry: the pooled map the previous stage's last conv wrote
+                    x = at<uint16_t>(a.pooled[s - 1], f0, px * kCin[c]);
+                FOSVOS_REQUIRE(wsn >= fosvos_conv3x3_workspace_bytes(nf, h, wd, kCin[c], kCout[c]), FOSVOS_E_WORKSPACE,
+                               "vgg_forward: split-K workspace of the second chain");
+                if (c == kLastOfStage[s] && s < 4) {  // the pool that feeds the next stage rides in this conv's epilogue
+                    const size_t qpx = (size_t)a.sh[s + 1] * a.sw[s + 1];
+                    uint16_t *yp = at<uint16_t>(a.pooled[s], f0, qpx * kCout[c]);
+                    if (c == 1 && compact)  // ... with the winner codes (one word per pooled pixel and 8 channels) in place of y
+                        FOSVOS_TRY(fosvos_conv3x3_fwd_pool_codes(x, w->conv_wf[c], w->conv_b[c], yp,
+                                                                 at<uint32_t>(a.act[1], f0, qpx * (kCout[1] / 8)), nf, h, wd,
+                                                                 kCin[c], kCout[c], FOSVOS_CONV_RELU, device, st));
+                    else
+                        FOSVOS_TRY(fosvos_conv3x3_fwd_pool(x, w->conv_wf[c], w->conv_b[c], y, yp, nf, h, wd, kCin[c], kCout[c],
+                                                           FOSVOS_CONV_RELU, ws, wsn, device, st));
+                } else {
+                    FOSVOS_TRY(fosvos_conv3x3_fwd(x, w->conv_wf[c], w->conv_b[c], y, nf, h, wd, kCin[c], kCout[c],
+                                                  FOSVOS_CONV_RELU, ws, wsn, device, st));
+                }
+            }
+            x = y;
+            if (s > 0 && c == kLastOfStage[s]) {
+                hipStream_t sd = s < 4 ? ss : st;
+                if (sd != st) {  // the stage output is complete on `st`: the side conv may read it on the other stream
+                    FOSVOS_HIP_CHECK(hipEventRecord(ev[c], st));
+                    FOSVOS_HIP_CHECK(hipStreamWaitEvent(sd, ev[c], 0));
+                }
+                const bool own = own_ws || sd != st;
+                FOSVOS_TRY(fosvos_conv3x3_fwd(x, w->side_wf[s - 1], w->side_b[s - 1], at<float>(a.side[s - 1], f0, px * 16), nf, h,
+                                              wd, kStageCh[s], 16, FOSVOS_CONV_OUT_F32, base + (own ? a.wsa_side[s - 1] : a.ws),
+                                              own ? a.wsa_side_bytes[s - 1] : a.ws_bytes, device, sd));
+            }
+        }
+        return FOSVOS_OK;
+    }
+
+    // the head (it is per frame) of frames [f0, f0 + nf), on `st`
+    int head(int f0, int nf, float *fused, float *const side_out[4], hipStream_t st) const {
+        const SideTable t = side_table(a, base, f0);
+        const bool with_so = side_out && side_out[0];
+        float *so[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; with_so && i < 4; ++i)
+            if (side_out[i]) so[i] = side_out[i] + (size_t)f0 * H * W;
+        return fosvos_head_fwd(t.side, t.hs, t.ws, w->filt, w->filt1, w->dsn_w, w->dsn_b, w->fuse_w, w->fuse_b,
+                               fused + (size_t)f0 * H * W, with_so ? so : nullptr, nf, H, W, w->filt_uniform, device, st);
+    }
+};
+
+// aux_stream (optional): part of the pass runs on it, beside what runs on `stream`; `stream` waits for it, so the caller sees
+// single-stream semantics on `stream`.
 int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame, int N, int H, int W, void *arena,
                  size_t arena_bytes, float *fused, float *const side_out[4], int device, void *stream, void *aux_stream,
                  unsigned flags) {
@@ -188,18 +286,17 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
     FOSVOS_TRY(check_net(w, frame, arena, N, H, W, arena_bytes, a, "vgg_forward"));
     FOSVOS_REQUIRE(fused, FOSVOS_E_ARG, "vgg_forward: null output");
     FOSVOS_REQUIRE((flags & ~FOSVOS_VGG_COMPACT_STAGE1) == 0, FOSVOS_E_ARG, "vgg_forward: unknown flags 0x%x", flags);
-    const bool compact = stage1_compact(flags, N, H, W);
-    char *base = reinterpret_cast<char *>(arena);
-    // compact stage 1: the codes of frame f0 onwards (one word per pooled pixel and 8 channels of conv1_2's output)
-    auto codes1 = [&](int f0) {
-        return reinterpret_cast<uint32_t *>(base + a.act[1]) + (size_t)f0 * a.sh[1] * a.sw[1] * (kCout[1] / 8);
-    };
-    auto act = [&](int c) { return reinterpret_cast<uint16_t *>(base + a.act[c]); };
-    void *ws = base + a.ws;
     hipStream_t sm = (hipStream_t)stream;
     const bool par = ev != nullptr && aux_stream != nullptr && aux_stream != stream;
     hipStream_t sa = par ? (hipStream_t)aux_stream : sm;
+    const Forward f{a, reinterpret_cast<char *>(arena), w, frame, H, W, device, stage1_compact(flags, N, H, W), ev};
     if (par) FOSVOS_ENTER(device);
+    auto join = [&]() -> int {  // `stream` sees what the auxiliary stream has done
+        if (!par) return FOSVOS_OK;
+        FOSVOS_HIP_CHECK(hipEventRecord(ev[13], sa));
+        FOSVOS_HIP_CHECK(hipStreamWaitEvent(sm, ev[13], 0));
+        return FOSVOS_OK;
+    };
     // The frames of a batched pass run as TWO independent chains, the first ceil(N/2) on `stream`, the rest on the auxiliary
     // stream: the launches of one chain fill the partial last round of the other's (five 480x854 frames: conv3 is 4.1 rounds
     // of 512 workgroups, conv4 2.2) and what one chain's workgroups spend outside their chunk loops.  +1.0 % on the step.
@@ -207,134 +304,21 @@ int forward_impl(hipEvent_t *ev, const fosvos_vgg_weights *w, const float *frame
     // does not depend on how it is scheduled).  FOSVOS_FWD_SPLIT=0 (lab switch): one chain of N frames.
     if (fwd_split_on() && N >= 2) {
         const int na = (N + 1) / 2;
-        if (par) {
+        if (par) {  // fork
             FOSVOS_HIP_CHECK(hipEventRecord(ev[14], sm));
             FOSVOS_HIP_CHECK(hipStreamWaitEvent(sa, ev[14], 0));
         }
-        for (int half = 0; half < 2; ++half) {
-            const int f0 = half ? na : 0, nf = half ? N - na : na;
-            hipStream_t st = half ? sa : sm;
-            const uint16_t *xh = nullptr;
-            for (int c = 0; c < kNConv; ++c) {
-                const int s = kStageOf[c];
-                const size_t px = (size_t)a.sh[s] * a.sw[s];
-                uint16_t *yc = act(c) + (size_t)f0 * px * kCout[c];
-                // the second chain's split-K workspace: the layer's own weight-gradient workspace (idle in the forward pass)
-                void *wsc = half ? base + a.wsa_conv[c] : ws;
-                const size_t wsn = half ? a.wsa_conv_bytes[c] : a.ws_bytes;
-                if (c == 0) {
-                    FOSVOS_TRY(fosvos_conv3x3_first_fwd(frame + (size_t)f0 * 3 * H * W, w->conv_w[0], w->conv_b[0], yc,
-                                                        reinterpret_cast<uint8_t *>(base + a.bits0) + (size_t)f0 * px * (kCout[0] / 8),
-                                                        nf, H, W, kCout[0], device, st));
-                } else {
-                    if (c == kFirstOfStage[s]) {
-                        const size_t ppx = (size_t)a.sh[s] * a.sw[s];
-                        xh = reinterpret_cast<uint16_t *>(base + a.pooled[s - 1]) + (size_t)f0 * ppx * kCin[c];
-                    }
-                    FOSVOS_REQUIRE(wsn >= fosvos_conv3x3_workspace_bytes(nf, a.sh[s], a.sw[s], kCin[c], kCout[c]),
-                                   FOSVOS_E_WORKSPACE, "vgg_forward: split-K workspace of the second chain");
-                    if (c == 1 && compact) {
-                        const size_t qpx = (size_t)a.sh[1] * a.sw[1];
-                        FOSVOS_TRY(fosvos_conv3x3_fwd_pool_codes(xh, w->conv_wf[c], w->conv_b[c],
-                                                                 reinterpret_cast<uint16_t *>(base + a.pooled[0]) + (size_t)f0 * qpx * kCout[c],
-                                                                 codes1(f0), nf, H, W, kCin[c], kCout[c], FOSVOS_CONV_RELU, device, st));
-                    } else if (c == kLastOfStage[s] && s < 4) {
-                        const size_t qpx = (size_t)a.sh[s + 1] * a.sw[s + 1];
-                        FOSVOS_TRY(fosvos_conv3x3_fwd_pool(xh, w->conv_wf[c], w->conv_b[c], yc,
-                                                           reinterpret_cast<uint16_t *>(base + a.pooled[s]) + (size_t)f0 * qpx * kCout[c],
-                                                           nf, a.sh[s], a.sw[s], kCin[c], kCout[c], FOSVOS_CONV_RELU, wsc, wsn,
-                                                           device, st));
-                    } else {
-                        FOSVOS_TRY(fosvos_conv3x3_fwd(xh, w->conv_wf[c], w->conv_b[c], yc, nf, a.sh[s], a.sw[s], kCin[c],
-                                                      kCout[c], FOSVOS_CONV_RELU, wsc, wsn, device, st));
-                    }
-                }
-                xh = yc;
-                if (s > 0 && c == kLastOfStage[s]) {
-                    float *so = reinterpret_cast<float *>(base + a.side[s - 1]) + (size_t)f0 * px * 16;
-                    FOSVOS_TRY(fosvos_conv3x3_fwd(xh, w->side_wf[s - 1], w->side_b[s - 1], so, nf, a.sh[s], a.sw[s], kStageCh[s],
-                                                  16, FOSVOS_CONV_OUT_F32, half ? base + a.wsa_side[s - 1] : ws,
-                                                  half ? a.wsa_side_bytes[s - 1] : a.ws_bytes, device, st));
-                }
-            }
-        }
-        // each chain runs the head for its own frames (the head is per frame), so the first chain's head runs beside the
-        // second chain's last convs instead of behind them
-        static const bool head_per_chain = lab_env_int("FOSVOS_HEAD_PER_CHAIN", 1) != 0;
-        if (head_per_chain) {
-            for (int half = 0; half < 2; ++half) {
-                const int f0 = half ? na : 0, nf = half ? N - na : na;
-                const float *sideh[4];
-                float *soh[4] = {nullptr, nullptr, nullptr, nullptr};
-                int hsh[4], wsh[4];
-                for (int i = 0; i < 4; ++i) {
-                    hsh[i] = a.sh[i + 1];
-                    wsh[i] = a.sw[i + 1];
-                    sideh[i] = reinterpret_cast<const float *>(base + a.side[i]) + (size_t)f0 * hsh[i] * wsh[i] * 16;
-                    if (side_out && side_out[i]) soh[i] = side_out[i] + (size_t)f0 * H * W;
-                }
-                FOSVOS_TRY(fosvos_head_fwd(sideh, hsh, wsh, w->filt, w->filt1, w->dsn_w, w->dsn_b, w->fuse_w, w->fuse_b,
-                                           fused + (size_t)f0 * H * W, (side_out && side_out[0]) ? soh : nullptr, nf, H, W,
-                                           w->filt_uniform, device, half ? sa : sm));
-            }
-        }
-        if (par) {
-            FOSVOS_HIP_CHECK(hipEventRecord(ev[13], sa));
-            FOSVOS_HIP_CHECK(hipStreamWaitEvent(sm, ev[13], 0));
-        }
-        if (head_per_chain) return FOSVOS_OK;
-    } else {
-    const uint16_t *x = nullptr;
-    for (int c = 0; c < kNConv; ++c) {
-        const int s = kStageOf[c];
-        if (c == 0) {
-            FOSVOS_TRY(fosvos_conv3x3_first_fwd(frame, w->conv_w[0], w->conv_b[0], act(0),
-                                                reinterpret_cast<uint8_t *>(base + a.bits0), N, H, W, kCout[0], device, stream));
-        } else {
-            if (c == kFirstOfStage[s])  // stage entry: the pooled map the previous stage's last conv wrote
-                x = reinterpret_cast<uint16_t *>(base + a.pooled[s - 1]);
-            if (c == 1 && compact) {
-                FOSVOS_TRY(fosvos_conv3x3_fwd_pool_codes(x, w->conv_wf[c], w->conv_b[c], reinterpret_cast<uint16_t *>(base + a.pooled[0]),
-                                                         codes1(0), N, H, W, kCin[c], kCout[c], FOSVOS_CONV_RELU, device, stream));
-            } else if (c == kLastOfStage[s] && s < 4) {  // the pool that feeds the next stage rides in this conv's epilogue
-                FOSVOS_TRY(fosvos_conv3x3_fwd_pool(x, w->conv_wf[c], w->conv_b[c], act(c),
-                                                   reinterpret_cast<uint16_t *>(base + a.pooled[s]), N, a.sh[s], a.sw[s],
-                                                   kCin[c], kCout[c], FOSVOS_CONV_RELU, ws, a.ws_bytes, device, stream));
-            } else {
-                FOSVOS_TRY(fosvos_conv3x3_fwd(x, w->conv_wf[c], w->conv_b[c], act(c), N, a.sh[s], a.sw[s], kCin[c], kCout[c],
-                                              FOSVOS_CONV_RELU, ws, a.ws_bytes, device, stream));
-            }
-        }
-        x = act(c);
-        if (s > 0 && c == kLastOfStage[s]) {
-            // the last stage's side conv has nothing left to run beside: it stays on `stream` (the round trip through the
-            // other stream cost 25 us in front of the head)
-            const bool on_aux = par && s < 4;
-            if (on_aux) {  // the stage output is complete on `stream`: the side conv may read it on the other one
-                FOSVOS_HIP_CHECK(hipEventRecord(ev[c], sm));
-                FOSVOS_HIP_CHECK(hipStreamWaitEvent(sa, ev[c], 0));
-            }
-            // (on the auxiliary stream the layer's own weight-gradient workspace doubles as its split-K workspace: `ws`
-            // is in use by the backbone convs running beside it)
-            FOSVOS_TRY(fosvos_conv3x3_fwd(x, w->side_wf[s - 1], w->side_b[s - 1], base + a.side[s - 1], N, a.sh[s], a.sw[s],
-                                          kStageCh[s], 16, FOSVOS_CONV_OUT_F32, on_aux ? base + a.wsa_side[s - 1] : ws,
-                                          on_aux ? a.wsa_side_bytes[s - 1] : a.ws_bytes, device, on_aux ? sa : sm));
-        }
+        FOSVOS_TRY(f.chain(0, na, sm, sm, false));
+        FOSVOS_TRY(f.chain(na, N - na, sa, sa, true));
+        // each chain runs the head for its own frames, so the first chain's head runs beside the second chain's last convs
+        // instead of behind them
+        FOSVOS_TRY(f.head(0, na, fused, side_out, sm));
+        FOSVOS_TRY(f.head(na, N - na, fused, side_out, sa));
+        return join();
     }
-    if (par) {  // join: the head reads the four side maps
-        FOSVOS_HIP_CHECK(hipEventRecord(ev[13], sa));
-        FOSVOS_HIP_CHECK(hipStreamWaitEvent(sm, ev[13], 0));
-    }
-    }
-    const float *side[4];
-    int hs[4], wsz[4];
-    for (int i = 0; i < 4; ++i) {
-        side[i] = reinterpret_cast<const float *>(base + a.side[i]);
-        hs[i] = a.sh[i + 1];
-        wsz[i] = a.sw[i + 1];
-    }
-    return fosvos_head_fwd(side, hs, wsz, w->filt, w->filt1, w->dsn_w, w->dsn_b, w->fuse_w, w->fuse_b, fused, side_out, N, H,
-                           W, w->filt_uniform, device, stream);
+    FOSVOS_TRY(f.chain(0, N, sm, sa, false));
+    FOSVOS_TRY(join());  // the head reads the four side maps
+    return f.head(0, N, fused, side_out, sm);
 }
 }  // namespace
 
@@ -427,16 +411,9 @@ extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weigh
     };
 
     // ---- head: d_side[i], fuse / score_dsn gradients
-    const float *side[4];
-    uint16_t *dside[4];
-    int hs[4], wsz[4];
-    for (int i = 0; i < 4; ++i) {
-        side[i] = reinterpret_cast<const float *>(base + a.side[i]);
-        dside[i] = reinterpret_cast<uint16_t *>(base + a.dside[i]);
-        hs[i] = a.sh[i + 1];
-        wsz[i] = a.sw[i + 1];
-    }
-    const HeadBwdArgs ha{side, hs, wsz, w->filt, with_so ? w->filt1 : nullptr, with_so ? w->dsn_w : nullptr, w->fuse_w,
+    const SideTable t = side_table(a, base);
+    uint16_t *const *dside = t.dside;
+    const HeadBwdArgs ha{t.side, t.hs, t.ws, w->filt, with_so ? w->filt1 : nullptr, with_so ? w->dsn_w : nullptr, w->fuse_w,
                          d_fused, with_so ? d_side_out : nullptr, dside, g->fuse_w, g->fuse_b,
                          with_so ? g->dsn_w : nullptr, with_so ? g->dsn_b : nullptr, N, H, W, acc, base + a.hws,
                          a.hws_bytes, device, w->filt_uniform & 15};
@@ -455,6 +432,27 @@ extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weigh
     // -2.3 % on the step, profiles/r04_lab_step_ab_head_loss.txt)
     FOSVOS_TRY(head_bwd_finish(ha, sa));
 
+    // ---- weight gradients: a layer of stage s queues its kernel on the wgrad stream and its slab reduction in a table
+    auto queue_wgrad = [&](const uint16_t *x, const uint16_t *dy, float *dw, float *db, int s, int ci, int co, size_t ws_off,
+                           size_t ws_bytes) {
+        return wgrad_impl(x, dy, dw, db, N, a.sh[s], a.sw[s], ci, co, acc, base + ws_off, ws_bytes, device, sa,
+                          (offload && s == 1) ? &reduce_m : &reduce, tail && s <= tail_stages);
+    };
+    auto side_wgrad = [&](int s) {  // side_prep[s-1]: from (stage output, d_side)
+        return queue_wgrad(act(kLastOfStage[s]), dside[s - 1], g->side_w[s - 1], g->side_b[s - 1], s, kStageCh[s], 16,
+                           a.wsa_side[s - 1], a.wsa_side_bytes[s - 1]);
+    };
+    auto conv_wgrad = [&](int c) {  // conv c: from (its input - the frame, the pool output or the conv before it -, gact(c))
+        const int s = kStageOf[c];
+        if (c == 0) {  // offload: gact(0) is the main stream's own last output: no event, and it runs beside conv1_2's
+            const auto [st0, red0] = offload ? std::pair(sm, &reduce_m) : std::pair(sa, &reduce);
+            return first_wgrad_impl(frame, gact(0), g->conv_w[0], g->conv_b[0], N, H, W, kCout[0], acc, base + a.wsa_conv[0],
+                                    a.wsa_conv_bytes[0], device, st0, red0);
+        }
+        const uint16_t *xin = c == kFirstOfStage[s] ? reinterpret_cast<const uint16_t *>(base + a.pooled[s - 1]) : act(c - 1);
+        return queue_wgrad(xin, gact(c), g->conv_w[c], g->conv_b[c], s, kCin[c], kCout[c], a.wsa_conv[c], a.wsa_conv_bytes[c]);
+    };
+
     // ---- stages 4..0
     static const bool unpool_fused = lab_env_int("FOSVOS_UNPOOL", 1) != 0;  // lab switch: 0 = pool backward as its own pass
     for (int s = 4; s >= 0; --s) {
@@ -462,9 +460,7 @@ extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weigh
         if (s > 0) {
             // side_prep[s-1]: wgrad from (stage output, d_side) on the wgrad stream; its dgrad into the stage-output
             // gradient: ReLU-masked and added to what came back through the next stage's pool (already in gact[last])
-            FOSVOS_TRY(wgrad_impl(act(last), dside[s - 1], g->side_w[s - 1], g->side_b[s - 1], N, hh, ww, kStageCh[s], 16,
-                                  acc, base + a.wsa_side[s - 1], a.wsa_side_bytes[s - 1], device, sa,
-                                  (offload && s == 1) ? &reduce_m : &reduce, tail && s <= tail_stages));
+            FOSVOS_TRY(side_wgrad(s));
             const uint16_t *addend = (s < 4) ? gact(last) : nullptr;
             if (par && s < 4) FOSVOS_HIP_CHECK(hipStreamWaitEvent(sm, ev[16 + s - 1], 0));  // d_side[s-1] from the wgrad stream
             if (s < 4 && unpool_fused)  // ... the pool backward in the same pass (no pool pass ran for this stage: see below)
@@ -477,17 +473,11 @@ extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weigh
         }
         FOSVOS_TRY(publish(last));  // gradient wrt the stage output is complete
         for (int c = last; c >= first; --c) {
-            if (c == 0) {
-                if (offload)  // gact(0) is the main stream's own last output: no event, and it runs beside conv1_2's
-                    FOSVOS_TRY(first_wgrad_impl(frame, gact(0), g->conv_w[0], g->conv_b[0], N, H, W, kCout[0], acc,
-                                                base + a.wsa_conv[0], a.wsa_conv_bytes[0], device, sm, &reduce_m));
-                else
-                    FOSVOS_TRY(first_wgrad_impl(frame, gact(0), g->conv_w[0], g->conv_b[0], N, H, W, kCout[0], acc,
-                                                base + a.wsa_conv[0], a.wsa_conv_bytes[0], device, sa, &reduce));
+            if (c == 0) {  // conv1_1 has no data gradient
+                FOSVOS_TRY(conv_wgrad(0));
                 break;
             }
             const bool from_pool = (c == first) && s > 0;  // its input is the pool output; conv 1 reads conv 0
-            const uint16_t *xin = from_pool ? reinterpret_cast<const uint16_t *>(base + a.pooled[s - 1]) : act(c - 1);
             // dgrad: into the previous conv's output gradient (masked by its ReLU), or into the pool-output gradient
             // (unmasked: the pool backward applies the producer's mask)
             uint16_t *dx = from_pool ? reinterpret_cast<uint16_t *>(base + a.gpooled[s - 1]) : gact(c - 1);
@@ -495,10 +485,7 @@ extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weigh
             // In a 3-conv stage the middle conv's gradient gets no event of its own (an event costs ~3 us of main-stream
             // time): its dgrad is issued first and the event behind it covers both gact(c) and gact(c-1).
             const bool middle = (last - first == 2) && c == last - 1;
-            if (!middle)
-                FOSVOS_TRY(wgrad_impl(xin, gact(c), g->conv_w[c], g->conv_b[c], N, hh, ww, kCin[c], kCout[c], acc,
-                                      base + a.wsa_conv[c], a.wsa_conv_bytes[c], device, sa,
-                                      (offload && s == 1) ? &reduce_m : &reduce, tail && s <= tail_stages));
+            if (!middle) FOSVOS_TRY(conv_wgrad(c));
             static const bool bits_on = lab_env_int("FOSVOS_RELU_BITS", 1) != 0;  // lab switch: 0 = read conv1_1's output itself
             if (c == 1 && bits_on)  // conv1_2: its input's ReLU mask as the bits conv1_1's forward wrote (8 B instead of 128 B a pixel)
                 FOSVOS_TRY(fosvos_conv3x3_dgrad_bits(gact(c), w->conv_wd[c], reinterpret_cast<const uint8_t *>(base + a.bits0), nullptr,
@@ -508,10 +495,7 @@ extern "C" int fosvos_vgg_backward_flags(fosvos_ctx *ctx, const fosvos_vgg_weigh
                                                 a.ws_bytes, device, sm));
             const bool skip_event = (last - first == 2) && c == last;  // gact(last-1): covered by the middle conv's event
             if (!from_pool && !skip_event) FOSVOS_TRY(publish(c - 1));
-            if (middle)
-                FOSVOS_TRY(wgrad_impl(xin, gact(c), g->conv_w[c], g->conv_b[c], N, hh, ww, kCin[c], kCout[c], acc,
-                                      base + a.wsa_conv[c], a.wsa_conv_bytes[c], device, sa,
-                                      (offload && s == 1) ? &reduce_m : &reduce, tail && s <= tail_stages));
+            if (middle) FOSVOS_TRY(conv_wgrad(c));
         }
         // pool backward into the previous stage's output gradient, its ReLU mask fused - for stage 1 only (it has no
         // side_prep): the outputs of stages 2-4 get theirs inside side_prep's data gradient, next iteration

@@ -52,12 +52,8 @@ PARAM_NAMES = param_names()
 PARAM_INDEX = {n: i for i, n in enumerate(PARAM_NAMES)}
 
 
-class _PassFlagsSlots:
-    __slots__ = ("_compact_stage1",)
-
-
 @dataclass(slots=True)
-class PassFlags(_PassFlagsSlots):
+class PassFlags:
     """What a loop tells the next passes of one model (``PackedWeights.flags``; OSVOS_VGG exposes every field as an attribute
     of the same name).  All off by default, so plain ``loss.backward(); opt.step()`` is safe.  A misspelt name raises."""
 
@@ -80,21 +76,13 @@ class PassFlags(_PassFlagsSlots):
     # Hint for the next backward pass: no forward pass follows it before the optimizer step, so its trailing weight-gradient
     # kernels may take the whole chip (the training loops set it around a cycle's last pass).
     last_pass_of_cycle: bool = False
-
-    # compact_stage1 (below; kept in the base class's slot, so the declared field list above stays what it was).
     # True: the next passes may run stage 1 in its COMPACT form - conv1_2's forward writes the pooled map and the pool's winner
     # codes (3 MB a 480x854 frame) instead of its dense output (52 MB), which nothing but the pool's backward reads, and the
     # backward routes the pooled gradient from the codes.  Results are bit-identical; the arena's act[1] region then holds the
     # codes, not conv1_2's output.  Only where the persistent conv kernel takes conv1_2 of every forward chain
     # (``ops.vgg_stage1_compact``), otherwise the pass is dense as before.  It must not change between a forward pass and its
     # backward (a backward pass runs with what its own forward pass saw).  The training loops set it around their passes.
-    @property
-    def compact_stage1(self) -> bool:
-        return getattr(self, "_compact_stage1", False)
-
-    @compact_stage1.setter
-    def compact_stage1(self, value: bool) -> None:
-        self._compact_stage1 = bool(value)
+    compact_stage1: bool = False
 
 
 class PackedWeights:

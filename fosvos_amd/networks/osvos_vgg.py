@@ -239,4 +239,3 @@ def _pass_flag(name):
 
 for _field in dataclasses.fields(engine.PassFlags):
     setattr(OSVOS_VGG, _field.name, _pass_flag(_field.name))
-OSVOS_VGG.compact_stage1 = _pass_flag('compact_stage1')  # (a property of PassFlags, not one of its dataclass fields)

@@ -279,7 +279,7 @@ def test_pass_flags_are_declared():
     from networks.osvos_vgg import OSVOS_VGG
     flags = PassFlags()
     assert [f.name for f in dataclasses.fields(flags)] == ["defer_wgrad_join", "forward_one_stream", "publish_grad_buckets",
-                                                          "overwrite_grads", "last_pass_of_cycle"]
+                                                          "overwrite_grads", "last_pass_of_cycle", "compact_stage1"]
     assert not any(getattr(flags, f.name) for f in dataclasses.fields(flags))
     with pytest.raises(AttributeError):
         flags.no_such_flag = True

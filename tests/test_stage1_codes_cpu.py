@@ -165,7 +165,7 @@ def test_flag_is_declared_and_off_by_default():
     from networks.osvos_vgg import OSVOS_VGG
     flags = PassFlags()
     assert flags.compact_stage1 is False
-    flags.compact_stage1 = 1
+    flags.compact_stage1 = True
     assert flags.compact_stage1 is True
     assert PackedWeights().flags.compact_stage1 is False
     net = OSVOS_VGG(pretrained=0)
