@@ -31,6 +31,18 @@
 //   k_overlay_scaled     k_overlay with the logit of an output pixel gathered from the [Hn,Wn] map: bilinear at half-pixel
 //                        centres with integer weights, in fp64, as 4 Hf Wf times the logit (its sign is the boolean mask).
 //
+// Following the object (opt-in; util/frame_roi.py states all three): the net sees a WINDOW (y0, x0, Hw, Ww) of each frame, and the
+// windows come from device memory, int32 [N][4], so the host never reads one.  Every kernel sanitises what it loads
+// (sane_window): a window that is not valid is the whole frame, so no bound or address depends on an unchecked value.
+// fosvos_frame_prep_window, one launch:
+//   k_frame_prep_window  k_frame_prep_scaled's body (prep_scaled) on the window of the workgroup's frame: same grid, same stage.
+// fosvos_overlay_window, one launch:
+//   k_overlay_window     the paint skeleton with the source MapUpWindow: MapUp's value inside the window, -inf outside it.
+// fosvos_window_next, two launches:
+//   k_window_reset       the frames' boxes and counts in the workspace to their start values.
+//   k_window_next        the bounding box of logits >= 0 by __ballot and one atomic min / max per workgroup and bound; the
+//                        workgroup that finishes last turns the box into the next window.
+//
 // Several objects a stream (opt-in; util/object_overlay.py states both): the K logit maps of K per-object nets, pointers by value.
 // fosvos_overlay_objects, one launch:
 //   k_overlay_objects         a thread takes its 16 logits from each of the K maps in turn and keeps (best value, label) per
@@ -49,7 +61,9 @@
 // a label) anchor on the output row and store aligned uint4.  A PAINT turns the value and the frame's bytes into the output's:
 // OneChannel (level<MODE> in one channel), PaletteBlend (towards the label's colour, all three) or OneByte (a mask or a label,
 // no frame read).  k_overlay = MapInPlace + OneChannel | OneByte, k_overlay_scaled = MapUp + the same, k_overlay_objects =
-// MapsInPlace + PaletteBlend, k_overlay_objects_scaled = MapsUp + PaletteBlend | OneByte.
+// MapsInPlace + PaletteBlend, k_overlay_objects_scaled = MapsUp + PaletteBlend | OneByte.  k_overlay_window is a fifth wrapper,
+// MapUpWindow + OneChannel | OneByte: a source beside MapUp, the paints as they are.
+#include <limits.h>
 #include <math.h>
 
 #include <type_traits>
@@ -176,12 +190,18 @@ __device__ __forceinline__ int overlap(int s, int j, int n_src, int n_dst) {
 // store.  The workgroup walks the source rows under its 4 output rows, `g.rows` at a time, and the source columns under its
 // cells, pitch / 3 at a time - the window of an output pixel has no bound (Hn = 1 averages a column), so neither walk may
 // be assumed to be one step - and every thread adds the staged part of its windows: S is a sum, any order gives it exactly.
+//
+// The SOURCE of the walk is a rectangle of the frame: `src` = (y0, x0, Hs, Ws) in the unmirrored frame, the whole frame
+// (0, 0, Hf, Wf) for k_frame_prep_scaled, a sanitised window for k_frame_prep_window.  The weights, the windows of the output
+// pixels and the area are the rectangle's; only the staging adds its origin, and the frame's own Wf is the row pitch.  The
+// stage was sized for the whole frame, and both walks cut their steps to it, so any rectangle inside the frame fits.
+struct Rect {
+    int y0, x0, H, W;
+};
 template <bool MIRROR>
-__global__ __launch_bounds__(kScaleThreads) void k_frame_prep_scaled(const uint8_t *__restrict__ frames,
-                                                                     float *__restrict__ image, ScaleGeom g,
-                                                                     int64_t frame_bytes, MeanBGR mean) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
-    const int Hf = g.Hf, Wf = g.Wf, Hn = g.Hn, Wn = g.Wn;
+__device__ __forceinline__ void prep_scaled(const uint8_t *__restrict__ frames, float *__restrict__ image, const ScaleGeom &g,
+                                            const Rect src, int64_t frame_bytes, const MeanBGR &mean, uint8_t *stage) {
+    const int Hf = src.H, Wf = src.W, Hn = g.Hn, Wn = g.Wn;  // from here on the source's sides; the frame's are g.Hf, g.Wf
     const int tile = (int)(blockIdx.x % g.tiles), strip = (int)((blockIdx.x / g.tiles) % g.strips);
     const int64_t n = blockIdx.x / ((unsigned)g.tiles * g.strips);
     const int q = threadIdx.x % kScaleCells, c = (threadIdx.x / kScaleCells) % 3, il = threadIdx.x / (3 * kScaleCells);
@@ -215,7 +235,7 @@ __global__ __launch_bounds__(kScaleThreads) void k_frame_prep_scaled(const uint8
             __syncthreads();  // the last stage has been read
             for (int t = threadIdx.x; t < (ye - yb) * pieces; t += kScaleThreads) {
                 const int r = t / pieces, k = t - r * pieces;
-                const int64_t at = (((n * Hf + yb + r) * Wf) + xa) * 3 + 16 * k;
+                const int64_t at = (((n * g.Hf + src.y0 + yb + r) * g.Wf) + src.x0 + xa) * 3 + 16 * k;
                 uint8_t *d = stage + r * g.pitch + 16 * k;
                 if (at + 16 <= frame_bytes) {  // may run into the next row: still the caller's bytes, never used
                     const bytes16 v = *reinterpret_cast<const bytes16 *>(frames + at);
@@ -251,6 +271,45 @@ __global__ __launch_bounds__(kScaleThreads) void k_frame_prep_scaled(const uint8
         for (int p = 0; p < 4; ++p)
             if (col0 + p >= 0 && col0 + p < Wn) rowp[col0 + p] = v[p];
     }
+}
+template <bool MIRROR>
+__global__ __launch_bounds__(kScaleThreads) void k_frame_prep_scaled(const uint8_t *__restrict__ frames,
+                                                                     float *__restrict__ image, ScaleGeom g,
+                                                                     int64_t frame_bytes, MeanBGR mean) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+    prep_scaled<MIRROR>(frames, image, g, Rect{0, 0, g.Hf, g.Wf}, frame_bytes, mean, stage);
+}
+
+// ------------------------------------------------------------------------------------------ windows (util/frame_roi.py)
+// A window (y0, x0, Hw, Ww) comes from device memory, so nothing about it is known: it is valid when Hn <= Hw <= Hf, Wn <=
+// Ww <= Wf, 0 <= y0 <= Hf - Hw and 0 <= x0 <= Wf - Ww, and any other - negative, overflowing - is the whole frame.  The sides
+// are compared first, so the two differences are taken of numbers in [0, 8192].  Whatever passes lies inside the frame: every
+// loop bound and address behind this function is one the whole-frame launch could have had.
+__device__ __forceinline__ Rect sane_window(int y0, int x0, int Hw, int Ww, int Hf, int Wf, int Hn, int Wn) {
+    const bool sides = Hw >= Hn && Hw <= Hf && Ww >= Wn && Ww <= Wf;
+    const bool ok = sides && y0 >= 0 && x0 >= 0 && y0 <= Hf - (sides ? Hw : Hf) && x0 <= Wf - (sides ? Ww : Wf);
+    return ok ? Rect{y0, x0, Hw, Ww} : Rect{0, 0, Hf, Wf};
+}
+// frame n's window, the same for every lane of the wave that asks: four ordinary loads, then one copy in scalar registers
+__device__ __forceinline__ Rect uniform_window(const int32_t *__restrict__ windows, int64_t n, int Hf, int Wf, int Hn, int Wn) {
+    const int32_t *__restrict__ w = windows + 4 * n;
+    const int y0 = __builtin_amdgcn_readfirstlane(w[0]), x0 = __builtin_amdgcn_readfirstlane(w[1]);
+    const int Hw = __builtin_amdgcn_readfirstlane(w[2]), Ww = __builtin_amdgcn_readfirstlane(w[3]);
+    return sane_window(y0, x0, Hw, Ww, Hf, Wf, Hn, Wn);
+}
+
+// k_frame_prep_scaled on the window of the workgroup's frame.  The window is given in the picture the net sees: with MIRROR
+// its columns [x0, x0 + Ww) are the unmirrored frame's [Wf - x0 - Ww, Wf - x0), walked backwards as the whole frame is.
+template <bool MIRROR>
+__global__ __launch_bounds__(kScaleThreads) void k_frame_prep_window(const uint8_t *__restrict__ frames,
+                                                                     const int32_t *__restrict__ windows,
+                                                                     float *__restrict__ image, ScaleGeom g,
+                                                                     int64_t frame_bytes, MeanBGR mean) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+    const int64_t n = blockIdx.x / ((unsigned)g.tiles * g.strips);
+    Rect w = uniform_window(windows, n, g.Hf, g.Wf, g.Hn, g.Wn);
+    if (MIRROR) w.x0 = g.Wf - w.x0 - w.W;
+    prep_scaled<MIRROR>(frames, image, g, w, frame_bytes, mean, stage);
 }
 
 // ------------------------------------------------------------------------------------------ the overlays: paints
@@ -429,6 +488,11 @@ __device__ __forceinline__ double logit_up(const float *__restrict__ a0, const f
 // integer weights, in fp64.  The segments are the rows; their groups start where the OUTPUT row crosses a 16-byte boundary
 // (the logits are gathered, four floats a pixel out of a map that stays in L2, so they have no aligned side to offer), which
 // makes every group store an aligned uint4.  The row's taps are taken once, the column taps walk along with the pixels.
+__device__ __forceinline__ Span span_of_row(int64_t gid, int64_t seg, int64_t slots, int Wf, const uint8_t *dst, int bytes) {
+    // pixels up to the boundary: k0 (or 3 k0, 3 * 11 = 1 mod 16) + the address = 0 mod 16
+    const unsigned lead = (16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u;
+    return span_at(gid, seg, slots, Wf, (int)(bytes == 3 ? (11u * lead) & 15u : lead));
+}
 struct RowsUp {
     using Store = uint4;
     int Hf, Wf, Hn, Wn;
@@ -440,9 +504,7 @@ struct RowsUp {
         const int64_t n = seg / Hf;
         ty = tap_of(walk_from((int)(seg - n * Hf), Hn, Hf), Hn, Hf);
         top = (n * Hn + ty.i0) * Wn, bot = (n * Hn + ty.i1) * Wn;
-        // pixels up to the boundary: k0 (or 3 k0, 3 * 11 = 1 mod 16) + the address = 0 mod 16
-        const unsigned lead = (16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u;
-        const Span s = span_at(gid, seg, slots, Wf, (int)(bytes == 3 ? (11u * lead) & 15u : lead));
+        const Span s = span_of_row(gid, seg, slots, Wf, dst, bytes);
         wx = walk_from((int)s.qa, Wn, Wf);
         return s;
     }
@@ -475,6 +537,53 @@ struct MapsUp : RowsUp {
         return label;
     }
     __device__ __forceinline__ uint32_t at(int64_t) { return take(0); }
+};
+// One map painted into a window of the frame (util/frame_roi.py): the segments, the anchor and the store are RowsUp's, the
+// frame's.  Inside the frame's sanitised window a pixel's value is MapUp's with (Hw, Ww) in place of (Hf, Wf) and the pixel
+// counted from the window's corner; outside it the value is -inf, which every paint reads as "not object": the boolean test
+// fails, and the fp64 sigmoid of -inf is 1 / (1 + inf) = 0.0 exactly, so the frame's byte (or a 0 mask byte) comes out.
+// The column walk stands at the window's first column until the pixels reach it and is never read behind its last one.  A
+// thread reads its frame's window itself: the threads of a wave may lie in two frames.
+template <bool SOFT>
+struct MapUpWindow {
+    using Store = uint4;
+    int Hf, Wf, Hn, Wn;
+    const float *__restrict__ logits;
+    const int32_t *__restrict__ windows;
+    Rect w;
+    Tap ty;
+    Walk wx;
+    int64_t top, bot;
+    int x;  // the output column of the next pixel taken
+    bool row_in;
+    __device__ __forceinline__ int64_t length() const { return Wf; }
+    __device__ __forceinline__ Span open(int64_t gid, int64_t seg, int64_t slots, const uint8_t *dst, int bytes) {
+        const int64_t n = seg / Hf;
+        const int y = (int)(seg - n * Hf);
+        const int32_t *__restrict__ wp = windows + 4 * n;
+        w = sane_window(wp[0], wp[1], wp[2], wp[3], Hf, Wf, Hn, Wn);
+        row_in = y >= w.y0 && y < w.y0 + w.H;
+        ty = tap_of(walk_from(row_in ? y - w.y0 : 0, Hn, w.H), Hn, w.H);
+        top = (n * Hn + ty.i0) * Wn, bot = (n * Hn + ty.i1) * Wn;
+        const Span s = span_of_row(gid, seg, slots, Wf, dst, bytes);
+        x = (int)s.qa;
+        wx = walk_from(max(x - w.x0, 0), Wn, w.W);
+        return s;
+    }
+    __device__ __forceinline__ void load_group(int64_t) {}
+    __device__ __forceinline__ double take(int) {
+        const bool in = row_in && x >= w.x0 && x < w.x0 + w.W;
+        ++x;
+        double v = -INFINITY;
+        if (in) {
+            const Tap tx = tap_of(wx, Wn, w.W);
+            walk_on(wx, Wn, w.W);
+            v = logit_up(logits + top, logits + bot, tx, ty);
+            if (SOFT) v = v / (double)(4 * w.H * w.W);
+        }
+        return v;
+    }
+    __device__ __forceinline__ double at(int64_t) { return take(0); }
 };
 
 // ------------------------------------------------------------------------------------------ the overlays: the skeleton
@@ -563,6 +672,112 @@ __global__ __launch_bounds__(kStreamThreads) void k_overlay_scaled(const uint8_t
     else
         paint_pixels<MIRROR>(from, OneByte<MODE>{}, frames, out, slots, total);
 }
+template <int MODE, bool MIRROR>
+__global__ __launch_bounds__(kStreamThreads) void k_overlay_window(const uint8_t *__restrict__ frames,
+                                                                   const float *__restrict__ logits,
+                                                                   const int32_t *__restrict__ windows, uint8_t *__restrict__ out,
+                                                                   int Hf, int Wf, int Hn, int Wn, int64_t slots, int64_t total,
+                                                                   int channel, double a255) {
+    const MapUpWindow<(MODE & 1) != 0> from = {Hf, Wf, Hn, Wn, logits, windows};
+    if constexpr (MODE < 2)
+        paint_pixels<MIRROR>(from, OneChannel<MODE>{channel, a255}, frames, out, slots, total);
+    else
+        paint_pixels<MIRROR>(from, OneByte<MODE>{}, frames, out, slots, total);
+}
+
+// ------------------------------------------------------------------------------------------ window_next
+// The window of the next frame from this frame's logits (util/frame_roi.next_window), two launches:
+//   k_window_reset  one thread a frame: the frame's box (min row, max row, min column, max column) to (INT_MAX, -1, INT_MAX,
+//                   -1) and its count of finished workgroups to 0.
+//   k_window_next   a workgroup owns kBoxRows rows of one frame's map, a wave one row at a time, a lane one column of a segment
+//                   of 64: __ballot(logit >= 0) of a segment gives its first and last object column, and a non-zero ballot
+//                   makes the row an object row - all in scalar registers.  The four waves meet in LDS, and thread 0 puts the
+//                   workgroup's four bounds into the frame's box with one agent-scope atomic min / max each (none where the
+//                   workgroup saw no object).  Min and max commute: no order of workgroups changes the box.  Thread 0 then
+//                   counts its workgroup as finished (acquire-release); the one that counts last - nobody waits for it - has
+//                   every bound before it, turns the box into the next window and stores it.  Only that thread reads
+//                   `in`, after every logit was read, so `out` may be `in`.
+constexpr int kBoxRows = 8;
+constexpr int kBoxWords = 5;  // int32 a frame in the workspace: the box and the count
+#define WIN_AGENT __HIP_MEMORY_SCOPE_AGENT
+
+__global__ void k_window_reset(int32_t *__restrict__ box, int N) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    int32_t *b = box + (int64_t)kBoxWords * n;
+    b[0] = INT_MAX, b[1] = -1, b[2] = INT_MAX, b[3] = -1, b[4] = 0;
+}
+
+struct NextGeom {
+    int Hf, Wf, Hn, Wn, levels, permille, min_pad, strips;
+};
+// steps 3 to 7 of util/frame_roi.next_window.  Every product stays below 2^27: sides <= 8192, levels <= 64, permille <= 4000
+__device__ __forceinline__ Rect window_from_box(int i_min, int i_max, int j_min, int j_max, const Rect w, const NextGeom &g) {
+    if (i_max < 0) return Rect{0, 0, g.Hf, g.Wf};
+    const int by0 = w.y0 + i_min * w.H / g.Hn, by1 = w.y0 + ((i_max + 1) * w.H + g.Hn - 1) / g.Hn;
+    const int bx0 = w.x0 + j_min * w.W / g.Wn, bx1 = w.x0 + ((j_max + 1) * w.W + g.Wn - 1) / g.Wn;
+    const int pad = g.min_pad + (g.permille * max(by1 - by0, bx1 - bx0) + 999) / 1000;
+    const int need_h = min(g.Hf, by1 - by0 + 2 * pad), need_w = min(g.Wf, bx1 - bx0 + 2 * pad);
+    int Hk = g.Hf, Wk = g.Wf;  // level `levels`
+    for (int k = 0; k < g.levels; ++k) {
+        const int h = g.Hn + (g.Hf - g.Hn) * k / g.levels, ww = g.Wn + (g.Wf - g.Wn) * k / g.levels;
+        if (h >= need_h && ww >= need_w) {
+            Hk = h, Wk = ww;
+            break;
+        }
+    }
+    // floor((a + b - size) / 2) of a sum that may be negative: the arithmetic shift
+    const int y0 = min(max((by0 + by1 - Hk) >> 1, 0), g.Hf - Hk), x0 = min(max((bx0 + bx1 - Wk) >> 1, 0), g.Wf - Wk);
+    return Rect{y0, x0, Hk, Wk};
+}
+
+__global__ __launch_bounds__(kStreamThreads) void k_window_next(const float *__restrict__ logits,
+                                                                const int32_t *win_in, int32_t *win_out,
+                                                                int32_t *__restrict__ box, NextGeom g) {
+    __shared__ int part[kStreamThreads / 64][4];
+    const int strip = (int)(blockIdx.x % g.strips);
+    const int64_t n = blockIdx.x / g.strips;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float *__restrict__ map = logits + n * g.Hn * g.Wn;
+    int i_min = INT_MAX, i_max = -1, j_min = INT_MAX, j_max = -1;
+    const int i_end = min((strip + 1) * kBoxRows, g.Hn);
+    for (int i = strip * kBoxRows + wave; i < i_end; i += kStreamThreads / 64) {
+        const float *__restrict__ row = map + (int64_t)i * g.Wn;
+        for (int j0 = 0; j0 < g.Wn; j0 += 64) {
+            const int j = j0 + lane;
+            const unsigned long long m = __ballot(j < g.Wn && row[min(j, g.Wn - 1)] >= 0.f);  // a NaN is not >= 0, -0.0 is
+            if (m) {
+                i_min = min(i_min, i), i_max = max(i_max, i);
+                j_min = min(j_min, j0 + (int)__builtin_ctzll(m)), j_max = max(j_max, j0 + 63 - (int)__builtin_clzll(m));
+            }
+        }
+    }
+    if (lane == 0) part[wave][0] = i_min, part[wave][1] = i_max, part[wave][2] = j_min, part[wave][3] = j_max;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 1; k < kStreamThreads / 64; ++k) {
+        i_min = min(i_min, part[k][0]), i_max = max(i_max, part[k][1]);
+        j_min = min(j_min, part[k][2]), j_max = max(j_max, part[k][3]);
+    }
+    int32_t *b = box + (int64_t)kBoxWords * n;
+    if (i_max >= 0) {
+        __hip_atomic_fetch_min(b + 0, i_min, __ATOMIC_RELAXED, WIN_AGENT);
+        __hip_atomic_fetch_max(b + 1, i_max, __ATOMIC_RELAXED, WIN_AGENT);
+        __hip_atomic_fetch_min(b + 2, j_min, __ATOMIC_RELAXED, WIN_AGENT);
+        __hip_atomic_fetch_max(b + 3, j_max, __ATOMIC_RELAXED, WIN_AGENT);
+    }
+    // release what this workgroup put into the box, acquire what every workgroup counted before it did
+    if (__hip_atomic_fetch_add(b + 4, 1, __ATOMIC_ACQ_REL, WIN_AGENT) != g.strips - 1) return;
+    const int32_t *wp = win_in + 4 * n;  // (may be win_out: read here, stored below)
+    const Rect w = sane_window(wp[0], wp[1], wp[2], wp[3], g.Hf, g.Wf, g.Hn, g.Wn);
+    const Rect next = window_from_box(__hip_atomic_load(b + 0, __ATOMIC_RELAXED, WIN_AGENT),
+                                      __hip_atomic_load(b + 1, __ATOMIC_RELAXED, WIN_AGENT),
+                                      __hip_atomic_load(b + 2, __ATOMIC_RELAXED, WIN_AGENT),
+                                      __hip_atomic_load(b + 3, __ATOMIC_RELAXED, WIN_AGENT), w, g);
+    int32_t *o = win_out + 4 * n;
+    o[0] = next.y0, o[1] = next.x0, o[2] = next.H, o[3] = next.W;
+}
+
 template <bool MIRROR>
 __global__ __launch_bounds__(kStreamThreads) void k_overlay_objects(const uint8_t *__restrict__ frames, const ObjectLogits maps,
                                                                     int K, const uint8_t *__restrict__ palette,
@@ -672,6 +887,44 @@ int check_blend(const char *who, bool blend, double alpha) {
     FOSVOS_REQUIRE(!blend || (alpha >= 0.0 && alpha <= 1.0), FOSVOS_E_ARG, "%s: alpha %g is not a number in [0, 1]", who, alpha);
     return FOSVOS_OK;
 }
+// the windows of a call: int32 [N][4] in device memory, read by the kernels alone
+int check_windows(const char *who, const int32_t *windows) {
+    FOSVOS_REQUIRE(windows != nullptr, FOSVOS_E_ARG, "%s: null pointer", who);
+    FOSVOS_REQUIRE(((uintptr_t)windows & 3) == 0, FOSVOS_E_ARG, "%s: the windows must be 4-byte aligned", who);
+    return FOSVOS_OK;
+}
+// fosvos_frame_prep_scaled (windows == nullptr) and fosvos_frame_prep_window: one geometry, one launch.  The stage is sized
+// for the whole frame, the largest source there is, so nothing here depends on what the windows hold.
+int prep_scaled_launch(const char *who, const uint8_t *frames, const int32_t *windows, int N, int Hf, int Wf, int Hn, int Wn,
+                       int mirror, const float mean[3], float *image, int device, void *stream) {
+    FOSVOS_REQUIRE(frames && mean && image, FOSVOS_E_ARG, "%s: null pointer", who);
+    if (int rc = check_sizes(who, N, Hf, Wf, Hn, Wn)) return rc;
+    FOSVOS_REQUIRE(((uintptr_t)image & 3) == 0, FOSVOS_E_ARG, "%s: the image must be 4-byte aligned", who);
+    FOSVOS_ENTER(device);
+    ScaleGeom g = {Hf, Wf, Hn, Wn, 0, 0, 0, 0};
+    // the source pixels under a workgroup's columns (64, and up to 3 more in front), cut to the chunk; the rows under its rows
+    const int64_t under = cdiv((int64_t)(4 * kScaleCells + 3) * Wf, Wn) + 1;
+    g.pitch = roundup(3 * (int)std::min<int64_t>(under, kScaleChunkPx), 16);
+    g.rows = (int)std::min<int64_t>(cdiv((int64_t)kScaleRows * Hf, Hn) + 1, kScaleStageBytes / g.pitch);
+    g.tiles = (int)cdiv(cdiv(Wn + 3, 4), kScaleCells);
+    g.strips = (int)cdiv(Hn, kScaleRows);
+    const int64_t blocks = (int64_t)N * g.tiles * g.strips;
+    FOSVOS_REQUIRE(blocks < ((int64_t)1 << 31), FOSVOS_E_SHAPE, "%s: %lld workgroups", who, (long long)blocks);
+    const MeanBGR m = {{mean[0], mean[1], mean[2]}};
+    const int64_t frame_bytes = (int64_t)N * Hf * Wf * 3;
+    const size_t lds = (size_t)g.pitch * g.rows;
+    FOSVOS_PROF(windows ? "k_frame_prep_window" : "k_frame_prep_scaled", stream, 0.0);
+    with_mirror(mirror, [&](auto mi) {
+        if (windows)
+            hipLaunchKernelGGL(k_frame_prep_window<decltype(mi)::value>, dim3((unsigned)blocks), dim3(kScaleThreads), lds,
+                               (hipStream_t)stream, frames, windows, image, g, frame_bytes, m);
+        else
+            hipLaunchKernelGGL(k_frame_prep_scaled<decltype(mi)::value>, dim3((unsigned)blocks), dim3(kScaleThreads), lds,
+                               (hipStream_t)stream, frames, image, g, frame_bytes, m);
+    });
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
 }  // namespace
 
 extern "C" int fosvos_frame_prep(const uint8_t *frames, int N, int H, int W, int mirror, const float mean[3], float *image,
@@ -710,27 +963,63 @@ extern "C" int fosvos_overlay(const uint8_t *frames, const float *logits, int N,
 
 extern "C" int fosvos_frame_prep_scaled(const uint8_t *frames, int N, int Hf, int Wf, int Hn, int Wn, int mirror,
                                         const float mean[3], float *image, int device, void *stream) {
-    FOSVOS_REQUIRE(frames && mean && image, FOSVOS_E_ARG, "frame_prep_scaled: null pointer");
-    if (int rc = check_sizes("frame_prep_scaled", N, Hf, Wf, Hn, Wn)) return rc;
-    FOSVOS_REQUIRE(((uintptr_t)image & 3) == 0, FOSVOS_E_ARG, "frame_prep_scaled: the image must be 4-byte aligned");
+    return prep_scaled_launch("frame_prep_scaled", frames, nullptr, N, Hf, Wf, Hn, Wn, mirror, mean, image, device, stream);
+}
+
+extern "C" int fosvos_frame_prep_window(const uint8_t *frames, const int32_t *windows, int N, int Hf, int Wf, int Hn, int Wn,
+                                        int mirror, const float mean[3], float *image, int device, void *stream) {
+    if (int rc = check_windows("frame_prep_window", windows)) return rc;
+    return prep_scaled_launch("frame_prep_window", frames, windows, N, Hf, Wf, Hn, Wn, mirror, mean, image, device, stream);
+}
+
+extern "C" int fosvos_overlay_window(const uint8_t *frames, const float *logits, const int32_t *windows, int N, int Hf, int Wf,
+                                     int Hn, int Wn, int mirror, int mode, int channel, double alpha, uint8_t *out, int device,
+                                     void *stream) {
+    if (int rc = check_map("overlay_window", mode, frames, logits, out)) return rc;
+    if (int rc = check_windows("overlay_window", windows)) return rc;
+    if (int rc = check_sizes("overlay_window", N, Hf, Wf, Hn, Wn)) return rc;
+    if (int rc = check_level("overlay_window", channel, alpha, logits)) return rc;
     FOSVOS_ENTER(device);
-    ScaleGeom g = {Hf, Wf, Hn, Wn, 0, 0, 0, 0};
-    // the source pixels under a workgroup's columns (64, and up to 3 more in front), cut to the chunk; the rows under its rows
-    const int64_t under = cdiv((int64_t)(4 * kScaleCells + 3) * Wf, Wn) + 1;
-    g.pitch = roundup(3 * (int)std::min<int64_t>(under, kScaleChunkPx), 16);
-    g.rows = (int)std::min<int64_t>(cdiv((int64_t)kScaleRows * Hf, Hn) + 1, kScaleStageBytes / g.pitch);
-    g.tiles = (int)cdiv(cdiv(Wn + 3, 4), kScaleCells);
-    g.strips = (int)cdiv(Hn, kScaleRows);
-    const int64_t blocks = (int64_t)N * g.tiles * g.strips;
-    FOSVOS_REQUIRE(blocks < ((int64_t)1 << 31), FOSVOS_E_SHAPE, "frame_prep_scaled: %lld workgroups", (long long)blocks);
-    const MeanBGR m = {{mean[0], mean[1], mean[2]}};
-    const int64_t frame_bytes = (int64_t)N * Hf * Wf * 3;
-    const size_t lds = (size_t)g.pitch * g.rows;
-    FOSVOS_PROF("k_frame_prep_scaled", stream, 0.0);
-    with_mirror(mirror, [&](auto mi) {
-        hipLaunchKernelGGL(k_frame_prep_scaled<decltype(mi)::value>, dim3((unsigned)blocks), dim3(kScaleThreads), lds,
-                           (hipStream_t)stream, frames, image, g, frame_bytes, m);
+    const Partition p = partition_of(N, Hf, Wf, 1);  // rows, in every mode: the frame's grid
+    FOSVOS_PROF("k_overlay_window", stream, 0.0);
+    with_mode(mode, mirror, [&](auto mo, auto mi) {
+        hipLaunchKernelGGL((k_overlay_window<decltype(mo)::value, decltype(mi)::value>), p.grid, dim3(kStreamThreads), 0,
+                           (hipStream_t)stream, frames, logits, windows, out, Hf, Wf, Hn, Wn, p.slots, p.total, channel,
+                           alpha * 255.0);
     });
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" size_t fosvos_window_next_workspace_bytes(int N) {
+    return N > 0 ? (size_t)N * kBoxWords * sizeof(int32_t) : 0;
+}
+
+extern "C" int fosvos_window_next(const float *logits, const int32_t *windows, int N, int Hf, int Wf, int Hn, int Wn, int levels,
+                                  int margin_permille, int min_pad, int32_t *out, void *workspace, size_t workspace_bytes,
+                                  int device, void *stream) {
+    FOSVOS_REQUIRE(logits && out && workspace, FOSVOS_E_ARG, "window_next: null pointer");
+    if (int rc = check_windows("window_next", windows)) return rc;
+    if (int rc = check_sizes("window_next", N, Hf, Wf, Hn, Wn)) return rc;
+    FOSVOS_REQUIRE(levels >= 1 && levels <= 64, FOSVOS_E_ARG, "window_next: levels %d outside [1, 64]", levels);
+    FOSVOS_REQUIRE(margin_permille >= 0 && margin_permille <= 4000, FOSVOS_E_ARG, "window_next: margin of %d permille outside [0, 4000]",
+                   margin_permille);
+    FOSVOS_REQUIRE(min_pad >= 0 && min_pad <= 4095, FOSVOS_E_ARG, "window_next: min_pad %d outside [0, 4095]", min_pad);
+    FOSVOS_REQUIRE((((uintptr_t)logits | (uintptr_t)out | (uintptr_t)workspace) & 3) == 0, FOSVOS_E_ARG,
+                   "window_next: the logits, the windows and the workspace must be 4-byte aligned");
+    FOSVOS_REQUIRE(workspace_bytes >= fosvos_window_next_workspace_bytes(N), FOSVOS_E_ARG, "window_next: workspace of %zu bytes, need %zu",
+                   workspace_bytes, fosvos_window_next_workspace_bytes(N));
+    const NextGeom g = {Hf, Wf, Hn, Wn, levels, margin_permille, min_pad, (int)cdiv(Hn, kBoxRows)};
+    const int64_t blocks = (int64_t)N * g.strips;
+    FOSVOS_REQUIRE(blocks < ((int64_t)1 << 31), FOSVOS_E_SHAPE, "window_next: %lld workgroups", (long long)blocks);
+    FOSVOS_ENTER(device);
+    int32_t *box = static_cast<int32_t *>(workspace);
+    FOSVOS_PROF("k_window_reset", stream, 0.0);
+    hipLaunchKernelGGL(k_window_reset, dim3((unsigned)cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, box, N);
+    FOSVOS_LAUNCH_CHECK();
+    FOSVOS_PROF("k_window_next", stream, 0.0);
+    hipLaunchKernelGGL(k_window_next, dim3((unsigned)blocks), dim3(kStreamThreads), 0, (hipStream_t)stream, logits, windows, out, box,
+                       g);
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;
 }

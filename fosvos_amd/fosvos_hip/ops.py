@@ -1896,6 +1896,116 @@ def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False,
     return out
 
 
+# following the object: the net on a window of the frame (util/frame_roi.py states all three)
+ROI_MAX_LEVELS = 64
+ROI_MAX_PAD = 4095
+ROI_MAX_MARGIN = 4.0
+
+
+def _roi_net_size(net_size, h: int, w: int, what: str) -> Tuple[int, int]:
+    """``net_size`` of the window ops: mandatory, ``_net_size``'s rules, and the frames' own size is a size like any other
+    (a ladder of one level)."""
+    if net_size is None:
+        raise ValueError(f"{what}: net_size=(Hn, Wn) is needed: a window is scaled to the net's size")
+    return _net_size(net_size, h, w, what) or (h, w)
+
+
+def _windows(windows: torch.Tensor, n: int, like: torch.Tensor, what: str) -> torch.Tensor:
+    _need_eval(windows, torch.int32, f"{what} windows")
+    if tuple(windows.shape) != (n, 4):
+        raise ValueError(f"{what}: windows must be int32 {(n, 4)} = (y0, x0, Hw, Ww) a frame, got {tuple(windows.shape)}")
+    if windows.device != like.device:
+        raise RuntimeError(f"{what}: every tensor must be on {like.device}, got one on {windows.device}")
+    return windows
+
+
+def roi_margin_permille(margin, what: str = "window_next") -> int:
+    """``margin`` (a finite number in [0, 4], a share of the box's longer side) as the integer the kernel pads with."""
+    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not 0.0 <= margin <= ROI_MAX_MARGIN:
+        raise ValueError(f"{what}: margin must be a finite number in [0, {ROI_MAX_MARGIN:g}], got {margin!r}")
+    return int(round(1000 * margin))
+
+
+def frame_prep_window(frames_u8: torch.Tensor, windows: torch.Tensor, net_size: Tuple[int, int], mirror: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_frame_prep_window: raw frames uint8 [N,H,W,3] and one window int32 (y0, x0, Hw, Ww) a frame, in DEVICE memory
+    [N,4] -> fp32 [N,3,Hn,Wn], the window of the (mirrored) frame area-averaged to the net's size less the mean
+    (util/frame_roi.prepare_frame_window, bit for bit).  A window that is not valid is read as the whole frame.  One launch on
+    the current stream, no synchronisation: the host never sees the windows."""
+    n, h, w = _frame_shape(frames_u8, "frame_prep_window")
+    hn, wn = _roi_net_size(net_size, h, w, "frame_prep_window")
+    _windows(windows, n, frames_u8, "frame_prep_window")
+    out = _out_like(out, (n, 3, hn, wn), _F32, frames_u8, "frame_prep_window")
+    dev, st = _ctx(frames_u8)
+    e0 = _pb()
+    check(lib().fosvos_frame_prep_window(frames_u8.data_ptr(), windows.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0,
+                                         _mean_bgr(), out.data_ptr(), dev, st), "frame_prep_window")
+    _pe(e0, "frame_prep_window", 0.0, 3.0 * n * h * w + 12.0 * n * hn * wn)  # (at the most: the whole-frame window)
+    return out
+
+
+def overlay_window(frames_u8: torch.Tensor, logits: torch.Tensor, windows: torch.Tensor, mirror: bool = False,
+                   boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, overlay: bool = True,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_overlay_window: ``overlay(net_size=)`` with the logits fp32 [N,1,Hn,Wn] painted into the frames' windows (int32
+    [N,4] in device memory): interpolated up to the window's size inside it, nothing is object outside it
+    (util/frame_roi.py states the bytes).  The net's size is the logits'.  One launch, no synchronisation."""
+    n, h, w = _frame_shape(frames_u8, "overlay_window")
+    _need_eval(logits, _F32, "overlay_window logits")
+    if logits.dim() != 4 or logits.shape[0] != n or logits.shape[1] != 1 or logits.numel() == 0:
+        raise ValueError(f"overlay_window: logits must be a non-empty {(n, 1, 'Hn', 'Wn')}, got {tuple(logits.shape)}")
+    hn, wn = _roi_net_size((int(logits.shape[2]), int(logits.shape[3])), h, w, "overlay_window")
+    if logits.device != frames_u8.device:
+        raise RuntimeError(f"overlay_window: every tensor must be on {frames_u8.device}, got one on {logits.device}")
+    _windows(windows, n, frames_u8, "overlay_window")
+    if color not in OVERLAY_CHANNEL:
+        raise ValueError(f"overlay_window: color must be one of {tuple(OVERLAY_CHANNEL)}, got {color!r}")
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and alpha != float("inf")):
+        raise ValueError(f"overlay_window: alpha must be a finite number >= 0, got {alpha!r}")
+    out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay_window")
+    mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
+    dev, st = _ctx(frames_u8)
+    e0 = _pb()
+    check(lib().fosvos_overlay_window(frames_u8.data_ptr(), logits.data_ptr(), windows.data_ptr(), n, h, w, hn, wn,
+                                      1 if mirror else 0, mode, OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st),
+          "overlay_window")
+    _pe(e0, "overlay_window", 0.0, (6.0 if overlay else 1.0) * n * h * w + 4.0 * n * hn * wn)
+    return out
+
+
+def window_next(logits: torch.Tensor, windows: torch.Tensor, frame_size: Tuple[int, int], levels: int = 8,
+                margin: float = 0.25, min_pad: int = 16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_window_next: the logits fp32 [N,1,Hn,Wn] of N frames and the windows int32 [N,4] they were made through -> the
+    windows of the next frames, int32 [N,4] (``out`` may be ``windows``): the box of ``logits >= 0``, padded by ``min_pad +
+    margin * its longer side``, in the smallest of the ``levels + 1`` sizes between the net's and the frame's that holds it
+    (util/frame_roi.next_window, exactly); no object: the whole frame.  Two launches, no synchronisation."""
+    _need_eval(logits, _F32, "window_next logits")
+    n, hn, wn = _logit_shape(logits, "window_next")
+    try:
+        hf, wf = frame_size
+    except (TypeError, ValueError):
+        raise ValueError(f"window_next: frame_size must be a pair (Hf, Wf), got {frame_size!r}") from None
+    for v in (hf, wf):
+        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+            raise ValueError(f"window_next: frame_size must be a pair of positive ints, got {frame_size!r}")
+    _roi_net_size((hn, wn), hf, wf, "window_next")
+    _windows(windows, n, logits, "window_next")
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= ROI_MAX_LEVELS:
+        raise ValueError(f"window_next: levels must be an integer in 1..{ROI_MAX_LEVELS}, got {levels!r}")
+    if isinstance(min_pad, bool) or not isinstance(min_pad, int) or not 0 <= min_pad <= ROI_MAX_PAD:
+        raise ValueError(f"window_next: min_pad must be an integer in 0..{ROI_MAX_PAD}, got {min_pad!r}")
+    permille = roi_margin_permille(margin)
+    out = _out_like(out, (n, 4), torch.int32, logits, "window_next")
+    ws, wsn = _WS.get(int(lib().fosvos_window_next_workspace_bytes(n)), logits.device)
+    dev, st = _ctx(logits)
+    e0 = _pb()
+    check(lib().fosvos_window_next(logits.data_ptr(), windows.data_ptr(), n, hf, wf, hn, wn, levels, permille, min_pad,
+                                   out.data_ptr(), ws, wsn, dev, st), "window_next")
+    _pe(e0, "window_next", 0.0, 4.0 * n * hn * wn)
+    return out
+
+
 def overlay_objects(frames_u8: torch.Tensor, logits: Sequence[torch.Tensor], mirror: bool = False, overlay: bool = True,
                     palette: Optional[torch.Tensor] = None, alpha: float = 0.5, out: Optional[torch.Tensor] = None,
                     net_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:

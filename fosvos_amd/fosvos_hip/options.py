@@ -162,6 +162,36 @@ class CleanOptions:
                 'fill': float(self.fill)}
 
 
+@dataclass(frozen=True)
+class RoiOptions:
+    """Following the object in a stream (``FrameSegmenter(roi=)``; util/frame_roi.py states the rules; DESIGN.md section
+    12.2): the net looks at a window of the frame around the last mask.  Opt-in by being passed; this class reads no
+    environment variable.  The defaults are unmeasured."""
+
+    # the window sizes between the net's size (level 0) and the frame's (level ``levels``): 1..64
+    levels: int = 8
+    # the box of the mask is padded on every side by this share of its longer side: a finite number in [0, 4]
+    margin: float = 0.25
+    # ... and by this many frame pixels: 0..4095.  What the object may move from one frame to the next
+    min_pad: int = 16
+
+    def __post_init__(self) -> None:
+        if isinstance(self.levels, bool) or not isinstance(self.levels, int) or not 1 <= self.levels <= 64:
+            raise ValueError(f"RoiOptions: levels must be an integer in 1..64, got {self.levels!r}")
+        if isinstance(self.margin, bool) or not isinstance(self.margin, (int, float)) or not 0.0 <= self.margin <= 4.0:
+            raise ValueError(f"RoiOptions: margin must be a finite number in [0, 4], got {self.margin!r}")
+        if isinstance(self.min_pad, bool) or not isinstance(self.min_pad, int) or not 0 <= self.min_pad <= 4095:
+            raise ValueError(f"RoiOptions: min_pad must be an integer in 0..4095, got {self.min_pad!r}")
+
+    @property
+    def margin_permille(self) -> int:
+        """The margin as the integer the kernel and the numpy definition pad with."""
+        return int(round(1000 * self.margin))
+
+    def as_dict(self) -> dict:
+        return {'levels': self.levels, 'margin': float(self.margin), 'min_pad': self.min_pad}
+
+
 def _real(v) -> bool:
     return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
 

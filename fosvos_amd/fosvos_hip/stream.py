@@ -48,6 +48,14 @@ states the bytes).  Its label-map form can end in a palette PNG (``encode='png'`
 slot exactly like the JPEG: ``[length | file]`` on the device, ``[length | first budget bytes]`` on the host.  Only the
 compute step differs from ``FrameSegmenter``, whose launches, order and bytes are what they were.
 
+``roi=RoiOptions(...)`` (opt-in, with ``net_size``; ``fosvos_hip.options``) follows the object: the net sees a WINDOW of the
+frame around the last mask, ``ops.frame_prep_window`` area-averages that window to the net's size, ``ops.overlay_window`` paints
+the logits back into it, and ``ops.window_next`` makes the next frame's window of this frame's (cleaned) logits (csrc/stream.hip;
+util/frame_roi.py states all three).  The window never leaves the device: the segmenter's ``_window`` (int32 [1,4]) is written
+by frame t's ``window_next`` and copied into frame t + 1's slot on the one net's stream, in submit order - the hand-over of
+the clean seed, no event and no host read of its own.  ``seed_window(mask)`` sets it from an annotation.  ``None`` is the object
+described above.
+
 Not thread-safe: one host thread drives a segmenter.
 """
 from __future__ import annotations
@@ -60,7 +68,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .options import CleanOptions
+from .options import CleanOptions, RoiOptions
 
 
 _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that the file starts 8-byte aligned
@@ -68,12 +76,13 @@ _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that t
 
 class _Slot:
     def __init__(self, h: int, w: int, out_shape, device: torch.device, capacity: int = 0, budget: int = 0,
-                 net_size=None) -> None:
+                 net_size=None, roi: bool = False) -> None:
         self.host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
         self.host_in_np = self.host_in.numpy()
         self.frame = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
         self.image = torch.empty((1, 3) + tuple(net_size or (h, w)), dtype=torch.float32, device=device)
         self.out = torch.empty(out_shape, dtype=torch.uint8, device=device)
+        self.window = torch.empty((1, 4), dtype=torch.int32, device=device) if roi else None  # the one this frame is seen through
         if capacity:
             self.store = torch.empty((_HEAD + capacity,), dtype=torch.uint8, device=device)
             self.length = self.store[:4].view(torch.int32)
@@ -98,6 +107,10 @@ class FrameSegmenter:
                      with ``encode='jpeg'`` the same picture as ``bytes``, a complete .jpg file of quality ``quality``
     segment(frames)  generator: outputs in input order, ``depth`` frames in flight
     apply(frame)     one frame, synchronously
+    seed_window(mask)  with ``roi``: the window of the next submitted frame from an annotation (uint8 or bool, the frame's size,
+                     in the frame's own coordinates; non-zero = object); never called, the first frame is seen whole
+    last_window()    with ``roi``: the window the next frame will use, as a tuple (y0, x0, Hw, Ww); synchronises - for logs and
+                     tests
     seed(mask)       with ``clean.temporal_radius``: the mask (uint8 or bool, the frame's size or the net's; non-zero = object)
                      the next submitted frame is gated by, e.g. the annotation the net was fine-tuned on; never called, the
                      first frame is not gated
@@ -105,17 +118,30 @@ class FrameSegmenter:
     """
 
     clean: Optional[CleanOptions] = None  # (ObjectSegmenter has none)
+    roi: Optional[RoiOptions] = None      # (likewise)
     _seed = None
+    _window = None
 
     def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
                  quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None,
-                 net_size: Optional[Tuple[int, int]] = None, clean: Optional[CleanOptions] = None) -> None:
+                 net_size: Optional[Tuple[int, int]] = None, clean: Optional[CleanOptions] = None,
+                 roi: Optional[RoiOptions] = None) -> None:
         from util import frame_overlay
         self._set_geometry(height, width, depth, net_size)
         if clean is not None and not isinstance(clean, CleanOptions):
             raise ValueError(f"{self._who}: clean must be a fosvos_hip.options.CleanOptions or None, got {type(clean).__name__}")
         self.clean = clean
+        if roi is not None:
+            if not isinstance(roi, RoiOptions):
+                raise ValueError(f"{self._who}: roi must be a fosvos_hip.options.RoiOptions or None, got {type(roi).__name__}")
+            if net_size is None:
+                raise ValueError(f"{self._who}: roi needs net_size=(Hn, Wn): a window of the frame is scaled to the net's size, "
+                                 "and without one the net sees the whole frame as it is")
+            if clean is not None and clean.chain:
+                raise ValueError(f"{self._who}: roi with clean.temporal_radius is not built: the chained seed lives on the "
+                                 "net's map, whose coordinates move from frame to frame with the window")
+        self.roi = roi
         frame_overlay.check_color(color)
         self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
         self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
@@ -182,8 +208,10 @@ class FrameSegmenter:
             self._up = torch.cuda.Stream(device=self.device)
             self._down = torch.cuda.Stream(device=self.device)
             self._rest = torch.cuda.Stream(device=self.device) if self.encode else None  # second copies of long files
-            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget, self.net_size)
-                                       for _ in range(self.depth)]
+            self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget, self.net_size,
+                                             self.roi is not None) for _ in range(self.depth)]
+            # roi: the window the next frame is seen through.  The whole frame until a frame or seed_window says otherwise
+            self._window = torch.tensor([[0, 0, h, w]], dtype=torch.int32, device=self.device) if self.roi is not None else None
             # the temporal gate's seed: what the last frame computed kept, at the net's size.  Empty = no gate (the rule
             # of an empty seed), so a segmenter nobody seeded starts ungated
             chained = self.clean is not None and self.clean.chain
@@ -253,8 +281,15 @@ class FrameSegmenter:
 
     def _compute(self, slot: _Slot) -> None:
         """What a frame needs on the net's stream, from ``slot.frame`` to ``slot.out`` (and the slot's file)."""
+        roi = self.roi
         with self._last_output_only(self.net), torch.no_grad():
-            ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
+            if roi is not None:
+                # the window this frame is seen through: what the frame before left in self._window, kept in the slot because
+                # the overlay needs it after window_next has overwritten self._window.  All of it on the one net's stream
+                slot.window.copy_(self._window, non_blocking=True)
+                ops.frame_prep_window(slot.frame, slot.window, self._roi_size, self.mirror, out=slot.image)
+            else:
+                ops.frame_prep(slot.frame, self.mirror, out=slot.image, net_size=self.net_size)
             logits = self.net.forward(slot.image)[-1]
             if self.clean is not None:
                 # in place on the net's output.  The seed is read AND written by this one call (chain over one frame: gated
@@ -265,8 +300,15 @@ class FrameSegmenter:
                 ops.clean_components(logits, self._seed, 0 if c.temporal_radius is None else c.temporal_radius, c.min_area,
                                      c.largest, chain=c.chain, fill=c.fill, out=logits,
                                      kept=None if self._seed is None else self._seed)
-            ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
-                        out=slot.out, net_size=self.net_size)
+            if roi is not None:
+                logits = logits.contiguous()
+                ops.window_next(logits, slot.window, (self.height, self.width), roi.levels, roi.margin, roi.min_pad,
+                                out=self._window)
+                ops.overlay_window(slot.frame, logits, slot.window, self.mirror, self.boolean_mask, self.color, self.alpha,
+                                   self.overlay, out=slot.out)
+            else:
+                ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
+                            out=slot.out, net_size=self.net_size)
             if self.encode:
                 ops.jpeg_encode(slot.out, self.quality, out=slot.file, lengths=slot.length, subsampling=self.subsampling)
 
@@ -365,11 +407,44 @@ class FrameSegmenter:
         with torch.cuda.device(self.device):
             self._seed.copy_(host)  # on the current stream, the net's: ordered with the frames before and behind
 
+    @property
+    def _roi_size(self) -> Tuple[int, int]:
+        """The net's size as the window ops take it: the frame's own is a size like any other there."""
+        return self.net_size or (self.height, self.width)
+
+    def seed_window(self, mask) -> None:
+        """Set the window of the next submitted frame from an annotation (see the class)."""
+        self._check_open()
+        if self.roi is None:
+            raise RuntimeError(f"{self._who}.seed_window: there is no window to seed (roi=RoiOptions(...))")
+        if isinstance(mask, torch.Tensor):
+            mask = mask.detach().cpu().numpy()
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.uint8, np.bool_) or mask.shape != (self.height, self.width):
+            raise ValueError(f"{self._who}.seed_window: a uint8 or bool mask of {(self.height, self.width)}, got {mask.dtype} "
+                             f"{mask.shape}")
+        from util import frame_roi
+        if self.mirror:  # the mask is in the frame's coordinates, the windows in those of the mirrored picture
+            mask = mask[:, ::-1]
+        hn, wn = self._roi_size
+        window = frame_roi.window_of_mask(mask, hn, wn, self.roi.levels, self.roi.margin_permille, self.roi.min_pad)
+        host = torch.tensor([window], dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            self._window.copy_(host)  # on the current stream, the net's: ordered with the frames before and behind
+
+    def last_window(self) -> Tuple[int, int, int, int]:
+        """The window the next frame will use (see the class).  Waits for the frames submitted so far."""
+        self._check_open()
+        if self.roi is None:
+            raise RuntimeError(f"{self._who}.last_window: there is no window (roi=RoiOptions(...))")
+        return tuple(int(v) for v in self._window.cpu()[0])
+
     def close(self) -> None:
         if self._closed:
             return
         self._closed = True
         self._seed = None
+        self._window = None
         for slot in self._flight:
             try:
                 slot.moved.synchronize()
@@ -410,8 +485,10 @@ class ObjectSegmenter(FrameSegmenter):
     def __init__(self, nets, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  palette=None, alpha: float = 0.5, encode: Optional[str] = None, quality: int = 90,
                  subsampling: str = '4:4:4', budget: Optional[int] = None, huffman: str = 'fixed',
-                 net_size: Optional[Tuple[int, int]] = None, clean=None) -> None:
+                 net_size: Optional[Tuple[int, int]] = None, clean=None, roi=None) -> None:
         from util import object_overlay
+        if roi is not None:
+            raise ValueError("ObjectSegmenter: roi= follows ONE object (FrameSegmenter); a window around K objects is not built")
         if clean is not None:
             raise ValueError("ObjectSegmenter: clean= cleans the mask of ONE object (FrameSegmenter); per-object cleaning of "
                              "K logit maps before the merge is not built")

@@ -20,7 +20,11 @@ towards its DAVIS palette colour (``--palette-alpha``, 0..1), or with ``--no-ove
 as palette PNG files that the device encoded.  ``--clean-min-area N``, ``--clean-largest`` and ``--clean-temporal R`` (any of them;
 single object only) clean the net's mask on the device before the overlay (``FrameSegmenter(clean=)``;
 util/mask_components.py): connected components that are too small, not the largest, or further than R net pixels from what the
-frame before kept are dropped; ``--clean-seed FILE.png`` is the mask the first frame is gated by.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+frame before kept are dropped; ``--clean-seed FILE.png`` is the mask the first frame is gated by.  ``--roi`` (with
+``--net-height`` / ``--net-width``; single object only) follows the object: the net sees a window of the frame around the last
+mask, scaled to the net's size, and the logits are painted back into it (``FrameSegmenter(roi=)``; util/frame_roi.py);
+``--roi-levels N``, ``--roi-margin F`` and ``--roi-min-pad P`` are the RoiOptions, ``--roi-seed FILE.png`` is the annotation the
+first window is taken from.  ``--clean-largest`` is its recommended companion.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -97,7 +101,45 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--clean-seed', type=str, default=None, metavar='FILE.png',
                    help='the mask --clean-temporal starts from (non-zero = object; the frames\' or the net\'s size), '
                         'e.g. the annotation the net was fine-tuned on')
+    p.add_argument('--roi', action='store_true',
+                   help='follow the object: run the net on a window around the last mask (with --net-height and --net-width)')
+    p.add_argument('--roi-levels', type=int, default=None, metavar='N',
+                   help='with --roi: window sizes between the net\'s size and the frame\'s, 1..64 (default 8)')
+    p.add_argument('--roi-margin', type=float, default=None, metavar='F',
+                   help='with --roi: pad the mask\'s box by this share of its longer side, 0..4 (default 0.25)')
+    p.add_argument('--roi-min-pad', type=int, default=None, metavar='P',
+                   help='with --roi: ... and by this many frame pixels, 0..4095 (default 16)')
+    p.add_argument('--roi-seed', type=str, default=None, metavar='FILE.png',
+                   help='with --roi: the mask the first window is taken from (non-zero = object; the frames\' size)')
     return p
+
+
+def roi_of(parser: argparse.ArgumentParser, args, net_size):
+    """The RoiOptions of --roi [--roi-levels --roi-margin --roi-min-pad], or None without --roi; what it does not go with is
+    refused with its reason."""
+    for flag, value in (('--roi-levels', args.roi_levels), ('--roi-margin', args.roi_margin), ('--roi-min-pad', args.roi_min_pad),
+                        ('--roi-seed', args.roi_seed)):
+        if value is not None and not args.roi:
+            parser.error('{} is an option of --roi: give --roi'.format(flag))
+    if not args.roi:
+        return None
+    if not args.use_network:
+        parser.error('--roi follows the net\'s mask: --no-network runs no net')
+    if args.models is not None:
+        parser.error('--roi follows one object (--model): a window around several objects (--models) is not built')
+    if args.clean_temporal is not None:
+        parser.error('--roi with --clean-temporal is not built: the temporal gate\'s seed lives on the net\'s map, whose '
+                     'coordinates move from frame to frame with the window')
+    if net_size is None:
+        parser.error('--roi needs --net-height and --net-width: a window of the frame is scaled to the net\'s size')
+    from fosvos_hip.options import RoiOptions
+    given = {k: v for k, v in (('levels', args.roi_levels), ('margin', args.roi_margin), ('min_pad', args.roi_min_pad))
+             if v is not None}
+    try:
+        return RoiOptions(**given)
+    except ValueError as e:
+        parser.error(str(e).replace('RoiOptions: levels', '--roi-levels').replace('RoiOptions: margin', '--roi-margin').replace(
+            'RoiOptions: min_pad', '--roi-min-pad'))
 
 
 def clean_of(parser: argparse.ArgumentParser, args):
@@ -375,6 +417,7 @@ def main(argv=None) -> List[float]:
     args = parser.parse_args(argv)
     net_size = net_size_of(parser, args)
     clean = clean_of(parser, args)
+    roi = roi_of(parser, args, net_size)
     if args.models is not None:
         check_models(parser, args, argv)
     if not args.use_cuda:
@@ -454,10 +497,14 @@ def main(argv=None) -> List[float]:
                                    suffix='.png' if seg.encode == 'png' else '.jpg')
         if clean is not None:  # (absent: the segmenter is constructed exactly as it was)
             encode['clean'] = clean
+        if roi is not None:
+            encode['roi'] = roi
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
                             boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha, **encode) as seg:
             if args.clean_seed is not None:
                 seg.seed(read_seed(args.clean_seed))
+            if args.roi_seed is not None:
+                seg.seed_window(read_seed(args.roi_seed))
             return loop_frames(seg.segment(chain_first(first, frames)), output, avi=avi)
     finally:
         if avi is not None:

@@ -651,6 +651,37 @@ int fosvos_frame_prep_scaled(const uint8_t *frames, int N, int Hf, int Wf, int H
 int fosvos_overlay_scaled(const uint8_t *frames, const float *logits, int N, int Hf, int Wf, int Hn, int Wn, int mirror,
                           int mode, int channel, double alpha, uint8_t *out, int device, void *stream);
 
+/* Following the object (opt-in): the net sees a WINDOW of every frame, and the window comes from device memory, so the host
+ * never reads it.  util/frame_roi.py states all three in numpy.  `windows` is int32 [N][4] = (y0, x0, Hw, Ww) per frame, in
+ * the coordinates of the picture the net sees (after `mirror`), 4-byte aligned.  A window is valid when Hn <= Hw <= Hf,
+ * Wn <= Ww <= Wf, 0 <= y0 <= Hf - Hw and 0 <= x0 <= Wf - Ww; every kernel reads ANY other window - negative or overflowing
+ * values included - as the whole frame (0, 0, Hf, Wf), so no loop bound or address depends on an unchecked value.  Sizes,
+ * alignment, modes, alpha, channel and error codes as for the scaled entries.  No synchronisation, no host read.
+ *
+ * fosvos_frame_prep_window: fosvos_frame_prep_scaled of the window's pixels: weights of (Hw -> Hn) and (Ww -> Wn), one fp64
+ *   division by Hw Ww.  Grid and LDS are those of fosvos_frame_prep_scaled at the same sizes.  The whole-frame window gives
+ *   fosvos_frame_prep_scaled bit for bit, a window of the net's size float(byte) - mean of the crop.  One launch.
+ *
+ * fosvos_overlay_window: fosvos_overlay_scaled with the logits painted into the window: inside it the taps are those of
+ *   (Hn -> Hw) and (Wn -> Ww) and the soft modes divide by 4 Hw Ww; outside it nothing is object (the frame's bytes, or a 0
+ *   mask byte).  The grid is the frame's.  One launch.
+ *
+ * fosvos_window_next: logits fp32 [N,1,Hn,Wn] and the windows they were made through -> out int32 [N][4], the windows of the
+ *   next frames (out == windows is allowed): the bounding box of logits >= 0 on the net's map (a NaN is not object, -0.0 is),
+ *   mapped into the frame through the sanitised window, padded by min_pad + ceil(margin_permille max(box sides) / 1000),
+ *   fitted into the smallest of the levels + 1 sizes Hn + (Hf - Hn) k / levels (widths likewise) that holds it, centred on
+ *   the box and pushed into the frame; no object: the whole frame.  1 <= levels <= 64, 0 <= margin_permille <= 4000,
+ *   0 <= min_pad <= 4095 (FOSVOS_E_ARG).  workspace: fosvos_window_next_workspace_bytes, 4-byte aligned; the entry
+ *   initialises it.  An order-free min / max reduction by agent-scope atomics; nothing waits.  Two launches. */
+int fosvos_frame_prep_window(const uint8_t *frames, const int32_t *windows, int N, int Hf, int Wf, int Hn, int Wn, int mirror,
+                             const float mean[3], float *image, int device, void *stream);
+int fosvos_overlay_window(const uint8_t *frames, const float *logits, const int32_t *windows, int N, int Hf, int Wf, int Hn,
+                          int Wn, int mirror, int mode, int channel, double alpha, uint8_t *out, int device, void *stream);
+size_t fosvos_window_next_workspace_bytes(int N);
+int fosvos_window_next(const float *logits, const int32_t *windows, int N, int Hf, int Wf, int Hn, int Wn, int levels,
+                       int margin_permille, int min_pad, int32_t *out, void *workspace, size_t workspace_bytes, int device,
+                       void *stream);
+
 /* Several objects a stream (ABI 32, opt-in): the K logit maps of K per-object nets on the same frames (`logits` as for
  * fosvos_merge_objects: a host array of K device pointers that travel by value, 1 <= K <= FOSVOS_MAX_OBJECTS) are merged
  * and painted in one pass; no label map is written in between.  util/object_overlay.py states both in numpy; every byte is
