@@ -43,6 +43,13 @@
 //   k_window_next        the bounding box of logits >= 0 by __ballot and one atomic min / max per workgroup and bound; the
 //                        workgroup that finishes last turns the box into the next window.
 //
+// Edge-aware upsampling (opt-in; util/guided_upsample.py states it): the coefficient maps of the guided filter (csrc/guided.hip)
+// in place of the logits.
+// fosvos_overlay_guided, one launch:
+//   k_overlay_guided     the paint skeleton with the source PairUp - 4 Hf Wf times abar and bbar, fp64 [N,2,Hn,Wn], interpolated
+//                        with k_overlay_scaled's taps - and the paint Guided: v = A I + Bv, I the fp64 sum of the (mirrored)
+//                        pixel's own mean-free bytes, then OneChannel / OneByte on v.  It reads the frame in every mode.
+//
 // Several objects a stream (opt-in; util/object_overlay.py states both): the K logit maps of K per-object nets, pointers by value.
 // fosvos_overlay_objects, one launch:
 //   k_overlay_objects         a thread takes its 16 logits from each of the K maps in turn and keeps (best value, label) per
@@ -62,7 +69,10 @@
 // OneChannel (level<MODE> in one channel), PaletteBlend (towards the label's colour, all three) or OneByte (a mask or a label,
 // no frame read).  k_overlay = MapInPlace + OneChannel | OneByte, k_overlay_scaled = MapUp + the same, k_overlay_objects =
 // MapsInPlace + PaletteBlend, k_overlay_objects_scaled = MapsUp + PaletteBlend | OneByte.  k_overlay_window is a fifth wrapper,
-// MapUpWindow + OneChannel | OneByte: a source beside MapUp, the paints as they are.
+// MapUpWindow + OneChannel | OneByte: a source beside MapUp, the paints as they are.  k_overlay_guided is a sixth, PairUp +
+// Guided<OneChannel | OneByte>: a source whose value is a pair and a paint that reduces it in front of the paint of the mode.
+// Whether the body loads the frame is the paint's compile-time property kReadsFrame, not its byte count: the guided mask
+// modes write one byte and read the frame.
 #include <limits.h>
 #include <math.h>
 
@@ -314,7 +324,8 @@ __global__ __launch_bounds__(kScaleThreads) void k_frame_prep_window(const uint8
 
 // ------------------------------------------------------------------------------------------ the overlays: paints
 // A paint turns the value of a pixel and the frame's bytes b[3] into the output bytes o[0..kBytes): 3 repaint the frame, 1
-// writes a map of its own and reads no frame.
+// writes a map of its own.  kReadsFrame says whether the skeleton loads b for it: every paint that repaints the frame, and the
+// guided paint in its mask modes too, whose value is made of the pixel's own bytes.
 //
 // the new byte of one pixel: `byte` is the frame's value in the overlay's channel (unused in the mask modes); x is the fp32
 // logit, or (scaled) the fp64 one - in the boolean modes any positive multiple of it
@@ -329,6 +340,7 @@ __device__ __forceinline__ uint32_t level(T x, uint32_t byte, double a255) {
 template <int MODE>
 struct OneChannel {
     static constexpr int kBytes = 3;
+    static constexpr bool kReadsFrame = true;
     int channel;
     double a255;
     template <typename T>
@@ -343,6 +355,7 @@ struct OneChannel {
 template <int MODE>
 struct OneByte {
     static constexpr int kBytes = 1;
+    static constexpr bool kReadsFrame = false;
     template <typename T>
     __device__ __forceinline__ void operator()(T x, const uint32_t (&)[3], uint32_t (&o)[3]) const {
         o[0] = level<MODE>(x, 0u, 0.0);
@@ -362,6 +375,7 @@ __device__ __forceinline__ void stage_colours(const uint8_t *__restrict__ palett
 }
 struct PaletteBlend {
     static constexpr int kBytes = 3;
+    static constexpr bool kReadsFrame = true;
     const uint32_t *cols;  // what stage_colours staged
     double alpha;
     __device__ __forceinline__ void operator()(uint32_t label, const uint32_t (&b)[3], uint32_t (&o)[3]) const {
@@ -586,6 +600,75 @@ struct MapUpWindow {
     __device__ __forceinline__ double at(int64_t) { return take(0); }
 };
 
+// Edge-aware upsampling (util/guided_upsample.py): the value of a pixel is the PAIR (A, Bv), 4 Hf Wf times the interpolated
+// abar and bbar of the coefficient maps fp64 [N,2,Hn,Wn] (csrc/guided.hip) - RowsUp's segments, anchor, store and taps, applied
+// to two fp64 maps.  The paint below reduces the pair with the pixel's own bytes.
+struct Pair {
+    double a, b;
+};
+// The pixels of a thread walk along one output row, and Wn <= Wf: the column taps move on by at most one map column a pixel.
+// So the thread keeps the two map columns of the last taps - four doubles each: abar and bbar at the rows of ty - and loads
+// a column only when a tap reaches one it does not hold: about 4 Wn / Wf loads a pixel in place of 8.  The values are the
+// map's either way.
+struct Column {
+    double at, ab, bt, bb;  // abar at the top and bottom row of ty, bbar likewise
+};
+struct PairUp : RowsUp {
+    const double *__restrict__ coeff;
+    const double *__restrict__ ca = nullptr;  // the frame's abar map; bbar lies one plane behind it
+    int64_t plane = 0;
+    int k0 = -1, k1 = -1;  // the map columns held in c0, c1
+    Column c0 = {}, c1 = {};
+    __device__ __forceinline__ Span open(int64_t gid, int64_t seg, int64_t slots, const uint8_t *dst, int bytes) {
+        const Span s = RowsUp::open(gid, seg, slots, dst, bytes);
+        plane = (int64_t)Hn * Wn;
+        ca = coeff + (seg / Hf) * 2 * plane;
+        top = (int64_t)ty.i0 * Wn, bot = (int64_t)ty.i1 * Wn;  // rows of the frame's own maps
+        return s;
+    }
+    __device__ __forceinline__ Column column(int i) const {
+        return Column{ca[top + i], ca[bot + i], ca[plane + top + i], ca[plane + bot + i]};
+    }
+    __device__ __forceinline__ Pair take(int) {
+        const Tap tx = next_tap();
+        if (tx.i0 != k0) {  // (first c0 from the old c1, then c1 from the new c0)
+            if (tx.i0 == k1)
+                c0 = c1;
+            else
+                c0 = column(tx.i0);
+            k0 = tx.i0;
+        }
+        if (tx.i1 != k1) {
+            if (tx.i1 == k0)
+                c1 = c0;
+            else
+                c1 = column(tx.i1);
+            k1 = tx.i1;
+        }
+        Pair v;  // value_up's expressions on the held columns
+        v.a = (c0.at * tx.w0 + c1.at * tx.w1) * ty.w0 + (c0.ab * tx.w0 + c1.ab * tx.w1) * ty.w1;
+        v.b = (c0.bt * tx.w0 + c1.bt * tx.w1) * ty.w0 + (c0.bb * tx.w0 + c1.bb * tx.w1) * ty.w1;
+        return v;
+    }
+    __device__ __forceinline__ Pair at(int64_t) { return take(0); }
+};
+// The guided paint: I = (b0 - m0) + (b1 - m1) + (b2 - m2) in fp64, the guide of the (mirrored) frame pixel; v = A I + Bv, which
+// is 4 Hf Wf times the refined logit - its sign for the boolean modes, v / scale for the soft ones - and then the paint of
+// the mode as it is.  It reads the frame in every mode.
+template <int MODE, typename Inner>
+struct Guided {
+    static constexpr int kBytes = Inner::kBytes;
+    static constexpr bool kReadsFrame = true;
+    Inner inner;
+    double m[3];
+    double scale;  // 4 Hf Wf
+    __device__ __forceinline__ void operator()(const Pair &p, const uint32_t (&b)[3], uint32_t (&o)[3]) const {
+        const double I = (((double)b[0] - m[0]) + ((double)b[1] - m[1])) + ((double)b[2] - m[2]);
+        const double v = p.a * I + p.b;
+        inner((MODE & 1) ? v / scale : v, b, o);
+    }
+};
+
 // ------------------------------------------------------------------------------------------ the overlays: the skeleton
 __device__ __forceinline__ void store16(bytes16 *__restrict__ p, const uint32_t *o) {
     bytes16 t;
@@ -602,23 +685,24 @@ template <bool MIRROR, typename Source, typename Paint>
 __device__ __forceinline__ void paint_pixels(Source from, const Paint paint, const uint8_t *__restrict__ frames,
                                              uint8_t *__restrict__ out, int64_t slots, int64_t total) {
     constexpr int NB = Paint::kBytes;
+    constexpr bool FRAME = Paint::kReadsFrame;
     const int64_t gid = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
     if (gid >= total) return;
     const int64_t seg = segment_of(gid, slots), L = from.length();
-    const uint8_t *__restrict__ src = NB == 3 ? frames + seg * 3 * L : nullptr;
+    const uint8_t *__restrict__ src = FRAME ? frames + seg * 3 * L : nullptr;
     uint8_t *__restrict__ dst = out + seg * NB * L;
     const Span s = from.open(gid, seg, slots, dst, NB);
     if (__builtin_expect(s.qb - s.qa == kGroup, 1)) {  // nearly every thread: keeps the group's code in the straight line
         from.load_group(s.qa);
         uint32_t w[12], o[4 * NB];
-        if constexpr (NB == 3) load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
+        if constexpr (FRAME) load48(src + 3 * (MIRROR ? L - kGroup - s.qa : s.qa), w);
 #pragma unroll
         for (int k = 0; k < 4 * NB; ++k) o[k] = 0;
 #pragma unroll
         for (int i = 0; i < kGroup; ++i) {
             const auto v = from.take(i);
             uint32_t b[3] = {0, 0, 0}, ob[3];
-            if constexpr (NB == 3) {
+            if constexpr (FRAME) {
                 const int px = MIRROR ? kGroup - 1 - i : i;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) b[c] = byte_at(w, 3 * px + c);
@@ -637,7 +721,7 @@ __device__ __forceinline__ void paint_pixels(Source from, const Paint paint, con
         for (int64_t q = s.qa; q < s.qb; ++q) {
             const auto v = from.at(q);
             uint32_t b[3] = {0, 0, 0}, ob[3];
-            if constexpr (NB == 3) {
+            if constexpr (FRAME) {
                 const int64_t sp = MIRROR ? L - 1 - q : q;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) b[c] = src[3 * sp + c];
@@ -683,6 +767,20 @@ __global__ __launch_bounds__(kStreamThreads) void k_overlay_window(const uint8_t
         paint_pixels<MIRROR>(from, OneChannel<MODE>{channel, a255}, frames, out, slots, total);
     else
         paint_pixels<MIRROR>(from, OneByte<MODE>{}, frames, out, slots, total);
+}
+
+// every mode mirrors here: the mask modes read the (mirrored) frame too
+template <int MODE, bool MIRROR>
+__global__ __launch_bounds__(kStreamThreads) void k_overlay_guided(const uint8_t *__restrict__ frames,
+                                                                   const double *__restrict__ coeff, uint8_t *__restrict__ out,
+                                                                   int Hf, int Wf, int Hn, int Wn, int64_t slots, int64_t total,
+                                                                   int channel, double a255, MeanBGR mean) {
+    const PairUp from = {{Hf, Wf, Hn, Wn}, coeff};
+    const double m0 = (double)mean.v[0], m1 = (double)mean.v[1], m2 = (double)mean.v[2], scale = (double)(4 * Hf * Wf);
+    if constexpr (MODE < 2)
+        paint_pixels<MIRROR>(from, Guided<MODE, OneChannel<MODE>>{{channel, a255}, {m0, m1, m2}, scale}, frames, out, slots, total);
+    else
+        paint_pixels<MIRROR>(from, Guided<MODE, OneByte<MODE>>{{}, {m0, m1, m2}, scale}, frames, out, slots, total);
 }
 
 // ------------------------------------------------------------------------------------------ window_next
@@ -838,6 +936,17 @@ void with_mode(int mode, int mirror, F &&f) {
         case 1: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 1>{}, m); }); break;
         case 2: f(std::integral_constant<int, 2>{}, std::false_type{}); break;
         default: f(std::integral_constant<int, 3>{}, std::false_type{}); break;
+    }
+}
+
+// the same where a mask mirrors as well (the guided paint reads the frame in every mode)
+template <typename F>
+void with_mode_and_mirror(int mode, int mirror, F &&f) {
+    switch (mode) {
+        case 0: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 0>{}, m); }); break;
+        case 1: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 1>{}, m); }); break;
+        case 2: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 2>{}, m); }); break;
+        default: with_mirror(mirror, [&](auto m) { f(std::integral_constant<int, 3>{}, m); }); break;
     }
 }
 
@@ -1035,6 +1144,27 @@ extern "C" int fosvos_overlay_scaled(const uint8_t *frames, const float *logits,
     with_mode(mode, mirror, [&](auto mo, auto mi) {
         hipLaunchKernelGGL((k_overlay_scaled<decltype(mo)::value, decltype(mi)::value>), p.grid, dim3(kStreamThreads), 0,
                            (hipStream_t)stream, frames, logits, out, Hf, Wf, Hn, Wn, p.slots, p.total, channel, alpha * 255.0);
+    });
+    FOSVOS_LAUNCH_CHECK();
+    return FOSVOS_OK;
+}
+
+extern "C" int fosvos_overlay_guided(const uint8_t *frames, const double *coeff, int N, int Hf, int Wf, int Hn, int Wn, int mirror,
+                                     int mode, int channel, double alpha, const float mean[3], uint8_t *out, int device,
+                                     void *stream) {
+    FOSVOS_REQUIRE(mode >= 0 && mode <= 3, FOSVOS_E_ARG, "overlay_guided: mode %d outside [0, 3]", mode);
+    FOSVOS_REQUIRE(frames && coeff && mean && out, FOSVOS_E_ARG, "overlay_guided: null pointer");  // the frames in every mode
+    if (int rc = check_sizes("overlay_guided", N, Hf, Wf, Hn, Wn)) return rc;
+    FOSVOS_REQUIRE(channel >= 0 && channel <= 2, FOSVOS_E_ARG, "overlay_guided: channel %d outside [0, 2]", channel);
+    FOSVOS_REQUIRE(alpha >= 0.0 && isfinite(alpha), FOSVOS_E_ARG, "overlay_guided: alpha %g is not a finite number >= 0", alpha);
+    FOSVOS_REQUIRE(((uintptr_t)coeff & 7) == 0, FOSVOS_E_ARG, "overlay_guided: the coefficients must be 8-byte aligned");
+    FOSVOS_ENTER(device);
+    const Partition p = partition_of(N, Hf, Wf, 1);  // rows, in every mode
+    const MeanBGR m = {{mean[0], mean[1], mean[2]}};
+    FOSVOS_PROF("k_overlay_guided", stream, 0.0);
+    with_mode_and_mirror(mode, mirror, [&](auto mo, auto mi) {
+        hipLaunchKernelGGL((k_overlay_guided<decltype(mo)::value, decltype(mi)::value>), p.grid, dim3(kStreamThreads), 0,
+                           (hipStream_t)stream, frames, coeff, out, Hf, Wf, Hn, Wn, p.slots, p.total, channel, alpha * 255.0, m);
     });
     FOSVOS_LAUNCH_CHECK();
     return FOSVOS_OK;

@@ -261,6 +261,11 @@ SIGNATURES = {
     "fosvos_window_next_workspace_bytes": (c_size_t, [c_int]),
     "fosvos_window_next": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_guided_coefficients_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fosvos_guided_coefficients": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                           c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_overlay_guided": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      ctypes.c_double, POINTER(c_float), c_void_p, c_int, c_void_p]),
     "fosvos_overlay_objects": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p,
                                        ctypes.c_double, c_void_p, c_int, c_void_p]),
     "fosvos_overlay_objects_scaled": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_int,

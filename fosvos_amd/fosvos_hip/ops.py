@@ -1896,6 +1896,85 @@ def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False,
     return out
 
 
+# edge-aware upsampling: the guided filter on the frame (util/guided_upsample.py states both)
+GUIDED_MAX_RADIUS = 8
+GUIDED_EPS_RANGE = (1e-3, 1e9)
+GUIDED_MAX_CLIP = 1e4
+_F64 = torch.float64
+
+
+def _real_number(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+def guided_params(radius, eps, clip, what: str = "guided_coefficients") -> Tuple[int, float, float]:
+    """The filter's three parameters, checked against the ranges the kernel and the numpy definition take."""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= GUIDED_MAX_RADIUS:
+        raise ValueError(f"{what}: radius must be an integer in 1..{GUIDED_MAX_RADIUS}, got {radius!r}")
+    if not _real_number(eps) or not GUIDED_EPS_RANGE[0] <= eps <= GUIDED_EPS_RANGE[1]:
+        raise ValueError(f"{what}: eps must be a finite number in [{GUIDED_EPS_RANGE[0]:g}, {GUIDED_EPS_RANGE[1]:g}], got {eps!r}")
+    if not _real_number(clip) or not 0.0 < clip <= GUIDED_MAX_CLIP:
+        raise ValueError(f"{what}: clip must be a finite number in (0, {GUIDED_MAX_CLIP:g}], got {clip!r}")
+    return radius, float(eps), float(clip)
+
+
+def guided_coefficients(image: torch.Tensor, logits: torch.Tensor, radius: int = 4, eps: float = 400.0, clip: float = 6.0,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_guided_coefficients: the net's input fp32 [N,3,Hn,Wn] (what ``frame_prep`` made) and its logits fp32 [N,1,Hn,Wn]
+    -> fp64 [N,2,Hn,Wn], the smoothed coefficients [abar, bbar] of the guided filter whose guide is the sum of the image's
+    planes and whose target is the logits clipped to ``[-clip, clip]`` (util/guided_upsample.coefficients, bit for bit).  Two
+    launches on the current stream, no synchronisation; the unsmoothed maps live in the stream's workspace."""
+    _need_eval(image, _F32, "guided_coefficients image")
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0:
+        raise ValueError(f"guided_coefficients: image must be a non-empty [N,3,Hn,Wn], got {tuple(image.shape)}")
+    n, hn, wn = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
+    if hn > MAX_FRAME_SIDE or wn > MAX_FRAME_SIDE:
+        raise ValueError(f"guided_coefficients: maps may have sides of up to {MAX_FRAME_SIDE}, got {(hn, wn)}")
+    _need_eval(logits, _F32, "guided_coefficients logits")
+    if tuple(logits.shape) != (n, 1, hn, wn):
+        raise ValueError(f"guided_coefficients: logits must be {(n, 1, hn, wn)}, got {tuple(logits.shape)}")
+    if logits.device != image.device:
+        raise RuntimeError(f"guided_coefficients: every tensor must be on {image.device}, got one on {logits.device}")
+    radius, eps, clip = guided_params(radius, eps, clip)
+    out = _out_like(out, (n, 2, hn, wn), _F64, image, "guided_coefficients")
+    ws, wsn = _WS.get(int(lib().fosvos_guided_coefficients_workspace_bytes(n, hn, wn)), image.device)
+    dev, st = _ctx(image)
+    e0 = _pb()
+    check(lib().fosvos_guided_coefficients(image.data_ptr(), logits.data_ptr(), n, hn, wn, radius, eps, clip, out.data_ptr(),
+                                           ws, wsn, dev, st), "guided_coefficients")
+    _pe(e0, "guided_coefficients", 0.0, (16.0 + 3 * 16.0) * n * hn * wn)
+    return out
+
+
+def overlay_guided(frames_u8: torch.Tensor, coeff: torch.Tensor, mirror: bool = False, boolean_mask: bool = True,
+                   color: str = 'r', alpha: float = 1.0, overlay: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_overlay_guided: ``overlay(net_size=)`` with the refined logit ``A I + Bv`` in place of the interpolated one: the
+    coefficients fp64 [N,2,Hn,Wn] (``guided_coefficients``) are interpolated up to the frames' size inside the launch and
+    applied to every (mirrored) frame pixel's own bytes (util/guided_upsample.py states the bytes).  The net's size is the
+    coefficients', no larger than the frames; the mask of ``overlay=False`` is the mirrored picture's with ``mirror``.  One
+    launch, no synchronisation."""
+    n, h, w = _frame_shape(frames_u8, "overlay_guided")
+    _need_eval(coeff, _F64, "overlay_guided coeff")
+    if coeff.dim() != 4 or coeff.shape[0] != n or coeff.shape[1] != 2 or coeff.numel() == 0:
+        raise ValueError(f"overlay_guided: coeff must be a non-empty {(n, 2, 'Hn', 'Wn')}, got {tuple(coeff.shape)}")
+    hn, wn = _roi_net_size((int(coeff.shape[2]), int(coeff.shape[3])), h, w, "overlay_guided")
+    if coeff.device != frames_u8.device:
+        raise RuntimeError(f"overlay_guided: every tensor must be on {frames_u8.device}, got one on {coeff.device}")
+    if color not in OVERLAY_CHANNEL:
+        raise ValueError(f"overlay_guided: color must be one of {tuple(OVERLAY_CHANNEL)}, got {color!r}")
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and alpha != float("inf")):
+        raise ValueError(f"overlay_guided: alpha must be a finite number >= 0, got {alpha!r}")
+    out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay_guided")
+    mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
+    dev, st = _ctx(frames_u8)
+    e0 = _pb()
+    check(lib().fosvos_overlay_guided(frames_u8.data_ptr(), coeff.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, mode,
+                                      OVERLAY_CHANNEL[color], alpha, _mean_bgr(), out.data_ptr(), dev, st), "overlay_guided")
+    _pe(e0, "overlay_guided", 0.0, (6.0 if overlay else 4.0) * n * h * w + 16.0 * n * hn * wn)
+    return out
+
+
 # following the object: the net on a window of the frame (util/frame_roi.py states all three)
 ROI_MAX_LEVELS = 64
 ROI_MAX_PAD = 4095

@@ -2,7 +2,8 @@
 (EngineOptions).  ``from_env`` of each is the ONLY place of the package that parses a ``FOSVOS_*`` switch; everything else
 takes an options object.  The defaults are the measured best; every switch selects between two paths that both stay tested.
 The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleaning) is opt-in by being
-passed and has no environment switch; so is AdaptOptions (online adaptation of the test pass).
+passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
+and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3).
 
 No torch and no library load here: importable anywhere.
 """
@@ -194,6 +195,33 @@ class RoiOptions:
 
 def _real(v) -> bool:
     return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+@dataclass(frozen=True)
+class RefineOptions:
+    """Edge-aware upsampling in a stream (``FrameSegmenter(refine=)``; util/guided_upsample.py states the rules; DESIGN.md
+    section 12.3): the guided filter with the frame as the guide, in place of the bilinear upsampling of the logits.  Opt-in
+    by being passed; this class reads no environment variable.  The defaults are the design's and are unmeasured on trained
+    nets."""
+
+    # the fit's and the smoothing's window reaches this many net pixels to every side: 1..8
+    radius: int = 4
+    # the regulariser beside the guide's variance in the window (the guide is the sum of three mean-free bytes, so an edge of
+    # 50 grey levels has a variance of about 5000): a finite number in [1e-3, 1e9].  Larger: smoother, less edge-following
+    eps: float = 400.0
+    # the logits are clipped to [-clip, clip] first, so that one confident pixel does not outweigh its window: (0, 1e4]
+    clip: float = 6.0
+
+    def __post_init__(self) -> None:
+        if isinstance(self.radius, bool) or not isinstance(self.radius, int) or not 1 <= self.radius <= 8:
+            raise ValueError(f"RefineOptions: radius must be an integer in 1..8, got {self.radius!r}")
+        if not _real(self.eps) or not 1e-3 <= self.eps <= 1e9:
+            raise ValueError(f"RefineOptions: eps must be a finite number in [1e-3, 1e9], got {self.eps!r}")
+        if not _real(self.clip) or not 0.0 < self.clip <= 1e4:
+            raise ValueError(f"RefineOptions: clip must be a finite number in (0, 1e4], got {self.clip!r}")
+
+    def as_dict(self) -> dict:
+        return {'radius': self.radius, 'eps': float(self.eps), 'clip': float(self.clip)}
 
 
 @dataclass(frozen=True)

@@ -56,6 +56,13 @@ by frame t's ``window_next`` and copied into frame t + 1's slot on the one net's
 the clean seed, no event and no host read of its own.  ``seed_window(mask)`` sets it from an annotation.  ``None`` is the object
 described above.
 
+``refine=RefineOptions(...)`` (opt-in, with or without ``net_size``; ``fosvos_hip.options``) upsamples by the frame's own edges:
+``ops.guided_coefficients`` fits, at the net's size, a linear model between the (cleaned) logits and the image the net saw and
+smooths it into the slot's coefficient maps (fp64 [1,2,Hn,Wn]), and ``ops.overlay_guided`` - in place of ``ops.overlay`` -
+interpolates the coefficients, not the logits, and applies them to every frame pixel's own bytes (csrc/guided.hip,
+csrc/stream.hip; util/guided_upsample.py states both).  The slot's image is read after the net: both nets' passes take their
+input const.  ``None`` is the object described above.
+
 Not thread-safe: one host thread drives a segmenter.
 """
 from __future__ import annotations
@@ -68,7 +75,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .options import CleanOptions, RoiOptions
+from .options import CleanOptions, RefineOptions, RoiOptions
 
 
 _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that the file starts 8-byte aligned
@@ -76,13 +83,15 @@ _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that t
 
 class _Slot:
     def __init__(self, h: int, w: int, out_shape, device: torch.device, capacity: int = 0, budget: int = 0,
-                 net_size=None, roi: bool = False) -> None:
+                 net_size=None, roi: bool = False, refine: bool = False) -> None:
         self.host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
         self.host_in_np = self.host_in.numpy()
         self.frame = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
         self.image = torch.empty((1, 3) + tuple(net_size or (h, w)), dtype=torch.float32, device=device)
         self.out = torch.empty(out_shape, dtype=torch.uint8, device=device)
         self.window = torch.empty((1, 4), dtype=torch.int32, device=device) if roi else None  # the one this frame is seen through
+        # refine: the smoothed coefficient maps of this frame (the unsmoothed ones live in the stream's workspace)
+        self.coeff = torch.empty((1, 2) + tuple(net_size or (h, w)), dtype=torch.float64, device=device) if refine else None
         if capacity:
             self.store = torch.empty((_HEAD + capacity,), dtype=torch.uint8, device=device)
             self.length = self.store[:4].view(torch.int32)
@@ -119,6 +128,7 @@ class FrameSegmenter:
 
     clean: Optional[CleanOptions] = None  # (ObjectSegmenter has none)
     roi: Optional[RoiOptions] = None      # (likewise)
+    refine: Optional[RefineOptions] = None  # (likewise)
     _seed = None
     _window = None
 
@@ -126,7 +136,7 @@ class FrameSegmenter:
                  boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
                  quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None,
                  net_size: Optional[Tuple[int, int]] = None, clean: Optional[CleanOptions] = None,
-                 roi: Optional[RoiOptions] = None) -> None:
+                 roi: Optional[RoiOptions] = None, refine: Optional[RefineOptions] = None) -> None:
         from util import frame_overlay
         self._set_geometry(height, width, depth, net_size)
         if clean is not None and not isinstance(clean, CleanOptions):
@@ -142,6 +152,14 @@ class FrameSegmenter:
                 raise ValueError(f"{self._who}: roi with clean.temporal_radius is not built: the chained seed lives on the "
                                  "net's map, whose coordinates move from frame to frame with the window")
         self.roi = roi
+        if refine is not None:
+            if not isinstance(refine, RefineOptions):
+                raise ValueError(f"{self._who}: refine must be a fosvos_hip.options.RefineOptions or None, got "
+                                 f"{type(refine).__name__}")
+            if roi is not None:
+                raise ValueError(f"{self._who}: refine with roi is not built: the filter's guide is the image the net saw, a "
+                                 "window of the frame, and the guide of a window is not built")
+        self.refine = refine
         frame_overlay.check_color(color)
         self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
         self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
@@ -209,7 +227,7 @@ class FrameSegmenter:
             self._down = torch.cuda.Stream(device=self.device)
             self._rest = torch.cuda.Stream(device=self.device) if self.encode else None  # second copies of long files
             self._free: List[_Slot] = [_Slot(h, w, out_shape, self.device, self.capacity, self.budget, self.net_size,
-                                             self.roi is not None) for _ in range(self.depth)]
+                                             self.roi is not None, self.refine is not None) for _ in range(self.depth)]
             # roi: the window the next frame is seen through.  The whole frame until a frame or seed_window says otherwise
             self._window = torch.tensor([[0, 0, h, w]], dtype=torch.int32, device=self.device) if self.roi is not None else None
             # the temporal gate's seed: what the last frame computed kept, at the net's size.  Empty = no gate (the rule
@@ -306,6 +324,11 @@ class FrameSegmenter:
                                 out=self._window)
                 ops.overlay_window(slot.frame, logits, slot.window, self.mirror, self.boolean_mask, self.color, self.alpha,
                                    self.overlay, out=slot.out)
+            elif self.refine is not None:
+                f = self.refine
+                ops.guided_coefficients(slot.image, logits.contiguous(), f.radius, f.eps, f.clip, out=slot.coeff)
+                ops.overlay_guided(slot.frame, slot.coeff, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
+                                   out=slot.out)
             else:
                 ops.overlay(slot.frame, logits, self.mirror, self.boolean_mask, self.color, self.alpha, self.overlay,
                             out=slot.out, net_size=self.net_size)
@@ -485,8 +508,11 @@ class ObjectSegmenter(FrameSegmenter):
     def __init__(self, nets, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  palette=None, alpha: float = 0.5, encode: Optional[str] = None, quality: int = 90,
                  subsampling: str = '4:4:4', budget: Optional[int] = None, huffman: str = 'fixed',
-                 net_size: Optional[Tuple[int, int]] = None, clean=None, roi=None) -> None:
+                 net_size: Optional[Tuple[int, int]] = None, clean=None, roi=None, refine=None) -> None:
         from util import object_overlay
+        if refine is not None:
+            raise ValueError("ObjectSegmenter: refine= refines the logits of ONE object (FrameSegmenter); K fits in front of the "
+                             "merge are not built")
         if roi is not None:
             raise ValueError("ObjectSegmenter: roi= follows ONE object (FrameSegmenter); a window around K objects is not built")
         if clean is not None:

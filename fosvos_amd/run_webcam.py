@@ -24,7 +24,10 @@ frame before kept are dropped; ``--clean-seed FILE.png`` is the mask the first f
 ``--net-height`` / ``--net-width``; single object only) follows the object: the net sees a window of the frame around the last
 mask, scaled to the net's size, and the logits are painted back into it (``FrameSegmenter(roi=)``; util/frame_roi.py);
 ``--roi-levels N``, ``--roi-margin F`` and ``--roi-min-pad P`` are the RoiOptions, ``--roi-seed FILE.png`` is the annotation the
-first window is taken from.  ``--clean-largest`` is its recommended companion.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
+first window is taken from.  ``--clean-largest`` is its recommended companion.  ``--refine`` (single object only, not with
+``--roi``) upsamples by the frame's own edges: the guided filter with the frame as the guide replaces the bilinear upsampling of
+the logits (``FrameSegmenter(refine=)``; util/guided_upsample.py); ``--refine-radius N``, ``--refine-eps F`` and ``--refine-clip F``
+are the RefineOptions.  There is no CPU path (``--no-cuda`` is refused) and no display; ``--webcam`` needs OpenCV for the capture.
 """
 import argparse
 import os
@@ -111,7 +114,42 @@ def build_parser() -> argparse.ArgumentParser:
                    help='with --roi: ... and by this many frame pixels, 0..4095 (default 16)')
     p.add_argument('--roi-seed', type=str, default=None, metavar='FILE.png',
                    help='with --roi: the mask the first window is taken from (non-zero = object; the frames\' size)')
+    p.add_argument('--refine', action='store_true',
+                   help='upsample by the frame\'s own edges: the guided filter on the frame in place of the bilinear upsampling')
+    p.add_argument('--refine-radius', type=int, default=None, metavar='N',
+                   help='with --refine: the filter\'s window reaches N net pixels to every side, 1..8 (default 4)')
+    p.add_argument('--refine-eps', type=float, default=None, metavar='F',
+                   help='with --refine: the regulariser beside the guide\'s variance, 1e-3..1e9 (default 400)')
+    p.add_argument('--refine-clip', type=float, default=None, metavar='F',
+                   help='with --refine: the logits are clipped to [-F, F] first, 0 < F <= 1e4 (default 6)')
     return p
+
+
+def refine_of(parser: argparse.ArgumentParser, args):
+    """The RefineOptions of --refine [--refine-radius --refine-eps --refine-clip], or None without --refine; what it does not go
+    with is refused with its reason."""
+    for flag, value in (('--refine-radius', args.refine_radius), ('--refine-eps', args.refine_eps),
+                        ('--refine-clip', args.refine_clip)):
+        if value is not None and not args.refine:
+            parser.error('{} is an option of --refine: give --refine'.format(flag))
+    if not args.refine:
+        return None
+    if not args.use_network:
+        parser.error('--refine refines the net\'s logits: --no-network runs no net')
+    if args.models is not None:
+        parser.error('--refine refines the logits of one object (--model): a fit per object in front of the merge (--models) '
+                     'is not built')
+    if args.roi:
+        parser.error('--refine with --roi is not built: the filter\'s guide is the image the net saw, and the guide of a window '
+                     'of the frame is not built')
+    from fosvos_hip.options import RefineOptions
+    given = {k: v for k, v in (('radius', args.refine_radius), ('eps', args.refine_eps), ('clip', args.refine_clip))
+             if v is not None}
+    try:
+        return RefineOptions(**given)
+    except ValueError as e:
+        parser.error(str(e).replace('RefineOptions: radius', '--refine-radius').replace('RefineOptions: eps', '--refine-eps').replace(
+            'RefineOptions: clip', '--refine-clip'))
 
 
 def roi_of(parser: argparse.ArgumentParser, args, net_size):
@@ -418,6 +456,7 @@ def main(argv=None) -> List[float]:
     net_size = net_size_of(parser, args)
     clean = clean_of(parser, args)
     roi = roi_of(parser, args, net_size)
+    refine = refine_of(parser, args)
     if args.models is not None:
         check_models(parser, args, argv)
     if not args.use_cuda:
@@ -499,6 +538,8 @@ def main(argv=None) -> List[float]:
             encode['clean'] = clean
         if roi is not None:
             encode['roi'] = roi
+        if refine is not None:
+            encode['refine'] = refine
         with FrameSegmenter(net, first.shape[0], first.shape[1], depth=args.depth, mirror=args.mirror, overlay=args.overlay,
                             boolean_mask=args.boolean_mask, color=args.overlay_color, alpha=args.overlay_alpha, **encode) as seg:
             if args.clean_seed is not None:

@@ -682,6 +682,30 @@ int fosvos_window_next(const float *logits, const int32_t *windows, int N, int H
                        int margin_permille, int min_pad, int32_t *out, void *workspace, size_t workspace_bytes, int device,
                        void *stream);
 
+/* Edge-aware upsampling of the stream's logits (opt-in): the guided filter with the frame as the guide.
+ * util/guided_upsample.py states both entries in numpy; the coefficient maps and the boolean modes are compared with it bit
+ * for bit.  Every fp64 operation is one IEEE operation of that file, in its order, uncontracted.  No synchronisation.
+ *
+ * fosvos_guided_coefficients (csrc/guided.hip): image fp32 [N,3,Hn,Wn] (what the prep made for the net) and logits fp32
+ *   [N,1,Hn,Wn] -> coeff fp64 [N,2,Hn,Wn] = [abar, bbar]: the guide g = the sum of the three planes, the target p = the logit
+ *   clipped to [-clip, clip] (a NaN is -clip), the linear model a g + b of every window of radius `radius` cut to the map,
+ *   fitted with `eps`, then box-smoothed.  1 <= radius <= 8, 1e-3 <= eps <= 1e9, 0 < clip <= 1e4 (FOSVOS_E_ARG); sides of
+ *   1..8192 (FOSVOS_E_SHAPE); image and logits 4-byte, coeff and workspace 8-byte aligned.  workspace:
+ *   fosvos_guided_coefficients_workspace_bytes (the unsmoothed [a, b], fp64 [N,2,Hn,Wn]); every byte of it that is read was
+ *   written by the call.  Two launches (fit, smooth) of 16 x 64 tiles with a halo of `radius` in 60 KB of LDS; no workgroup
+ *   waits for another, no atomics.
+ *
+ * fosvos_overlay_guided (csrc/stream.hip): fosvos_overlay_scaled with, in place of the interpolated logit, v = A I + Bv: A and
+ *   Bv are 4 Hf Wf times abar and bbar interpolated with the scaled overlay's taps, I = sum_c (byte_c - mean[c]) in fp64 of
+ *   the (mirrored) frame pixel.  Modes, channel, alpha and sizes as for fosvos_overlay_scaled (Hn == Hf, Wn == Wf included),
+ *   but the frames are read in EVERY mode (null: FOSVOS_E_ARG) and `mirror` applies to the mask modes too: the mask is that of
+ *   the mirrored picture.  coeff 8-byte aligned.  One launch. */
+size_t fosvos_guided_coefficients_workspace_bytes(int N, int Hn, int Wn);
+int fosvos_guided_coefficients(const float *image, const float *logits, int N, int Hn, int Wn, int radius, double eps, double clip,
+                               double *coeff, void *workspace, size_t workspace_bytes, int device, void *stream);
+int fosvos_overlay_guided(const uint8_t *frames, const double *coeff, int N, int Hf, int Wf, int Hn, int Wn, int mirror, int mode,
+                          int channel, double alpha, const float mean[3], uint8_t *out, int device, void *stream);
+
 /* Several objects a stream (ABI 32, opt-in): the K logit maps of K per-object nets on the same frames (`logits` as for
  * fosvos_merge_objects: a host array of K device pointers that travel by value, 1 <= K <= FOSVOS_MAX_OBJECTS) are merged
  * and painted in one pass; no label map is written in between.  util/object_overlay.py states both in numpy; every byte is
