@@ -98,6 +98,17 @@ def _first_sample(data_loader) -> dict:
     raise ValueError('online adaptation needs the training frame as it is; this training loader only yields augmented ones')
 
 
+def _report_score(result: Optional[dict], save_dir: Path, seq_name: str) -> None:
+    """A sequence's score (None: the pass had no annotations, nothing happens) goes to the log, to
+    ``<save_dir>/<seq_name>/scores.yml`` and into ``scored_sequences``."""
+    if result is None:
+        return
+    log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
+    (Path(save_dir) / seq_name).mkdir(parents=True, exist_ok=True)
+    experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
+    scored_sequences.append(result)
+
+
 def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: OnlineSettings) -> None:
     train_seed = None
     first_sample = None
@@ -134,10 +145,7 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
             annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
             result = experiment_helper.test_adaptive(net_provider, data_loader, save_dir, first_sample, adapt, annotations,
                                                      seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
-            if result is not None:
-                log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
-                experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
-                scored_sequences.append(result)
+            _report_score(result, save_dir, seq_name)
             return
         if fast_test:
             annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
@@ -148,19 +156,13 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                     cleaning['clean_seed'] = _clean_seed(train_seed, annotations, data_loader, seq_name)
             result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name,
                                                  png_huffman='fitted' if png_fitted else 'fixed', **cleaning)
-            if result is not None:
-                log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
-                experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
-                scored_sequences.append(result)
+            _report_score(result, save_dir, seq_name)
             return
         if score:
             result = experiment_helper.test_scored(net_provider, data_loader, save_dir,
                                                    io_helper.get_annotations(db_root_dir, data_loader, synthetic_size),
                                                    seq_name=seq_name)
-            log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
-            (Path(save_dir) / seq_name).mkdir(parents=True, exist_ok=True)
-            experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
-            scored_sequences.append(result)
+            _report_score(result, save_dir, seq_name)
             return
         experiment_helper.test(net_provider, data_loader, save_dir, settings.is_visualizing_results,
                                settings.eval_speeds, seq_name=seq_name)
@@ -224,10 +226,7 @@ def train_and_test_objects(make_provider, seq_name: str, settings: OnlineSetting
         save_dir = save_dir_results / providers[0].name / str(settings.variant_offline) / str(settings.variant_online)
     result = experiment_helper.test_objects(providers, test_loader, save_dir, annotations if score else None,
                                             seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
-    if result is not None:
-        log.info('Score {0}: {1}'.format(seq_name, experiment_helper.format_score(result)))
-        experiment_helper.write_scores(Path(save_dir) / seq_name / 'scores.yml', result)
-        scored_sequences.append(result)
+    _report_score(result, save_dir, seq_name)
     return result
 
 

@@ -106,14 +106,155 @@ def test(net_provider, data_loader, save_dir: Path, is_visualizing_results: bool
     return None
 
 
-def _frame_annotation(annotations: Callable, seq: str, fname: str, h: int, w: int) -> Optional[np.ndarray]:
+def _frame_annotation(annotations: Callable, seq: str, fname: str, h: int, w: int, ids: bool = False) -> Optional[np.ndarray]:
+    """uint8 [H,W] of one frame, or None: 1 = object, or with ``ids`` the object ids as they come."""
     ann = annotations(seq, fname)
     if ann is None:
         return None
     ann = np.asarray(ann)
     if ann.shape != (h, w):
         raise ValueError('annotation of {}/{} is {}, the logits are {}'.format(seq, fname, ann.shape, (h, w)))
-    return (ann != 0).astype(np.uint8)
+    return ann.astype(np.uint8) if ids else (ann != 0).astype(np.uint8)
+
+
+class _Frames:
+    """The frames a test pass has seen so far: their sequences, their names and whether each has an annotation."""
+
+    def __init__(self, data_loader, save_dir: Path) -> None:
+        self.n_frames, self.save_dir = len(data_loader.dataset), Path(save_dir)
+        self.seqs, self.fnames, self.scored = [], [], []
+
+    def __len__(self) -> int:
+        return len(self.fnames)
+
+    def add(self, minibatches, h: int, w: int, annotations: Optional[Callable], ids: bool = False):
+        """Takes a group's minibatches in.  Returns the index of its first frame, its annotations as one uint8 [n,H,W] (a
+        frame without one: zeros, and not scored; None without ``annotations``) and the paths of its files."""
+        first = len(self.fnames)
+        n = sum(len(minibatch['fname']) for minibatch in minibatches)
+        if first + n > self.n_frames:
+            raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(self.n_frames))
+        gt = np.zeros((n, h, w), dtype=np.uint8) if annotations is not None else None
+        for minibatch in minibatches:
+            for seq, fname in zip(minibatch['seq_name'], minibatch['fname']):
+                ann = _frame_annotation(annotations, seq, fname, h, w, ids) if annotations is not None else None
+                if ann is not None:
+                    gt[len(self.fnames) - first] = ann
+                self.seqs.append(seq)
+                self.fnames.append(fname)
+                self.scored.append(ann is not None)
+        paths = [self.save_dir / self.seqs[k] / '{0}.png'.format(self.fnames[k]) for k in range(first, first + n)]
+        return first, gt, paths
+
+    def score_head(self, seq_name: Optional[str], radius) -> dict:
+        """The keys every score dict starts with."""
+        return {'seq_name': seq_name if seq_name is not None else (self.seqs[0] if self.seqs else None),
+                'radius': radius, 'fnames': list(self.fnames), 'scored': [bool(k) for k in self.scored]}
+
+
+class _Counters:
+    """Integer counters per frame, [n_frames, *tail]: an int64 array the host branches fill, or - made at its first use - an
+    int32 device tensor whose rows the kernels fill and which comes back in ONE read at the end of the pass."""
+
+    def __init__(self, n_frames: int, *tail: int) -> None:
+        self.host, self.dev = np.zeros((n_frames,) + tail, dtype=np.int64), None
+
+    def rows(self, first: int, n: int, device) -> torch.Tensor:
+        if self.dev is None:
+            self.dev = torch.zeros(self.host.shape, dtype=torch.int32, device=device)
+        return self.dev[first:first + n]
+
+    def read(self, n_seen: int) -> np.ndarray:
+        if self.dev is not None:
+            self.host, self.dev = self.dev.cpu().numpy().astype(np.int64), None
+        return self.host[:n_seen]
+
+
+def _sequence_score(frames: _Frames, counts: np.ndarray, radius, seconds: float, seq_name: Optional[str], **extra) -> dict:
+    """The score dict of one object's sequence from its [n,6] J / F counts (``test_scored`` states the keys)."""
+    j, f = davis_measures.jf_from_counts(counts) if len(frames) else (np.zeros(0), np.zeros(0))
+    keep = np.asarray(frames.scored, dtype=bool)
+    j_stats = davis_measures.sequence_statistics(j[keep])
+    f_stats = davis_measures.sequence_statistics(f[keep])
+    return {**frames.score_head(seq_name, radius),
+            'counts': [[int(v) for v in row] if k else None for row, k in zip(counts, keep)],
+            'J': [float(v) if k else None for v, k in zip(j, keep)],
+            'F': [float(v) if k else None for v, k in zip(f, keep)],
+            'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
+            'seconds': seconds, **extra}
+
+
+class _Slot:
+    """Device bytes laid out as [n files at capacity | n int32 lengths] - the lengths sit behind the files in the same buffer,
+    so that one copy brings both - and their pinned twin on the host."""
+
+    def __init__(self, n: int, cap: int, device) -> None:
+        self.n, self.cap = n, cap
+        self.dev = torch.empty(n * cap + 4 * n, dtype=torch.uint8, device=device)
+        self.host = torch.empty(n * cap + 4 * n, dtype=torch.uint8).pin_memory()
+        self.files, self.lengths = self.dev[:n * cap].view(n, cap), self.dev[n * cap:].view(torch.int32)
+
+    def send(self, paths):
+        """The ONE copy of a group, at capacity, and the event that says it has landed: the group's pending item."""
+        self.host.copy_(self.dev, non_blocking=True)
+        landed = torch.cuda.Event()
+        landed.record()
+        return self, landed, paths
+
+
+class _FileSlots:
+    """The files of a pass.  The device encodes a group's files into one of two slots, so the host can write a group's files
+    one group later, while the device works on the next."""
+
+    def __init__(self) -> None:
+        self.slots, self.turn, self.png_bytes = {}, 0, 0
+
+    def take(self, n: int, h: int, w: int, capacity: int, device) -> _Slot:
+        key = (self.turn, n, h, w, capacity + -capacity % 4)
+        self.turn ^= 1
+        if key not in self.slots:
+            self.slots[key] = _Slot(n, key[-1], device)
+        return self.slots[key]
+
+    def write(self, paths, blobs) -> None:
+        for path, blob in zip(paths, blobs):
+            path.parent.mkdir(parents=True, exist_ok=True)
+            with open(str(path), 'wb') as fh:
+                fh.write(blob)
+            self.png_bytes += len(blob)
+
+    def retire(self, item, stage: Optional[dict] = None) -> None:
+        """Waits for a sent group to have landed and writes its files; ``stage`` receives the seconds of either."""
+        slot, landed, paths = item
+        t0 = timeit.default_timer()
+        landed.synchronize()
+        t1 = timeit.default_timer()
+        n, cap = slot.n, slot.cap
+        lengths = slot.host[n * cap:].view(torch.int32).tolist()
+        data = slot.host.numpy()
+        self.write(paths, [data[k * cap:k * cap + lengths[k]].data for k in range(n)])
+        if stage is not None:
+            stage['wait'] += t1 - t0
+            stage['write'] += timeit.default_timer() - t1
+
+
+def _forward_logits(net, inputs: torch.Tensor, forward_batch: int) -> torch.Tensor:
+    """The fused logits of a batch, fp32 [n,1,H,W], forwarded ``forward_batch`` frames a call."""
+    n = int(inputs.shape[0])
+    if n <= forward_batch:
+        return net.forward(inputs)[-1].detach().float().contiguous()
+    return torch.cat([net.forward(inputs[k:k + forward_batch])[-1].detach().float() for k in range(0, n, forward_batch)])
+
+
+def _check_png_huffman(who: str, png_huffman: str) -> None:
+    from util import png_layout
+    if png_huffman not in png_layout.HUFFMAN_MODES:
+        raise ValueError('{}: png_huffman must be one of {}, got {!r}'.format(who, png_layout.HUFFMAN_MODES, png_huffman))
+
+
+def _check_batching(who: str, group: int, forward_batch: int) -> None:
+    if group < 1 or forward_batch < 1:
+        raise ValueError('{}: group and forward_batch must be at least 1, got {} and {}'.format(who, group, forward_batch))
 
 
 def test_scored(net_provider, data_loader, save_dir: Path, annotations: Callable, write_png: bool = True,
@@ -130,60 +271,33 @@ def test_scored(net_provider, data_loader, save_dir: Path, annotations: Callable
     from PIL import Image
     log.info('Testing Network (scored)')
     net = net_provider.network
-    n_frames = len(data_loader.dataset)
-    fnames, seqs, scored = [], [], []
-    counts_dev, counts_host, radius = None, np.zeros((n_frames, 6), dtype=np.int64), None
+    frames = _Frames(data_loader, save_dir)
+    counts, radius = _Counters(frames.n_frames, 6), None
     time_all_start = timeit.default_timer()
     with torch.no_grad():
         for minibatch in data_loader:
             inputs, = gpu_handler.cast_cuda_if_possible([minibatch['image']])
             logits = net.forward(inputs)[-1].detach().float().contiguous()
             n, h, w = int(logits.shape[0]), int(logits.shape[2]), int(logits.shape[3])
-            first = len(fnames)
-            if first + n > n_frames:
-                raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
             radius = davis_measures.default_radius(h, w)
-            gt = np.zeros((n, h, w), dtype=np.uint8)
-            for index in range(n):
-                seq, fname = minibatch['seq_name'][index], minibatch['fname'][index]
-                ann = _frame_annotation(annotations, seq, fname, h, w)
-                if ann is not None:
-                    gt[index] = ann
-                seqs.append(seq)
-                fnames.append(fname)
-                scored.append(ann is not None)
+            first, gt, paths = frames.add([minibatch], h, w, annotations)
             if logits.is_cuda:
                 from fosvos_hip import ops
-                if counts_dev is None:
-                    counts_dev = torch.zeros((n_frames, 6), dtype=torch.int32, device=logits.device)
-                ops.jf_counts(logits, torch.from_numpy(gt).to(logits.device), radius, out=counts_dev[first:first + n])
+                ops.jf_counts(logits, torch.from_numpy(gt).to(logits.device), radius, out=counts.rows(first, n, logits.device))
                 png = ops.prob_bytes(logits).cpu().numpy() if write_png else None
             else:
                 x = logits[:, 0].numpy().astype(np.float64)
                 for index in range(n):
-                    counts_host[first + index] = davis_measures.jf_counts_numpy(x[index] >= 0, gt[index], radius)
+                    counts.host[first + index] = davis_measures.jf_counts_numpy(x[index] >= 0, gt[index], radius)
                 png = np.stack([bytescale(1.0 / (1.0 + np.exp(-x[index]))) for index in range(n)]) if write_png else None
             if write_png:
                 for index in range(n):
-                    save_dir_seq = Path(save_dir) / seqs[first + index]
-                    save_dir_seq.mkdir(parents=True, exist_ok=True)
-                    Image.fromarray(png[index], mode='L').save(str(save_dir_seq / '{0}.png'.format(fnames[first + index])))
-    if counts_dev is not None:
-        counts_host = counts_dev.cpu().numpy().astype(np.int64)
+                    paths[index].parent.mkdir(parents=True, exist_ok=True)
+                    Image.fromarray(png[index], mode='L').save(str(paths[index]))
+    counts_host = counts.read(len(frames))
     time_for_all = timeit.default_timer() - time_all_start
-    counts_host = counts_host[:len(fnames)]
-    j, f = davis_measures.jf_from_counts(counts_host) if len(fnames) else (np.zeros(0), np.zeros(0))
-    keep = np.asarray(scored, dtype=bool)
-    j_stats = davis_measures.sequence_statistics(j[keep])
-    f_stats = davis_measures.sequence_statistics(f[keep])
-    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
-             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep],
-             'counts': [[int(v) for v in row] if k else None for row, k in zip(counts_host, keep)],
-             'J': [float(v) if k else None for v, k in zip(j, keep)],
-             'F': [float(v) if k else None for v, k in zip(f, keep)],
-             'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
-             'seconds': time_for_all}
-    log.info('Test {0}: {1} images, {2} scored, total test time {3} sec'.format(seq_name, len(fnames), int(keep.sum()),
+    score = _sequence_score(frames, counts_host, radius, time_for_all, seq_name)
+    log.info('Test {0}: {1} images, {2} scored, total test time {3} sec'.format(seq_name, len(frames), sum(frames.scored),
                                                                                time_for_all))
     last_score.clear()
     last_score.update(score)
@@ -231,10 +345,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     ``clean_seed`` (uint8 or bool [H,W], non-zero = object; None: not gated).  The score dict then holds the options under
     'clean'."""
     from util import png_layout
-    if png_huffman not in png_layout.HUFFMAN_MODES:
-        raise ValueError('test_fast: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
-    if group < 1 or forward_batch < 1:
-        raise ValueError('test_fast: group and forward_batch must be at least 1, got {} and {}'.format(group, forward_batch))
+    _check_png_huffman('test_fast', png_huffman)
+    _check_batching('test_fast', group, forward_batch)
     if clean is None and clean_seed is not None:
         raise ValueError('test_fast: clean_seed is the first seed of clean=CleanOptions(temporal_radius=...)')
     if clean is not None:
@@ -254,33 +366,12 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     kept_dev = {}            # (n, h, w) -> the group's kept masks
     log.info('Testing Network (fast)')
     net = net_provider.network
-    n_frames = len(data_loader.dataset)
-    fnames, seqs, scored = [], [], []
-    counts_dev, counts_host, radius = None, np.zeros((n_frames, 6), dtype=np.int64), None
-    stores = {}      # (slot, n, h, w) -> (device bytes, host pinned bytes): two slots, a group's files are written one group later
-    pending = None   # (host bytes, n, capacity, copy-landed event, paths) of the group whose files are not written yet
+    frames = _Frames(data_loader, save_dir)
+    counts, radius = _Counters(frames.n_frames, 6), None
+    files = _FileSlots()
+    pending = None   # the sent group whose files are not written yet
     stage = {'load': 0.0, 'issue': 0.0, 'wait': 0.0, 'write': 0.0}
-    group_sizes, png_bytes = [], 0
-
-    def write_files(paths, blobs):
-        for path, blob in zip(paths, blobs):
-            path.parent.mkdir(parents=True, exist_ok=True)
-            with open(str(path), 'wb') as fh:
-                fh.write(blob)
-
-    def retire(item):
-        nonlocal png_bytes
-        host, n, cap, landed, paths = item
-        t0 = timeit.default_timer()
-        landed.synchronize()
-        t1 = timeit.default_timer()
-        lengths = host[n * cap:n * cap + 4 * n].view(torch.int32).tolist()
-        data = host.numpy()
-        write_files(paths, [data[k * cap:k * cap + lengths[k]].data for k in range(n)])
-        png_bytes += sum(lengths)
-        stage['wait'] += t1 - t0
-        stage['write'] += timeit.default_timer() - t1
-
+    group_sizes = []
     time_all_start = timeit.default_timer()
     with torch.no_grad():
         groups = iter(_frame_groups(data_loader, group))
@@ -294,27 +385,11 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
             images = minibatches[0]['image'] if len(minibatches) == 1 else torch.cat([m['image'] for m in minibatches])
             inputs, = gpu_handler.cast_cuda_if_possible([images])
             n = int(inputs.shape[0])
-            if n <= forward_batch:
-                logits = net.forward(inputs)[-1].detach().float().contiguous()
-            else:
-                logits = torch.cat([net.forward(inputs[k:k + forward_batch])[-1].detach().float()
-                                    for k in range(0, n, forward_batch)])
+            logits = _forward_logits(net, inputs, forward_batch)
             h, w = int(logits.shape[2]), int(logits.shape[3])
-            first = len(fnames)
-            if first + n > n_frames:
-                raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
+            first, gt, paths = frames.add(minibatches, h, w, annotations)
             group_sizes.append(n)
             radius = davis_measures.default_radius(h, w)
-            gt = np.zeros((n, h, w), dtype=np.uint8) if annotations is not None else None
-            for minibatch in minibatches:
-                for seq, fname in zip(minibatch['seq_name'], minibatch['fname']):
-                    ann = _frame_annotation(annotations, seq, fname, h, w) if annotations is not None else None
-                    if ann is not None:
-                        gt[len(fnames) - first] = ann
-                    seqs.append(seq)
-                    fnames.append(fname)
-                    scored.append(ann is not None)
-            paths = [Path(save_dir) / seqs[k] / '{0}.png'.format(fnames[k]) for k in range(first, first + n)]
             if clean is not None and seed_host is not None and seed_host.shape != (h, w):
                 if first == 0:
                     raise ValueError('test_fast: clean_seed is {}, the logits are {}'.format(seed_host.shape, (h, w)))
@@ -339,25 +414,15 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                     else:
                         ops.clean_components(logits, None, 0, clean.min_area, clean.largest, fill=clean.fill, out=logits)
                 if annotations is not None:
-                    if counts_dev is None:
-                        counts_dev = torch.zeros((n_frames, 6), dtype=torch.int32, device=logits.device)
-                    ops.jf_counts(logits, torch.from_numpy(gt).to(logits.device), radius, out=counts_dev[first:first + n])
-                cap = ops.png_capacity(h, w)
-                cap += -cap % 4  # the lengths sit behind the n file slots, in the same buffer: one copy brings both
-                key = (len(group_sizes) % 2, n, h, w)
-                if key not in stores:
-                    stores[key] = (torch.empty(n * cap + 4 * n, dtype=torch.uint8, device=logits.device),
-                                   torch.empty(n * cap + 4 * n, dtype=torch.uint8).pin_memory())
-                dev_store, host_store = stores[key]
-                ops.png_encode(ops.prob_bytes(logits), out=dev_store[:n * cap].view(n, cap),
-                               lengths=dev_store[n * cap:].view(torch.int32), huffman=png_huffman)
-                host_store.copy_(dev_store, non_blocking=True)
-                landed = torch.cuda.Event()
-                landed.record()
+                    ops.jf_counts(logits, torch.from_numpy(gt).to(logits.device), radius,
+                                  out=counts.rows(first, n, logits.device))
+                slot = files.take(n, h, w, ops.png_capacity(h, w), logits.device)
+                ops.png_encode(ops.prob_bytes(logits), out=slot.files, lengths=slot.lengths, huffman=png_huffman)
+                sent = slot.send(paths)
                 stage['issue'] += timeit.default_timer() - t0
                 if pending is not None:
-                    retire(pending)  # the previous group's files, while the device works on this group
-                pending = (host_store, n, cap, landed, paths)
+                    files.retire(pending, stage)  # the previous group's files, while the device works on this group
+                pending = sent
             else:
                 x = logits[:, 0].numpy()
                 if clean is not None:
@@ -371,42 +436,26 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                 blobs = []
                 for index in range(n):
                     if annotations is not None:
-                        counts_host[first + index] = davis_measures.jf_counts_numpy(x[index] >= 0, gt[index], radius)
+                        counts.host[first + index] = davis_measures.jf_counts_numpy(x[index] >= 0, gt[index], radius)
                     blobs.append(png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x[index]))), huffman=png_huffman))
                 stage['issue'] += timeit.default_timer() - t0
                 t0 = timeit.default_timer()
-                write_files(paths, blobs)
-                png_bytes += sum(len(b) for b in blobs)
+                files.write(paths, blobs)
                 stage['write'] += timeit.default_timer() - t0
         if pending is not None:
-            retire(pending)
-    if counts_dev is not None:
-        counts_host = counts_dev.cpu().numpy().astype(np.int64)
+            files.retire(pending, stage)
+    counts_host = counts.read(len(frames))
     time_for_all = timeit.default_timer() - time_all_start
+    cleaned = {'clean': clean.as_dict()} if clean is not None else {}
     last_fast.clear()
-    last_fast.update(n_frames=len(fnames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
+    last_fast.update(n_frames=len(frames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
                      seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],
-                     seconds_write=stage['write'], png_bytes=png_bytes, png_huffman=png_huffman)
-    if clean is not None:
-        last_fast['clean'] = clean.as_dict()
-    log.info('Test {0}: {1} images in {2} groups, total test time {3} sec'.format(seq_name, len(fnames), len(group_sizes),
+                     seconds_write=stage['write'], png_bytes=files.png_bytes, png_huffman=png_huffman, **cleaned)
+    log.info('Test {0}: {1} images in {2} groups, total test time {3} sec'.format(seq_name, len(frames), len(group_sizes),
                                                                                  time_for_all))
     if annotations is None:
         return None
-    counts_host = counts_host[:len(fnames)]
-    j, f = davis_measures.jf_from_counts(counts_host) if len(fnames) else (np.zeros(0), np.zeros(0))
-    keep = np.asarray(scored, dtype=bool)
-    j_stats = davis_measures.sequence_statistics(j[keep])
-    f_stats = davis_measures.sequence_statistics(f[keep])
-    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
-             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep],
-             'counts': [[int(v) for v in row] if k else None for row, k in zip(counts_host, keep)],
-             'J': [float(v) if k else None for v, k in zip(j, keep)],
-             'F': [float(v) if k else None for v, k in zip(f, keep)],
-             'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
-             'seconds': time_for_all}
-    if clean is not None:
-        score['clean'] = clean.as_dict()
+    score = _sequence_score(frames, counts_host, radius, time_for_all, seq_name, **cleaned)
     last_score.clear()
     last_score.update(score)
     return score
@@ -480,8 +529,7 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
     from util import online_adapt, png_layout
     if not isinstance(adapt, AdaptOptions):
         raise ValueError('test_adaptive: adapt must be a fosvos_hip.options.AdaptOptions, got {!r}'.format(adapt))
-    if png_huffman not in png_layout.HUFFMAN_MODES:
-        raise ValueError('test_adaptive: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
+    _check_png_huffman('test_adaptive', png_huffman)
     if trace is not None and not isinstance(trace, list):
         raise ValueError('test_adaptive: trace must be a list or None')
     first_image, first_gt = _first_sample_tensors(first_sample)
@@ -489,29 +537,14 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
     net = net_provider.network
     optimizer = net_provider.get_optimizer(learning_rate=adapt.learning_rate) if adapt.steps > 0 else None
     pos_logit = adapt.pos_logit
-    n_frames = len(data_loader.dataset)
-    fnames, seqs, scored = [], [], []
-    counts_dev, counts_host, radius = None, np.zeros((n_frames, 6), dtype=np.int64), None
-    adapt_dev, adapt_host = None, np.zeros((n_frames, 3), dtype=np.int64)
-    stores = {}      # (slot, h, w) -> (device bytes, host pinned bytes): two slots, a frame's file is written one frame later
-    pending = None   # (host bytes, capacity, copy-landed event, path) of the frame whose file is not written yet
+    frames = _Frames(data_loader, save_dir)
+    counts, radius = _Counters(frames.n_frames, 6), None
+    adapt_counts = _Counters(frames.n_frames, 3)
+    files = _FileSlots()
+    pending = None   # the sent frame whose file is not written yet
     buffers = {}     # (h, w) -> (label, void) of the device labelling
     on_device = {}   # the first frame, its labels and the pass's constants on the logits' device, made at the first frame
     last_mask = None
-    png_bytes = 0
-
-    def write_file(path, blob):
-        path.parent.mkdir(parents=True, exist_ok=True)
-        with open(str(path), 'wb') as fh:
-            fh.write(blob)
-
-    def retire(item):
-        nonlocal png_bytes
-        host, cap, landed, path = item
-        landed.synchronize()
-        length = int(host[cap:cap + 4].view(torch.int32)[0])
-        write_file(path, host.numpy()[:length].data)
-        png_bytes += length
 
     def train_steps(x, label, void):
         """Step 3 on the device."""
@@ -541,19 +574,11 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
         if int(inputs.shape[0]) != 1:
             raise ValueError('test_adaptive: frames come one at a time (the chain of masks and steps is sequential); the '
                              'loader yields batches of {}'.format(int(inputs.shape[0])))
-        first = len(fnames)
-        if first + 1 > n_frames:
-            raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
         with torch.no_grad():
             logits0 = net.forward(inputs)[-1].detach().float().contiguous()
         h, w = int(logits0.shape[2]), int(logits0.shape[3])
         radius = davis_measures.default_radius(h, w)
-        seq, fname = minibatch['seq_name'][0], minibatch['fname'][0]
-        ann = _frame_annotation(annotations, seq, fname, h, w) if annotations is not None else None
-        seqs.append(seq)
-        fnames.append(fname)
-        scored.append(ann is not None)
-        path = Path(save_dir) / seq / '{0}.png'.format(fname)
+        first, gt, paths = frames.add([minibatch], h, w, annotations)
         if first == 0 and tuple(first_gt.shape[2:]) != (h, w):
             raise ValueError('test_adaptive: first_sample is {}, the logits are {}'.format(tuple(first_gt.shape[2:]), (h, w)))
         if logits0.is_cuda:
@@ -564,7 +589,6 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
                 on_device['weights'] = torch.tensor([adapt.first_weight, adapt.frame_weight], dtype=torch.float32,
                                                     device=device)
                 on_device['no_void'] = torch.zeros((1, 1, h, w), dtype=torch.uint8, device=device)
-                adapt_dev = torch.zeros((n_frames, 3), dtype=torch.int32, device=device)
                 last_mask = (on_device['gt'][:, 0] >= 0.5).to(torch.uint8)
             if tuple(last_mask.shape) != (1, h, w):
                 raise ValueError('test_adaptive: the frames changed their size from {} to {}'.format(
@@ -574,7 +598,7 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
                                    torch.empty((1, 1, h, w), dtype=torch.uint8, device=device))
             label, void = buffers[(h, w)]
             ops.adapt_labels(logits0, last_mask, pos_logit, adapt.neg_distance, adapt.erode, label=label, void=void,
-                             counts=adapt_dev[first:first + 1])
+                             counts=adapt_counts.rows(first, 1, device))
             if adapt.steps > 0:
                 train_steps(inputs, label, void)
                 with torch.no_grad():
@@ -586,34 +610,22 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
                               'void': void.clone(), 'logits1': logits1.clone()})
             with torch.no_grad():
                 if annotations is not None:
-                    if counts_dev is None:
-                        counts_dev = torch.zeros((n_frames, 6), dtype=torch.int32, device=device)
-                    gt = ann[None] if ann is not None else np.zeros((1, h, w), dtype=np.uint8)
-                    ops.jf_counts(logits1, torch.from_numpy(gt).to(device), radius, out=counts_dev[first:first + 1])
-                cap = ops.png_capacity(h, w)
-                cap += -cap % 4  # the length sits behind the file slot, in the same buffer: one copy brings both
-                key = (first % 2, h, w)
-                if key not in stores:
-                    stores[key] = (torch.empty(cap + 4, dtype=torch.uint8, device=device),
-                                   torch.empty(cap + 4, dtype=torch.uint8).pin_memory())
-                dev_store, host_store = stores[key]
-                ops.png_encode(ops.prob_bytes(logits1), out=dev_store[:cap].view(1, cap),
-                               lengths=dev_store[cap:].view(torch.int32), huffman=png_huffman)
-                host_store.copy_(dev_store, non_blocking=True)
-                landed = torch.cuda.Event()
-                landed.record()
+                    ops.jf_counts(logits1, torch.from_numpy(gt).to(device), radius, out=counts.rows(first, 1, device))
+                slot = files.take(1, h, w, ops.png_capacity(h, w), device)
+                ops.png_encode(ops.prob_bytes(logits1), out=slot.files, lengths=slot.lengths, huffman=png_huffman)
+                sent = slot.send(paths)
                 last_mask = (logits1[:, 0] >= 0).to(torch.uint8)
             if pending is not None:
-                retire(pending)  # the previous frame's file, while the device works on this frame
-            pending = (host_store, cap, landed, path)
+                files.retire(pending)  # the previous frame's file, while the device works on this frame
+            pending = sent
         else:
             if last_mask is None:
                 last_mask = (first_gt[0, 0].numpy() >= 0.5).astype(np.uint8)
             if last_mask.shape != (h, w):
                 raise ValueError('test_adaptive: the frames changed their size from {} to {}'.format(last_mask.shape, (h, w)))
             x0 = np.ascontiguousarray(logits0[0, 0].numpy(), dtype=np.float32)
-            label, void, adapt_host[first] = online_adapt.adapt_labels(x0, last_mask, pos_logit, adapt.neg_distance,
-                                                                       adapt.erode)
+            label, void, adapt_counts.host[first] = online_adapt.adapt_labels(x0, last_mask, pos_logit, adapt.neg_distance,
+                                                                              adapt.erode)
             if adapt.steps > 0:
                 train_steps_host(inputs, label, void)
                 with torch.no_grad():
@@ -625,52 +637,26 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
                               'label': torch.from_numpy(label.copy())[None, None],
                               'void': torch.from_numpy(void.copy())[None, None], 'logits1': logits1.clone()})
             x1 = logits1[0, 0].numpy().astype(np.float64)
-            if ann is not None:
-                counts_host[first] = davis_measures.jf_counts_numpy(x1 >= 0, ann, radius)
-            blob = png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x1))), huffman=png_huffman)
-            write_file(path, blob)
-            png_bytes += len(blob)
+            if frames.scored[first]:
+                counts.host[first] = davis_measures.jf_counts_numpy(x1 >= 0, gt[0], radius)
+            files.write(paths, [png_layout.encode(bytescale(1.0 / (1.0 + np.exp(-x1))), huffman=png_huffman)])
             last_mask = (logits1[0, 0].numpy() >= 0).astype(np.uint8)
     if pending is not None:
-        retire(pending)
-    if counts_dev is not None:
-        counts_host = counts_dev.cpu().numpy().astype(np.int64)
-    if adapt_dev is not None:
-        adapt_host = adapt_dev.cpu().numpy().astype(np.int64)
+        files.retire(pending)
+    counts_host, adapt_host = counts.read(len(frames)), adapt_counts.read(len(frames))
     time_for_all = timeit.default_timer() - time_all_start
-    adapt_report = dict(adapt.as_dict(), counts=[[int(v) for v in row] for row in adapt_host[:len(fnames)]])
+    adapt_report = dict(adapt.as_dict(), counts=[[int(v) for v in row] for row in adapt_host])
     last_fast.clear()
-    last_fast.update(n_frames=len(fnames), n_groups=len(fnames), group_sizes=[1] * len(fnames), seconds=time_for_all,
-                     png_bytes=png_bytes, png_huffman=png_huffman, adapt=adapt_report)
-    log.info('Test {0}: {1} images adapted with {2} steps each, total test time {3} sec'.format(seq_name, len(fnames),
+    last_fast.update(n_frames=len(frames), n_groups=len(frames), group_sizes=[1] * len(frames), seconds=time_for_all,
+                     png_bytes=files.png_bytes, png_huffman=png_huffman, adapt=adapt_report)
+    log.info('Test {0}: {1} images adapted with {2} steps each, total test time {3} sec'.format(seq_name, len(frames),
                                                                                               adapt.steps, time_for_all))
     if annotations is None:
         return None
-    counts_host = counts_host[:len(fnames)]
-    j, f = davis_measures.jf_from_counts(counts_host) if len(fnames) else (np.zeros(0), np.zeros(0))
-    keep = np.asarray(scored, dtype=bool)
-    j_stats = davis_measures.sequence_statistics(j[keep])
-    f_stats = davis_measures.sequence_statistics(f[keep])
-    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
-             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep],
-             'counts': [[int(v) for v in row] if k else None for row, k in zip(counts_host, keep)],
-             'J': [float(v) if k else None for v, k in zip(j, keep)],
-             'F': [float(v) if k else None for v, k in zip(f, keep)],
-             'J_stats': j_stats, 'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2,
-             'seconds': time_for_all, 'adapt': adapt_report}
+    score = _sequence_score(frames, counts_host, radius, time_for_all, seq_name, adapt=adapt_report)
     last_score.clear()
     last_score.update(score)
     return score
-
-
-def _frame_ids(annotations: Callable, seq: str, fname: str, h: int, w: int) -> Optional[np.ndarray]:
-    ann = annotations(seq, fname)
-    if ann is None:
-        return None
-    ann = np.asarray(ann)
-    if ann.shape != (h, w):
-        raise ValueError('annotation of {}/{} is {}, the logits are {}'.format(seq, fname, ann.shape, (h, w)))
-    return ann.astype(np.uint8)
 
 
 def test_objects(net_providers, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
@@ -691,67 +677,30 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
     {'object_id', 'counts', 'J', 'F', 'J_stats', 'F_stats'} as ``test_scored`` forms them -, 'J_stats' / 'F_stats' - each
     statistic averaged over the objects -, 'J&F' and 'seconds'.  Toolkit parity unpinned, as for the single-object J / F."""
     from util import object_merge, png_layout
-    if png_huffman not in png_layout.HUFFMAN_MODES:
-        raise ValueError('test_objects: png_huffman must be one of {}, got {!r}'.format(png_layout.HUFFMAN_MODES, png_huffman))
-    if group < 1 or forward_batch < 1:
-        raise ValueError('test_objects: group and forward_batch must be at least 1, got {} and {}'.format(group, forward_batch))
+    _check_png_huffman('test_objects', png_huffman)
+    _check_batching('test_objects', group, forward_batch)
     nets = [p.network for p in net_providers]
     n_obj = len(nets)
     if not 1 <= n_obj <= object_merge.MAX_OBJECTS:
         raise ValueError('test_objects: {} nets, outside [1, {}]'.format(n_obj, object_merge.MAX_OBJECTS))
     log.info('Testing Network ({} objects)'.format(n_obj))
-    n_frames = len(data_loader.dataset)
-    fnames, seqs, scored = [], [], []
-    counts_dev, counts_host, radius = None, np.zeros((n_frames, n_obj, 6), dtype=np.int64), None
+    frames = _Frames(data_loader, save_dir)
+    counts, radius = _Counters(frames.n_frames, n_obj, 6), None
     palette_dev, palette_host = None, (None if palette is None else np.asarray(palette, dtype=np.uint8))
-    stores = {}      # (slot, n, h, w) -> (device bytes, host pinned bytes)
-    pending = None   # (host bytes, n, capacity, copy-landed event, paths) of the group whose files are not written yet
-    group_sizes, png_bytes = [], 0
-
-    def write_files(paths, blobs):
-        for path, blob in zip(paths, blobs):
-            path.parent.mkdir(parents=True, exist_ok=True)
-            with open(str(path), 'wb') as fh:
-                fh.write(blob)
-
-    def retire(item):
-        nonlocal png_bytes
-        host, n, cap, landed, paths = item
-        landed.synchronize()
-        lengths = host[n * cap:n * cap + 4 * n].view(torch.int32).tolist()
-        data = host.numpy()
-        write_files(paths, [data[k * cap:k * cap + lengths[k]].data for k in range(n)])
-        png_bytes += sum(lengths)
-
+    files = _FileSlots()
+    pending = None   # the sent group whose files are not written yet
+    n_groups = 0
     time_all_start = timeit.default_timer()
     with torch.no_grad():
         for minibatches in _frame_groups(data_loader, group):
             images = minibatches[0]['image'] if len(minibatches) == 1 else torch.cat([m['image'] for m in minibatches])
             inputs, = gpu_handler.cast_cuda_if_possible([images])
             n = int(inputs.shape[0])
-            logits = []
-            for net in nets:  # every net forwards the same uploaded batch
-                if n <= forward_batch:
-                    logits.append(net.forward(inputs)[-1].detach().float().contiguous())
-                else:
-                    logits.append(torch.cat([net.forward(inputs[k:k + forward_batch])[-1].detach().float()
-                                             for k in range(0, n, forward_batch)]))
+            logits = [_forward_logits(net, inputs, forward_batch) for net in nets]  # every net forwards the same uploaded batch
             h, w = int(logits[0].shape[2]), int(logits[0].shape[3])
-            first = len(fnames)
-            if first + n > n_frames:
-                raise RuntimeError('the loader yields more frames than its dataset holds ({})'.format(n_frames))
-            group_sizes.append(n)
+            first, gt, paths = frames.add(minibatches, h, w, annotations, ids=True)
+            n_groups += 1
             radius = davis_measures.default_radius(h, w)
-            gt = np.zeros((n, h, w), dtype=np.uint8) if annotations is not None else None
-            for minibatch in minibatches:
-                for seq, fname in zip(minibatch['seq_name'], minibatch['fname']):
-                    ann = _frame_ids(annotations, seq, fname, h, w) if annotations is not None else None
-                    if ann is not None:
-                        gt[len(fnames) - first] = ann
-                    seqs.append(seq)
-                    fnames.append(fname)
-                    scored.append(ann is not None)
-            paths = [Path(save_dir) / seqs[k] / '{0}.png'.format(fnames[k]) for k in range(first, first + n)]
             if logits[0].is_cuda:
                 from fosvos_hip import ops
                 device = logits[0].device
@@ -759,53 +708,37 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
                     palette_dev = torch.from_numpy(palette_host).to(device)
                 labels = ops.merge_objects(logits)
                 if annotations is not None:
-                    if counts_dev is None:
-                        counts_dev = torch.zeros((n_frames, n_obj, 6), dtype=torch.int32, device=device)
                     ops.jf_counts_labels(labels, torch.from_numpy(gt).to(device), n_obj, radius,
-                                         out=counts_dev[first:first + n])
-                cap = ops.png_indexed_capacity(h, w)
-                cap += -cap % 4  # the lengths sit behind the n file slots, in the same buffer: one copy brings both
-                key = (len(group_sizes) % 2, n, h, w)
-                if key not in stores:
-                    stores[key] = (torch.empty(n * cap + 4 * n, dtype=torch.uint8, device=device),
-                                   torch.empty(n * cap + 4 * n, dtype=torch.uint8).pin_memory())
-                dev_store, host_store = stores[key]
-                ops.png_encode_indexed(labels, palette_dev, out=dev_store[:n * cap].view(n, cap),
-                                       lengths=dev_store[n * cap:].view(torch.int32), huffman=png_huffman)
-                host_store.copy_(dev_store, non_blocking=True)
-                landed = torch.cuda.Event()
-                landed.record()
+                                         out=counts.rows(first, n, device))
+                slot = files.take(n, h, w, ops.png_indexed_capacity(h, w), device)
+                ops.png_encode_indexed(labels, palette_dev, out=slot.files, lengths=slot.lengths, huffman=png_huffman)
+                sent = slot.send(paths)
                 if pending is not None:
-                    retire(pending)  # the previous group's files, while the device works on this group
-                pending = (host_store, n, cap, landed, paths)
+                    files.retire(pending)  # the previous group's files, while the device works on this group
+                pending = sent
             else:
                 labels = object_merge.merge_labels([x[:, 0].numpy() for x in logits])
                 blobs = []
                 for index in range(n):
                     if annotations is not None:
-                        counts_host[first + index] = object_merge.jf_counts_labels_numpy(labels[index], gt[index], n_obj,
+                        counts.host[first + index] = object_merge.jf_counts_labels_numpy(labels[index], gt[index], n_obj,
                                                                                          radius)
                     blobs.append(png_layout.encode_indexed(labels[index], palette_host, huffman=png_huffman))
-                write_files(paths, blobs)
-                png_bytes += sum(len(b) for b in blobs)
+                files.write(paths, blobs)
         if pending is not None:
-            retire(pending)
-    if counts_dev is not None:
-        counts_host = counts_dev.cpu().numpy().astype(np.int64)
+            files.retire(pending)
+    counts_host = counts.read(len(frames))
     time_for_all = timeit.default_timer() - time_all_start
     log.info('Test {0}: {1} images of {2} objects in {3} groups, {4} PNG bytes, total test time {5} sec'.format(
-        seq_name, len(fnames), n_obj, len(group_sizes), png_bytes, time_for_all))
+        seq_name, len(frames), n_obj, n_groups, files.png_bytes, time_for_all))
     if annotations is None:
         return None
-    counts_host = counts_host[:len(fnames)]
-    keep = np.asarray(scored, dtype=bool)
+    keep = np.asarray(frames.scored, dtype=bool)
     objects = [object_merge.object_score(counts_host[:, k], keep, k + 1) for k in range(n_obj)]
     j_stats = object_merge.mean_statistics([o['J_stats'] for o in objects])
     f_stats = object_merge.mean_statistics([o['F_stats'] for o in objects])
-    score = {'seq_name': seq_name if seq_name is not None else (seqs[0] if seqs else None),
-             'radius': radius, 'fnames': list(fnames), 'scored': [bool(k) for k in keep], 'n_objects': n_obj,
-             'objects': objects, 'J_stats': j_stats, 'F_stats': f_stats,
-             'J&F': (j_stats['mean'] + f_stats['mean']) / 2, 'seconds': time_for_all}
+    score = {**frames.score_head(seq_name, radius), 'n_objects': n_obj, 'objects': objects, 'J_stats': j_stats,
+             'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2, 'seconds': time_for_all}
     last_score.clear()
     last_score.update(score)
     return score
