@@ -1,0 +1,80 @@
+"""The ranges the kernels take and the scalar checks of the Python face, each stated once.  ``ops``
+keeps its public constant names as aliases of the ranges, ``options`` and ``stream`` check against them; the numpy definitions
+under util/ keep their own copies (they are what the kernels are tested against and stand alone), and
+tests/test_limits_cpu.py pins the two sides equal.
+
+No torch, no numpy and no library load here: importable anywhere.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+# following the object (util/frame_roi.py: MAX_LEVELS, MAX_PAD, MAX_PERMILLE / 1000)
+ROI_MAX_LEVELS = 64
+ROI_MAX_PAD = 4095
+ROI_MAX_MARGIN = 4.0
+# the distance gate and the pseudo-labels (util/online_adapt.MAX_DISTANCE)
+GATE_MAX_DISTANCE = 4095
+GATE_MAX_SIDE = 8192
+# mask cleaning (util/mask_components.MAX_RADIUS); an area is a positive int32
+CLEAN_MAX_RADIUS = 63
+CLEAN_MAX_AREA = (1 << 31) - 1
+FILL_RANGE = (-3.4028234663852886e38, 0.0)  # [lowest finite float32, 0)
+# the guided filter (util/guided_upsample.py: MAX_RADIUS, EPS_RANGE, MAX_CLIP)
+GUIDED_MAX_RADIUS = 8
+GUIDED_EPS_RANGE = (1e-3, 1e9)
+GUIDED_MAX_CLIP = 1e4
+# a scaled call's frames (util/frame_resample.MAX_SIDE), the nets of a sequence (util/object_merge.MAX_OBJECTS)
+MAX_FRAME_SIDE = 8192
+MAX_OBJECTS = 16
+# the boundary tolerance of the F measure, the JPEG encoder
+JF_RADIUS = (1, 63)
+JPEG_QUALITY = (1, 100)
+JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
+
+
+def real_number(v) -> bool:
+    """A finite int or float that is not a bool."""
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+def check_int(who: str, name: str, v, lo: int, hi: Optional[int] = None, expect: Optional[str] = None,
+              integral: bool = False) -> int:
+    """``v`` as an int in ``lo..hi`` (``hi=None``: no upper bound), a bool refused; ``integral`` also takes any number equal
+    to its ``int()`` (90.0, a numpy integer).  ``expect`` words the rule where the default does not say it."""
+    if isinstance(v, bool) or (int(v) != v if integral else not isinstance(v, int)) or v < lo or (hi is not None and v > hi):
+        if expect is None:
+            expect = f"an integer >= {lo}" if hi is None else f"an integer in {lo}..{hi}"
+        raise ValueError(f"{who}: {name} must be {expect}, got {v!r}")
+    return int(v)
+
+
+def check_real(who: str, name: str, v, lo: float, hi: Optional[float] = None, lo_open: bool = False, hi_open: bool = False,
+               expect: Optional[str] = None) -> float:
+    """``v`` as a float: a finite number in the range from ``lo`` to ``hi`` (``hi=None``: no upper bound), either end open
+    or closed."""
+    if not real_number(v) or not (v > lo if lo_open else v >= lo) or not (hi is None or (v < hi if hi_open else v <= hi)):
+        if expect is None:
+            expect = f"a finite number {'>' if lo_open else '>='} {lo:g}" if hi is None else \
+                f"a finite number in {'(' if lo_open else '['}{lo:g}, {hi:g}{')' if hi_open else ']'}"
+        raise ValueError(f"{who}: {name} must be {expect}, got {v!r}")
+    return float(v)
+
+
+def check_pair(who: str, name: str, v, of: str) -> Tuple[int, int]:
+    """``v`` as a pair of positive ints; ``of`` names the two, e.g. '(Hn, Wn)'."""
+    try:
+        a, b = v
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {name} must be a pair {of}, got {v!r}") from None
+    for x in (a, b):
+        if isinstance(x, bool) or not isinstance(x, int) or x <= 0:
+            raise ValueError(f"{who}: {name} must be a pair of positive ints, got {v!r}")
+    return a, b
+
+
+def check_member(who: str, name: str, v, allowed):
+    """``v`` where it is one of ``allowed`` (a tuple, or the keys of a dict)."""
+    if v not in allowed:
+        raise ValueError(f"{who}: {name} must be one of {tuple(allowed)}, got {v!r}")
+    return v

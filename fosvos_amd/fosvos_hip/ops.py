@@ -6,21 +6,25 @@ reference; side maps are fp32 NHWC [N,h,w,16].
 """
 from __future__ import annotations
 
+import ctypes
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import CONV_OUT_F32, CONV_RELU, check, int_array4, lib, ptr_array4
+from . import CONV_OUT_F32, CONV_RELU, check, int_array4, lib, limits, ptr_array4
 
 _BF16 = torch.bfloat16
 _F32 = torch.float32
 
 
-def _need(t: torch.Tensor, dtype, what: str) -> torch.Tensor:
+def _need(t: torch.Tensor, dtype, what: str, dtype_error=TypeError) -> torch.Tensor:
+    """``t`` where it is a contiguous ``dtype`` tensor on the GPU.  A wrong dtype is a TypeError in the ops of the training
+    step and a ValueError (``dtype_error``) in the ops from ``prob_bytes`` down, as each was written."""
     if not t.is_cuda:
         raise RuntimeError(f"{what}: tensor must live on the GPU (the HIP path has no CPU fallback)")
     if t.dtype != dtype:
-        raise TypeError(f"{what}: expected {dtype}, got {t.dtype}")
+        raise dtype_error(f"{what}: expected {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{what}: tensor must be contiguous")
     return t
@@ -107,14 +111,23 @@ def _pe(e0, name: str, flops: float = 0.0, nbytes: float = 0.0) -> None:
     _PROF.records.append((name, float(flops), float(nbytes), e0, e1))
 
 
+def _launch(entry: str, like: torch.Tensor, *args, record=None, flops: float = 0.0, nbytes: float = 0.0) -> None:
+    """The tail of every op: ``fosvos_<entry>(*args, device, stream)`` of ``like``'s device and its current stream, a
+    non-zero return raised under the entry's name, the call between the profiler's events.  ``record`` is the profiler's
+    name for the call where that is not the entry's (several entries share one); False: the op was never profiled."""
+    dev, st = _ctx(like)
+    e0 = None if record is False else _pb()
+    check(getattr(lib(), "fosvos_" + entry)(*args, dev, st), entry)
+    _pe(e0, record or entry, flops, nbytes)
+
+
 # ------------------------------------------------------------------------------------------ layout
 def nchw_to_nhwc_bf16(x: torch.Tensor, c_pad: Optional[int] = None) -> torch.Tensor:
     _need(x, _F32, "nchw_to_nhwc_bf16")
     n, c, h, w = x.shape
     c_pad = _ru(c, 8) if c_pad is None else c_pad
     out = torch.empty((n, h, w, c_pad), dtype=_BF16, device=x.device)
-    dev, st = _ctx(x)
-    check(lib().fosvos_nchw_f32_to_nhwc_bf16(x.data_ptr(), out.data_ptr(), n, c, h, w, c_pad, dev, st), "nchw_f32_to_nhwc_bf16")
+    _launch("nchw_f32_to_nhwc_bf16", x, x.data_ptr(), out.data_ptr(), n, c, h, w, c_pad, record=False)
     return out
 
 
@@ -123,8 +136,7 @@ def nhwc_bf16_to_nchw(x: torch.Tensor, c: Optional[int] = None) -> torch.Tensor:
     n, h, w, c_pad = x.shape
     c = c_pad if c is None else c
     out = torch.empty((n, c, h, w), dtype=_F32, device=x.device)
-    dev, st = _ctx(x)
-    check(lib().fosvos_nhwc_bf16_to_nchw_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, c_pad, dev, st), "nhwc_bf16_to_nchw_f32")
+    _launch("nhwc_bf16_to_nchw_f32", x, x.data_ptr(), out.data_ptr(), n, c, h, w, c_pad, record=False)
     return out
 
 
@@ -132,8 +144,7 @@ def nhwc_f32_to_nchw(x: torch.Tensor) -> torch.Tensor:
     _need(x, _F32, "nhwc_f32_to_nchw")
     n, h, w, c = x.shape
     out = torch.empty((n, c, h, w), dtype=_F32, device=x.device)
-    dev, st = _ctx(x)
-    check(lib().fosvos_nhwc_f32_to_nchw_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, dev, st), "nhwc_f32_to_nchw_f32")
+    _launch("nhwc_f32_to_nchw_f32", x, x.data_ptr(), out.data_ptr(), n, c, h, w, record=False)
     return out
 
 
@@ -141,8 +152,7 @@ def nchw_to_nhwc_f32(x: torch.Tensor) -> torch.Tensor:
     _need(x, _F32, "nchw_to_nhwc_f32")
     n, c, h, w = x.shape
     out = torch.empty((n, h, w, c), dtype=_F32, device=x.device)
-    dev, st = _ctx(x)
-    check(lib().fosvos_nchw_f32_to_nhwc_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, dev, st), "nchw_f32_to_nhwc_f32")
+    _launch("nchw_f32_to_nhwc_f32", x, x.data_ptr(), out.data_ptr(), n, c, h, w, record=False)
     return out
 
 
@@ -156,10 +166,8 @@ def pack_conv3x3_weights(w: torch.Tensor, want_fwd: bool = True, want_dgrad: boo
     L = lib()
     fwd = torch.empty(L.fosvos_packed_weight_elems(co, ci), dtype=_BF16, device=w.device) if want_fwd else None
     dgr = torch.empty(L.fosvos_packed_weight_elems(ci, co), dtype=_BF16, device=w.device) if want_dgrad else None
-    dev, st = _ctx(w)
-    t0 = _pb()
-    check(L.fosvos_pack_conv3x3_weights(w.data_ptr(), co, ci, _p(fwd), _p(dgr), dev, st), "pack_conv3x3_weights")
-    _pe(t0, "pack_weights", 0.0, w.numel() * 4 + 2 * ((fwd.numel() if fwd is not None else 0) + (dgr.numel() if dgr is not None else 0)))
+    _launch("pack_conv3x3_weights", w, w.data_ptr(), co, ci, _p(fwd), _p(dgr), record="pack_weights",
+            nbytes=w.numel() * 4 + 2 * ((fwd.numel() if fwd is not None else 0) + (dgr.numel() if dgr is not None else 0)))
     return fwd, dgr
 
 
@@ -182,10 +190,7 @@ def pack_conv3x3_weights_multi(ws: Sequence[torch.Tensor]):
         arr[i].w, arr[i].w_fwd, arr[i].w_dgrad, arr[i].Co, arr[i].Ci = w.data_ptr(), fwd.data_ptr(), dgr.data_ptr(), co, ci
         out.append((fwd, dgr))
         nbytes += w.numel() * 4 + 2 * (fwd.numel() + dgr.numel())
-    dev, st = _ctx(ws[0])
-    t0 = _pb()
-    check(L.fosvos_pack_conv3x3_weights_multi(arr, len(ws), dev, st), "pack_conv3x3_weights_multi")
-    _pe(t0, "pack_weights", 0.0, nbytes)
+    _launch("pack_conv3x3_weights_multi", ws[0], arr, len(ws), record="pack_weights", nbytes=nbytes)
     return out
 
 
@@ -199,12 +204,9 @@ def conv3x3_first_fwd(frame: torch.Tensor, w: torch.Tensor, b: torch.Tensor, wan
         raise ValueError("conv3x3_first_fwd: expects a 3-channel frame and [Co,3,3,3] weights")
     co = w.shape[0]
     y = torch.empty((n, h, wd, co), dtype=_BF16, device=frame.device)
-    dev, st = _ctx(frame)
-    t0 = _pb()
     bits = torch.empty((n, h, wd, co // 8), dtype=torch.uint8, device=frame.device) if want_bits else None
-    check(lib().fosvos_conv3x3_first_fwd(frame.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), _p(bits), n, h, wd, co,
-                                         dev, st), "conv3x3_first_fwd")
-    _pe(t0, "conv1_1_fwd", 2.0 * n * h * wd * 27 * co, n * h * wd * (12 + 2 * co))
+    _launch("conv3x3_first_fwd", frame, frame.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), _p(bits), n, h, wd, co,
+            record="conv1_1_fwd", flops=2.0 * n * h * wd * 27 * co, nbytes=n * h * wd * (12 + 2 * co))
     return (y, bits) if want_bits else y
 
 
@@ -218,18 +220,14 @@ def conv3x3_first_wgrad(frame: torch.Tensor, dy: torch.Tensor) -> Tuple[torch.Te
     dw = torch.empty((co, 3, 3, 3), dtype=_F32, device=frame.device)
     db = torch.empty((co,), dtype=_F32, device=frame.device)
     ws, wsn = _WS.get(L.fosvos_conv3x3_first_wgrad_workspace_bytes(n, h, wd, co), frame.device)
-    dev, st = _ctx(frame)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_first_wgrad(frame.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr(), n, h, wd, co, ws, wsn,
-                                       dev, st), "conv3x3_first_wgrad")
-    _pe(t0, "conv1_1_wgrad", 2.0 * n * h * wd * 27 * co, n * h * wd * (12 + 2 * co))
+    _launch("conv3x3_first_wgrad", frame, frame.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr(), n, h, wd, co, ws, wsn,
+            record="conv1_1_wgrad", flops=2.0 * n * h * wd * 27 * co, nbytes=n * h * wd * (12 + 2 * co))
     return dw, db
 
 
 def conv3x3_plan(n: int, h: int, w: int, in_ch: int, out_ch: int) -> dict:
     """The igemm instantiation fosvos_conv3x3_dgrad (and the forward forms the persistent kernel does not take) launch for
     this shape (host arithmetic only): {"tile": (tile_h, tile_w, tile_co), "k_splits", "workgroups", "persistent"}."""
-    import ctypes
     from . import Conv3x3PlanInfo
     info = Conv3x3PlanInfo()
     check(lib().fosvos_conv3x3_plan(n, h, w, in_ch, out_ch, ctypes.byref(info)), "conv3x3_plan")
@@ -240,7 +238,6 @@ def conv3x3_plan(n: int, h: int, w: int, in_ch: int, out_ch: int) -> dict:
 def conv3x3_fwd_plan(n: int, h: int, w: int, in_ch: int, out_ch: int, relu: bool = True) -> dict:
     """What fosvos_conv3x3_fwd / _fwd_pool launch for a bf16-output forward conv of this shape: the persistent eight-wave
     kernel k_conv3x3_pp ("persistent": True, 256 workgroups) where its tiles fill the chip, else the igemm instantiation."""
-    import ctypes
     from . import Conv3x3PlanInfo
     info = Conv3x3PlanInfo()
     check(lib().fosvos_conv3x3_fwd_plan(n, h, w, in_ch, out_ch, CONV_RELU if relu else 0, ctypes.byref(info)), "conv3x3_fwd_plan")
@@ -251,7 +248,6 @@ def conv3x3_fwd_plan(n: int, h: int, w: int, in_ch: int, out_ch: int, relu: bool
 def vgg_arena_layout(n: int, h: int, w: int) -> dict:
     """fosvos_vgg_arena_layout as a dict (host arithmetic only): field name -> int, or list of ints for the per-layer arrays
     (byte offsets from the aligned arena base, byte sizes, stage resolutions)."""
-    import ctypes
     from . import VggArenaLayout
     info = VggArenaLayout()
     check(lib().fosvos_vgg_arena_layout(n, h, w, ctypes.byref(info)), "vgg_arena_layout")
@@ -264,7 +260,6 @@ def vgg_arena_layout(n: int, h: int, w: int) -> dict:
 
 def conv3x3_first_plan(n: int, h: int, w: int) -> Tuple[int, int]:
     """(tiles, persistent workgroups) of fosvos_conv3x3_first_fwd."""
-    import ctypes
     tiles, wgs = ctypes.c_int(), ctypes.c_int()
     check(lib().fosvos_conv3x3_first_plan(n, h, w, ctypes.byref(tiles), ctypes.byref(wgs)), "conv3x3_first_plan")
     return tiles.value, wgs.value
@@ -286,12 +281,8 @@ def conv3x3_fwd(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Te
     y = torch.empty((n, h, wd, co), dtype=_F32 if out_f32 else _BF16, device=x.device)
     flags = (CONV_RELU if relu else 0) | (CONV_OUT_F32 if out_f32 else 0)
     ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, ci, co), x.device)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_fwd(x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), n, h, wd, ci, co, flags, ws, wsn,
-                               dev, st), "conv3x3_fwd")
-    _pe(t0, "conv3x3_fwd", 2.0 * n * h * wd * 9 * ci * co,
-        n * h * wd * (2 * cx + (4 if out_f32 else 2) * co) + 2 * 9 * ci * co)
+    _launch("conv3x3_fwd", x, x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), n, h, wd, ci, co, flags, ws, wsn,
+            flops=2.0 * n * h * wd * 9 * ci * co, nbytes=n * h * wd * (2 * cx + (4 if out_f32 else 2) * co) + 2 * 9 * ci * co)
     return y
 
 
@@ -310,11 +301,9 @@ def conv3x3_fwd_pool(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[tor
     y = torch.empty((n, h, wd, co), dtype=_BF16, device=x.device)
     yp = torch.empty((n, (h + 1) // 2, (wd + 1) // 2, co), dtype=_BF16, device=x.device)
     ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, ci, co), x.device)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_fwd_pool(x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), yp.data_ptr(), n, h, wd, ci,
-                                    co, CONV_RELU if relu else 0, ws, wsn, dev, st), "conv3x3_fwd_pool")
-    _pe(t0, "conv3x3_fwd", 2.0 * n * h * wd * 9 * ci * co, n * h * wd * (2 * cx + 2 * co) + 2 * 9 * ci * co + yp.numel() * 2)
+    _launch("conv3x3_fwd_pool", x, x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), yp.data_ptr(), n, h, wd, ci, co,
+            CONV_RELU if relu else 0, ws, wsn, record="conv3x3_fwd", flops=2.0 * n * h * wd * 9 * ci * co,
+            nbytes=n * h * wd * (2 * cx + 2 * co) + 2 * 9 * ci * co + yp.numel() * 2)
     return y, yp
 
 
@@ -349,11 +338,9 @@ def conv3x3_fwd_pool_codes(x: torch.Tensor, w_packed: torch.Tensor, bias: Option
             raise ValueError("conv3x3_fwd_pool_codes: codes must be a contiguous int32 tensor on the GPU")
         if yp.numel() != n * ((h + 1) // 2) * ((wd + 1) // 2) * co or codes.numel() * 4 != L.fosvos_conv3x3_pool_codes_bytes(n, h, wd, co):
             raise ValueError("conv3x3_fwd_pool_codes: output sizes")
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_fwd_pool_codes(x.data_ptr(), w_packed.data_ptr(), _p(bias), yp.data_ptr(), codes.data_ptr(), n, h,
-                                          wd, ci, co, CONV_RELU, dev, st), "conv3x3_fwd_pool_codes")
-    _pe(t0, "conv3x3_fwd", 2.0 * n * h * wd * 9 * ci * co, n * h * wd * 2 * cx + 2 * 9 * ci * co + yp.numel() * 2 + codes.numel() * 4)
+    _launch("conv3x3_fwd_pool_codes", x, x.data_ptr(), w_packed.data_ptr(), _p(bias), yp.data_ptr(), codes.data_ptr(), n, h, wd,
+            ci, co, CONV_RELU, record="conv3x3_fwd", flops=2.0 * n * h * wd * 9 * ci * co,
+            nbytes=n * h * wd * 2 * cx + 2 * 9 * ci * co + yp.numel() * 2 + codes.numel() * 4)
     return yp, codes
 
 
@@ -377,19 +364,15 @@ def conv3x3_dgrad(dy: torch.Tensor, w_dgrad_packed: torch.Tensor, ci: int, co: i
                 raise ValueError(f"conv3x3_dgrad: {nm} shape {tuple(t.shape)} != {shape}")
     dx = out if out is not None else torch.empty(shape, dtype=_BF16, device=dy.device)
     ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, co, ci), dy.device)
-    dev, st = _ctx(dy)
-    t0 = _pb()
     if relu_bits is not None:
         if relu_src is not None or relu_bits.dtype != torch.uint8 or tuple(relu_bits.shape) != (n, h, wd, ci // 8) or \
                 not relu_bits.is_contiguous() or not relu_bits.is_cuda:
             raise ValueError("conv3x3_dgrad: relu_bits must be a contiguous uint8 [N,H,W,Ci/8] GPU tensor, given instead of relu_src")
-        check(L.fosvos_conv3x3_dgrad_bits(dy.data_ptr(), w_dgrad_packed.data_ptr(), relu_bits.data_ptr(), _p(addend),
-                                          dx.data_ptr(), n, h, wd, ci, co, ws, wsn, dev, st), "conv3x3_dgrad_bits")
-    else:
-        check(L.fosvos_conv3x3_dgrad(dy.data_ptr(), w_dgrad_packed.data_ptr(), _p(relu_src), _p(addend), dx.data_ptr(), n, h, wd,
-                                     ci, co, ws, wsn, dev, st), "conv3x3_dgrad")
-    _pe(t0, "conv3x3_dgrad", 2.0 * n * h * wd * 9 * ci * co,
-        n * h * wd * 2 * (cy + ci * (1 + (relu_src is not None) + (addend is not None))) + 2 * 9 * ci * co)
+    mask = relu_src if relu_bits is None else relu_bits
+    _launch("conv3x3_dgrad" if relu_bits is None else "conv3x3_dgrad_bits", dy, dy.data_ptr(), w_dgrad_packed.data_ptr(),
+            _p(mask), _p(addend), dx.data_ptr(), n, h, wd, ci, co, ws, wsn, record="conv3x3_dgrad",
+            flops=2.0 * n * h * wd * 9 * ci * co,
+            nbytes=n * h * wd * 2 * (cy + ci * (1 + (relu_src is not None) + (addend is not None))) + 2 * 9 * ci * co)
     return dx
 
 
@@ -415,11 +398,9 @@ def conv3x3_dgrad_unpool(dy: torch.Tensor, w_dgrad_packed: torch.Tensor, ci: int
             raise ValueError("conv3x3_dgrad_unpool: out must have x's shape and must not alias it")
     dx = out if out is not None else torch.empty((n, h, wd, ci), dtype=_BF16, device=dy.device)
     ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, co, ci), dy.device)
-    dev, st = _ctx(dy)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_dgrad_unpool(dy.data_ptr(), w_dgrad_packed.data_ptr(), x.data_ptr(), d_pooled.data_ptr(), dx.data_ptr(),
-                                        n, h, wd, ci, co, ws, wsn, dev, st), "conv3x3_dgrad_unpool")
-    _pe(t0, "conv3x3_dgrad_unpool", 2.0 * n * h * wd * 9 * ci * co, n * h * wd * 2 * (cy + 2 * ci + ci // 4) + 2 * 9 * ci * co)
+    _launch("conv3x3_dgrad_unpool", dy, dy.data_ptr(), w_dgrad_packed.data_ptr(), x.data_ptr(), d_pooled.data_ptr(), dx.data_ptr(),
+            n, h, wd, ci, co, ws, wsn, flops=2.0 * n * h * wd * 9 * ci * co,
+            nbytes=n * h * wd * 2 * (cy + 2 * ci + ci // 4) + 2 * 9 * ci * co)
     return dx
 
 
@@ -440,17 +421,12 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, ci: int, co: int, with_bias
         db = torch.empty((co,), dtype=_F32, device=x.device)
     _need(dw, _F32, "conv3x3_wgrad dw")
     ws, wsn = _WS.get(L.fosvos_conv3x3_wgrad_workspace_bytes(n, h, wd, ci, co), x.device)
-    dev, st = _ctx(x)
     # the two halves of fosvos_conv3x3_wgrad, timed apart: the MFMA kernel, then the slab reduction (memory-bound; the
     # network call batches the reductions of all layers into two launches)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_wgrad_slabs(x.data_ptr(), dy.data_ptr(), 1 if with_bias else 0, n, h, wd, ci, co, ws, wsn, dev, st),
-          "conv3x3_wgrad_slabs")
-    _pe(t0, "conv3x3_wgrad", 2.0 * n * h * wd * 9 * ci * co, n * h * wd * 2 * (ci + dy.shape[3]))
-    t0 = _pb()
-    check(L.fosvos_conv3x3_wgrad_reduce(dw.data_ptr(), _p(db) if with_bias else None, n, h, wd, ci, co,
-                                        1 if accumulate else 0, ws, wsn, dev, st), "conv3x3_wgrad_reduce")
-    _pe(t0, "wgrad_reduce", 0.0, 4 * 9 * ci * co * 3)
+    _launch("conv3x3_wgrad_slabs", x, x.data_ptr(), dy.data_ptr(), 1 if with_bias else 0, n, h, wd, ci, co, ws, wsn,
+            record="conv3x3_wgrad", flops=2.0 * n * h * wd * 9 * ci * co, nbytes=n * h * wd * 2 * (ci + dy.shape[3]))
+    _launch("conv3x3_wgrad_reduce", x, dw.data_ptr(), _p(db) if with_bias else None, n, h, wd, ci, co, 1 if accumulate else 0,
+            ws, wsn, record="wgrad_reduce", nbytes=4 * 9 * ci * co * 3)
     return dw, (db if with_bias else None)
 
 
@@ -462,9 +438,7 @@ def conv3x3_wgrad_one_call(x: torch.Tensor, dy: torch.Tensor, ci: int, co: int, 
     dw = torch.empty((co, ci, 3, 3), dtype=_F32, device=x.device)
     db = torch.empty((co,), dtype=_F32, device=x.device) if with_bias else None
     ws, wsn = _WS.get(L.fosvos_conv3x3_wgrad_workspace_bytes(n, h, wd, ci, co), x.device)
-    dev, st = _ctx(x)
-    check(L.fosvos_conv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _p(db), n, h, wd, ci, co, 0, ws, wsn, dev, st),
-          "conv3x3_wgrad")
+    _launch("conv3x3_wgrad", x, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _p(db), n, h, wd, ci, co, 0, ws, wsn, record=False)
     return dw, db
 
 
@@ -473,10 +447,7 @@ def maxpool_fwd(x: torch.Tensor) -> torch.Tensor:
     _need(x, _BF16, "maxpool_fwd")
     n, h, w, c = x.shape
     y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=_BF16, device=x.device)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(lib().fosvos_maxpool2x2_ceil_fwd(x.data_ptr(), y.data_ptr(), n, h, w, c, dev, st), "maxpool2x2_ceil_fwd")
-    _pe(t0, "maxpool_fwd", 0.0, 2 * (x.numel() + y.numel()))
+    _launch("maxpool2x2_ceil_fwd", x, x.data_ptr(), y.data_ptr(), n, h, w, c, record="maxpool_fwd", nbytes=2 * (x.numel() + y.numel()))
     return y
 
 
@@ -486,11 +457,8 @@ def maxpool_bwd(x: torch.Tensor, dy: torch.Tensor, relu_mask: bool = True) -> to
     if tuple(dy.shape) != (n, (h + 1) // 2, (w + 1) // 2, c):
         raise ValueError("maxpool_bwd: dy shape mismatch")
     dx = torch.empty_like(x)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(lib().fosvos_maxpool2x2_ceil_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, 1 if relu_mask else 0,
-                                           dev, st), "maxpool2x2_ceil_bwd")
-    _pe(t0, "maxpool_bwd", 0.0, 2 * (2 * x.numel() + dy.numel()))
+    _launch("maxpool2x2_ceil_bwd", x, x.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, 1 if relu_mask else 0,
+            record="maxpool_bwd", nbytes=2 * (2 * x.numel() + dy.numel()))
     return dx
 
 
@@ -507,11 +475,8 @@ def maxpool_bwd_codes(codes: torch.Tensor, dy: torch.Tensor, h: int, w: int, out
         _need(out, _BF16, "maxpool_bwd_codes out")
         if out.numel() != n * h * w * c:
             raise ValueError("maxpool_bwd_codes: out size")
-    dev, st = _ctx(dy)
-    t0 = _pb()
-    check(lib().fosvos_maxpool2x2_ceil_bwd_codes(codes.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, dev, st),
-          "maxpool2x2_ceil_bwd_codes")
-    _pe(t0, "maxpool_bwd", 0.0, 2 * (dx.numel() + dy.numel()) + 4 * codes.numel())
+    _launch("maxpool2x2_ceil_bwd_codes", dy, codes.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, record="maxpool_bwd",
+            nbytes=2 * (dx.numel() + dy.numel()) + 4 * codes.numel())
     return dx
 
 
@@ -548,14 +513,11 @@ def head_fwd(side: Sequence[torch.Tensor], filt: Sequence[torch.Tensor], filt1: 
             _need(filt1[s], _F32, "head_fwd filt1")
         f1_ptrs = [f.data_ptr() for f in filt1]
         _need(dsn_w, _F32, "head_fwd dsn_w"); _need(dsn_b, _F32, "head_fwd dsn_b")
-    dev, st = _ctx(side[0])
-    t0 = _pb()
-    check(lib().fosvos_head_fwd(ptr_array4([t.data_ptr() for t in side]), int_array4([t.shape[1] for t in side]),
-                                int_array4([t.shape[2] for t in side]), ptr_array4([t.data_ptr() for t in filt]),
-                                ptr_array4(f1_ptrs), _p(dsn_w) if with_side_out else None,
-                                _p(dsn_b) if with_side_out else None, fuse_w.data_ptr(), fuse_b.data_ptr(),
-                                fused.data_ptr(), ptr_array4(so_ptrs), n, H, W, int(filt_uniform) & 15, dev, st), "head_fwd")
-    _pe(t0, "head_fwd", 2.0 * n * H * W * 256, 4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_side_out else 1)))
+    _launch("head_fwd", side[0], ptr_array4([t.data_ptr() for t in side]), int_array4([t.shape[1] for t in side]),
+            int_array4([t.shape[2] for t in side]), ptr_array4([t.data_ptr() for t in filt]), ptr_array4(f1_ptrs),
+            _p(dsn_w) if with_side_out else None, _p(dsn_b) if with_side_out else None, fuse_w.data_ptr(), fuse_b.data_ptr(),
+            fused.data_ptr(), ptr_array4(so_ptrs), n, H, W, int(filt_uniform) & 15, flops=2.0 * n * H * W * 256,
+            nbytes=4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_side_out else 1)))
     return fused, outs
 
 
@@ -592,18 +554,13 @@ def head_bwd(side: Sequence[torch.Tensor], filt: Sequence[torch.Tensor], filt1: 
         dso_ptrs = [t.data_ptr() for t in d_side_out]
         f1_ptrs = [t.data_ptr() for t in filt1]
         _need(dsn_w, _F32, "head_bwd dsn_w")
-    L = lib()
-    ws, wsn = _WS.get(L.fosvos_head_bwd_workspace_bytes(n, H, W), dev_t)
-    dev, st = _ctx(side[0])
-    t0 = _pb()
-    check(L.fosvos_head_bwd(ptr_array4([t.data_ptr() for t in side]), int_array4([t.shape[1] for t in side]),
-                            int_array4([t.shape[2] for t in side]), ptr_array4([t.data_ptr() for t in filt]),
-                            ptr_array4(f1_ptrs), _p(dsn_w) if with_so else None, fuse_w.data_ptr(), _p(d_fused),
-                            ptr_array4(dso_ptrs), ptr_array4([t.data_ptr() for t in d_side]), d_fuse_w.data_ptr(),
-                            d_fuse_b.data_ptr(), _p(d_dsn_w), _p(d_dsn_b), n, H, W, int(filt_uniform) & 15, ws, wsn, dev, st),
-          "head_bwd")
-    _pe(t0, "head_bwd", 2.0 * n * H * W * 256, 4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_so else 1)) +
-        2 * sum(t.numel() for t in d_side))
+    ws, wsn = _WS.get(lib().fosvos_head_bwd_workspace_bytes(n, H, W), dev_t)
+    _launch("head_bwd", side[0], ptr_array4([t.data_ptr() for t in side]), int_array4([t.shape[1] for t in side]),
+            int_array4([t.shape[2] for t in side]), ptr_array4([t.data_ptr() for t in filt]), ptr_array4(f1_ptrs),
+            _p(dsn_w) if with_so else None, fuse_w.data_ptr(), _p(d_fused), ptr_array4(dso_ptrs),
+            ptr_array4([t.data_ptr() for t in d_side]), d_fuse_w.data_ptr(), d_fuse_b.data_ptr(), _p(d_dsn_w), _p(d_dsn_b),
+            n, H, W, int(filt_uniform) & 15, ws, wsn, flops=2.0 * n * H * W * 256,
+            nbytes=4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_so else 1)) + 2 * sum(t.numel() for t in d_side))
     return d_side, d_fuse_w, d_fuse_b, d_dsn_w, d_dsn_b
 
 
@@ -630,28 +587,21 @@ def cbce_loss(logits: torch.Tensor, label: torch.Tensor, size_average: bool = Tr
     # the loss keeps its own small workspace: it must stay valid until the kernels ran, and the shared
     # grow-only buffer may be re-used by the next op on the same stream (which is ordered after us)
     ws, wsn = _WS.get(L.fosvos_cbce_workspace_bytes(logits.numel()), logits.device)
-    dev, st = _ctx(logits)
-    t0 = _pb()
+    head = (logits.data_ptr(), label.data_ptr(), logits.numel(), 1 if size_average else 0, float(grad_scale))
+    tail = (loss.data_ptr(), _p(grad), ws, wsn)
     if batch_counts is None:
-        check(L.fosvos_cbce_loss(logits.data_ptr(), label.data_ptr(), logits.numel(), 1 if size_average else 0,
-                                 float(grad_scale), loss.data_ptr(), _p(grad), ws, wsn, dev, st), "cbce_loss")
+        _launch("cbce_loss", logits, *head, *tail, nbytes=logits.numel() * (16 if want_grad else 12))
     else:
-        check(L.fosvos_cbce_loss_batch_counts(logits.data_ptr(), label.data_ptr(), logits.numel(),
-                                              1 if size_average else 0, float(grad_scale), batch_counts.data_ptr(),
-                                              loss.data_ptr(), _p(grad), ws, wsn, dev, st), "cbce_loss_batch_counts")
-    _pe(t0, "cbce_loss", 0.0, logits.numel() * (16 if want_grad else 12))
+        _launch("cbce_loss_batch_counts", logits, *head, batch_counts.data_ptr(), *tail, record="cbce_loss",
+                nbytes=logits.numel() * (16 if want_grad else 12))
     return loss, grad
 
 
 def _cbce_loss_frames_void(logits: torch.Tensor, label: torch.Tensor, void: torch.Tensor, size_average: bool, want_grad: bool,
                            grad_scale: float):
     """cbce_loss_frames with ignored pixels (fosvos_cbce_loss_frames_void)."""
-    if void.dtype != torch.uint8:
-        raise TypeError(f"cbce_loss_frames void: expected torch.uint8, got {void.dtype}")
-    if not void.is_cuda or void.device != logits.device:
-        raise RuntimeError(f"cbce_loss_frames void: must be on {logits.device}, got {void.device}")
-    if not void.is_contiguous():
-        raise ValueError("cbce_loss_frames void: tensor must be contiguous")
+    _need(void, torch.uint8, "cbce_loss_frames void")
+    _same_device("cbce_loss_frames", logits, void)
     if void.shape != logits.shape:
         raise ValueError(f"cbce_loss_frames: logits {tuple(logits.shape)} vs void {tuple(void.shape)}")
     n = logits.shape[0]
@@ -671,12 +621,9 @@ def _cbce_loss_frames_void(logits: torch.Tensor, label: torch.Tensor, void: torc
     losses = torch.empty((n,), dtype=_F32, device=logits.device)
     grad = torch.empty_like(logits) if want_grad else None
     ws, wsn = _WS.get(L.fosvos_cbce_void_workspace_bytes(per, n), logits.device)
-    dev, st = _ctx(logits)
-    t0 = _pb()
-    check(L.fosvos_cbce_loss_frames_void(logits.data_ptr(), label.data_ptr(), void.data_ptr(), per, n,
-                                         1 if size_average else 0, float(grad_scale), losses.data_ptr(), _p(grad), ws, wsn,
-                                         dev, st), "cbce_loss_frames_void")
-    _pe(t0, "cbce_loss_void", 0.0, logits.numel() * (18 if want_grad else 14))
+    _launch("cbce_loss_frames_void", logits, logits.data_ptr(), label.data_ptr(), void.data_ptr(), per, n,
+            1 if size_average else 0, float(grad_scale), losses.data_ptr(), _p(grad), ws, wsn, record="cbce_loss_void",
+            nbytes=logits.numel() * (18 if want_grad else 14))
     return losses, grad
 
 
@@ -701,11 +648,8 @@ def cbce_loss_frames(logits: torch.Tensor, label: torch.Tensor, size_average: bo
     losses = torch.empty((n,), dtype=_F32, device=logits.device)
     grad = torch.empty_like(logits) if want_grad else None
     ws, wsn = _WS.get(n * L.fosvos_cbce_workspace_bytes(per), logits.device)
-    dev, st = _ctx(logits)
-    t0 = _pb()
-    check(L.fosvos_cbce_loss_frames(logits.data_ptr(), label.data_ptr(), per, n, 1 if size_average else 0, float(grad_scale),
-                                    losses.data_ptr(), _p(grad), ws, wsn, dev, st), "cbce_loss_frames")
-    _pe(t0, "cbce_loss", 0.0, logits.numel() * (16 if want_grad else 12))
+    _launch("cbce_loss_frames", logits, logits.data_ptr(), label.data_ptr(), per, n, 1 if size_average else 0, float(grad_scale),
+            losses.data_ptr(), _p(grad), ws, wsn, record="cbce_loss", nbytes=logits.numel() * (16 if want_grad else 12))
     return losses, grad
 
 
@@ -715,7 +659,6 @@ CBCE_MAX_MAPS = 8
 
 def _map_tables(tensors):
     """HOST array of device pointers (a NULL entry for None), as the multi-map loss takes its logits and gradients."""
-    import ctypes
     return (ctypes.c_void_p * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
@@ -746,7 +689,6 @@ def cbce_loss_frames_multi(logits: Sequence[torch.Tensor], label: torch.Tensor, 
     gradients or None); map m's gradient comes out multiplied by ``map_scale[m]``.  One count and one loss launch for all
     maps (fosvos_cbce_loss_frames_multi); every value equals ``cbce_loss_frames(logits[m], label, grad_scale=map_scale[m])``
     bit for bit.  workspace: a uint8 tensor of cbce_multi_workspace_bytes to use instead of the ops' scratch."""
-    import ctypes
     logits = list(logits)
     _multi_args(logits, label, map_scale, "cbce_loss_frames_multi")
     m = len(logits)
@@ -760,13 +702,10 @@ def cbce_loss_frames_multi(logits: Sequence[torch.Tensor], label: torch.Tensor, 
     else:
         _need(workspace, torch.uint8, "cbce_loss_frames_multi workspace")
         ws, wsn = workspace.data_ptr(), workspace.numel()
-    dev, st = _ctx(label)
-    t0 = _pb()
-    check(L.fosvos_cbce_loss_frames_multi(_map_tables(logits), label.data_ptr(), per, n, m, 1 if size_average else 0,
-                                          (ctypes.c_float * max(m, 1))(*[float(v) for v in map_scale]), losses.data_ptr(),
-                                          _map_tables(grads) if want_grad else None, ws, wsn,
-                                          CBCE_COUNT | CBCE_LOSS | CBCE_FINISH, dev, st), "cbce_loss_frames_multi")
-    _pe(t0, "cbce_loss", 0.0, label.numel() * (8 + m * (8 if want_grad else 4)))
+    _launch("cbce_loss_frames_multi", label, _map_tables(logits), label.data_ptr(), per, n, m, 1 if size_average else 0,
+            (ctypes.c_float * max(m, 1))(*[float(v) for v in map_scale]), losses.data_ptr(),
+            _map_tables(grads) if want_grad else None, ws, wsn, CBCE_COUNT | CBCE_LOSS | CBCE_FINISH, record="cbce_loss",
+            nbytes=label.numel() * (8 + m * (8 if want_grad else 4)))
     return losses, grads
 
 
@@ -802,7 +741,6 @@ class CbceFramesMultiStaged(object):
 
     def _launch(self, parts: int, stage: str, logits=None, map_scale=None, grads=None):
         """One call of the C entry point for the stages ``parts``; the maps' arguments only with the loss stage."""
-        import ctypes
         dev, st = _ctx(self.label)
         check(lib().fosvos_cbce_loss_frames_multi(None if logits is None else _map_tables(logits), self.label.data_ptr(),
                                                   self.per, self.n, self.m, 1 if self.size_average else 0,
@@ -883,9 +821,7 @@ def fold_conv_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn: 
         eps = float(bn[4])
     if conv_bias is not None:
         _need(conv_bias, _F32, "fold_conv_bn conv bias")
-    dev, st = _ctx(w)
-    check(lib().fosvos_fold_conv_bn(w.data_ptr(), co, ci, k, _p(conv_bias), bnp[0], bnp[1], bnp[2], bnp[3], eps,
-                                    out.data_ptr(), bias.data_ptr(), dev, st), "fold_conv_bn")
+    _launch("fold_conv_bn", w, w.data_ptr(), co, ci, k, _p(conv_bias), *bnp, eps, out.data_ptr(), bias.data_ptr(), record=False)
     return out, bias
 
 
@@ -908,13 +844,11 @@ def conv3x3_fwd_add(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor,
         if addend.shape != y.shape:
             raise ValueError(f"conv3x3_fwd_add: addend {tuple(addend.shape)} vs output {tuple(y.shape)}")
     ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, ci, co), x.device)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_fwd_add(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), _p(addend), y.data_ptr(), n, h, wd, ci,
-                                   co, (CONV_RELU if relu else 0) | (CONV_OUT_F32 if out_f32 else 0), ws, wsn, dev, st),
-          "conv3x3_fwd_add")
-    _pe(t0, f"mfma3x3s1 {ci}->{co} @{h}x{wd}" if _PROF is not None and _PROF.detail else "mfma3x3s1",
-        2.0 * n * h * wd * 9 * ci * co, 2 * (x.numel() + y.numel()) + (2 * addend.numel() if addend is not None else 0))
+    _launch("conv3x3_fwd_add", x, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), _p(addend), y.data_ptr(), n, h, wd, ci, co,
+            (CONV_RELU if relu else 0) | (CONV_OUT_F32 if out_f32 else 0), ws, wsn,
+            record=f"mfma3x3s1 {ci}->{co} @{h}x{wd}" if _PROF is not None and _PROF.detail else "mfma3x3s1",
+            flops=2.0 * n * h * wd * 9 * ci * co,
+            nbytes=2 * (x.numel() + y.numel()) + (2 * addend.numel() if addend is not None else 0))
     return y
 
 
@@ -932,12 +866,10 @@ def conv3x3_s2_fwd(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, 
     ho, wo = (h - 1) // 2 + 1, (wd - 1) // 2 + 1
     y = torch.empty((n, ho, wo, co), dtype=_BF16, device=x.device)
     ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, ci, co), x.device)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(L.fosvos_conv3x3_s2_fwd(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, wd, ci, co,
-                                  CONV_RELU if relu else 0, ws, wsn, dev, st), "conv3x3_s2_fwd")
-    _pe(t0, f"mfma3x3s2 {ci}->{co} @{ho}x{wo}" if _PROF is not None and _PROF.detail else "mfma3x3s2",
-        2.0 * n * ho * wo * 9 * ci * co, 2 * (x.numel() + y.numel()))
+    _launch("conv3x3_s2_fwd", x, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, wd, ci, co,
+            CONV_RELU if relu else 0, ws, wsn,
+            record=f"mfma3x3s2 {ci}->{co} @{ho}x{wo}" if _PROF is not None and _PROF.detail else "mfma3x3s2",
+            flops=2.0 * n * ho * wo * 9 * ci * co, nbytes=2 * (x.numel() + y.numel()))
     return y
 
 
@@ -966,9 +898,8 @@ def pack_conv2d_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn
         eps = float(bn[4])
     if conv_bias is not None:
         _need(conv_bias, _F32, "pack_conv2d_bn conv bias")
-    dev, st = _ctx(w)
-    check(L.fosvos_pack_conv2d_bn(w.data_ptr(), co, ci, k, _p(conv_bias), bnp[0], bnp[1], bnp[2], bnp[3], eps,
-                                  packed.data_ptr(), bias.data_ptr(), dev, st), "pack_conv2d_bn")
+    _launch("pack_conv2d_bn", w, w.data_ptr(), co, ci, k, _p(conv_bias), *bnp, eps, packed.data_ptr(), bias.data_ptr(),
+            record=False)
     return packed, bias
 
 
@@ -976,7 +907,6 @@ def conv2d_plan(n: int, h: int, w: int, ci: int, co: int, k: int, stride: int = 
     """What fosvos_conv2d_fwd launches for this shape (host arithmetic only): {"cob", "threads", "slices", "workgroups"}.
     k = 7, stride = 2, ci = 3: what fosvos_conv7x7s2_first_fwd launches - with fp32_math (or more than 64 channels) the same
     keys for its vector-ALU form, else {"mfma_frag_blocks", "workgroups"} of the MFMA form."""
-    import ctypes
     from . import Conv2dPlanInfo
     info = Conv2dPlanInfo()
     check(lib().fosvos_conv2d_plan(n, h, w, ci, co, k, stride, ctypes.byref(info)), "conv2d_plan")
@@ -1003,13 +933,10 @@ def conv2d_fwd(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, ci: in
         if addend.shape != y.shape:
             raise ValueError(f"conv2d_fwd: addend {tuple(addend.shape)} vs output {tuple(y.shape)}")
     flags = (CONV_RELU if relu else 0) | (CONV_OUT_F32 if out_f32 else 0)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(L.fosvos_conv2d_fwd(x.data_ptr(), packed.data_ptr(), bias.data_ptr(), _p(addend), y.data_ptr(), n, h, w, ci, co,
-                              k, stride, flags, dev, st), "conv2d_fwd")
-    _pe(t0, f"conv{k}x{k}s{stride} {ci}->{co} @{ho}x{wo}" if _PROF is not None and _PROF.detail else f"conv{k}x{k}s{stride}",
-        2.0 * n * ho * wo * k * k * ci * co,
-        2 * x.numel() + y.numel() * y.element_size() + (2 * addend.numel() if addend is not None else 0))
+    _launch("conv2d_fwd", x, x.data_ptr(), packed.data_ptr(), bias.data_ptr(), _p(addend), y.data_ptr(), n, h, w, ci, co, k, stride,
+            flags, record=f"conv{k}x{k}s{stride}" + (f" {ci}->{co} @{ho}x{wo}" if _PROF is not None and _PROF.detail else ""),
+            flops=2.0 * n * ho * wo * k * k * ci * co,
+            nbytes=2 * x.numel() + y.numel() * y.element_size() + (2 * addend.numel() if addend is not None else 0))
     return y
 
 
@@ -1028,9 +955,7 @@ def pack_conv7x7_bn(w: torch.Tensor, bn: Optional[Sequence] = None):
             _need(t, _F32, "pack_conv7x7_bn BatchNorm tensor")
         bnp = [t.data_ptr() for t in bn[:4]]
         eps = float(bn[4])
-    dev, st = _ctx(w)
-    check(L.fosvos_pack_conv7x7_bn(w.data_ptr(), co, bnp[0], bnp[1], bnp[2], bnp[3], eps, packed.data_ptr(),
-                                   bias.data_ptr(), dev, st), "pack_conv7x7_bn")
+    _launch("pack_conv7x7_bn", w, w.data_ptr(), co, *bnp, eps, packed.data_ptr(), bias.data_ptr(), record=False)
     return packed, bias
 
 
@@ -1051,12 +976,9 @@ def conv7x7s2_first_fwd(frame: torch.Tensor, packed: torch.Tensor, bias: torch.T
         raise ValueError("conv7x7s2_first_fwd: packed image / bias size does not match co")
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y = torch.empty((n, ho, wo, _ru(co, 8)), dtype=_BF16, device=frame.device)
-    dev, st = _ctx(frame)
-    t0 = _pb()
-    check(L.fosvos_conv7x7s2_first_fwd(frame.data_ptr(), packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, w, co,
-                                       (CONV_RELU if relu else 0) | (CONV_FP32_MATH if fp32_math else 0), dev, st),
-          "conv7x7s2_first_fwd")
-    _pe(t0, "conv7x7s2_first", 2.0 * n * ho * wo * 147 * co, 4 * frame.numel() + 2 * y.numel())
+    _launch("conv7x7s2_first_fwd", frame, frame.data_ptr(), packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, w, co,
+            (CONV_RELU if relu else 0) | (CONV_FP32_MATH if fp32_math else 0), record="conv7x7s2_first",
+            flops=2.0 * n * ho * wo * 147 * co, nbytes=4 * frame.numel() + 2 * y.numel())
     return y
 
 
@@ -1074,11 +996,8 @@ def conv7x7s2_pool_first_fwd(frame: torch.Tensor, packed: torch.Tensor, bias: to
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     hp, wp = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
     y = torch.empty((n, hp, wp, _ru(co, 8)), dtype=_BF16, device=frame.device)
-    dev, st = _ctx(frame)
-    t0 = _pb()
-    check(L.fosvos_conv7x7s2_pool_first_fwd(frame.data_ptr(), packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, w, co,
-                                            dev, st), "conv7x7s2_pool_first_fwd")
-    _pe(t0, "conv7x7s2_pool_first", 2.0 * n * ho * wo * 147 * co, 4 * frame.numel() + 2 * y.numel())
+    _launch("conv7x7s2_pool_first_fwd", frame, frame.data_ptr(), packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, w, co,
+            record="conv7x7s2_pool_first", flops=2.0 * n * ho * wo * 147 * co, nbytes=4 * frame.numel() + 2 * y.numel())
     return y
 
 
@@ -1086,10 +1005,7 @@ def maxpool3x3s2_fwd(x: torch.Tensor) -> torch.Tensor:
     _need(x, _BF16, "maxpool3x3s2_fwd")
     n, h, w, c = x.shape
     y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=_BF16, device=x.device)
-    dev, st = _ctx(x)
-    t0 = _pb()
-    check(lib().fosvos_maxpool3x3s2_fwd(x.data_ptr(), y.data_ptr(), n, h, w, c, dev, st), "maxpool3x3s2_fwd")
-    _pe(t0, "maxpool3x3s2", 0.0, 2 * (x.numel() + y.numel()))
+    _launch("maxpool3x3s2_fwd", x, x.data_ptr(), y.data_ptr(), n, h, w, c, record="maxpool3x3s2", nbytes=2 * (x.numel() + y.numel()))
     return y
 
 
@@ -1119,15 +1035,11 @@ def deconv_head_fwd(side: Sequence[torch.Tensor], strides: Sequence[int], filt: 
                 raise ValueError("deconv_head_fwd: filt1 shape")
         f1_ptrs = [f.data_ptr() for f in filt1]
         _need(dsn_w, _F32, "deconv_head_fwd dsn_w"); _need(dsn_b, _F32, "deconv_head_fwd dsn_b")
-    dev, st = _ctx(side[0])
-    t0 = _pb()
-    check(lib().fosvos_deconv_head_fwd(ptr_array4([t.data_ptr() for t in side]), int_array4([t.shape[1] for t in side]),
-                                       int_array4([t.shape[2] for t in side]), int_array4([int(f) for f in strides]),
-                                       ptr_array4([t.data_ptr() for t in filt]), ptr_array4(f1_ptrs),
-                                       _p(dsn_w) if with_side_out else None, _p(dsn_b) if with_side_out else None,
-                                       fuse_b.data_ptr(), fused.data_ptr(), ptr_array4(so_ptrs), n, H, W, dev, st),
-          "deconv_head_fwd")
-    _pe(t0, "deconv_head_fwd", 2.0 * n * H * W * 256, 4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_side_out else 1)))
+    _launch("deconv_head_fwd", side[0], ptr_array4([t.data_ptr() for t in side]), int_array4([t.shape[1] for t in side]),
+            int_array4([t.shape[2] for t in side]), int_array4([int(f) for f in strides]),
+            ptr_array4([t.data_ptr() for t in filt]), ptr_array4(f1_ptrs), _p(dsn_w) if with_side_out else None,
+            _p(dsn_b) if with_side_out else None, fuse_b.data_ptr(), fused.data_ptr(), ptr_array4(so_ptrs), n, H, W,
+            flops=2.0 * n * H * W * 256, nbytes=4 * (sum(t.numel() for t in side) + n * H * W * (5 if with_side_out else 1)))
     return fused, outs
 
 
@@ -1176,23 +1088,49 @@ def augment_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, img_lut:
     for t in (mask, img_lut, gt_lut, image, gt) + tuple(tables or ()):
         if t.device != frame.device:
             raise RuntimeError(f"augment_sample: every tensor must be on {frame.device}, got one on {t.device}")
-    dev, st = _ctx(frame)
-    e0 = _pb()
-    check(lib().fosvos_augment_sample(frame.data_ptr(), mask.data_ptr(), h, w, 1 if flip else 0, *ptrs, oh, ow,
-                                      img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(), dev, st),
-          "augment_sample")
-    _pe(e0, "augment_sample", 0.0, float(frame.numel() + mask.numel() + 4 * (image.numel() + gt.numel())))
+    _launch("augment_sample", frame, frame.data_ptr(), mask.data_ptr(), h, w, 1 if flip else 0, *ptrs, oh, ow, img_lut.data_ptr(),
+            gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(),
+            nbytes=float(frame.numel() + mask.numel() + 4 * (image.numel() + gt.numel())))
 
 
-# ------------------------------------------------------------------------------------------ scoring (eval.hip)
-def _need_eval(t: torch.Tensor, dtype, what: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: tensor must live on the GPU (the HIP path has no CPU fallback)")
-    if t.dtype != dtype:
-        raise ValueError(f"{what}: expected {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: tensor must be contiguous")
-    return t
+# ------------------------------------------------------------------------------------------ shared argument checks
+# (of the ops from here down: a wrong dtype is a ValueError; DESIGN.md section 21 lists who uses which)
+MAX_OBJECTS = limits.MAX_OBJECTS
+MAX_FRAME_SIDE = limits.MAX_FRAME_SIDE  # of a scaled call (util/frame_resample.MAX_SIDE)
+_PALETTES = {}  # device -> the default palette (util/object_merge.davis_palette) on it
+
+
+def _same_device(what: str, first, *others: torch.Tensor) -> None:
+    """``first``: a tensor, or the device itself."""
+    device = first.device if isinstance(first, torch.Tensor) else first
+    for t in others:
+        if t.device != device:
+            raise RuntimeError(f"{what}: every tensor must be on {device}, got one on {t.device}")
+
+
+def _out_like(out: Optional[torch.Tensor], shape, dtype, like, what: str, name: str = "out") -> torch.Tensor:
+    """The output buffer ``name``: a new one on ``like``'s device (``like``: a tensor, or the device itself), or the
+    caller's where it is a contiguous ``dtype`` tensor of ``shape`` on that device."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device if isinstance(like, torch.Tensor) else like)
+    _need(out, dtype, f"{what} {name}", ValueError)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {tuple(out.shape)}")
+    _same_device(what, like, out)
+    return out
+
+
+def _file_buffers(out: Optional[torch.Tensor], lengths: Optional[torch.Tensor], n: int, cap: int, like: torch.Tensor,
+                  what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What a file encoder writes into: ``out`` uint8 [n, >= cap] and ``lengths`` int32 [n] on ``like``'s device."""
+    if out is None:
+        out = torch.empty((n, cap), dtype=torch.uint8, device=like.device)
+    else:
+        _need(out, torch.uint8, f"{what} out", ValueError)
+        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cap:
+            raise ValueError(f"{what}: out must be [{n}, >= {cap}], got {tuple(out.shape)}")
+        _same_device(what, like, out)
+    return out, _out_like(lengths, (n,), torch.int32, like, what, "lengths")
 
 
 def _logit_shape(logits: torch.Tensor, what: str) -> Tuple[int, int, int]:
@@ -1201,31 +1139,75 @@ def _logit_shape(logits: torch.Tensor, what: str) -> Tuple[int, int, int]:
     return int(logits.shape[0]), int(logits.shape[2]), int(logits.shape[3])
 
 
+def _map_shape(t: torch.Tensor, what: str, name: str) -> Tuple[int, int, int]:
+    """(N, H, W) of ``t`` where it is a non-empty uint8 [N,H,W] map on the GPU."""
+    _need(t, torch.uint8, f"{what} {name}", ValueError)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty [N,H,W], got {tuple(t.shape)}")
+    return int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+
+
+def _logit_table(logits: Sequence[torch.Tensor], what: str, shape=None):
+    """The K logit maps of several objects: (the maps as a list, their shape (N,1,H,W), the HOST array of their K device
+    pointers).  Every map is checked against ``shape``, or - None - the first against ``_logit_shape`` and the rest against it."""
+    logits = list(logits)
+    k = len(logits)
+    if not 1 <= k <= MAX_OBJECTS:
+        raise ValueError(f"{what}: {k} logit maps, outside [1, {MAX_OBJECTS}]")
+    for t in logits:
+        _need(t, _F32, f"{what} logits", ValueError)
+    if shape is None:
+        n, h, w = _logit_shape(logits[0], what)
+        shape = (n, 1, h, w)
+    for t in logits:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what}: every logit map must be {shape}, got {tuple(t.shape)}")
+    return logits, shape, (ctypes.c_void_p * k)(*[t.data_ptr() for t in logits])
+
+
+def default_palette(device) -> torch.Tensor:
+    """``object_merge.davis_palette()`` as a uint8 [256,3] tensor on ``device``, uploaded once per device."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f"default_palette: a GPU device, got {device} (the HIP path has no CPU fallback)")
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    pal = _PALETTES.get(key)
+    if pal is None:
+        from util.object_merge import davis_palette
+        pal = _PALETTES[key] = torch.from_numpy(davis_palette()).to(device)
+    return pal
+
+
+def _palette(palette: Optional[torch.Tensor], device: torch.device, what: str) -> torch.Tensor:
+    """``palette`` where it is a uint8 [256,3] tensor on ``device``; None: the default one."""
+    if palette is None:
+        return default_palette(device)
+    _need(palette, torch.uint8, f"{what} palette", ValueError)
+    if tuple(palette.shape) != (256, 3):
+        raise ValueError(f"{what}: palette must be (256, 3), got {tuple(palette.shape)}")
+    _same_device(what, device, palette)
+    return palette
+
+
+def _jf_radius(radius: Optional[int], h: int, w: int, what: str) -> int:
+    return limits.check_int(what, "radius", jf_default_radius(h, w) if radius is None else int(radius), *limits.JF_RADIUS)
+
+
+# ------------------------------------------------------------------------------------------ scoring (eval.hip)
 def prob_bytes(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fosvos_prob_bytes: logits fp32 [N,1,H,W] -> uint8 [N,H,W], per frame ``bytescale(sigmoid(logits))`` of
     util/experiment_helper.py evaluated in fp64 (the bytes of the probability PNG).  Launched on the current stream, no
     synchronisation."""
-    _need_eval(logits, _F32, "prob_bytes logits")
+    _need(logits, _F32, "prob_bytes logits", ValueError)
     n, h, w = _logit_shape(logits, "prob_bytes")
-    if out is None:
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=logits.device)
-    else:
-        _need_eval(out, torch.uint8, "prob_bytes out")
-        if tuple(out.shape) != (n, h, w):
-            raise ValueError(f"prob_bytes: out must be {(n, h, w)}, got {tuple(out.shape)}")
-        if out.device != logits.device:
-            raise RuntimeError(f"prob_bytes: every tensor must be on {logits.device}, got one on {out.device}")
+    out = _out_like(out, (n, h, w), torch.uint8, logits, "prob_bytes")
     ws, _ = _WS.get(8 * n, logits.device)
-    dev, st = _ctx(logits)
-    e0 = _pb()
-    check(lib().fosvos_prob_bytes(logits.data_ptr(), n, h, w, ws, out.data_ptr(), dev, st), "prob_bytes")
-    _pe(e0, "prob_bytes", 0.0, 9.0 * n * h * w)
+    _launch("prob_bytes", logits, logits.data_ptr(), n, h, w, ws, out.data_ptr(), nbytes=9.0 * n * h * w)
     return out
 
 
 def jf_default_radius(h: int, w: int) -> int:
     """ceil(0.008 * diagonal), the DAVIS boundary tolerance (util/davis_measures.default_radius)."""
-    import math
     return int(math.ceil(0.008 * math.sqrt(h * h + w * w)))
 
 
@@ -1235,48 +1217,35 @@ def jf_counts(logits: torch.Tensor, gt: torch.Tensor, radius: Optional[int] = No
     union, n_pred_b, n_gt_b, match_pred, match_gt of the mask ``logits >= 0`` against ``gt`` (util/davis_measures.py states
     the definitions).  ``radius`` (1..63) defaults to ceil(0.008 * diagonal).  ``out`` may be any [N,6] int32 rows, e.g. a
     slice of a sequence's counter tensor; the op zeroes them itself.  Launched on the current stream, no synchronisation."""
-    _need_eval(logits, _F32, "jf_counts logits")
-    _need_eval(gt, torch.uint8, "jf_counts gt")
+    _need(logits, _F32, "jf_counts logits", ValueError)
+    _need(gt, torch.uint8, "jf_counts gt", ValueError)
     n, h, w = _logit_shape(logits, "jf_counts")
     if tuple(gt.shape) != (n, h, w):
         raise ValueError(f"jf_counts: gt must be {(n, h, w)}, got {tuple(gt.shape)}")
-    if radius is None:
-        radius = jf_default_radius(h, w)
-    radius = int(radius)
-    if not 1 <= radius <= 63:
-        raise ValueError(f"jf_counts: radius {radius} outside [1, 63]")
-    if out is None:
-        out = torch.empty((n, 6), dtype=torch.int32, device=logits.device)
-    else:
-        _need_eval(out, torch.int32, "jf_counts out")
-        if tuple(out.shape) != (n, 6):
-            raise ValueError(f"jf_counts: out must be {(n, 6)}, got {tuple(out.shape)}")
-    for t in (gt, out):
-        if t.device != logits.device:
-            raise RuntimeError(f"jf_counts: every tensor must be on {logits.device}, got one on {t.device}")
-    L = lib()
-    ws, wsn = _WS.get(L.fosvos_jf_workspace_bytes(n, h, w), logits.device)
-    dev, st = _ctx(logits)
-    e0 = _pb()
-    check(L.fosvos_jf_counts(logits.data_ptr(), gt.data_ptr(), n, h, w, radius, out.data_ptr(), ws, wsn, dev, st), "jf_counts")
-    _pe(e0, "jf_counts", 0.0, 5.0 * n * h * w)
+    radius = _jf_radius(radius, h, w, "jf_counts")
+    out = _out_like(out, (n, 6), torch.int32, logits, "jf_counts")
+    _same_device("jf_counts", logits, gt)
+    ws, wsn = _WS.get(lib().fosvos_jf_workspace_bytes(n, h, w), logits.device)
+    _launch("jf_counts", logits, logits.data_ptr(), gt.data_ptr(), n, h, w, radius, out.data_ptr(), ws, wsn, nbytes=5.0 * n * h * w)
     return out
 
 
 # ------------------------------------------------------------------------------------------ mask cleaning (components.hip)
+def _components_shape(logits: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    _need(logits, _F32, f"{what} logits", ValueError)
+    n, h, w = _logit_shape(logits, what)
+    if h * w >= 1 << 31 or n > 65535:
+        raise ValueError(f"{what}: N={n} (<= 65535) H={h} W={w} (H W < 2^31)")
+    return n, h, w
+
+
 def component_roots(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fosvos_component_roots: logits fp32 [N,1,H,W] -> int32 [N,H,W]: -1 where ``logits >= 0`` does not hold, else the
     smallest raster index ``y * W + x`` of the pixel's 8-connected component (util/mask_components.component_roots).
     Launched on the current stream, no synchronisation."""
-    _need_eval(logits, _F32, "component_roots logits")
-    n, h, w = _logit_shape(logits, "component_roots")
-    if h * w >= 1 << 31 or n > 65535:
-        raise ValueError(f"component_roots: N={n} (<= 65535) H={h} W={w} (H W < 2^31)")
+    n, h, w = _components_shape(logits, "component_roots")
     out = _out_like(out, (n, h, w), torch.int32, logits, "component_roots")
-    dev, st = _ctx(logits)
-    e0 = _pb()
-    check(lib().fosvos_component_roots(logits.data_ptr(), n, h, w, out.data_ptr(), None, 0, dev, st), "component_roots")
-    _pe(e0, "component_roots", 0.0, 8.0 * n * h * w)
+    _launch("component_roots", logits, logits.data_ptr(), n, h, w, out.data_ptr(), None, 0, nbytes=8.0 * n * h * w)
     return out
 
 
@@ -1290,57 +1259,29 @@ def clean_components(logits: torch.Tensor, seed: Optional[torch.Tensor] = None, 
     uint8 [N,H,W], a non-zero byte is a set pixel; with ``chain`` uint8 [1,H,W] or None for frame 0, and frame n is gated by
     what frame n - 1 kept.  ``out`` may be ``logits`` itself; ``kept`` (uint8 [N,H,W]) receives 1 on kept pixels.  Launched
     on the current stream, no synchronisation."""
-    _need_eval(logits, _F32, "clean_components logits")
-    n, h, w = _logit_shape(logits, "clean_components")
-    if h * w >= 1 << 31 or n > 65535:
-        raise ValueError(f"clean_components: N={n} (<= 65535) H={h} W={w} (H W < 2^31)")
-    for name, v in (("radius", radius), ("min_area", min_area)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"clean_components: {name} must be an integer, got {v!r}")
-    if not 0 <= radius <= 63:
-        raise ValueError(f"clean_components: radius {radius} outside [0, 63]")
-    if not 0 <= min_area < 1 << 31:
-        raise ValueError(f"clean_components: min_area {min_area} must be >= 0")
-    fill = float(fill)
-    if not -3.4028234663852886e38 <= fill < 0:  # finite as a float32 too
-        raise ValueError(f"clean_components: fill must be finite and negative, got {fill!r}")
+    n, h, w = _components_shape(logits, "clean_components")
+    limits.check_int("clean_components", "radius", radius, 0, limits.CLEAN_MAX_RADIUS)
+    limits.check_int("clean_components", "min_area", min_area, 0, limits.CLEAN_MAX_AREA)
+    fill = limits.check_real("clean_components", "fill", float(fill), *limits.FILL_RANGE, hi_open=True,
+                             expect="finite and negative")  # finite as a float32 too
     if seed is not None:
-        _need_eval(seed, torch.uint8, "clean_components seed")
+        _need(seed, torch.uint8, "clean_components seed", ValueError)
         want = (1, h, w) if chain else (n, h, w)
         if tuple(seed.shape) != want:
             raise ValueError(f"clean_components: seed must be {want}{' with chain' if chain else ''}, got {tuple(seed.shape)}")
-    if out is None:
-        out = torch.empty_like(logits)
-    else:
-        _need_eval(out, _F32, "clean_components out")
-        if tuple(out.shape) != (n, 1, h, w):
-            raise ValueError(f"clean_components: out must be {(n, 1, h, w)}, got {tuple(out.shape)}")
+        _same_device("clean_components", logits, seed)
+    out = _out_like(out, (n, 1, h, w), _F32, logits, "clean_components")
     if kept is not None:
-        _need_eval(kept, torch.uint8, "clean_components kept")
-        if tuple(kept.shape) != (n, h, w):
-            raise ValueError(f"clean_components: kept must be {(n, h, w)}, got {tuple(kept.shape)}")
-    _same_device("clean_components", logits, out, *[t for t in (seed, kept) if t is not None])
-    L = lib()
-    ws, wsn = _WS.get(L.fosvos_components_workspace_bytes(n, h, w), logits.device)
-    dev, st = _ctx(logits)
-    e0 = _pb()
-    check(L.fosvos_clean_components(logits.data_ptr(), _p(seed), n, h, w, radius, min_area, int(bool(largest)),
-                                    int(bool(chain)), fill, out.data_ptr(), _p(kept), ws, wsn, dev, st), "clean_components")
-    _pe(e0, "clean_components", 0.0, 25.0 * n * h * w)
+        _out_like(kept, (n, h, w), torch.uint8, logits, "clean_components", "kept")
+    ws, wsn = _WS.get(lib().fosvos_components_workspace_bytes(n, h, w), logits.device)
+    _launch("clean_components", logits, logits.data_ptr(), _p(seed), n, h, w, radius, min_area, int(bool(largest)),
+            int(bool(chain)), fill, out.data_ptr(), _p(kept), ws, wsn, nbytes=25.0 * n * h * w)
     return out
 
 
 # ------------------------------------------------------------------------------------------ online adaptation (adapt.hip)
-GATE_MAX_DISTANCE = 4095  # util/online_adapt.MAX_DISTANCE
-GATE_MAX_SIDE = 8192
-
-
-def _gate_int(who: str, name: str, v) -> int:
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise ValueError(f"{who}: {name} must be an integer, got {v!r}")
-    if not 0 <= v <= GATE_MAX_DISTANCE:
-        raise ValueError(f"{who}: {name} {v} outside [0, {GATE_MAX_DISTANCE}]")
-    return v
+GATE_MAX_DISTANCE = limits.GATE_MAX_DISTANCE  # util/online_adapt.MAX_DISTANCE
+GATE_MAX_SIDE = limits.GATE_MAX_SIDE
 
 
 def _gate_shape(who: str, n: int, h: int, w: int) -> None:
@@ -1353,22 +1294,15 @@ def distance_gate(mask: torch.Tensor, distance: int, invert: bool = False, out: 
     ``distance`` (0..4095, Euclidean, exact in integers); a pixel is set when ``(mask != 0) != invert``, and a frame without
     a set pixel gives all 1 (util/online_adapt.far_from).  With ``invert`` it is the erosion of the mask by the disk.
     Launched on the current stream, no synchronisation."""
-    _need_eval(mask, torch.uint8, "distance_gate mask")
-    if mask.dim() != 3 or mask.numel() == 0:
-        raise ValueError(f"distance_gate: mask must be a non-empty [N,H,W], got {tuple(mask.shape)}")
-    n, h, w = (int(v) for v in mask.shape)
+    n, h, w = _map_shape(mask, "distance_gate", "mask")
     _gate_shape("distance_gate", n, h, w)
-    distance = _gate_int("distance_gate", "distance", distance)
+    limits.check_int("distance_gate", "distance", distance, 0, GATE_MAX_DISTANCE)
     out = _out_like(out, (n, h, w), torch.uint8, mask, "distance_gate")
     if out.data_ptr() == mask.data_ptr():
         raise ValueError("distance_gate: out must not be the mask itself")
-    L = lib()
-    ws, wsn = _WS.get(L.fosvos_distance_gate_workspace_bytes(n, h, w), mask.device)
-    dev, st = _ctx(mask)
-    e0 = _pb()
-    check(L.fosvos_distance_gate(mask.data_ptr(), n, h, w, distance, int(bool(invert)), out.data_ptr(), ws, wsn, dev, st),
-          "distance_gate")
-    _pe(e0, "distance_gate", 0.0, 6.0 * n * h * w)
+    ws, wsn = _WS.get(lib().fosvos_distance_gate_workspace_bytes(n, h, w), mask.device)
+    _launch("distance_gate", mask, mask.data_ptr(), n, h, w, distance, int(bool(invert)), out.data_ptr(), ws, wsn,
+            nbytes=6.0 * n * h * w)
     return out
 
 
@@ -1381,27 +1315,24 @@ def adapt_labels(logits: torch.Tensor, last_mask: torch.Tensor, pos_logit: float
     negative - unless that core is empty -, elsewhere ``logits >= float32(pos_logit)`` is a positive, the rest is void.
     ``counts`` may be any [N,3] int32 rows, e.g. a slice of a sequence's counter tensor; the op zeroes them itself.
     Launched on the current stream, no synchronisation."""
-    _need_eval(logits, _F32, "adapt_labels logits")
-    _need_eval(last_mask, torch.uint8, "adapt_labels last_mask")
+    _need(logits, _F32, "adapt_labels logits", ValueError)
+    _need(last_mask, torch.uint8, "adapt_labels last_mask", ValueError)
     n, h, w = _logit_shape(logits, "adapt_labels")
     _gate_shape("adapt_labels", n, h, w)
     if tuple(last_mask.shape) != (n, h, w):
         raise ValueError(f"adapt_labels: last_mask must be {(n, h, w)}, got {tuple(last_mask.shape)}")
-    neg_distance = _gate_int("adapt_labels", "neg_distance", neg_distance)
-    erode = _gate_int("adapt_labels", "erode", erode)
+    limits.check_int("adapt_labels", "neg_distance", neg_distance, 0, GATE_MAX_DISTANCE)
+    limits.check_int("adapt_labels", "erode", erode, 0, GATE_MAX_DISTANCE)
+    # (a threshold, not a range: an infinite one is a number here)
     if isinstance(pos_logit, bool) or not isinstance(pos_logit, (int, float)) or pos_logit != pos_logit:
         raise ValueError(f"adapt_labels: pos_logit must be a number, got {pos_logit!r}")
     label = _out_like(label, (n, 1, h, w), _F32, logits, "adapt_labels label")
     void = _out_like(void, (n, 1, h, w), torch.uint8, logits, "adapt_labels void")
     counts = _out_like(counts, (n, 3), torch.int32, logits, "adapt_labels counts")
     _same_device("adapt_labels", logits, last_mask)
-    L = lib()
-    ws, wsn = _WS.get(L.fosvos_adapt_labels_workspace_bytes(n, h, w), logits.device)
-    dev, st = _ctx(logits)
-    e0 = _pb()
-    check(L.fosvos_adapt_labels(logits.data_ptr(), last_mask.data_ptr(), n, h, w, float(pos_logit), neg_distance, erode,
-                                label.data_ptr(), void.data_ptr(), counts.data_ptr(), ws, wsn, dev, st), "adapt_labels")
-    _pe(e0, "adapt_labels", 0.0, (15.0 if erode == 0 else 21.0) * n * h * w)
+    ws, wsn = _WS.get(lib().fosvos_adapt_labels_workspace_bytes(n, h, w), logits.device)
+    _launch("adapt_labels", logits, logits.data_ptr(), last_mask.data_ptr(), n, h, w, float(pos_logit), neg_distance, erode,
+            label.data_ptr(), void.data_ptr(), counts.data_ptr(), ws, wsn, nbytes=(15.0 if erode == 0 else 21.0) * n * h * w)
     return label, void, counts
 
 
@@ -1422,78 +1353,27 @@ def png_encode(bytes_u8: torch.Tensor, out: Optional[torch.Tensor] = None, lengt
     buffer.  ``huffman='fitted'``: a segment may also be a dynamic-Huffman block with a code fitted
     to it, where that is shorter - the same pixels in files that are never longer, ``png_layout.encode(img, 'fitted')``.
     Launched on the current stream, no synchronisation."""
-    if huffman not in PNG_HUFFMAN:
-        raise ValueError(f"png_encode: huffman must be one of {tuple(PNG_HUFFMAN)}, got {huffman!r}")
-    _need_eval(bytes_u8, torch.uint8, "png_encode bytes")
-    if bytes_u8.dim() != 3 or bytes_u8.numel() == 0:
-        raise ValueError(f"png_encode: bytes must be a non-empty [N,H,W], got {tuple(bytes_u8.shape)}")
-    n, h, w = (int(v) for v in bytes_u8.shape)
+    mode = PNG_HUFFMAN[limits.check_member("png_encode", "huffman", huffman, PNG_HUFFMAN)]
+    n, h, w = _map_shape(bytes_u8, "png_encode", "bytes")
     L = lib()
-    cap = int(L.fosvos_png_capacity_bytes(n, h, w))
-    if out is None:
-        out = torch.empty((n, cap), dtype=torch.uint8, device=bytes_u8.device)
-    else:
-        _need_eval(out, torch.uint8, "png_encode out")
-        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cap:
-            raise ValueError(f"png_encode: out must be [{n}, >= {cap}], got {tuple(out.shape)}")
-    if lengths is None:
-        lengths = torch.empty((n,), dtype=torch.int32, device=bytes_u8.device)
-    else:
-        _need_eval(lengths, torch.int32, "png_encode lengths")
-        if tuple(lengths.shape) != (n,):
-            raise ValueError(f"png_encode: lengths must be {(n,)}, got {tuple(lengths.shape)}")
-    for t in (out, lengths):
-        if t.device != bytes_u8.device:
-            raise RuntimeError(f"png_encode: every tensor must be on {bytes_u8.device}, got one on {t.device}")
-    mode = PNG_HUFFMAN[huffman]
+    out, lengths = _file_buffers(out, lengths, n, int(L.fosvos_png_capacity_bytes(n, h, w)), bytes_u8, "png_encode")
     ws, wsn = _WS.get(L.fosvos_png_workspace_bytes(n, h, w, mode), bytes_u8.device)
-    dev, st = _ctx(bytes_u8)
-    e0 = _pb()
-    check(L.fosvos_png_encode(bytes_u8.data_ptr(), n, h, w, mode, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(), ws,
-                              wsn, dev, st), "png_encode")
-    _pe(e0, "png_encode", 0.0, 2.0 * n * h * w)
+    _launch("png_encode", bytes_u8, bytes_u8.data_ptr(), n, h, w, mode, out.data_ptr(), int(out.shape[1]), lengths.data_ptr(),
+            ws, wsn, nbytes=2.0 * n * h * w)
     return out, lengths
 
 
 # ------------------------------------------------------------------------------------------ several objects (eval.hip, png.hip)
-MAX_OBJECTS = 16
-_PALETTES = {}  # device -> the default palette (util/object_merge.davis_palette) on it
-
-
-def _same_device(what: str, first: torch.Tensor, *others: torch.Tensor) -> None:
-    for t in others:
-        if t.device != first.device:
-            raise RuntimeError(f"{what}: every tensor must be on {first.device}, got one on {t.device}")
-
-
 def merge_objects(logits: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fosvos_merge_objects: the logits fp32 [N,1,H,W] of K per-object nets (1 <= K <= 16) -> labels uint8 [N,H,W]: 0 where
     no logit of the pixel is >= 0, else 1 + the lowest k holding the largest such logit (util/object_merge.merge_labels).
     The K pointers travel by value: nothing is concatenated.  ``out`` may be a view of a caller's buffer.  Launched on the
     current stream, no synchronisation."""
-    logits = list(logits)
+    logits, (n, _, h, w), table = _logit_table(logits, "merge_objects")
+    out = _out_like(out, (n, h, w), torch.uint8, logits[0], "merge_objects")
+    _same_device("merge_objects", logits[0], *logits[1:])
     k = len(logits)
-    if not 1 <= k <= MAX_OBJECTS:
-        raise ValueError(f"merge_objects: {k} logit maps, outside [1, {MAX_OBJECTS}]")
-    for t in logits:
-        _need_eval(t, _F32, "merge_objects logits")
-    n, h, w = _logit_shape(logits[0], "merge_objects")
-    for t in logits[1:]:
-        if tuple(t.shape) != (n, 1, h, w):
-            raise ValueError(f"merge_objects: every logit map must be {(n, 1, h, w)}, got {tuple(t.shape)}")
-    if out is None:
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=logits[0].device)
-    else:
-        _need_eval(out, torch.uint8, "merge_objects out")
-        if tuple(out.shape) != (n, h, w):
-            raise ValueError(f"merge_objects: out must be {(n, h, w)}, got {tuple(out.shape)}")
-    _same_device("merge_objects", logits[0], out, *logits[1:])
-    import ctypes
-    table = (ctypes.c_void_p * k)(*[t.data_ptr() for t in logits])
-    dev, st = _ctx(logits[0])
-    e0 = _pb()
-    check(lib().fosvos_merge_objects(table, k, n, h, w, out.data_ptr(), dev, st), "merge_objects")
-    _pe(e0, "merge_objects", 0.0, (4.0 * k + 1.0) * n * h * w)
+    _launch("merge_objects", logits[0], table, k, n, h, w, out.data_ptr(), nbytes=(4.0 * k + 1.0) * n * h * w)
     return out
 
 
@@ -1504,54 +1384,23 @@ def jf_counts_labels(pred_labels: torch.Tensor, gt_labels: torch.Tensor, n_objec
     ``n_objects`` belong to no object.  ``radius`` (1..63) defaults to ceil(0.008 * diagonal).  ``out`` may be any [N,K,6]
     int32 rows, e.g. a slice of a sequence's counter tensor; the op zeroes them itself.  Launched on the current stream, no
     synchronisation."""
-    _need_eval(pred_labels, torch.uint8, "jf_counts_labels pred")
-    _need_eval(gt_labels, torch.uint8, "jf_counts_labels gt")
-    if pred_labels.dim() != 3 or pred_labels.numel() == 0:
-        raise ValueError(f"jf_counts_labels: labels must be a non-empty [N,H,W], got {tuple(pred_labels.shape)}")
-    n, h, w = (int(v) for v in pred_labels.shape)
+    _need(gt_labels, torch.uint8, "jf_counts_labels gt", ValueError)
+    n, h, w = _map_shape(pred_labels, "jf_counts_labels", "pred")
     if tuple(gt_labels.shape) != (n, h, w):
         raise ValueError(f"jf_counts_labels: gt must be {(n, h, w)}, got {tuple(gt_labels.shape)}")
-    k = int(n_objects)
-    if not 1 <= k <= MAX_OBJECTS:
-        raise ValueError(f"jf_counts_labels: n_objects {k} outside [1, {MAX_OBJECTS}]")
-    if radius is None:
-        radius = jf_default_radius(h, w)
-    radius = int(radius)
-    if not 1 <= radius <= 63:
-        raise ValueError(f"jf_counts_labels: radius {radius} outside [1, 63]")
-    if out is None:
-        out = torch.empty((n, k, 6), dtype=torch.int32, device=pred_labels.device)
-    else:
-        _need_eval(out, torch.int32, "jf_counts_labels out")
-        if tuple(out.shape) != (n, k, 6):
-            raise ValueError(f"jf_counts_labels: out must be {(n, k, 6)}, got {tuple(out.shape)}")
-    _same_device("jf_counts_labels", pred_labels, gt_labels, out)
-    L = lib()
-    ws, wsn = _WS.get(L.fosvos_jf_labels_workspace_bytes(n, k, h, w), pred_labels.device)
-    dev, st = _ctx(pred_labels)
-    e0 = _pb()
-    check(L.fosvos_jf_counts_labels(pred_labels.data_ptr(), gt_labels.data_ptr(), n, k, h, w, radius, out.data_ptr(), ws, wsn,
-                                    dev, st), "jf_counts_labels")
-    _pe(e0, "jf_counts_labels", 0.0, 2.0 * n * h * w)
+    k = limits.check_int("jf_counts_labels", "n_objects", int(n_objects), 1, MAX_OBJECTS)
+    radius = _jf_radius(radius, h, w, "jf_counts_labels")
+    out = _out_like(out, (n, k, 6), torch.int32, pred_labels, "jf_counts_labels")
+    _same_device("jf_counts_labels", pred_labels, gt_labels)
+    ws, wsn = _WS.get(lib().fosvos_jf_labels_workspace_bytes(n, k, h, w), pred_labels.device)
+    _launch("jf_counts_labels", pred_labels, pred_labels.data_ptr(), gt_labels.data_ptr(), n, k, h, w, radius, out.data_ptr(),
+            ws, wsn, nbytes=2.0 * n * h * w)
     return out
 
 
 def png_indexed_capacity(h: int, w: int) -> int:
     """Bytes ``png_encode_indexed`` reserves per frame (util/png_layout.max_file_bytes_indexed)."""
     return int(lib().fosvos_png_indexed_capacity_bytes(1, int(h), int(w)))
-
-
-def default_palette(device) -> torch.Tensor:
-    """``object_merge.davis_palette()`` as a uint8 [256,3] tensor on ``device``, uploaded once per device."""
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise RuntimeError(f"default_palette: a GPU device, got {device} (the HIP path has no CPU fallback)")
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    pal = _PALETTES.get(key)
-    if pal is None:
-        from util.object_merge import davis_palette
-        pal = _PALETTES[key] = torch.from_numpy(davis_palette()).to(device)
-    return pal
 
 
 def png_encode_indexed(labels_u8: torch.Tensor, palette: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -1561,57 +1410,30 @@ def png_encode_indexed(labels_u8: torch.Tensor, palette: Optional[torch.Tensor] 
     ``palette``: uint8 [256,3] RGB on the device; None = the DAVIS palette (``default_palette``).  ``out`` (uint8
     [N, >= png_indexed_capacity(H, W)]) and ``lengths`` (int32 [N]) may be views of a caller's buffer.  Launched on the
     current stream, no synchronisation."""
-    if huffman not in PNG_HUFFMAN:
-        raise ValueError(f"png_encode_indexed: huffman must be one of {tuple(PNG_HUFFMAN)}, got {huffman!r}")
-    _need_eval(labels_u8, torch.uint8, "png_encode_indexed labels")
-    if labels_u8.dim() != 3 or labels_u8.numel() == 0:
-        raise ValueError(f"png_encode_indexed: labels must be a non-empty [N,H,W], got {tuple(labels_u8.shape)}")
-    n, h, w = (int(v) for v in labels_u8.shape)
-    if palette is None:
-        palette = default_palette(labels_u8.device)
-    _need_eval(palette, torch.uint8, "png_encode_indexed palette")
-    if tuple(palette.shape) != (256, 3):
-        raise ValueError(f"png_encode_indexed: palette must be (256, 3), got {tuple(palette.shape)}")
+    mode = PNG_HUFFMAN[limits.check_member("png_encode_indexed", "huffman", huffman, PNG_HUFFMAN)]
+    n, h, w = _map_shape(labels_u8, "png_encode_indexed", "labels")
+    palette = _palette(palette, labels_u8.device, "png_encode_indexed")
     L = lib()
-    cap = int(L.fosvos_png_indexed_capacity_bytes(n, h, w))
-    if out is None:
-        out = torch.empty((n, cap), dtype=torch.uint8, device=labels_u8.device)
-    else:
-        _need_eval(out, torch.uint8, "png_encode_indexed out")
-        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cap:
-            raise ValueError(f"png_encode_indexed: out must be [{n}, >= {cap}], got {tuple(out.shape)}")
-    if lengths is None:
-        lengths = torch.empty((n,), dtype=torch.int32, device=labels_u8.device)
-    else:
-        _need_eval(lengths, torch.int32, "png_encode_indexed lengths")
-        if tuple(lengths.shape) != (n,):
-            raise ValueError(f"png_encode_indexed: lengths must be {(n,)}, got {tuple(lengths.shape)}")
-    _same_device("png_encode_indexed", labels_u8, palette, out, lengths)
-    mode = PNG_HUFFMAN[huffman]
+    out, lengths = _file_buffers(out, lengths, n, int(L.fosvos_png_indexed_capacity_bytes(n, h, w)), labels_u8,
+                                 "png_encode_indexed")
     ws, wsn = _WS.get(L.fosvos_png_workspace_bytes(n, h, w, mode), labels_u8.device)
-    dev, st = _ctx(labels_u8)
-    e0 = _pb()
-    check(L.fosvos_png_encode_indexed(labels_u8.data_ptr(), palette.data_ptr(), n, h, w, mode, out.data_ptr(),
-                                      int(out.shape[1]), lengths.data_ptr(), ws, wsn, dev, st), "png_encode_indexed")
-    _pe(e0, "png_encode_indexed", 0.0, 2.0 * n * h * w)
+    _launch("png_encode_indexed", labels_u8, labels_u8.data_ptr(), palette.data_ptr(), n, h, w, mode, out.data_ptr(),
+            int(out.shape[1]), lengths.data_ptr(), ws, wsn, nbytes=2.0 * n * h * w)
     return out, lengths
 
 
 # ------------------------------------------------------------------------------------------ JPEG files (jpeg.hip)
-JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
+JPEG_SUBSAMPLINGS = limits.JPEG_SUBSAMPLINGS
 
 
-def _jpeg_subsampling(subsampling, what: str) -> bool:
-    """True for '4:2:0', False for '4:4:4', ValueError for anything else."""
-    if subsampling not in JPEG_SUBSAMPLINGS:
-        raise ValueError(f"{what}: subsampling must be one of {JPEG_SUBSAMPLINGS}, got {subsampling!r}")
-    return subsampling == '4:2:0'
+def _jpeg_sampling(subsampling, what: str) -> int:
+    """The C ABI's code of a chroma sampling: 420 for '4:2:0', 444 for '4:4:4', ValueError for anything else."""
+    return 420 if limits.check_member(what, "subsampling", subsampling, JPEG_SUBSAMPLINGS) == '4:2:0' else 444
 
 
 def jpeg_capacity(h: int, w: int, components: int, subsampling: str = '4:4:4') -> int:
     """Bytes ``jpeg_encode`` reserves per frame: the layout's size bound (util/jpeg_layout.capacity)."""
-    sampling = 420 if _jpeg_subsampling(subsampling, "jpeg_capacity") else 444
-    cap = int(lib().fosvos_jpeg_capacity_bytes(1, int(h), int(w), int(components), sampling))
+    cap = int(lib().fosvos_jpeg_capacity_bytes(1, int(h), int(w), int(components), _jpeg_sampling(subsampling, "jpeg_capacity")))
     if cap == 0:
         raise ValueError(f"jpeg_capacity: h, w in 1..65535 and components 1 or 3, got {h}, {w}, {components}")
     return cap
@@ -1624,39 +1446,21 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 90, out: Optional[torch.
     bytes behind it are not written.  ``out`` (uint8 [N, >= jpeg_capacity(H, W, components, subsampling)]) and ``lengths``
     (int32 [N]) may be views of a caller's buffer.  ``subsampling='4:2:0'`` halves the chroma
     planes of a colour frame; a grey frame ignores it.  Launched on the current stream, no synchronisation."""
-    sampling = 420 if _jpeg_subsampling(subsampling, "jpeg_encode") else 444
-    _need_eval(frames_u8, torch.uint8, "jpeg_encode frames")
+    sampling = _jpeg_sampling(subsampling, "jpeg_encode")
+    _need(frames_u8, torch.uint8, "jpeg_encode frames", ValueError)
     if frames_u8.numel() == 0 or not (frames_u8.dim() == 3 or (frames_u8.dim() == 4 and frames_u8.shape[3] == 3)):
         raise ValueError(f"jpeg_encode: frames must be a non-empty [N,H,W,3] or [N,H,W], got {tuple(frames_u8.shape)}")
-    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
-        raise ValueError(f"jpeg_encode: quality must be an integer in 1..100, got {quality!r}")
+    quality = limits.check_int("jpeg_encode", "quality", quality, *limits.JPEG_QUALITY, integral=True)
     n, h, w = (int(v) for v in frames_u8.shape[:3])
     comps = 3 if frames_u8.dim() == 4 else 1
     L = lib()
     cap = int(L.fosvos_jpeg_capacity_bytes(n, h, w, comps, sampling))
     if cap == 0:
         raise ValueError(f"jpeg_encode: H and W must be at most 65535, got {h}, {w}")
-    if out is None:
-        out = torch.empty((n, cap), dtype=torch.uint8, device=frames_u8.device)
-    else:
-        _need_eval(out, torch.uint8, "jpeg_encode out")
-        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cap:
-            raise ValueError(f"jpeg_encode: out must be [{n}, >= {cap}], got {tuple(out.shape)}")
-    if lengths is None:
-        lengths = torch.empty((n,), dtype=torch.int32, device=frames_u8.device)
-    else:
-        _need_eval(lengths, torch.int32, "jpeg_encode lengths")
-        if tuple(lengths.shape) != (n,):
-            raise ValueError(f"jpeg_encode: lengths must be {(n,)}, got {tuple(lengths.shape)}")
-    for t in (out, lengths):
-        if t.device != frames_u8.device:
-            raise RuntimeError(f"jpeg_encode: every tensor must be on {frames_u8.device}, got one on {t.device}")
+    out, lengths = _file_buffers(out, lengths, n, cap, frames_u8, "jpeg_encode")
     ws, wsn = _WS.get(L.fosvos_jpeg_workspace_bytes(n, h, w, comps, sampling), frames_u8.device)
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
-    check(L.fosvos_jpeg_encode(frames_u8.data_ptr(), n, h, w, comps, sampling, int(quality), out.data_ptr(), int(out.shape[1]),
-                               lengths.data_ptr(), ws, wsn, dev, st), "jpeg_encode")
-    _pe(e0, "jpeg_encode", 0.0, 2.0 * n * h * w * comps)
+    _launch("jpeg_encode", frames_u8, frames_u8.data_ptr(), n, h, w, comps, sampling, quality, out.data_ptr(), int(out.shape[1]),
+            lengths.data_ptr(), ws, wsn, nbytes=2.0 * n * h * w * comps)
     return out, lengths
 
 
@@ -1684,7 +1488,7 @@ def _jpeg_decode_plans(files, plans):
 def jpeg_decode_workspace(n: int, h: int, w: int, components: int, subsampling: str = '4:4:4') -> int:
     """Bytes of scratch ``jpeg_decode`` needs for ``n`` files of this shape (fosvos_jpeg_decode_workspace_bytes)."""
     need = int(lib().fosvos_jpeg_decode_workspace_bytes(int(n), int(h), int(w), int(components),
-                                                        420 if _jpeg_subsampling(subsampling, "jpeg_decode_workspace") else 444))
+                                                        _jpeg_sampling(subsampling, "jpeg_decode_workspace")))
     if need == 0:
         raise ValueError(f"jpeg_decode_workspace: n, h, w in 1..65535, components 1 or 3, 4:2:0 from w = 5, got {n}, {h}, {w}, "
                          f"{components}, {subsampling}")
@@ -1742,14 +1546,8 @@ def jpeg_decode(files: Sequence[bytes], out: Optional[torch.Tensor] = None, stat
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     shape = (n, h, w, 3) if comps == 3 else (n, h, w)
-    for t, dtype, want, what in ((out, torch.uint8, shape, "out"), (status, torch.int32, (n,), "status")):
-        if t is None:
-            continue
-        _need_eval(t, dtype, f"jpeg_decode {what}")
-        if tuple(t.shape) != tuple(want):
-            raise ValueError(f"jpeg_decode: {what} must be {tuple(want)}, got {tuple(t.shape)}")
-        if t.device != device:
-            raise RuntimeError(f"jpeg_decode: every tensor must be on {device}, got {what} on {t.device}")
+    out = _out_like(out, shape, torch.uint8, device, "jpeg_decode")
+    status = _out_like(status, (n,), torch.int32, device, "jpeg_decode", "status")
     L = lib()
     sampling = jpeg_read.SAMPLING_CODE[p0.subsampling]
     need = int(L.fosvos_jpeg_decode_workspace_bytes(n, h, w, comps, sampling))
@@ -1758,17 +1556,10 @@ def jpeg_decode(files: Sequence[bytes], out: Optional[torch.Tensor] = None, stat
     host, n_seg, off_tables, off_bytes, n_bytes = jpeg_decode_pack(files, plans)
     with torch.cuda.device(device):
         dev_buf = host.to(device, non_blocking=True)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=device)
-        if status is None:
-            status = torch.empty((n,), dtype=torch.int32, device=device)
-        ws, wsn = _WS.get(need, device)
-        dev, st = _ctx(out)
-        e0 = _pb()
         base = dev_buf.data_ptr()
-        check(L.fosvos_jpeg_decode(base + off_bytes, n_bytes, base, n_seg, base + off_tables, n, h, w, comps, sampling,
-                                   out.data_ptr(), status.data_ptr(), ws, wsn, dev, st), "jpeg_decode")
-        _pe(e0, "jpeg_decode", 0.0, float(n_bytes) + float(out.numel()))
+        ws, wsn = _WS.get(need, device)
+        _launch("jpeg_decode", out, base + off_bytes, n_bytes, base, n_seg, base + off_tables, n, h, w, comps, sampling,
+                out.data_ptr(), status.data_ptr(), ws, wsn, nbytes=float(n_bytes) + float(out.numel()))
     return out, status
 
 
@@ -1781,31 +1572,24 @@ def _mean_bgr():
     """The dataset mean the frames lose in front of the net: the one constant of dataloaders/davis_2016.py."""
     global _MEAN_BGR
     if _MEAN_BGR is None:
-        import ctypes
         from dataloaders.davis_2016 import MEANVAL
         _MEAN_BGR = (ctypes.c_float * 3)(*MEANVAL)
     return _MEAN_BGR
 
 
 def _frame_shape(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
-    _need_eval(frames, torch.uint8, f"{what} frames")
+    _need(frames, torch.uint8, f"{what} frames", ValueError)
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
         raise ValueError(f"{what}: frames must be a non-empty [N,H,W,3], got {tuple(frames.shape)}")
     return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
 
 
-def _out_like(out: Optional[torch.Tensor], shape, dtype, like: torch.Tensor, what: str) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=like.device)
-    _need_eval(out, dtype, f"{what} out")
-    if tuple(out.shape) != tuple(shape):
-        raise ValueError(f"{what}: out must be {tuple(shape)}, got {tuple(out.shape)}")
-    if out.device != like.device:
-        raise RuntimeError(f"{what}: every tensor must be on {like.device}, got one on {out.device}")
-    return out
-
-
-MAX_FRAME_SIDE = 8192  # of a scaled call (util/frame_resample.MAX_SIDE)
+def _paint(what: str, color, alpha, overlay, boolean_mask) -> Tuple[int, float, int]:
+    """What the single-object paint launches take beside their tensors: (the channel of ``color``, ``alpha`` as a finite
+    float >= 0, the mode: 0 overlay of the mask, 1 of the probability, 2 / 3 the mask / the probability alone)."""
+    channel = OVERLAY_CHANNEL[limits.check_member(what, "color", color, OVERLAY_CHANNEL)]
+    alpha = limits.check_real(what, "alpha", float(alpha), 0.0)
+    return channel, alpha, (0 if overlay else 2) + (0 if boolean_mask else 1)
 
 
 def _net_size(net_size, h: int, w: int, what: str) -> Optional[Tuple[int, int]]:
@@ -1813,13 +1597,7 @@ def _net_size(net_size, h: int, w: int, what: str) -> Optional[Tuple[int, int]]:
     launch), else (Hn, Wn) checked against the frames."""
     if net_size is None:
         return None
-    try:
-        hn, wn = net_size
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: net_size must be a pair (Hn, Wn), got {net_size!r}") from None
-    for v in (hn, wn):
-        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
-            raise ValueError(f"{what}: net_size must be a pair of positive ints, got {net_size!r}")
+    hn, wn = limits.check_pair(what, "net_size", net_size, "(Hn, Wn)")
     if hn > h or wn > w:
         raise ValueError(f"{what}: the net's size {(hn, wn)} exceeds the frames' {(h, w)}")
     if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
@@ -1841,18 +1619,12 @@ def frame_prep(frames_u8: torch.Tensor, mirror: bool = False, out: Optional[torc
     if scaled is not None:
         hn, wn = scaled
         out = _out_like(out, (n, 3, hn, wn), _F32, frames_u8, "frame_prep")
-        dev, st = _ctx(frames_u8)
-        e0 = _pb()
-        check(lib().fosvos_frame_prep_scaled(frames_u8.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, _mean_bgr(),
-                                             out.data_ptr(), dev, st), "frame_prep_scaled")
-        _pe(e0, "frame_prep_scaled", 0.0, 3.0 * n * h * w + 12.0 * n * hn * wn)
+        _launch("frame_prep_scaled", frames_u8, frames_u8.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, _mean_bgr(),
+                out.data_ptr(), nbytes=3.0 * n * h * w + 12.0 * n * hn * wn)
         return out
     out = _out_like(out, (n, 3, h, w), _F32, frames_u8, "frame_prep")
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
-    check(lib().fosvos_frame_prep(frames_u8.data_ptr(), n, h, w, 1 if mirror else 0, _mean_bgr(), out.data_ptr(), dev, st),
-          "frame_prep")
-    _pe(e0, "frame_prep", 0.0, 15.0 * n * h * w)
+    _launch("frame_prep", frames_u8, frames_u8.data_ptr(), n, h, w, 1 if mirror else 0, _mean_bgr(), out.data_ptr(),
+            nbytes=15.0 * n * h * w)
     return out
 
 
@@ -1871,51 +1643,33 @@ def overlay(frames_u8: torch.Tensor, logits: torch.Tensor, mirror: bool = False,
     n, h, w = _frame_shape(frames_u8, "overlay")
     scaled = _net_size(net_size, h, w, "overlay")
     hn, wn = scaled if scaled is not None else (h, w)
-    _need_eval(logits, _F32, "overlay logits")
+    _need(logits, _F32, "overlay logits", ValueError)
     if tuple(logits.shape) != (n, 1, hn, wn):
         raise ValueError(f"overlay: logits must be {(n, 1, hn, wn)}, got {tuple(logits.shape)}")
-    if logits.device != frames_u8.device:
-        raise RuntimeError(f"overlay: every tensor must be on {frames_u8.device}, got one on {logits.device}")
-    if color not in OVERLAY_CHANNEL:
-        raise ValueError(f"overlay: color must be one of {tuple(OVERLAY_CHANNEL)}, got {color!r}")
-    alpha = float(alpha)
-    if not (alpha >= 0.0 and alpha != float("inf")):
-        raise ValueError(f"overlay: alpha must be a finite number >= 0, got {alpha!r}")
+    _same_device("overlay", frames_u8, logits)
+    channel, alpha, mode = _paint("overlay", color, alpha, overlay, boolean_mask)
     out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay")
-    mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
     if scaled is not None:
-        check(lib().fosvos_overlay_scaled(frames_u8.data_ptr(), logits.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, mode,
-                                          OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st), "overlay_scaled")
-        _pe(e0, "overlay_scaled", 0.0, (6.0 if overlay else 1.0) * n * h * w + 4.0 * n * hn * wn)
+        _launch("overlay_scaled", frames_u8, frames_u8.data_ptr(), logits.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, mode,
+                channel, alpha, out.data_ptr(), nbytes=(6.0 if overlay else 1.0) * n * h * w + 4.0 * n * hn * wn)
         return out
-    check(lib().fosvos_overlay(frames_u8.data_ptr(), logits.data_ptr(), n, h, w, 1 if mirror else 0, mode,
-                               OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st), "overlay")
-    _pe(e0, "overlay", 0.0, (10.0 if overlay else 5.0) * n * h * w)
+    _launch("overlay", frames_u8, frames_u8.data_ptr(), logits.data_ptr(), n, h, w, 1 if mirror else 0, mode, channel, alpha,
+            out.data_ptr(), nbytes=(10.0 if overlay else 5.0) * n * h * w)
     return out
 
 
 # edge-aware upsampling: the guided filter on the frame (util/guided_upsample.py states both)
-GUIDED_MAX_RADIUS = 8
-GUIDED_EPS_RANGE = (1e-3, 1e9)
-GUIDED_MAX_CLIP = 1e4
+GUIDED_MAX_RADIUS = limits.GUIDED_MAX_RADIUS
+GUIDED_EPS_RANGE = limits.GUIDED_EPS_RANGE
+GUIDED_MAX_CLIP = limits.GUIDED_MAX_CLIP
 _F64 = torch.float64
-
-
-def _real_number(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
 
 
 def guided_params(radius, eps, clip, what: str = "guided_coefficients") -> Tuple[int, float, float]:
     """The filter's three parameters, checked against the ranges the kernel and the numpy definition take."""
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= GUIDED_MAX_RADIUS:
-        raise ValueError(f"{what}: radius must be an integer in 1..{GUIDED_MAX_RADIUS}, got {radius!r}")
-    if not _real_number(eps) or not GUIDED_EPS_RANGE[0] <= eps <= GUIDED_EPS_RANGE[1]:
-        raise ValueError(f"{what}: eps must be a finite number in [{GUIDED_EPS_RANGE[0]:g}, {GUIDED_EPS_RANGE[1]:g}], got {eps!r}")
-    if not _real_number(clip) or not 0.0 < clip <= GUIDED_MAX_CLIP:
-        raise ValueError(f"{what}: clip must be a finite number in (0, {GUIDED_MAX_CLIP:g}], got {clip!r}")
-    return radius, float(eps), float(clip)
+    return (limits.check_int(what, "radius", radius, 1, GUIDED_MAX_RADIUS),
+            limits.check_real(what, "eps", eps, *GUIDED_EPS_RANGE),
+            limits.check_real(what, "clip", clip, 0.0, GUIDED_MAX_CLIP, lo_open=True))
 
 
 def guided_coefficients(image: torch.Tensor, logits: torch.Tensor, radius: int = 4, eps: float = 400.0, clip: float = 6.0,
@@ -1924,25 +1678,21 @@ def guided_coefficients(image: torch.Tensor, logits: torch.Tensor, radius: int =
     -> fp64 [N,2,Hn,Wn], the smoothed coefficients [abar, bbar] of the guided filter whose guide is the sum of the image's
     planes and whose target is the logits clipped to ``[-clip, clip]`` (util/guided_upsample.coefficients, bit for bit).  Two
     launches on the current stream, no synchronisation; the unsmoothed maps live in the stream's workspace."""
-    _need_eval(image, _F32, "guided_coefficients image")
+    _need(image, _F32, "guided_coefficients image", ValueError)
     if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0:
         raise ValueError(f"guided_coefficients: image must be a non-empty [N,3,Hn,Wn], got {tuple(image.shape)}")
     n, hn, wn = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
     if hn > MAX_FRAME_SIDE or wn > MAX_FRAME_SIDE:
         raise ValueError(f"guided_coefficients: maps may have sides of up to {MAX_FRAME_SIDE}, got {(hn, wn)}")
-    _need_eval(logits, _F32, "guided_coefficients logits")
+    _need(logits, _F32, "guided_coefficients logits", ValueError)
     if tuple(logits.shape) != (n, 1, hn, wn):
         raise ValueError(f"guided_coefficients: logits must be {(n, 1, hn, wn)}, got {tuple(logits.shape)}")
-    if logits.device != image.device:
-        raise RuntimeError(f"guided_coefficients: every tensor must be on {image.device}, got one on {logits.device}")
+    _same_device("guided_coefficients", image, logits)
     radius, eps, clip = guided_params(radius, eps, clip)
     out = _out_like(out, (n, 2, hn, wn), _F64, image, "guided_coefficients")
     ws, wsn = _WS.get(int(lib().fosvos_guided_coefficients_workspace_bytes(n, hn, wn)), image.device)
-    dev, st = _ctx(image)
-    e0 = _pb()
-    check(lib().fosvos_guided_coefficients(image.data_ptr(), logits.data_ptr(), n, hn, wn, radius, eps, clip, out.data_ptr(),
-                                           ws, wsn, dev, st), "guided_coefficients")
-    _pe(e0, "guided_coefficients", 0.0, (16.0 + 3 * 16.0) * n * hn * wn)
+    _launch("guided_coefficients", image, image.data_ptr(), logits.data_ptr(), n, hn, wn, radius, eps, clip, out.data_ptr(), ws, wsn,
+            nbytes=(16.0 + 3 * 16.0) * n * hn * wn)
     return out
 
 
@@ -1954,31 +1704,22 @@ def overlay_guided(frames_u8: torch.Tensor, coeff: torch.Tensor, mirror: bool = 
     coefficients', no larger than the frames; the mask of ``overlay=False`` is the mirrored picture's with ``mirror``.  One
     launch, no synchronisation."""
     n, h, w = _frame_shape(frames_u8, "overlay_guided")
-    _need_eval(coeff, _F64, "overlay_guided coeff")
+    _need(coeff, _F64, "overlay_guided coeff", ValueError)
     if coeff.dim() != 4 or coeff.shape[0] != n or coeff.shape[1] != 2 or coeff.numel() == 0:
         raise ValueError(f"overlay_guided: coeff must be a non-empty {(n, 2, 'Hn', 'Wn')}, got {tuple(coeff.shape)}")
     hn, wn = _roi_net_size((int(coeff.shape[2]), int(coeff.shape[3])), h, w, "overlay_guided")
-    if coeff.device != frames_u8.device:
-        raise RuntimeError(f"overlay_guided: every tensor must be on {frames_u8.device}, got one on {coeff.device}")
-    if color not in OVERLAY_CHANNEL:
-        raise ValueError(f"overlay_guided: color must be one of {tuple(OVERLAY_CHANNEL)}, got {color!r}")
-    alpha = float(alpha)
-    if not (alpha >= 0.0 and alpha != float("inf")):
-        raise ValueError(f"overlay_guided: alpha must be a finite number >= 0, got {alpha!r}")
+    _same_device("overlay_guided", frames_u8, coeff)
+    channel, alpha, mode = _paint("overlay_guided", color, alpha, overlay, boolean_mask)
     out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay_guided")
-    mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
-    check(lib().fosvos_overlay_guided(frames_u8.data_ptr(), coeff.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, mode,
-                                      OVERLAY_CHANNEL[color], alpha, _mean_bgr(), out.data_ptr(), dev, st), "overlay_guided")
-    _pe(e0, "overlay_guided", 0.0, (6.0 if overlay else 4.0) * n * h * w + 16.0 * n * hn * wn)
+    _launch("overlay_guided", frames_u8, frames_u8.data_ptr(), coeff.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0, mode, channel,
+            alpha, _mean_bgr(), out.data_ptr(), nbytes=(6.0 if overlay else 4.0) * n * h * w + 16.0 * n * hn * wn)
     return out
 
 
 # following the object: the net on a window of the frame (util/frame_roi.py states all three)
-ROI_MAX_LEVELS = 64
-ROI_MAX_PAD = 4095
-ROI_MAX_MARGIN = 4.0
+ROI_MAX_LEVELS = limits.ROI_MAX_LEVELS
+ROI_MAX_PAD = limits.ROI_MAX_PAD
+ROI_MAX_MARGIN = limits.ROI_MAX_MARGIN
 
 
 def _roi_net_size(net_size, h: int, w: int, what: str) -> Tuple[int, int]:
@@ -1990,19 +1731,16 @@ def _roi_net_size(net_size, h: int, w: int, what: str) -> Tuple[int, int]:
 
 
 def _windows(windows: torch.Tensor, n: int, like: torch.Tensor, what: str) -> torch.Tensor:
-    _need_eval(windows, torch.int32, f"{what} windows")
+    _need(windows, torch.int32, f"{what} windows", ValueError)
     if tuple(windows.shape) != (n, 4):
         raise ValueError(f"{what}: windows must be int32 {(n, 4)} = (y0, x0, Hw, Ww) a frame, got {tuple(windows.shape)}")
-    if windows.device != like.device:
-        raise RuntimeError(f"{what}: every tensor must be on {like.device}, got one on {windows.device}")
+    _same_device(what, like, windows)
     return windows
 
 
 def roi_margin_permille(margin, what: str = "window_next") -> int:
     """``margin`` (a finite number in [0, 4], a share of the box's longer side) as the integer the kernel pads with."""
-    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not 0.0 <= margin <= ROI_MAX_MARGIN:
-        raise ValueError(f"{what}: margin must be a finite number in [0, {ROI_MAX_MARGIN:g}], got {margin!r}")
-    return int(round(1000 * margin))
+    return int(round(1000 * limits.check_real(what, "margin", margin, 0.0, ROI_MAX_MARGIN)))
 
 
 def frame_prep_window(frames_u8: torch.Tensor, windows: torch.Tensor, net_size: Tuple[int, int], mirror: bool = False,
@@ -2015,11 +1753,8 @@ def frame_prep_window(frames_u8: torch.Tensor, windows: torch.Tensor, net_size: 
     hn, wn = _roi_net_size(net_size, h, w, "frame_prep_window")
     _windows(windows, n, frames_u8, "frame_prep_window")
     out = _out_like(out, (n, 3, hn, wn), _F32, frames_u8, "frame_prep_window")
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
-    check(lib().fosvos_frame_prep_window(frames_u8.data_ptr(), windows.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0,
-                                         _mean_bgr(), out.data_ptr(), dev, st), "frame_prep_window")
-    _pe(e0, "frame_prep_window", 0.0, 3.0 * n * h * w + 12.0 * n * hn * wn)  # (at the most: the whole-frame window)
+    _launch("frame_prep_window", frames_u8, frames_u8.data_ptr(), windows.data_ptr(), n, h, w, hn, wn, 1 if mirror else 0,
+            _mean_bgr(), out.data_ptr(), nbytes=3.0 * n * h * w + 12.0 * n * hn * wn)  # (at the most: the whole-frame window)
     return out
 
 
@@ -2030,26 +1765,17 @@ def overlay_window(frames_u8: torch.Tensor, logits: torch.Tensor, windows: torch
     [N,4] in device memory): interpolated up to the window's size inside it, nothing is object outside it
     (util/frame_roi.py states the bytes).  The net's size is the logits'.  One launch, no synchronisation."""
     n, h, w = _frame_shape(frames_u8, "overlay_window")
-    _need_eval(logits, _F32, "overlay_window logits")
+    _need(logits, _F32, "overlay_window logits", ValueError)
     if logits.dim() != 4 or logits.shape[0] != n or logits.shape[1] != 1 or logits.numel() == 0:
         raise ValueError(f"overlay_window: logits must be a non-empty {(n, 1, 'Hn', 'Wn')}, got {tuple(logits.shape)}")
     hn, wn = _roi_net_size((int(logits.shape[2]), int(logits.shape[3])), h, w, "overlay_window")
-    if logits.device != frames_u8.device:
-        raise RuntimeError(f"overlay_window: every tensor must be on {frames_u8.device}, got one on {logits.device}")
+    _same_device("overlay_window", frames_u8, logits)
     _windows(windows, n, frames_u8, "overlay_window")
-    if color not in OVERLAY_CHANNEL:
-        raise ValueError(f"overlay_window: color must be one of {tuple(OVERLAY_CHANNEL)}, got {color!r}")
-    alpha = float(alpha)
-    if not (alpha >= 0.0 and alpha != float("inf")):
-        raise ValueError(f"overlay_window: alpha must be a finite number >= 0, got {alpha!r}")
+    channel, alpha, mode = _paint("overlay_window", color, alpha, overlay, boolean_mask)
     out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay_window")
-    mode = (0 if overlay else 2) + (0 if boolean_mask else 1)
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
-    check(lib().fosvos_overlay_window(frames_u8.data_ptr(), logits.data_ptr(), windows.data_ptr(), n, h, w, hn, wn,
-                                      1 if mirror else 0, mode, OVERLAY_CHANNEL[color], alpha, out.data_ptr(), dev, st),
-          "overlay_window")
-    _pe(e0, "overlay_window", 0.0, (6.0 if overlay else 1.0) * n * h * w + 4.0 * n * hn * wn)
+    _launch("overlay_window", frames_u8, frames_u8.data_ptr(), logits.data_ptr(), windows.data_ptr(), n, h, w, hn, wn,
+            1 if mirror else 0, mode, channel, alpha, out.data_ptr(),
+            nbytes=(6.0 if overlay else 1.0) * n * h * w + 4.0 * n * hn * wn)
     return out
 
 
@@ -2059,29 +1785,18 @@ def window_next(logits: torch.Tensor, windows: torch.Tensor, frame_size: Tuple[i
     windows of the next frames, int32 [N,4] (``out`` may be ``windows``): the box of ``logits >= 0``, padded by ``min_pad +
     margin * its longer side``, in the smallest of the ``levels + 1`` sizes between the net's and the frame's that holds it
     (util/frame_roi.next_window, exactly); no object: the whole frame.  Two launches, no synchronisation."""
-    _need_eval(logits, _F32, "window_next logits")
+    _need(logits, _F32, "window_next logits", ValueError)
     n, hn, wn = _logit_shape(logits, "window_next")
-    try:
-        hf, wf = frame_size
-    except (TypeError, ValueError):
-        raise ValueError(f"window_next: frame_size must be a pair (Hf, Wf), got {frame_size!r}") from None
-    for v in (hf, wf):
-        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
-            raise ValueError(f"window_next: frame_size must be a pair of positive ints, got {frame_size!r}")
+    hf, wf = limits.check_pair("window_next", "frame_size", frame_size, "(Hf, Wf)")
     _roi_net_size((hn, wn), hf, wf, "window_next")
     _windows(windows, n, logits, "window_next")
-    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= ROI_MAX_LEVELS:
-        raise ValueError(f"window_next: levels must be an integer in 1..{ROI_MAX_LEVELS}, got {levels!r}")
-    if isinstance(min_pad, bool) or not isinstance(min_pad, int) or not 0 <= min_pad <= ROI_MAX_PAD:
-        raise ValueError(f"window_next: min_pad must be an integer in 0..{ROI_MAX_PAD}, got {min_pad!r}")
+    limits.check_int("window_next", "levels", levels, 1, ROI_MAX_LEVELS)
+    limits.check_int("window_next", "min_pad", min_pad, 0, ROI_MAX_PAD)
     permille = roi_margin_permille(margin)
     out = _out_like(out, (n, 4), torch.int32, logits, "window_next")
     ws, wsn = _WS.get(int(lib().fosvos_window_next_workspace_bytes(n)), logits.device)
-    dev, st = _ctx(logits)
-    e0 = _pb()
-    check(lib().fosvos_window_next(logits.data_ptr(), windows.data_ptr(), n, hf, wf, hn, wn, levels, permille, min_pad,
-                                   out.data_ptr(), ws, wsn, dev, st), "window_next")
-    _pe(e0, "window_next", 0.0, 4.0 * n * hn * wn)
+    _launch("window_next", logits, logits.data_ptr(), windows.data_ptr(), n, hf, wf, hn, wn, levels, permille, min_pad,
+            out.data_ptr(), ws, wsn, nbytes=4.0 * n * hn * wn)
     return out
 
 
@@ -2102,37 +1817,19 @@ def overlay_objects(frames_u8: torch.Tensor, logits: Sequence[torch.Tensor], mir
     n, h, w = _frame_shape(frames_u8, "overlay_objects")
     scaled = _net_size(net_size, h, w, "overlay_objects")
     hn, wn = scaled if scaled is not None else (h, w)
-    logits = list(logits)
-    k = len(logits)
-    if not 1 <= k <= MAX_OBJECTS:
-        raise ValueError(f"overlay_objects: {k} logit maps, outside [1, {MAX_OBJECTS}]")
-    for t in logits:
-        _need_eval(t, _F32, "overlay_objects logits")
-        if tuple(t.shape) != (n, 1, hn, wn):
-            raise ValueError(f"overlay_objects: every logit map must be {(n, 1, hn, wn)}, got {tuple(t.shape)}")
-    alpha = float(alpha)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"overlay_objects: alpha must be a finite number in [0, 1], got {alpha!r}")
-    if palette is None:
-        palette = default_palette(frames_u8.device)
-    _need_eval(palette, torch.uint8, "overlay_objects palette")
-    if tuple(palette.shape) != (256, 3):
-        raise ValueError(f"overlay_objects: palette must be (256, 3), got {tuple(palette.shape)}")
+    logits, _, table = _logit_table(logits, "overlay_objects", (n, 1, hn, wn))
+    alpha = limits.check_real("overlay_objects", "alpha", float(alpha), 0.0, 1.0)
+    palette = _palette(palette, frames_u8.device, "overlay_objects")
     out = _out_like(out, (n, h, w, 3) if overlay else (n, h, w), torch.uint8, frames_u8, "overlay_objects")
-    _same_device("overlay_objects", frames_u8, palette, *logits)
+    _same_device("overlay_objects", frames_u8, *logits)
     if not overlay and scaled is None:
         return merge_objects(logits, out=out)
-    import ctypes
-    table = (ctypes.c_void_p * k)(*[t.data_ptr() for t in logits])
-    dev, st = _ctx(frames_u8)
-    e0 = _pb()
+    k = len(logits)
     if scaled is not None:
-        check(lib().fosvos_overlay_objects_scaled(frames_u8.data_ptr(), table, k, n, h, w, hn, wn, 1 if mirror else 0,
-                                                  0 if overlay else 1, palette.data_ptr(), alpha, out.data_ptr(), dev, st),
-              "overlay_objects_scaled")
-        _pe(e0, "overlay_objects_scaled", 0.0, (6.0 if overlay else 1.0) * n * h * w + 4.0 * k * n * hn * wn)
+        _launch("overlay_objects_scaled", frames_u8, frames_u8.data_ptr(), table, k, n, h, w, hn, wn, 1 if mirror else 0,
+                0 if overlay else 1, palette.data_ptr(), alpha, out.data_ptr(),
+                nbytes=(6.0 if overlay else 1.0) * n * h * w + 4.0 * k * n * hn * wn)
         return out
-    check(lib().fosvos_overlay_objects(frames_u8.data_ptr(), table, k, n, h, w, 1 if mirror else 0, palette.data_ptr(), alpha,
-                                       out.data_ptr(), dev, st), "overlay_objects")
-    _pe(e0, "overlay_objects", 0.0, (4.0 * k + 6.0) * n * h * w)
+    _launch("overlay_objects", frames_u8, frames_u8.data_ptr(), table, k, n, h, w, 1 if mirror else 0, palette.data_ptr(), alpha,
+            out.data_ptr(), nbytes=(4.0 * k + 6.0) * n * h * w)
     return out

@@ -5,13 +5,15 @@ The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleani
 passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
 and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3).
 
-No torch and no library load here: importable anywhere.
+No torch and no library load here: importable anywhere.  The ranges and the scalar checks are ``limits``'.
 """
 from __future__ import annotations
 
 import os
 from dataclasses import dataclass
 from typing import Mapping, Optional
+
+from . import limits
 
 
 def _on(environ: Mapping[str, str], name: str) -> bool:
@@ -143,16 +145,13 @@ class CleanOptions:
     fill: float = -100.0
 
     def __post_init__(self) -> None:
-        if isinstance(self.min_area, bool) or not isinstance(self.min_area, int) or not 0 <= self.min_area < 1 << 31:
-            raise ValueError(f"CleanOptions: min_area must be an integer >= 0, got {self.min_area!r}")
+        limits.check_int("CleanOptions", "min_area", self.min_area, 0, limits.CLEAN_MAX_AREA)
         if not isinstance(self.largest, bool):
             raise ValueError(f"CleanOptions: largest must be a bool, got {self.largest!r}")
-        r = self.temporal_radius
-        if r is not None and (isinstance(r, bool) or not isinstance(r, int) or not 0 <= r <= 63):
-            raise ValueError(f"CleanOptions: temporal_radius must be None or an integer in 0..63, got {r!r}")
-        if isinstance(self.fill, bool) or not isinstance(self.fill, (int, float)) \
-                or not -3.4028234663852886e38 <= self.fill < 0:
-            raise ValueError(f"CleanOptions: fill must be finite and negative, got {self.fill!r}")
+        if self.temporal_radius is not None:
+            limits.check_int("CleanOptions", "temporal_radius", self.temporal_radius, 0, limits.CLEAN_MAX_RADIUS,
+                             expect=f"None or an integer in 0..{limits.CLEAN_MAX_RADIUS}")
+        limits.check_real("CleanOptions", "fill", self.fill, *limits.FILL_RANGE, hi_open=True, expect="finite and negative")
 
     @property
     def chain(self) -> bool:
@@ -177,12 +176,9 @@ class RoiOptions:
     min_pad: int = 16
 
     def __post_init__(self) -> None:
-        if isinstance(self.levels, bool) or not isinstance(self.levels, int) or not 1 <= self.levels <= 64:
-            raise ValueError(f"RoiOptions: levels must be an integer in 1..64, got {self.levels!r}")
-        if isinstance(self.margin, bool) or not isinstance(self.margin, (int, float)) or not 0.0 <= self.margin <= 4.0:
-            raise ValueError(f"RoiOptions: margin must be a finite number in [0, 4], got {self.margin!r}")
-        if isinstance(self.min_pad, bool) or not isinstance(self.min_pad, int) or not 0 <= self.min_pad <= 4095:
-            raise ValueError(f"RoiOptions: min_pad must be an integer in 0..4095, got {self.min_pad!r}")
+        limits.check_int("RoiOptions", "levels", self.levels, 1, limits.ROI_MAX_LEVELS)
+        limits.check_real("RoiOptions", "margin", self.margin, 0.0, limits.ROI_MAX_MARGIN)
+        limits.check_int("RoiOptions", "min_pad", self.min_pad, 0, limits.ROI_MAX_PAD)
 
     @property
     def margin_permille(self) -> int:
@@ -191,10 +187,6 @@ class RoiOptions:
 
     def as_dict(self) -> dict:
         return {'levels': self.levels, 'margin': float(self.margin), 'min_pad': self.min_pad}
-
-
-def _real(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
 
 
 @dataclass(frozen=True)
@@ -213,12 +205,9 @@ class RefineOptions:
     clip: float = 6.0
 
     def __post_init__(self) -> None:
-        if isinstance(self.radius, bool) or not isinstance(self.radius, int) or not 1 <= self.radius <= 8:
-            raise ValueError(f"RefineOptions: radius must be an integer in 1..8, got {self.radius!r}")
-        if not _real(self.eps) or not 1e-3 <= self.eps <= 1e9:
-            raise ValueError(f"RefineOptions: eps must be a finite number in [1e-3, 1e9], got {self.eps!r}")
-        if not _real(self.clip) or not 0.0 < self.clip <= 1e4:
-            raise ValueError(f"RefineOptions: clip must be a finite number in (0, 1e4], got {self.clip!r}")
+        limits.check_int("RefineOptions", "radius", self.radius, 1, limits.GUIDED_MAX_RADIUS)
+        limits.check_real("RefineOptions", "eps", self.eps, *limits.GUIDED_EPS_RANGE)
+        limits.check_real("RefineOptions", "clip", self.clip, 0.0, limits.GUIDED_MAX_CLIP, lo_open=True)
 
     def as_dict(self) -> dict:
         return {'radius': self.radius, 'eps': float(self.eps), 'clip': float(self.clip)}
@@ -246,20 +235,14 @@ class AdaptOptions:
     learning_rate: float = 1e-8
 
     def __post_init__(self) -> None:
-        if isinstance(self.steps, bool) or not isinstance(self.steps, int) or self.steps < 0:
-            raise ValueError(f"AdaptOptions: steps must be an integer >= 0, got {self.steps!r}")
-        if not _real(self.pos_prob) or not 0.5 < self.pos_prob < 1:
-            raise ValueError(f"AdaptOptions: pos_prob must be a probability in (0.5, 1), got {self.pos_prob!r}")
-        for name in ("neg_distance", "erode"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 4095:
-                raise ValueError(f"AdaptOptions: {name} must be an integer in 0..4095, got {v!r}")
-        if not _real(self.frame_weight) or not self.frame_weight > 0:
-            raise ValueError(f"AdaptOptions: frame_weight must be a finite number > 0, got {self.frame_weight!r}")
-        if not _real(self.first_weight) or not self.first_weight >= 0:
-            raise ValueError(f"AdaptOptions: first_weight must be a finite number >= 0, got {self.first_weight!r}")
-        if not _real(self.learning_rate) or not self.learning_rate > 0:
-            raise ValueError(f"AdaptOptions: learning_rate must be a finite number > 0, got {self.learning_rate!r}")
+        limits.check_int("AdaptOptions", "steps", self.steps, 0)
+        limits.check_real("AdaptOptions", "pos_prob", self.pos_prob, 0.5, 1.0, lo_open=True, hi_open=True,
+                          expect="a probability in (0.5, 1)")
+        limits.check_int("AdaptOptions", "neg_distance", self.neg_distance, 0, limits.GATE_MAX_DISTANCE)
+        limits.check_int("AdaptOptions", "erode", self.erode, 0, limits.GATE_MAX_DISTANCE)
+        limits.check_real("AdaptOptions", "frame_weight", self.frame_weight, 0.0, lo_open=True)
+        limits.check_real("AdaptOptions", "first_weight", self.first_weight, 0.0)
+        limits.check_real("AdaptOptions", "learning_rate", self.learning_rate, 0.0, lo_open=True)
 
     @property
     def pos_logit(self) -> float:

@@ -74,7 +74,7 @@ from typing import Deque, Iterable, Iterator, List, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import ops
+from . import limits, ops
 from .options import CleanOptions, RefineOptions, RoiOptions
 
 
@@ -190,10 +190,8 @@ class FrameSegmenter:
 
     def _set_budget(self, budget, default: int) -> None:
         """The download budget of an encoder whose capacity is set: ``default`` bytes where none is given."""
-        if budget is None:
-            budget = default
-        if isinstance(budget, bool) or not isinstance(budget, int) or budget <= 0:
-            raise ValueError(f"{self._who}: budget must be a positive number of bytes, got {budget!r}")
+        budget = limits.check_int(self._who, "budget", default if budget is None else budget, 1,
+                                  expect="a positive number of bytes")
         self.budget = min(budget, self.capacity)
 
     def _set_jpeg(self, encode, quality, subsampling, budget) -> None:
@@ -207,10 +205,8 @@ class FrameSegmenter:
         self.second_copies = 0  # frames whose file was longer than the budget
         self.bytes_down = 0     # bytes the downloads moved
         if encode:
-            if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-                raise ValueError(f"{self._who}: quality must be an integer in 1..100, got {quality!r}")
-            if self.subsampling not in ops.JPEG_SUBSAMPLINGS:
-                raise ValueError(f"{self._who}: subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {subsampling!r}")
+            limits.check_int(self._who, "quality", quality, *limits.JPEG_QUALITY)
+            limits.check_member(self._who, "subsampling", subsampling, limits.JPEG_SUBSAMPLINGS)
             self.capacity = ops.jpeg_capacity(h, w, 3 if self.overlay else 1, self.subsampling)
             raw = h * w * (3 if self.overlay else 1)
             self._set_budget(budget, max(raw // 4, 1024))
@@ -539,8 +535,7 @@ class ObjectSegmenter(FrameSegmenter):
         if encode == 'png' and self.overlay:
             raise ValueError("ObjectSegmenter: encode='png' is the palette file of the label map (overlay=False); "
                              "the frame's PNG is the host's job")
-        if huffman not in ops.PNG_HUFFMAN:
-            raise ValueError(f"ObjectSegmenter: huffman must be one of {tuple(ops.PNG_HUFFMAN)}, got {huffman!r}")
+        limits.check_member("ObjectSegmenter", "huffman", huffman, ops.PNG_HUFFMAN)
         if huffman != 'fixed' and encode != 'png':
             raise ValueError("ObjectSegmenter: huffman is the table choice of encode='png'")
         self.huffman = huffman
@@ -558,10 +553,11 @@ class ObjectSegmenter(FrameSegmenter):
         else:
             if isinstance(palette, np.ndarray):
                 palette = torch.from_numpy(object_overlay.check_palette(palette)).to(self.device)
-            if not isinstance(palette, torch.Tensor) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) \
-                    or palette.device != self.device or not palette.is_contiguous():
-                raise ValueError(f"ObjectSegmenter: a palette must be a contiguous uint8 [256,3] array or tensor on {self.device}")
-            self.palette = palette
+            try:  # the ops' rule; here one sentence says it, for arrays and tensors alike
+                self.palette = ops._palette(palette, self.device, "ObjectSegmenter")
+            except (AttributeError, ValueError, RuntimeError):
+                raise ValueError(f"ObjectSegmenter: a palette must be a contiguous uint8 [256,3] array or tensor on "
+                                 f"{self.device}") from None
         self._open()
 
     def _compute(self, slot: _Slot) -> None:
