@@ -143,31 +143,44 @@ def rotation_matrix(center, angle_deg: float, scale: float) -> np.ndarray:
 
 class ScaleNRotate(object):
     """Random zoom and rotation about the centre; tuples = continuous ranges, lists = fixed choices
-    (src/dataloaders/custom_transforms.py:7-60; not part of the default training pipeline)."""
+    (src/dataloaders/custom_transforms.py:7-60; not part of the default training pipeline).
 
-    def __init__(self, rots=(-30, 30), scales=(.75, 1.25)):
+    renormalize=True is the reference's class: after the warp, ``if tmp.min() < 0: tmp -= tmp.min()`` and then
+    ``if tmp.max() > 1: tmp /= tmp.max()``, which turns the mean-subtracted frame into a [0, 1] image.  False skips both
+    and keeps the frame in the values the nets are trained on (what ``fosvos_hip.options.RotateOptions`` defaults to)."""
+
+    def __init__(self, rots=(-30, 30), scales=(.75, 1.25), renormalize=True):
         assert isinstance(rots, type(scales))
-        self.rots, self.scales = rots, scales
+        self.rots, self.scales, self.renormalize = rots, scales, bool(renormalize)
 
-    def __call__(self, sample):
+    def draw(self, rng=random):
+        """(rot, sc) from ``rng``, the two draws of ``__call__`` in its order."""
         if isinstance(self.rots, tuple):
-            rot = (self.rots[1] - self.rots[0]) * random.random() - (self.rots[1] - self.rots[0]) / 2
-            sc = (self.scales[1] - self.scales[0]) * random.random() - (self.scales[1] - self.scales[0]) / 2 + 1
+            rot = (self.rots[1] - self.rots[0]) * rng.random() - (self.rots[1] - self.rots[0]) / 2
+            sc = (self.scales[1] - self.scales[0]) * rng.random() - (self.scales[1] - self.scales[0]) / 2 + 1
         else:
-            rot = self.rots[random.randint(0, len(self.rots) - 1)]
-            sc = self.scales[random.randint(0, len(self.scales) - 1)]
+            rot = self.rots[rng.randint(0, len(self.rots) - 1)]
+            sc = self.scales[rng.randint(0, len(self.scales) - 1)]
+        return rot, sc
+
+    def apply(self, sample, rot, sc):
+        """``__call__`` with the draws fixed."""
         for key in sample.keys():
             if key in _SKIP:
                 continue
             tmp = sample[key]
             h, w = tmp.shape[:2]
             tmp = warp_affine(tmp, rotation_matrix((w / 2, h / 2), rot, sc))
-            if tmp.min() < 0.0:
-                tmp = tmp - tmp.min()
-            if tmp.max() > 1.0:
-                tmp = tmp / tmp.max()
+            if self.renormalize:
+                if tmp.min() < 0.0:
+                    tmp = tmp - tmp.min()
+                if tmp.max() > 1.0:
+                    tmp = tmp / tmp.max()
             sample[key] = tmp
         return sample
+
+    def __call__(self, sample):
+        return self.apply(sample, *self.draw())
 
 
 class Resize(object):

@@ -212,6 +212,9 @@ SIGNATURES = {
     "fosvos_augment_sample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p]),
+    "fosvos_warp_sample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [ctypes.c_double] * 6 +
+                           [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "fosvos_warp_workspace_bytes": (c_size_t, [c_int, c_int]),
     "fosvos_prob_bytes": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fosvos_jf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fosvos_jf_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int,

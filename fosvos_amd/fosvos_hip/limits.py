@@ -31,6 +31,9 @@ MAX_OBJECTS = 16
 JF_RADIUS = (1, 63)
 JPEG_QUALITY = (1, 100)
 JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
+# rotating and zooming the training sample (dataloaders/custom_transforms.ScaleNRotate): degrees, and the zoom factor
+ROTATE_MAX_ANGLE = 360.0
+ROTATE_SCALE_RANGE = (1.0 / 16, 16.0)
 
 
 def real_number(v) -> bool:

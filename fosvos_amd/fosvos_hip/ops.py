@@ -1093,6 +1093,80 @@ def augment_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, img_lut:
             nbytes=float(frame.numel() + mask.numel() + 4 * (image.numel() + gt.numel())))
 
 
+def warp_workspace_bytes(h: int, w: int) -> int:
+    """fosvos_warp_workspace_bytes: what ``warp_sample(renormalize=True)`` needs for an h x w frame."""
+    limits.check_int("warp_workspace_bytes", "h", h, 1, limits.MAX_FRAME_SIDE)
+    limits.check_int("warp_workspace_bytes", "w", w, 1, limits.MAX_FRAME_SIDE)
+    return int(lib().fosvos_warp_workspace_bytes(h, w))
+
+
+def warp_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, matrix, img_lut: torch.Tensor, gt_lut: torch.Tensor,
+                image: torch.Tensor, gt: torch.Tensor, renormalize: bool = False,
+                workspace: Optional[torch.Tensor] = None) -> None:
+    """fosvos_warp_sample: uint8 frame [H,W,3] and mask [H,W] -> image [1,3,H,W] / gt [1,1,H,W] (fp32, written in place),
+    mirrored first if ``flip`` and then warped by ``matrix``, the 2x3 SOURCE -> DESTINATION matrix of
+    custom_transforms.rotation_matrix, bit for bit custom_transforms.warp_affine.  The matrix is inverted here exactly as
+    warp_affine inverts it (np.linalg.inv of the 3x3 in fp64), so kernel and definition start from the same six doubles.
+    img_lut fp32 [256,3], gt_lut fp32 [256].
+
+    renormalize: the reference's ScaleNRotate shifts the warped frame to min 0 and divides it by its max where that exceeds 1
+    (custom_transforms.ScaleNRotate(renormalize=True)); it needs ``workspace``, a uint8 tensor of at least
+    ``warp_workspace_bytes(H, W)`` bytes.  On a mask the renormalisation is a no-op, because its values are in [0, 1]: the
+    gt is never rewritten."""
+    import numpy as np
+    _need(frame, torch.uint8, "warp_sample frame")
+    _need(mask, torch.uint8, "warp_sample mask")
+    _need(img_lut, _F32, "warp_sample img_lut")
+    _need(gt_lut, _F32, "warp_sample gt_lut")
+    _need(image, _F32, "warp_sample image")
+    _need(gt, _F32, "warp_sample gt")
+    if frame.dim() != 3 or frame.shape[2] != 3:
+        raise ValueError(f"warp_sample: frame must be [H,W,3], got {tuple(frame.shape)}")
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    limits.check_int("warp_sample", "H", h, 1, limits.MAX_FRAME_SIDE)
+    limits.check_int("warp_sample", "W", w, 1, limits.MAX_FRAME_SIDE)
+    if tuple(mask.shape) != (h, w):
+        raise ValueError(f"warp_sample: mask {tuple(mask.shape)} does not match the frame's {(h, w)}")
+    if tuple(img_lut.shape) != (256, 3) or tuple(gt_lut.shape) != (256,):
+        raise ValueError("warp_sample: img_lut must be [256,3] and gt_lut [256]")
+    if tuple(image.shape) != (1, 3, h, w):
+        raise ValueError(f"warp_sample: a warp keeps the size: image must be [1,3,{h},{w}], got {tuple(image.shape)}")
+    if tuple(gt.shape) != (1, 1, h, w):
+        raise ValueError(f"warp_sample: gt must be [1,1,{h},{w}], got {tuple(gt.shape)}")
+    try:
+        m = np.array(matrix, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"warp_sample: matrix must be 2x3 numbers, got {matrix!r}") from None
+    if m.shape != (2, 3):
+        raise ValueError(f"warp_sample: matrix must be 2x3 (source -> destination), got shape {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError(f"warp_sample: matrix must be finite, got {m.tolist()}")
+    try:
+        inv = np.linalg.inv(np.vstack([m, [0.0, 0.0, 1.0]]))  # warp_affine's own inversion
+    except np.linalg.LinAlgError:
+        raise ValueError(f"warp_sample: matrix is singular: {m.tolist()}") from None
+    if not np.isfinite(inv).all():
+        raise ValueError(f"warp_sample: the inverse of the matrix is not finite: {m.tolist()}")
+    if not isinstance(renormalize, bool):
+        raise ValueError(f"warp_sample: renormalize must be a bool, got {renormalize!r}")
+    ws_ptr, ws_bytes = None, 0
+    if renormalize:
+        need = warp_workspace_bytes(h, w)
+        if workspace is None:
+            raise ValueError(f"warp_sample: renormalize needs a workspace of {need} bytes (warp_workspace_bytes)")
+        _need(workspace, torch.uint8, "warp_sample workspace")
+        if workspace.numel() < need:
+            raise ValueError(f"warp_sample: workspace of {workspace.numel()} bytes, {need} needed (warp_workspace_bytes)")
+        if workspace.data_ptr() % 4:
+            raise ValueError("warp_sample: the workspace must be 4-byte aligned")
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    _same_device("warp_sample", frame, mask, img_lut, gt_lut, image, gt, *(() if workspace is None else (workspace,)))
+    _launch("warp_sample", frame, frame.data_ptr(), mask.data_ptr(), h, w, 1 if flip else 0,
+            *(float(v) for v in inv[:2].reshape(-1)), img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(),
+            1 if renormalize else 0, ws_ptr, ws_bytes,
+            nbytes=float(49 * h * w + 4 * (image.numel() + gt.numel()) + (8 * image.numel() if renormalize else 0)))
+
+
 # ------------------------------------------------------------------------------------------ shared argument checks
 # (of the ops from here down: a wrong dtype is a ValueError; DESIGN.md section 21 lists who uses which)
 MAX_OBJECTS = limits.MAX_OBJECTS

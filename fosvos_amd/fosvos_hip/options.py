@@ -3,7 +3,8 @@
 takes an options object.  The defaults are the measured best; every switch selects between two paths that both stay tested.
 The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleaning) is opt-in by being
 passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
-and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3).
+and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3), and
+RotateOptions (rotating and zooming the training sample).
 
 No torch and no library load here: importable anywhere.  The ranges and the scalar checks are ``limits``'.
 """
@@ -11,7 +12,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Mapping, Optional
+from typing import Mapping, Optional, Union
 
 from . import limits
 
@@ -255,6 +256,52 @@ class AdaptOptions:
         return {'steps': self.steps, 'pos_prob': float(self.pos_prob), 'pos_logit': self.pos_logit,
                 'neg_distance': self.neg_distance, 'erode': self.erode, 'frame_weight': float(self.frame_weight),
                 'first_weight': float(self.first_weight), 'learning_rate': float(self.learning_rate)}
+
+
+@dataclass(frozen=True)
+class RotateOptions:
+    """Rotating and zooming the training sample about its centre (the reference's ``ScaleNRotate``, commented out beside
+    ``Resize`` in its training loader; ``get_data_loader_train(rotate=)`` and the resident loaders).
+    Opt-in by being passed; this class reads no environment variable.  The ranges are the reference's.
+
+    A tuple is a continuous range, drawn as ``(hi - lo) * random() - (hi - lo) / 2`` (plus 1 for the zoom): the reference
+    centres the draw on 0 degrees and on zoom 1 whatever the ends are.  A list is a set of fixed choices.  Both fields are of
+    one kind."""
+
+    # degrees, counter-clockwise: every entry a finite number in [-360, 360]
+    rots: Union[tuple, list] = (-30.0, 30.0)
+    # zoom factors: every entry a finite number in [1/16, 16]
+    scales: Union[tuple, list] = (0.75, 1.25)
+    # True: the reference's renormalisation of the warped frame to [0, 1] (``ScaleNRotate(renormalize=True)``), which is not
+    # what the nets are trained on; the default keeps the mean-subtracted values (a documented deviation)
+    renormalize: bool = False
+
+    def __post_init__(self) -> None:
+        if type(self.rots) not in (tuple, list) or type(self.scales) is not type(self.rots):
+            raise ValueError("RotateOptions: rots and scales must both be tuples (continuous ranges) or both be lists "
+                             f"(fixed choices), got {self.rots!r} and {self.scales!r}")
+        for name, v in (("rots", self.rots), ("scales", self.scales)):
+            if isinstance(v, tuple) and len(v) != 2:
+                raise ValueError(f"RotateOptions: {name} as a range must be (lo, hi), got {v!r}")
+            if not v:
+                raise ValueError(f"RotateOptions: {name} must not be empty")
+        for v in self.rots:
+            limits.check_real("RotateOptions", "rots", v, -limits.ROTATE_MAX_ANGLE, limits.ROTATE_MAX_ANGLE)
+        for v in self.scales:
+            limits.check_real("RotateOptions", "scales", v, *limits.ROTATE_SCALE_RANGE)
+        if isinstance(self.rots, tuple):
+            if self.rots[0] > self.rots[1] or self.scales[0] > self.scales[1]:
+                raise ValueError(f"RotateOptions: a range must be (lo, hi) with lo <= hi, got {self.rots!r} and {self.scales!r}")
+            # what the reference's draw can reach: 1 +- (hi - lo) / 2
+            limits.check_real("RotateOptions", "scales", 1 - (self.scales[1] - self.scales[0]) / 2, *limits.ROTATE_SCALE_RANGE,
+                              expect="a range whose draw 1 +- (hi - lo) / 2 stays in [1/16, 16]")
+        if not isinstance(self.renormalize, bool):
+            raise ValueError(f"RotateOptions: renormalize must be a bool, got {self.renormalize!r}")
+
+    def transform(self):
+        """The ``custom_transforms.ScaleNRotate`` these options describe."""
+        from dataloaders import custom_transforms
+        return custom_transforms.ScaleNRotate(self.rots, self.scales, self.renormalize)
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

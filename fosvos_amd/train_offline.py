@@ -34,6 +34,7 @@ db_root_dir = None
 synthetic_size = None
 data_parallel = False
 resident_train_set = False
+rotate = None               # --augment-rotate (and --rotate-range / --zoom-range / --rotate-renormalize): a RotateOptions
 microbatch_group = 1        # --microbatch-group: frames per batched pass of an accumulation cycle (1 = the reference's order)
 
 
@@ -44,7 +45,8 @@ def train_and_test(net_provider: NetworkProvider, settings: OfflineSettings) -> 
         shard = (parallel.rank(), parallel.world_size()) if data_parallel else None
         data_loader_train = io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train,
                                                             synthetic=synthetic_size, shard=shard,
-                                                            resident_set=resident_train_set)
+                                                            resident_set=resident_train_set,
+                                                            **({} if rotate is None else {'rotate': rotate}))
         data_loader_test = io_helper.get_data_loader_test(db_root_dir, settings.batch_size_test,
                                                           synthetic=synthetic_size)
         optimizer = net_provider.get_optimizer()
@@ -301,7 +303,7 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
 
 
 def main(argv=None):
-    global db_root_dir, synthetic_size, data_parallel, resident_train_set, microbatch_group
+    global db_root_dir, synthetic_size, data_parallel, resident_train_set, microbatch_group, rotate
     args = args_helper.parse_args(is_online=False, argv=argv)
     if args.network != 'vgg16':
         raise SystemExit('only --network vgg16 is implemented on the HIP path (ResNet family: SURVEY.md §8 f4)')
@@ -311,6 +313,7 @@ def main(argv=None):
     synthetic_size = (args.height, args.width) if args.synthetic else None
     resident_train_set = bool(args.resident_train_set)
     microbatch_group = args.microbatch_group
+    rotate = args.rotate
     save_dir_models.mkdir(parents=True, exist_ok=True)
     save_dir_results.mkdir(parents=True, exist_ok=True)
 

@@ -46,6 +46,7 @@ png_fitted = False          # --png-fitted (with --fast-test): Huffman codes fit
 device_decode = False       # --device-decode: the test pass's JPEG frames are decoded on the device (dataloaders/device_decode.py)
 multi_object = False        # --multi-object: one net per object, merged and scored on the device (train_and_test_objects)
 clean = None                # --clean-min-area / --clean-largest / --clean-temporal (with --fast-test): a CleanOptions
+rotate = None               # --augment-rotate (and its options): a RotateOptions; the one-shot loaders rotate and zoom the sample
 adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
@@ -77,6 +78,12 @@ def _clean_seed(train_seed, annotations, data_loader, seq_name: str) -> Optional
             return (np.asarray(ann) != 0).astype(np.uint8)
     log.info('Clean {0}: no annotation to start the temporal gate from, the first frame is not gated'.format(seq_name))
     return None
+
+
+def _train_loader(seq_name: str, settings: OnlineSettings):
+    """The training loader of a sequence run; ``rotate`` is passed only when set (absent: the call is what it was)."""
+    return io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train, seq_name, synthetic=synthetic_size,
+                                           **({} if rotate is None else {'rotate': rotate}))
 
 
 def _first_sample(data_loader) -> dict:
@@ -118,8 +125,7 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
 
     if settings.is_training:
         net_provider.load_network_train()
-        data_loader = io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train, seq_name,
-                                                      synthetic=synthetic_size)
+        data_loader = _train_loader(seq_name, settings)
         optimizer = net_provider.get_optimizer()
         _train(net_provider, data_loader, optimizer, summary_writer, seq_name, settings.start_epoch, settings.n_epochs,
                settings.avg_grad_every_n, settings.snapshot_every_n)
@@ -140,8 +146,7 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                         str(settings.variant_online))
         if adapt is not None:
             if first_sample is None:  # this call did not train: the training loader still holds the annotated frame
-                first_sample = _first_sample(io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train, seq_name,
-                                                                             synthetic=synthetic_size))
+                first_sample = _first_sample(_train_loader(seq_name, settings))
             annotations = io_helper.get_annotations(db_root_dir, data_loader, synthetic_size) if score else None
             result = experiment_helper.test_adaptive(net_provider, data_loader, save_dir, first_sample, adapt, annotations,
                                                      seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
@@ -184,7 +189,8 @@ def _object_loaders(seq_name: str, object_id: int, settings: OnlineSettings, n_o
     from dataloaders.resident import ResidentOneShotLoader
     from torch.utils.data import DataLoader
     train = ResidentOneShotLoader(DAVIS2017(mode='train', db_root_dir=str(db_root_dir), seq_name=seq_name,
-                                            object_id=object_id, transform=None))
+                                            object_id=object_id, transform=None),
+                                  **({} if rotate is None else {'rotate': rotate}))
     test = DataLoader(DAVIS2017(mode='test', db_root_dir=str(db_root_dir), seq_name=seq_name, object_id=object_id,
                                 transform=custom_transforms.ToTensor()),
                       batch_size=settings.batch_size_test, shuffle=False, num_workers=2)
@@ -614,7 +620,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean, adapt
+    global multi_object, synthetic_objects, clean, adapt, rotate
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -631,6 +637,7 @@ def main(argv=None):
         clean = CleanOptions(min_area=args.clean_min_area or 0, largest=bool(args.clean_largest),
                              temporal_radius=args.clean_temporal)
     adapt = args.adapt
+    rotate = args.rotate
     synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':

@@ -3,7 +3,8 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --resident-train-set and --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
+--data-parallel, --augment-rotate with --rotate-range / --zoom-range / --rotate-renormalize, --resident-train-set and
+--microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
 --multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal and --adapt-steps with its --adapt-* options
 (online only).
 """
@@ -31,7 +32,41 @@ def _get_base_parser() -> argparse.ArgumentParser:
     parser.add_argument('--data-parallel', action='store_true',
                         help='spread the gradient-accumulation micro-batches over the ranks of a torchrun job '
                              '(RCCL all-reduce per optimizer step)')
+    parser.add_argument('--augment-rotate', action='store_true',
+                        help='rotate and zoom every training sample about its centre (the reference\'s ScaleNRotate in '
+                             'place of its rescale; the frame keeps its size).  The resident loaders warp on the GPU; the '
+                             'offline loader without --resident-train-set warps in numpy on the host, slowly (about 0.16 s '
+                             'a 480p sample)')
+    parser.add_argument('--rotate-range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                        help='with --augment-rotate: the angle is drawn from +-(HI - LO) / 2 degrees (default -30 30)')
+    parser.add_argument('--zoom-range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                        help='with --augment-rotate: the zoom is drawn from 1 +- (HI - LO) / 2 (default 0.75 1.25)')
+    parser.add_argument('--rotate-renormalize', action='store_true',
+                        help='with --augment-rotate: the reference\'s renormalisation of the warped frame to [0, 1] (off by '
+                             'default: the nets are trained on mean-subtracted frames)')
     return parser
+
+
+def _rotate_options(parser: argparse.ArgumentParser, args: argparse.Namespace):
+    """``args.rotate``: the RotateOptions of --augment-rotate and its options, or None."""
+    given = [flag for flag, on in (('--rotate-range', args.rotate_range is not None), ('--zoom-range', args.zoom_range is not None),
+                                   ('--rotate-renormalize', args.rotate_renormalize)) if on]
+    if not args.augment_rotate:
+        if given:
+            parser.error('{} set(s) an option of the rotation: it needs --augment-rotate'.format(' / '.join(given)))
+        return None
+    if args.synthetic:
+        parser.error('--augment-rotate augments DAVIS samples: the loader of --synthetic augments nothing')
+    if args.data_parallel:
+        parser.error('--augment-rotate is not wired to the sharded loaders of --data-parallel')
+    try:
+        from fosvos_hip.options import RotateOptions
+        defaults = RotateOptions()
+        return RotateOptions(rots=defaults.rots if args.rotate_range is None else tuple(args.rotate_range),
+                             scales=defaults.scales if args.zoom_range is None else tuple(args.zoom_range),
+                             renormalize=bool(args.rotate_renormalize))
+    except ValueError as err:
+        parser.error(str(err).replace('RotateOptions: ', '--augment-rotate: '))
 
 
 def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -94,6 +129,7 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                                  'frames of one shape (every frame keeps the class weights of its own label; 1 = one '
                                  'minibatch per pass, the reference\'s order)')
     args = parser.parse_args(argv)
+    args.rotate = _rotate_options(parser, args)
     if not is_online and args.microbatch_group < 1:
         parser.error('--microbatch-group counts frames per pass: at least 1')
     if not is_online and args.microbatch_group > 1 and args.data_parallel:

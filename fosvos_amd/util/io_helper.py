@@ -47,7 +47,7 @@ def write_settings(save_dir: Path, name: str, settings, variant_offline: Optiona
 def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] = None,
                           synthetic: Optional[Tuple[int, int]] = None,
                           shard: Optional[Tuple[int, int]] = None, resident: bool = True,
-                          resident_set: bool = False) -> DataLoader:
+                          resident_set: bool = False, rotate=None) -> DataLoader:
     """shard = (rank, world): this process draws its own 1/world of every epoch (data-parallel OFFLINE training, where
     the ranks split each iteration's batch); None: the reference's single-process loader.
     resident: a sequence run (``seq_name``: ONE training sample, src/dataloaders/davis_2016.py:72-83) gets the loader that
@@ -57,21 +57,30 @@ def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] 
     resident_set (opt-in): the whole training set (no ``seq_name``, no ``synthetic``) gets the loader that decodes every
     sample once, keeps the uint8 frames and masks on the device and flips / rescales each draw there in one HIP launch
     (dataloaders/resident.py: ResidentTrainSetLoader, same tensors in the same order as the DataLoader below under the
-    same torch seed, ``shard`` included).  It yields batches of one sample only and raises for any other batch_size."""
+    same torch seed, ``shard`` included).  It yields batches of one sample only and raises for any other batch_size.
+    rotate (opt-in): a fosvos_hip.options.RotateOptions.  ``ScaleNRotate(rots, scales, renormalize)`` stands in place of
+    ``Resize``, as in the reference's commented line; the DataLoader below then warps in numpy on the host (about 0.16 s for
+    a 480x854 sample) and is the yardstick the resident loaders replay with one HIP launch per draw.  The synthetic loader
+    augments nothing and refuses it."""
     if synthetic is not None:
+        if rotate is not None:
+            raise ValueError('get_data_loader_train: rotate augments DAVIS samples; the synthetic loader augments nothing')
         ds = SyntheticSequence(seq_name or 'synthetic', synthetic[0], synthetic[1], n_frames=1,
                                seed=1234 + (shard[0] if shard else 0))
         return DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=0)
-    # src/util/io_helper.py:62-70: random flip, random rescale (ScaleNRotate stays disabled as in the reference), ToTensor
-    composed = custom_transforms.Compose([custom_transforms.RandomHorizontalFlip(), custom_transforms.Resize(),
+    # src/util/io_helper.py:62-70: random flip, random rescale (ScaleNRotate stays disabled as in the reference unless
+    # ``rotate`` asks for it: it then stands where Resize stood, as in the reference's commented line), ToTensor
+    composed = custom_transforms.Compose([custom_transforms.RandomHorizontalFlip(),
+                                          custom_transforms.Resize() if rotate is None else rotate.transform(),
                                           custom_transforms.ToTensor()])
     if resident and seq_name is not None and shard is None and batch_size == 1:
         from dataloaders.resident import ResidentOneShotLoader
-        return ResidentOneShotLoader(DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=None, seq_name=seq_name))
+        return ResidentOneShotLoader(DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=None, seq_name=seq_name),
+                                     rotate=rotate)
     if resident_set and seq_name is None:
         from dataloaders.resident import ResidentTrainSetLoader
         return ResidentTrainSetLoader(DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=None),
-                                      shard=shard, batch_size=batch_size)
+                                      shard=shard, batch_size=batch_size, rotate=rotate)
     db_train = DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=composed, seq_name=seq_name)
     if shard is not None:
         from torch.utils.data.distributed import DistributedSampler

@@ -426,6 +426,26 @@ int fosvos_augment_sample(const uint8_t *frame, const uint8_t *mask, int H, int 
                           const float *col_w, const int32_t *row_taps, const float *row_w, const int32_t *col_near,
                           const int32_t *row_near, int OH, int OW, const float *img_lut, const float *gt_lut, float *image,
                           float *gt, int device, void *stream);
+/* fosvos_warp_sample: the same sample rotated and zoomed about its centre (flip, then the reference's ScaleNRotate,
+ * src/dataloaders/custom_transforms.py:7-60: cv2.warpAffine at the frame's own size, bicubic for the frame, nearest for
+ * the mask, 0 outside the source), bit for bit dataloaders/custom_transforms.warp_affine.
+ *   frame, mask, flip, img_lut, gt_lut   as above, at any byte alignment; image fp32 [3,H,W] out; gt fp32 [H,W] out
+ *   i00 .. i12   the INVERSE 2x3 matrix (destination -> source) in fp64: sx = (i00*x + i01*y) + i02, sy = (i10*x + i11*y)
+ *                + i12, no contraction.  Mask: rint (half to even) of both, the table value of the byte there or 0.  Frame:
+ *                floor of both, the fractions as fp32, interpolateCubic's weights (A = -0.75) in fp32, the 16 taps row-outer
+ *                and column-inner as out = out + val * (wy[j] * wx[i]) from +0.0, val = 0 for a tap outside the source.
+ *   renormalize  nonzero: the reference's `if min < 0: image -= min; if max > 1: image /= max` over the whole image in fp32
+ *                (the gt is left alone: table values in [0, 1] make both steps no-ops).  The warp launch writes one (min, max)
+ *                pair per workgroup to `workspace` (fosvos_warp_workspace_bytes(H, W) bytes, 4-byte aligned) and a second
+ *                launch reduces all pairs in every workgroup and rewrites the image.  Finite table values only.
+ *                Zero: one launch, no workspace (NULL, 0).
+ * Refused: H or W above 8192, a non-finite coefficient, a matrix that sends one of the four output corners beyond +-2^30
+ * (within that bound every source coordinate fits int32), renormalize without its workspace.  Every tap is bounds-checked.
+ * replaces: the per-iteration DataLoader worker's ScaleNRotate, commented out in src/util/io_helper.py:62-70. */
+int fosvos_warp_sample(const uint8_t *frame, const uint8_t *mask, int H, int W, int flip, double i00, double i01, double i02,
+                       double i10, double i11, double i12, const float *img_lut, const float *gt_lut, float *image,
+                       float *gt, int renormalize, void *workspace, size_t workspace_bytes, int device, void *stream);
+size_t fosvos_warp_workspace_bytes(int H, int W); /* 0 for sizes fosvos_warp_sample refuses */
 
 /* ---- scoring a segmented sequence (DAVIS 2016 J and F) and its PNG bytes ------------------------------------------
  * The reference writes probability PNGs and leaves the measures to an outside toolkit (src/eval/README.md); these two
