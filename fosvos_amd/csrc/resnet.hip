@@ -13,7 +13,7 @@
 //     them with scalar loads and feeds them to the dot instruction as its SGPR operand - no LDS, no broadcast reads.
 // Padded channels hold exact zeros everywhere (zero weights and bias), so no kernel ever masks a channel.
 #include "common.hpp"
-
+#include <type_traits>
 
 using namespace fosvos;
 
@@ -79,8 +79,11 @@ __global__ void k_fold_conv_bn(const float *__restrict__ w, int Co, int per_co, 
 
 // First layer: [Co][3][7][7] fp32 -> two images.  (1) fp32 [tap * 3 + ci][Cop] for the vector-ALU kernel; (2) bf16 MFMA
 // fragments [k-step 6][k-group 4][channel NC][8] over K = 8 rows x 24 (a filter row is kx-major, channel-minor: 21 values +
-// 3 zeros; the 8th row is zeros), at float offset 147 * Cop + 64 of the same buffer, NC = Cop rounded up to 16.
+// 3 zeros; the 8th row is zeros), behind the fp32 image and its slack in the same buffer, NC = Cop rounded up to 16.
 __host__ __device__ constexpr int f7_nc(int Cop) { return (Cop + 15) / 16 * 16; }
+__host__ __device__ constexpr int f7_fp32_elems(int Cop) { return 147 * Cop + 64; }
+template <class T>
+__host__ __device__ T *f7_mfma_image(T *wp, int Cop) { return wp + f7_fp32_elems(Cop); }
 __global__ void k_pack_conv7x7_bn(const float *__restrict__ w, int Co, const float *__restrict__ bn_w,
                                   const float *__restrict__ bn_b, const float *__restrict__ bn_m,
                                   const float *__restrict__ bn_v, float eps, float *__restrict__ wp,
@@ -100,7 +103,7 @@ __global__ void k_pack_conv7x7_bn(const float *__restrict__ w, int Co, const flo
             const float s = bn_w ? bn_w[n] / sqrtf(bn_v[n] + eps) : 1.f;
             v = w[((int64_t)n * 3 + j % 3) * 49 + ky * 7 + j / 3] * s;
         }
-        reinterpret_cast<uint16_t *>(wp + 147 * Cop + 64)[i] = f2bf(v);
+        reinterpret_cast<uint16_t *>(f7_mfma_image(wp, Cop))[i] = f2bf(v);
     }
     if (i >= total) return;
     const int co = i % Cop, r = i / Cop;  // r = tap * 3 + ci
@@ -340,51 +343,70 @@ __device__ __forceinline__ bool stage_patch_vec4(const float *__restrict__ f0, i
     return true;
 }
 
+// The whole patch of an MFMA first-layer workgroup (256 threads): ROWS staged rows in an LDS buffer of (ROWS + 1) *
+// F7_PITCH + 8 elements.  The 16-byte form where it applies, else scalar loads, then the zero fill.
+template <int ROWS>
+__device__ __forceinline__ void stage_patch(const float *__restrict__ f0, int64_t plane, int y_base, int x_base, int H, int W,
+                                            uint16_t *sIn, int tid) {
+    // patch loads in batches of 6 from clamped addresses (zero padding applied as a select): rolled, with the load under
+    // a bounds branch, every element waited out its own trip to memory - 17 in a row per thread
+    constexpr int N = 3 * ROWS * F7_PW, B = 6;
+    PatchWalk pw;
+    pw.start(tid, ROWS);
+    const bool staged = stage_patch_vec4<ROWS>(f0, plane, y_base, x_base, H, W, sIn, tid);
+    for (int base = tid; !staged && base < N; base += 256 * B) {
+        float v[B];
+        int dst[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+            const int ci = min(pw.ci, 2), r = pw.r, c = pw.c;
+            const int iy = y_base + r, ix = x_base + c;
+            const float t = f0[ci * plane + (int64_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)];
+            v[u] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? t : 0.f;
+            dst[u] = pw.ci < 3 ? r * F7_PITCH + c * 3 + ci : -1;
+            pw.step256(ROWS);
+        }
+#pragma unroll
+        for (int u = 0; u < B; ++u)
+            if (dst[u] >= 0) sIn[dst[u]] = f2bf(v[u]);
+    }
+    // what only zero weights ever multiply must still be finite: the pad column of every row, the 8th filter row's patch
+    // row and the few elements a last lane reads past it
+    for (int idx = tid; idx < F7_PITCH + 8 + ROWS + 1; idx += 256) {
+        if (idx < F7_PITCH + 8) sIn[ROWS * F7_PITCH + idx] = 0;
+        else sIn[(idx - F7_PITCH - 8) * F7_PITCH + F7_PITCH - 1] = 0;
+    }
+}
+
+// All 6 x NFB weight fragments of a lane (k-group kg, channel l16 of each fragment block), for the kernel's lifetime.
+template <int NFB>
+__device__ __forceinline__ void load_wfrags(const uint4 *__restrict__ wimg, int kg, int l16, bf16x8 (&wf)[6][NFB]) {
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks)
+#pragma unroll
+        for (int nf = 0; nf < NFB; ++nf) wf[ks][nf] = __builtin_bit_cast(bf16x8, wimg[(ks * 4 + kg) * (NFB * 16) + nf * 16 + l16]);
+}
+
+// The 8 consecutive k of k-step ks and k-group kg for the conv pixel (ly, lx) of the staged patch.  Both kernels read
+// their operands here and step ks = 0..5 in order: the same K order, so the same bits.
+__device__ __forceinline__ bf16x8 a_frag(const uint16_t *sIn, int ly, int lx, int ks, int kg) {
+    const int k0 = ks * 32 + kg * 8, ky = k0 / 24, j0 = k0 % 24;
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(sIn + (2 * ly + ky) * F7_PITCH + 6 * lx + j0);
+    return __builtin_bit_cast(bf16x8, make_uint4(p[0], p[1], p[2], p[3]));
+}
 
 template <int NFB>
 __global__ __launch_bounds__(256) void k_conv7x7s2_first_mfma(const float *__restrict__ frame, const uint4 *__restrict__ wimg,
                                                               const float *__restrict__ bias, uint16_t *__restrict__ y,
                                                               int H, int W, int Ho, int Wo, int tiles_x, int Cop, int relu) {
-    constexpr int ROWS = F7_PH + 1, NC = NFB * 16;
-    __shared__ __attribute__((aligned(16))) uint16_t sIn[ROWS * F7_PITCH + 8];
+    __shared__ __attribute__((aligned(16))) uint16_t sIn[(F7_PH + 1) * F7_PITCH + 8];
     const int tile = blockIdx.x, n = blockIdx.z, tid = threadIdx.x;
     const int oy0 = (tile / tiles_x) * F7_TH, ox0 = (tile % tiles_x) * F7_TW;
     const int64_t plane = (int64_t)H * W;
-    const float *f0 = frame + (int64_t)n * 3 * plane;
-    // patch loads in batches of 6 from clamped addresses (zero padding applied as a select): rolled, with the load under
-    // a bounds branch, every element waited out its own trip to memory - 17 in a row per thread
-    constexpr int F7_N = 3 * F7_PH * F7_PW, F7_B = 6;
-    PatchWalk pw;
-    pw.start(tid, F7_PH);
-    const bool staged = stage_patch_vec4<F7_PH>(f0, plane, oy0 * 2 - 3, ox0 * 2 - 3, H, W, sIn, tid);
-    for (int base = tid; !staged && base < F7_N; base += 256 * F7_B) {
-        float v[F7_B];
-        int dst[F7_B];
-#pragma unroll
-        for (int u = 0; u < F7_B; ++u) {
-            const int ci = min(pw.ci, 2), r = pw.r, c = pw.c;
-            const int iy = oy0 * 2 - 3 + r, ix = ox0 * 2 - 3 + c;
-            const float t = f0[ci * plane + (int64_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)];
-            v[u] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? t : 0.f;
-            dst[u] = pw.ci < 3 ? r * F7_PITCH + c * 3 + ci : -1;
-            pw.step256(F7_PH);
-        }
-#pragma unroll
-        for (int u = 0; u < F7_B; ++u)
-            if (dst[u] >= 0) sIn[dst[u]] = f2bf(v[u]);
-    }
-    // what only zero weights ever multiply must still be finite: the pad column of every row, the 8th filter row's patch
-    // row and the few elements a last lane reads past it
-    for (int idx = tid; idx < F7_PITCH + 8 + ROWS; idx += 256) {
-        if (idx < F7_PITCH + 8) sIn[F7_PH * F7_PITCH + idx] = 0;
-        else sIn[(idx - F7_PITCH - 8) * F7_PITCH + F7_PITCH - 1] = 0;
-    }
+    stage_patch<F7_PH>(frame + (int64_t)n * 3 * plane, plane, oy0 * 2 - 3, ox0 * 2 - 3, H, W, sIn, tid);
     const int wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kg = lane >> 4;
     bf16x8 wf[6][NFB];
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks)
-#pragma unroll
-        for (int nf = 0; nf < NFB; ++nf) wf[ks][nf] = __builtin_bit_cast(bf16x8, wimg[(ks * 4 + kg) * NC + nf * 16 + l16]);
+    load_wfrags<NFB>(wimg, kg, l16, wf);
     f32x4 acc[4][NFB];
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf)
@@ -393,13 +415,9 @@ __global__ __launch_bounds__(256) void k_conv7x7s2_first_mfma(const float *__res
     __syncthreads();
 #pragma unroll
     for (int ks = 0; ks < 6; ++ks) {
-        const int k0 = ks * 32 + kg * 8, ky = k0 / 24, j0 = k0 % 24;
 #pragma unroll
         for (int mf = 0; mf < 4; ++mf) {
-            const int ly = wave * 2 + (mf >> 1), lx = (mf & 1) * 16 + l16;
-            const uint32_t *p = reinterpret_cast<const uint32_t *>(sIn + (2 * ly + ky) * F7_PITCH + 6 * lx + j0);
-            const uint4 av = make_uint4(p[0], p[1], p[2], p[3]);
-            const bf16x8 a = __builtin_bit_cast(bf16x8, av);
+            const bf16x8 a = a_frag(sIn, wave * 2 + (mf >> 1), (mf & 1) * 16 + l16, ks, kg);
 #pragma unroll
             for (int nf = 0; nf < NFB; ++nf)
                 acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][nf], a, acc[mf][nf], 0, 0, 0);
@@ -427,9 +445,9 @@ __global__ __launch_bounds__(256) void k_conv7x7s2_first_mfma(const float *__res
 
 // First layer AND its 3x3 stride-2 max pool in one launch: the 540 x 960 conv map of a 1080p frame is never written (33-66
 // MB out and back in) - a workgroup owns 8 x 15 POOLED pixels, computes the 17 x 31 conv pixels under them (18 x 32 are
-// computed: 36 fragments of 16, 9 per wave) exactly as k_conv7x7s2_first_mfma does (same K order, so the same bits), keeps
-// them in LDS as bf16 after bias + ReLU, and pools from there.  Conv positions outside the map count as 0, which is
-// neutral under max because every window holds at least one real, ReLU'd (>= 0) value.
+// computed: 36 fragments of 16, 9 per wave) from the same patch, fragments and K order as k_conv7x7s2_first_mfma (stage_patch,
+// load_wfrags, a_frag: the same bits), keeps them in LDS as bf16 after bias + ReLU, and pools from there.  Conv positions
+// outside the map count as 0, which is neutral under max because every window holds at least one real, ReLU'd (>= 0) value.
 constexpr int FP_PH = 8, FP_PW = 15, FP_CR = 2 * FP_PH + 2, FP_CC = 32, FP_ROWS = 2 * (FP_CR - 1) + 7;  // 18 x 32 conv, 41 rows
 
 template <int NFB>
@@ -445,37 +463,10 @@ __global__ __launch_bounds__(256) void k_conv7x7s2_pool_first_mfma(const float *
     const int py0 = (tile / tiles_x) * FP_PH, px0 = (tile % tiles_x) * FP_PW;
     const int cr0 = 2 * py0 - 1, cc0 = 2 * px0 - 1;  // conv position of local (0, 0)
     const int64_t plane = (int64_t)H * W;
-    const float *f0 = frame + (int64_t)n * 3 * plane;
-    constexpr int FP_N = 3 * FP_ROWS * F7_PW, FP_B = 6;  // batched, unconditional loads: see k_conv7x7s2_first_mfma
-    PatchWalk pw;
-    pw.start(tid, FP_ROWS);
-    const bool staged = stage_patch_vec4<FP_ROWS>(f0, plane, cr0 * 2 - 3, cc0 * 2 - 3, H, W, sIn, tid);
-    for (int base = tid; !staged && base < FP_N; base += 256 * FP_B) {
-        float v[FP_B];
-        int dst[FP_B];
-#pragma unroll
-        for (int u = 0; u < FP_B; ++u) {
-            const int ci = min(pw.ci, 2), r = pw.r, c = pw.c;
-            const int iy = cr0 * 2 - 3 + r, ix = cc0 * 2 - 3 + c;
-            const float t = f0[ci * plane + (int64_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)];
-            v[u] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? t : 0.f;
-            dst[u] = pw.ci < 3 ? r * F7_PITCH + c * 3 + ci : -1;
-            pw.step256(FP_ROWS);
-        }
-#pragma unroll
-        for (int u = 0; u < FP_B; ++u)
-            if (dst[u] >= 0) sIn[dst[u]] = f2bf(v[u]);
-    }
-    for (int idx = tid; idx < F7_PITCH + 8 + FP_ROWS + 1; idx += 256) {  // see k_conv7x7s2_first_mfma
-        if (idx < F7_PITCH + 8) sIn[FP_ROWS * F7_PITCH + idx] = 0;
-        else sIn[(idx - F7_PITCH - 8) * F7_PITCH + F7_PITCH - 1] = 0;
-    }
+    stage_patch<FP_ROWS>(frame + (int64_t)n * 3 * plane, plane, cr0 * 2 - 3, cc0 * 2 - 3, H, W, sIn, tid);
     const int wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kg = lane >> 4;
     bf16x8 wf[6][NFB];
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks)
-#pragma unroll
-        for (int nf = 0; nf < NFB; ++nf) wf[ks][nf] = __builtin_bit_cast(bf16x8, wimg[(ks * 4 + kg) * NC + nf * 16 + l16]);
+    load_wfrags<NFB>(wimg, kg, l16, wf);
     float bv[NFB][4];
 #pragma unroll
     for (int nf = 0; nf < NFB; ++nf)
@@ -493,13 +484,11 @@ __global__ __launch_bounds__(256) void k_conv7x7s2_pool_first_mfma(const float *
             for (int nf = 0; nf < NFB; ++nf) acc[u][nf] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 6; ++ks) {
-            const int k0 = ks * 32 + kg * 8, ky = k0 / 24, j0 = k0 % 24;
             bf16x8 a[3];
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
-                const int frag = wave * 9 + m0 + u, ly = frag >> 1, lx = (frag & 1) * 16 + l16;
-                const uint32_t *p = reinterpret_cast<const uint32_t *>(sIn + (2 * ly + ky) * F7_PITCH + 6 * lx + j0);
-                a[u] = __builtin_bit_cast(bf16x8, make_uint4(p[0], p[1], p[2], p[3]));
+                const int frag = wave * 9 + m0 + u;
+                a[u] = a_frag(sIn, frag >> 1, (frag & 1) * 16 + l16, ks, kg);
             }
 #pragma unroll
             for (int u = 0; u < 3; ++u)
@@ -728,24 +717,32 @@ ConvLaunch plan_conv2d(int64_t npix, int Cop, int cic) {
     return {pick, 64, slices};
 }
 
+// A planned channel block (64/32/16/8) or a fragment-block count (1..4) as a template argument: f(constant) for the built
+// instance that `cob` / `nfb` names.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+void with_cob(int cob, F &&f) {
+    cob == 64 ? f(int_c<64>{}) : cob == 32 ? f(int_c<32>{}) : cob == 16 ? f(int_c<16>{}) : f(int_c<8>{});
+}
+template <class F>
+void with_nfb(int nfb, F &&f) {
+    nfb == 1 ? f(int_c<1>{}) : nfb == 2 ? f(int_c<2>{}) : nfb == 3 ? f(int_c<3>{}) : f(int_c<4>{});
+}
+
 template <int KS, int S, bool OUT_F32>
 void launch_conv2d(const ConvLaunch &L, dim3 grid, hipStream_t st, const uint4 *x, const uint32_t *wp, const float *bias,
                    const uint4 *addend, void *y, int N, int H, int W, int Ho, int Wo, int cic, int Cop, int relu) {
     const size_t lds = L.slices > 1 ? (size_t)(L.slices - 1) * L.cob * L.threads * sizeof(float) : 0;  // <= 7*64*64*4
-#define FOSVOS_GO(COB, SLICED)                                                                                          \
-    hipLaunchKernelGGL((k_conv2d<KS, S, COB, OUT_F32, SLICED>), grid, dim3(L.threads, L.slices), lds, st, x, wp, bias,      \
-                       addend, y, N, H, W, Ho, Wo, cic, Cop, relu)
-    if (L.slices > 1) {  // (only ever planned with 8-channel blocks)
-        FOSVOS_GO(8, true);
-        return;
-    }
-    switch (L.cob) {
-        case 64: FOSVOS_GO(64, false); break;
-        case 32: FOSVOS_GO(32, false); break;
-        case 16: FOSVOS_GO(16, false); break;
-        default: FOSVOS_GO(8, false); break;
-    }
-#undef FOSVOS_GO
+    const dim3 block(L.threads, L.slices);
+    if (L.slices > 1)  // (only ever planned with 8-channel blocks)
+        hipLaunchKernelGGL((k_conv2d<KS, S, 8, OUT_F32, true>), grid, block, lds, st, x, wp, bias, addend, y, N, H, W, Ho, Wo,
+                           cic, Cop, relu);
+    else
+        with_cob(L.cob, [&](auto cob) {
+            hipLaunchKernelGGL((k_conv2d<KS, S, cob.value, OUT_F32, false>), grid, block, lds, st, x, wp, bias, addend, y, N, H, W,
+                               Ho, Wo, cic, Cop, relu);
+        });
 }
 
 // Shape arithmetic and plan of one fosvos_conv2d_fwd launch (shared with fosvos_conv2d_plan).
@@ -769,25 +766,29 @@ Conv2dGeom conv2d_geom(int N, int H, int W, int Ci, int Co, int k, int stride) {
 }
 
 // ... and of one fosvos_conv7x7s2_first_fwd launch: the MFMA form (nfb fragment blocks of 16 channels, one workgroup per
-// 8 x 32 tile) or the fp32 vector-ALU form (channel blocks of L.cob).
+// 8 x 32 tile) or the fp32 vector-ALU form (channel blocks of L.cob); and of the MFMA form fused with the pool
+// (fosvos_conv7x7s2_pool_first_fwd: one workgroup per 8 x 15 tile of the Hp x Wp pooled map).
 struct FirstGeom {
-    int Ho, Wo, Cop, tiles_x, tiles_y, nfb;
+    int Ho, Wo, Hp, Wp, Cop, tiles_x, pool_tiles_x, nfb;
     bool mfma;
     ConvLaunch L;
-    dim3 grid;
+    dim3 grid, pool_grid;
 };
 FirstGeom first_geom(int N, int H, int W, int Co, unsigned flags) {
     FirstGeom g;
     g.Ho = (H - 1) / 2 + 1;
     g.Wo = (W - 1) / 2 + 1;
+    g.Hp = (g.Ho - 1) / 2 + 1;
+    g.Wp = (g.Wo - 1) / 2 + 1;
     g.Cop = roundup(Co, 8);
     g.tiles_x = (int)cdiv(g.Wo, F7_TW);
-    g.tiles_y = (int)cdiv(g.Ho, F7_TH);
+    g.pool_tiles_x = (int)cdiv(g.Wp, FP_PW);
+    const unsigned tiles = (unsigned)(g.tiles_x * cdiv(g.Ho, F7_TH));
     g.mfma = !(flags & FOSVOS_CONV_FP32_MATH) && g.Cop <= 64;
     g.nfb = std::min(f7_nc(g.Cop) / 16, 4);
     g.L = plan_conv2d((int64_t)N * g.Ho * g.Wo, g.Cop, 1);
-    g.grid = g.mfma ? dim3((unsigned)(g.tiles_x * g.tiles_y), 1, (unsigned)N)
-                    : dim3((unsigned)(g.tiles_x * g.tiles_y), (unsigned)cdiv(g.Cop, g.L.cob), (unsigned)N);
+    g.grid = dim3(tiles, g.mfma ? 1u : (unsigned)cdiv(g.Cop, g.L.cob), (unsigned)N);
+    g.pool_grid = dim3((unsigned)(g.pool_tiles_x * cdiv(g.Hp, FP_PH)), 1, (unsigned)N);
     return g;
 }
 
@@ -875,25 +876,18 @@ extern "C" int fosvos_conv2d_fwd(const uint16_t *x, const uint32_t *w_packed, co
     FOSVOS_REQUIRE((int64_t)N * H * W * cic < (int64_t)1 << 31 && (int64_t)N * Ho * Wo * Cop < (int64_t)1 << 34, FOSVOS_E_ARG,
                    "conv2d_fwd: tensor too large for 32-bit tap offsets");
     FOSVOS_ENTER(device);
+    FOSVOS_REQUIRE(!f32 || (k == 3 && stride == 1), FOSVOS_E_SHAPE, "conv2d_fwd: fp32 output only for 3x3 stride 1");
     const ConvLaunch L = geom.L;
     const dim3 grid = geom.grid;
     const int relu = (flags & FOSVOS_CONV_RELU) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
     const uint4 *xv = reinterpret_cast<const uint4 *>(x), *av = reinterpret_cast<const uint4 *>(addend);
 #define FOSVOS_ARGS L, grid, st, xv, w_packed, bias, av, y, N, H, W, Ho, Wo, cic, Cop, relu
-    if (k == 3 && stride == 1) {
-        if (f32) launch_conv2d<3, 1, true>(FOSVOS_ARGS);
-        else launch_conv2d<3, 1, false>(FOSVOS_ARGS);
-    } else if (k == 3) {
-        FOSVOS_REQUIRE(!f32, FOSVOS_E_SHAPE, "conv2d_fwd: fp32 output only for 3x3 stride 1");
-        launch_conv2d<3, 2, false>(FOSVOS_ARGS);
-    } else if (stride == 1) {
-        FOSVOS_REQUIRE(!f32, FOSVOS_E_SHAPE, "conv2d_fwd: fp32 output only for 3x3 stride 1");
-        launch_conv2d<1, 1, false>(FOSVOS_ARGS);
-    } else {
-        FOSVOS_REQUIRE(!f32, FOSVOS_E_SHAPE, "conv2d_fwd: fp32 output only for 3x3 stride 1");
-        launch_conv2d<1, 2, false>(FOSVOS_ARGS);
-    }
+    if (f32) launch_conv2d<3, 1, true>(FOSVOS_ARGS);
+    else if (k == 3 && stride == 1) launch_conv2d<3, 1, false>(FOSVOS_ARGS);
+    else if (k == 3) launch_conv2d<3, 2, false>(FOSVOS_ARGS);
+    else if (stride == 1) launch_conv2d<1, 1, false>(FOSVOS_ARGS);
+    else launch_conv2d<1, 2, false>(FOSVOS_ARGS);
 #undef FOSVOS_ARGS
     FOSVOS_LAUNCH_CHECK();
     return 0;
@@ -902,7 +896,7 @@ extern "C" int fosvos_conv2d_fwd(const uint16_t *x, const uint32_t *w_packed, co
 extern "C" size_t fosvos_conv7x7_packed_elems(int out_ch) {  // fp32 image + slack, then the bf16 MFMA image (2 per float)
     if (out_ch <= 0) return 0;
     const int Cop = roundup(out_ch, 8);
-    return (size_t)147 * Cop + 64 + (size_t)6 * 4 * f7_nc(Cop) * 8 / 2;
+    return (size_t)f7_fp32_elems(Cop) + (size_t)6 * 4 * f7_nc(Cop) * 8 / 2;
 }
 
 extern "C" int fosvos_pack_conv7x7_bn(const float *w_oihw, int Co, const float *bn_weight, const float *bn_bias,
@@ -911,7 +905,7 @@ extern "C" int fosvos_pack_conv7x7_bn(const float *w_oihw, int Co, const float *
     FOSVOS_REQUIRE(w_oihw && w_packed && bias_out && Co > 0, FOSVOS_E_ARG, "pack_conv7x7_bn: bad argument");
     FOSVOS_REQUIRE(!bn_weight || (bn_bias && bn_mean && bn_var), FOSVOS_E_ARG, "pack_conv7x7_bn: partial BatchNorm");
     FOSVOS_ENTER(device);
-    const int Cop = roundup(Co, 8), total = 147 * Cop + 64;
+    const int Cop = roundup(Co, 8), total = f7_fp32_elems(Cop);
     const int bias_len = (int)fosvos_conv2d_bias_elems(Co);
     const int n = std::max(std::max(total, bias_len), 6 * 4 * f7_nc(Cop) * 8);
     hipLaunchKernelGGL(k_pack_conv7x7_bn, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, w_oihw, Co,
@@ -928,38 +922,22 @@ extern "C" int fosvos_conv7x7s2_first_fwd(const float *frame, const float *w_pac
                    "conv7x7s2_first_fwd: flags 0x%x", flags);
     FOSVOS_ENTER(device);
     FOSVOS_REQUIRE(N < 65536, FOSVOS_E_ARG, "conv7x7s2_first_fwd: N=%d", N);
-    const FirstGeom geom = first_geom(N, H, W, Co, flags);
-    const int Ho = geom.Ho, Wo = geom.Wo, Cop = geom.Cop, tiles_x = geom.tiles_x;
+    const FirstGeom g = first_geom(N, H, W, Co, flags);
     const int relu = (flags & FOSVOS_CONV_RELU) ? 1 : 0;
-    if (geom.mfma) {  // bf16 MFMA form
-        const uint4 *wimg = reinterpret_cast<const uint4 *>(w_packed + 147 * Cop + 64);
-        const dim3 g = geom.grid;
-#define FOSVOS_GO(NFB)                                                                                                   \
-    hipLaunchKernelGGL(k_conv7x7s2_first_mfma<NFB>, g, dim3(256), 0, (hipStream_t)stream, frame, wimg, bias, y, H, W, Ho, Wo, \
-                       tiles_x, Cop, relu)
-        switch (geom.nfb) {
-            case 1: FOSVOS_GO(1); break;
-            case 2: FOSVOS_GO(2); break;
-            case 3: FOSVOS_GO(3); break;
-            default: FOSVOS_GO(4); break;
-        }
-#undef FOSVOS_GO
-        FOSVOS_LAUNCH_CHECK();
-        return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (g.mfma) {  // bf16 MFMA form
+        const uint4 *wimg = reinterpret_cast<const uint4 *>(f7_mfma_image(w_packed, g.Cop));
+        with_nfb(g.nfb, [&](auto nfb) {
+            hipLaunchKernelGGL(k_conv7x7s2_first_mfma<nfb.value>, g.grid, dim3(256), 0, st, frame, wimg, bias, y, H, W, g.Ho, g.Wo,
+                               g.tiles_x, g.Cop, relu);
+        });
+    } else {
+        uint4 *yv = reinterpret_cast<uint4 *>(y);
+        with_cob(g.L.cob, [&](auto cob) {
+            hipLaunchKernelGGL(k_conv7x7s2_first<cob.value>, g.grid, dim3(256), 0, st, frame, w_packed, bias, yv, H, W, g.Ho, g.Wo,
+                               g.tiles_x, g.Cop, relu);
+        });
     }
-    const ConvLaunch L = geom.L;
-    const dim3 grid = geom.grid;
-    uint4 *yv = reinterpret_cast<uint4 *>(y);
-#define FOSVOS_GO(COB)                                                                                                \
-    hipLaunchKernelGGL(k_conv7x7s2_first<COB>, grid, dim3(256), 0, (hipStream_t)stream, frame, w_packed, bias, yv, H, W, Ho, \
-                       Wo, tiles_x, Cop, relu)
-    switch (L.cob) {
-        case 64: FOSVOS_GO(64); break;
-        case 32: FOSVOS_GO(32); break;
-        case 16: FOSVOS_GO(16); break;
-        default: FOSVOS_GO(8); break;
-    }
-#undef FOSVOS_GO
     FOSVOS_LAUNCH_CHECK();
     return 0;
 }
@@ -969,23 +947,14 @@ extern "C" int fosvos_conv7x7s2_pool_first_fwd(const float *frame, const float *
     FOSVOS_REQUIRE(frame && w_packed && bias && y_pooled, FOSVOS_E_ARG, "conv7x7s2_pool_first_fwd: null pointer");
     FOSVOS_REQUIRE(N > 0 && N < 65536 && H > 0 && W > 0 && Co > 0, FOSVOS_E_ARG, "conv7x7s2_pool_first_fwd: N=%d H=%d W=%d Co=%d",
                    N, H, W, Co);
-    const int Cop = roundup(Co, 8);
-    FOSVOS_REQUIRE(Cop <= 64, FOSVOS_E_SHAPE, "conv7x7s2_pool_first_fwd: at most 64 channels (got %d)", Co);
+    const FirstGeom g = first_geom(N, H, W, Co, 0);
+    FOSVOS_REQUIRE(g.mfma, FOSVOS_E_SHAPE, "conv7x7s2_pool_first_fwd: at most 64 channels (got %d)", Co);
     FOSVOS_ENTER(device);
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, Hp = (Ho - 1) / 2 + 1, Wp = (Wo - 1) / 2 + 1;
-    const int tiles_x = (int)cdiv(Wp, FP_PW), tiles_y = (int)cdiv(Hp, FP_PH);
-    const uint4 *wimg = reinterpret_cast<const uint4 *>(w_packed + 147 * Cop + 64);
-    const dim3 g((unsigned)(tiles_x * tiles_y), 1, (unsigned)N);
-#define FOSVOS_GO(NFB)                                                                                                    \
-    hipLaunchKernelGGL(k_conv7x7s2_pool_first_mfma<NFB>, g, dim3(256), 0, (hipStream_t)stream, frame, wimg, bias, y_pooled, H, \
-                       W, Ho, Wo, Hp, Wp, tiles_x, Cop)
-    switch (f7_nc(Cop) / 16) {
-        case 1: FOSVOS_GO(1); break;
-        case 2: FOSVOS_GO(2); break;
-        case 3: FOSVOS_GO(3); break;
-        default: FOSVOS_GO(4); break;
-    }
-#undef FOSVOS_GO
+    const uint4 *wimg = reinterpret_cast<const uint4 *>(f7_mfma_image(w_packed, g.Cop));
+    with_nfb(g.nfb, [&](auto nfb) {
+        hipLaunchKernelGGL(k_conv7x7s2_pool_first_mfma<nfb.value>, g.pool_grid, dim3(256), 0, (hipStream_t)stream, frame, wimg,
+                           bias, y_pooled, H, W, g.Ho, g.Wo, g.Hp, g.Wp, g.pool_tiles_x, g.Cop);
+    });
     FOSVOS_LAUNCH_CHECK();
     return 0;
 }
@@ -1061,7 +1030,7 @@ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Arena: [first conv output][4 rotating activation slots of the largest block tensor][4 fp32 side maps]
 struct ResnetLayout {
-    size_t first_bytes, slot_bytes, side_off[4], side_bytes[4], ws_off, ws_bytes, aux_ws_off, aux_ws_bytes, total;
+    size_t first_bytes, slot_bytes, side_off[4], side_bytes[4], total;
     int hs[4], ws[4];
 };
 
@@ -1073,7 +1042,7 @@ int resnet_layout(const fosvos_resnet_net *net, int N, int H, int W, ResnetLayou
     L->first_bytes = align256(a.bytes(N));
     a.h = (a.h - 1) / 2 + 1;
     a.w = (a.w - 1) / 2 + 1;
-    size_t slot = a.bytes(N), ws = 0, aux_ws = 0;
+    size_t slot = a.bytes(N);
     int b = 0;
     for (int s = 0; s < 4; ++s) {
         FOSVOS_REQUIRE(net->blocks_per_stage[s] > 0, FOSVOS_E_ARG, "resnet: stage %d has no blocks", s);
@@ -1111,11 +1080,8 @@ int resnet_layout(const fosvos_resnet_net *net, int N, int H, int W, ResnetLayou
         const fosvos_conv2d_desc &sp = net->side[s];
         FOSVOS_REQUIRE(sp.w_packed && sp.bias && sp.Co == 16 && sp.k == 3 && sp.stride == 1 && (sp.kind == 0 || sp.kind == 1),
                        FOSVOS_E_SHAPE, "resnet: side_prep %d must be a 3x3 stride-1 conv to 16 channels", s);
-        if (sp.kind == 1) {
-            FOSVOS_REQUIRE(sp.Ci % 32 == 0, FOSVOS_E_SHAPE, "resnet: side_prep %d (%d channels in) does not fit the MFMA path", s,
-                           sp.Ci);
-            aux_ws = std::max(aux_ws, fosvos_conv3x3_workspace_bytes(N, a.h, a.w, sp.Ci, 16));
-        }
+        FOSVOS_REQUIRE(sp.kind == 0 || sp.Ci % 32 == 0, FOSVOS_E_SHAPE,
+                       "resnet: side_prep %d (%d channels in) does not fit the MFMA path", s, sp.Ci);
         FOSVOS_REQUIRE(sp.Ci == a.c, FOSVOS_E_SHAPE, "resnet: side_prep %d expects %d input channels, the stage produces %d", s,
                        sp.Ci, a.c);
         L->hs[s] = a.h;
@@ -1128,12 +1094,23 @@ int resnet_layout(const fosvos_resnet_net *net, int N, int H, int W, ResnetLayou
         L->side_off[s] = off;
         off += L->side_bytes[s];
     }
-    L->ws_off = off;
-    L->ws_bytes = align256(ws);
-    L->aux_ws_off = off + L->ws_bytes;  // the side_prep convs may run beside the trunk (aux_stream): their own split-K slabs
-    L->aux_ws_bytes = align256(aux_ws);
-    L->total = L->aux_ws_off + L->aux_ws_bytes + 256;
+    L->total = off + 256;
     return 0;
+}
+
+// One conv of the net through the C entry its descriptor names: the MFMA implicit GEMM (kind 1; stride 2 is its
+// subsampling form, which has no residual epilogue - resnet_layout lets it be no block's last conv) or the vector-ALU
+// conv.  Neither MFMA entry splits K: they take no workspace.
+int run_conv(const fosvos_conv2d_desc &c, const uint16_t *in, const uint16_t *addend, void *out, int N, int h, int w,
+             unsigned flags, int device, void *stream) {
+    const uint16_t *wf = reinterpret_cast<const uint16_t *>(c.w_packed);
+    if (c.kind == 1 && c.stride == 2)
+        return fosvos_conv3x3_s2_fwd(in, wf, c.bias, reinterpret_cast<uint16_t *>(out), N, h, w, c.Ci, c.Co, flags, nullptr, 0,
+                                     device, stream);
+    if (c.kind == 1)
+        return fosvos_conv3x3_fwd_add(in, wf, c.bias, addend, out, N, h, w, c.Ci, c.Co, flags, nullptr, 0, device, stream);
+    return fosvos_conv2d_fwd(in, reinterpret_cast<const uint32_t *>(c.w_packed), c.bias, addend, out, N, h, w, c.Ci, c.Co, c.k,
+                             c.stride, flags, device, stream);
 }
 
 }  // namespace
@@ -1153,6 +1130,8 @@ extern "C" int fosvos_resnet_forward(const fosvos_resnet_net *net, const float *
     ResnetLayout L;
     if (int rc = resnet_layout(net, N, H, W, &L)) return rc;
     FOSVOS_REQUIRE(frame && arena && fused, FOSVOS_E_ARG, "resnet_forward: null pointer");
+    FOSVOS_REQUIRE(net->first_unfused || !net->first_fp32_math, FOSVOS_E_ARG,
+                   "resnet_forward: the first layer fused with the pool has no fp32 form (first_unfused = 0 with first_fp32_math)");
     FOSVOS_REQUIRE(arena_bytes >= L.total, FOSVOS_E_WORKSPACE, "resnet_forward: arena of %zu bytes, %zu needed", arena_bytes,
                    L.total);
     FOSVOS_ENTER(device);
@@ -1186,9 +1165,7 @@ extern "C" int fosvos_resnet_forward(const fosvos_resnet_net *net, const float *
     };
 
     int h = (H - 1) / 2 + 1, w = (W - 1) / 2 + 1;
-    // (fused with the pool up to 32 channels: above, the conv tile in LDS leaves one workgroup per CU and the fused launch
-    // loses to the two kernels - 0.578 vs 0.55 ms per 1080p frame at 64 channels)
-    if (!net->first_fp32_math && !net->first_unfused && roundup(net->first_co, 8) <= 32) {
+    if (!net->first_unfused) {  // (the caller's decision: ResnetPlan.fuse_first states when it pays)
         if (int rc = fosvos_conv7x7s2_pool_first_fwd(frame, net->first_w, net->first_b, slot[0], N, H, W, net->first_co, device,
                                                      stream))
             return rc;
@@ -1215,9 +1192,7 @@ extern "C" int fosvos_resnet_forward(const fosvos_resnet_net *net, const float *
                     FOSVOS_HIP_CHECK(hipEventRecord(ev[0], sm));
                     FOSVOS_HIP_CHECK(hipStreamWaitEvent(sa, ev[0], 0));
                 }
-                if (int rc = fosvos_conv2d_fwd(slot[cur], reinterpret_cast<const uint32_t *>(blk.down.w_packed), blk.down.bias,
-                                               nullptr, slot[res], N, h, w, blk.down.Ci, blk.down.Co, blk.down.k, blk.down.stride, 0,
-                                               device, par ? aux_stream : stream))
+                if (int rc = run_conv(blk.down, slot[cur], nullptr, slot[res], N, h, w, 0, device, par ? aux_stream : stream))
                     return rc;
                 if (par) FOSVOS_HIP_CHECK(hipEventRecord(ev[1], sa));
             }
@@ -1228,19 +1203,8 @@ extern "C" int fosvos_resnet_forward(const fosvos_resnet_net *net, const float *
                 const int out = other(in, res, last ? -1 : cur);  // (the block input stays live until the residual is taken)
                 if (int rc = before_write(out)) return rc;
                 if (last && blk.has_down && par) FOSVOS_HIP_CHECK(hipStreamWaitEvent(sm, ev[1], 0));
-                const uint16_t *add = last ? slot[res] : nullptr;
-                const int rc = c.kind == 1 && c.stride == 2
-                                   ? fosvos_conv3x3_s2_fwd(slot[in], reinterpret_cast<const uint16_t *>(c.w_packed), c.bias, slot[out],
-                                                           N, ih, iw, c.Ci, c.Co, FOSVOS_CONV_RELU, base + L.ws_off, L.ws_bytes,
-                                                           device, stream)
-                               : c.kind == 1
-                                   ? fosvos_conv3x3_fwd_add(slot[in], reinterpret_cast<const uint16_t *>(c.w_packed), c.bias, add,
-                                                            slot[out], N, ih, iw, c.Ci, c.Co, FOSVOS_CONV_RELU, base + L.ws_off,
-                                                            L.ws_bytes, device, stream)
-                                   : fosvos_conv2d_fwd(slot[in], reinterpret_cast<const uint32_t *>(c.w_packed), c.bias, add,
-                                                       slot[out], N, ih, iw, c.Ci, c.Co, c.k, c.stride, FOSVOS_CONV_RELU, device,
-                                                       stream);
-                if (rc) return rc;
+                if (int rc = run_conv(c, slot[in], last ? slot[res] : nullptr, slot[out], N, ih, iw, FOSVOS_CONV_RELU, device, stream))
+                    return rc;
                 ih = conv_out(ih, c.k, c.stride);
                 iw = conv_out(iw, c.k, c.stride);
                 in = out;
@@ -1262,12 +1226,7 @@ extern "C" int fosvos_resnet_forward(const fosvos_resnet_net *net, const float *
             FOSVOS_HIP_CHECK(hipStreamWaitEvent(sa, ev[6 + s], 0));
             st = aux_stream;
         }
-        const int rc = sp.kind == 1 ? fosvos_conv3x3_fwd_add(slot[cur], reinterpret_cast<const uint16_t *>(sp.w_packed), sp.bias,
-                                                             nullptr, smap, N, h, w, sp.Ci, 16, FOSVOS_CONV_OUT_F32,
-                                                             base + L.aux_ws_off, L.aux_ws_bytes, device, st)
-                                    : fosvos_conv2d_fwd(slot[cur], reinterpret_cast<const uint32_t *>(sp.w_packed), sp.bias, nullptr,
-                                                        smap, N, h, w, sp.Ci, sp.Co, 3, 1, FOSVOS_CONV_OUT_F32, device, st);
-        if (rc) return rc;
+        if (int rc = run_conv(sp, slot[cur], nullptr, smap, N, h, w, FOSVOS_CONV_OUT_F32, device, st)) return rc;
         if (par) {
             FOSVOS_HIP_CHECK(hipEventRecord(ev[2 + s], sa));
             busy_slot = cur;

@@ -17,7 +17,7 @@ PKG_ROOT = os.path.dirname(_HERE)                       # .../fosvos_amd
 LIB_PATH = os.environ.get("FOSVOS_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libfosvos_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "fosvos_hip.h")
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 CONV_RELU = 1
 CONV_OUT_F32 = 2
 VGG_COMPACT_STAGE1 = 1  # pass flag of fosvos_vgg_forward_flags / _backward_flags

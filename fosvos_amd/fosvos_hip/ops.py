@@ -802,6 +802,18 @@ class CbceFramesStaged(CbceFramesMultiStaged):
 
 
 # ------------------------------------------------------------------------------------------ thin-channel ResNet path
+def _bn_args(bn: Optional[Sequence], co: int, who: str) -> list:
+    """The (weight, bias, running_mean, running_var, eps) of an eval-mode BatchNorm2d over ``co`` channels, or None, as the
+    pack entries take it: four pointers and eps."""
+    if bn is None:
+        return [None] * 4 + [0.0]
+    for t in bn[:4]:
+        _need(t, _F32, f"{who} BatchNorm tensor")
+        if t.numel() != co:
+            raise ValueError(f"{who}: BatchNorm size != out channels")
+    return [t.data_ptr() for t in bn[:4]] + [float(bn[4])]
+
+
 def fold_conv_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn: Optional[Sequence] = None):
     """(w * s, bn_bias - mean * s [+ conv_bias * s]) with s = bn_weight / sqrt(var + eps): fp32 OIHW in and out."""
     _need(w, _F32, "fold_conv_bn weight")
@@ -810,18 +822,10 @@ def fold_conv_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn: 
         raise ValueError("fold_conv_bn: square kernels only")
     out = torch.empty_like(w)
     bias = torch.empty((co,), dtype=_F32, device=w.device)
-    bnp = [None] * 4
-    eps = 0.0
-    if bn is not None:
-        for t in bn[:4]:
-            _need(t, _F32, "fold_conv_bn BatchNorm tensor")
-            if t.numel() != co:
-                raise ValueError("fold_conv_bn: BatchNorm size != out channels")
-        bnp = [t.data_ptr() for t in bn[:4]]
-        eps = float(bn[4])
+    bnp = _bn_args(bn, co, "fold_conv_bn")
     if conv_bias is not None:
         _need(conv_bias, _F32, "fold_conv_bn conv bias")
-    _launch("fold_conv_bn", w, w.data_ptr(), co, ci, k, _p(conv_bias), *bnp, eps, out.data_ptr(), bias.data_ptr(), record=False)
+    _launch("fold_conv_bn", w, w.data_ptr(), co, ci, k, _p(conv_bias), *bnp, out.data_ptr(), bias.data_ptr(), record=False)
     return out, bias
 
 
@@ -843,9 +847,8 @@ def conv3x3_fwd_add(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor,
         _need(addend, _BF16, "conv3x3_fwd_add addend")
         if addend.shape != y.shape:
             raise ValueError(f"conv3x3_fwd_add: addend {tuple(addend.shape)} vs output {tuple(y.shape)}")
-    ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, ci, co), x.device)
     _launch("conv3x3_fwd_add", x, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), _p(addend), y.data_ptr(), n, h, wd, ci, co,
-            (CONV_RELU if relu else 0) | (CONV_OUT_F32 if out_f32 else 0), ws, wsn,
+            (CONV_RELU if relu else 0) | (CONV_OUT_F32 if out_f32 else 0), None, 0,   # (never splits K: no workspace)
             record=f"mfma3x3s1 {ci}->{co} @{h}x{wd}" if _PROF is not None and _PROF.detail else "mfma3x3s1",
             flops=2.0 * n * h * wd * 9 * ci * co,
             nbytes=2 * (x.numel() + y.numel()) + (2 * addend.numel() if addend is not None else 0))
@@ -865,9 +868,8 @@ def conv3x3_s2_fwd(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, 
         raise ValueError("conv3x3_s2_fwd: packed weight / bias size does not match (Co, Ci)")
     ho, wo = (h - 1) // 2 + 1, (wd - 1) // 2 + 1
     y = torch.empty((n, ho, wo, co), dtype=_BF16, device=x.device)
-    ws, wsn = _WS.get(L.fosvos_conv3x3_workspace_bytes(n, h, wd, ci, co), x.device)
     _launch("conv3x3_s2_fwd", x, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, wd, ci, co,
-            CONV_RELU if relu else 0, ws, wsn,
+            CONV_RELU if relu else 0, None, 0,   # (never splits K: no workspace)
             record=f"mfma3x3s2 {ci}->{co} @{ho}x{wo}" if _PROF is not None and _PROF.detail else "mfma3x3s2",
             flops=2.0 * n * ho * wo * 9 * ci * co, nbytes=2 * (x.numel() + y.numel()))
     return y
@@ -887,19 +889,10 @@ def pack_conv2d_bn(w: torch.Tensor, conv_bias: Optional[torch.Tensor] = None, bn
     L = lib()
     packed = torch.empty((L.fosvos_conv2d_packed_dwords(co, ci, k),), dtype=torch.int32, device=w.device)
     bias = torch.empty((L.fosvos_conv2d_bias_elems(co),), dtype=_F32, device=w.device)
-    bnp = [None] * 4
-    eps = 0.0
-    if bn is not None:
-        for t in bn[:4]:
-            _need(t, _F32, "pack_conv2d_bn BatchNorm tensor")
-            if t.numel() != co:
-                raise ValueError("pack_conv2d_bn: BatchNorm size != out channels")
-        bnp = [t.data_ptr() for t in bn[:4]]
-        eps = float(bn[4])
+    bnp = _bn_args(bn, co, "pack_conv2d_bn")
     if conv_bias is not None:
         _need(conv_bias, _F32, "pack_conv2d_bn conv bias")
-    _launch("pack_conv2d_bn", w, w.data_ptr(), co, ci, k, _p(conv_bias), *bnp, eps, packed.data_ptr(), bias.data_ptr(),
-            record=False)
+    _launch("pack_conv2d_bn", w, w.data_ptr(), co, ci, k, _p(conv_bias), *bnp, packed.data_ptr(), bias.data_ptr(), record=False)
     return packed, bias
 
 
@@ -948,14 +941,8 @@ def pack_conv7x7_bn(w: torch.Tensor, bn: Optional[Sequence] = None):
     L = lib()
     packed = torch.empty((L.fosvos_conv7x7_packed_elems(co),), dtype=_F32, device=w.device)
     bias = torch.empty((L.fosvos_conv2d_bias_elems(co),), dtype=_F32, device=w.device)
-    bnp = [None] * 4
-    eps = 0.0
-    if bn is not None:
-        for t in bn[:4]:
-            _need(t, _F32, "pack_conv7x7_bn BatchNorm tensor")
-        bnp = [t.data_ptr() for t in bn[:4]]
-        eps = float(bn[4])
-    _launch("pack_conv7x7_bn", w, w.data_ptr(), co, *bnp, eps, packed.data_ptr(), bias.data_ptr(), record=False)
+    bnp = _bn_args(bn, co, "pack_conv7x7_bn")
+    _launch("pack_conv7x7_bn", w, w.data_ptr(), co, *bnp, packed.data_ptr(), bias.data_ptr(), record=False)
     return packed, bias
 
 

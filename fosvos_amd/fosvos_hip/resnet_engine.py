@@ -39,6 +39,19 @@ def _pad_to(t: Optional[torch.Tensor], n: int, value: float = 0.0) -> Optional[t
     return out
 
 
+def _padded(conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d], ci_p: int, co_p: int):
+    """(weight, conv bias, BatchNorm tuple) of a conv widened with zeros to the stored widths ci_p -> co_p; padded
+    channels: scale 0 (weight 0 over variance 1), shift 0."""
+    w = conv.weight.detach()
+    if (co_p, ci_p) != tuple(w.shape[:2]):
+        wp = torch.zeros((co_p, ci_p) + tuple(w.shape[2:]), dtype=w.dtype, device=w.device)
+        wp[:w.shape[0], :w.shape[1]] = w
+        w = wp
+    bnp = None if bn is None else (_pad_to(bn.weight.detach(), co_p), _pad_to(bn.bias.detach(), co_p),
+                                   _pad_to(bn.running_mean, co_p), _pad_to(bn.running_var, co_p, 1.0), bn.eps)
+    return w.contiguous(), None if conv.bias is None else _pad_to(conv.bias.detach(), co_p), bnp
+
+
 class _Conv:
     """One packed conv (+ folded BatchNorm) between maps of physical widths ci_p -> co_p (see width()).  3x3 layers whose
     physical channel counts fit the MFMA implicit GEMM (Ci % 32 == 0; Co % 64 == 0, Co = 32, or the 16-channel side_prep
@@ -55,38 +68,26 @@ class _Conv:
             raise NotImplementedError(f"{what}: BatchNorm without affine running statistics cannot be folded")
         self.ci_real, self.co_real = conv.in_channels, conv.out_channels
         self.ci, self.co, self.k, self.stride = ci_p, co_p, k, conv.stride[0]
-        w = conv.weight.detach()
-        if (co_p, ci_p) != tuple(w.shape[:2]):
-            wp = torch.zeros((co_p, ci_p, k, k), dtype=w.dtype, device=w.device)
-            wp[:w.shape[0], :w.shape[1]] = w
-            w = wp
-        bnp = None
-        if bn is not None:  # padded channels: scale 0 (weight 0 over variance 1), shift 0
-            bnp = (_pad_to(bn.weight.detach(), co_p), _pad_to(bn.bias.detach(), co_p), _pad_to(bn.running_mean, co_p),
-                   _pad_to(bn.running_var, co_p, 1.0), bn.eps)
-        cb = None if conv.bias is None else _pad_to(conv.bias.detach(), co_p)
+        w, cb, bnp = _padded(conv, bn, ci_p, co_p)
         # (16 output channels is the side_prep shape: the MFMA path has a 16-wide tile with an fp32 store for it;
         # stride 2 runs there too, with a subsampling store: fosvos_conv3x3_s2_fwd)
         self.kind = int(allow_mfma and k == 3 and ci_p % 32 == 0
                         and (co_p % 64 == 0 or co_p == 32 or (co_p == 16 and self.stride == 1)))
         if self.kind:
-            folded, self.bias = ops.fold_conv_bn(w.contiguous(), cb, bnp)
+            folded, self.bias = ops.fold_conv_bn(w, cb, bnp)
             self.packed, _ = ops.pack_conv3x3_weights(folded, want_fwd=True, want_dgrad=False)
         else:
-            self.packed, self.bias = ops.pack_conv2d_bn(w.contiguous(), cb, bnp)
+            self.packed, self.bias = ops.pack_conv2d_bn(w, cb, bnp)
 
     def __call__(self, x: torch.Tensor, relu: bool, addend: Optional[torch.Tensor] = None,
                  out_f32: bool = False) -> torch.Tensor:
-        if self.kind and self.co == 16:
-            if addend is not None:
-                raise NotImplementedError("16-channel MFMA conv has no residual epilogue")
-            return ops.conv3x3_fwd_add(x, self.packed, self.bias, self.ci, self.co, relu, None, out_f32=out_f32)
+        """The same three-way choice as run_conv of fosvos_resnet_forward."""
         if self.kind and self.stride == 2:
             if addend is not None:
                 raise NotImplementedError("stride-2 MFMA conv has no residual epilogue")
             return ops.conv3x3_s2_fwd(x, self.packed, self.bias, self.ci, self.co, relu)
         if self.kind:
-            return ops.conv3x3_fwd_add(x, self.packed, self.bias, self.ci, self.co, relu, addend)
+            return ops.conv3x3_fwd_add(x, self.packed, self.bias, self.ci, self.co, relu, addend, out_f32=out_f32)
         return ops.conv2d_fwd(x, self.packed, self.bias, self.ci, self.co, self.k, self.stride, relu, addend, out_f32)
 
     def desc(self) -> Conv2dDesc:
@@ -200,14 +201,12 @@ class ResnetPlan:
             raise NotImplementedError(f"layer_base pool {pool}: the HIP path has MaxPool2d(3, 2, 1)")
         c = conv1.out_channels
         self.c0 = width(c, mfma)  # (the first layer writes the padded width too: zero filters, zero shift)
-        w1 = conv1.weight.detach()
-        if self.c0 != c:
-            w1p = torch.zeros((self.c0, 3, 7, 7), dtype=w1.dtype, device=w1.device)
-            w1p[:c] = w1
-            w1 = w1p
-        self.first = ops.pack_conv7x7_bn(w1.contiguous(),
-                                         (_pad_to(bn1.weight.detach(), self.c0), _pad_to(bn1.bias.detach(), self.c0),
-                                          _pad_to(bn1.running_mean, self.c0), _pad_to(bn1.running_var, self.c0, 1.0), bn1.eps))
+        # First layer and pool as one launch: only the MFMA form has it, and up to 32 channels - above, the conv tile in LDS
+        # leaves one workgroup per CU and the fused launch loses to the two kernels (0.578 vs 0.55 ms per 1080p frame at 64
+        # channels).  forward_ops and fosvos_resnet_forward (first_unfused) both take this.
+        self.fuse_first = mfma and self.options.resnet_fuse_first and self.c0 <= 32
+        w1, _, bn1p = _padded(conv1, bn1, 3, self.c0)
+        self.first = ops.pack_conv7x7_bn(w1, bn1p)
         if len(net.layer_stages) != 4 or len(net.side_prep) != 4:
             raise NotImplementedError("the side-output head takes exactly four stages")
         self.stages: List[List[_Block]] = []
@@ -259,7 +258,7 @@ class ResnetPlan:
         net = ResnetNet()
         net.first_w, net.first_b, net.first_co = self.first[0].data_ptr(), self.first[1].data_ptr(), self.c0
         net.first_fp32_math = 0 if self.options.resnet_mfma else 1
-        net.first_unfused = 0 if self.options.resnet_fuse_first else 1
+        net.first_unfused = 0 if self.fuse_first else 1
         for s in range(4):
             net.blocks_per_stage[s] = len(self.stages[s])
             net.side[s] = self.side[s].desc()
@@ -288,11 +287,11 @@ def forward_ops(net: nn.Module, plan: ResnetPlan, x: torch.Tensor) -> List[torch
     with torch.no_grad():
         plan.refresh(net)
         n, _c, h, w = x.shape
-        mfma = plan.options.resnet_mfma
-        if mfma and plan.c0 <= 32 and plan.options.resnet_fuse_first:
+        if plan.fuse_first:
             y = ops.conv7x7s2_pool_first_fwd(x, plan.first[0], plan.first[1], plan.c0)   # conv + pool, one launch
         else:
-            y = ops.conv7x7s2_first_fwd(x, plan.first[0], plan.first[1], plan.c0, relu=True, fp32_math=not mfma)
+            y = ops.conv7x7s2_first_fwd(x, plan.first[0], plan.first[1], plan.c0, relu=True,
+                                        fp32_math=not plan.options.resnet_mfma)
             y = ops.maxpool3x3s2_fwd(y)
         sides = []
         for blocks, side in zip(plan.stages, plan.side):

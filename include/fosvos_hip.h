@@ -39,8 +39,10 @@ extern "C" {
 
 /* 33 also covers the entries added since without touching an existing symbol or struct (additive: an older caller sees no
  * difference): fosvos_conv3x3_fwd_pool_codes, fosvos_conv3x3_pool_codes_bytes, fosvos_maxpool2x2_ceil_bwd_codes,
- * fosvos_vgg_stage1_compact, fosvos_vgg_forward_flags, fosvos_vgg_forward_streams_flags, fosvos_vgg_backward_flags. */
-#define FOSVOS_ABI_VERSION 33
+ * fosvos_vgg_stage1_compact, fosvos_vgg_forward_flags, fosvos_vgg_forward_streams_flags, fosvos_vgg_backward_flags.
+ * 34: no symbol or layout changed, but fosvos_resnet_net.first_unfused is now taken at its word (an older caller that
+ * left it 0 for a wide or fp32 first layer sees a difference), and fosvos_resnet_arena_bytes shrank. */
+#define FOSVOS_ABI_VERSION 34
 
 #define FOSVOS_OK 0
 #define FOSVOS_E_SHAPE (-1)     /* unsupported or inconsistent shape            */
@@ -845,7 +847,8 @@ typedef struct fosvos_resnet_net {
     const float *first_b;
     int first_co;
     int first_fp32_math;        /* != 0: FOSVOS_CONV_FP32_MATH for the first layer */
-    int first_unfused;          /* != 0: first layer and max pool as two launches (A/B runs) */
+    int first_unfused;          /* 0: first layer and max pool in one launch (fosvos_conv7x7s2_pool_first_fwd: the MFMA form
+                                 * only, so first_fp32_math must be 0, and at most 64 channels; it pays up to 32); != 0: two */
     int blocks_per_stage[4];
     const fosvos_resnet_block *blocks;
     fosvos_conv2d_desc side[4]; /* side_prep: 3x3 stride 1, Co = 16 */

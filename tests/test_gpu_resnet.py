@@ -193,6 +193,27 @@ def test_fused_first_conv_and_pool_equal_the_two_kernels():
         assert got.shape == want.shape and torch.equal(got, want), (co, h, w)
 
 
+def test_both_patch_staging_paths_build_the_same_patch():
+    """stage_patch of the two MFMA first-layer kernels: a frame of a width % 4 == 0 on a 16-byte boundary takes 16-byte
+    loads, the same values 4 bytes into a larger buffer take the scalar walk - same bits from both kernels (the smallest
+    frames with ragged right and bottom tiles in both)."""
+    from fosvos_hip import ops
+    g = torch.Generator().manual_seed(17)
+    for co in (16, 64):
+        wt = torch.randn(co, 3, 7, 7, generator=g) * (2.0 / 147) ** 0.5 / 60.0
+        bn = _bn_params(co, g)
+        packed, bias = ops.pack_conv7x7_bn(wt.to(DEV), tuple(t.to(DEV) for t in bn[:4]) + (bn[4],))
+        for shape in ((2, 3, 33, 44), (2, 3, 19, 132)):
+            aligned = (60.0 * torch.randn(shape, generator=g)).to(DEV)
+            shifted = torch.empty(aligned.numel() + 1, dtype=torch.float32, device=DEV)[1:].view(shape)
+            shifted.copy_(aligned)
+            assert aligned.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4 and shifted.is_contiguous()
+            for op in (ops.conv7x7s2_first_fwd, ops.conv7x7s2_pool_first_fwd):
+                a, b = op(aligned, packed, bias, co), op(shifted, packed, bias, co)
+                torch.cuda.synchronize()
+                assert torch.equal(a, b), (op.__name__, co, shape)
+
+
 @pytest.mark.parametrize("h,w", [(64, 96), (70, 101), (33, 47)])
 def test_deconv_head_matches_torch(h, w):
     from fosvos_hip import ops

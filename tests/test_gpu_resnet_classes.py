@@ -590,7 +590,7 @@ def test_teacher_forced_layers_at_1080p(e, mfma):
         w1 = _first_weights(plan, mfma)
         frame = x.cpu().double() if not mfma else bf(x.cpu()).double()
         ref = F.relu(F.conv2d(frame, w1.double(), plan.first[1].cpu()[:plan.c0].double(), stride=2, padding=3))
-        if mfma and plan.c0 <= 32:
+        if plan.fuse_first:
             y = ops.conv7x7s2_pool_first_fwd(x, plan.first[0], plan.first[1], plan.c0)
             M.bf16(f"first+pool 3->{plan.c0}", y.permute(0, 3, 1, 2).cpu().double(), F.max_pool2d(ref, 3, 2, 1))
         else:

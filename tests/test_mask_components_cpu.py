@@ -432,9 +432,9 @@ def lib():
 def test_abi_and_workspace_query():
     import fosvos_hip
     L = lib()
-    assert fosvos_hip.ABI_VERSION == 33 and L.fosvos_abi_version() == 33
+    assert fosvos_hip.ABI_VERSION == 34 and L.fosvos_abi_version() == 34
     with open(fosvos_hip.HEADER_PATH) as f:
-        assert "#define FOSVOS_ABI_VERSION 33" in f.read()
+        assert "#define FOSVOS_ABI_VERSION 34" in f.read()
     q = L.fosvos_components_workspace_bytes
     for n, h, w in ((1, 1, 1), (3, 33, 130), (5, 480, 854)):
         words = h * ((w + 63) // 64)
