@@ -57,7 +57,7 @@ class LoopOptions:
     defer_join: bool = True
     # FOSVOS_SPLIT_STEP=0 = one optimizer step.  On the GPU the step is split by gradient bucket: stages 5-3 (97 % of the
     # parameters) are stepped, zeroed and repacked behind the data-gradient chain, while the weight-gradient stream still
-    # works through stages 3-1; only the small rest waits for that stream (train_online: close_cycle_if_due).
+    # works through stages 3-1; only the small rest waits for that stream (train_online: close_cycle).
     split_step: bool = True
     # FOSVOS_STAGE_LOSS (on only when exactly '1').  The loss of a batched pass in three stages (class counts in front of the
     # forward pass, values and host copy behind the backward pass; fosvos_cbce_loss_frames_parts): two launches and the copy

@@ -5,7 +5,7 @@ Same entry points and loop semantics (src/train_offline.py:77-110): five deeply-
 backward, step every ``avg_grad_every_n``-th iteration; snapshots every ``snapshot_every_n`` epochs.
 
 Opt-in (``--microbatch-group N``, ``_train(..., microbatch_group=N)``): the one-frame minibatches of an accumulation cycle
-run as shape-bucketed batched passes of up to N frames, as the online loop's do (window_closes / plan_passes below).
+run as shape-bucketed batched passes of up to N frames, as the online loop's do (accumulation.window_closes / plan_passes).
 """
 import timeit
 from pathlib import Path
@@ -23,6 +23,7 @@ from util import gpu_handler, io_helper, experiment_helper, args_helper
 from util.logger import get_logger
 from util.network_provider import NetworkProvider, provider_mapping
 from util.settings import OfflineSettings
+import accumulation
 import parallel
 
 log = get_logger(__file__)
@@ -59,10 +60,7 @@ def train_and_test(net_provider: NetworkProvider, settings: OfflineSettings) -> 
         if not settings.is_training:
             net_provider.load_network_test()
         data_loader = io_helper.get_data_loader_test(db_root_dir, settings.batch_size_test, synthetic=synthetic_size)
-        if settings.variant_offline is None:
-            save_dir = save_dir_results / net_provider.name / 'offline'
-        else:
-            save_dir = save_dir_results / net_provider.name / str(settings.variant_offline) / 'offline'
+        save_dir = io_helper.results_dir(save_dir_results, net_provider.name, 'offline', settings.variant_offline)
         experiment_helper.test(net_provider, data_loader, save_dir, settings.is_visualizing_results,
                                settings.eval_speeds)
 
@@ -72,42 +70,13 @@ def _get_summary_writer():
 
 
 def _losses(net, minibatch):
-    inputs, gts = gpu_handler.cast_cuda_if_possible([minibatch['image'], minibatch['gt']])
+    inputs, gts = accumulation.gather([minibatch])
     outputs = net.forward(inputs)
     # Data parallel: this minibatch is one rank's shard of the step's batch.  The reference balances the classes over the
     # whole batch tensor (src/layers/osvos_layers.py:28-39), so the two counts are summed over the ranks first (one
     # 16-byte all-reduce, shared by the five losses); the ranks' losses then add up to the single-process value.
     counts = parallel.batch_label_counts(gts) if data_parallel else None
     return [class_balanced_cross_entropy_loss(o, gts, size_average=False, batch_counts=counts) for o in outputs]
-
-
-def window_closes(n_window: int, counter_gradient: int, avg_grad_every_n: int, max_window: int, end_of_epoch: bool) -> bool:
-    """Whether the minibatches collected so far (``n_window`` of them, ``counter_gradient`` iterations of the accumulation
-    cycle already run in front of them) are run now: a window never crosses an optimizer step, never the end of an epoch
-    (the side-loss weight, the epoch log and the snapshot change there - a CYCLE may straddle it, as in the reference) and
-    holds at most ``max_window`` minibatches."""
-    return ((counter_gradient + n_window) % avg_grad_every_n == 0) or n_window >= max_window or end_of_epoch
-
-
-def plan_passes(shapes, group: int):
-    """The passes of one window.  shapes: the image shapes (N, C, H, W) of its minibatches in draw order.  Returns a list of
-    (indices, batched) in the order the passes run: one-frame minibatches are bucketed by shape, buckets in order of first
-    appearance and frames in draw order, each bucket cut into passes of at most ``group`` frames (batched = True: the frames
-    run concatenated, every frame with the class weights of its own label).  A minibatch that holds several frames is a
-    pass of its own at its place (the reference balances its classes over the whole batch tensor), and so is a frame whose
-    H x W is no multiple of 4 (the per-frame loss kernels read 16-byte vectors): batched = False, today's path."""
-    buckets = {}
-    for i, shape in enumerate(shapes):
-        shape = tuple(int(v) for v in shape)
-        alone = shape[0] != 1 or (shape[-2] * shape[-1]) % 4 != 0
-        buckets.setdefault(('alone', i) if alone else shape, []).append(i)
-    passes = []
-    for key, idx in buckets.items():
-        if key[0] == 'alone':
-            passes.append((idx, False))
-        else:
-            passes.extend((idx[j:j + group], True) for j in range(0, len(idx), group))
-    return passes
 
 
 def _losses_frames(outputs, gts, map_scale, ones, staged=None):
@@ -153,19 +122,15 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
     local_accum = avg_grad_every_n
     # gradients live in one flat fp32 buffer: the wgrad kernels accumulate straight into it, zeroing is one memset,
     # and under data parallelism it is the single all-reduce payload
-    named = list(net.named_parameters())
-    flat = parallel.FlatGrads.attach(net, [p for _, p in named], names=[n for n, _ in named])
+    flat = parallel.FlatGrads.attach_module(net)
     sync = parallel.GradSync(net, flat, options)
     device = next(net.parameters()).device
 
     n_samples_train = len(data_loader_train)
     loss_train, loss_test, losses_train = [], [], []
-    counter_gradient = 0
-    n_iters = 0
-    n_passes = 0
+    cycle = accumulation.Cycle(local_accum)
     max_window = max(microbatch_group, options.group_window)
     ones = torch.ones((microbatch_group, 5), device=device) if microbatch_group > 1 else None  # seed of a batched backward pass
-    reserved_frames = getattr(net, 'reserve_arena_frames', None)
 
     def log_epoch(epoch, running, n_images, start_time):
         if world > 1:  # every rank holds its shards' part of the batch losses: the logged value is their sum
@@ -179,62 +144,54 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
             log.info('Loss %d: %f' % (l, vals[l]))
         log.info('Execution time: ' + str(timeit.default_timer() - start_time))
 
-    def step_if_due():
-        nonlocal counter_gradient
-        if counter_gradient % local_accum == 0:
-            net.join_gradients()
-            sync.finish()  # the bucketed all-reduce begun right behind the cycle's last backward pass
-            optimizer.step()
-            flat.zero()
-            counter_gradient = 0
+    def run_unbatched(minibatch, epoch, running, log_at=None):
+        """The reference's pass over one minibatch, class counts over its whole tensor; `running` takes its five losses.
+        log_at: (images so far, the epoch's start time) where the epoch's log goes between the loss and the backward pass."""
+        losses = _losses(net, minibatch)
+        running += torch.stack([l.detach() for l in losses])
+        loss = (1 - epoch / n_epochs) * sum(losses[:-1]) + losses[-1]
+        if log_at is not None:
+            log_epoch(epoch, running, *log_at)
+        # `loss /= nAveGrad; loss.backward()` of the reference, as a backward pass seeded with 1/nAveGrad (same
+        # gradient, three fewer tiny kernels: see train_online._train)
+        last_of_cycle = world > 1 and cycle.closes(1)
+        if last_of_cycle:
+            sync.arm()
+        loss.backward(torch.full_like(loss.detach(), 1.0 / avg_grad_every_n))
+        if last_of_cycle:
+            sync.begin()
+        if cycle.advance(1):
+            accumulation.close_plain(net, sync, optimizer, flat)
 
     def run_window(window, epoch, running):
         """The minibatches of `window` (inside one accumulation cycle and one epoch, draw order) as the passes of
-        plan_passes; `running` takes the five loss sums of every frame."""
-        nonlocal counter_gradient, n_iters, n_passes
+        accumulation.plan_passes; `running` takes the five loss sums of every frame."""
         w = 1 - epoch / n_epochs
         map_scale = [w / avg_grad_every_n] * 4 + [1.0 / avg_grad_every_n]
-        for idx, batched in plan_passes([mb['image'].shape for mb in window], microbatch_group):
-            if not batched:  # today's pass: class counts over the whole minibatch tensor
-                losses = _losses(net, window[idx[0]])
-                running += torch.stack([l.detach() for l in losses])
-                loss = w * sum(losses[:-1]) + losses[-1]
-                loss.backward(torch.full_like(loss.detach(), 1.0 / avg_grad_every_n))
-            else:
-                if len(idx) == 1:
-                    inputs, gts = window[idx[0]]['image'], window[idx[0]]['gt']
-                else:
-                    inputs = torch.cat([window[i]['image'] for i in idx])
-                    gts = torch.cat([window[i]['gt'] for i in idx])
-                inputs, gts = gpu_handler.cast_cuda_if_possible([inputs, gts])
-                # the loss in three places, as in the online loop: the class counts in front of the forward pass (they need
-                # no logits), ONE launch for the five maps' gradients between the passes, the values behind the backward pass
-                staged = None
-                if options.stage_loss and gts.is_cuda and class_balanced_cross_entropy_loss is _hip_cbce:
-                    staged = stage_frames_loss_multi(gts.contiguous().float(), 5)
-                    if staged is not None:
-                        gts = staged.label
-                outputs = net.forward(inputs)
-                losses, seed = _losses_frames(outputs, gts, map_scale, ones, staged)
-                losses.backward(seed)
+        for idx, batched in accumulation.plan_passes([mb['image'].shape for mb in window], microbatch_group):
+            if not batched:
+                run_unbatched(window[idx[0]], epoch, running)
+                continue
+            inputs, gts = accumulation.gather([window[i] for i in idx])
+            # the loss in three places, as in the online loop: the class counts in front of the forward pass (they need
+            # no logits), ONE launch for the five maps' gradients between the passes, the values behind the backward pass
+            staged = None
+            if options.stage_loss and gts.is_cuda and class_balanced_cross_entropy_loss is _hip_cbce:
+                staged = stage_frames_loss_multi(gts.contiguous().float(), 5)
                 if staged is not None:
-                    staged.finish()
-                running += losses.detach().sum(0)  # (queued behind finish(): no host sync)
-            counter_gradient += len(idx)
-            n_iters += len(idx)
-            n_passes += 1
-        step_if_due()
+                    gts = staged.label
+            outputs = net.forward(inputs)
+            losses, seed = _losses_frames(outputs, gts, map_scale, ones, staged)
+            losses.backward(seed)
+            if staged is not None:
+                staged.finish()
+            running += losses.detach().sum(0)  # (queued behind finish(): no host sync)
+            if cycle.advance(len(idx)):
+                accumulation.close_plain(net, sync, optimizer, flat)
 
     time_all_start = timeit.default_timer()
-    net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
-    if microbatch_group > 1 and reserved_frames is not None:
-        net.reserve_arena_frames = min(microbatch_group, avg_grad_every_n)  # (a pass never holds more frames than a cycle)
-    if not options.defer_join:
-        net.join_gradients()
-    # weights are constant inside an accumulation cycle: let the next forward overlap the wgrad tail of this backward
-    flags.defer_wgrad_join = options.defer_join
-    try:
-        flags.compact_stage1 = bool(compact_stage1)  # (this loop reads nothing of a pass's arena)
+    with accumulation.loop_state(net, flags, options, compact_stage1,
+                                 min(microbatch_group, avg_grad_every_n) if microbatch_group > 1 else None):
         for epoch in range(start_epoch, n_epochs):
             start_time = timeit.default_timer()
             # a DistributedSampler (data-parallel loader) draws the same permutation every epoch unless it is told the
@@ -245,34 +202,18 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
             running = torch.zeros(5, device=device)
             window = []
             for index, minibatch in enumerate(data_loader_train):
-                if microbatch_group > 1:
-                    end_of_epoch = index % n_samples_train == n_samples_train - 1
-                    window.append(minibatch)
-                    if window_closes(len(window), counter_gradient, local_accum, max_window, end_of_epoch):
-                        run_window(window, epoch, running)
-                        window = []
-                    if end_of_epoch:
-                        log_epoch(epoch, running, index + 1, start_time)
+                end_of_epoch = index % n_samples_train == n_samples_train - 1
+                if microbatch_group == 1:
+                    # the epoch's log in front of its last backward pass: the one .tolist() sync per epoch lands while that
+                    # pass and the optimizer step are still to be queued
+                    run_unbatched(minibatch, epoch, running, (index + 1, start_time) if end_of_epoch else None)
                     continue
-                losses = _losses(net, minibatch)
-                running += torch.stack([l.detach() for l in losses])
-                loss = (1 - epoch / n_epochs) * sum(losses[:-1]) + losses[-1]
-
-                if index % n_samples_train == n_samples_train - 1:
+                window.append(minibatch)
+                if accumulation.window_closes(len(window), cycle.counter, local_accum, max_window, end_of_epoch):
+                    run_window(window, epoch, running)
+                    window = []
+                if end_of_epoch:
                     log_epoch(epoch, running, index + 1, start_time)
-
-                # `loss /= nAveGrad; loss.backward()` of the reference, as a backward pass seeded with 1/nAveGrad (same
-                # gradient, three fewer tiny kernels: see train_online._train)
-                last_of_cycle = world > 1 and (counter_gradient + 1) % local_accum == 0
-                if last_of_cycle:
-                    sync.arm()
-                loss.backward(torch.full_like(loss.detach(), 1.0 / avg_grad_every_n))
-                if last_of_cycle:
-                    sync.begin()
-                counter_gradient += 1
-                n_iters += 1
-                n_passes += 1
-                step_if_due()
             if window:  # (a loader that ended before its own length)
                 run_window(window, epoch, running)
 
@@ -290,16 +231,10 @@ def _train(net_provider: NetworkProvider, data_loader_train, data_loader_test, o
                 for l in range(len(vals)):
                     log.info('***Testing *** Loss %d: %f' % (l, vals[l]))
         summary_writer.close()
-    finally:  # whatever happened in the loop, the caller's module does not keep the deferred join
-        net.join_gradients()
-        flags.defer_wgrad_join = False
-        flags.compact_stage1 = False
-        if microbatch_group > 1 and reserved_frames is not None:
-            net.reserve_arena_frames = reserved_frames
     if torch.cuda.is_available():
         torch.cuda.synchronize()
-    return {'loss_train': loss_train, 'loss_test': loss_test, 'losses_train': losses_train, 'iterations': n_iters,
-            'passes': n_passes, 'seconds': timeit.default_timer() - time_all_start}
+    return {'loss_train': loss_train, 'loss_test': loss_test, 'losses_train': losses_train, 'iterations': cycle.iterations,
+            'passes': cycle.passes, 'seconds': timeit.default_timer() - time_all_start}
 
 
 def main(argv=None):

@@ -28,6 +28,7 @@ from util import gpu_handler, io_helper, experiment_helper, args_helper
 from util.logger import get_logger
 from util.network_provider import NetworkProvider, provider_mapping
 from util.settings import OnlineSettings
+import accumulation
 import parallel
 
 log = get_logger(__file__)
@@ -116,6 +117,13 @@ def _report_score(result: Optional[dict], save_dir: Path, seq_name: str) -> None
     scored_sequences.append(result)
 
 
+def _log_mean_score(scored, over: str) -> None:
+    """The run's mean J and F over ``scored`` (each with 'J_stats' and 'F_stats'), as one log line."""
+    j_mean = sum(r['J_stats']['mean'] for r in scored) / len(scored)
+    f_mean = sum(r['F_stats']['mean'] for r in scored) / len(scored)
+    log.info('Score over {0}: J mean {1:.4f}, F mean {2:.4f}, J&F {3:.4f}'.format(over, j_mean, f_mean, (j_mean + f_mean) / 2))
+
+
 def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: OnlineSettings) -> None:
     train_seed = None
     first_sample = None
@@ -139,11 +147,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
             net_provider.load_network_test(sequence=seq_name)
         data_loader = io_helper.get_data_loader_test(db_root_dir, settings.batch_size_test, seq_name,
                                                      synthetic=synthetic_size, device_decode=device_decode)
-        if settings.variant_offline is None:
-            save_dir = save_dir_results / net_provider.name / 'online'
-        else:
-            save_dir = (save_dir_results / net_provider.name / str(settings.variant_offline) /
-                        str(settings.variant_online))
+        save_dir = io_helper.results_dir(save_dir_results, net_provider.name, 'online', settings.variant_offline,
+                                         settings.variant_online)
         if adapt is not None:
             if first_sample is None:  # this call did not train: the training loader still holds the annotated frame
                 first_sample = _first_sample(_train_loader(seq_name, settings))
@@ -226,10 +231,8 @@ def train_and_test_objects(make_provider, seq_name: str, settings: OnlineSetting
         providers.append(provider)
     if not settings.is_testing:
         return None
-    if settings.variant_offline is None:
-        save_dir = save_dir_results / providers[0].name / 'online'
-    else:
-        save_dir = save_dir_results / providers[0].name / str(settings.variant_offline) / str(settings.variant_online)
+    save_dir = io_helper.results_dir(save_dir_results, providers[0].name, 'online', settings.variant_offline,
+                                     settings.variant_online)
     result = experiment_helper.test_objects(providers, test_loader, save_dir, annotations if score else None,
                                             seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
     _report_score(result, save_dir, seq_name)
@@ -328,6 +331,34 @@ class _LossLog:
         self.flush(False)
 
 
+class _PassStreams:
+    """The second stream (``side``, or None) of a cycle whose passes alternate between two (LoopOptions.pass_streams)."""
+
+    def __init__(self, side, device) -> None:
+        self.side, self.device = side, device
+        self.used = False          # a pass of the current cycle ran on the side stream: the optimizer step waits for it
+        self.last_on_side = False  # ... and it was the most recent pass
+
+    def pick(self, i: int, n: int, multi: bool):
+        """The stream of pass i of n of a window (None = the caller's).  The window's LAST pass (the one that may close the
+        cycle) always runs on the caller's: the split optimizer step is queued there, behind that pass's data-gradient chain."""
+        self.last_on_side = multi and (n - 1 - i) % 2 == 1
+        self.used = self.used or self.last_on_side
+        return self.side if self.last_on_side else None
+
+    def wait(self) -> None:
+        """The caller's stream waits for the passes of this cycle that ran on the second pass stream.  (The EARLY part of a
+        split optimizer step does not need this for the EARLIER passes: the weight-gradient kernels of all passes share one
+        stream, in order, and a pass's last weight-gradient kernels wait for the end of its data-gradient chain, so the
+        bucket events of the cycle's last pass also say that every earlier pass has left the stages they cover.  The closing
+        pass's OWN data-gradient chain is not covered by its bucket events - a stage's event is recorded behind the weight
+        gradient of the stage's first conv, which is issued in front of that conv's data gradient - so the closing pass runs
+        on the caller's stream, where the step queues behind it; see pick and _train's close_cycle.)"""
+        if self.used:
+            torch.cuda.current_stream(self.device).wait_stream(self.side)
+            self.used = False
+
+
 def _get_summary_writer(seq_name: str):
     return io_helper.get_summary_writer(Path('tensorboard') / path_stem)
 
@@ -357,7 +388,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
     sync = parallel.GradSync(net, flat, options)
     on_gpu = flat.flat.is_cuda and native
 
-    # on the GPU the optimizer step is split by gradient bucket (see close_cycle_if_due; LoopOptions.split_step)
+    # on the GPU the optimizer step is split by gradient bucket (see close_cycle; LoopOptions.split_step)
     # (slice indices of the flat buffer; flat.bucket_ids maps a slice to the native bucket its gradients are published as)
     early_buckets = [b for b, bid in enumerate(flat.bucket_ids) if bid < parallel.VGG_EARLY_BUCKETS]
     late_buckets = [b for b in range(len(flat.slices)) if b not in early_buckets]
@@ -370,18 +401,18 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
     early_prefixes = tuple(pre for b in early_buckets for pre in parallel.VGG_BUCKETS[flat.bucket_ids[b]])
 
     lazy_zero = on_gpu and options.grad_overwrite  # gradient buffers without zeroing (LoopOptions.grad_overwrite)
-    grads_stale = False
-    pass_streams = None  # a cycle of several passes on two alternating streams (LoopOptions.pass_streams)
+    side_stream = None  # a cycle of several passes on two alternating streams (LoopOptions.pass_streams)
     if flat.flat.is_cuda:
         from fosvos_hip import engine as _engine
         dev_index = flat.flat.device.index if flat.flat.device.index is not None else torch.cuda.current_device()
         # the library's auxiliary streams exist from here on, in their fixed creation order (engine.shared_stream)
         _engine.shared_stream(dev_index, "comm")
         if native and options.defer_join and options.pass_streams:
-            pass_streams = [None, _engine.shared_stream(dev_index, "pass")]  # None = the caller's stream
-    counter_gradient = 0
-    log_every = max(n_epochs // 20, 1)  # the reference divides by n_epochs // 20, which is 0 below 20 epochs
+            side_stream = _engine.shared_stream(dev_index, "pass")
     device = next(net.parameters()).device
+    streams = _PassStreams(side_stream, device)
+    cycle = accumulation.Cycle(local_accum)
+    log_every = max(n_epochs // 20, 1)  # the reference divides by n_epochs // 20, which is 0 below 20 epochs
     max_group = options.microbatch_group
     max_window = max(max_group, options.group_window)
     consts = flat.cache.get(('online', avg_grad_every_n, max_group, str(device)))
@@ -393,40 +424,16 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
     inv_avg, inv_avg_k = consts['inv_avg'], consts['inv_avg_k']
     loss_log = _LossLog(consts['ring'], len(dataloader), log_every, seq_name, summary_writer)
 
-    def is_snapshot_epoch(epoch: int) -> bool:
-        return (epoch % snapshot_every_n) == snapshot_every_n - 1
-
-    side_stream_used = False   # a pass of the current cycle ran on pass_streams[1]: the optimizer step waits for it
-    last_pass_on_side = False  # ... and it was the most recent pass
-
-    def run_group(group, stream=None) -> None:
-        """One forward / loss / backward pass over the micro-batches of `group` (iterations of the reference's loop with
-        the same frame size, inside one accumulation cycle; consecutive or not - see run_window).  The weights do not change inside a cycle, so running k
-        iterations as one batch of k frames leaves every frame's logits, loss (the class weights are still counted per
-        frame) and gradient contribution what the one-by-one loop computes; only the order of the fp32 sums over frames
-        differs.  What it buys on the GPU: k frames per kernel launch (the small stage-5 layers fill the chip without
-        split-K, fewer launch gaps) and one set of weight-gradient partial slabs per group instead of per frame."""
-        nonlocal counter_gradient, n_iters, side_stream_used, last_pass_on_side
+    def run_pass(group) -> None:
+        """One forward / loss / backward pass, on the current stream, over the micro-batches of `group` (iterations of the
+        reference's loop with the same frame size, inside one accumulation cycle; consecutive or not - see run_window).  The
+        weights do not change inside a cycle, so running k iterations as one batch of k frames leaves every frame's logits,
+        loss (the class weights are still counted per frame) and gradient contribution what the one-by-one loop computes; only
+        the order of the fp32 sums over frames differs.  What it buys on the GPU: k frames per kernel launch (the small stage-5
+        layers fill the chip without split-K, fewer launch gaps) and one set of weight-gradient partial slabs per group
+        instead of per frame."""
         k = len(group)
-        last_pass_on_side = stream is not None
-        if stream is not None:
-            side_stream_used = True
-            with torch.cuda.stream(stream):
-                run_pass(group, k)
-        else:
-            run_pass(group, k)
-        counter_gradient += k
-        n_iters += k
-        close_cycle_if_due()
-
-    def run_pass(group, k) -> None:
-        """Forward, loss and backward pass of one group, on the current stream."""
-        if k == 1:
-            inputs, gts = group[0][2]['image'], group[0][2]['gt']
-        else:
-            inputs = torch.cat([g[2]['image'] for g in group])
-            gts = torch.cat([g[2]['gt'] for g in group])
-        inputs, gts = gpu_handler.cast_cuda_if_possible([inputs, gts])
+        inputs, gts = accumulation.gather([g[2] for g in group])
 
         # A batched pass spreads its loss over three places (LoopOptions.stage_loss): the class counts of the labels are taken
         # here, in front of the forward pass (they need no logits), the loss kernel proper sits between the passes, and the
@@ -456,7 +463,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
         # reference: `loss /= nAveGrad; loss.backward()` (src/train_online.py:92-93).  Seeding the backward pass with
         # 1/nAveGrad is the same gradient (the division's own backward produces exactly this factor) without the
         # three tiny kernels of the division, the ones-fill and its backward on the critical path
-        closes_cycle = (counter_gradient + k) % local_accum == 0
+        closes_cycle = cycle.closes(k)
         last_of_cycle = dp_on and closes_cycle
         flags.last_pass_of_cycle = closes_cycle
         if last_of_cycle:
@@ -475,135 +482,99 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
         # (the reference also sums loss.item() into a per-epoch tensorboard scalar, src/train_online.py:94-104: one
         # device sync per frame; the per-pass asynchronous copy above carries the same information without it)
 
-    def wait_side_stream() -> None:
-        """The caller's stream waits for the passes of this cycle that ran on the second pass stream.  (The EARLY part of a
-        split optimizer step does not need this for the EARLIER passes: the weight-gradient kernels of all passes share one
-        stream, in order, and a pass's last weight-gradient kernels wait for the end of its data-gradient chain, so the
-        bucket events of the cycle's last pass also say that every earlier pass has left the stages they cover.  The closing
-        pass's OWN data-gradient chain is not covered by its bucket events - a stage's event is recorded behind the weight
-        gradient of the stage's first conv, which is issued in front of that conv's data gradient - so the closing pass runs
-        on the caller's stream, where the step queues behind it; see run_window and close_cycle_if_due.)"""
-        nonlocal side_stream_used
-        if side_stream_used:
-            torch.cuda.current_stream(device).wait_stream(pass_streams[1])
-            side_stream_used = False
-
-    def close_cycle_if_due() -> None:
+    def close_cycle() -> None:
         """The optimizer step behind the cycle's last pass, on the caller's stream."""
-        nonlocal counter_gradient, grads_stale
-        if counter_gradient % local_accum == 0:
-            if split_step:
-                # Stages 5-3 hold 97 % of the parameters and their gradients are final well before the backward pass ends.
-                # Their share of the optimizer step, the zeroing of their gradients and the repacking of their weights are
-                # queued on the main stream right here - behind the data-gradient chain, while the weight-gradient stream
-                # is still working through stages 3-1 - and only the small rest waits for that stream.
-                # Data parallel: "final" means all-reduced - the early buckets' collectives were begun while the backward pass
-                # was still running, and each is waited for on its own.
-                flags.publish_grad_buckets = False
-                if last_pass_on_side:
-                    # (run_window schedules a window's last pass on the caller's stream, so this is a guard: the early step
-                    # rewrites and repacks weights the closing pass's data-gradient chain on the other stream still reads)
-                    wait_side_stream()
-                for b in early_buckets:
-                    if dp_on:
-                        sync.wait_bucket(b)
-                    else:
-                        net.wait_grad_bucket(flat.bucket_ids[b])
-                optimizer.step(only=early_params, tag='early', zero_grad=not lazy_zero)  # (the step kernel zeroes what it read)
-                net.prepack_weights(early_prefixes)
-                wait_side_stream()
-                net.join_gradients()
-                sync.finish()
-                optimizer.step(only=late_params, tag='late', zero_grad=not lazy_zero)
-            else:
-                wait_side_stream()
-                net.join_gradients()
-                sync.finish()  # the bucketed all-reduce begun right behind the cycle's last backward pass
-                optimizer.step()
-                if not lazy_zero:
-                    flat.zero()
-            grads_stale = lazy_zero
-            counter_gradient = 0
+        if split_step:
+            # Stages 5-3 hold 97 % of the parameters and their gradients are final well before the backward pass ends.
+            # Their share of the optimizer step, the zeroing of their gradients and the repacking of their weights are
+            # queued on the main stream right here - behind the data-gradient chain, while the weight-gradient stream
+            # is still working through stages 3-1 - and only the small rest waits for that stream.
+            # Data parallel: "final" means all-reduced - the early buckets' collectives were begun while the backward pass
+            # was still running, and each is waited for on its own.
+            flags.publish_grad_buckets = False
+            if streams.last_on_side:
+                # (_PassStreams.pick schedules a window's last pass on the caller's stream, so this is a guard: the early step
+                # rewrites and repacks weights the closing pass's data-gradient chain on the other stream still reads)
+                streams.wait()
+            for b in early_buckets:
+                if dp_on:
+                    sync.wait_bucket(b)
+                else:
+                    net.wait_grad_bucket(flat.bucket_ids[b])
+            optimizer.step(only=early_params, tag='early', zero_grad=not lazy_zero)  # (the step kernel zeroes what it read)
+            net.prepack_weights(early_prefixes)
+            streams.wait()
+            net.join_gradients()
+            sync.finish()
+            optimizer.step(only=late_params, tag='late', zero_grad=not lazy_zero)
+        else:
+            streams.wait()
+            accumulation.close_plain(net, sync, optimizer, flat, zero=not lazy_zero)
+        cycle.grads_stale = lazy_zero
 
     def run_window(window) -> None:
-        """The micro-batches the loop has collected (all inside one accumulation cycle, in iteration order) as batched
-        passes: bucketed by frame shape in order of first appearance, each bucket cut into groups of at most `max_group`
-        frames.  The cycle's gradient is a sum over its micro-batches, so the order of the passes changes nothing but the
-        order of fp32 additions - and a loader that yields the same frames already sorted by shape runs the IDENTICAL
-        passes (tested bit for bit).  Minibatches that are batches themselves (N > 1) run alone."""
-        nonlocal grads_stale
-        buckets = {}
-        for item in window:
-            shape = tuple(item[2]['image'].shape)
-            buckets.setdefault(shape if shape[0] == 1 else ('batch', id(item)), []).append(item)
-        groups = [items[i:i + max_group] for items in buckets.values() for i in range(0, len(items), max_group)]
+        """The micro-batches the loop has collected (all inside one accumulation cycle, in iteration order) as the batched
+        passes of accumulation.plan_passes: bucketed by frame shape, each bucket cut into groups of at most `max_group`
+        frames; minibatches that are batches themselves (N > 1) run alone."""
+        plan = accumulation.plan_passes([item[2]['image'].shape for item in window], max_group, odd_alone=False)
+        groups = [[window[i] for i in idx] for idx, _ in plan]
         # (measured at 480x854, passes of 1 / 2 / 3+2 frames: +9.4 % / +2.0 % / -2.6 % - a pass of three or more frames does
         # better with its two forward chains side by side, which needs the auxiliary stream the previous pass's weight
         # gradients would still occupy)
-        multi = pass_streams is not None and not dp_on and len(groups) > 1 and max(len(g) for g in groups) <= 2
+        multi = streams.side is not None and not dp_on and len(groups) > 1 and max(len(g) for g in groups) <= 2
         if lazy_zero:
             # a window that opens a cycle: one pass that is the whole cycle writes its gradients; anything else adds - to
             # zeros (queued here, on the caller's stream, in front of everything the window's passes do on either stream)
-            whole_cycle = counter_gradient == 0 and len(groups) == 1 and len(groups[0]) == local_accum
+            whole_cycle = cycle.counter == 0 and len(groups) == 1 and len(groups[0]) == local_accum
             flags.overwrite_grads = whole_cycle
-            if counter_gradient == 0:
-                if grads_stale and not whole_cycle:
+            if cycle.counter == 0:
+                if cycle.grads_stale and not whole_cycle:
                     flat.zero()
-                grads_stale = False
+                cycle.grads_stale = False
         if multi:
             # both pass streams must see the last optimizer step and the repacked weight images: pack once here, on the
             # caller's stream, instead of inside the first forward pass (which the second stream would have to wait for)
             net.prepack_weights()
-            pass_streams[1].wait_stream(torch.cuda.current_stream(device))
+            streams.side.wait_stream(torch.cuda.current_stream(device))
         flags.forward_one_stream = multi
         for i, group in enumerate(groups):
-            # the window's LAST pass (the one that may close the cycle) always runs on the caller's stream: the split
-            # optimizer step is queued there, behind that pass's data-gradient chain
-            run_group(group, pass_streams[(len(groups) - 1 - i) % 2] if multi else None)
+            stream = streams.pick(i, len(groups), multi)
+            if stream is not None:
+                with torch.cuda.stream(stream):
+                    run_pass(group)
+            else:
+                run_pass(group)
+            if cycle.advance(len(group)):
+                close_cycle()
         if multi:
             # the window's minibatches were allocated on the caller's stream and read on the other one: before they are
             # released (window = [] below; a window can end without a cycle close) the caller's stream waits for it
-            wait_side_stream()
+            streams.wait()
         loss_log.close_window()
-        epoch, _idx, _mb, end_of_epoch = window[-1]
-        if end_of_epoch and is_snapshot_epoch(epoch) and parallel.rank() == 0:
+        epoch, _idx, _mb, snapshot_due = window[-1]
+        if snapshot_due and parallel.rank() == 0:  # (the window ended here: the snapshot holds exactly the updates up to its epoch)
             net_provider.save_model(epoch, sequence=seq_name)
 
     time_all_start = timeit.default_timer()
-    n_iters = 0
-    if native:
-        net.reserve_arena_frames = min(max_group, avg_grad_every_n)  # (a pass never holds more frames than a cycle)
-    net.accumulate_grads_in_place = True  # this loop only ever calls loss.backward()
-    net.compute_side_outputs = False      # ... on outputs[-1] only (src/train_online.py:80): skip the 4 side logit maps
-    if not options.defer_join:
-        net.join_gradients()
-    flags.defer_wgrad_join = options.defer_join
     try:
-        flags.compact_stage1 = bool(compact_stage1)  # (this loop reads nothing of a pass's arena)
-        window = []  # pending (epoch, minibatch index, minibatch, last of its epoch) tuples, all of one accumulation cycle
-        for epoch in range(start_epoch, n_epochs):
-            n_mb = len(dataloader)
-            for minibatch_index, minibatch in enumerate(dataloader):
-                end_of_epoch = minibatch_index == n_mb - 1
-                window.append((epoch, minibatch_index, minibatch, end_of_epoch))
-                # a window ends with its accumulation cycle, and before a snapshot is due (the snapshot must hold exactly the
-                # updates up to its epoch)
-                closes_cycle = (counter_gradient + len(window)) % local_accum == 0
-                if closes_cycle or len(window) >= max_window or (end_of_epoch and is_snapshot_epoch(epoch)):
-                    run_window(window)
-                    window = []
-        if window:
-            run_window(window)
-    finally:  # whatever happened in the loop, the caller's module gets back the flags it came with
-        net.join_gradients()
-        flags.defer_wgrad_join = False
-        flags.publish_grad_buckets = False
+        with accumulation.loop_state(net, flags, options, compact_stage1, min(max_group, avg_grad_every_n) if native else None):
+            net.compute_side_outputs = False  # the loss is on outputs[-1] only (src/train_online.py:80): skip the 4 side logit maps
+            window = []  # pending (epoch, minibatch index, minibatch, snapshot due behind it) tuples, all of one accumulation cycle
+            for epoch in range(start_epoch, n_epochs):
+                n_mb = len(dataloader)
+                for minibatch_index, minibatch in enumerate(dataloader):
+                    snapshot_due = minibatch_index == n_mb - 1 and (epoch % snapshot_every_n) == snapshot_every_n - 1
+                    window.append((epoch, minibatch_index, minibatch, snapshot_due))
+                    if accumulation.window_closes(len(window), cycle.counter, local_accum, max_window, snapshot_due):
+                        run_window(window)
+                        window = []
+            if window:
+                run_window(window)
+    finally:  # (behind loop_state's own: the gradients are joined by now)
         if lazy_zero:
             flags.overwrite_grads = False
-            if grads_stale:  # leave the buffers as optimizer.zero_grad() would (src/train_online.py:100-104)
+            if cycle.grads_stale:  # leave the buffers as optimizer.zero_grad() would (src/train_online.py:100-104)
                 flat.zero()
-        flags.forward_one_stream = False
-        flags.compact_stage1 = False
         net.compute_side_outputs = True
     time_enqueued = timeit.default_timer() - time_all_start  # how far ahead of the device the host loop ran
     if torch.cuda.is_available():
@@ -614,8 +585,8 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
     log.info('Train {0}: total time {1} sec'.format(seq_name, str(time_for_all)))
     log.info('Train {0}: {1} images'.format(seq_name, str(n_images)))
     log.info('Train {0}: time per sample {1} sec'.format(seq_name, str(time_for_all / max(n_images, 1))))
-    return {'loss': loss_log.loss_tr, 'seconds': time_for_all, 'iterations': n_iters, 'seconds_host_enqueue': time_enqueued,
-            'comm_timing': sync.timing_summary() if sync.active and sync.timing else None}
+    return {'loss': loss_log.loss_tr, 'seconds': time_for_all, 'iterations': cycle.iterations,
+            'seconds_host_enqueue': time_enqueued, 'comm_timing': sync.timing_summary() if sync.active and sync.timing else None}
 
 
 def main(argv=None):
@@ -691,10 +662,7 @@ def main(argv=None):
         if score and scored_sequences:
             # the run's mean is over OBJECTS: every object of every sequence counts once
             objects = [o for r in scored_sequences for o in r['objects']]
-            j_mean = sum(o['J_stats']['mean'] for o in objects) / len(objects)
-            f_mean = sum(o['F_stats']['mean'] for o in objects) / len(objects)
-            log.info('Score over {0} objects of {1} sequences: J mean {2:.4f}, F mean {3:.4f}, J&F {4:.4f}'.format(
-                len(objects), len(scored_sequences), j_mean, f_mean, (j_mean + f_mean) / 2))
+            _log_mean_score(objects, '{0} objects of {1} sequences'.format(len(objects), len(scored_sequences)))
         return
     if args.sequence_name is None:
         # replicas: the reference's -sg/-sgs sharding; under torchrun without --data-parallel the ranks shard
@@ -706,11 +674,7 @@ def main(argv=None):
     else:
         train_and_test(net_provider, args.sequence_name, settings)
     if score and scored_sequences:
-        n = len(scored_sequences)
-        j_mean = sum(r['J_stats']['mean'] for r in scored_sequences) / n
-        f_mean = sum(r['F_stats']['mean'] for r in scored_sequences) / n
-        log.info('Score over {0} sequences: J mean {1:.4f}, F mean {2:.4f}, J&F {3:.4f}'.format(
-            n, j_mean, f_mean, (j_mean + f_mean) / 2))
+        _log_mean_score(scored_sequences, '{0} sequences'.format(len(scored_sequences)))
 
 
 if __name__ == '__main__':

@@ -44,6 +44,14 @@ def write_settings(save_dir: Path, name: str, settings, variant_offline: Optiona
         yaml.safe_dump(dataclasses.asdict(settings), f, default_flow_style=False)
 
 
+def results_dir(root: Path, name: str, stage: str, variant_offline, variant_online=None) -> Path:
+    """Where a test pass writes: ``<root>/<name>/<stage>`` (stage 'online' or 'offline') for the plain net, for a variant
+    ``<root>/<name>/<variant_offline>/`` and then 'offline' (its parent network) or the online variant."""
+    if variant_offline is None:
+        return root / name / stage
+    return root / name / str(variant_offline) / ('offline' if stage == 'offline' else str(variant_online))
+
+
 def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] = None,
                           synthetic: Optional[Tuple[int, int]] = None,
                           shard: Optional[Tuple[int, int]] = None, resident: bool = True,

@@ -84,7 +84,7 @@ PAIR = (2, 3, 48, 86)      # a minibatch of two frames: class counts over the wh
 
 
 def test_plan_passes_buckets_by_shape_in_order_of_first_appearance():
-    from train_offline import plan_passes
+    from accumulation import plan_passes
     assert plan_passes([A, B, A, C, B], 5) == [([0, 2], True), ([1, 4], True), ([3], True)]
     assert plan_passes([B, A, A, B], 5) == [([0, 3], True), ([1, 2], True)]
     assert plan_passes([A], 5) == [([0], True)]
@@ -94,14 +94,14 @@ def test_plan_passes_buckets_by_shape_in_order_of_first_appearance():
 
 
 def test_plan_passes_cuts_a_bucket_into_groups():
-    from train_offline import plan_passes
+    from accumulation import plan_passes
     assert plan_passes([A] * 7, 3) == [([0, 1, 2], True), ([3, 4, 5], True), ([6], True)]
     assert plan_passes([A, B] * 3, 2) == [([0, 2], True), ([4], True), ([1, 3], True), ([5], True)]
     assert plan_passes([A] * 3, 1) == [([0], True), ([1], True), ([2], True)]
 
 
 def test_plan_passes_keeps_batches_and_odd_frames_alone():
-    from train_offline import plan_passes
+    from accumulation import plan_passes
     got = plan_passes([A, PAIR, A, ODD, ODD, PAIR], 5)
     assert got == [([0, 2], True), ([1], False), ([3], False), ([4], False), ([5], False)]
     # every minibatch runs exactly once
@@ -114,7 +114,7 @@ def test_plan_passes_keeps_batches_and_odd_frames_alone():
 
 def _windows(n_minibatches, n_epochs, accum, max_window, counter=0):
     """The windows the loop forms: (epoch, first index, length) - a replica of the loop's collection around window_closes."""
-    from train_offline import window_closes
+    from accumulation import window_closes
     out = []
     for epoch in range(n_epochs):
         n = 0
