@@ -89,6 +89,11 @@ class PackEntry(ctypes.Structure):
 
 
 
+class EnsembleView(ctypes.Structure):
+    """fosvos_ensemble_view."""
+    _fields_ = [("data", c_void_p), ("h", c_int), ("w", c_int), ("flip", c_int)]
+
+
 class Conv2dDesc(ctypes.Structure):
     """fosvos_conv2d_desc."""
     _fields_ = [("w_packed", c_void_p), ("bias", c_void_p), ("Ci", c_int), ("Co", c_int), ("k", c_int), ("stride", c_int),
@@ -273,6 +278,8 @@ SIGNATURES = {
                                        ctypes.c_double, c_void_p, c_int, c_void_p]),
     "fosvos_overlay_objects_scaled": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                               c_int, c_void_p, ctypes.c_double, c_void_p, c_int, c_void_p]),
+    "fosvos_ensemble_views": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(EnsembleView), c_int, c_int, c_void_p]),
+    "fosvos_ensemble_merge": (c_int, [POINTER(EnsembleView), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fosvos_vgg_backward": (c_int, [c_void_p, POINTER(VggWeights), POINTER(VggGrads), c_void_p, c_int, c_int, c_int, c_void_p,
                                     c_size_t, c_void_p, POINTER(c_void_p), c_void_p, c_void_p]),
     # compact stage 1 (the pool's winner codes in place of conv1_2's dense output)

@@ -34,6 +34,9 @@ JPEG_SUBSAMPLINGS = ('4:4:4', '4:2:0')
 # rotating and zooming the training sample (dataloaders/custom_transforms.ScaleNRotate): degrees, and the zoom factor
 ROTATE_MAX_ANGLE = 360.0
 ROTATE_SCALE_RANGE = (1.0 / 16, 16.0)
+# the test-time ensemble (util/test_ensemble.py: MAX_VIEWS, SCALE_RANGE); a view's sides are within MAX_FRAME_SIDE
+ENSEMBLE_MAX_VIEWS = 8
+ENSEMBLE_SCALE_RANGE = (0.25, 4.0)
 
 
 def real_number(v) -> bool:

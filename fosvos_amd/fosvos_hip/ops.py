@@ -1483,6 +1483,119 @@ def png_encode_indexed(labels_u8: torch.Tensor, palette: Optional[torch.Tensor] 
     return out, lengths
 
 
+# ------------------------------------------------------------------------------------------ test-time ensemble (ensemble.hip)
+ENSEMBLE_MAX_VIEWS = limits.ENSEMBLE_MAX_VIEWS  # util/test_ensemble.MAX_VIEWS
+
+
+def _ensemble_views(views, h: int, w: int, what: str):
+    """The views of an [h,w] frame as a list of (scale, flip, (hs, ws)); (hs, ws) = ``test_ensemble.view_sizes``."""
+    from util.test_ensemble import view_sizes
+    views = list(views)
+    if not 1 <= len(views) <= ENSEMBLE_MAX_VIEWS:
+        raise ValueError(f"{what}: {len(views)} views, outside [1, {ENSEMBLE_MAX_VIEWS}]")
+    out = []
+    for v in views:
+        try:
+            scale, flip = v
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: a view must be (scale, flip), got {v!r}") from None
+        limits.check_real(what, "a view's scale", scale, *limits.ENSEMBLE_SCALE_RANGE)
+        if not isinstance(flip, bool):
+            raise ValueError(f"{what}: a view's flip must be a bool, got {flip!r}")
+        hs, ws = view_sizes(h, w, scale)
+        if hs > MAX_FRAME_SIDE or ws > MAX_FRAME_SIDE:
+            raise ValueError(f"{what}: the view of scale {scale!r} is {(hs, ws)}, a side above {MAX_FRAME_SIDE}")
+        out.append((scale, flip, (hs, ws)))
+    return out
+
+
+def _ensemble_frame(n: int, h: int, w: int, what: str) -> None:
+    if n > 65535 or h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
+        raise ValueError(f"{what}: N={n} (<= 65535) H={h} W={w} (<= {MAX_FRAME_SIDE})")
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Two contiguous tensors share a byte."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _ensemble_table(tensors, views):
+    from . import EnsembleView
+    table = (EnsembleView * len(tensors))()
+    for entry, t, (_, flip, (hs, ws)) in zip(table, tensors, views):
+        entry.data, entry.h, entry.w, entry.flip = t.data_ptr(), hs, ws, int(flip)
+    return table
+
+
+def ensemble_views(image: torch.Tensor, views, out=None) -> List[torch.Tensor]:
+    """fosvos_ensemble_views: image fp32 [N,3,H,W] and up to 8 views ``(scale, flip)`` -> one fp32 [N,3,Hs,Ws] per view,
+    ``test_ensemble.make_views(image, views)`` bit for bit, all of them from ONE launch.  (Hs, Ws) =
+    ``test_ensemble.view_sizes(H, W, scale)``; a flipped view is mirrored along W; a view of the frame's size is a copy, any
+    other is resampled bilinearly in fp64.  An unflipped view of the frame's size comes back as ``image`` itself, not a
+    copy, and takes no part in the launch (with nothing else asked for, nothing is launched).  ``out``: a list with one
+    entry per view - None for such an identity view, else the tensor to write; none may overlap the image or another.
+    Launched on the current stream, no synchronisation."""
+    what = "ensemble_views"
+    _need(image, _F32, f"{what} image", ValueError)
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0:
+        raise ValueError(f"{what}: image must be a non-empty [N,3,H,W], got {tuple(image.shape)}")
+    n, h, w = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
+    _ensemble_frame(n, h, w, what)
+    views = _ensemble_views(views, h, w, what)
+    if out is not None:
+        out = list(out)
+        if len(out) != len(views):
+            raise ValueError(f"{what}: out must hold one entry per view ({len(views)}), got {len(out)}")
+    result, made = [], []
+    for k, (scale, flip, size) in enumerate(views):
+        given = None if out is None else out[k]
+        if size == (h, w) and not flip:
+            if given is not None:
+                raise ValueError(f"{what}: out[{k}] must be None: view {k} is the image itself")
+            result.append(image)
+            continue
+        t = _out_like(given, (n, 3) + size, _F32, image, what, f"out[{k}]")
+        if given is not None and (_overlap(t, image) or any(_overlap(t, other) for other, _ in made)):
+            raise ValueError(f"{what}: out[{k}] must not overlap the image or another view")
+        result.append(t)
+        made.append((t, views[k]))
+    if made:
+        table = _ensemble_table([t for t, _ in made], [v for _, v in made])
+        _launch(what, image, image.data_ptr(), n, h, w, table, len(made),
+                nbytes=4.0 * (len(made) * image.numel() + sum(t.numel() for t, _ in made)))
+    return result
+
+
+def ensemble_merge(logits: Sequence[torch.Tensor], views, size: Tuple[int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_ensemble_merge: the logits fp32 [N,1,Hs_k,Ws_k] the net gave for the views ``(scale, flip)`` of a frame of
+    ``size`` = (H, W) -> fp32 [N,1,H,W], ``test_ensemble.merge(logits, views, H, W)`` bit for bit: every map resampled to
+    [H,W] (a map of that size as it is), mirrored back where its view was flipped, summed in fp64 in the order of the views
+    and divided by their number.  The pointers travel by value: nothing is concatenated.  ``out`` must not overlap a map.
+    Launched on the current stream, no synchronisation."""
+    what = "ensemble_merge"
+    h, w = limits.check_pair(what, "size", size, "(H, W)")
+    logits = list(logits)
+    views = _ensemble_views(views, h, w, what)
+    if len(logits) != len(views):
+        raise ValueError(f"{what}: {len(logits)} logit maps for {len(views)} views")
+    for t in logits:
+        _need(t, _F32, f"{what} logits", ValueError)
+    n = _logit_shape(logits[0], what)[0]
+    _ensemble_frame(n, h, w, what)
+    for k, (t, (scale, flip, vsize)) in enumerate(zip(logits, views)):
+        if tuple(t.shape) != (n, 1) + vsize:
+            raise ValueError(f"{what}: the map of view {k} {(scale, flip)} must be {(n, 1) + vsize}, got {tuple(t.shape)}")
+    _same_device(what, logits[0], *logits[1:])
+    given = out
+    out = _out_like(out, (n, 1, h, w), _F32, logits[0], what)
+    if given is not None and any(_overlap(out, t) for t in logits):
+        raise ValueError(f"{what}: out must not overlap a logit map")
+    _launch(what, logits[0], _ensemble_table(logits, views), len(views), n, h, w, out.data_ptr(),
+            nbytes=4.0 * (sum(t.numel() for t in logits) + out.numel()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ JPEG files (jpeg.hip)
 JPEG_SUBSAMPLINGS = limits.JPEG_SUBSAMPLINGS
 

@@ -3,8 +3,9 @@
 takes an options object.  The defaults are the measured best; every switch selects between two paths that both stay tested.
 The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleaning) is opt-in by being
 passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
-and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3), and
-RotateOptions (rotating and zooming the training sample).
+and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3),
+RotateOptions (rotating and zooming the training sample) and EnsembleOptions (the test-time ensemble of the
+test pass).
 
 No torch and no library load here: importable anywhere.  The ranges and the scalar checks are ``limits``'.
 """
@@ -302,6 +303,43 @@ class RotateOptions:
         """The ``custom_transforms.ScaleNRotate`` these options describe."""
         from dataloaders import custom_transforms
         return custom_transforms.ScaleNRotate(self.rots, self.scales, self.renormalize)
+
+
+@dataclass(frozen=True)
+class EnsembleOptions:
+    """Test-time ensemble of the test pass (``test_fast(ensemble=)`` and ``test_objects(ensemble=)``; util/test_ensemble.py
+    states the rules): the net also sees the frame mirrored and at other sizes, and the logits are
+    averaged back on the frame's grid.  Opt-in by being passed; this class reads no environment variable."""
+
+    # every scale is also forwarded mirrored along W
+    flip: bool = False
+    # the sizes the net sees the frame at, as factors of the frame's: distinct finite numbers in [0.25, 4]
+    scales: tuple = (1.0,)
+
+    def __post_init__(self) -> None:
+        if not isinstance(self.flip, bool):
+            raise ValueError(f"EnsembleOptions: flip must be a bool, got {self.flip!r}")
+        if type(self.scales) not in (tuple, list) or not self.scales:
+            raise ValueError(f"EnsembleOptions: scales must be a non-empty tuple of numbers, got {self.scales!r}")
+        object.__setattr__(self, "scales", tuple(self.scales))
+        for v in self.scales:
+            limits.check_real("EnsembleOptions", "scales", v, *limits.ENSEMBLE_SCALE_RANGE,
+                              expect=f"finite numbers in [{limits.ENSEMBLE_SCALE_RANGE[0]:g}, {limits.ENSEMBLE_SCALE_RANGE[1]:g}]")
+        if len(set(float(v) for v in self.scales)) != len(self.scales):
+            raise ValueError(f"EnsembleOptions: scales must be distinct, got {self.scales!r}")
+        n_views = len(self.scales) * (2 if self.flip else 1)
+        if n_views == 1 and float(self.scales[0]) == 1.0:
+            raise ValueError("EnsembleOptions: the frame as it is, once, is no ensemble: set flip or give further scales")
+        if not 2 <= n_views <= limits.ENSEMBLE_MAX_VIEWS:
+            raise ValueError(f"EnsembleOptions: {n_views} views, outside [2, {limits.ENSEMBLE_MAX_VIEWS}] "
+                             f"({len(self.scales)} scales{', each also mirrored' if self.flip else ''})")
+
+    def views(self) -> list:
+        """``test_ensemble.views(flip, scales)``: per scale ``(s, False)`` and then, with ``flip``, ``(s, True)``."""
+        return [(float(s), f) for s in self.scales for f in ((False, True) if self.flip else (False,))]
+
+    def as_dict(self) -> dict:
+        return {'flip': self.flip, 'scales': [float(s) for s in self.scales]}
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

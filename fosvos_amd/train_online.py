@@ -49,6 +49,7 @@ multi_object = False        # --multi-object: one net per object, merged and sco
 clean = None                # --clean-min-area / --clean-largest / --clean-temporal (with --fast-test): a CleanOptions
 rotate = None               # --augment-rotate (and its options): a RotateOptions; the one-shot loaders rotate and zoom the sample
 adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
+ensemble = None             # --ensemble-flip / --ensemble-scales (with --fast-test or --multi-object): an EnsembleOptions
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
 
@@ -164,6 +165,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                 cleaning['clean'] = clean
                 if clean.chain:
                     cleaning['clean_seed'] = _clean_seed(train_seed, annotations, data_loader, seq_name)
+            if ensemble is not None:  # (absent: the call is what it was)
+                cleaning['ensemble'] = ensemble
             result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name,
                                                  png_huffman='fitted' if png_fitted else 'fixed', **cleaning)
             _report_score(result, save_dir, seq_name)
@@ -234,7 +237,8 @@ def train_and_test_objects(make_provider, seq_name: str, settings: OnlineSetting
     save_dir = io_helper.results_dir(save_dir_results, providers[0].name, 'online', settings.variant_offline,
                                      settings.variant_online)
     result = experiment_helper.test_objects(providers, test_loader, save_dir, annotations if score else None,
-                                            seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed')
+                                            seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed',
+                                            **({} if ensemble is None else {'ensemble': ensemble}))
     _report_score(result, save_dir, seq_name)
     return result
 
@@ -591,7 +595,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean, adapt, rotate
+    global multi_object, synthetic_objects, clean, adapt, rotate, ensemble
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -609,6 +613,7 @@ def main(argv=None):
                              temporal_radius=args.clean_temporal)
     adapt = args.adapt
     rotate = args.rotate
+    ensemble = args.ensemble
     synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':

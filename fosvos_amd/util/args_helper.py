@@ -5,8 +5,8 @@ argparse cannot call; the intended types are used here.  Exten
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
 --data-parallel, --augment-rotate with --rotate-range / --zoom-range / --rotate-renormalize, --resident-train-set and
 --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
---multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal and --adapt-steps with its --adapt-* options
-(online only).
+--multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal, --adapt-steps with its --adapt-* options,
+--ensemble-flip and --ensemble-scales (online only).
 """
 import argparse
 from typing import List, Optional
@@ -118,6 +118,13 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                             help='with --adapt-steps: weight of the annotated first frame\'s loss in a step (>= 0; default 1)')
         parser.add_argument('--adapt-lr', type=float, default=None, metavar='LR',
                             help='with --adapt-steps: learning rate of the adaptation steps (default: the online loop\'s, 1e-8)')
+        parser.add_argument('--ensemble-flip', action='store_true',
+                            help='with --fast-test or --multi-object: test-time ensemble - the net also sees every frame '
+                                 'mirrored, and the logits are averaged on the device')
+        parser.add_argument('--ensemble-scales', type=float, nargs='+', default=None, metavar='S',
+                            help='with --fast-test or --multi-object: test-time ensemble - the net sees every frame at these '
+                                 'sizes (distinct factors in [0.25, 4], e.g. 0.75 1 1.25), and the logits are averaged on '
+                                 'the frame\'s grid on the device; at most 8 views with --ensemble-flip counted in')
         parser.add_argument('--objects', default=2, type=int, metavar='K',
                             help='with --multi-object --synthetic: the number of objects of the synthetic sequence (1..16)')
     if not is_online:
@@ -197,6 +204,27 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                 parser.error(str(err).replace('AdaptOptions: ', '--adapt-*: '))
         else:
             args.adapt = None
+    if is_online:
+        args.ensemble = None
+        if args.ensemble_flip or args.ensemble_scales is not None:
+            if not args.fast_test and not args.multi_object:
+                parser.error('--ensemble-flip / --ensemble-scales average the logits of the device test pass: they need '
+                             '--fast-test or --multi-object')
+            if args.adapt_steps is not None:
+                parser.error('--ensemble-flip / --ensemble-scales average the answers of a frozen net; adaptation of an '
+                             'ensemble (--adapt-steps) is not built')
+            if args.eval_speeds:
+                parser.error('--ensemble-flip / --ensemble-scales belong to a PNG-writing test pass; --eval-speeds times one '
+                             'forward and writes nothing')
+            if args.data_parallel:
+                parser.error('--ensemble-flip / --ensemble-scales run every view on one device; --data-parallel spreads a '
+                             'training cycle over the ranks')
+            try:
+                from fosvos_hip.options import EnsembleOptions
+                args.ensemble = EnsembleOptions(flip=bool(args.ensemble_flip),
+                                                scales=(1.0,) if args.ensemble_scales is None else tuple(args.ensemble_scales))
+            except ValueError as err:
+                parser.error(str(err).replace('EnsembleOptions: ', '--ensemble-*: '))
     if is_online and args.device_decode and args.synthetic:
         parser.error('--device-decode decodes JPEG files: the synthetic sequence has none')
     args.is_training = not args.no_training

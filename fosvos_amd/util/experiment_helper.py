@@ -15,7 +15,10 @@ group; the device merges their answers into label maps, encodes palette PNG file
 (util/object_merge.py states the definitions).
 
 ``test_adaptive`` (``--adapt-steps N``) is the test pass with online adaptation: between a frame's two forward passes the net
-takes fine-tune steps against pseudo-labels made from its own output on the device (util/online_adapt.py states them)."""
+takes fine-tune steps against pseudo-labels made from its own output on the device (util/online_adapt.py states them).
+
+``test_fast`` and ``test_objects`` take ``ensemble=`` (``--ensemble-flip``, ``--ensemble-scales``): the net also sees every frame
+mirrored and at other sizes, and the device averages its answers back on the frame's grid (util/test_ensemble.py states it)."""
 import timeit
 from pathlib import Path
 from typing import Callable, Optional
@@ -246,6 +249,41 @@ def _forward_logits(net, inputs: torch.Tensor, forward_batch: int) -> torch.Tens
     return torch.cat([net.forward(inputs[k:k + forward_batch])[-1].detach().float() for k in range(0, n, forward_batch)])
 
 
+def _check_ensemble(who: str, ensemble) -> None:
+    if ensemble is not None:
+        from fosvos_hip.options import EnsembleOptions
+        if not isinstance(ensemble, EnsembleOptions):
+            raise ValueError('{}: ensemble must be a fosvos_hip.options.EnsembleOptions or None, got {!r}'.format(who, ensemble))
+
+
+def _ensemble_inputs(inputs: torch.Tensor, ensemble) -> list:
+    """The views of a group's frames, one tensor per view of ``ensemble.views()``: ONE ``ops.ensemble_views`` call on the
+    device (the unflipped view of the frame's size is ``inputs`` itself), ``test_ensemble.make_views`` for CPU tensors."""
+    if inputs.is_cuda:
+        from fosvos_hip import ops
+        return ops.ensemble_views(inputs, ensemble.views())
+    from util import test_ensemble
+    return [torch.from_numpy(v) for v in test_ensemble.make_views(inputs.numpy(), ensemble.views())]
+
+
+def _ensemble_logits(net, inputs: torch.Tensor, forward_batch: int, ensemble, views: Optional[list] = None) -> torch.Tensor:
+    """``_forward_logits`` behind a test-time ensemble (``ensemble``: an EnsembleOptions; None: ``_forward_logits`` itself,
+    nothing else is called).  The net forwards every view of the group in view order - ``views``: what ``_ensemble_inputs``
+    made, where several nets share it; None: made here - and ONE ``ops.ensemble_merge`` averages its V answers back on the
+    frame's grid (CPU tensors: ``test_ensemble.merge``).  No host synchronisation."""
+    if ensemble is None:
+        return _forward_logits(net, inputs, forward_batch)
+    if views is None:
+        views = _ensemble_inputs(inputs, ensemble)
+    maps = [_forward_logits(net, view, forward_batch) for view in views]
+    h, w = int(inputs.shape[2]), int(inputs.shape[3])
+    if maps[0].is_cuda:
+        from fosvos_hip import ops
+        return ops.ensemble_merge(maps, ensemble.views(), (h, w))
+    from util import test_ensemble
+    return torch.from_numpy(test_ensemble.merge([m.numpy() for m in maps], ensemble.views(), h, w))
+
+
 def _check_png_huffman(who: str, png_huffman: str) -> None:
     from util import png_layout
     if png_huffman not in png_layout.HUFFMAN_MODES:
@@ -320,7 +358,7 @@ def _frame_groups(data_loader, group: int):
 
 def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
               seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed', clean=None,
-              clean_seed: Optional[np.ndarray] = None) -> Optional[dict]:
+              clean_seed: Optional[np.ndarray] = None, ensemble=None) -> Optional[dict]:
     """The test pass with the PNG files made on the device.  Up to ``group`` consecutive frames of one shape are uploaded
     as one batch and forwarded ``forward_batch`` frames a call into one logit tensor.  Two frames a call is the largest
     batch whose frames the engine computes exactly as it computes a frame alone (a batch runs as two chains of ceil(N/2)
@@ -343,10 +381,16 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     CPU logits: ``mask_components.clean_sequence``).  With ``clean.temporal_radius`` the group is a chain: its first frame is
     gated by what the last frame of the group before kept - carried on the device - and the very first frame by
     ``clean_seed`` (uint8 or bool [H,W], non-zero = object; None: not gated).  The score dict then holds the options under
-    'clean'."""
+    'clean'.
+    ``ensemble`` (a ``fosvos_hip.options.EnsembleOptions``; None: nothing changes): the test-time ensemble.  ONE
+    ``ops.ensemble_views`` makes the group's mirrored and rescaled views, the net forwards them view by view
+    (``forward_batch`` frames a call, as above) and ONE ``ops.ensemble_merge`` averages the answers back on the frame's grid
+    (util/test_ensemble.py states both; CPU tensors take it).  Cleaning, counts and bytes work on the merged logits; no host
+    synchronisation is added.  The score dict and ``last_fast`` then hold the options under 'ensemble'."""
     from util import png_layout
     _check_png_huffman('test_fast', png_huffman)
     _check_batching('test_fast', group, forward_batch)
+    _check_ensemble('test_fast', ensemble)
     if clean is None and clean_seed is not None:
         raise ValueError('test_fast: clean_seed is the first seed of clean=CleanOptions(temporal_radius=...)')
     if clean is not None:
@@ -385,7 +429,7 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
             images = minibatches[0]['image'] if len(minibatches) == 1 else torch.cat([m['image'] for m in minibatches])
             inputs, = gpu_handler.cast_cuda_if_possible([images])
             n = int(inputs.shape[0])
-            logits = _forward_logits(net, inputs, forward_batch)
+            logits = _ensemble_logits(net, inputs, forward_batch, ensemble)
             h, w = int(logits.shape[2]), int(logits.shape[3])
             first, gt, paths = frames.add(minibatches, h, w, annotations)
             group_sizes.append(n)
@@ -447,6 +491,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     counts_host = counts.read(len(frames))
     time_for_all = timeit.default_timer() - time_all_start
     cleaned = {'clean': clean.as_dict()} if clean is not None else {}
+    if ensemble is not None:
+        cleaned['ensemble'] = ensemble.as_dict()
     last_fast.clear()
     last_fast.update(n_frames=len(frames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
                      seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],
@@ -661,7 +707,7 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
 
 def test_objects(net_providers, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
                  seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed',
-                 palette=None) -> Optional[dict]:
+                 palette=None, ensemble=None) -> Optional[dict]:
     """The test pass of a sequence with several objects: ``net_providers[k - 1]`` holds the net fine-tuned on object k
     against everything else.  ``test_fast``'s structure - groups of up to ``group`` frames uploaded once, ``forward_batch``
     frames a forward call, two buffer slots, ONE copy per group of files plus lengths, the host writing the previous group's
@@ -675,10 +721,15 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
     ``jf_counts_labels_numpy``).
     The score dict (kept in ``last_score``): 'seq_name', 'radius', 'fnames', 'scored', 'n_objects', 'objects' - per object
     {'object_id', 'counts', 'J', 'F', 'J_stats', 'F_stats'} as ``test_scored`` forms them -, 'J_stats' / 'F_stats' - each
-    statistic averaged over the objects -, 'J&F' and 'seconds'.  Toolkit parity unpinned, as for the single-object J / F."""
+    statistic averaged over the objects -, 'J&F' and 'seconds'.  Toolkit parity unpinned, as for the single-object J / F.
+    ``ensemble`` (an EnsembleOptions; None: nothing changes): the test-time ensemble of ``test_fast``.  The group's views are
+    made ONCE and shared among the K nets; each net forwards them in view order and has its V answers merged
+    (``ops.ensemble_merge``) before ``ops.merge_objects`` sees them.  The score dict then holds the options under
+    'ensemble'."""
     from util import object_merge, png_layout
     _check_png_huffman('test_objects', png_huffman)
     _check_batching('test_objects', group, forward_batch)
+    _check_ensemble('test_objects', ensemble)
     nets = [p.network for p in net_providers]
     n_obj = len(nets)
     if not 1 <= n_obj <= object_merge.MAX_OBJECTS:
@@ -696,7 +747,9 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
             images = minibatches[0]['image'] if len(minibatches) == 1 else torch.cat([m['image'] for m in minibatches])
             inputs, = gpu_handler.cast_cuda_if_possible([images])
             n = int(inputs.shape[0])
-            logits = [_forward_logits(net, inputs, forward_batch) for net in nets]  # every net forwards the same uploaded batch
+            views = None if ensemble is None else _ensemble_inputs(inputs, ensemble)  # made once, shared among the nets
+            # every net forwards the same uploaded batch
+            logits = [_ensemble_logits(net, inputs, forward_batch, ensemble, views) for net in nets]
             h, w = int(logits[0].shape[2]), int(logits[0].shape[3])
             first, gt, paths = frames.add(minibatches, h, w, annotations, ids=True)
             n_groups += 1
@@ -739,6 +792,8 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
     f_stats = object_merge.mean_statistics([o['F_stats'] for o in objects])
     score = {**frames.score_head(seq_name, radius), 'n_objects': n_obj, 'objects': objects, 'J_stats': j_stats,
              'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2, 'seconds': time_for_all}
+    if ensemble is not None:
+        score['ensemble'] = ensemble.as_dict()
     last_score.clear()
     last_score.update(score)
     return score

@@ -753,6 +753,32 @@ int fosvos_overlay_objects_scaled(const uint8_t *frames, const float *const *log
                                   int Wn, int mirror, int mode, const uint8_t *palette, double alpha, uint8_t *out, int device,
                                   void *stream);
 
+/* Test-time ensemble of the test pass (opt-in; csrc/ensemble.hip): the net sees the frame mirrored and at other sizes, and its
+ * answers are averaged back on the frame's grid.  util/test_ensemble.py states both entries in numpy; every output is
+ * compared with it bit for bit.  Resampling is bilinear at half-pixel centres with the integer taps of
+ * fosvos_overlay_scaled (util/frame_resample.taps, which also serve shrinking), every fp64 operation one IEEE operation of
+ * that file, in its order, uncontracted.  `views` is a host array of V entries, 1 <= V <= FOSVOS_ENSEMBLE_MAX_VIEWS, that
+ * travel by value in the kernel's arguments: data = device pointer fp32, h and w = the view's size, flip != 0 = mirrored
+ * along W.
+ *
+ * fosvos_ensemble_views: image fp32 [N,3,H,W] -> V views fp32 [N,3,h_k,w_k].  A view of the frame's size is a (mirrored)
+ *   copy, any other float32(v / (4 h_k w_k)) of the (mirrored) plane resampled in fp64.
+ * fosvos_ensemble_merge: V logit maps fp32 [N,1,h_k,w_k] -> out fp32 [N,1,H,W] = float32((u_0 + u_1 + ... ) / V), summed in
+ *   fp64 in the order of the views; u_k is the map itself where it has the frame's size and the map resampled to [H,W]
+ *   otherwise, mirrored back where the view was flipped.  `out` must not overlap a map.
+ *
+ * One launch each, no workspace, no atomics, no state; a thread takes four consecutive output pixels of a row and stores
+ * them as 16 bytes where they are aligned.  Every pointer 4-byte aligned.  Null pointer, V out of range: FOSVOS_E_ARG; a side
+ * outside 1..8192, N outside 1..65535, more than 2^31 - 1 groups of four pixels in a launch: FOSVOS_E_SHAPE. */
+#define FOSVOS_ENSEMBLE_MAX_VIEWS 8
+typedef struct fosvos_ensemble_view {
+    void *data;
+    int h, w, flip;
+} fosvos_ensemble_view;
+int fosvos_ensemble_views(const float *image, int N, int H, int W, const fosvos_ensemble_view *views, int V, int device,
+                          void *stream);
+int fosvos_ensemble_merge(const fosvos_ensemble_view *views, int V, int N, int H, int W, float *out, int device, void *stream);
+
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
  * Eval-mode BatchNorm is folded into the conv in front of it when the weights are packed:
