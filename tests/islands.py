@@ -7,6 +7,8 @@ islands of one call are carved out of ONE torch.uint8 allocation, so a stray acc
 memory the test owns.  An operand starts at a multiple of 256 bytes (plus ``offset`` where a case asks for the least alignment
 an entry point allows).  A map [N,H,W,C] gets margins of at least 17 rows plus one pixel of itself (the tallest tile is 16
 rows and a halo row) and never less than 64 KiB, rounded up to 256; vectors, weights, loss outputs and workspaces get 64 KiB.
+Every kind of operand takes an ``offset``, in-out operands and workspaces included.  A file of variable length (the PNG and
+JPEG encoders) lives in an in-out slot: the pre-fill behind the file is part of the expected bits.
 
 Three runs of every case, which differ only in what surrounds and pre-fills the operands:
   Z  margins of zero bytes; outputs and workspace pre-filled with 0x00.
@@ -82,13 +84,13 @@ def out(name, shape, dtype, is_map=None, offset=0):
     return Operand(name, "out", shape, dtype, None, len(shape) == 4 if is_map is None else is_map, offset)
 
 
-def inout(name, data, is_map=None):
-    return Operand(name, "inout", data.shape, data.dtype, data, data.dim() == 4 if is_map is None else is_map)
+def inout(name, data, is_map=None, offset=0):
+    return Operand(name, "inout", data.shape, data.dtype, data, data.dim() == 4 if is_map is None else is_map, offset)
 
 
-def workspace(name, nbytes, margin=None):
-    """margin: a larger margin than the flat one (an arena that holds maps)."""
-    o = Operand(name, "ws", (int(nbytes),), torch.uint8)
+def workspace(name, nbytes, margin=None, offset=0):
+    """margin: a larger margin than the flat one (an arena that holds maps); offset: the least alignment the entry accepts."""
+    o = Operand(name, "ws", (int(nbytes),), torch.uint8, offset=offset)
     if margin is not None:
         assert margin % ALIGN == 0 and margin >= FLAT_MARGIN
         o.margin = margin

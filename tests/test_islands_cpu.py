@@ -199,6 +199,55 @@ def test_island_geometry():
     assert torch.equal(a.arena, b.arena)  # seeded
 
 
+def _file_operands(prefill):
+    """A fake file encoder's operands (tests/test_gpu_io_islands.py): two slots of 40 bytes in an IN-OUT buffer that begins at
+    an odd address, the lengths, a workspace at the 4 bytes such an entry asks for."""
+    return [I.inp("bytes", torch.arange(24, dtype=torch.uint8).view(2, 12), offset=3), I.inout("out", prefill, offset=1),
+            I.out("lengths", (2,), torch.int32, offset=4), I.workspace("ws", 32, offset=4)]
+
+
+def _fake_encoder(isl, fault=None):
+    """File n = the frame's 12 bytes behind a 2-byte mark, in slot n; the bytes behind a file stay as they were."""
+    src, out, lengths = isl.view("bytes"), isl.view("out"), isl.view("lengths")
+    isl.arena[isl.start["ws"]:isl.end["ws"]] = 7
+    for n in range(2):
+        out[40 * n:40 * n + 2] = 0x4D
+        out[40 * n + 2:40 * n + 14] = src[n]
+        lengths[n] = 14
+    if fault == "ragged_tail":  # the last dword of a file copied whole: two bytes behind the file, inside its slot
+        out[14:16] = 0
+    if fault == "prefill_in_file":  # a file byte that depends on what the slot held
+        out[40 + 5] ^= out[40 + 20]
+
+
+def test_offsets_of_in_out_and_workspace_operands_and_a_store_behind_a_file():
+    """An in-out operand and a workspace take an ``offset`` like inputs and outputs do.  A file of variable length lives in
+    an in-out slot: its pre-fill is data, so a store behind the file but inside the slot - which no margin sees - is a
+    differing output element, under either pre-fill."""
+    g = torch.Generator().manual_seed(3)
+    for k in range(2):
+        prefill = torch.randint(0, 256, (80,), generator=g, dtype=torch.uint8)
+        ops_ = _file_operands(prefill)
+        for run_ in I.RUNS:
+            isl = I.Islands(ops_, run_, "cpu", seed=k)
+            for o in ops_:
+                assert (isl.arena.data_ptr() + isl.start[o.name]) % 256 == o.offset == {"bytes": 3, "out": 1, "lengths": 4, "ws": 4}[o.name]
+                assert isl.start[o.name] - isl.lo[o.name] >= o.margin and isl.hi[o.name] - isl.end[o.name] >= o.margin
+            assert torch.equal(isl.view("out"), prefill)  # the same data in every run
+        want = prefill.clone()
+        for n in range(2):
+            want[40 * n:40 * n + 2] = 0x4D
+            want[40 * n + 2:40 * n + 14] = torch.arange(12 * n, 12 * n + 12, dtype=torch.uint8)
+        expected = {"out": want, "lengths": torch.tensor([14, 14], dtype=torch.int32)}
+        assert int(prefill[14]) != 0 and int(prefill[60]) != 0
+        r = I.run_case("fake encoder", ops_, _fake_encoder, expected, device="cpu", seed=k)
+        assert r.ok(), r.lines()
+        _all_runs_say(I.run_case("ragged", ops_, lambda isl: _fake_encoder(isl, "ragged_tail"), expected, device="cpu", seed=k),
+                      "output out", "first at (14,)")
+        _all_runs_say(I.run_case("dep", ops_, lambda isl: _fake_encoder(isl, "prefill_in_file"), expected, device="cpu", seed=k),
+                      "output out", "1 / 80 elements differ", "first at (45,)")
+
+
 def test_loss_void_maps_leave_both_classes():
     """The loss cases of tests/test_gpu_islands.py: neither class is empty among the valid pixels of any frame, nor in the
     labels, and every frame has void pixels."""
