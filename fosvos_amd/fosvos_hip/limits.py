@@ -37,6 +37,14 @@ ROTATE_SCALE_RANGE = (1.0 / 16, 16.0)
 # the test-time ensemble (util/test_ensemble.py: MAX_VIEWS, SCALE_RANGE); a view's sides are within MAX_FRAME_SIDE
 ENSEMBLE_MAX_VIEWS = 8
 ENSEMBLE_SCALE_RANGE = (0.25, 4.0)
+# the CRF on the frame (util/mask_crf.py: MAX_ITERATIONS, MAX_RADIUS, THETA_*_RANGE, MAX_WEIGHT, MAX_CLIP)
+CRF_MAX_ITERATIONS = 10
+CRF_MAX_RADIUS = 5
+CRF_THETA_POS_RANGE = (0.25, 1e3)
+CRF_THETA_RGB_RANGE = (1.0, 1e3)
+CRF_THETA_SMOOTH_RANGE = (0.25, 1e3)
+CRF_MAX_WEIGHT = 100.0
+CRF_MAX_CLIP = 1e4
 
 
 def real_number(v) -> bool:

@@ -1596,6 +1596,60 @@ def ensemble_merge(logits: Sequence[torch.Tensor], views, size: Tuple[int, int],
     return out
 
 
+# ------------------------------------------------------------------------------------------ the CRF on the frame (crf.hip)
+CRF_MAX_RADIUS = limits.CRF_MAX_RADIUS          # util/mask_crf.MAX_RADIUS
+CRF_MAX_ITERATIONS = limits.CRF_MAX_ITERATIONS  # util/mask_crf.MAX_ITERATIONS
+_CRF_TABLES = {}  # (CrfOptions, device index) -> the fp64 table vector on that device
+
+
+def _crf_tables(options, device: torch.device) -> torch.Tensor:
+    """``mask_crf.tables(options)`` on ``device``, made and uploaded at the first call with these options (the one moment a
+    ``crf_refine`` call waits for the host copy) and kept."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (options, idx)
+    tab = _CRF_TABLES.get(key)
+    if tab is None:
+        from util import mask_crf
+        tab = _CRF_TABLES[key] = torch.from_numpy(mask_crf.tables(options)).to(device)
+    return tab
+
+
+def crf_refine(image: torch.Tensor, logits: torch.Tensor, options=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_crf_refine: the net's input fp32 [N,3,H,W] (the frame minus MEANVAL) and logits fp32 [N,1,H,W] -> fp32 [N,1,H,W],
+    the logits after ``options.iterations`` mean-field iterations of the local CRF whose guide is the frame's bytes
+    (``mask_crf.refine(image[k], logits[k, 0], options)`` of every frame, bit for bit).  ``options``: a
+    ``fosvos_hip.options.CrfOptions`` (None: its defaults).  ``out`` must not overlap the image or the logits.  The table
+    vector (``mask_crf.tables(options)``) is kept on the device per (options, device).  ``options.iterations`` launches on the
+    current stream, no synchronisation; z^t lives in the stream's workspace."""
+    from .options import CrfOptions
+    what = "crf_refine"
+    if options is None:
+        options = CrfOptions()
+    if not isinstance(options, CrfOptions):
+        raise ValueError(f"{what}: options must be a fosvos_hip.options.CrfOptions or None, got {options!r}")
+    _need(image, _F32, f"{what} image", ValueError)
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0:
+        raise ValueError(f"{what}: image must be a non-empty [N,3,H,W], got {tuple(image.shape)}")
+    n, h, w = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
+    if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
+        raise ValueError(f"{what}: maps may have sides of up to {MAX_FRAME_SIDE}, got {(h, w)}")
+    _need(logits, _F32, f"{what} logits", ValueError)
+    if tuple(logits.shape) != (n, 1, h, w):
+        raise ValueError(f"{what}: logits must be {(n, 1, h, w)}, got {tuple(logits.shape)}")
+    _same_device(what, image, logits)
+    given = out
+    out = _out_like(out, (n, 1, h, w), _F32, image, what)
+    if given is not None and (_overlap(out, image) or _overlap(out, logits)):
+        raise ValueError(f"{what}: out must not overlap the image or the logits")
+    tab = _crf_tables(options, image.device)
+    ws, wsn = _WS.get(int(lib().fosvos_crf_refine_workspace_bytes(n, h, w)), image.device)
+    window = (2 * options.radius + 1) ** 2 - 1
+    _launch(what, image, image.data_ptr(), logits.data_ptr(), tab.data_ptr(), n, h, w, options.iterations, options.radius,
+            float(options.weight_appearance), float(options.weight_smooth), float(options.clip), _mean_bgr(), out.data_ptr(), ws,
+            wsn, flops=9.0 * window * options.iterations * n * h * w, nbytes=(16.0 * options.iterations + 4.0) * n * h * w)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ JPEG files (jpeg.hip)
 JPEG_SUBSAMPLINGS = limits.JPEG_SUBSAMPLINGS
 

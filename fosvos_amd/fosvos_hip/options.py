@@ -4,8 +4,8 @@ takes an options object.  The defaults are the measured best; every switch selec
 The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleaning) is opt-in by being
 passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
 and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3),
-RotateOptions (rotating and zooming the training sample) and EnsembleOptions (the test-time ensemble of the
-test pass).
+RotateOptions (rotating and zooming the training sample), EnsembleOptions (the test-time ensemble of the
+test pass) and CrfOptions (the CRF on the frame behind the test pass).
 
 No torch and no library load here: importable anywhere.  The ranges and the scalar checks are ``limits``'.
 """
@@ -340,6 +340,46 @@ class EnsembleOptions:
 
     def as_dict(self) -> dict:
         return {'flip': self.flip, 'scales': [float(s) for s in self.scales]}
+
+
+@dataclass(frozen=True)
+class CrfOptions:
+    """Refining the test pass's logits with a local CRF on the frame's colours (``test_fast(crf=)`` and ``test_objects(crf=)``,
+    ``ops.crf_refine``; util/mask_crf.py states the rules): mean-field inference over a window of the
+    frame with an appearance and a smoothness kernel.  Opt-in by being passed; this class reads no environment variable.  The
+    defaults are DenseCRF-like and are unmeasured on trained nets."""
+
+    # mean-field iterations, one launch each: 1..10
+    iterations: int = 5
+    # the window reaches this many pixels to every side: 1..5
+    radius: int = 5
+    # the appearance kernel's width in pixels: a finite number in [0.25, 1e3]
+    theta_pos: float = 8.0
+    # ... and in grey levels of one channel: [1, 1e3].  Smaller: only pixels of nearly the same colour vote
+    theta_rgb: float = 13.0
+    # the smoothness kernel's width in pixels: [0.25, 1e3]
+    theta_smooth: float = 3.0
+    # what the two kernels' (normalised) messages weigh beside the clipped logit: [0, 100] each
+    weight_appearance: float = 4.0
+    weight_smooth: float = 3.0
+    # the logits are clipped to [-clip, clip] first, so that the picture can outvote a confident net: (0, 1e4]
+    clip: float = 6.0
+
+    def __post_init__(self) -> None:
+        limits.check_int("CrfOptions", "iterations", self.iterations, 1, limits.CRF_MAX_ITERATIONS)
+        limits.check_int("CrfOptions", "radius", self.radius, 1, limits.CRF_MAX_RADIUS)
+        limits.check_real("CrfOptions", "theta_pos", self.theta_pos, *limits.CRF_THETA_POS_RANGE)
+        limits.check_real("CrfOptions", "theta_rgb", self.theta_rgb, *limits.CRF_THETA_RGB_RANGE)
+        limits.check_real("CrfOptions", "theta_smooth", self.theta_smooth, *limits.CRF_THETA_SMOOTH_RANGE)
+        limits.check_real("CrfOptions", "weight_appearance", self.weight_appearance, 0.0, limits.CRF_MAX_WEIGHT)
+        limits.check_real("CrfOptions", "weight_smooth", self.weight_smooth, 0.0, limits.CRF_MAX_WEIGHT)
+        limits.check_real("CrfOptions", "clip", self.clip, 0.0, limits.CRF_MAX_CLIP, lo_open=True)
+
+    def as_dict(self) -> dict:
+        return {'iterations': self.iterations, 'radius': self.radius, 'theta_pos': float(self.theta_pos),
+                'theta_rgb': float(self.theta_rgb), 'theta_smooth': float(self.theta_smooth),
+                'weight_appearance': float(self.weight_appearance), 'weight_smooth': float(self.weight_smooth),
+                'clip': float(self.clip)}
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

@@ -50,6 +50,7 @@ clean = None                # --clean-min-area / --clean-largest / --clean-tempo
 rotate = None               # --augment-rotate (and its options): a RotateOptions; the one-shot loaders rotate and zoom the sample
 adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
 ensemble = None             # --ensemble-flip / --ensemble-scales (with --fast-test or --multi-object): an EnsembleOptions
+crf = None                  # --crf (and --crf-*; with --fast-test or --multi-object): a CrfOptions
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
 
@@ -167,6 +168,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                     cleaning['clean_seed'] = _clean_seed(train_seed, annotations, data_loader, seq_name)
             if ensemble is not None:  # (absent: the call is what it was)
                 cleaning['ensemble'] = ensemble
+            if crf is not None:  # (absent: the call is what it was)
+                cleaning['crf'] = crf
             result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name,
                                                  png_huffman='fitted' if png_fitted else 'fixed', **cleaning)
             _report_score(result, save_dir, seq_name)
@@ -238,7 +241,8 @@ def train_and_test_objects(make_provider, seq_name: str, settings: OnlineSetting
                                      settings.variant_online)
     result = experiment_helper.test_objects(providers, test_loader, save_dir, annotations if score else None,
                                             seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed',
-                                            **({} if ensemble is None else {'ensemble': ensemble}))
+                                            **({} if ensemble is None else {'ensemble': ensemble}),
+                                            **({} if crf is None else {'crf': crf}))
     _report_score(result, save_dir, seq_name)
     return result
 
@@ -595,7 +599,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean, adapt, rotate, ensemble
+    global multi_object, synthetic_objects, clean, adapt, rotate, ensemble, crf
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -614,6 +618,7 @@ def main(argv=None):
     adapt = args.adapt
     rotate = args.rotate
     ensemble = args.ensemble
+    crf = args.crf_options
     synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':

@@ -6,7 +6,7 @@ reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/
 --data-parallel, --augment-rotate with --rotate-range / --zoom-range / --rotate-renormalize, --resident-train-set and
 --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
 --multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal, --adapt-steps with its --adapt-* options,
---ensemble-flip and --ensemble-scales (online only).
+--ensemble-flip and --ensemble-scales, --crf with its --crf-* options (online only).
 """
 import argparse
 from typing import List, Optional
@@ -125,6 +125,26 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                             help='with --fast-test or --multi-object: test-time ensemble - the net sees every frame at these '
                                  'sizes (distinct factors in [0.25, 4], e.g. 0.75 1 1.25), and the logits are averaged on '
                                  'the frame\'s grid on the device; at most 8 views with --ensemble-flip counted in')
+        parser.add_argument('--crf', action='store_true',
+                            help='with --fast-test or --multi-object: refine the logits with a local CRF on the frame\'s '
+                                 'colours on the device (mean-field over a window; util/mask_crf.py), before cleaning, merging, '
+                                 'scoring and the PNG files')
+        parser.add_argument('--crf-iterations', type=int, default=None, metavar='N',
+                            help='with --crf: mean-field iterations (1..10; default 5)')
+        parser.add_argument('--crf-radius', type=int, default=None, metavar='R',
+                            help='with --crf: the window reaches R pixels to every side (1..5; default 5)')
+        parser.add_argument('--crf-theta-pos', type=float, default=None, metavar='F',
+                            help='with --crf: width of the appearance kernel in pixels ([0.25, 1000]; default 8)')
+        parser.add_argument('--crf-theta-rgb', type=float, default=None, metavar='F',
+                            help='with --crf: width of the appearance kernel in grey levels ([1, 1000]; default 13)')
+        parser.add_argument('--crf-theta-smooth', type=float, default=None, metavar='F',
+                            help='with --crf: width of the smoothness kernel in pixels ([0.25, 1000]; default 3)')
+        parser.add_argument('--crf-weight-appearance', type=float, default=None, metavar='F',
+                            help='with --crf: weight of the appearance kernel\'s message ([0, 100]; default 4)')
+        parser.add_argument('--crf-weight-smooth', type=float, default=None, metavar='F',
+                            help='with --crf: weight of the smoothness kernel\'s message ([0, 100]; default 3)')
+        parser.add_argument('--crf-clip', type=float, default=None, metavar='F',
+                            help='with --crf: the logits are clipped to [-F, F] first ((0, 10000]; default 6)')
         parser.add_argument('--objects', default=2, type=int, metavar='K',
                             help='with --multi-object --synthetic: the number of objects of the synthetic sequence (1..16)')
     if not is_online:
@@ -225,6 +245,31 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                                                 scales=(1.0,) if args.ensemble_scales is None else tuple(args.ensemble_scales))
             except ValueError as err:
                 parser.error(str(err).replace('EnsembleOptions: ', '--ensemble-*: '))
+    if is_online:
+        args.crf_options = None
+        fields = {'iterations': args.crf_iterations, 'radius': args.crf_radius, 'theta_pos': args.crf_theta_pos,
+                  'theta_rgb': args.crf_theta_rgb, 'theta_smooth': args.crf_theta_smooth,
+                  'weight_appearance': args.crf_weight_appearance, 'weight_smooth': args.crf_weight_smooth,
+                  'clip': args.crf_clip}
+        given = ['--crf-' + name.replace('_', '-') for name, v in fields.items() if v is not None]
+        if given and not args.crf:
+            parser.error('{} set(s) an option of the CRF: it needs --crf'.format(' / '.join(given)))
+        if args.crf:
+            if not args.fast_test and not args.multi_object:
+                parser.error('--crf refines the logits of the device test pass: it needs --fast-test or --multi-object')
+            if args.adapt_steps is not None:
+                parser.error('--crf refines the answers of a frozen net; a CRF in the adaptive test pass (--adapt-steps) is '
+                             'not built')
+            if args.eval_speeds:
+                parser.error('--crf belongs to a PNG-writing test pass; --eval-speeds times one forward and writes nothing')
+            if args.data_parallel:
+                parser.error('--crf runs in the test pass on one device; --data-parallel spreads a training cycle over the '
+                             'ranks')
+            try:
+                from fosvos_hip.options import CrfOptions
+                args.crf_options = CrfOptions(**{name: v for name, v in fields.items() if v is not None})
+            except ValueError as err:
+                parser.error(str(err).replace('CrfOptions: ', '--crf-*: '))
     if is_online and args.device_decode and args.synthetic:
         parser.error('--device-decode decodes JPEG files: the synthetic sequence has none')
     args.is_training = not args.no_training

@@ -18,7 +18,9 @@ group; the device merges their answers into label maps, encodes palette PNG file
 takes fine-tune steps against pseudo-labels made from its own output on the device (util/online_adapt.py states them).
 
 ``test_fast`` and ``test_objects`` take ``ensemble=`` (``--ensemble-flip``, ``--ensemble-scales``): the net also sees every frame
-mirrored and at other sizes, and the device averages its answers back on the frame's grid (util/test_ensemble.py states it)."""
+mirrored and at other sizes, and the device averages its answers back on the frame's grid (util/test_ensemble.py states it).
+They also take ``crf=`` (``--crf``): a local CRF on the frame's colours refines the logits on the device before anything else
+reads them (util/mask_crf.py states it)."""
 import timeit
 from pathlib import Path
 from typing import Callable, Optional
@@ -284,6 +286,23 @@ def _ensemble_logits(net, inputs: torch.Tensor, forward_batch: int, ensemble, vi
     return torch.from_numpy(test_ensemble.merge([m.numpy() for m in maps], ensemble.views(), h, w))
 
 
+def _check_crf(who: str, crf) -> None:
+    if crf is not None:
+        from fosvos_hip.options import CrfOptions
+        if not isinstance(crf, CrfOptions):
+            raise ValueError('{}: crf must be a fosvos_hip.options.CrfOptions or None, got {!r}'.format(who, crf))
+
+
+def _crf_logits(inputs: torch.Tensor, logits: torch.Tensor, crf) -> torch.Tensor:
+    """A group's logits fp32 [n,1,H,W] refined by the CRF on the group's uploaded frames ``inputs`` (``crf``: a CrfOptions): ONE
+    ``ops.crf_refine`` on the device, ``mask_crf.refine`` frame by frame for CPU tensors.  No host synchronisation."""
+    if logits.is_cuda:
+        from fosvos_hip import ops
+        return ops.crf_refine(inputs.float().contiguous(), logits, crf)
+    from util import mask_crf
+    return torch.from_numpy(mask_crf.refine_batch(inputs.float().contiguous().numpy(), logits.numpy(), crf))
+
+
 def _check_png_huffman(who: str, png_huffman: str) -> None:
     from util import png_layout
     if png_huffman not in png_layout.HUFFMAN_MODES:
@@ -358,7 +377,7 @@ def _frame_groups(data_loader, group: int):
 
 def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
               seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed', clean=None,
-              clean_seed: Optional[np.ndarray] = None, ensemble=None) -> Optional[dict]:
+              clean_seed: Optional[np.ndarray] = None, ensemble=None, crf=None) -> Optional[dict]:
     """The test pass with the PNG files made on the device.  Up to ``group`` consecutive frames of one shape are uploaded
     as one batch and forwarded ``forward_batch`` frames a call into one logit tensor.  Two frames a call is the largest
     batch whose frames the engine computes exactly as it computes a frame alone (a batch runs as two chains of ceil(N/2)
@@ -386,11 +405,16 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     ``ops.ensemble_views`` makes the group's mirrored and rescaled views, the net forwards them view by view
     (``forward_batch`` frames a call, as above) and ONE ``ops.ensemble_merge`` averages the answers back on the frame's grid
     (util/test_ensemble.py states both; CPU tensors take it).  Cleaning, counts and bytes work on the merged logits; no host
-    synchronisation is added.  The score dict and ``last_fast`` then hold the options under 'ensemble'."""
+    synchronisation is added.  The score dict and ``last_fast`` then hold the options under 'ensemble'.
+    ``crf`` (a ``fosvos_hip.options.CrfOptions``; None: nothing changes): each group's logits - the merged ones behind an
+    ensemble - go through ONE ``ops.crf_refine`` whose guide is the group's uploaded frames, before the cleaning, the counts
+    and the bytes (util/mask_crf.py states it; CPU tensors: ``mask_crf.refine``).  No host synchronisation is added.  The
+    score dict and ``last_fast`` then hold the options under 'crf'."""
     from util import png_layout
     _check_png_huffman('test_fast', png_huffman)
     _check_batching('test_fast', group, forward_batch)
     _check_ensemble('test_fast', ensemble)
+    _check_crf('test_fast', crf)
     if clean is None and clean_seed is not None:
         raise ValueError('test_fast: clean_seed is the first seed of clean=CleanOptions(temporal_radius=...)')
     if clean is not None:
@@ -430,6 +454,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
             inputs, = gpu_handler.cast_cuda_if_possible([images])
             n = int(inputs.shape[0])
             logits = _ensemble_logits(net, inputs, forward_batch, ensemble)
+            if crf is not None:
+                logits = _crf_logits(inputs, logits, crf)
             h, w = int(logits.shape[2]), int(logits.shape[3])
             first, gt, paths = frames.add(minibatches, h, w, annotations)
             group_sizes.append(n)
@@ -493,6 +519,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     cleaned = {'clean': clean.as_dict()} if clean is not None else {}
     if ensemble is not None:
         cleaned['ensemble'] = ensemble.as_dict()
+    if crf is not None:
+        cleaned['crf'] = crf.as_dict()
     last_fast.clear()
     last_fast.update(n_frames=len(frames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
                      seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],
@@ -707,7 +735,7 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
 
 def test_objects(net_providers, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
                  seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed',
-                 palette=None, ensemble=None) -> Optional[dict]:
+                 palette=None, ensemble=None, crf=None) -> Optional[dict]:
     """The test pass of a sequence with several objects: ``net_providers[k - 1]`` holds the net fine-tuned on object k
     against everything else.  ``test_fast``'s structure - groups of up to ``group`` frames uploaded once, ``forward_batch``
     frames a forward call, two buffer slots, ONE copy per group of files plus lengths, the host writing the previous group's
@@ -725,11 +753,15 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
     ``ensemble`` (an EnsembleOptions; None: nothing changes): the test-time ensemble of ``test_fast``.  The group's views are
     made ONCE and shared among the K nets; each net forwards them in view order and has its V answers merged
     (``ops.ensemble_merge``) before ``ops.merge_objects`` sees them.  The score dict then holds the options under
-    'ensemble'."""
+    'ensemble'.
+    ``crf`` (a CrfOptions; None: nothing changes): the CRF of ``test_fast``, per net: each net's logits - merged behind an
+    ensemble - go through ONE ``ops.crf_refine`` on the group's uploaded frames before ``ops.merge_objects`` sees them (a joint
+    CRF over the K labels is not built).  The score dict then holds the options under 'crf'."""
     from util import object_merge, png_layout
     _check_png_huffman('test_objects', png_huffman)
     _check_batching('test_objects', group, forward_batch)
     _check_ensemble('test_objects', ensemble)
+    _check_crf('test_objects', crf)
     nets = [p.network for p in net_providers]
     n_obj = len(nets)
     if not 1 <= n_obj <= object_merge.MAX_OBJECTS:
@@ -750,6 +782,8 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
             views = None if ensemble is None else _ensemble_inputs(inputs, ensemble)  # made once, shared among the nets
             # every net forwards the same uploaded batch
             logits = [_ensemble_logits(net, inputs, forward_batch, ensemble, views) for net in nets]
+            if crf is not None:
+                logits = [_crf_logits(inputs, x, crf) for x in logits]
             h, w = int(logits[0].shape[2]), int(logits[0].shape[3])
             first, gt, paths = frames.add(minibatches, h, w, annotations, ids=True)
             n_groups += 1
@@ -794,6 +828,8 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
              'F_stats': f_stats, 'J&F': (j_stats['mean'] + f_stats['mean']) / 2, 'seconds': time_for_all}
     if ensemble is not None:
         score['ensemble'] = ensemble.as_dict()
+    if crf is not None:
+        score['crf'] = crf.as_dict()
     last_score.clear()
     last_score.update(score)
     return score

@@ -779,6 +779,27 @@ int fosvos_ensemble_views(const float *image, int N, int H, int W, const fosvos_
                           void *stream);
 int fosvos_ensemble_merge(const fosvos_ensemble_view *views, int V, int N, int H, int W, float *out, int device, void *stream);
 
+/* Refining the test pass's logits with a local CRF on the frame's colours (opt-in; csrc/crf.hip): mean-field inference over a
+ * window of radius `radius` with an appearance kernel (near and alike in colour) and a smoothness kernel (near).
+ * util/mask_crf.py states the arithmetic in numpy; `out` is compared with it bit for bit.  Every fp64 operation is one IEEE
+ * operation of that file, in its order, uncontracted, and there is no transcendental: `tables` is the device copy of the fp64
+ * vector mask_crf.tables made, [RGB 256 | A (2 radius + 1)^2 | B (2 radius + 1)^2 | D 2049] - the entry cannot see its length;
+ * what it holds is only ever a value, never an index.
+ *
+ * fosvos_crf_refine: image fp32 [N,3,H,W] (the net's input: the frame minus `mean`, whose bytes the kernel takes back as the
+ *   guide; a NaN is level 0) and logits fp32 [N,1,H,W] -> out fp32 [N,1,H,W] = float32(z^T); the unary is the logit clipped
+ *   to [-clip, clip] (a NaN is -clip), z^t = (u + weight_appearance ma) + weight_smooth ms with ma and ms the two kernels'
+ *   normalised messages of the beliefs of z^{t-1} (0.0 where a pixel's kernel mass is not positive).  `out` must not overlap
+ *   an input.  1 <= iterations <= 10, 1 <= radius <= 5, weights in [0, 100], 0 < clip <= 1e4 (FOSVOS_E_ARG); sides of
+ *   1..8192 (FOSVOS_E_SHAPE); image, logits and out 4-byte, tables and workspace 8-byte aligned.  workspace:
+ *   fosvos_crf_refine_workspace_bytes (two fp64 maps [N,H,W], z^t by turns); every byte of it that is read was written by
+ *   the call.  `iterations` launches of one kernel, 16 x 64 tiles with a halo of `radius` in 27 KB of LDS; the last writes
+ *   `out`.  No workgroup waits for another, no atomics, no synchronisation. */
+size_t fosvos_crf_refine_workspace_bytes(int N, int H, int W);
+int fosvos_crf_refine(const float *image, const float *logits, const double *tables, int N, int H, int W, int iterations,
+                      int radius, double weight_appearance, double weight_smooth, double clip, const float mean[3], float *out,
+                      void *workspace, size_t workspace_bytes, int device, void *stream);
+
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
  * Eval-mode BatchNorm is folded into the conv in front of it when the weights are packed:
