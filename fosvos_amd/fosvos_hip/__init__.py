@@ -284,6 +284,10 @@ SIGNATURES = {
     "fosvos_crf_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, POINTER(c_float), c_void_p, c_void_p, c_size_t, c_int,
                                   c_void_p]),
+    "fosvos_motion_luma": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "fosvos_motion_estimate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                       c_void_p]),
+    "fosvos_motion_warp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fosvos_vgg_backward": (c_int, [c_void_p, POINTER(VggWeights), POINTER(VggGrads), c_void_p, c_int, c_int, c_int, c_void_p,
                                     c_size_t, c_void_p, POINTER(c_void_p), c_void_p, c_void_p]),
     # compact stage 1 (the pool's winner codes in place of conv1_2's dense output)

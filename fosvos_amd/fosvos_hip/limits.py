@@ -45,6 +45,10 @@ CRF_THETA_RGB_RANGE = (1.0, 1e3)
 CRF_THETA_SMOOTH_RANGE = (0.25, 1e3)
 CRF_MAX_WEIGHT = 100.0
 CRF_MAX_CLIP = 1e4
+# block matching (util/block_motion.py: BLOCKS, MAX_SEARCH, MAX_ZERO_BIAS)
+MOTION_BLOCKS = (8, 16)
+MOTION_MAX_SEARCH = 16
+MOTION_MAX_ZERO_BIAS = 255
 
 
 def real_number(v) -> bool:

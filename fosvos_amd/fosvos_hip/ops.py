@@ -1650,6 +1650,82 @@ def crf_refine(image: torch.Tensor, logits: torch.Tensor, options=None, out: Opt
     return out
 
 
+# ------------------------------------------------------------------------------------------ block matching (motion.hip)
+MOTION_BLOCKS = limits.MOTION_BLOCKS          # util/block_motion.BLOCKS
+MOTION_MAX_SEARCH = limits.MOTION_MAX_SEARCH  # util/block_motion.MAX_SEARCH
+
+
+def _motion_grid(h: int, w: int, block: int) -> Tuple[int, int]:
+    return -(-h // block), -(-w // block)
+
+
+def motion_luma(image: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_motion_luma: the net's input fp32 [N,3,H,W] (the frame minus MEANVAL) -> uint8 [N,H,W], the luma of the frame's
+    bytes (``block_motion.luma``, bit for bit; a NaN is level 0).  One launch on the current stream, no synchronisation."""
+    what = "motion_luma"
+    _need(image, _F32, f"{what} image", ValueError)
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0:
+        raise ValueError(f"{what}: image must be a non-empty [N,3,H,W], got {tuple(image.shape)}")
+    n, h, w = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
+    if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
+        raise ValueError(f"{what}: frames may have sides of up to {MAX_FRAME_SIDE}, got {(h, w)}")
+    out = _out_like(out, (n, h, w), torch.uint8, image, what)
+    _launch(what, image, image.data_ptr(), _mean_bgr(), n, h, w, out.data_ptr(), nbytes=13.0 * n * h * w)
+    return out
+
+
+def motion_estimate(prev_y: torch.Tensor, cur_y: torch.Tensor, options=None, field: Optional[torch.Tensor] = None,
+                    cost: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fosvos_motion_estimate: luma planes uint8 [N,H,W] of the frames before and the current frames -> (field int8
+    [N,Hb,Wb,2], cost int32 [N,Hb,Wb]): for every ``options.block``-sized block of every pair the vector ``(dy, dx)`` within
+    ``options.search`` with ``cur[p] ~ prev[p + (dy, dx)]`` and its sum of absolute differences (``block_motion.estimate``,
+    bit for bit).  ``options``: a ``fosvos_hip.options.MotionOptions`` (None: its defaults).  The two planes may be views of one
+    buffer one frame apart.  ONE launch for all N pairs on the current stream, no synchronisation."""
+    from .options import MotionOptions
+    what = "motion_estimate"
+    if options is None:
+        options = MotionOptions()
+    if not isinstance(options, MotionOptions):
+        raise ValueError(f"{what}: options must be a fosvos_hip.options.MotionOptions or None, got {options!r}")
+    n, h, w = _map_shape(prev_y, what, "prev_y")
+    _need(cur_y, torch.uint8, f"{what} cur_y", ValueError)
+    if tuple(cur_y.shape) != (n, h, w):
+        raise ValueError(f"{what}: cur_y must be {(n, h, w)}, got {tuple(cur_y.shape)}")
+    if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
+        raise ValueError(f"{what}: planes may have sides of up to {MAX_FRAME_SIDE}, got {(h, w)}")
+    _same_device(what, prev_y, cur_y)
+    hb, wb = _motion_grid(h, w, options.block)
+    field = _out_like(field, (n, hb, wb, 2), torch.int8, prev_y, what, "field")
+    cost = _out_like(cost, (n, hb, wb), torch.int32, prev_y, what, "cost")
+    cands = (2 * options.search + 1) ** 2
+    _launch(what, prev_y, prev_y.data_ptr(), cur_y.data_ptr(), n, h, w, options.block, options.search, options.zero_bias,
+            field.data_ptr(), cost.data_ptr(), flops=2.0 * cands * n * h * w, nbytes=2.0 * n * h * w)
+    return field, cost
+
+
+def motion_warp(mask: torch.Tensor, field: torch.Tensor, block: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_motion_warp: mask uint8 [N,H,W] (non-zero = set) and field int8 [N,Hb,Wb,2] -> uint8 [N,H,W] of 0 and 1:
+    ``out[y, x] = mask[y + dy, x + dx] != 0`` with the vector of the pixel's block, 0 where the source lies outside the frame
+    (``block_motion.warp``, bit for bit; the field may hold any values).  ``out`` must not overlap the mask.  One launch on
+    the current stream, no synchronisation."""
+    what = "motion_warp"
+    n, h, w = _map_shape(mask, what, "mask")
+    if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
+        raise ValueError(f"{what}: masks may have sides of up to {MAX_FRAME_SIDE}, got {(h, w)}")
+    limits.check_member(what, "block", block, MOTION_BLOCKS)
+    _need(field, torch.int8, f"{what} field", ValueError)
+    want = (n,) + _motion_grid(h, w, block) + (2,)
+    if tuple(field.shape) != want:
+        raise ValueError(f"{what}: field must be {want}, got {tuple(field.shape)}")
+    _same_device(what, mask, field)
+    given = out
+    out = _out_like(out, (n, h, w), torch.uint8, mask, what)
+    if given is not None and _overlap(out, mask):
+        raise ValueError(f"{what}: out must not overlap the mask")
+    _launch(what, mask, mask.data_ptr(), field.data_ptr(), n, h, w, int(block), out.data_ptr(), nbytes=2.0 * n * h * w)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ JPEG files (jpeg.hip)
 JPEG_SUBSAMPLINGS = limits.JPEG_SUBSAMPLINGS
 

@@ -5,7 +5,8 @@ The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleani
 passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
 and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3),
 RotateOptions (rotating and zooming the training sample), EnsembleOptions (the test-time ensemble of the
-test pass) and CrfOptions (the CRF on the frame behind the test pass).
+test pass), CrfOptions (the CRF on the frame behind the test pass) and MotionOptions
+(the temporal gate's seed carried along the picture's motion).
 
 No torch and no library load here: importable anywhere.  The ranges and the scalar checks are ``limits``'.
 """
@@ -380,6 +381,32 @@ class CrfOptions:
                 'theta_rgb': float(self.theta_rgb), 'theta_smooth': float(self.theta_smooth),
                 'weight_appearance': float(self.weight_appearance), 'weight_smooth': float(self.weight_smooth),
                 'clip': float(self.clip)}
+
+
+@dataclass(frozen=True)
+class MotionOptions:
+    """Carrying the temporal gate's seed along the picture's motion (``test_fast(clean=, motion=)``,
+    ``FrameSegmenter(clean=, motion=)``, ``ops.motion_estimate``; util/block_motion.py states the rules):
+    full-search block matching on the frames' luma, and the kept mask of the frame before warped block by block.  It needs
+    ``CleanOptions.temporal_radius``.  Opt-in by being passed; this class reads no environment variable.  The defaults are the
+    design's and are unmeasured on real sequences."""
+
+    # the side of a block in pixels: 8 or 16
+    block: int = 16
+    # a block is looked for up to this many pixels away in every direction: 1..16
+    search: int = 8
+    # what a non-zero vector must win by, in sixteenths of a grey level a pixel: 0..255.  Holds flat blocks still
+    zero_bias: int = 8
+
+    def __post_init__(self) -> None:
+        limits.check_int("MotionOptions", "block", self.block, min(limits.MOTION_BLOCKS), max(limits.MOTION_BLOCKS),
+                         expect=f"one of {limits.MOTION_BLOCKS}")
+        limits.check_member("MotionOptions", "block", self.block, limits.MOTION_BLOCKS)
+        limits.check_int("MotionOptions", "search", self.search, 1, limits.MOTION_MAX_SEARCH)
+        limits.check_int("MotionOptions", "zero_bias", self.zero_bias, 0, limits.MOTION_MAX_ZERO_BIAS)
+
+    def as_dict(self) -> dict:
+        return {'block': self.block, 'search': self.search, 'zero_bias': self.zero_bias}
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

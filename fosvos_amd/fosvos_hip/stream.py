@@ -42,6 +42,14 @@ With ``net_size`` it runs at the net's size, the radius in net pixels.  The temp
 segmenter's seed: the kept mask of the last frame computed, written by that frame's call and read by the next one's;
 ``seed(mask)`` sets it by hand.  ``None`` is the object described above.
 
+``motion=MotionOptions(...)`` (opt-in, with ``clean.temporal_radius``; ``fosvos_hip.options``) makes that gate follow the
+picture: per frame ONE ``ops.motion_luma`` of the image the net saw (with ``net_size`` the net's map, where the seed lives) and -
+once a frame before exists - ONE ``ops.motion_estimate`` against its luma plane and ONE ``ops.motion_warp`` of the seed into a
+second buffer, which the clean call reads in place of the seed (csrc/motion.hip; util/block_motion.py states all three, and its
+``track`` the whole chain).  Two luma planes, the field, the cost and the warped seed are allocated once; which plane is the
+previous one is host state that changes in submit order, as the launches do.  ``seed(mask)`` drops the previous plane: a
+hand-set seed belongs to the next submitted frame and is used unwarped.  ``None`` is the object described above.
+
 ``ObjectSegmenter`` (opt-in) is the same object for several objects a frame: K per-object nets run on the slot's one image and
 ONE ``ops.overlay_objects`` merges their logits and paints the palette overlay (csrc/stream.hip; util/object_overlay.py
 states the bytes).  Its label-map form can end in a palette PNG (``encode='png'``, ``ops.png_encode_indexed``), which leaves the
@@ -75,7 +83,7 @@ import numpy as np
 import torch
 
 from . import limits, ops
-from .options import CleanOptions, RefineOptions, RoiOptions
+from .options import CleanOptions, MotionOptions, RefineOptions, RoiOptions
 
 
 _HEAD = 8  # bytes in front of a slot's file: the int32 length, padded so that the file starts 8-byte aligned
@@ -129,14 +137,18 @@ class FrameSegmenter:
     clean: Optional[CleanOptions] = None  # (ObjectSegmenter has none)
     roi: Optional[RoiOptions] = None      # (likewise)
     refine: Optional[RefineOptions] = None  # (likewise)
+    motion: Optional[MotionOptions] = None  # (likewise)
     _seed = None
+    _luma = None
+    _luma_prev = None  # the index of the plane of self._luma that holds the frame before, or None
     _window = None
 
     def __init__(self, net, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  boolean_mask: bool = True, color: str = 'r', alpha: float = 1.0, encode: Optional[str] = None,
                  quality: int = 90, subsampling: str = '4:4:4', budget: Optional[int] = None,
                  net_size: Optional[Tuple[int, int]] = None, clean: Optional[CleanOptions] = None,
-                 roi: Optional[RoiOptions] = None, refine: Optional[RefineOptions] = None) -> None:
+                 roi: Optional[RoiOptions] = None, refine: Optional[RefineOptions] = None,
+                 motion: Optional[MotionOptions] = None) -> None:
         from util import frame_overlay
         self._set_geometry(height, width, depth, net_size)
         if clean is not None and not isinstance(clean, CleanOptions):
@@ -160,6 +172,14 @@ class FrameSegmenter:
                 raise ValueError(f"{self._who}: refine with roi is not built: the filter's guide is the image the net saw, a "
                                  "window of the frame, and the guide of a window is not built")
         self.refine = refine
+        if motion is not None:
+            if not isinstance(motion, MotionOptions):
+                raise ValueError(f"{self._who}: motion must be a fosvos_hip.options.MotionOptions or None, got "
+                                 f"{type(motion).__name__}")
+            if clean is None or not clean.chain:
+                raise ValueError(f"{self._who}: motion carries the seed of the temporal gate along the picture's motion: it "
+                                 "needs clean=CleanOptions(temporal_radius=...)")
+        self.motion = motion
         frame_overlay.check_color(color)
         self.mirror, self.overlay, self.boolean_mask = bool(mirror), bool(overlay), bool(boolean_mask)
         self.color, self.alpha = color, frame_overlay.check_alpha(alpha)
@@ -231,6 +251,15 @@ class FrameSegmenter:
             chained = self.clean is not None and self.clean.chain
             self._seed = torch.zeros((1,) + tuple(self.net_size or (h, w)), dtype=torch.uint8, device=self.device) \
                 if chained else None
+            self._luma = self._luma_prev = None
+            if self.motion is not None:
+                # the luma planes of the frame before and of this one by turns, the field and cost of the pair, the warped seed
+                hn, wn = self.net_size or (h, w)
+                hb, wb = -(-hn // self.motion.block), -(-wn // self.motion.block)
+                self._luma = torch.empty((2, 1, hn, wn), dtype=torch.uint8, device=self.device)
+                self._field = torch.empty((1, hb, wb, 2), dtype=torch.int8, device=self.device)
+                self._cost = torch.empty((1, hb, wb), dtype=torch.int32, device=self.device)
+                self._warped = torch.empty((1, hn, wn), dtype=torch.uint8, device=self.device)
         self._flight: Deque[_Slot] = deque()     # submitted, oldest first
         self._ready: Deque[Union[np.ndarray, bytes]] = deque()  # retired by a submit that needed the slot, not yet asked for
 
@@ -311,7 +340,18 @@ class FrameSegmenter:
                 # stream in submit order, so frame t finds frame t - 1's kept mask there without an event of its own
                 c = self.clean
                 logits = logits.contiguous()
-                ops.clean_components(logits, self._seed, 0 if c.temporal_radius is None else c.temporal_radius, c.min_area,
+                seed = self._seed
+                if self.motion is not None:
+                    # the seed in this frame's coordinates: the luma of what the net saw, its motion against the frame
+                    # before, the seed warped along it into a buffer of its own.  The planes change roles in submit order
+                    now = 0 if self._luma_prev is None else 1 - self._luma_prev
+                    ops.motion_luma(slot.image, out=self._luma[now])
+                    if self._luma_prev is not None:
+                        ops.motion_estimate(self._luma[self._luma_prev], self._luma[now], self.motion, field=self._field,
+                                            cost=self._cost)
+                        seed = ops.motion_warp(self._seed, self._field, self.motion.block, out=self._warped)
+                    self._luma_prev = now
+                ops.clean_components(logits, seed, 0 if c.temporal_radius is None else c.temporal_radius, c.min_area,
                                      c.largest, chain=c.chain, fill=c.fill, out=logits,
                                      kept=None if self._seed is None else self._seed)
             if roi is not None:
@@ -369,6 +409,7 @@ class FrameSegmenter:
                     for st in (self._up, main, self._down):
                         st.synchronize()
                     self._free.append(slot)
+                    self._luma_prev = None  # (motion) whichever plane the frame reached: the next frame's seed is not warped
                 except Exception:
                     self.close()
                 raise
@@ -425,6 +466,7 @@ class FrameSegmenter:
         host = torch.from_numpy(np.ascontiguousarray((mask != 0).astype(np.uint8)))[None]
         with torch.cuda.device(self.device):
             self._seed.copy_(host)  # on the current stream, the net's: ordered with the frames before and behind
+        self._luma_prev = None  # (motion) the mask belongs to the next submitted frame: used unwarped
 
     @property
     def _roi_size(self) -> Tuple[int, int]:
@@ -464,6 +506,8 @@ class FrameSegmenter:
         self._closed = True
         self._seed = None
         self._window = None
+        self._luma = self._luma_prev = None
+        self._field = self._cost = self._warped = None
         for slot in self._flight:
             try:
                 slot.moved.synchronize()
@@ -504,8 +548,11 @@ class ObjectSegmenter(FrameSegmenter):
     def __init__(self, nets, height: int, width: int, depth: int = 2, mirror: bool = True, overlay: bool = True,
                  palette=None, alpha: float = 0.5, encode: Optional[str] = None, quality: int = 90,
                  subsampling: str = '4:4:4', budget: Optional[int] = None, huffman: str = 'fixed',
-                 net_size: Optional[Tuple[int, int]] = None, clean=None, roi=None, refine=None) -> None:
+                 net_size: Optional[Tuple[int, int]] = None, clean=None, roi=None, refine=None, motion=None) -> None:
         from util import object_overlay
+        if motion is not None:
+            raise ValueError("ObjectSegmenter: motion= carries the temporal gate of ONE object's mask (FrameSegmenter); "
+                             "per-object gates in front of the merge are not built")
         if refine is not None:
             raise ValueError("ObjectSegmenter: refine= refines the logits of ONE object (FrameSegmenter); K fits in front of the "
                              "merge are not built")

@@ -20,7 +20,9 @@ towards its DAVIS palette colour (``--palette-alpha``, 0..1), or with ``--no-ove
 as palette PNG files that the device encoded.  ``--clean-min-area N``, ``--clean-largest`` and ``--clean-temporal R`` (any of them;
 single object only) clean the net's mask on the device before the overlay (``FrameSegmenter(clean=)``;
 util/mask_components.py): connected components that are too small, not the largest, or further than R net pixels from what the
-frame before kept are dropped; ``--clean-seed FILE.png`` is the mask the first frame is gated by.  ``--roi`` (with
+frame before kept are dropped; ``--clean-seed FILE.png`` is the mask the first frame is gated by; ``--clean-motion`` (with
+``--motion-block`` / ``--motion-search`` / ``--motion-zero-bias``) carries that kept mask along the motion of the picture first
+(``FrameSegmenter(motion=)``; util/block_motion.py).  ``--roi`` (with
 ``--net-height`` / ``--net-width``; single object only) follows the object: the net sees a window of the frame around the last
 mask, scaled to the net's size, and the logits are painted back into it (``FrameSegmenter(roi=)``; util/frame_roi.py);
 ``--roi-levels N``, ``--roi-margin F`` and ``--roi-min-pad P`` are the RoiOptions, ``--roi-seed FILE.png`` is the annotation the
@@ -101,6 +103,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--clean-temporal', type=int, default=None, metavar='R',
                    help='clean the mask on the device: keep only components within R (0..63) net pixels of what the '
                         'frame before kept')
+    from util import args_helper
+    args_helper.add_motion_arguments(p)
     p.add_argument('--clean-seed', type=str, default=None, metavar='FILE.png',
                    help='the mask --clean-temporal starts from (non-zero = object; the frames\' or the net\'s size), '
                         'e.g. the annotation the net was fine-tuned on')
@@ -455,6 +459,8 @@ def main(argv=None) -> List[float]:
     args = parser.parse_args(argv)
     net_size = net_size_of(parser, args)
     clean = clean_of(parser, args)
+    from util import args_helper
+    motion = args_helper.motion_of(parser, args)  # (--clean-temporal's own refusals come first, in clean_of)
     roi = roi_of(parser, args, net_size)
     refine = refine_of(parser, args)
     if args.models is not None:
@@ -536,6 +542,8 @@ def main(argv=None) -> List[float]:
                                    suffix='.png' if seg.encode == 'png' else '.jpg')
         if clean is not None:  # (absent: the segmenter is constructed exactly as it was)
             encode['clean'] = clean
+        if motion is not None:
+            encode['motion'] = motion
         if roi is not None:
             encode['roi'] = roi
         if refine is not None:

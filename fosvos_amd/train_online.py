@@ -51,6 +51,7 @@ rotate = None               # --augment-rotate (and its options): a RotateOption
 adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
 ensemble = None             # --ensemble-flip / --ensemble-scales (with --fast-test or --multi-object): an EnsembleOptions
 crf = None                  # --crf (and --crf-*; with --fast-test or --multi-object): a CrfOptions
+motion = None               # --clean-motion (and --motion-*; with --clean-temporal): a MotionOptions
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
 
@@ -170,6 +171,8 @@ def train_and_test(net_provider: NetworkProvider, seq_name: str, settings: Onlin
                 cleaning['ensemble'] = ensemble
             if crf is not None:  # (absent: the call is what it was)
                 cleaning['crf'] = crf
+            if motion is not None:  # (absent: the call is what it was)
+                cleaning['motion'] = motion
             result = experiment_helper.test_fast(net_provider, data_loader, save_dir, annotations, seq_name=seq_name,
                                                  png_huffman='fitted' if png_fitted else 'fixed', **cleaning)
             _report_score(result, save_dir, seq_name)
@@ -599,7 +602,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean, adapt, rotate, ensemble, crf
+    global multi_object, synthetic_objects, clean, adapt, rotate, ensemble, crf, motion
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -619,6 +622,7 @@ def main(argv=None):
     rotate = args.rotate
     ensemble = args.ensemble
     crf = args.crf_options
+    motion = args.motion
     synthetic_objects = int(args.objects)
     del scored_sequences[:]
     if args.network != 'vgg16':

@@ -6,7 +6,8 @@ reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/
 --data-parallel, --augment-rotate with --rotate-range / --zoom-range / --rotate-renormalize, --resident-train-set and
 --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
 --multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal, --adapt-steps with its --adapt-* options,
---ensemble-flip and --ensemble-scales, --crf with its --crf-* options (online only).
+--ensemble-flip and --ensemble-scales, --crf with its --crf-* options, --clean-motion with its --motion-* options (online
+only).
 """
 import argparse
 from typing import List, Optional
@@ -69,6 +70,39 @@ def _rotate_options(parser: argparse.ArgumentParser, args: argparse.Namespace):
         parser.error(str(err).replace('RotateOptions: ', '--augment-rotate: '))
 
 
+def add_motion_arguments(parser: argparse.ArgumentParser) -> None:
+    """--clean-motion and its options, the same on every command line that has --clean-temporal."""
+    parser.add_argument('--clean-motion', action='store_true',
+                        help='with --clean-temporal: carry what the frame before kept along the motion of the picture before '
+                             'it gates this frame (block matching on the device; util/block_motion.py)')
+    parser.add_argument('--motion-block', type=int, default=None, metavar='B',
+                        help='with --clean-motion: the side of a block in pixels (8 or 16; default 16)')
+    parser.add_argument('--motion-search', type=int, default=None, metavar='S',
+                        help='with --clean-motion: a block is looked for up to S pixels away (1..16; default 8)')
+    parser.add_argument('--motion-zero-bias', type=int, default=None, metavar='Z',
+                        help='with --clean-motion: what a non-zero vector must win by, in sixteenths of a grey level a pixel '
+                             '(0..255; default 8)')
+
+
+def motion_of(parser: argparse.ArgumentParser, args):
+    """The MotionOptions of --clean-motion / --motion-*, or None; what cannot be combined is refused with the reason.  (What
+    --clean-temporal itself is refused with is said where that flag is checked.)"""
+    fields = {'block': args.motion_block, 'search': args.motion_search, 'zero_bias': args.motion_zero_bias}
+    given = ['--motion-' + name.replace('_', '-') for name, v in fields.items() if v is not None]
+    if given and not args.clean_motion:
+        parser.error('{} set(s) an option of the motion-compensated gate: it needs --clean-motion'.format(' / '.join(given)))
+    if not args.clean_motion:
+        return None
+    if args.clean_temporal is None:
+        parser.error('--clean-motion carries the seed of the temporal gate along the picture\'s motion: it needs '
+                     '--clean-temporal R')
+    try:
+        from fosvos_hip.options import MotionOptions
+        return MotionOptions(**{name: v for name, v in fields.items() if v is not None})
+    except ValueError as err:
+        parser.error(str(err).replace('MotionOptions: ', '--motion-*: '))
+
+
 def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Namespace:
     parser = _get_base_parser()
     if is_online:
@@ -100,6 +134,7 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         parser.add_argument('--clean-temporal', type=int, default=None, metavar='R',
                             help='with --fast-test: keep only components within R (0..63) pixels of what the frame before '
                                  'kept; the first frame is gated by the training annotation')
+        add_motion_arguments(parser)
         parser.add_argument('--adapt-steps', type=int, default=None, metavar='N',
                             help='online adaptation in the test pass: N (>= 1) fine-tune steps on every frame against '
                                  'pseudo-labels made from the net\'s own output (confident pixels positive, pixels far from '
@@ -185,6 +220,8 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
             parser.error('--clean-min-area must be >= 0, got {}'.format(args.clean_min_area))
         if args.clean_temporal is not None and not 0 <= args.clean_temporal <= 63:
             parser.error('--clean-temporal must be 0..63, got {}'.format(args.clean_temporal))
+    if is_online:
+        args.motion = motion_of(parser, args)
     if is_online:
         given = [flag for flag, v in (('--adapt-pos-prob', args.adapt_pos_prob), ('--adapt-distance', args.adapt_distance),
                                       ('--adapt-erode', args.adapt_erode), ('--adapt-frame-weight', args.adapt_frame_weight),

@@ -20,7 +20,9 @@ takes fine-tune steps against pseudo-labels made from its own output on the devi
 ``test_fast`` and ``test_objects`` take ``ensemble=`` (``--ensemble-flip``, ``--ensemble-scales``): the net also sees every frame
 mirrored and at other sizes, and the device averages its answers back on the frame's grid (util/test_ensemble.py states it).
 They also take ``crf=`` (``--crf``): a local CRF on the frame's colours refines the logits on the device before anything else
-reads them (util/mask_crf.py states it)."""
+reads them (util/mask_crf.py states it).  ``test_fast`` takes ``motion=`` (``--clean-motion``) beside a temporal gate: the
+gate's seed is carried along the motion of the picture, estimated by block matching on the device (util/block_motion.py
+states it)."""
 import timeit
 from pathlib import Path
 from typing import Callable, Optional
@@ -303,6 +305,53 @@ def _crf_logits(inputs: torch.Tensor, logits: torch.Tensor, crf) -> torch.Tensor
     return torch.from_numpy(mask_crf.refine_batch(inputs.float().contiguous().numpy(), logits.numpy(), crf))
 
 
+def _check_motion(who: str, motion, clean) -> None:
+    if motion is not None:
+        from fosvos_hip.options import MotionOptions
+        if not isinstance(motion, MotionOptions):
+            raise ValueError('{}: motion must be a fosvos_hip.options.MotionOptions or None, got {!r}'.format(who, motion))
+        if clean is None or getattr(clean, 'temporal_radius', None) is None:
+            raise ValueError('{}: motion carries the seed of the temporal gate along the picture\'s motion: it needs '
+                             'clean=CleanOptions(temporal_radius=...)'.format(who))
+
+
+class _MotionBuffers:
+    """What the motion-compensated gate keeps on the device per frame size: the luma planes of a group behind the last plane
+    of the group before ([group + 1, H, W]; plane 0 is that last plane), the fields and costs of the group's pairs and the
+    warped seed.  Allocated at the first group of a size."""
+
+    def __init__(self, group: int, h: int, w: int, block: int, device) -> None:
+        hb, wb = -(-h // block), -(-w // block)
+        self.luma = torch.empty((group + 1, h, w), dtype=torch.uint8, device=device)
+        self.field = torch.empty((group, hb, wb, 2), dtype=torch.int8, device=device)
+        self.cost = torch.empty((group, hb, wb), dtype=torch.int32, device=device)
+        self.warped = torch.empty((1, h, w), dtype=torch.uint8, device=device)
+
+
+def _motion_clean(ops, inputs: torch.Tensor, logits: torch.Tensor, seed_dev, kept: torch.Tensor, buffers: _MotionBuffers,
+                  continued: bool, clean, motion) -> None:
+    """A group's chain with its seed carried along the motion: ONE ``motion_luma`` of the group's uploaded frames, ONE
+    ``motion_estimate`` over its consecutive pairs - the pair across the group boundary included when the chain is
+    ``continued``: plane 0 of ``buffers.luma`` then holds the last plane of the group before and ``seed_dev`` what that frame
+    kept -, and per frame ``motion_warp`` of the seed and ``clean_components`` on that one frame, in place.  The very first
+    frame of a chain is gated by ``seed_dev`` unwarped (None: not gated).  No host synchronisation."""
+    n = int(logits.shape[0])
+    planes = buffers.luma
+    ops.motion_luma(inputs.float().contiguous(), out=planes[1:n + 1])
+    lo = 0 if continued else 1          # the first plane that is a pair's previous frame
+    pairs = n - lo
+    if pairs > 0:
+        ops.motion_estimate(planes[lo:n], planes[lo + 1:n + 1], motion, field=buffers.field[:pairs], cost=buffers.cost[:pairs])
+    for t in range(n):
+        seed = seed_dev if t == 0 else kept[t - 1:t]
+        if t > 0 or continued:
+            pair = t - lo
+            seed = ops.motion_warp(seed, buffers.field[pair:pair + 1], motion.block, out=buffers.warped)
+        ops.clean_components(logits[t:t + 1], seed, clean.temporal_radius, clean.min_area, clean.largest, chain=True,
+                             fill=clean.fill, out=logits[t:t + 1], kept=kept[t:t + 1])
+    planes[0].copy_(planes[n])          # the next group's boundary pair: a copy in stream order, no host
+
+
 def _check_png_huffman(who: str, png_huffman: str) -> None:
     from util import png_layout
     if png_huffman not in png_layout.HUFFMAN_MODES:
@@ -377,7 +426,7 @@ def _frame_groups(data_loader, group: int):
 
 def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
               seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed', clean=None,
-              clean_seed: Optional[np.ndarray] = None, ensemble=None, crf=None) -> Optional[dict]:
+              clean_seed: Optional[np.ndarray] = None, ensemble=None, crf=None, motion=None) -> Optional[dict]:
     """The test pass with the PNG files made on the device.  Up to ``group`` consecutive frames of one shape are uploaded
     as one batch and forwarded ``forward_batch`` frames a call into one logit tensor.  Two frames a call is the largest
     batch whose frames the engine computes exactly as it computes a frame alone (a batch runs as two chains of ceil(N/2)
@@ -409,12 +458,21 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     ``crf`` (a ``fosvos_hip.options.CrfOptions``; None: nothing changes): each group's logits - the merged ones behind an
     ensemble - go through ONE ``ops.crf_refine`` whose guide is the group's uploaded frames, before the cleaning, the counts
     and the bytes (util/mask_crf.py states it; CPU tensors: ``mask_crf.refine``).  No host synchronisation is added.  The
-    score dict and ``last_fast`` then hold the options under 'crf'."""
+    score dict and ``last_fast`` then hold the options under 'crf'.
+    ``motion`` (a ``fosvos_hip.options.MotionOptions``; None: nothing changes; it needs ``clean.temporal_radius``): the
+    temporal gate follows the picture.  Per group ONE ``ops.motion_luma`` of the uploaded frames and ONE
+    ``ops.motion_estimate`` over the consecutive pairs - the pair across the group boundary uses the last luma plane of the
+    group before, kept on the device -, then frame by frame ``ops.motion_warp`` of what the frame before kept and
+    ``ops.clean_components`` on that one frame with the warped mask as its seed (util/block_motion.py: ``gate_sequence``
+    states it and is the CPU tensors' path).  The sequence's first frame is gated by ``clean_seed`` unwarped; a change of the
+    frame size starts the chain again.  It sits where cleaning sits, behind the ensemble's merge and the CRF; no host
+    synchronisation is added.  The score dict and ``last_fast`` then hold the options under 'motion'."""
     from util import png_layout
     _check_png_huffman('test_fast', png_huffman)
     _check_batching('test_fast', group, forward_batch)
     _check_ensemble('test_fast', ensemble)
     _check_crf('test_fast', crf)
+    _check_motion('test_fast', motion, clean)
     if clean is None and clean_seed is not None:
         raise ValueError('test_fast: clean_seed is the first seed of clean=CleanOptions(temporal_radius=...)')
     if clean is not None:
@@ -432,6 +490,9 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
     seed_host = clean_seed   # the chain's seed for the next group: host form (CPU logits) ...
     seed_dev = None          # ... and device form, uint8 [1,H,W]
     kept_dev = {}            # (n, h, w) -> the group's kept masks
+    motion_dev = {}          # (h, w) -> the _MotionBuffers of that frame size
+    motion_size = None       # the frame size whose last luma plane the device holds (motion): the chain can continue
+    motion_host = None       # (luma plane, kept mask) of the last frame, host form (motion, CPU logits)
     log.info('Testing Network (fast)')
     net = net_provider.network
     frames = _Frames(data_loader, save_dir)
@@ -475,8 +536,15 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                         if (n, h, w) not in kept_dev:
                             kept_dev[(n, h, w)] = torch.empty((n, h, w), dtype=torch.uint8, device=logits.device)
                         kept = kept_dev[(n, h, w)]
-                        ops.clean_components(logits, seed_dev, clean.temporal_radius, clean.min_area, clean.largest,
-                                             chain=True, fill=clean.fill, out=logits, kept=kept)
+                        if motion is None:
+                            ops.clean_components(logits, seed_dev, clean.temporal_radius, clean.min_area, clean.largest,
+                                                 chain=True, fill=clean.fill, out=logits, kept=kept)
+                        else:
+                            if (h, w) not in motion_dev:
+                                motion_dev[(h, w)] = _MotionBuffers(group, h, w, motion.block, logits.device)
+                            _motion_clean(ops, inputs, logits, seed_dev, kept, motion_dev[(h, w)],
+                                          motion_size == (h, w) and seed_dev is not None, clean, motion)
+                            motion_size = (h, w)
                         # what the group's last frame kept gates the next group's first: a copy in stream order, no host
                         if seed_dev is None:
                             seed_dev = torch.empty((1, h, w), dtype=torch.uint8, device=logits.device)
@@ -495,7 +563,17 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
                 pending = sent
             else:
                 x = logits[:, 0].numpy()
-                if clean is not None:
+                if motion is not None:
+                    from util import block_motion
+                    if motion_host is not None and motion_host[0].shape != (h, w):
+                        motion_host = None  # the frames changed their size: the chain starts again
+                    frames_host = inputs.float().contiguous().numpy()
+                    x, kept = block_motion.gate_sequence(
+                        frames_host, np.ascontiguousarray(x, dtype=np.float32), seed_host if motion_host is None else None,
+                        clean, motion, *(motion_host or (None, None)))
+                    motion_host = (block_motion.luma(frames_host[n - 1]), kept[n - 1])
+                    seed_host = None  # used: every later frame is gated by what the frame before kept
+                elif clean is not None:
                     from util import mask_components
                     x, kept = mask_components.clean_sequence(
                         np.ascontiguousarray(x, dtype=np.float32), seed_host if clean.chain else None,
@@ -521,6 +599,8 @@ def test_fast(net_provider, data_loader, save_dir: Path, annotations: Optional[C
         cleaned['ensemble'] = ensemble.as_dict()
     if crf is not None:
         cleaned['crf'] = crf.as_dict()
+    if motion is not None:
+        cleaned['motion'] = motion.as_dict()
     last_fast.clear()
     last_fast.update(n_frames=len(frames), n_groups=len(group_sizes), group_sizes=group_sizes, seconds=time_for_all,
                      seconds_load=stage['load'], seconds_issue=stage['issue'], seconds_wait=stage['wait'],

@@ -800,6 +800,31 @@ int fosvos_crf_refine(const float *image, const float *logits, const double *tab
                       int radius, double weight_appearance, double weight_smooth, double clip, const float mean[3], float *out,
                       void *workspace, size_t workspace_bytes, int device, void *stream);
 
+/* Measuring how the picture moved between two frames and moving a mask along with it (opt-in; csrc/motion.hip): full-search
+ * block matching on the frames' luma and a per-block warp, all in integers.  util/block_motion.py states the arithmetic in
+ * numpy; every output is compared with it bit for bit.  Each entry is ONE launch on `stream`; no workspace, no atomics, no
+ * workgroup waits for another, no synchronisation.  Sides of 1..8192 (FOSVOS_E_SHAPE).
+ *
+ * fosvos_motion_luma: image fp32 [N,3,H,W] (the net's input: the frame minus `mean`, whose bytes are taken back as
+ *   fosvos_crf_refine takes them; a NaN is level 0) -> out u8 [N,H,W], Y = (29 g0 + 150 g1 + 77 g2 + 128) >> 8.  The image
+ *   4-byte aligned.
+ * fosvos_motion_estimate: prev, cur u8 [N,H,W] -> field i8 [N,Hb,Wb,2] = (dy, dx) and cost i32 [N,Hb,Wb] (4-byte aligned),
+ *   Hb = ceil(H / block), Wb = ceil(W / block); pair n is (prev[n], cur[n]), so consecutive frames of one buffer are two
+ *   pointers one plane apart.  Block (by, bx) owns the pixels P of its square that lie in the frame; a candidate d in
+ *   [-search, search]^2 counts iff P + d lies wholly in the frame (skipped otherwise, never clamped); SAD(d) = sum over P of
+ *   |cur[p] - prev[p + d]|, score(d) = SAD(d) + (d != 0 ? (zero_bias |P|) >> 4 : 0); the winner is the smallest
+ *   (score, dy^2 + dx^2, dy, dx); cost is its SAD.  cur[p] ~ prev[p + field].  block 8 or 16, 1 <= search <= 16,
+ *   0 <= zero_bias <= 255 (FOSVOS_E_ARG).  16 x 64 tiles with a halo of `search` in 5.7 KB of LDS; a wave owns a block, its
+ *   lanes share out the candidates.
+ * fosvos_motion_warp: mask u8 [N,H,W] (non-zero = set) and field i8 [N,Hb,Wb,2] (ANY values) -> out u8 [N,H,W] of 0 and 1:
+ *   out[y, x] = mask[y + dy, x + dx] != 0 with the pixel's block's (dy, dx), 0 where the source lies outside the frame (tested
+ *   before the read).  block 8 or 16; `out` must not overlap `mask` (FOSVOS_E_ARG). */
+int fosvos_motion_luma(const float *image, const float mean[3], int N, int H, int W, uint8_t *out, int device, void *stream);
+int fosvos_motion_estimate(const uint8_t *prev, const uint8_t *cur, int N, int H, int W, int block, int search, int zero_bias,
+                           int8_t *field, int32_t *cost, int device, void *stream);
+int fosvos_motion_warp(const uint8_t *mask, const int8_t *field, int N, int H, int W, int block, uint8_t *out, int device,
+                       void *stream);
+
 /* ---- thin-channel ResNet inference path (OSVOS_RESNET and the nets prune.py derives from it) ------
  * Activations: bf16 NHWC [N,H,W,Cp] with Cp = channels rounded up to a multiple of 8, padded channels zero.
  * Eval-mode BatchNorm is folded into the conv in front of it when the weights are packed:
