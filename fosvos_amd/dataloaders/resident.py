@@ -26,6 +26,12 @@ one HIP launch (fosvos_hip.ops.augment_sample, bit for bit custom_transforms.res
 so nothing can be precomputed: both loaders keep the uint8 sample(s) and the lookup tables on the device, replay per draw
 the flip's ``random()`` and then ScaleNRotate's two draws (``random()`` twice for ranges, ``randint`` twice for lists), and
 launch fosvos_hip.ops.warp_sample (bit for bit custom_transforms.warp_affine) into fresh tensors of the frame's own size.
+
+``lucid=LucidOptions(...)`` (opt-in, the one-shot loader only, not together with ``rotate``): the object moves against its
+background (dataloaders/lucid.py).  The loader paints the object out once on the host, keeps frame, filled background, mask
+and tables on the device, replays per epoch the flip's ``random()`` and the eleven draws of ``LucidDream.draw``, and launches
+fosvos_hip.ops.lucid_sample (bit for bit ``lucid.compose``) into fresh tensors.  There is no host DataLoader to replay: the
+definition is this loader on a CPU device.
 """
 import random
 import time
@@ -89,39 +95,58 @@ class ResidentOneShotLoader(object):
     dict (``image`` [1,3,h,w], ``gt`` [1,1,h,w] on ``device``, ``seq_name`` / ``fname`` lists as default_collate builds them)."""
 
     def __init__(self, dataset, device: Optional[torch.device] = None, scales: Sequence[float] = (0.5, 0.8, 1),
-                 rotate=None):
+                 rotate=None, lucid=None):
         """rotate: a fosvos_hip.options.RotateOptions - ScaleNRotate in place of the rescale.  The loader then keeps the
         sample as bytes and warps it per draw (``draws`` records (flip, rot, sc)); ``variants`` holds the one tensor pair
-        that is still fixed, the unaugmented frame ((False, 0), ``scales == [1]``), which online adaptation trains on."""
+        that is still fixed, the unaugmented frame ((False, 0), ``scales == [1]``), which online adaptation trains on.
+        lucid: a fosvos_hip.options.LucidOptions (not together with ``rotate``) - the object moves against its background
+        (dataloaders/lucid.py).  The loader paints the object out once on the host (``lucid.fill_background``), keeps frame,
+        filled background, mask and the tables on the device, replays per epoch the flip's ``random()`` and then the eleven
+        draws of ``LucidDream.draw``, and composes with one fosvos_hip.ops.lucid_sample call (on a CPU device:
+        ``lucid.compose``, the same bits); ``draws`` records (flip, draws) and ``variants`` holds the unaugmented frame."""
         if len(dataset) != 1:
             raise ValueError("ResidentOneShotLoader holds the single sample of a one-shot sequence run, got %d samples"
                              % len(dataset))
         if dataset.transform is not None:
             raise ValueError("pass the dataset without its transform: the loader applies flip / rescale / ToTensor itself")
+        if rotate is not None and lucid is not None:
+            raise ValueError("ResidentOneShotLoader: rotate and lucid both stand in place of the rescale: pass one of them")
         self.dataset = dataset
         self.scales = list(scales)
         self.device = device if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.rotate = rotate
-        self.draws: List[tuple] = []  # (flip, scale index) of every epoch so far; rotating: (flip, rot, sc)
+        self.lucid = lucid
+        self.draws: List[tuple] = []  # (flip, scale index) of every epoch so far; rotating: (flip, rot, sc); lucid: (flip, draws)
         self.variants: Dict[tuple, Dict[str, torch.Tensor]] = {}
         to_tensor = custom_transforms.ToTensor()
-        if rotate is not None:
+        if rotate is not None or lucid is not None:
             self.device = torch.device(self.device)
             self.scales = [1]
-            self._transform = rotate.transform()
             img, lab = dataset.read_raw(0)  # decoded once
             self._raw = (np.array(img, dtype=np.uint8, order="C"),
                          None if lab is None else np.array(lab, dtype=np.uint8, order="C"))
             self._meta = {"seq_name": [dataset.seq_list[0]], "fname": [dataset.fname_list[0]]}
             plain = to_tensor(dict(zip(("image", "gt"), dataset.convert_raw(*self._raw))))
             self.variants[(False, 0)] = {k: v.unsqueeze(0).to(self.device) for k, v in plain.items()}
+            img, lab = self._raw
+            img_lut, gt_luts = _value_tables(dataset, [lab])
+            mask = np.zeros(img.shape[:2], np.uint8) if lab is None else lab
+            if rotate is not None:
+                self._transform = rotate.transform()
+            else:
+                from dataloaders import lucid as lucid_rules
+                self._dream = lucid.dream()
+                self._host = (img, lucid_rules.fill_background(img, mask, lucid.dilate, lucid.smooth), mask, img_lut, gt_luts[0])
+                box = lucid_rules.mask_box(mask)  # None: an empty or hidden annotation - no object
+                self._boxes = {False: box, True: lucid_rules.mirrored_box(box, img.shape[1])}
             if self.device.type != "cpu":
-                img, lab = self._raw
-                img_lut, gt_luts = _value_tables(dataset, [lab])
                 self._frame = torch.from_numpy(img).to(self.device)
-                self._mask = torch.from_numpy(np.zeros(img.shape[:2], np.uint8) if lab is None else lab).to(self.device)
+                self._mask = torch.from_numpy(mask).to(self.device)
                 self._img_lut, self._gt_lut = torch.from_numpy(img_lut).to(self.device), torch.from_numpy(gt_luts[0]).to(self.device)
-                self._workspace = _warp_workspace(self._transform, [img.shape[:2]], self.device)
+                if rotate is not None:
+                    self._workspace = _warp_workspace(self._transform, [img.shape[:2]], self.device)
+                else:
+                    self._background = torch.from_numpy(self._host[1]).to(self.device)
             return
         base = dataset[0]  # decoded once
         self._meta = {k: [base[k]] for k in ("seq_name", "fname") if k in base}
@@ -148,6 +173,12 @@ class ResidentOneShotLoader(object):
             self.draws.append((flip, rot, sc))
             yield self.sample(flip, rot, sc)
             return
+        if self.lucid is not None:
+            draws = self._dream.draw(rng)         # the eleven draws, in lucid.DRAWS' order
+            torch.empty((), dtype=torch.int64).random_()  # RandomSampler.__iter__ (below)
+            self.draws.append((flip, draws))
+            yield self.composed(flip, draws)
+            return
         si = rng.randint(0, len(self.scales) - 1)  # Resize.__call__
         torch.empty((), dtype=torch.int64).random_()  # RandomSampler.__iter__: its own seed, drawn at the first index
         self.draws.append((flip, si))
@@ -162,6 +193,23 @@ class ResidentOneShotLoader(object):
         else:
             batch = _rotated_on_device(self._frame, self._mask, self._img_lut, self._gt_lut, self._transform,
                                        self._workspace, flip, rot, sc)
+        batch.update({k: list(v) for k, v in self._meta.items()})
+        return batch
+
+    def composed(self, flip: bool, draws) -> dict:
+        """The minibatch of a lucid loader with the draws (flip, the eleven of ``lucid.DRAWS``) fixed."""
+        h, w = self._host[0].shape[:2]
+        m_bg, m_fg, gain, bias = self._dream.matrices(draws, self._boxes[bool(flip)], (h, w))
+        if self.device.type == "cpu":
+            from dataloaders import lucid as lucid_rules
+            image, gt = lucid_rules.compose(*self._host[:3], *self._host[3:], flip, m_bg, m_fg, gain, bias)
+            batch = {k: v.unsqueeze(0) for k, v in custom_transforms.ToTensor()({"image": image, "gt": gt}).items()}
+        else:
+            from fosvos_hip import ops
+            batch = {"image": torch.empty((1, 3, h, w), dtype=torch.float32, device=self.device),
+                     "gt": torch.empty((1, 1, h, w), dtype=torch.float32, device=self.device)}
+            ops.lucid_sample(self._frame, self._background, self._mask, flip, m_bg, m_fg, gain, bias, self._img_lut,
+                             self._gt_lut, batch["image"], batch["gt"])
         batch.update({k: list(v) for k, v in self._meta.items()})
         return batch
 
@@ -185,7 +233,10 @@ class ResidentTrainSetLoader(object):
     every sample keeps its own size and ``draws`` records (flip, rot, sc)."""
 
     def __init__(self, dataset, device: Optional[torch.device] = None, shard: Optional[Tuple[int, int]] = None,
-                 batch_size: int = 1, scales: Sequence[float] = (0.5, 0.8, 1), threads: int = 16, rotate=None):
+                 batch_size: int = 1, scales: Sequence[float] = (0.5, 0.8, 1), threads: int = 16, rotate=None, lucid=None):
+        if lucid is not None:
+            raise ValueError("ResidentTrainSetLoader: lucid is built for the one-shot sample only (ResidentOneShotLoader); the "
+                             "offline set would need a filled background per training frame")
         if batch_size != 1:
             raise ValueError("ResidentTrainSetLoader yields batches of one sample (frames of different scales cannot be "
                              "collated), got batch_size=%d" % batch_size)

@@ -220,6 +220,8 @@ SIGNATURES = {
     "fosvos_warp_sample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [ctypes.c_double] * 6 +
                            [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_warp_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "fosvos_lucid_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [ctypes.c_double] * 12 + [c_int] +
+                            [c_float] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "fosvos_prob_bytes": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fosvos_jf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fosvos_jf_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int,

@@ -49,6 +49,13 @@ CRF_MAX_CLIP = 1e4
 MOTION_BLOCKS = (8, 16)
 MOTION_MAX_SEARCH = 16
 MOTION_MAX_ZERO_BIAS = 255
+# moving the object against its background (dataloaders/lucid.py: MAX_DILATE, MAX_SMOOTH); angles and zooms as ROTATE_*, the
+# object's shift in box sizes, contrast and tint as factors, brightness in grey levels
+LUCID_MAX_DILATE = 31
+LUCID_MAX_SMOOTH = 16
+LUCID_MAX_SHIFT = 4.0
+LUCID_GAIN_RANGE = (1.0 / 16, 16.0)
+LUCID_MAX_BRIGHTNESS = 255.0
 
 
 def real_number(v) -> bool:

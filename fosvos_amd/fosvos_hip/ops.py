@@ -1100,7 +1100,6 @@ def warp_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, matrix, img
     (custom_transforms.ScaleNRotate(renormalize=True)); it needs ``workspace``, a uint8 tensor of at least
     ``warp_workspace_bytes(H, W)`` bytes.  On a mask the renormalisation is a no-op, because its values are in [0, 1]: the
     gt is never rewritten."""
-    import numpy as np
     _need(frame, torch.uint8, "warp_sample frame")
     _need(mask, torch.uint8, "warp_sample mask")
     _need(img_lut, _F32, "warp_sample img_lut")
@@ -1120,20 +1119,7 @@ def warp_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, matrix, img
         raise ValueError(f"warp_sample: a warp keeps the size: image must be [1,3,{h},{w}], got {tuple(image.shape)}")
     if tuple(gt.shape) != (1, 1, h, w):
         raise ValueError(f"warp_sample: gt must be [1,1,{h},{w}], got {tuple(gt.shape)}")
-    try:
-        m = np.array(matrix, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"warp_sample: matrix must be 2x3 numbers, got {matrix!r}") from None
-    if m.shape != (2, 3):
-        raise ValueError(f"warp_sample: matrix must be 2x3 (source -> destination), got shape {m.shape}")
-    if not np.isfinite(m).all():
-        raise ValueError(f"warp_sample: matrix must be finite, got {m.tolist()}")
-    try:
-        inv = np.linalg.inv(np.vstack([m, [0.0, 0.0, 1.0]]))  # warp_affine's own inversion
-    except np.linalg.LinAlgError:
-        raise ValueError(f"warp_sample: matrix is singular: {m.tolist()}") from None
-    if not np.isfinite(inv).all():
-        raise ValueError(f"warp_sample: the inverse of the matrix is not finite: {m.tolist()}")
+    inv = _inverse_2x3("warp_sample", "matrix", matrix)
     if not isinstance(renormalize, bool):
         raise ValueError(f"warp_sample: renormalize must be a bool, got {renormalize!r}")
     ws_ptr, ws_bytes = None, 0
@@ -1149,9 +1135,78 @@ def warp_sample(frame: torch.Tensor, mask: torch.Tensor, flip: bool, matrix, img
         ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
     _same_device("warp_sample", frame, mask, img_lut, gt_lut, image, gt, *(() if workspace is None else (workspace,)))
     _launch("warp_sample", frame, frame.data_ptr(), mask.data_ptr(), h, w, 1 if flip else 0,
-            *(float(v) for v in inv[:2].reshape(-1)), img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(),
+            *inv, img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(),
             1 if renormalize else 0, ws_ptr, ws_bytes,
             nbytes=float(49 * h * w + 4 * (image.numel() + gt.numel()) + (8 * image.numel() if renormalize else 0)))
+
+
+def _inverse_2x3(what: str, name: str, matrix) -> Tuple[float, ...]:
+    """The six doubles of destination -> source of a 2x3 SOURCE -> DESTINATION ``matrix``, inverted exactly as
+    custom_transforms.warp_affine inverts it (np.linalg.inv of the 3x3 in fp64)."""
+    import numpy as np
+    try:
+        m = np.array(matrix, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be 2x3 numbers, got {matrix!r}") from None
+    if m.shape != (2, 3):
+        raise ValueError(f"{what}: {name} must be 2x3 (source -> destination), got shape {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError(f"{what}: {name} must be finite, got {m.tolist()}")
+    try:
+        inv = np.linalg.inv(np.vstack([m, [0.0, 0.0, 1.0]]))  # warp_affine's own inversion
+    except np.linalg.LinAlgError:
+        raise ValueError(f"{what}: {name} is singular: {m.tolist()}") from None
+    if not np.isfinite(inv).all():
+        raise ValueError(f"{what}: the inverse of the {name} is not finite: {m.tolist()}")
+    return tuple(float(v) for v in inv[:2].reshape(-1))
+
+
+def lucid_sample(frame: torch.Tensor, background: torch.Tensor, mask: torch.Tensor, flip: bool, matrix_bg, matrix_fg, gain,
+                 bias, img_lut: torch.Tensor, gt_lut: torch.Tensor, image: torch.Tensor, gt: torch.Tensor) -> None:
+    """fosvos_lucid_sample: uint8 frame, background [H,W,3] (the frame with the object painted out) and mask [H,W] -> image
+    [1,3,H,W] / gt [1,1,H,W] (fp32, written in place): the object under ``matrix_fg`` composed over the background under
+    ``matrix_bg`` (2x3, SOURCE -> DESTINATION, inverted here as warp_sample inverts its matrix), then ``* gain[c] + bias[c]``;
+    bit for bit dataloaders/lucid.compose.  ``matrix_fg=None`` is no object: the warped background alone and gt = 0.
+    ``gain`` / ``bias``: three finite numbers each, taken as float32.  img_lut fp32 [256,3], gt_lut fp32 [256].  One launch."""
+    import numpy as np
+    what = "lucid_sample"
+    _need(frame, torch.uint8, "lucid_sample frame")
+    _need(background, torch.uint8, "lucid_sample background")
+    _need(mask, torch.uint8, "lucid_sample mask")
+    _need(img_lut, _F32, "lucid_sample img_lut")
+    _need(gt_lut, _F32, "lucid_sample gt_lut")
+    _need(image, _F32, "lucid_sample image")
+    _need(gt, _F32, "lucid_sample gt")
+    if frame.dim() != 3 or frame.shape[2] != 3:
+        raise ValueError(f"{what}: frame must be [H,W,3], got {tuple(frame.shape)}")
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    limits.check_int(what, "H", h, 1, limits.MAX_FRAME_SIDE)
+    limits.check_int(what, "W", w, 1, limits.MAX_FRAME_SIDE)
+    if tuple(background.shape) != (h, w, 3):
+        raise ValueError(f"{what}: background {tuple(background.shape)} does not match the frame's {(h, w, 3)}")
+    if tuple(mask.shape) != (h, w):
+        raise ValueError(f"{what}: mask {tuple(mask.shape)} does not match the frame's {(h, w)}")
+    if tuple(img_lut.shape) != (256, 3) or tuple(gt_lut.shape) != (256,):
+        raise ValueError(f"{what}: img_lut must be [256,3] and gt_lut [256]")
+    if tuple(image.shape) != (1, 3, h, w):
+        raise ValueError(f"{what}: the composition keeps the size: image must be [1,3,{h},{w}], got {tuple(image.shape)}")
+    if tuple(gt.shape) != (1, 1, h, w):
+        raise ValueError(f"{what}: gt must be [1,1,{h},{w}], got {tuple(gt.shape)}")
+    inv_bg = _inverse_2x3(what, "matrix_bg", matrix_bg)
+    inv_fg = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0) if matrix_fg is None else _inverse_2x3(what, "matrix_fg", matrix_fg)
+    scalars = []
+    for name, v in (("gain", gain), ("bias", bias)):
+        try:
+            a = np.array(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.shape != (3,) or not (np.abs(a) <= np.finfo(np.float32).max).all():  # (a NaN compares False)
+            raise ValueError(f"{what}: {name} must be three finite float32 numbers, got {v!r}")
+        scalars += [float(x) for x in a.astype(np.float32)]
+    _same_device(what, frame, background, mask, img_lut, gt_lut, image, gt)
+    _launch(what, frame, frame.data_ptr(), background.data_ptr(), mask.data_ptr(), h, w, 1 if flip else 0, *inv_bg, *inv_fg,
+            0 if matrix_fg is None else 1, *scalars, img_lut.data_ptr(), gt_lut.data_ptr(), image.data_ptr(), gt.data_ptr(),
+            nbytes=float(49 * h * w + 4 * (image.numel() + gt.numel())))
 
 
 # ------------------------------------------------------------------------------------------ shared argument checks

@@ -5,8 +5,9 @@ The table of all of them is in DESIGN.md (section 2).  CleanOptions (mask cleani
 passed and has no environment switch; so are AdaptOptions (online adaptation of the test pass), RoiOptions
 and RefineOptions (following the object and edge-aware upsampling in a stream, DESIGN.md sections 12.2 and 12.3),
 RotateOptions (rotating and zooming the training sample), EnsembleOptions (the test-time ensemble of the
-test pass), CrfOptions (the CRF on the frame behind the test pass) and MotionOptions
-(the temporal gate's seed carried along the picture's motion).
+test pass), CrfOptions (the CRF on the frame behind the test pass), MotionOptions
+(the temporal gate's seed carried along the picture's motion) and LucidOptions (the one-shot sample with the
+object moved against its background).
 
 No torch and no library load here: importable anywhere.  The ranges and the scalar checks are ``limits``'.
 """
@@ -407,6 +408,56 @@ class MotionOptions:
 
     def as_dict(self) -> dict:
         return {'block': self.block, 'search': self.search, 'zero_bias': self.zero_bias}
+
+
+@dataclass(frozen=True)
+class LucidOptions:
+    """Moving the object against its background in the one-shot training sample (``ResidentOneShotLoader(lucid=)``,
+    ``get_data_loader_train(lucid=)``, ``ops.lucid_sample``; dataloaders/lucid.py states the rules): per
+    draw the background and the object are rotated, zoomed and (the object) shifted independently, the illumination is changed
+    and the two are composed again.  Every range is ``(lo, hi)`` with lo <= hi; a draw is lo + (hi - lo) u.  Opt-in by being
+    passed; this class reads no environment variable.  The defaults are the design's and are unmeasured on real sequences."""
+
+    # the background about the frame's centre: degrees in [-360, 360], zoom factors in [1/16, 16]
+    bg_rots: tuple = (-10.0, 10.0)
+    bg_scales: tuple = (1.0, 1.2)
+    # the object about the centre of its box: degrees, zoom factors, and a shift in box widths / heights in [-4, 4]
+    fg_rots: tuple = (-15.0, 15.0)
+    fg_scales: tuple = (0.85, 1.15)
+    fg_shift: tuple = (-0.15, 0.15)
+    # the illumination: out * (contrast * tint_c) + brightness; factors in [1/16, 16], grey levels in [-255, 255]
+    contrast: tuple = (0.85, 1.15)
+    tint: tuple = (0.95, 1.05)
+    brightness: tuple = (-15.0, 15.0)
+    # the painted-out background: the hole is the mask grown by `dilate` pixels (0..31), the fill smoothed `smooth` times (0..16)
+    dilate: int = 5
+    smooth: int = 2
+
+    def __post_init__(self) -> None:
+        angle = (-limits.ROTATE_MAX_ANGLE, limits.ROTATE_MAX_ANGLE)
+        for name, (lo, hi) in (("bg_rots", angle), ("bg_scales", limits.ROTATE_SCALE_RANGE), ("fg_rots", angle),
+                               ("fg_scales", limits.ROTATE_SCALE_RANGE),
+                               ("fg_shift", (-limits.LUCID_MAX_SHIFT, limits.LUCID_MAX_SHIFT)),
+                               ("contrast", limits.LUCID_GAIN_RANGE), ("tint", limits.LUCID_GAIN_RANGE),
+                               ("brightness", (-limits.LUCID_MAX_BRIGHTNESS, limits.LUCID_MAX_BRIGHTNESS))):
+            v = getattr(self, name)
+            if type(v) not in (tuple, list) or len(v) != 2:
+                raise ValueError(f"LucidOptions: {name} must be a range (lo, hi), got {v!r}")
+            object.__setattr__(self, name, tuple(v))
+            for x in v:
+                limits.check_real("LucidOptions", name, x, lo, hi)
+            if v[0] > v[1]:
+                raise ValueError(f"LucidOptions: {name} must be (lo, hi) with lo <= hi, got {v!r}")
+        limits.check_int("LucidOptions", "dilate", self.dilate, 0, limits.LUCID_MAX_DILATE)
+        limits.check_int("LucidOptions", "smooth", self.smooth, 0, limits.LUCID_MAX_SMOOTH)
+
+    def dream(self):
+        """The ``lucid.LucidDream`` these options describe."""
+        from dataloaders import lucid
+        return lucid.LucidDream(self)
+
+    def as_dict(self) -> dict:
+        return {name: (list(v) if isinstance(v, tuple) else v) for name, v in self.__dict__.items()}
 
 
 def native_loop_from_env(environ: Mapping[str, str] = os.environ) -> bool:

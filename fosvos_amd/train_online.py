@@ -48,6 +48,7 @@ device_decode = False       # --device-decode: the test pass's JPEG frames are d
 multi_object = False        # --multi-object: one net per object, merged and scored on the device (train_and_test_objects)
 clean = None                # --clean-min-area / --clean-largest / --clean-temporal (with --fast-test): a CleanOptions
 rotate = None               # --augment-rotate (and its options): a RotateOptions; the one-shot loaders rotate and zoom the sample
+lucid = None                # --augment-lucid (and --lucid-*): a LucidOptions; the one-shot loaders move the object against its background
 adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
 ensemble = None             # --ensemble-flip / --ensemble-scales (with --fast-test or --multi-object): an EnsembleOptions
 crf = None                  # --crf (and --crf-*; with --fast-test or --multi-object): a CrfOptions
@@ -84,10 +85,15 @@ def _clean_seed(train_seed, annotations, data_loader, seq_name: str) -> Optional
     return None
 
 
+def _augment_kwargs() -> dict:
+    """``rotate`` / ``lucid`` for a training loader, each passed only when set (absent: the call is what it was)."""
+    return {name: v for name, v in (('rotate', rotate), ('lucid', lucid)) if v is not None}
+
+
 def _train_loader(seq_name: str, settings: OnlineSettings):
-    """The training loader of a sequence run; ``rotate`` is passed only when set (absent: the call is what it was)."""
+    """The training loader of a sequence run."""
     return io_helper.get_data_loader_train(db_root_dir, settings.batch_size_train, seq_name, synthetic=synthetic_size,
-                                           **({} if rotate is None else {'rotate': rotate}))
+                                           **_augment_kwargs())
 
 
 def _first_sample(data_loader) -> dict:
@@ -204,7 +210,7 @@ def _object_loaders(seq_name: str, object_id: int, settings: OnlineSettings, n_o
     from torch.utils.data import DataLoader
     train = ResidentOneShotLoader(DAVIS2017(mode='train', db_root_dir=str(db_root_dir), seq_name=seq_name,
                                             object_id=object_id, transform=None),
-                                  **({} if rotate is None else {'rotate': rotate}))
+                                  **_augment_kwargs())
     test = DataLoader(DAVIS2017(mode='test', db_root_dir=str(db_root_dir), seq_name=seq_name, object_id=object_id,
                                 transform=custom_transforms.ToTensor()),
                       batch_size=settings.batch_size_test, shuffle=False, num_workers=2)
@@ -602,7 +608,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean, adapt, rotate, ensemble, crf, motion
+    global multi_object, synthetic_objects, clean, adapt, rotate, lucid, ensemble, crf, motion
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -620,6 +626,7 @@ def main(argv=None):
                              temporal_radius=args.clean_temporal)
     adapt = args.adapt
     rotate = args.rotate
+    lucid = args.lucid
     ensemble = args.ensemble
     crf = args.crf_options
     motion = args.motion

@@ -3,7 +3,8 @@
 Same flag names and meanings.  The reference declares ``type=Optional[str]`` for -s/-sg/-sgs, which
 argparse cannot call; the intended types are used here.  Extensions (not in the
 reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/--width, --parent-model,
---data-parallel, --augment-rotate with --rotate-range / --zoom-range / --rotate-renormalize, --resident-train-set and
+--data-parallel, --augment-rotate with --rotate-range / --zoom-range / --rotate-renormalize, --augment-lucid with its --lucid-*
+options (refused offline with the reason), --resident-train-set and
 --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
 --multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal, --adapt-steps with its --adapt-* options,
 --ensemble-flip and --ensemble-scales, --crf with its --crf-* options, --clean-motion with its --motion-* options (online
@@ -46,6 +47,63 @@ def _get_base_parser() -> argparse.ArgumentParser:
                         help='with --augment-rotate: the reference\'s renormalisation of the warped frame to [0, 1] (off by '
                              'default: the nets are trained on mean-subtracted frames)')
     return parser
+
+
+# the range options of --augment-lucid: flag suffix -> (LucidOptions field, what it is)
+_LUCID_RANGES = (('bg-rotate', 'bg_rots', 'the background\'s angle about the frame\'s centre, in degrees'),
+                 ('bg-zoom', 'bg_scales', 'the background\'s zoom factor'),
+                 ('fg-rotate', 'fg_rots', 'the object\'s angle about the centre of its box, in degrees'),
+                 ('fg-zoom', 'fg_scales', 'the object\'s zoom factor'),
+                 ('fg-shift', 'fg_shift', 'the object\'s shift, in widths / heights of its box'),
+                 ('contrast', 'contrast', 'the factor on every channel'),
+                 ('tint', 'tint', 'the further factor of each channel'),
+                 ('brightness', 'brightness', 'what is added to every channel, in grey levels'))
+_LUCID_COUNTS = (('dilate', 'the object is painted out with a margin of D pixels (0..31)'),
+                 ('smooth', 'smoothing passes over the painted-out hole (0..16)'))
+
+
+def add_lucid_arguments(parser: argparse.ArgumentParser) -> None:
+    """--augment-lucid and its options (the online command line)."""
+    from fosvos_hip.options import LucidOptions
+    defaults = LucidOptions()
+    parser.add_argument('--augment-lucid', action='store_true',
+                        help='one-shot augmentation that moves the object against its background (after Lucid Data Dreaming): '
+                             'per draw the painted-out background and the object are rotated, zoomed and shifted '
+                             'independently, the illumination is changed and the two are composed again on the GPU, in place '
+                             'of the rescale (dataloaders/lucid.py)')
+    for suffix, field, what in _LUCID_RANGES:
+        parser.add_argument('--lucid-' + suffix, type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                            help='with --augment-lucid: {}, drawn from [LO, HI] (default {:g} {:g})'.format(
+                                what, *getattr(defaults, field)))
+    for name, what in _LUCID_COUNTS:
+        parser.add_argument('--lucid-' + name, type=int, default=None, metavar=name[0].upper(),
+                            help='with --augment-lucid: {} (default {})'.format(what, getattr(defaults, name)))
+
+
+def lucid_of(parser: argparse.ArgumentParser, args, is_online: bool):
+    """The LucidOptions of --augment-lucid / --lucid-*, or None; what cannot be combined is refused with the reason."""
+    fields = {field: getattr(args, 'lucid_' + suffix.replace('-', '_')) for suffix, field, _ in _LUCID_RANGES}
+    fields.update({name: getattr(args, 'lucid_' + name) for name, _ in _LUCID_COUNTS})
+    flags = {field: '--lucid-' + suffix for suffix, field, _ in _LUCID_RANGES}
+    given = [flags.get(name, '--lucid-' + name) for name, v in fields.items() if v is not None]
+    if not args.augment_lucid:
+        if given:
+            parser.error('{} set(s) an option of the lucid augmentation: it needs --augment-lucid'.format(' / '.join(given)))
+        return None
+    if not is_online:
+        parser.error('--augment-lucid is built for the one-shot sample of train_online.py: the offline training set would '
+                     'need a filled background per training frame')
+    if args.augment_rotate:
+        parser.error('--augment-lucid and --augment-rotate both stand in place of the rescale: give one of them')
+    if args.synthetic:
+        parser.error('--augment-lucid augments DAVIS samples: the loader of --synthetic augments nothing')
+    if args.data_parallel:
+        parser.error('--augment-lucid is not wired to the sharded loaders of --data-parallel')
+    try:
+        from fosvos_hip.options import LucidOptions
+        return LucidOptions(**{name: (tuple(v) if isinstance(v, list) else v) for name, v in fields.items() if v is not None})
+    except ValueError as err:
+        parser.error(str(err).replace('LucidOptions: ', '--lucid-*: '))
 
 
 def _rotate_options(parser: argparse.ArgumentParser, args: argparse.Namespace):
@@ -190,8 +248,10 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                             help='run the one-frame minibatches of an accumulation cycle as batched passes of up to N '
                                  'frames of one shape (every frame keeps the class weights of its own label; 1 = one '
                                  'minibatch per pass, the reference\'s order)')
+    add_lucid_arguments(parser)
     args = parser.parse_args(argv)
     args.rotate = _rotate_options(parser, args)
+    args.lucid = lucid_of(parser, args, is_online)
     if not is_online and args.microbatch_group < 1:
         parser.error('--microbatch-group counts frames per pass: at least 1')
     if not is_online and args.microbatch_group > 1 and args.data_parallel:

@@ -55,7 +55,7 @@ def results_dir(root: Path, name: str, stage: str, variant_offline, variant_onli
 def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] = None,
                           synthetic: Optional[Tuple[int, int]] = None,
                           shard: Optional[Tuple[int, int]] = None, resident: bool = True,
-                          resident_set: bool = False, rotate=None) -> DataLoader:
+                          resident_set: bool = False, rotate=None, lucid=None) -> DataLoader:
     """shard = (rank, world): this process draws its own 1/world of every epoch (data-parallel OFFLINE training, where
     the ranks split each iteration's batch); None: the reference's single-process loader.
     resident: a sequence run (``seq_name``: ONE training sample, src/dataloaders/davis_2016.py:72-83) gets the loader that
@@ -69,7 +69,24 @@ def get_data_loader_train(db_root_dir, batch_size: int, seq_name: Optional[str] 
     rotate (opt-in): a fosvos_hip.options.RotateOptions.  ``ScaleNRotate(rots, scales, renormalize)`` stands in place of
     ``Resize``, as in the reference's commented line; the DataLoader below then warps in numpy on the host (about 0.16 s for
     a 480x854 sample) and is the yardstick the resident loaders replay with one HIP launch per draw.  The synthetic loader
-    augments nothing and refuses it."""
+    augments nothing and refuses it.
+    lucid (opt-in): a fosvos_hip.options.LucidOptions - the object moves against its background (dataloaders/lucid.py).  Only
+    the resident one-shot loader composes it (one HIP launch per draw); every other loader, ``rotate`` beside it and the
+    synthetic loader are refused."""
+    if lucid is not None:
+        if synthetic is not None:
+            raise ValueError('get_data_loader_train: lucid augments DAVIS samples; the synthetic loader augments nothing')
+        if rotate is not None:
+            raise ValueError('get_data_loader_train: rotate and lucid both stand in place of the rescale: pass one of them')
+        if seq_name is None:
+            raise ValueError('get_data_loader_train: lucid is built for the one-shot sample of a sequence run; the offline '
+                             'training set would need a filled background per training frame')
+        if not (resident and shard is None and batch_size == 1):
+            raise ValueError('get_data_loader_train: lucid composes from the bytes the resident one-shot loader keeps on the '
+                             'device (resident=True, no shard, batch_size 1); the host DataLoader has none to fill from')
+        from dataloaders.resident import ResidentOneShotLoader
+        return ResidentOneShotLoader(DAVIS2016(mode='train', db_root_dir=str(db_root_dir), transform=None, seq_name=seq_name),
+                                     lucid=lucid)
     if synthetic is not None:
         if rotate is not None:
             raise ValueError('get_data_loader_train: rotate augments DAVIS samples; the synthetic loader augments nothing')

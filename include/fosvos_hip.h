@@ -448,6 +448,27 @@ int fosvos_warp_sample(const uint8_t *frame, const uint8_t *mask, int H, int W, 
                        double i10, double i11, double i12, const float *img_lut, const float *gt_lut, float *image,
                        float *gt, int renormalize, void *workspace, size_t workspace_bytes, int device, void *stream);
 size_t fosvos_warp_workspace_bytes(int H, int W); /* 0 for sizes fosvos_warp_sample refuses */
+/* fosvos_lucid_sample: the same sample with the object moved against its background (opt-in; csrc/lucid.hip), bit for bit
+ * dataloaders/lucid.py: compose.  ONE launch on `stream`; no workspace, no atomics, no workgroup waits for another.
+ *   frame, background  u8 [H,W,3] (background: the frame with the object painted out, lucid.fill_background); mask u8 [H,W];
+ *                all three at any byte alignment, mirrored first if `flip`
+ *   b00 .. b12   the INVERSE 2x3 matrix of the background (destination -> source) in fp64, f00 .. f12 that of the object;
+ *                coordinates as in fosvos_warp_sample.  fg_on == 0: no object - alpha = 0 and gt = 0 everywhere, and frame, mask
+ *                and f00 .. f12 are not read
+ *   gt           nearest (rint, half to even) through the object's matrix, the table value of the mask byte there or 0
+ *   alpha        the four bilinear taps of `mask != 0` through the object's matrix (fractions and weights 1 - f, f in fp32,
+ *                row-outer / column-inner, acc = acc + val * (wy[j] * wx[i]) from +0.0, 0 outside); exactly 1 where all four
+ *                taps lie inside the frame and on the object
+ *   image        B where alpha == 0, Fg where alpha == 1, else B + alpha * (Fg - B), each operation rounded in fp32; then
+ *                * gain[c] + bias[c] (two roundings).  B / Fg: fosvos_warp_sample's bicubic gather of background / frame under
+ *                its matrix; B is gathered only where alpha != 1, Fg only where alpha != 0.  image fp32 [3,H,W], gt fp32 [H,W]
+ * Refused: H or W above 8192, a non-finite coefficient, gain or bias, a matrix that sends one of the four output corners
+ * beyond +-2^30.  Every tap's address is clamped into the frame before the load. */
+int fosvos_lucid_sample(const uint8_t *frame, const uint8_t *background, const uint8_t *mask, int H, int W, int flip, double b00,
+                        double b01, double b02, double b10, double b11, double b12, double f00, double f01, double f02,
+                        double f10, double f11, double f12, int fg_on, float gain0, float gain1, float gain2, float bias0,
+                        float bias1, float bias2, const float *img_lut, const float *gt_lut, float *image, float *gt, int device,
+                        void *stream);
 
 /* ---- scoring a segmented sequence (DAVIS 2016 J and F) and its PNG bytes ------------------------------------------
  * The reference writes probability PNGs and leaves the measures to an outside toolkit (src/eval/README.md); these two
