@@ -286,6 +286,10 @@ SIGNATURES = {
     "fosvos_crf_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, POINTER(c_float), c_void_p, c_void_p, c_size_t, c_int,
                                   c_void_p]),
+    "fosvos_crf_labels_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fosvos_crf_labels": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, POINTER(c_float), c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_int, c_void_p]),
     "fosvos_motion_luma": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fosvos_motion_estimate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                        c_void_p]),

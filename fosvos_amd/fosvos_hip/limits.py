@@ -24,7 +24,8 @@ FILL_RANGE = (-3.4028234663852886e38, 0.0)  # [lowest finite float32, 0)
 GUIDED_MAX_RADIUS = 8
 GUIDED_EPS_RANGE = (1e-3, 1e9)
 GUIDED_MAX_CLIP = 1e4
-# a scaled call's frames (util/frame_resample.MAX_SIDE), the nets of a sequence (util/object_merge.MAX_OBJECTS)
+# a scaled call's frames (util/frame_resample.MAX_SIDE), the nets of a sequence (util/object_merge.MAX_OBJECTS; the joint CRF
+# of util/label_crf.py has the same K and one label more)
 MAX_FRAME_SIDE = 8192
 MAX_OBJECTS = 16
 # the boundary tolerance of the F measure, the JPEG encoder

@@ -1657,27 +1657,22 @@ CRF_MAX_ITERATIONS = limits.CRF_MAX_ITERATIONS  # util/mask_crf.MAX_ITERATIONS
 _CRF_TABLES = {}  # (CrfOptions, device index) -> the fp64 table vector on that device
 
 
-def _crf_tables(options, device: torch.device) -> torch.Tensor:
-    """``mask_crf.tables(options)`` on ``device``, made and uploaded at the first call with these options (the one moment a
-    ``crf_refine`` call waits for the host copy) and kept."""
+def _crf_tables(options, device: torch.device, labels: bool = False) -> torch.Tensor:
+    """``mask_crf.tables(options)`` - ``labels``: ``label_crf.tables(options)``, under a key of its own - on ``device``, made
+    and uploaded at the first call with these options (the one moment a ``crf_refine`` / ``crf_labels`` call waits for the host
+    copy) and kept."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (options, idx)
+    key = (options, idx, "labels") if labels else (options, idx)
     tab = _CRF_TABLES.get(key)
     if tab is None:
-        from util import mask_crf
-        tab = _CRF_TABLES[key] = torch.from_numpy(mask_crf.tables(options)).to(device)
+        from util import label_crf, mask_crf
+        tab = _CRF_TABLES[key] = torch.from_numpy((label_crf if labels else mask_crf).tables(options)).to(device)
     return tab
 
 
-def crf_refine(image: torch.Tensor, logits: torch.Tensor, options=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fosvos_crf_refine: the net's input fp32 [N,3,H,W] (the frame minus MEANVAL) and logits fp32 [N,1,H,W] -> fp32 [N,1,H,W],
-    the logits after ``options.iterations`` mean-field iterations of the local CRF whose guide is the frame's bytes
-    (``mask_crf.refine(image[k], logits[k, 0], options)`` of every frame, bit for bit).  ``options``: a
-    ``fosvos_hip.options.CrfOptions`` (None: its defaults).  ``out`` must not overlap the image or the logits.  The table
-    vector (``mask_crf.tables(options)``) is kept on the device per (options, device).  ``options.iterations`` launches on the
-    current stream, no synchronisation; z^t lives in the stream's workspace."""
+def _crf_frames(what: str, image: torch.Tensor, options):
+    """The checks ``crf_refine`` and ``crf_labels`` share: (the options, N, H, W) of the net's input fp32 [N,3,H,W]."""
     from .options import CrfOptions
-    what = "crf_refine"
     if options is None:
         options = CrfOptions()
     if not isinstance(options, CrfOptions):
@@ -1688,6 +1683,18 @@ def crf_refine(image: torch.Tensor, logits: torch.Tensor, options=None, out: Opt
     n, h, w = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
     if h > MAX_FRAME_SIDE or w > MAX_FRAME_SIDE:
         raise ValueError(f"{what}: maps may have sides of up to {MAX_FRAME_SIDE}, got {(h, w)}")
+    return options, n, h, w
+
+
+def crf_refine(image: torch.Tensor, logits: torch.Tensor, options=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_crf_refine: the net's input fp32 [N,3,H,W] (the frame minus MEANVAL) and logits fp32 [N,1,H,W] -> fp32 [N,1,H,W],
+    the logits after ``options.iterations`` mean-field iterations of the local CRF whose guide is the frame's bytes
+    (``mask_crf.refine(image[k], logits[k, 0], options)`` of every frame, bit for bit).  ``options``: a
+    ``fosvos_hip.options.CrfOptions`` (None: its defaults).  ``out`` must not overlap the image or the logits.  The table
+    vector (``mask_crf.tables(options)``) is kept on the device per (options, device).  ``options.iterations`` launches on the
+    current stream, no synchronisation; z^t lives in the stream's workspace."""
+    what = "crf_refine"
+    options, n, h, w = _crf_frames(what, image, options)
     _need(logits, _F32, f"{what} logits", ValueError)
     if tuple(logits.shape) != (n, 1, h, w):
         raise ValueError(f"{what}: logits must be {(n, 1, h, w)}, got {tuple(logits.shape)}")
@@ -1702,6 +1709,38 @@ def crf_refine(image: torch.Tensor, logits: torch.Tensor, options=None, out: Opt
     _launch(what, image, image.data_ptr(), logits.data_ptr(), tab.data_ptr(), n, h, w, options.iterations, options.radius,
             float(options.weight_appearance), float(options.weight_smooth), float(options.clip), _mean_bgr(), out.data_ptr(), ws,
             wsn, flops=9.0 * window * options.iterations * n * h * w, nbytes=(16.0 * options.iterations + 4.0) * n * h * w)
+    return out
+
+
+def crf_labels(image: torch.Tensor, logits: Sequence[torch.Tensor], options=None, out: Optional[torch.Tensor] = None,
+               scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fosvos_crf_labels: the net's input fp32 [N,3,H,W] and the logits fp32 [N,1,H,W] of K per-object nets (1 <= K <=
+    ``MAX_OBJECTS``) -> labels uint8 [N,H,W]: ONE mean-field CRF over the labels 0..K whose guide is the frame's bytes, in the
+    place of K ``crf_refine`` calls and ``merge_objects`` (``label_crf.refine_labels_batch(image, logits, options)``, bit for
+    bit).  ``scores``: None, or an fp32 [N,K+1,H,W] tensor that takes ``float32(z^T)``.  The K pointers travel by value:
+    nothing is concatenated.  ``out`` and ``scores`` may be views of a caller's buffer and must not overlap an input.  The table
+    vector (``label_crf.tables(options)``) is kept on the device per (options, device), beside ``crf_refine``'s.
+    ``options.iterations`` launches on the current stream, no synchronisation; z^t lives in the stream's workspace, 16 (K + 1)
+    N H W bytes, which grows to that (557 MB at K = 16, five frames of 480x854): the batch is not walked in sub-batches."""
+    what = "crf_labels"
+    options, n, h, w = _crf_frames(what, image, options)
+    logits, _, table = _logit_table(logits, what, (n, 1, h, w))
+    k = len(logits)
+    _same_device(what, image, *logits)
+    given = [t for t in (out, scores) if t is not None]
+    out = _out_like(out, (n, h, w), torch.uint8, image, what)
+    if scores is not None:
+        scores = _out_like(scores, (n, k + 1, h, w), _F32, image, what, "scores")
+    if any(_overlap(t, x) for t in given for x in [image] + logits) or (len(given) == 2 and _overlap(out, scores)):
+        raise ValueError(f"{what}: out and scores must not overlap the image, the logits or each other")
+    tab = _crf_tables(options, image.device, labels=True)
+    ws, wsn = _WS.get(int(lib().fosvos_crf_labels_workspace_bytes(n, k, h, w)), image.device)
+    window = (2 * options.radius + 1) ** 2 - 1
+    chunks = -(-(k + 1) // 4)
+    _launch(what, image, image.data_ptr(), table, k, tab.data_ptr(), n, h, w, options.iterations, options.radius,
+            float(options.weight_appearance), float(options.weight_smooth), float(options.clip), _mean_bgr(), out.data_ptr(),
+            _p(scores), ws, wsn, flops=(5.0 * chunks + 4.0 * (k + 1)) * window * options.iterations * n * h * w,
+            nbytes=(16.0 * (k + 1) * options.iterations + 4.0 * k + 1.0) * n * h * w)
     return out
 
 

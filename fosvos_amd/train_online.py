@@ -52,6 +52,7 @@ lucid = None                # --augment-lucid (and --lucid-*): a LucidOptions; t
 adapt = None                # --adapt-steps (and --adapt-*): an AdaptOptions; the test pass is experiment_helper.test_adaptive
 ensemble = None             # --ensemble-flip / --ensemble-scales (with --fast-test or --multi-object): an EnsembleOptions
 crf = None                  # --crf (and --crf-*; with --fast-test or --multi-object): a CrfOptions
+crf_joint = False           # --crf-joint (with --crf and --multi-object): ONE joint CRF over the labels in test_objects
 motion = None               # --clean-motion (and --motion-*; with --clean-temporal): a MotionOptions
 synthetic_objects = 2       # --objects: the objects of the synthetic sequence under --multi-object
 scored_sequences = []       # the score of every sequence of this run, in order
@@ -251,7 +252,8 @@ def train_and_test_objects(make_provider, seq_name: str, settings: OnlineSetting
     result = experiment_helper.test_objects(providers, test_loader, save_dir, annotations if score else None,
                                             seq_name=seq_name, png_huffman='fitted' if png_fitted else 'fixed',
                                             **({} if ensemble is None else {'ensemble': ensemble}),
-                                            **({} if crf is None else {'crf': crf}))
+                                            **({} if crf is None else {'crf': crf}),
+                                            **({'crf_joint': True} if crf_joint else {}))
     _report_score(result, save_dir, seq_name)
     return result
 
@@ -608,7 +610,7 @@ def _train(net_provider: NetworkProvider, dataloader, optimizer: optim.SGD, summ
 
 def main(argv=None):
     global db_root_dir, synthetic_size, data_parallel, save_dir_models, save_dir_results, score, fast_test, png_fitted, device_decode
-    global multi_object, synthetic_objects, clean, adapt, rotate, lucid, ensemble, crf, motion
+    global multi_object, synthetic_objects, clean, adapt, rotate, lucid, ensemble, crf, crf_joint, motion
     args = args_helper.parse_args(is_online=True, argv=argv)
     if args.score and args.eval_speeds:
         raise SystemExit('--score needs the PNG-writing test pass; --eval-speeds writes nothing')
@@ -629,6 +631,7 @@ def main(argv=None):
     lucid = args.lucid
     ensemble = args.ensemble
     crf = args.crf_options
+    crf_joint = bool(args.crf_joint)
     motion = args.motion
     synthetic_objects = int(args.objects)
     del scored_sequences[:]

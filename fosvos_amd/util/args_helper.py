@@ -7,8 +7,8 @@ reference, all optional): --n-epochs, --avg-grad-every-n, --synthetic, --height/
 options (refused offline with the reason), --resident-train-set and
 --microbatch-group (offline only), --score, --fast-test, --png-fitted, --device-decode,
 --multi-object, --objects, --clean-min-area, --clean-largest, --clean-temporal, --adapt-steps with its --adapt-* options,
---ensemble-flip and --ensemble-scales, --crf with its --crf-* options, --clean-motion with its --motion-* options (online
-only).
+--ensemble-flip and --ensemble-scales, --crf with its --crf-* options and --crf-joint, --clean-motion with its --motion-*
+options (online only).
 """
 import argparse
 from typing import List, Optional
@@ -222,6 +222,9 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
                             help='with --fast-test or --multi-object: refine the logits with a local CRF on the frame\'s '
                                  'colours on the device (mean-field over a window; util/mask_crf.py), before cleaning, merging, '
                                  'scoring and the PNG files')
+        parser.add_argument('--crf-joint', action='store_true',
+                            help='with --crf and --multi-object: ONE joint CRF over the labels 0..K (util/label_crf.py) in the '
+                                 'place of a CRF per net and the label merge: the objects compete at every pixel')
         parser.add_argument('--crf-iterations', type=int, default=None, metavar='N',
                             help='with --crf: mean-field iterations (1..10; default 5)')
         parser.add_argument('--crf-radius', type=int, default=None, metavar='R',
@@ -351,6 +354,11 @@ def parse_args(is_online: bool, argv: Optional[List[str]] = None) -> argparse.Na
         given = ['--crf-' + name.replace('_', '-') for name, v in fields.items() if v is not None]
         if given and not args.crf:
             parser.error('{} set(s) an option of the CRF: it needs --crf'.format(' / '.join(given)))
+        if args.crf_joint and not args.crf:
+            parser.error('--crf-joint is the joint form of the CRF: it needs --crf')
+        if args.crf_joint and not args.multi_object:
+            parser.error('--crf-joint lets the objects of a frame compete: it needs --multi-object (the single-object pass of '
+                         '--fast-test has one object)')
         if args.crf:
             if not args.fast_test and not args.multi_object:
                 parser.error('--crf refines the logits of the device test pass: it needs --fast-test or --multi-object')

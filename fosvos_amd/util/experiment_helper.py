@@ -20,7 +20,8 @@ takes fine-tune steps against pseudo-labels made from its own output on the devi
 ``test_fast`` and ``test_objects`` take ``ensemble=`` (``--ensemble-flip``, ``--ensemble-scales``): the net also sees every frame
 mirrored and at other sizes, and the device averages its answers back on the frame's grid (util/test_ensemble.py states it).
 They also take ``crf=`` (``--crf``): a local CRF on the frame's colours refines the logits on the device before anything else
-reads them (util/mask_crf.py states it).  ``test_fast`` takes ``motion=`` (``--clean-motion``) beside a temporal gate: the
+reads them (util/mask_crf.py states it); ``test_objects`` with ``crf_joint=True`` (``--crf-joint``) runs ONE CRF over the labels
+0..K in the place of a CRF per net and the label merge (util/label_crf.py states it).  ``test_fast`` takes ``motion=`` (``--clean-motion``) beside a temporal gate: the
 gate's seed is carried along the motion of the picture, estimated by block matching on the device (util/block_motion.py
 states it)."""
 import timeit
@@ -302,7 +303,18 @@ def _crf_logits(inputs: torch.Tensor, logits: torch.Tensor, crf) -> torch.Tensor
         from fosvos_hip import ops
         return ops.crf_refine(inputs.float().contiguous(), logits, crf)
     from util import mask_crf
-    return torch.from_numpy(mask_crf.refine_batch(inputs.float().contiguous().numpy(), logits.numpy(), crf))
+    return torch.from_numpy(mask_crf.refine_batch(inputs.float().cpu().contiguous().numpy(), logits.numpy(), crf))
+
+
+def _crf_joint_labels(inputs: torch.Tensor, logits, crf):
+    """A group's label maps uint8 [n,H,W] from the K nets' logits fp32 [n,1,H,W] by the joint CRF on the group's uploaded
+    frames ``inputs``: ONE ``ops.crf_labels`` on the device (a tensor), ``label_crf.refine_labels_batch`` for CPU logits (an
+    array; the frames come to the host if they were uploaded).  No host synchronisation on the device path."""
+    if logits[0].is_cuda:
+        from fosvos_hip import ops
+        return ops.crf_labels(inputs.float().contiguous(), logits, crf)
+    from util import label_crf
+    return label_crf.refine_labels_batch(inputs.float().cpu().contiguous().numpy(), [x.numpy() for x in logits], crf)[0]
 
 
 def _check_motion(who: str, motion, clean) -> None:
@@ -815,7 +827,7 @@ def test_adaptive(net_provider, data_loader, save_dir: Path, first_sample, adapt
 
 def test_objects(net_providers, data_loader, save_dir: Path, annotations: Optional[Callable] = None, group: int = 5,
                  seq_name: Optional[str] = None, forward_batch: int = 2, png_huffman: str = 'fixed',
-                 palette=None, ensemble=None, crf=None) -> Optional[dict]:
+                 palette=None, ensemble=None, crf=None, crf_joint: bool = False) -> Optional[dict]:
     """The test pass of a sequence with several objects: ``net_providers[k - 1]`` holds the net fine-tuned on object k
     against everything else.  ``test_fast``'s structure - groups of up to ``group`` frames uploaded once, ``forward_batch``
     frames a forward call, two buffer slots, ONE copy per group of files plus lengths, the host writing the previous group's
@@ -835,13 +847,21 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
     (``ops.ensemble_merge``) before ``ops.merge_objects`` sees them.  The score dict then holds the options under
     'ensemble'.
     ``crf`` (a CrfOptions; None: nothing changes): the CRF of ``test_fast``, per net: each net's logits - merged behind an
-    ensemble - go through ONE ``ops.crf_refine`` on the group's uploaded frames before ``ops.merge_objects`` sees them (a joint
-    CRF over the K labels is not built).  The score dict then holds the options under 'crf'."""
+    ensemble - go through ONE ``ops.crf_refine`` on the group's uploaded frames before ``ops.merge_objects`` sees them.  The
+    score dict then holds the options under 'crf'.
+    ``crf_joint`` (needs ``crf``; False: nothing changes): per group the K nets' logits - merged behind an ensemble - go through
+    ONE ``ops.crf_labels`` on the group's uploaded frames, a joint CRF over the labels 0..K (util/label_crf.py states it; CPU
+    tensors: ``label_crf.refine_labels_batch``), in the place of the K ``crf_refine`` calls AND of ``merge_objects``.  No host
+    synchronisation is added.  The score dict then holds 'crf' and 'crf_joint': True."""
     from util import object_merge, png_layout
     _check_png_huffman('test_objects', png_huffman)
     _check_batching('test_objects', group, forward_batch)
     _check_ensemble('test_objects', ensemble)
     _check_crf('test_objects', crf)
+    if not isinstance(crf_joint, bool):
+        raise ValueError('test_objects: crf_joint must be a bool, got {!r}'.format(crf_joint))
+    if crf_joint and crf is None:
+        raise ValueError('test_objects: crf_joint is the joint form of the CRF: it needs crf (a CrfOptions)')
     nets = [p.network for p in net_providers]
     n_obj = len(nets)
     if not 1 <= n_obj <= object_merge.MAX_OBJECTS:
@@ -862,7 +882,7 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
             views = None if ensemble is None else _ensemble_inputs(inputs, ensemble)  # made once, shared among the nets
             # every net forwards the same uploaded batch
             logits = [_ensemble_logits(net, inputs, forward_batch, ensemble, views) for net in nets]
-            if crf is not None:
+            if crf is not None and not crf_joint:
                 logits = [_crf_logits(inputs, x, crf) for x in logits]
             h, w = int(logits[0].shape[2]), int(logits[0].shape[3])
             first, gt, paths = frames.add(minibatches, h, w, annotations, ids=True)
@@ -873,7 +893,7 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
                 device = logits[0].device
                 if palette_host is not None and palette_dev is None:
                     palette_dev = torch.from_numpy(palette_host).to(device)
-                labels = ops.merge_objects(logits)
+                labels = _crf_joint_labels(inputs, logits, crf) if crf_joint else ops.merge_objects(logits)
                 if annotations is not None:
                     ops.jf_counts_labels(labels, torch.from_numpy(gt).to(device), n_obj, radius,
                                          out=counts.rows(first, n, device))
@@ -884,7 +904,8 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
                     files.retire(pending)  # the previous group's files, while the device works on this group
                 pending = sent
             else:
-                labels = object_merge.merge_labels([x[:, 0].numpy() for x in logits])
+                labels = _crf_joint_labels(inputs, logits, crf) if crf_joint else \
+                    object_merge.merge_labels([x[:, 0].numpy() for x in logits])
                 blobs = []
                 for index in range(n):
                     if annotations is not None:
@@ -910,6 +931,8 @@ def test_objects(net_providers, data_loader, save_dir: Path, annotations: Option
         score['ensemble'] = ensemble.as_dict()
     if crf is not None:
         score['crf'] = crf.as_dict()
+    if crf_joint:
+        score['crf_joint'] = True
     last_score.clear()
     last_score.update(score)
     return score

@@ -821,6 +821,27 @@ int fosvos_crf_refine(const float *image, const float *logits, const double *tab
                       int radius, double weight_appearance, double weight_smooth, double clip, const float mean[3], float *out,
                       void *workspace, size_t workspace_bytes, int device, void *stream);
 
+/* A joint CRF over the objects of a frame (opt-in; csrc/crf.hip): ONE mean-field CRF over the labels 0..K (0 = background) in
+ * the place of K fosvos_crf_refine calls and fosvos_merge_objects.  util/label_crf.py states the arithmetic in numpy; labels
+ * and scores are compared with it bit for bit, under the rules of fosvos_crf_refine.  `tables` is the device copy of the fp64
+ * vector label_crf.tables made, [RGB 256 | A (2 radius + 1)^2 | B (2 radius + 1)^2 | E 2049]; every index into it is clamped.
+ *
+ * fosvos_crf_labels: image fp32 [N,3,H,W] as for fosvos_crf_refine; logits[k] fp32 [N,1,H,W] of net k (`logits` as for
+ *   fosvos_merge_objects: a host array of K device pointers that travel by value, 1 <= K <= FOSVOS_MAX_OBJECTS) -> labels uint8
+ *   [N,H,W] and, where `scores` is not NULL, scores fp32 [N,K+1,H,W] = float32(z^T).  U_0 = 0, U_k the logit of net k - 1
+ *   clipped to [-clip, clip] (a NaN is -clip); the beliefs of a pixel are a soft-max of its z, piecewise linear on E;
+ *   z^t_l = (U_l + weight_appearance ma_l) + weight_smooth ms_l.  The label: the largest z^T, an object before the background
+ *   and the lowest object among equal ones (the rule of fosvos_merge_objects).  Ranges, codes and alignments as for
+ *   fosvos_crf_refine (the scores 4-byte aligned); K outside its range is FOSVOS_E_ARG.  workspace:
+ *   fosvos_crf_labels_workspace_bytes = 16 (K + 1) N H W (two sets of K + 1 fp64 maps [N,K+1,H,W], z^t by turns); every byte
+ *   of it that is read was written by the call.  `iterations` launches of one kernel, 16 x 64 tiles with a halo of `radius`;
+ *   a workgroup walks the labels in chunks of four (71.5 KB of LDS) and computes a neighbour's appearance weight once per
+ *   chunk; the last launch writes the labels and the scores.  No workgroup waits for another, no atomics, no synchronisation. */
+size_t fosvos_crf_labels_workspace_bytes(int N, int K, int H, int W);
+int fosvos_crf_labels(const float *image, const float *const *logits, int K, const double *tables, int N, int H, int W,
+                      int iterations, int radius, double weight_appearance, double weight_smooth, double clip, const float mean[3],
+                      uint8_t *labels, float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
+
 /* Measuring how the picture moved between two frames and moving a mask along with it (opt-in; csrc/motion.hip): full-search
  * block matching on the frames' luma and a per-block warp, all in integers.  util/block_motion.py states the arithmetic in
  * numpy; every output is compared with it bit for bit.  Each entry is ONE launch on `stream`; no workspace, no atomics, no
